@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
 """bench.py -- BASELINE.json's metric: tokens/s of single-stream greedy decode of an RWKV-4 uint8
-model on MI355X, with the achieved fraction of the HBM-read roofline of the dominant kernel and
-the CPU restatement timed beside it.
+model on MI355X; with --full also the achieved fraction of the HBM-read roofline of the dominant
+kernel, the other legs and gates, and the CPU restatement timed beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 7B] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--model 7B] [--dump-outputs DIR]
+    python bench.py --full [--no-cpu-baseline] ...
 
 A "step" is one pass of the hot path: one token through embed+ln0, L x {time-mix, channel-mix},
 ln_out + head, and the device-side greedy pick that feeds the next step (storygen's loop with
@@ -78,6 +79,12 @@ def main():
     ap.add_argument("--config2-steps", type=int, default=256, help="greedy steps of the 1B5 leg (BASELINE config 2) reported beside the 7B headline; 0 = skip")
     ap.add_argument("--parallel", choices=["pipeline", "replicas"], default=os.environ.get("RWKV_BENCH_PARALLEL", "pipeline"),
                     help="N > 1: layer pipeline over RCCL send/recv with N streams in flight (default), or N independent replicas")
+    ap.add_argument("--full", action="store_true", help="also run every leg beside the headline: per-kernel timing and roofline, drop-in "
+                    "and sampled decode, prefill and batched decode, the 1B5 configuration, the reference-kernel gates and the CPU baseline. "
+                    "Without it a single-model run only sets up, warms up, times --steps steps and prints the line (the N > 1 pipeline line "
+                    "is the same either way)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the timed path computed as DIR/<name>.npy: "
+                    "the ids picked in the timed steps, the logits of the last step, and the state it left")
     args = ap.parse_args()
     if args.model is None:
         args.model = "14B" if args.gpus > 1 and args.parallel == "pipeline" else "7B"
@@ -154,6 +161,43 @@ def main():
         dt = float(tmax.item())
     tok_s = args.steps * world / dt
     B_tok = m.bytes_per_token()
+    if args.dump_outputs and rank == 0:
+        m.pull_state(1)
+        outs = dict(tokens=ids.astype(np.float64), logits=m.logits(1).astype(np.float32))
+        for name, a in zip(("xy", "aa", "bb", "pp", "dd"), m.state.arrays()):
+            outs["state_" + name] = a[: L * D].reshape(L, D).copy()
+        dump_outputs(args.dump_outputs, outs)
+
+    line = dict(
+        metric="tokens/sec single-stream RWKV-4 uint8 greedy decode",
+        value=round(tok_s, 2), unit="tokens/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
+        ms_per_step=round(1e3 * dt / args.steps, 5), higher_is_better=True, scaling="weak",
+        vs_baseline=None, dtype="u8 weights x 23-bit fixed-point activations, exact 32-bit integer accumulate (tile form: v_mfma_i32_16x16x64_i8 on signed limbs; row form: v_dot4_u32_u8 on the VALU); f32/f64 epilogues, f64 state", data="synthetic",
+        config=dict(workload=f"RWKV-4-Raven-{args.model} uint8 single-stream greedy decode "
+                             f"(L={L}, D={D}, V={mf.VOCAB}), 32-token prompt then {args.steps}-token continuation, "
+                             "device-resident state",
+                    parallelism=("1 GPU" if world == 1 else f"{world} independent replicas, one stream per GPU (replicas only)"),
+                    launches_per_token=4 * L + 3, bytes_per_token=B_tok),
+        end_to_end=dict(achieved_GBps=round(B_tok * tok_s / world / 1e9, 1),
+                        frac_of_8TBps=round(B_tok * tok_s / world / 1e9 / HBM_PEAK_GBPS, 4)),
+        load_s=round(load_s, 2),
+        hbm_resident_bytes=dict(total=m.resident_bytes(), weight_bytes_one_copy=13 * L * D * D + mf.VOCAB * D,
+                                note="device bytes of this context: weights + row-sum tables + embedding + state + scratch.  The matrices of a decode "
+                                     "kernel class are resident in the ONE layout its kernel streams: the tile image (csrc/tile.hip.h) for the classes in "
+                                     "decode_form.tile, the row form for the others, the head in row form.  The chunk path (max_ctx > 1) multiplies with the "
+                                     "16-row tile image of every matrix: the same image at 4096 channels, a second copy elsewhere (DESIGN.md 3)"),
+        decode_form=(lambda f: dict(mask=f, tile=[n for b, n in enumerate(("att_kvr_wkv", "att_out", "ffn_rk", "ffn_v")) if f >> b & 1],
+                                    row=[n for b, n in enumerate(("att_kvr_wkv", "att_out", "ffn_rk", "ffn_v")) if not f >> b & 1] + ["head"]))(m.decode_form()),
+    )
+    if not args.full:
+        # the headline only: every other leg, gate and per-kernel figure is --full's
+        m.close()
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- drop-in mode: host-authoritative state, uploaded/downloaded every token (rwkv.h:353,372) ----
     drop_in = None
@@ -207,31 +251,9 @@ def main():
                    GBps=round(per_launch[k]["gbps"], 1), frac_of_8TBps=round(per_launch[k]["gbps"] / HBM_PEAK_GBPS, 4),
                    launches_per_token=per_launch[k]["launches_per_token"]) for k in absorbs if k in per_launch]
 
-    line = dict(
-        metric="tokens/sec single-stream RWKV-4 uint8 greedy decode",
-        value=round(tok_s, 2), unit="tokens/s", n_gpus=world, steps=args.steps, warmup=args.warmup,
-        ms_per_step=round(1e3 * dt / args.steps, 5), higher_is_better=True, scaling="weak",
-        vs_baseline=None, dtype="u8 weights x 23-bit fixed-point activations, exact 32-bit integer accumulate (tile form: v_mfma_i32_16x16x64_i8 on signed limbs; row form: v_dot4_u32_u8 on the VALU); f32/f64 epilogues, f64 state", data="synthetic",
-        config=dict(workload=f"RWKV-4-Raven-{args.model} uint8 single-stream greedy decode "
-                             f"(L={L}, D={D}, V={mf.VOCAB}), 32-token prompt then {args.steps}-token continuation, "
-                             "device-resident state",
-                    parallelism=("1 GPU" if world == 1 else f"{world} independent replicas, one stream per GPU (replicas only)"),
-                    launches_per_token=4 * L + 3, bytes_per_token=B_tok),
-        roofline=roof,
-        mm8_one_shapes=shapes,
-        end_to_end=dict(achieved_GBps=round(B_tok * tok_s / world / 1e9, 1),
-                        frac_of_8TBps=round(B_tok * tok_s / world / 1e9 / HBM_PEAK_GBPS, 4)),
-        kernels={k: dict(us=round(v["us"], 3), GBps=round(v["gbps"], 1), us_event_pair=round(v["us_event_pair"], 3))
-                 for k, v in per_launch.items()},
-        load_s=round(load_s, 2),
-        hbm_resident_bytes=dict(total=m.resident_bytes(), weight_bytes_one_copy=13 * L * D * D + mf.VOCAB * D,
-                                note="device bytes of this context: weights + row-sum tables + embedding + state + scratch.  The matrices of a decode "
-                                     "kernel class are resident in the ONE layout its kernel streams: the tile image (csrc/tile.hip.h) for the classes in "
-                                     "decode_form.tile, the row form for the others, the head in row form.  The chunk path (max_ctx > 1) multiplies with the "
-                                     "16-row tile image of every matrix: the same image at 4096 channels, a second copy elsewhere (DESIGN.md 3)"),
-        decode_form=(lambda f: dict(mask=f, tile=[n for b, n in enumerate(("att_kvr_wkv", "att_out", "ffn_rk", "ffn_v")) if f >> b & 1],
-                                    row=[n for b, n in enumerate(("att_kvr_wkv", "att_out", "ffn_rk", "ffn_v")) if not f >> b & 1] + ["head"]))(m.decode_form()),
-    )
+    line.update(roofline=roof, mm8_one_shapes=shapes,
+                kernels={k: dict(us=round(v["us"], 3), GBps=round(v["gbps"], 1), us_event_pair=round(v["us_event_pair"], 3))
+                         for k, v in per_launch.items()})
 
     if drop_in is not None:
         line["drop_in_mode"] = drop_in
@@ -351,6 +373,21 @@ def main():
         # the line above is on record; a number whose parity gate tripped must not pass for a result
         print("[bench] PARITY GATE FAILED: " + "; ".join(bad), file=sys.stderr, flush=True)
         raise SystemExit(4)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy (float32 / float64), at most DUMP_LIMIT_BYTES in all"""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def parity_failures(node, path=""):
@@ -541,6 +578,8 @@ def bench_pipeline(args, dist, rank, local_rank, world, L, D, dev):
     if args.warmup > 0:
         run(max(1, args.warmup // world))
     dt = timed(args.steps)
+    if args.dump_outputs and lastr:     # row k: the logits of stream k's last step (the last stage holds the head)
+        dump_outputs(args.dump_outputs, dict(logits=stage.m.logits(world).reshape(world, mf.VOCAB).astype(np.float32)))
     one_steps = max(4, min(args.steps, int(os.environ.get("RWKV_BENCH_ONE_STREAM_STEPS", "128"))))
     run(2, 1)
     dt1 = timed(one_steps, 1)

@@ -3,7 +3,7 @@
 SAME device-resident synthetic tensors, the engine teacher-forced with the reference's greedy ids, and compare the
 logits of every step with BASELINE.json's tolerance (parity.py) plus the greedy id of every step.
 
-Used by bench.py (7B, 1024 steps: `ref_kernel_baseline` + `parity_vs_reference_kernel`; the chunk, long-prompt and 96-stream
+Used by bench.py --full (7B, 1024 steps: `ref_kernel_baseline` + `parity_vs_reference_kernel`; the chunk, long-prompt and 96-stream
 gates beside the legs that time those paths) and by tests/test_ref_parity_gpu.py (1B5, 7B and 14B at full depth).  Nothing here reads /root/reference at run time."""
 import time
 

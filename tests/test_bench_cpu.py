@@ -111,3 +111,16 @@ def test_the_multi_gpu_line_is_assembled_from_per_rank_results(world):
                                 layer_ranges=ranges, transport="x", hop=None, parity=None, cpu=None, prefill=None, native_note="rank 1: boom", tinfo=[], resident=[1] * world, per_launch=none)
     assert line2["roofline"]["traffic"] is None and line2["transport_fallback"] == "rank 1: boom" and json.dumps(line2)
     assert bench.parity_failures(back) == []
+
+
+def test_dumped_outputs_are_float_npy_files_within_the_limit(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 / float64 only, at most 64 MiB in all"""
+    import numpy as np
+    outs = dict(tokens=np.arange(5, dtype=np.float64), logits=np.linspace(-1, 1, 7, dtype=np.float32))
+    bench.dump_outputs(str(tmp_path / "d"), outs)
+    for name, a in outs.items():
+        got = np.load(tmp_path / "d" / f"{name}.npy")
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), dict(x=np.zeros((64 << 20) // 8 + 1)))
+    assert not (tmp_path / "big").exists()

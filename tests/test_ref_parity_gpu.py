@@ -67,8 +67,8 @@ def test_reference_gpt_chunk(built, oracle, ref, tmp_path):
 def test_full_depth_gate_vs_reference_kernel(built, ref, name, steps):
     """BASELINE configs 2, 3 and 4 at FULL depth (1B5: L=24, D=2048; 7B: L=32, D=4096; 14B: L=40, D=5120): the engine,
     teacher-forced with the reference kernel's greedy ids on the same device-resident tensors, matches its logits within 1e-3 and
-    its greedy id at every step (the 1024-step instance of the 7B gate runs inside bench.py: parity_vs_reference_kernel, and
-    bench.py exits non-zero when it trips)."""
+    its greedy id at every step (the 1024-step instance of the 7B gate runs inside bench.py --full: parity_vs_reference_kernel,
+    and bench.py --full exits non-zero when it trips)."""
     import torch
     from rwkv_cpp_accelerated_amd import engine
     import refgate
@@ -89,7 +89,7 @@ def test_full_depth_gate_vs_reference_kernel(built, ref, name, steps):
 
 @pytest.mark.parametrize("name,T", [("14B", 32), ("7B", 32), ("1B5", 32)])
 def test_chunk_path_full_depth_vs_reference_kernel(built, ref, name, T):
-    """BASELINE config 5 (7B, T = 32) and its shape at 14B / 1B5, FULL depth (also inside bench.py: prefill.parity_vs_reference_kernel):
+    """BASELINE config 5 (7B, T = 32) and its shape at 14B / 1B5, FULL depth (also inside bench.py --full: prefill.parity_vs_reference_kernel):
     a T-token prompt as ONE GPT-mode call of the reference's own kernel (rwkv.h:339-376; in-kernel token loops rwkv.cu:227,279)
     against the engine's chunk path -- all T logits rows, the five state arrays, 8 greedy decode steps from that state -- and two
     T-slot PARRALEL steps (rwkv.cu:236-240), all rows, all slots of the state."""

@@ -1,4 +1,4 @@
-"""stdin: bench.py output; prints tok/s, per-kernel launch durations and the roofline fraction of the JSON line (A/B sweeps)"""
+"""stdin: `bench.py --full` output; prints tok/s, per-kernel launch durations and the roofline fraction of the JSON line (A/B sweeps)"""
 import json
 import sys
 

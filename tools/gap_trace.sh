@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 R=$PWD; O=${1:-$R/gpurun_out/r06y}; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/gapkt
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/gapkt -- python $R/bench.py --steps 64 --warmup 8 --no-cpu-baseline --ref-steps 0 --prefill-chunks 0 --config2-steps 0 --profile-reps 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $O/gapkt -- python $R/bench.py --full --steps 64 --warmup 8 --no-cpu-baseline --ref-steps 0 --prefill-chunks 0 --config2-steps 0 --profile-reps 0 > /dev/null 2>&1
 cd $R
 python - "$O" <<'PY'
 import csv, glob, sys, collections

@@ -9,7 +9,7 @@ export PYTHONUNBUFFERED=1
 if [ -z "$SKIP_TESTS" ]; then
   timeout 2400 python -m pytest tests -m gpu -q --timeout 900 -rs -rf 2>&1 | grep -v "^loading\|^n_layers\|^n_embed\|amdgpu.ids\|socket.cpp\|^RCCL version\|^HIP version\|^ROCm version\|^Hostname\|^Librccl\|pipeline transport up" | tail -80 > $O/pytest_gpu.log; tail -12 $O/pytest_gpu.log
 fi
-timeout 900 python bench.py 2>$O/bench7b_full.err | tail -1 > $O/bench7b_full.json; cut -c1-300 $O/bench7b_full.json
+timeout 900 python bench.py --full 2>$O/bench7b_full.err | tail -1 > $O/bench7b_full.json; cut -c1-300 $O/bench7b_full.json
 # the N > 1 line as the driver will run it, dry on the one GPU: 2 ranks, torch.distributed over gloo; (a) the engine's NATIVE schedule over the
 # shared-memory RCCL stand-in (tests/fake_rccl.cpp), 14B by default; (b) the Python schedule over torch P2P ops
 RWKV_BENCH_BACKEND=gloo RWKV_BENCH_ONE_DEVICE=1 RWKV_RCCL_LIB=$R/tests/_build/libfake_rccl.so timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 64 --warmup 8 --prefill-chunks 2 2>$O/bench_n2_dryrun_native.err | grep '^{"metric"' | tail -1 > $O/bench_n2_dryrun_native.json; echo "native dry run: exit $? $(wc -c < $O/bench_n2_dryrun_native.json) bytes"
@@ -20,7 +20,7 @@ import json, subprocess, sys, os
 O = sys.argv[1]
 out = {}
 for m in ("169M", "1B5", "3B", "14B"):
-    r = subprocess.run([sys.executable, "bench.py", "--model", m, "--steps", "256", "--warmup", "16", "--no-cpu-baseline", "--ref-steps", "0", "--config2-steps", "0"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--model", m, "--steps", "256", "--warmup", "16", "--no-cpu-baseline", "--ref-steps", "0", "--config2-steps", "0"], capture_output=True, text=True, timeout=600)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
         out[m] = dict(tokens_per_s=d["value"], ms_per_step=d["ms_per_step"], end_to_end=d["end_to_end"], kernels=d["kernels"], roofline=d["roofline"], prefill=d.get("prefill"))
@@ -31,8 +31,8 @@ json.dump(out, open(os.path.join(O, "bench_sizes.json"), "w"), indent=1)
 PY
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/kt $O/pmc
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --steps 128 --warmup 8 --no-cpu-baseline --ref-steps 0 --prefill-chunks 0 --config2-steps 0 2>/dev/null | tail -1 > $O/bench7b_under_rocprof.json
-timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc -- python $R/bench.py --steps 8 --warmup 2 --no-cpu-baseline --ref-steps 0 --profile-reps 4 --prefill-chunks 0 --config2-steps 0 > /dev/null 2>&1
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python $R/bench.py --full --steps 128 --warmup 8 --no-cpu-baseline --ref-steps 0 --prefill-chunks 0 --config2-steps 0 2>/dev/null | tail -1 > $O/bench7b_under_rocprof.json
+timeout 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc -- python $R/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --ref-steps 0 --profile-reps 4 --prefill-chunks 0 --config2-steps 0 > /dev/null 2>&1
 cd $R
 python - "$O" <<'PY'
 import csv, glob, json, sys, collections, shutil, os

@@ -17,7 +17,7 @@ echo "model,pass,counters,status" > $O/decode_pmc_passes.csv
 one_pass() {   # model, pass name, counters...
   local M=$1 P=$2; shift 2
   rm -rf $O/pmcd
-  timeout 420 rocprofv3 --pmc "$@" --output-format csv -d $O/pmcd -- python $R/bench.py --model $M --steps 8 --warmup 2 --no-cpu-baseline --ref-steps 0 --profile-reps 4 --prefill-chunks 0 --config2-steps 0 > $O/pmcd.log 2>&1
+  timeout 420 rocprofv3 --pmc "$@" --output-format csv -d $O/pmcd -- python $R/bench.py --full --model $M --steps 8 --warmup 2 --no-cpu-baseline --ref-steps 0 --profile-reps 4 --prefill-chunks 0 --config2-steps 0 > $O/pmcd.log 2>&1
   local n=$(find $O/pmcd -name '*counter_collection.csv' 2>/dev/null | wc -l)
   if [ "$n" -gt 0 ]; then
     python - "$O" "$M" "$P" <<'PY'
