@@ -213,10 +213,10 @@ void *rwkv_stream(rwkv_ctx *ctx);
  * max_ctx > 1 on a whole-model context, the SECOND resident copy of the matrices in the MFMA B-operand image of the chunk
  * path (+7.2 GB at 7B, +13.9 GB at 14B). */
 uint64_t rwkv_resident_bytes(const rwkv_ctx *ctx);
-/* Which of the four per-layer decode kernel classes of a loaded context stream the tile image (csrc/tile.hip.h):
- * bit 0 K/V/R + WKV, bit 1 att_out, bit 2 ffn k/r, bit 3 ffn_v; a clear bit = that class streams its matrices in row form.  A
- * class's matrices are resident in the one layout its kernel streams (15 at 4096 channels on 256 CUs, 4 at 5120, 0 otherwise;
- * RWKV_TILE=<mask> before the load overrides).  -1 without a loaded model. */
+/* The decode form of a loaded context: which of the four per-layer decode kernel classes stream the tile image (csrc/tile.hip.h,
+ * DESIGN.md 4.7), bit 0 K/V/R + WKV, bit 1 att_out, bit 2 ffn k/r, bit 3 ffn_v; a clear bit = that class runs the register row
+ * form (csrc/kernels.hip.h).  A class's matrices are resident in the one layout its kernel streams (on 256 CUs: 15 at 4096 and
+ * 5120 channels, 13 at 2048, 0 otherwise; RWKV_TILE=<mask> before the load overrides).  -1 without a loaded model. */
 int rwkv_decode_form(const rwkv_ctx *ctx);
 /* Algorithmic HBM bytes of one token (13*L*D^2 + V*D uint8 weight bytes
  * + 168*L*D + 40*D bytes of vectors/state). */

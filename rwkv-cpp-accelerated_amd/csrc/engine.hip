@@ -151,12 +151,6 @@ struct Pipe {
     std::string info;            // one JSON object describing this rank's end of the transport (rwkv_pipe_info)
 };
 
-// decode kernels that stream through the LDS ring: -1 = by model width (measured on MI355X, profiles/r02/ring_sweep.txt,
-// profiles/r04/early_take_ab.txt): rows of 3-5 KiB gain 2-5 % with k_att, k_ffn_rk and k_ffnv on the ring; <= 2 KiB rows lose
-#ifndef RWKV_RING
-#define RWKV_RING -1
-#endif
-
 // per-chunk scratch of the chunk path (one set per pipeline stage that may be in flight)
 struct SeqScratch {
     double *state = nullptr;            // [D] LayerNorm output of the chunk's last token
@@ -182,7 +176,6 @@ struct rwkv_ctx {
     int tile = -1;           // decode kernel classes that run in TILE form (tile.hip.h; bit 0 k_att, 1 k_attout, 2 k_ffn_rk, 3 k_ffnv; env RWKV_TILE; -1 = auto: 15 at
                              // D = 4096 and 5120 on 256 CUs, 13 at D = 2048, else 0).  15: the context holds ONLY the tile image of the per-layer
                              // matrices; a partial mask keeps both layouts (tuning)
-    int ring = RWKV_RING;    // decode kernels that stream their weights through the LDS ring (bit 0 k_att, 1 k_attout, 2 k_ffn_rk, 3 k_ffnv, 4 k_head; env RWKV_RING)
 
     // weights (device)
     float *embed = nullptr;
@@ -216,7 +209,7 @@ struct rwkv_ctx {
     unsigned *ts_key = nullptr;
     unsigned gen_cap = 0;
     hipGraphExec_t g_fwd = nullptr, g_greedy = nullptr;
-    // device error word: a mapped pinned word that a kernel raises when one of its bounded waits gave up (LDS ring hand-offs);
+    // device error word: a mapped pinned word that a kernel raises when one of its bounded waits gave up (tile-form LDS hand-offs);
     // checked after every stream synchronisation (device_check)
     unsigned *herr = nullptr, *d_herr = nullptr;
     unsigned long long *tl = nullptr;   // phase-timeline buffer (debug), [grid][NW][8]
@@ -230,7 +223,7 @@ struct rwkv_ctx {
     uint64_t sq_n = 0;                            // chunks enqueued so far
     // captured passes of the chunk path (GPT mode): one hipGraph per (layer range, residual buffer, rows, logits row of the last part);
     // a pass is 11 launches per layer -- 2.9 k launches and events for a 512-token 7B prompt, 3.5 us of host time each
-    // (RWKV_SEQ_GRAPH=0: direct launches)
+    // (RWKV_GRAPH bit 1 clear: direct launches)
     struct SeqGraphKey { uint64_t la, lb, row0; int buf, n; bool operator<(const SeqGraphKey &o) const { return std::tie(la, lb, row0, buf, n) < std::tie(o.la, o.lb, o.row0, o.buf, o.n); } };
     std::map<SeqGraphKey, hipGraphExec_t> sq_graphs;
     bool seq_graph = true;
@@ -288,17 +281,7 @@ size_t smem_attout(int S) { return RED_BYTES + (size_t)S * 3072; }
 size_t smem_frk(int S) { return RED_BYTES + 2 * (size_t)S * 3072; }
 size_t smem_fv(int S) { return RED_BYTES + 4 * (size_t)S * 3072; }
 size_t smem_head(int S) { return RED_BYTES + (size_t)S * 3072 + NW * 8; }
-// ring kernels: units of one row (S KiB) behind the staged vectors, as many as fit the CU's 160 KiB (a group of R rows takes R
-// consecutive units, wrapping: every group size shares the same ring)
-constexpr size_t LDS_BYTES = 160 * 1024;
-int ring_slots(size_t fixed, int, int S)
-{
-    return (int)((LDS_BYTES - fixed - sizeof(GldsCtl)) / ((size_t)S * 1024));
-}
-size_t smem_ring(size_t fixed, int R, int S) { return fixed + sizeof(GldsCtl) + (size_t)ring_slots(fixed, R, S) * S * 1024; }
-// k_att / k_ffn_rk / k_ffnv in ring form: [scratch][nv staged vectors][control block][ring]
-int ring_units(int nv, int S) { return (int)((LDS_BYTES - RED_BYTES - sizeof(GldsCtl) - (size_t)nv * S * 3072) / ((size_t)S * 1024)); }
-size_t smem_ring3(int nv, int S) { return RED_BYTES + (size_t)nv * S * 3072 + sizeof(GldsCtl) + (size_t)ring_units(nv, S) * S * 1024; }
+constexpr size_t LDS_BYTES = 160 * 1024;     // LDS of one CU
 
 // tile-form decode kernels (tile.hip.h; classes 1 att, 2 att_out, 3 ffn_rk, 4 ffn_v): ring of S KiB units behind each kernel's fixed LDS.
 // Which widths have a tile form: those whose channels split into whole TH-row tiles per workgroup on this grid --
@@ -455,7 +438,7 @@ struct ArgMaker {
     {
         HeadArgs ha;
         ha.x = c->x; ha.st = site_static(2, 0); ha.dy = site_dyn(2, grid); ha.w = c->w_head; ha.rs = c->rs_head; ha.logits = c->logits;
-        ha.blk_val = c->blk_val; ha.blk_idx = c->blk_idx; ha.ctl = c->ctl; ha.D = D; ha.ns = 0; ha.herr = c->d_herr;
+        ha.blk_val = c->blk_val; ha.blk_idx = c->blk_idx; ha.ctl = c->ctl; ha.D = D;
         return ha;
     }
 };
@@ -481,10 +464,6 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                           (k_att_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
                           (k_att_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
-        else if (c->ring & 1) {
-            aa.ns = ring_units(3, S);
-            DISPATCH_S(S, k_att<S_, 1, 1><<<dim3(grid), dim3(NT), smem_ring3(3, S), c->stream>>>(aa));
-        }
         else DISPATCH_S(S, k_att<S_, nb_att(S_)><<<dim3(grid), dim3(NT), smem_att(S), c->stream>>>(aa));
     } break;
     case 2: {
@@ -498,7 +477,6 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                           (k_attout_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
                           (k_attout_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
-        else if (c->ring & 2) { ao.ns = ring_slots(smem_attout(S), ATTOUT_R, S); DISPATCH_S(S, k_attout<S_, ATTOUT_R, 1, 1><<<dim3(grid), dim3(NT), smem_ring(smem_attout(S), ATTOUT_R, S), c->stream>>>(ao)); }
         else DISPATCH_S(S, k_attout<S_, ATTOUT_R, nb_attout(S_)><<<dim3(grid), dim3(NT), smem_attout(S), c->stream>>>(ao));
     } break;
     case 3: {
@@ -512,15 +490,10 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                           (k_ffn_rk_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
                           (k_ffn_rk_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
-        else if (c->ring & 4) {
-            fa.ns = ring_units(2, S);
-            DISPATCH_S(S, k_ffn_rk<S_, 1, 1><<<dim3(grid), dim3(NT), smem_ring3(2, S), c->stream>>>(fa));
-        }
         else DISPATCH_S(S, k_ffn_rk<S_, nb_frk(S_)><<<dim3(grid), dim3(NT), smem_frk(S), c->stream>>>(fa));
     } break;
     case 4: {
         FfnVArgs fv = mk.fv(l);
-        fv.ns = ring_units(4, S);
         if (tile_ok(c, 4)) {
             FfnVTArgs ta;
             ta.a = fv; ta.a.ns = tile_units(c, 4);
@@ -536,32 +509,29 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                               (k_ffnv_t<2, 4, 32, 4, 2, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
         else if (mk.fv_next_att(l)) {
-            if (c->ring & 8) DISPATCH_S(S, k_ffnv<S_, 3, 1, 1><<<dim3(grid), dim3(NT), smem_ring3(4, S), c->stream>>>(fv))
-            else DISPATCH_S(S, k_ffnv<S_, 3, nb_fv(S_)><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
+            DISPATCH_S(S, k_ffnv<S_, 3, nb_fv(S_)><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
         } else {
-            if (c->ring & 8) DISPATCH_S(S, k_ffnv<S_, 1, 1, 1><<<dim3(grid), dim3(NT), smem_ring3(4, S), c->stream>>>(fv))
-            else DISPATCH_S(S, k_ffnv<S_, 1, nb_fv(S_)><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
+            DISPATCH_S(S, k_ffnv<S_, 1, nb_fv(S_)><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
         }
     } break;
     case 5: {
         HeadArgs ha = mk.head();
-        if (c->ring & 16) { ha.ns = ring_slots(smem_head(S), RWKV_HEAD_RR, S); DISPATCH_S(S, k_head<S_, 1, 1><<<dim3(grid), dim3(NT), smem_ring(smem_head(S), RWKV_HEAD_RR, S), c->stream>>>(ha)); }
-        else DISPATCH_S(S, k_head<S_, nb_head(S_)><<<dim3(grid), dim3(NT), smem_head(S), c->stream>>>(ha));
+        DISPATCH_S(S, k_head<S_, nb_head(S_)><<<dim3(grid), dim3(NT), smem_head(S), c->stream>>>(ha));
     } break;
     default:
         k_argmax_finish<<<dim3(1), dim3(64), 0, c->stream>>>(c->blk_val, c->blk_idx, grid, c->ctl, c->gen, c->gen_cap);
     }
 }
 
-// after a synchronisation: did a bounded wait inside a kernel give up?  (a ring hand-off that never arrived: the GPU is shared
-// or preempted, or a workgroup died.)  The token's results are not to be trusted: fail loudly instead of returning them.
+// after a synchronisation: did a bounded wait inside a kernel give up?  (a tile-form LDS hand-off that never arrived: the GPU is
+// shared or preempted, or a workgroup died.)  The token's results are not to be trusted: fail loudly instead of returning them.
 int device_check(rwkv_ctx *c)
 {
     if (!c->herr || *c->herr == 0u) return 0;
     const unsigned code = *c->herr;
     *c->herr = 0u;
-    return fail(RWKV_E_DEVICE, "a device-side wait gave up (code %u: LDS ring hand-off timed out; is the GPU shared or preempted?) -- "
-                               "the results of this call are invalid; RWKV_RING=0 selects the register kernels", code);
+    return fail(RWKV_E_DEVICE, "a device-side wait gave up (code %u: an LDS hand-off timed out; is the GPU shared or preempted?) -- "
+                               "the results of this call are invalid; RWKV_TILE=0 selects kernels without bounded waits", code);
 }
 
 // enqueue the kernels of one token on the context's stream.  ev: optional array of
@@ -662,12 +632,6 @@ int set_smem_limits(rwkv_ctx *c)
     DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 3, nb_fv(S_)>, smem_fv(S))); if (rc) return rc;
     DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 1, nb_fv(S_)>, smem_fv(S))); if (rc) return rc;
     DISPATCH_S(S, rc = allow_smem(k_head<S_, nb_head(S_)>, smem_head(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_att<S_, 1, 1>, smem_ring3(3, S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_attout<S_, ATTOUT_R, 1, 1>, smem_ring(smem_attout(S), ATTOUT_R, S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffn_rk<S_, 1, 1>, smem_ring3(2, S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 3, 1, 1>, smem_ring3(4, S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 1, 1, 1>, smem_ring3(4, S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_head<S_, 1, 1>, smem_ring(smem_head(S), RWKV_HEAD_RR, S))); if (rc) return rc;
     if (c->tile_th) {
 #define TILE_ALLOW(K16, K45, K42, CLS)                                                                   \
         do {                                                                                             \
@@ -697,7 +661,6 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
         return fail(RWKV_E_ARG, "RWKV_GRID=%d is too small for n_embed=%llu (need >= %llu workgroups)", c->grid, (unsigned long long)D, (unsigned long long)((D + 511) / 512));
     HIPCHK(hipSetDevice(c->device));
     c->L = L; c->D = D; c->maxT = max_ctx; c->S = (int)((D + 1023) / 1024);
-    if (c->ring < 0) c->ring = c->S >= 3 ? 13 : 0;      // (5 KiB rows: k_ffnv joined the ring in round 4, with the early take: 21.4 -> 20.8 us, profiles/r04/early_take_ab.txt)
     if (c->l1 == UINT64_MAX) c->l1 = L;
     if (c->l0 >= c->l1 || c->l1 > L) return fail(RWKV_E_ARG, "layer range [%llu, %llu) does not fit a %llu-layer model", (unsigned long long)c->l0, (unsigned long long)c->l1, (unsigned long long)L);
     const uint64_t l0 = c->l0, l1 = c->l1, nl = l1 - l0;
@@ -1307,6 +1270,23 @@ int run_token(rwkv_ctx *c, bool with_argmax)
     return enqueue_token(c, with_argmax, nullptr);
 }
 
+// environment variables earlier versions read: setting one now changes nothing, so say so (replacement: nullptr = none)
+const struct { const char *name, *instead; } RETIRED_ENV[] = {
+    {"RWKV_RING", "RWKV_TILE (the LDS-ring form of the row-form decode kernels is gone)"},
+    {"RWKV_NO_GRAPH", "RWKV_GRAPH=0"},
+    {"RWKV_SEQ_GRAPH", "RWKV_GRAPH bit 1"},
+    {"RWKV_SEQ_SPLIT", "RWKV_SEQ_STAGES (RWKV_SEQ_SPLIT=0 is RWKV_SEQ_STAGES=1)"},
+    {"RWKV_PIPE_LOG", nullptr},
+    {"RWKV_SEQ_PIPE", nullptr},
+    {"RWKV_SEQ_SMALL", nullptr},
+};
+void warn_retired_env()
+{
+    for (const auto &r : RETIRED_ENV)
+        if (getenv(r.name))
+            fprintf(stderr, "[rwkv_mi355x] %s is retired and ignored%s%s\n", r.name, r.instead ? "; use " : "", r.instead ? r.instead : "");
+}
+
 } // namespace
 
 extern "C" {
@@ -1328,7 +1308,7 @@ int rwkv_create(rwkv_ctx **out, int device)
     c->grid = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     const char *g = getenv("RWKV_GRID");
     if (g && atoi(g) > 0) c->grid = atoi(g);
-    { const char *e = getenv("RWKV_RING"); if (e) c->ring = atoi(e); }
+    warn_retired_env();
     { const char *e = getenv("RWKV_SEQ_B"); if (e) c->seq_b = atoi(e); }
     { const char *e = getenv("RWKV_GRAPH"); if (e) { c->graphs = atoi(e); c->seq_graph = (c->graphs & 2) != 0; } }
     { const char *e = getenv("RWKV_SEQ_ROWS"); if (e) c->seq_rows = atoi(e) > SEQ_T ? SEQ_TM : SEQ_T; }

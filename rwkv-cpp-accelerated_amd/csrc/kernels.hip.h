@@ -582,9 +582,6 @@ constexpr int RED_BC = 96;     // doubles: scalars published by the prologue wav
 #ifndef RWKV_HEAD_R
 #define RWKV_HEAD_R 2      // rows per group in k_head (measured: 2 -> 35.8, 3 -> 36.2, 4 -> 36.8, 5 -> 38.0 us at 7B)
 #endif
-#ifndef RWKV_HEAD_RR
-#define RWKV_HEAD_RR 4     // the same in the ring variant (a group = one LDS slot: larger groups, fewer hand-offs)
-#endif
 // Row-group buffers per wave: 1, or 2 (a wave holds TWO groups of weight registers, A and B, and alternates between
 // them: R*S*2 loads requested ahead).  Measured on MI355X (profiles/r02/decode_variants.txt) two buffers LOSE 8 % at 7B
 // (485 vs 528 tokens/s): the CU's memory pipe accepts only ~16 KB of requests, so a loader wave that asks for two groups
@@ -805,19 +802,13 @@ __device__ __forceinline__ void vec_open(const float *vec, const double *partS, 
 }
 
 // ------------------------------------------------------------------------------------------
-// LDS-DMA streaming ("ring" kernels: template parameter RING of the five decode kernels, RWKV_RING bit per kernel class).
+// LDS-DMA primitives (the tile-form loaders, tile.hip.h, and the chunk path's staging, seq.hip.h).
 // Loads into registers top out at ~10 B/clk per CU on this chip whatever is kept in flight;
 // global_load_lds_dwordx4 -- the CU's DMA path from memory into LDS -- does not return through the vector register file.
-// The workgroup's row groups travel through a ring of `ns` LDS slots (one group of R rows x S KiB each):
-//   * the LAST wave of the workgroup is the loader: it issues the DMA of group k into slot k % ns -- R*S wave instructions
-//     of 1 KiB -- keeps up to DEPTH groups (<= 63 instructions, the vmcnt range) in flight and publishes a group
-//     (ready[slot] = k + 1) once its vmcnt says the group has landed (data returns in order);
-//   * the other NW-1 waves consume: group k belongs to wave k % (NW-1); it waits for ready[slot], copies the slot into
-//     registers (R*S ds_read_b128), hands the slot back (freeq[slot] = k + 1) and runs the same group_dot + epilogue as
-//     the register kernels;
-//   * the loader starts at the kernel's first instruction: the ring (>= 90 KiB) holds what HBM delivers during the
-//     prologue, which waves 0..3 run as in the SPLIT kernels.  No workgroup barrier sits between the order barrier and
-//     the closing reduction -- the roles meet on LDS counters only, and every wait loop is bounded.
+// A loader wave issues the DMA of one unit (S KiB) as ONE asm statement (dma_unit), READS its vmcnt instead of waiting on it, keeps up to
+// RWKV_RING_DEPTH pieces in flight and issues its first units in front of the workgroup's order barrier (RWKV_RING_PRE; per class in
+// tile.hip.h); its consumers meet it on LDS counters only, and every wait loop is bounded (GLDS_SPIN) and reported through the
+// context's error word (ring_report).
 // The DMA is inline asm (hipcc would otherwise count it in vmcnt and drain it before every LDS access of the loader);
 // m0 carries the wave-uniform LDS destination and is restored for the compiler.
 __device__ __forceinline__ unsigned lds_addr(const void *p)
@@ -872,8 +863,8 @@ constexpr int GLDS_SPIN = 1 << 18;    // bound of every wait loop (a lost hand-o
 // is path-insensitive, and the loader wave's instruction count is the stream's ceiling) and REPORTED once per wave, behind the
 // kernel's closing barrier (ring_report), to the context's error word (mapped host memory; engine.hip device_check reads it after
 // the stream synchronisation and fails the call with RWKV_E_DEVICE): the kernel still ends, but nobody is handed its results.
-// codes: 1 loader found no room, 2 a group never landed, 3 the prologue never staged (or the carried rows were never verified),
-// 4 the loader's own DMA never completed.  
+// codes: 1 loader found no room, 2 a unit never landed, 3 the prologue never staged (or the carried rows were never verified),
+// 4 the loader's own DMA never completed.
 __device__ __forceinline__ void wait_count(const unsigned *p, unsigned least, unsigned &fail)
 {
     bool ok = false;
@@ -889,7 +880,6 @@ __device__ __forceinline__ void ring_report(unsigned fail, unsigned *herr)
     if (fail != 0u && herr != nullptr && (threadIdx.x & 63) == 0) __hip_atomic_store(herr, fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 #endif
 }
-constexpr int GLDS_FQ = 32;             // groups the ring bookkeeping can hold
 // DMA pieces (1 KiB) the loader keeps in flight.  By Little's law the queueing delay of EVERY access of the CU is in-flight bytes /
 // stream rate: 63 KiB at 23 KB/us = 2.7 us -- paid by the prologue's loads and, after the last issue, by the kernel's tail --
 // while the stream itself is at full rate from ~24 KiB up (tools/dmabench.hip: depth 63 / 32 / 16 -> 7.3 / 7.3 / 6.0 TB/s).
@@ -898,7 +888,7 @@ constexpr int GLDS_FQ = 32;             // groups the ring bookkeeping can hold
 #ifndef RWKV_RING_DEPTH
 #define RWKV_RING_DEPTH 28
 #endif
-// The weight stream starts BEFORE the workgroup's order barrier: the loader issues its first RWKV_RING_PRE rows at once, thinly
+// The weight stream starts BEFORE the workgroup's order barrier: the loader issues its first RWKV_RING_PRE units at once, thinly
 // (RWKV_RING_PRE_DEPTH pieces in flight: the prologue's loads, issued ~1.4 us into the kernel, queue behind at most that), and
 // only then joins the barrier that lets the prologue's requests into the pipe ahead of the deep stream.  The cold start of a
 // kernel's stream (first translations, empty memory queues) then overlaps the prologue waves' own start-up.
@@ -906,354 +896,14 @@ constexpr int GLDS_FQ = 32;             // groups the ring bookkeeping can hold
 #define RWKV_RING_PRE 8
 #endif
 // TEST build only (tests/test_engine_gpu.py builds a variant with -DRWKV_TEST_DROP_GROUP=1): the loader "loses" every workgroup's last
-// group, so the consumers' bounded wait must give up and the call must fail with RWKV_E_DEVICE instead of returning garbage
+// units, so the consumers' bounded wait must give up and the call must fail with RWKV_E_DEVICE instead of returning garbage
 #ifndef RWKV_TEST_DROP_GROUP
 #define RWKV_TEST_DROP_GROUP 0
-#endif
-#ifndef RWKV_LOADER_PRIO
-#define RWKV_LOADER_PRIO 0        // s_setprio of the loader wave (0..3)
 #endif
 #ifndef RWKV_RING_PRE_DEPTH
 #define RWKV_RING_PRE_DEPTH 20
 #endif
-struct GldsCtl {            // LDS control block of the ring
-    unsigned staged;        // prologue waves that have staged their part of the vector
-    unsigned landed;        // ring units (rows of S KiB) whose DMA has completed: loader -> consumers, monotonic
-    unsigned pad[2];
-    unsigned freeq[GLDS_FQ];   // freeq[k % FQ] = k + 1: group k has been copied out of the ring
-    unsigned gend[GLDS_FQ];    // the loader's own: end unit of group k
-};
-static_assert(sizeof(GldsCtl) % 16 == 0, "the ring behind the control block stays 16-byte aligned");
-constexpr int GLDS_CTL_ZERO = (int)(sizeof(GldsCtl) / 4);
-constexpr int NC = NW - 1;              // consumer waves of a ring kernel
-// LDS of a row-form kernel in ring form: [reduction scratch RED_BYTES][staged vectors: nv x S x 3 KiB][GldsCtl][ring: ns units of S KiB]
-
-// The loader wave.  The ring is made of `nu` UNITS of one row (S KiB) each; a group of R rows takes the next R units (wrapping),
-// so slots of every group size share one ring and the LDS is used to the last 4 KiB.  Round 2's first loader handed out whole
-// group slots, counted its groups with blocking s_waitcnt and DRAINED (vmcnt(0)) whenever the consumers were behind -- which in
-// the ring-full regime (every kernel here, once the prologue is over) serialised issue -> land -> announce per group: 17 KB/us per
-// CU.  This one never blocks on a count it could read instead:
-//   * the wave's own vmcnt is READ (s_getreg IB_STS), so "everything but the last vm pieces has landed" is announced as a
-//     monotonic unit count while the wave waits for room -- the consumer that will free the wanted units may be waiting for exactly that;
-//   * consumers free groups out of order (freeq flags); the tail moves over every leading free group with ONE LDS round trip
-//     (lane i looks at group tail + i);
-//   * a row is one asm statement (dma_unit); all state is wave-uniform.  The loader wave's instruction count IS the stream's
-//     ceiling: tools/dmabench.hip, dmabench2.hip (this protocol with the real group_dot: 6.8 TB/s chip-wide, 26 KB/us per CU).
-template <int S> struct RingLoader {
-    GldsCtl *mc;
-    unsigned ring, nu;       // LDS byte address of unit 0, units
-    unsigned off[S];         // lane's byte offset in a row, per step (rows that are not whole KiB: the last pieces are clamped)
-    bool whole;              // rows are whole KiB: a unit is one dma_unit
-    unsigned issued = 0, pub = 0;       // units issued / announced as landed
-    unsigned k = 0, tail = 0;           // groups issued / groups known to be copied out
-    unsigned tailu = 0;                 // first unit still in use
-    unsigned pos = 0;                   // ring position of the next unit
-    int lane;
-    bool dead = false;
-    unsigned fail = 0;                  // see wait_count
-
-    __device__ __forceinline__ RingLoader(GldsCtl *mc_, unsigned ring_, int nu_, int chunks, int lane_)
-        : mc(mc_), ring((unsigned)__builtin_amdgcn_readfirstlane((int)ring_)), nu((unsigned)nu_), lane(lane_)
-    {
-        asm volatile("" : "+s"(ring));      // an opaque SGPR value (else the generic -> LDS address conversion is redone at every use)
-        whole = chunks == 64 * S;
-#pragma unroll
-        for (int s = 0; s < S; s++) {
-            int c = lane + 64 * s;
-            c = c < chunks ? c : chunks - 1;
-            off[s] = (unsigned)c << 4;
-        }
-    }
-    __device__ __forceinline__ void publish(unsigned units)
-    {
-        if ((int)(units - pub) > 0) {
-            pub = units;
-            if (lane == 0) __hip_atomic_store(&mc->landed, units, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        }
-    }
-    // DMA instructions of this wave that have not completed: HW_REG_IB_STS holds VM_CNT in bits 3:0 and its two high bits in 23:22.
-    // Loads complete in order and this wave issues no other vector memory instruction.
-    __device__ __forceinline__ unsigned in_flight() const
-    {
-        const unsigned v = (unsigned)__builtin_amdgcn_s_getreg((31 << 11) | 7);
-        return (v & 0xfu) | ((v >> 18) & 0x30u);
-    }
-    __device__ __forceinline__ void poll_landed()
-    {
-        const unsigned tot = issued * (unsigned)S, f = in_flight();
-        publish(tot > f ? (tot - f) / (unsigned)S : 0u);        // (saturating: never announce more than was issued, whatever vmcnt holds)
-    }
-    __device__ __forceinline__ void advance_tail()
-    {
-        const unsigned g = tail + (unsigned)(lane & 31);
-        const unsigned f = __hip_atomic_load(&mc->freeq[g % GLDS_FQ], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const unsigned e = __hip_atomic_load(&mc->gend[g % GLDS_FQ], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        asm volatile("" ::: "memory");      // compiler-level ordering is all LDS needs: a consumer's reads precede its flag in the LDS queue
-        const bool ok = lane < 32 && (g - tail) < (k - tail) && f == g + 1u;
-        const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-        const unsigned n = (unsigned)__builtin_ctzll(~m);          // leading groups that are free (<= 32: bits 32.. are never set)
-        if (n) {
-            tailu = (unsigned)__builtin_amdgcn_readlane((int)e, (int)(n - 1u));
-            tail += n;
-        }
-    }
-    template <int R> __device__ __forceinline__ bool room() const { return !(issued + R - tailu > nu || k - tail >= (unsigned)GLDS_FQ); }
-    // R rows starting at `src` (this lane's first piece of row 0; rows `stride` bytes apart) -> the next R units
-    template <int R> __device__ __forceinline__ void group(const uint8_t *src, size_t stride, bool thin = false)
-    {
-        for (int it = 0; !room<R>() && !dead; it++) {
-            advance_tail();
-            if (room<R>()) break;
-            poll_landed();
-            if (it >= GLDS_SPIN) { dead = true; fail = 1u; }      // a lost hand-off must end the kernel, not hang the GPU -- and must be reported
-            __builtin_amdgcn_s_sleep(1);
-        }
-        if (lane == 0) mc->gend[k % GLDS_FQ] = issued + R;
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            if (thin) wait_vm<(RWKV_RING_PRE_DEPTH > S ? RWKV_RING_PRE_DEPTH : S) - S>();
-            else wait_vm<(RWKV_RING_DEPTH < 63 ? RWKV_RING_DEPTH : 63) - S>();      // 63: the counter has 6 bits
-            const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(ring + pos * (unsigned)(S * 1024)));
-            if (whole) dma_unit<S>(src + r * stride, dst);
-            else {
-#pragma unroll
-                for (int s = 0; s < S; s++) dma_piece(src + r * stride + (off[s] - off[0]), dst + s * 1024);
-            }
-            pos = pos + 1 == nu ? 0u : pos + 1;
-        }
-        issued += R;
-        k++;
-        poll_landed();
-    }
-    __device__ __forceinline__ void finish()
-    {
-        int it = 0;
-        for (; it < GLDS_SPIN && in_flight() != 0u; it++) { poll_landed(); __builtin_amdgcn_s_sleep(1); }
-        fail = it >= GLDS_SPIN ? 4u : fail;
-        wait_vm<0>();
-        publish(issued);
-    }
-};
-// the loader wave of a launch kernel: groups [g0, g1) of the workgroup in order; base(g) = address of group g's first row
-template <int R, int S, class Base>
-__device__ __forceinline__ unsigned glds_loader(Base base, int g0, int g1, size_t stride, int chunks, int nu, unsigned ring, GldsCtl *ctl, int lane)
-{
-    loader_clean_slate();
-#if RWKV_LOADER_PRIO
-    __builtin_amdgcn_s_setprio(RWKV_LOADER_PRIO);     // the loader's instruction issue IS the stream's ceiling: let it win the SIMD's arbitration
-#endif
-    // the control block is this wave's to zero: nobody else touches it before the order barrier
-    for (int i = lane; i < GLDS_CTL_ZERO; i += 64) reinterpret_cast<unsigned *>(ctl)[i] = 0u;
-    RingLoader<S> ld(ctl, ring, nu, chunks, lane);
-    int g = g0;
-    const int pre = RWKV_RING_PRE < nu - R ? RWKV_RING_PRE : nu - R;      // never wait for room before the barrier: the consumers are behind it
-    for (; g < g1 && (int)ld.issued < pre; g++) ld.template group<R>(base(g) + ld.off[0], stride, true);
-    __syncthreads();   // order: the control block is zero, the prologue's requests are in the pipe
-    // (TEST build -DRWKV_TEST_DROP_GROUP=1: the loader "loses" the workgroup's last group)
-    for (; g < g1 - (RWKV_TEST_DROP_GROUP ? 1 : 0); g++) ld.template group<R>(base(g) + ld.off[0], stride);
-    ld.finish();
-    return ld.fail;
-}
-// consumer side of one group (kl = its index in the workgroup): wait, copy its R units into registers, hand them back
-template <int R, int S>
-__device__ __forceinline__ void glds_take(u32x4 (&w)[R][S], int kl, int nu, const unsigned char *ring, GldsCtl *ctl, int lane, unsigned &fail)
-{
-    const unsigned uend = (unsigned)(kl + 1) * R;
-    bool ok = false;
-    for (int it = 0; it < GLDS_SPIN; it++) {
-        if ((int)(__hip_atomic_load(&ctl->landed, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) - uend) >= 0) { ok = true; break; }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    fail = ok ? fail : 2u;
-    unsigned p0 = (uend - R) % (unsigned)nu;
-#pragma unroll
-    for (int r = 0; r < R; r++) {
-        const u32x4 *p = reinterpret_cast<const u32x4 *>(ring + (size_t)p0 * (S * 1024)) + lane;
-#pragma unroll
-        for (int s = 0; s < S; s++) w[r][s] = p[s * 64];
-        p0 = p0 + 1 == (unsigned)nu ? 0u : p0 + 1;
-    }
-    if (lane == 0) __hip_atomic_store(&ctl->freeq[kl % GLDS_FQ], (unsigned)kl + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-// EARLY TAKE (round 4).  The ring holds what HBM delivers while waves 0..3 run the prologue; when the prologue outlasts the ring --
-// 14B: vectors staged at 6.5 us, the ring (110-125 KiB) full at 4.4-5 us, the loader idle for ~2 us of every k_att / k_ffn_rk launch
-// (profiles/r04/timelines_14B_1B5.txt) -- the stream waits for the consumers.  The consumer waves that do NOT stage (4..6) therefore take
-// the workgroup's FIRST groups (the loader's tail only moves over LEADING free groups: freeing groups 4..6 would buy nothing) out of
-// the ring into registers as soon as they land, BEFORE the vectors are staged: three groups (45-75 KiB) more room for the loader.  So
-// the wait for "staged" (ready()) sits inside the first iteration, between the take and the dot products, and the first group of
-// wave w is (w + 3) mod 7.  The first group's epilogue inputs are still requested right in front of its dot products (an early
-// scattered global load would sit in the CU's in-order return queue in front of the stream).
-// Measured (profiles/r04/early_take_ab.txt, A/B on one box): 14B k_att 19.0 -> 18.0 us, token +1.5 %; at 3-4 KiB rows, where the ring
-// covers the prologue anyway, it loses 0.5 % (7B) / 3 % (3B) -- so: on for rows >= 5 KiB.
-#ifndef RWKV_EARLY_TAKE
-#define RWKV_EARLY_TAKE 2       // 0 off, 1 on, 2 by row size
-#endif
-template <int S> __device__ __forceinline__ constexpr bool early_take() { return RWKV_EARLY_TAKE == 1 || (RWKV_EARLY_TAKE == 2 && S >= 5); }
-// the consumer waves' streaming loop (wave < NC): same pre / epi contract as stream_groups; ready() = wait until the vectors are staged
-// and fetch the scalars the epilogues need (called once, by every wave)
-template <int R, int S, int PAT, class Pre, class Epi, class Ready>
-__device__ __forceinline__ void ring_groups(int g0, int g1, int nu, const unsigned char *ring, GldsCtl *ctl, const unsigned *xq, int lane, int wave,
-                                            int chunks, Pre pre, Epi epi, Ready ready, unsigned &fail, unsigned long long *g_tl_groups = nullptr)
-{
-#ifdef RWKV_TL_GROUPS
-    // debug build (tools/timeline.py): where a consumer wave's time goes.  Stamps of the wave: 1 inputs of its first group requested,
-    // 2 first group taken, 4 its dot products and reductions done, 3 its epilogue done (5 stays "staged", 6 / 7 the kernel's end)
-    int rr = 0;
-#endif
-    constexpr int NWP = NT / 2 / 64;
-    constexpr bool ET = early_take<S>();
-    bool first = true;
-    if (!ET) { ready(); first = false; }
-    const bool late_pre = ET && wave >= NWP;       // the waves that take their first group before the vectors are staged
-    for (int g = g0 + (ET ? (wave + NC - NWP) % NC : wave); g < g1; g += NC) {
-        decltype(pre(g)) in;
-        if (!(first && late_pre)) in = pre(g);
-#ifdef RWKV_TL_GROUPS
-        if (rr == 0) tl_stamp(g_tl_groups, 1);
-#endif
-        u32x4 w[R][S];
-        glds_take<R, S>(w, g - g0, nu, ring, ctl, lane, fail);
-        if (first) { ready(); if (late_pre) in = pre(g); first = false; }
-#ifdef RWKV_TL_GROUPS
-        asm volatile("" : "+v"(w[R - 1][S - 1]));
-        if (rr < 1) tl_stamp(g_tl_groups, 2);
-#endif
-        unsigned long long T[R];
-        group_dot<R, S, PAT, false>(w, xq, lane, T, nullptr, 0, chunks, false);
-#ifdef RWKV_TL_GROUPS
-        asm volatile("" : "+s"(T[R - 1]));
-        if (rr < 1) tl_stamp(g_tl_groups, 4);
-#endif
-        epi(g, T, in);
-#ifdef RWKV_TL_GROUPS
-        if (rr < 1) tl_stamp(g_tl_groups, 3);
-        rr++;
-#endif
-    }
-    if (first) ready();      // a wave without a group still meets the others (time-outs are reported per wave)
-}
-// ring kernels: the control block is zeroed before the order barrier
-__device__ __forceinline__ void ring_init(GldsCtl *gc)
-{
-    if (threadIdx.x < (unsigned)GLDS_CTL_ZERO) reinterpret_cast<unsigned *>(gc)[threadIdx.x] = 0u;
-}
-// LayerNorm-site prologue of a ring kernel, called by the consumer waves (wave < NC): waves 0..3 stage the NV vectors and
-// publish the scalars, the others wait; contains the workgroup's order barrier, which the loader executes once as well
-template <int NV, int S>
-__device__ __forceinline__ void ring_site(const SiteStatic &st, const SiteDyn &dy, const double *x, int D, double *red, unsigned *xq,
-                                          bool publish_stats, GldsCtl *gc, unsigned long long *tl, unsigned &fail)
-{
-    constexpr int NTP = NT / 2, NWP = NTP / 64, NQP = (S * 256 + NTP - 1) / NTP;
-    const int nqd = D >> 2;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    unsigned *spin = reinterpret_cast<unsigned *>(bc + 8);
-    if (wave_id() < NWP) {
-        double tc[NV];
-        float mc[NV];
-#pragma unroll
-        for (int m = 0; m < NV; m++) { tc[m] = st.TC[m]; mc[m] = st.maxC[m]; }
-        SiteTuple tup;
-        site_tuple_load(dy, tup);
-        double xl[NQP][4];
-        f32x4 Cq[NQP][NV], Bq[NQP][NV];
-#pragma unroll
-        for (int i = 0; i < NQP; i++) {
-            const int qd = threadIdx.x + i * NTP, qc = qd < nqd ? qd : nqd - 1;
-            load_quad_f64(x, qc, xl[i]);
-#pragma unroll
-            for (int m = 0; m < NV; m++) {
-                Cq[i][m] = reinterpret_cast<const f32x4 *>(st.C + (size_t)m * D)[qc];
-                Bq[i][m] = reinterpret_cast<const f32x4 *>(dy.B + (size_t)m * D)[qc];
-            }
-        }
-        tl_stamp(tl, 1);
-        if (threadIdx.x == 0) *spin = 0u;
-        __syncthreads();   // order
-        SiteRed<NV> r;
-        site_reduce<NV, NWP>(st, dy, tup, D, red, r, tc, mc, tl, spin);
-        if (publish_stats && blockIdx.x == 0 && threadIdx.x == 0) { dy.lnstat[0] = r.mean; dy.lnstat[1] = r.rstd; }
-        tl_stamp(tl, 4);
-        site_stage<NV, NQP, S, NTP>(xl, Cq, Bq, r, xq, nqd);
-        if (threadIdx.x == 0) {
-#pragma unroll
-            for (int m = 0; m < NV; m++) { bc[m] = (float)r.S[m]; bc[4 + m] = r.amax[m]; }
-        }
-        if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(&gc->staged, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    } else {
-        __syncthreads();   // order
-    }
-}
-// ... and its second half, run by every consumer wave inside its first group (ring_groups' ready()): the vectors are staged; the
-// scalars of the site come out of LDS
-template <int NV>
-__device__ __forceinline__ void ring_site_ready(double *red, GldsCtl *gc, SiteRed<NV> &sr, unsigned &fail, unsigned long long *tl)
-{
-    constexpr int NWP = NT / 2 / 64;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    wait_count(&gc->staged, NWP, fail);
-#pragma unroll
-    for (int m = 0; m < NV; m++) { sr.S[m] = (double)bc[m]; sr.amax[m] = bc[4 + m]; }
-    sr.mean = sr.rstd = 0.0;
-    tl_stamp(tl, 5);
-}
-// plain-vector prologue of a ring kernel (k_attout, k_ffnv), same roles
-template <int NVEC, int S>
-__device__ __forceinline__ void ring_vec(const float *vec, const double *partS, const float *partM, int n_part, int D, double *red, unsigned *xq,
-                                         GldsCtl *gc, unsigned long long *tl, unsigned &fail)
-{
-    constexpr int XVD = xvd<S>();
-    constexpr int NTP = NT / 2, NWP = NTP / 64, NQP = (S * 256 + NTP - 1) / NTP;
-    const int lane = threadIdx.x & 63, wave = wave_id(), nqd = D >> 2;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    unsigned *spin = reinterpret_cast<unsigned *>(bc + 8);
-    if (wave < NWP) {
-        double ps = partS[(int)threadIdx.x < n_part ? threadIdx.x : 0];
-        float pm = partM[(int)threadIdx.x < n_part ? threadIdx.x : 0];
-        float vl[NVEC][NQP][4];
-#pragma unroll
-        for (int q = 0; q < NVEC; q++)
-#pragma unroll
-            for (int i = 0; i < NQP; i++) {
-                const int qd = threadIdx.x + i * NTP, qc = qd < nqd ? qd : nqd - 1;
-                const f32x4 t = reinterpret_cast<const f32x4 *>(vec + (size_t)q * D)[qc];
-                vl[q][i][0] = t[0]; vl[q][i][1] = t[1]; vl[q][i][2] = t[2]; vl[q][i][3] = t[3];
-            }
-        tl_stamp(tl, 1);
-        if (threadIdx.x == 0) *spin = 0u;
-        __syncthreads();   // order
-        if ((int)threadIdx.x >= n_part) { ps = 0.0; pm = 0.f; }
-        float *redf = reinterpret_cast<float *>(red + RED_MAX);
-        const double ws = wave_sum(ps);
-        const float wm = wave_max(pm);
-        if (lane == 0) { red[RED_OFFS + wave] = ws; redf[wave] = wm; }
-        tl_stamp(tl, 3);
-        if (lane == 0) __hip_atomic_fetch_add(spin, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        wait_count(spin, NWP, fail);
-        double ts = 0.0; float tm = 0.f;
-#pragma unroll
-        for (int i = 0; i < NWP; i++) { ts += red[RED_OFFS + i]; tm = fmaxf(tm, redf[i]); }
-        tl_stamp(tl, 4);
-#pragma unroll
-        for (int q = 0; q < NVEC; q++)
-#pragma unroll
-            for (int i = 0; i < NQP; i++) {
-                const int qd = threadIdx.x + i * NTP;
-                if (qd < S * 256) stage_quad(xq + q * XVD, qd, vl[q][i], inv_scale(tm), qd < nqd);
-            }
-        if (threadIdx.x == 0) { bc[0] = (float)ts; bc[4] = tm; }
-        if (lane == 0) __hip_atomic_fetch_add(&gc->staged, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    } else {
-        __syncthreads();   // order
-    }
-}
-__device__ __forceinline__ void ring_vec_ready(double *red, GldsCtl *gc, float &Sf, float &amax, unsigned &fail, unsigned long long *tl)
-{
-    constexpr int NWP = NT / 2 / 64;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    wait_count(&gc->staged, NWP, fail);
-    Sf = bc[0]; amax = bc[4];
-    tl_stamp(tl, 5);
-}
+constexpr int NC = NW - 1;              // consumer waves of an LDS-DMA kernel (the last wave is the loader)
 
 // ------------------------------------------------------------------------------------------
 struct FirstArgs {
@@ -1316,14 +966,14 @@ struct AttArgs {
     float *partM;                         // [gridDim.x] partial max |ybuf| (k_attout's quantisation scale)
     const Ctl *ctl;
     int D;
-    int ns;                               // ring kernels: LDS slots
+    int ns;                               // tile form (tile.hip.h): LDS ring units
     unsigned long long *tl;               // optional phase timeline (see tl_stamp)
-    unsigned *herr;                       // ring kernels: the context's error word (raise_error)
+    unsigned *herr;                       // tile form: the context's error word (ring_report)
 };
 
 // ln1 site -> K,V,R dequant-GEMV -> WKV (rwkv.cu:535-545; kernels :351-392, :58-100, :221-259)
 struct AttIn { unsigned rs[3]; double aa, bb, uw, ew; float ra, oa; };
-template <int S, int NB, int RING = 0>
+template <int S, int NB>
 __global__ __launch_bounds__(NT) void k_att(AttArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1331,13 +981,9 @@ __global__ __launch_bounds__(NT) void k_att(AttArgs a)
     unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
-    if constexpr (RING) RWKV_ARGS_NOW(a.x, a.st.C, a.st.TC, a.st.maxC, a.dy.B, a.dy.pd, a.dy.pf, a.dy.n_part);
     const int g0 = block_lo(D);
     const int g1 = block_hi(D);
-    // (not on the loader wave: a compiler-visible load pending there makes hipcc guard the register it was given with s_waitcnt vmcnt(0)
-    // wherever the loader's code happens to reuse it -- in round 5 that was inside the loader's loop, i.e. a drain of its DMA queue per group)
-    size_t so = 0;
-    if (!RING || wave != NC) so = (size_t)a.ctl->slot * a.slot_stride;
+    const size_t so = (size_t)a.ctl->slot * a.slot_stride;
 
     tl_stamp(a.tl, 0);
     // every wave requests its first groups, even one without work (it re-reads a neighbour's rows): a
@@ -1379,33 +1025,18 @@ __global__ __launch_bounds__(NT) void k_att(AttArgs a)
             pmax = fmaxf(pmax, fabsf(ys));
         }
     };
-    unsigned fail = 0u;        // a bounded wait of this wave gave up (wait_count)
-    if constexpr (RING) {
-        GldsCtl *gc = reinterpret_cast<GldsCtl *>(smem + RED_BYTES + 3 * S * 3072);
-        unsigned char *ring = reinterpret_cast<unsigned char *>(gc + 1);
-        if (wave == NC) {
-            fail = glds_loader<3, S>(base, g0, g1, (size_t)D, chunks, a.ns, lds_addr(ring), gc, lane);
-            tl_stamp(a.tl, 2);
-        } else {
-            ring_site<3, S>(a.st, a.dy, a.x, D, red, xq, true, gc, a.tl, fail);
-            auto ready = [&]() { SiteRed<3> sr; ring_site_ready<3>(red, gc, sr, fail, a.tl); scalars(sr); };
-            ring_groups<3, S, PAT_PER_ROW>(g0, g1, a.ns, ring, gc, xq, lane, wave, chunks, pre, epi, ready, fail, a.tl);
-        }
-    } else {
-        u32x4 wA[3][S], wB[3][S];
-        int gA, gB;
-        unsigned *gctr = group_counter(red);
-        first_groups<NB>(g0, wave, gctr, gA, gB);   // the counter is visible behind the prologue's barriers
-        SiteRed<3> sr;
-        site_open<3, 3, S, (RWKV_SPLIT & 1) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, true, a.tl);
-        scalars(sr);
-        stream_groups<3, S, PAT_PER_ROW, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
-    }
+    u32x4 wA[3][S], wB[3][S];
+    int gA, gB;
+    unsigned *gctr = group_counter(red);
+    first_groups<NB>(g0, wave, gctr, gA, gB);   // the counter is visible behind the prologue's barriers
+    SiteRed<3> sr;
+    site_open<3, 3, S, (RWKV_SPLIT & 1) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, true, a.tl);
+    scalars(sr);
+    stream_groups<3, S, PAT_PER_ROW, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     tl_stamp(a.tl, 6);
     __syncthreads();   // every wave is past its last read of the reduction scratch
     block_sum_max(part, pmax, red + RED_PART);
     if (threadIdx.x == 0) { a.partS[blockIdx.x] = part; a.partM[blockIdx.x] = pmax; }
-    if constexpr (RING) ring_report(fail, a.herr);
     tl_stamp(a.tl, 7);
 }
 
@@ -1427,15 +1058,15 @@ struct AttOutArgs {
     size_t slot_stride;
     const Ctl *ctl;
     int D;
-    int ns;                // ring kernels: LDS slots
+    int ns;                // tile form (tile.hip.h): LDS ring units
     unsigned long long *tl;
-    unsigned *herr;
+    unsigned *herr;        // tile form: the context's error word (ring_report)
 };
 
 // att_out dequant-GEMV + residual through f32 (rwkv.cu:548-553), R rows per group; commits state xy;
 // opens the ln2 site for the rows it owns
 template <int R> struct AttOutIn { unsigned rsum; double xold, lw, lb, prev2; SitePre<2> pre; int mi, shift; };
-template <int S, int R, int NB, int RING = 0>
+template <int S, int R, int NB>
 __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1444,14 +1075,12 @@ __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
     tl_stamp(a.tl, 0);
-    if constexpr (RING) RWKV_ARGS_NOW(a.ybuf, a.partS, a.partM, a.n_part);
     const int G = (D + R - 1) / R;
     const int g0 = block_lo(G);
     const int g1 = block_hi(G);
 
-    double mean1 = 0.0, rstd1 = 1.0;
-    size_t so = 0;
-    if (!RING || wave != NC) { mean1 = a.lnstat[0]; rstd1 = a.lnstat[1]; so = (size_t)a.ctl->slot * a.slot_stride; }      // (not on the loader wave: see k_att)
+    const double mean1 = a.lnstat[0], rstd1 = a.lnstat[1];
+    const size_t so = (size_t)a.ctl->slot * a.slot_stride;
     auto base = [&](int gg) {
         int row = (gg < g1 ? gg : (g1 > g0 ? g1 - 1 : 0)) * R;
         if (row > D - R) row = D - R;          // the last group may overlap the previous one
@@ -1484,31 +1113,16 @@ __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
             }
         }
     };
-    unsigned fail = 0u;        // a bounded wait of this wave gave up (wait_count)
-    if constexpr (RING) {
-        GldsCtl *gc = reinterpret_cast<GldsCtl *>(smem + RED_BYTES + S * 3072);
-        unsigned char *ring = reinterpret_cast<unsigned char *>(gc + 1);
-        if (wave == NC) {
-            fail = glds_loader<R, S>(base, g0, g1, (size_t)D, chunks, a.ns, lds_addr(ring), gc, lane);
-            tl_stamp(a.tl, 2);
-        } else {
-            ring_vec<1, S>(a.ybuf, a.partS, a.partM, a.n_part, D, red, xq, gc, a.tl, fail);
-            auto ready = [&]() { ring_vec_ready(red, gc, Sf, amax, fail, a.tl); sc = scale_of(amax); };
-            ring_groups<R, S, PAT_SHARED>(g0, g1, a.ns, ring, gc, xq, lane, wave, chunks, pre, epi, ready, fail, nullptr);
-        }
-    } else {
-        u32x4 wA[R][S], wB[R][S];
-        int gA, gB;
-        unsigned *gctr = group_counter(red);
-        first_groups<NB>(g0, wave, gctr, gA, gB);
-        vec_open<1, R, S, (RWKV_SPLIT & 2) != 0, NB>(a.ybuf, a.partS, a.partM, a.n_part, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, Sf, amax, a.tl);
-        sc = scale_of(amax);
-        stream_groups<R, S, PAT_SHARED, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
-    }
-    __syncthreads();   // every wave is past its last read of the reduction scratch (and of the staged vector / the ring)
+    u32x4 wA[R][S], wB[R][S];
+    int gA, gB;
+    unsigned *gctr = group_counter(red);
+    first_groups<NB>(g0, wave, gctr, gA, gB);
+    vec_open<1, R, S, (RWKV_SPLIT & 2) != 0, NB>(a.ybuf, a.partS, a.partM, a.n_part, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, Sf, amax, a.tl);
+    sc = scale_of(amax);
+    stream_groups<R, S, PAT_SHARED, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
+    __syncthreads();   // every wave is past its last read of the reduction scratch (and of the staged vector)
     tl_stamp(a.tl, 6);
     site_publish<2, R>(acc, a.dy, xq);   // the staged vector is dead: its LDS is the scratch
-    if constexpr (RING) ring_report(fail, a.herr);
     tl_stamp(a.tl, 7);
 }
 
@@ -1526,14 +1140,14 @@ struct FfnRKArgs {
     float *partM;                     // [gridDim.x] partial max |hbuf| (k_ffnv's quantisation scale)
     const Ctl *ctl;
     int D;
-    int ns;                           // ring kernels: LDS slots
+    int ns;                           // tile form (tile.hip.h): LDS ring units
     unsigned long long *tl;           // optional phase timeline (see tl_stamp)
-    unsigned *herr;
+    unsigned *herr;                   // tile form: the context's error word (ring_report)
 };
 
 // ln2 site -> ffn_r GEMV + sigmoid, ffn_k GEMV + relu^2 (rwkv.cu:557-573)
 struct FfnRKIn { unsigned rsum; float rq, oq; };
-template <int S, int NB, int RING = 0>
+template <int S, int NB>
 __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1541,7 +1155,6 @@ __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
     unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
-    if constexpr (RING) RWKV_ARGS_NOW(a.x, a.st.C, a.st.TC, a.st.maxC, a.dy.B, a.dy.pd, a.dy.pf, a.dy.n_part);
     const int g0 = block_lo(D);
     const int g1 = block_hi(D);
     tl_stamp(a.tl, 0);
@@ -1579,33 +1192,18 @@ __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
             a.rgate[g] = (float)(1.0 / (1.0 + exp(-(double)val)));   // rwkv.cu:212
         }
     };
-    unsigned fail = 0u;        // a bounded wait of this wave gave up (wait_count)
-    if constexpr (RING) {
-        GldsCtl *gc = reinterpret_cast<GldsCtl *>(smem + RED_BYTES + 2 * S * 3072);
-        unsigned char *ring = reinterpret_cast<unsigned char *>(gc + 1);
-        if (wave == NC) {
-            fail = glds_loader<5, S>(base, g0, g1, (size_t)D, chunks, a.ns, lds_addr(ring), gc, lane);
-            tl_stamp(a.tl, 2);
-        } else {
-            ring_site<2, S>(a.st, a.dy, a.x, D, red, xq, true, gc, a.tl, fail);
-            auto ready = [&]() { SiteRed<2> sr; ring_site_ready<2>(red, gc, sr, fail, a.tl); scalars(sr); };
-            ring_groups<5, S, PAT_FFN_RK>(g0, g1, a.ns, ring, gc, xq, lane, wave, chunks, pre, epi, ready, fail, a.tl);
-        }
-    } else {
-        u32x4 wA[5][S], wB[5][S];
-        int gA, gB;
-        unsigned *gctr = group_counter(red);
-        first_groups<NB>(g0, wave, gctr, gA, gB);
-        SiteRed<2> sr;
-        site_open<2, 5, S, (RWKV_SPLIT & 4) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, true, a.tl);
-        scalars(sr);
-        stream_groups<5, S, PAT_FFN_RK, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
-    }
+    u32x4 wA[5][S], wB[5][S];
+    int gA, gB;
+    unsigned *gctr = group_counter(red);
+    first_groups<NB>(g0, wave, gctr, gA, gB);
+    SiteRed<2> sr;
+    site_open<2, 5, S, (RWKV_SPLIT & 4) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, true, a.tl);
+    scalars(sr);
+    stream_groups<5, S, PAT_FFN_RK, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     tl_stamp(a.tl, 6);
     __syncthreads();   // every wave is past its last read of the reduction scratch
     block_sum_max(part, pmax, red + RED_PART);
     if (threadIdx.x == 0) { a.partS[blockIdx.x] = part; a.partM[blockIdx.x] = pmax; }
-    if constexpr (RING) ring_report(fail, a.herr);
     tl_stamp(a.tl, 7);
 }
 
@@ -1628,14 +1226,14 @@ struct FfnVArgs {
     size_t slot_stride;
     const Ctl *ctl;
     int D;
-    int ns;                // ring kernels: LDS slots
+    int ns;                // tile form (tile.hip.h): LDS ring units
     unsigned long long *tl;
-    unsigned *herr;
+    unsigned *herr;        // tile form: the context's error word (ring_report)
 };
 
 // ffn_v dequant-GEMV, x += v * sigmoid(r) (rwkv.cu:574-577); commits state dd; opens the next site
 template <int NVN> struct FfnVIn { unsigned rsum; double xold, lw, lb, prevn; float rg; SitePre<NVN> pre; };
-template <int S, int NVN, int NB, int RING = 0>
+template <int S, int NVN, int NB>
 __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1643,14 +1241,12 @@ __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
     unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
-    if constexpr (RING) RWKV_ARGS_NOW(a.hbuf, a.partS, a.partM, a.n_part);
     tl_stamp(a.tl, 0);
     const int g0 = block_lo(D);
     const int g1 = block_hi(D);
 
-    double mean2 = 0.0, rstd2 = 1.0;
-    size_t so = 0;
-    if (!RING || wave != NC) { mean2 = a.lnstat[0]; rstd2 = a.lnstat[1]; so = (size_t)a.ctl->slot * a.slot_stride; }      // (not on the loader wave: see k_att)
+    const double mean2 = a.lnstat[0], rstd2 = a.lnstat[1];
+    const size_t so = (size_t)a.ctl->slot * a.slot_stride;
     auto base = [&](int g) { return a.w + (size_t)(g < g1 ? g : (g1 > g0 ? g1 - 1 : 0)) * 4 * D; };
     float Sf, amax;   // one scale for the whole 4D hidden vector
     double sc;
@@ -1674,31 +1270,16 @@ __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
             site_emit<NVN>(in.pre, a.dy, D, g, xnew, in.prevn, acc);
         }
     };
-    unsigned fail = 0u;        // a bounded wait of this wave gave up (wait_count)
-    if constexpr (RING) {
-        GldsCtl *gc = reinterpret_cast<GldsCtl *>(smem + RED_BYTES + 4 * S * 3072);
-        unsigned char *ring = reinterpret_cast<unsigned char *>(gc + 1);
-        if (wave == NC) {
-            fail = glds_loader<4, S>(base, g0, g1, (size_t)D, chunks, a.ns, lds_addr(ring), gc, lane);
-            tl_stamp(a.tl, 2);
-        } else {
-            ring_vec<4, S>(a.hbuf, a.partS, a.partM, a.n_part, D, red, xq, gc, a.tl, fail);
-            auto ready = [&]() { ring_vec_ready(red, gc, Sf, amax, fail, a.tl); sc = scale_of(amax); };
-            ring_groups<4, S, PAT_PER_ROW>(g0, g1, a.ns, ring, gc, xq, lane, wave, chunks, pre, epi, ready, fail, a.tl);
-        }
-    } else {
-        u32x4 wA[4][S], wB[4][S];
-        int gA, gB;
-        unsigned *gctr = group_counter(red);
-        first_groups<NB>(g0, wave, gctr, gA, gB);
-        vec_open<4, 4, S, (RWKV_SPLIT & 8) != 0, NB>(a.hbuf, a.partS, a.partM, a.n_part, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, Sf, amax, a.tl);
-        sc = scale_of(amax);
-        stream_groups<4, S, PAT_PER_ROW, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
-    }
+    u32x4 wA[4][S], wB[4][S];
+    int gA, gB;
+    unsigned *gctr = group_counter(red);
+    first_groups<NB>(g0, wave, gctr, gA, gB);
+    vec_open<4, 4, S, (RWKV_SPLIT & 8) != 0, NB>(a.hbuf, a.partS, a.partM, a.n_part, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, Sf, amax, a.tl);
+    sc = scale_of(amax);
+    stream_groups<4, S, PAT_PER_ROW, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     __syncthreads();   // every wave is past its last read of the reduction scratch
     tl_stamp(a.tl, 6);
     site_publish<NVN, 1>(acc, a.dy, xq);   // the staged vector is dead: its LDS is the scratch
-    if constexpr (RING) ring_report(fail, a.herr);
     tl_stamp(a.tl, 7);
 }
 
@@ -1714,13 +1295,11 @@ struct HeadArgs {
     unsigned *blk_idx;         // [gridDim.x]
     const Ctl *ctl;
     int D;
-    int ns;                    // ring kernels: LDS slots
-    unsigned *herr;
 };
 
 // ln_out site -> head dequant-GEMV -> logits (rwkv.cu:585-589); also per-workgroup argmax partials
 template <int R> struct HeadIn { unsigned rsr[R]; int row0, shift; };
-template <int S, int NB, int RING = 0, int R = RING ? RWKV_HEAD_RR : RWKV_HEAD_R>
+template <int S, int NB, int R = RWKV_HEAD_R>
 __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1735,8 +1314,7 @@ __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
     const int G = (V + R - 1) / R;
     const int g0 = block_lo(G);
     const int g1 = block_hi(G);
-    float *lg = a.logits;                                  // read at entry: behind the prologue's barriers it is a cold load (not on the loader wave: see k_att)
-    if (!RING || wave != NC) lg = a.logits + (size_t)a.ctl->out_row * V;
+    float *lg = a.logits + (size_t)a.ctl->out_row * V;     // read at entry: behind the prologue's barriers it is a cold load
 
     auto base = [&](int gg) {
         int row = (gg < g1 ? gg : (g1 > g0 ? g1 - 1 : 0)) * R;
@@ -1765,27 +1343,14 @@ __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
             if (i != 0 && (val > best || (val == best && (unsigned)i < besti))) { best = val; besti = (unsigned)i; }
         }
     };
-    unsigned fail = 0u;        // a bounded wait of this wave gave up (wait_count)
-    if constexpr (RING) {
-        GldsCtl *gc = reinterpret_cast<GldsCtl *>(smem + RED_BYTES + S * 3072 + 64);   // behind bval / bidx
-        unsigned char *ring = reinterpret_cast<unsigned char *>(gc + 1);
-        if (wave == NC) {
-            fail = glds_loader<R, S>(base, g0, g1, (size_t)D, chunks, a.ns, lds_addr(ring), gc, lane);
-        } else {
-            ring_site<1, S>(a.st, a.dy, a.x, D, red, xq, false, gc, nullptr, fail);
-            auto ready = [&]() { SiteRed<1> sr; ring_site_ready<1>(red, gc, sr, fail, nullptr); Sf = (float)sr.S[0]; sc = scale_of(sr.amax[0]); };
-            ring_groups<R, S, PAT_SHARED>(g0, g1, a.ns, ring, gc, xq, lane, wave, chunks, pre, epi, ready, fail);
-        }
-    } else {
-        u32x4 wA[R][S], wB[R][S];
-        int gA, gB;
-        unsigned *gctr = group_counter(red);
-        first_groups<NB>(g0, wave, gctr, gA, gB);
-        SiteRed<1> sr;
-        site_open<1, R, S, (RWKV_SPLIT & 16) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, false, nullptr);
-        Sf = (float)sr.S[0]; sc = scale_of(sr.amax[0]);
-        stream_groups<R, S, PAT_SHARED, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
-    }
+    u32x4 wA[R][S], wB[R][S];
+    int gA, gB;
+    unsigned *gctr = group_counter(red);
+    first_groups<NB>(g0, wave, gctr, gA, gB);
+    SiteRed<1> sr;
+    site_open<1, R, S, (RWKV_SPLIT & 16) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, false, nullptr);
+    Sf = (float)sr.S[0]; sc = scale_of(sr.amax[0]);
+    stream_groups<R, S, PAT_SHARED, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     if (lane == 0) { bval[wave] = best; bidx[wave] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1794,7 +1359,6 @@ __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
         a.blk_val[blockIdx.x] = best;
         a.blk_idx[blockIdx.x] = besti;
     }
-    if constexpr (RING) ring_report(fail, a.herr);
 }
 
 // finish the greedy pick: argmax over workgroup partials (ties -> lowest id), feed it back as the

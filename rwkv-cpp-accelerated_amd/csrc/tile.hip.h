@@ -13,7 +13,7 @@
 //     different waves meet as exact integer adds in LDS (ds_add_u32: the sums are integers, so the order they arrive in changes nothing);
 //   * the ring unit is S KiB = S fragments of ONE tile (contiguous in the image: one dma_unit), units go to the 7 consumer waves round
 //     robin (or in runs, tile_run), every unit is freed as soon as its S ds_read_b128 are in the LDS queue: fine-grained turnover, all
-//     waves busy from the first unit on (row form: 5 groups of 20 KiB in the ring for 7 waves);
+//     waves busy from the first unit on (the row form's retired LDS ring held 5 groups of 20 KiB for 7 waves);
 //   * the wave whose add completes a tile runs that tile's TH epilogues side by side on TH lanes;
 //   * activations: the same 23-bit fixed point, limbs stored SIGNED (limb - 128) so that v_dot4_i32_i8 multiplies the image's bytes as
 //     they are: sum u l = dot + 128 rowsum(u) + 128 sum(l) - 16384 N, folded into one constant per vector (cA) and the row-sum
@@ -90,7 +90,7 @@ __device__ __forceinline__ unsigned stage_quad_t(unsigned *xq, int qd, const flo
 }
 
 // LayerNorm-site prologue of a tile-form kernel, run by waves 0..3 (the other consumer waves and the loader meet them at the order
-// barrier inside); same ownership split as ring_site (kernels.hip.h).  SD = ceil(D / 1024).
+// barrier inside); same ownership split as the row form's SPLIT prologue (site_open, kernels.hip.h).  SD = ceil(D / 1024).
 template <int NV, int SD>
 __device__ __forceinline__ void tile_site(const SiteStatic &st, const SiteDyn &dy, const double *x, int D, double *red, unsigned *xq, int xvd_t,
                                           bool publish_stats, TileCtl *tc, unsigned long long *tl)
@@ -181,7 +181,7 @@ template <> __device__ __forceinline__ void dma_unit_s<5>(const uint8_t *src, un
                  : "=&s"(keep) : "v"(voff), "s"(src + 4096), "s"(lds_dst + 4096u) : "memory");
 }
 
-// The loader wave of a tile-form kernel: units of S KiB (S k-blocks of one tile), in order.  Same rules as RingLoader (kernels.hip.h):
+// The loader wave of a tile-form kernel: units of S KiB (S k-blocks of one tile), in order.  The LDS-DMA rules (kernels.hip.h):
 // one asm statement per unit, vmcnt READ instead of waited on, every wait bounded -- and, because one wave's instruction issue IS the
 // stream's ceiling (the first version of this loader spent 50 instructions per unit and streamed at 23 KB/us per CU where the row
 // form's reaches 26: profiles/r05/tile_check.txt), ALL state scalar: the unit's address is an SGPR pair advanced by two scalar adds,

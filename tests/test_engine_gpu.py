@@ -372,14 +372,13 @@ def fault_libs(built, tmp_path_factory):
 
 
 
-@pytest.mark.parametrize("tile", ["0", "15"])
+@pytest.mark.parametrize("tile", ["15"])
 def test_a_lost_ring_hand_off_fails_the_call_instead_of_returning_garbage(fault_libs, tile):
-    """every wait of the LDS-ring kernels is bounded; one that gives up is recorded and reported (kernels.hip.h ring_report,
-    engine.hip device_check): a variant of the engine whose loader wave never issues a workgroup's last group
+    """every wait of the tile-form kernels' LDS ring is bounded; one that gives up is recorded and reported (kernels.hip.h ring_report,
+    engine.hip device_check): a variant of the engine whose loader wave never issues a workgroup's last pair of units
     (-DRWKV_TEST_DROP_GROUP=1, built here with hipcc) must fail the forward with RWKV_E_DEVICE, and the context must be usable
-    for error reporting afterwards -- no hang, no silently wrong logits.  Runs in a subprocess (RWKV_LIB selects the variant), once
-    with the row-form ring kernels (RWKV_TILE=0) and once with the tile-form kernels a 4096-wide model gets by default (their loader
-    loses its last pair of units in the same build)."""
+    for error reporting afterwards -- no hang, no silently wrong logits.  Runs in a subprocess (RWKV_LIB selects the variant) with
+    the tile-form kernels a 4096-wide model gets by default."""
     import subprocess
     import sys
     lib = fault_libs["drop"]
@@ -396,17 +395,31 @@ def test_a_lost_ring_hand_off_fails_the_call_instead_of_returning_garbage(fault_
         "except engine.RWKVError as e:\n"
         "    print('RWKVERROR', str(e)[-120:], '|', str(e)[:120])\n"
     )
-    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RWKV_LIB=lib, RWKV_RING="13", RWKV_TILE=tile), capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RWKV_LIB=lib, RWKV_TILE=tile), capture_output=True, text=True, timeout=600)
     assert "RWKVERROR" in out.stdout and "device-side wait gave up" in out.stdout and "status -3" in out.stdout, out.stdout[-400:] + out.stderr[-400:]
+
+
+def test_a_retired_environment_variable_is_reported_not_silently_ignored(built, monkeypatch, capfd):
+    """RWKV_RING selected the LDS-ring form of the row-form decode kernels, which is gone: a context created with it set still
+    loads and decodes, and says on stderr that the variable is ignored (engine.hip RETIRED_ENV)."""
+    monkeypatch.setenv("RWKV_RING", "13")
+    import torch
+    from rwkv_cpp_accelerated_amd import engine
+    L, D = 1, 768
+    m = engine.RWKV(resident=True)
+    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=3))
+    assert np.isfinite(np.array(m.forward(7)[: mf.VOCAB])).all()
+    m.close()
+    assert "RWKV_RING is retired and ignored" in capfd.readouterr().err
 
 
 @pytest.mark.parametrize("tile", ["0", "15"])
 def test_two_contexts_decoding_at_once_are_independent(built, tile, monkeypatch):
     """two contexts of one process, a stream and a host thread each, greedy-decoding AT THE SAME TIME: their kernels interleave on the CUs
-    (every kernel owns its CU's whole LDS for its lifetime and zeroes its ring's control block on entry): ids equal to the same decode
-    run alone, no RWKV_E_DEVICE from a lost hand-off."""
+    (every kernel owns its CU's whole LDS for its lifetime and a tile-form kernel zeroes its ring's control block on entry): ids equal to
+    the same decode run alone, no RWKV_E_DEVICE from a lost hand-off."""
     import threading
-    monkeypatch.setenv("RWKV_TILE", tile)       # "0": the row-form ring kernels; "15": the tile-form kernels a 4096-wide model gets by default
+    monkeypatch.setenv("RWKV_TILE", tile)       # "0": the row-form register kernels; "15": the tile-form kernels a 4096-wide model gets by default
     import torch
     from rwkv_cpp_accelerated_amd import engine
     L, D, steps = 4, 4096, 96

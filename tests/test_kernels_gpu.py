@@ -1,6 +1,6 @@
 """Per-kernel parity of the PRODUCTION decode kernels: a token is launched one kernel at a time through
 rwkv_debug_launch -- k_first, then k_att / k_attout / k_ffn_rk / k_ffnv of every layer, then k_head: exactly the launches of the
-captured token graph, in the form (row registers, row ring, 16-row tiles, 4-row tiles) the context runs each class in -- and after every
+captured token graph, in the form (row registers, 16-row tiles, 4-row tiles) the context runs each class in -- and after every
 launch its outputs are read back and compared with the oracle's piece for THAT kernel, evaluated on the kernel's OWN inputs as the
 engine holds them (the residual vector and the state it was handed):
 

@@ -2,7 +2,7 @@
 hipcc -save-temps): a compiler-inserted wait inside a loader wave's loop drains the DMA queue the compiler does not know about.
 usage: hipcc ... -save-temps=obj engine.hip; python tools/loader_waits.py [file.s]   (spans of S = 5 instances include consumer code: look at the context)"""
 import re,sys
-# for every ring kernel: list s_waitcnt vmcnt(N) with small N that sit between the first and the last LDS-DMA instruction of the kernel (the loader's code)
+# for every LDS-DMA kernel (tile form, chunk path): list s_waitcnt vmcnt(N) with small N that sit between the first and the last LDS-DMA instruction of the kernel (the loader's code)
 src=open(sys.argv[1] if len(sys.argv) > 1 else 'engine-hip-amdgcn-amd-amdhsa-gfx950.s').read().split('\n')
 name=None; body=[]
 def report(name, body):
