@@ -280,6 +280,37 @@ public:
         if (!residentState) pullState();
         return std::vector<unsigned long long>(ids.begin(), ids.end());
     }
+    // batched decode: first.size() independent streams, stream s on state slot s; ids[s * n + k] = stream s's pick at step k.
+    // In the host-authoritative mode the N slots are pushed before the call and pulled after it, as decodeGreedy does for slot 0.
+    std::vector<unsigned long long> decodeBatchGreedy(const std::vector<unsigned long long> &first, unsigned long long n)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> ft(first.begin(), first.end()), ids(first.size() * n);
+        if (!residentState) pushState();
+        rwkv_detail::check(rwkv_decode_batch_greedy(ctx_, ft.data(), ft.size(), n, ids.data()));
+        if (!residentState) pullState();
+        return std::vector<unsigned long long>(ids.begin(), ids.end());
+    }
+    // the same with the device sampler: stream s draws what decodeTypical(first[s], n, temp, tau, seeds[s]) draws
+    std::vector<unsigned long long> decodeBatchTypical(const std::vector<unsigned long long> &first, unsigned long long n,
+                                                       const std::vector<unsigned long long> &seeds, float temp = 0.9f, float tau = 0.8f,
+                                                       bool recipe = RWKV_TYPICAL_RECIPE != 0)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (seeds.size() != first.size()) throw std::runtime_error("need one seed per stream");
+        std::vector<uint64_t> ft(first.begin(), first.end()), sd(seeds.begin(), seeds.end()), ids(first.size() * n);
+        if (!residentState) pushState();
+        rwkv_detail::check(rwkv_decode_batch_typical(ctx_, ft.data(), ft.size(), n, temp, tau, sd.data(), recipe ? RWKV_SAMPLE_RECIPE : 0, ids.data()));
+        if (!residentState) pullState();
+        return std::vector<unsigned long long>(ids.begin(), ids.end());
+    }
+    // copy state slot src into slot dst (fork a prefilled prompt); the host copy too when it is the authoritative one
+    void copyState(unsigned long long dst, unsigned long long src)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        rwkv_detail::check(rwkv_state_copy(ctx_, dst, src));
+        if (!residentState) { RWKVState sub = state->getSubState(src); state->setSubState(sub, dst); }
+    }
     rwkv_ctx *handle() { return ctx_; }
 
     ~RWKV()

@@ -126,6 +126,32 @@ int rwkv_sample_typical(rwkv_ctx *ctx, uint64_t row, float temp, float tau, doub
 int rwkv_decode_typical(rwkv_ctx *ctx, uint64_t first_token, uint64_t n_tokens, float temp, float tau,
                         uint64_t seed, int flags, uint64_t *out_tokens);
 
+/* ---- batched decode: N independent streams, one weight pass per step (no reference counterpart: SURVEY.md 2) ----
+ * Device-side continuation of n_streams independent sequences: stream s runs on state slot s (PARRALEL mode's mapping,
+ * rwkv.cu:236-240), is fed first_tokens[s], then n_steps - 1 times its own previous pick -- per stream exactly the contract of
+ * rwkv_decode_greedy (logit 0 banned, ties -> lowest id, no winner -> 0).  out_tokens is host [n_streams][n_steps].  The logits of
+ * the LAST step remain in the device logits buffer, rows 0 .. n_streams - 1.
+ * n_streams == 1 runs rwkv_decode_greedy itself (the decode kernels on slot 0).  For n_streams >= 2 every step is the schedule of
+ * rwkv_forward(n_streams tokens, RWKV_MODE_PARRALEL) -- passes of <= 64 rows, the RWKV_SEQ_STAGES pipeline for more than one pass,
+ * the same kernels, so bit-identical logits -- except that the embedding reads the step's ids from the device, where the previous
+ * step's pick over all rows left them.  Inside the loop there is no host synchronisation and no host <-> device copy: one upload of
+ * first_tokens (and seeds), one download of all picks.  The picks and the per-row pick scratch belong to the context: allocated at
+ * the first call, grown to the largest n_streams x n_steps seen, counted by rwkv_resident_bytes, freed by rwkv_free.
+ * Status: RWKV_E_ARG for a NULL pointer, n_streams == 0 or > max_ctx, n_steps == 0 or > RWKV_MAX_DECODE_STEPS, a token id >= 50277
+ * or !(temp > 0); RWKV_E_STATE when not loaded, on a pipeline-stage context, or for n_streams >= 2 without the chunk path (env
+ * RWKV_SEQ=0 at load time, or max_ctx 1).  Every check runs before anything is launched: a rejected call leaves the state as it was. */
+#define RWKV_MAX_DECODE_STEPS 65536u
+int rwkv_decode_batch_greedy(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps,
+                             uint64_t *out_tokens);
+/* Same with the device sampler: stream s draws u_k = uniform(splitmix64(seeds[s] + k)) at step k, i.e. the draws that
+ * rwkv_decode_typical(seed = seeds[s]) makes; flags: RWKV_SAMPLE_RECIPE (logit 0 is always banned, as there).  One launch of each
+ * of the sampler's three kernels covers all n_streams rows per step. */
+int rwkv_decode_batch_typical(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps,
+                              float temp, float tau, const uint64_t *seeds, int flags, uint64_t *out_tokens);
+/* Device-to-device copy of the five state arrays of slot src_slot into slot dst_slot: fork a prompt prefilled on slot 0 into the
+ * slots of a batched decode.  RWKV_E_ARG for a slot >= max_ctx, RWKV_E_STATE when not loaded. */
+int rwkv_state_copy(rwkv_ctx *ctx, uint64_t dst_slot, uint64_t src_slot);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

@@ -259,8 +259,14 @@ struct rwkv_ctx {
     uint8_t *t_kvr = nullptr, *t_att = nullptr, *t_frk = nullptr, *t_fv = nullptr;
     int tile_th = 0, tile_s = 0, tile_tpc = 0;     // rows per tile, KiB per ring unit, tiles per row class and workgroup (0: no tile form at this width)
     unsigned *r8_kvr = nullptr, *r8_att = nullptr, *r8_frk = nullptr, *r8_fv = nullptr, *r8_head = nullptr;
+    // batched decode (rwkv_decode_batch_*): allocated at the first call, grown to the largest one seen, freed by rwkv_free
+    struct Grown { void *p = nullptr; size_t bytes = 0; };
+    Grown bd_ids;                                 // u64 [n seeds][n_steps + 1][n]: row 0 = the first tokens, row k + 1 = the picks of step k
+    Grown bd_val, bd_idx;                         // greedy partials [n][AM_SLICES] (k_argmax_rows)
+    Grown bd_part, bd_p, bd_pw, bd_key;           // sampler scratch per row [n][...] (sampler.hip.h)
+    std::vector<unsigned long long> bd_host;      // staging of the one upload and the one download
     std::vector<void *> allocs;
-    size_t alloc_bytes = 0;                       // device bytes behind `allocs` (rwkv_resident_bytes)
+    size_t alloc_bytes = 0;                       // device bytes behind `allocs` and the Grown buffers (rwkv_resident_bytes)
 };
 
 namespace {
@@ -939,7 +945,7 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
 // part: nullptr = the context's whole layer range on its stream with its own scratch; else layers [la, lb) on part->st with
 // scratch part->S (the two-stage software pipeline of rwkv_forward: the embedding belongs to the part that starts at l0, the
 // head to the part that ends at l1)
-struct ChunkPart { uint64_t la, lb; hipStream_t st; const SeqScratch *S; bool no_upload = false; };
+struct ChunkPart { uint64_t la, lb; hipStream_t st; const SeqScratch *S; bool no_upload = false; const unsigned long long *dtok = nullptr; };
 // a pass's token ids: host -> pinned ring slot -> the device slot of the pass's residual buffer (what k_seq_embed reads; the copy is
 // stream-ordered behind the embedding kernel of the pass that used the buffer before)
 int upload_chunk_tokens(rwkv_ctx *c, const uint64_t *tokens, int n, int buf, hipStream_t st)
@@ -969,8 +975,10 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
     double *x = c->sq_x[buf];
     if (first) {
         if (buf < 0 || buf >= SQ_RING) return fail(RWKV_E_ARG, "residual buffer %d out of range", buf);
-        if (!(part && part->no_upload)) { const int rcu = upload_chunk_tokens(c, tokens, n, buf, st); if (rcu) return rcu; }
-        unsigned long long *d = c->sq_tokens + (size_t)buf * SEQ_TM;
+        // part->dtok: the pass's ids are already on the device (the batched decode's picks of the previous step)
+        const bool dev = part && part->dtok;
+        if (!(part && part->no_upload) && !dev) { const int rcu = upload_chunk_tokens(c, tokens, n, buf, st); if (rcu) return rcu; }
+        const unsigned long long *d = dev ? part->dtok : c->sq_tokens + (size_t)buf * SEQ_TM;
         SeqEmbedArgs ea{c->embed, c->ln, d, x, D};
         k_seq_embed<<<dim3(n), dim3(NT), 0, st>>>(ea);
     }
@@ -1254,6 +1262,65 @@ int enqueue_pass(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, int 
     return 0;
 }
 
+// The chunk path's schedule of T >= 2 rows (rwkv_forward's; every step of rwkv_decode_batch_* runs it too): passes of <= 64 rows and,
+// for more than one pass, the software pipeline over the RWKV_SEQ_STAGES streams.  The token ids come from the host
+// (`tokens`) or, PARRALEL mode only, from the device array `dtok` ([T], e.g. the picks of the previous decode step).  Only enqueues:
+// the context's stream holds the result when it returns.
+int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *dtok, uint64_t T, int mode)
+{
+    if (dtok && mode != RWKV_MODE_PARRALEL) return fail(RWKV_E_ARG, "device token ids need PARRALEL mode");
+    // rows per weight pass: 64 (two halves sharing every weight fragment) for calls of more than 32 rows, else 32
+    const uint64_t CH = (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T;
+    const uint64_t nchunks = (T + CH - 1) / CH;
+    SeqScratch own;      // stage 0 (or the one-stream schedule) uses the context's own scratch
+    own.state = c->sq_state; own.y = c->sq_y; own.imgh = c->sq_imgh;
+    for (int k = 0; k < 3; k++) own.img[k] = c->sq_img[k];
+    own.qpart = c->sq_qpart; own.qparta = c->sq_qparta; own.qparth = c->sq_qparth; own.stat = c->sq_stat;
+    own.pk3 = c->sq_pk3; own.pk5 = c->sq_pk5; own.pk1 = c->sq_pk1;
+    int rc = 0;
+    if (nchunks >= 2 && (rc = split_setup(c)) == 0 && c->n_split >= 2) {
+        // Software pipeline over the chunks: stage k = an equal share of the layers (the last one with the head) on its
+        // own stream with its own scratch, stage k on chunk i while stage k - 1 is on chunk i + 1.  Every launch of this path
+        // costs ~4.5 us of start-up and tail whatever it moves; with independent kernel sequences on the GPU those run under the
+        // other stages' streams (7B, 512-token prompt: 9.1k -> 12k tokens/s with three stages).  A chunk's residual stream stays
+        // in its buffer (sq_x[i % n], updated in place by every stage); results are bit-identical to the one-stream schedule.
+        const int ns = c->n_split;
+        HIPCHK(hipEventRecord(c->sp_end, c->stream));                 // the other stages start behind whatever the context's stream holds
+        for (int k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(c->sp_stream[k], c->sp_end, 0));
+        uint64_t i = 0;
+        for (uint64_t t0 = 0; t0 < T && !rc; t0 += CH, i++) {
+            const int n = (int)(T - t0 < CH ? T - t0 : CH);
+            const int b = (int)(i % (uint64_t)ns);
+            for (int k = 0; k < ns && !rc; k++) {
+                hipStream_t st = c->sp_stream[k];
+                if (k == 0) { if (i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0)); }   // the last stage is done with this buffer (chunk i - ns)
+                else HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                                        // the stage before has handed chunk i over
+                ChunkPart part{split_point(c, k, ns), split_point(c, k + 1, ns), st, k == 0 ? &own : c->sp_scratch[k]};
+                if (k == 0 && dtok) part.dtok = dtok + t0;
+                const uint64_t *tk = (k == 0 && tokens) ? tokens + t0 : nullptr;
+                if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tk, n, t0, true, b, &part);
+                else rc = enqueue_pass(c, tk, n, t0, b, part);
+                HIPCHK(hipEventRecord(c->sp_done[k][b], st));
+            }
+        }
+        for (int k = 1; k < ns; k++) {                                // the context's stream owns the result again
+            HIPCHK(hipEventRecord(c->sp_end, c->sp_stream[k]));
+            HIPCHK(hipStreamWaitEvent(c->stream, c->sp_end, 0));
+        }
+        return rc;
+    }
+    if (rc) return rc;
+    for (uint64_t t0 = 0; t0 < T; t0 += CH) {
+        const int n = (int)(T - t0 < CH ? T - t0 : CH);
+        ChunkPart part{c->l0, c->l1, c->stream, &own};
+        if (dtok) part.dtok = dtok + t0;
+        if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tokens ? tokens + t0 : nullptr, n, t0, true, 0, &part);
+        else rc = enqueue_pass(c, tokens + t0, n, t0, 0, part);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 // Start of every entry point that launches kernels: the device error word belongs to ONE call.  An entry point that left early
 // (a failed HIP call) never consumed it, and a code raised then would surface -- attributed to the wrong operation -- from whatever
 // synchronises next; so it is cleared here.
@@ -1382,58 +1449,9 @@ int rwkv_forward(rwkv_ctx *c, const uint64_t *tokens, uint64_t T, int mode)
     HIPCHK(hipSetDevice(c->device));
     { const int rcp = begin_call(c); if (rcp) return rcp; }
     trim_pass_graphs(c);
-    if (T >= 2 && c->seq_ok && c->l0 == 0 && c->l1 == c->L) {   // prompt chunks (GPT) / batched decode step of T streams (PARRALEL): weights read once per <= 32 rows
-        // rows per weight pass: 64 (two halves sharing every weight fragment) for calls of more than 32 rows, else 32
-        const uint64_t CH = (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T;
-        const uint64_t nchunks = (T + CH - 1) / CH;
-        int rc = 0;
-        if (nchunks >= 2 && (rc = split_setup(c)) == 0 && c->n_split >= 2) {
-            // Software pipeline over the chunks: stage k = an equal share of the layers (the last one with the head) on its
-            // own stream with its own scratch, stage k on chunk i while stage k - 1 is on chunk i + 1.  Every launch of this path
-            // costs ~4.5 us of start-up and tail whatever it moves; with independent kernel sequences on the GPU those run under the
-            // other stages' streams (7B, 512-token prompt: 9.1k -> 12k tokens/s with three stages).  A chunk's residual stream stays
-            // in its buffer (sq_x[i % n], updated in place by every stage); results are bit-identical to the one-stream schedule.
-            const int ns = c->n_split;
-            SeqScratch own;      // stage 0 uses the context's own scratch
-            own.state = c->sq_state; own.y = c->sq_y; own.imgh = c->sq_imgh;
-            for (int k = 0; k < 3; k++) own.img[k] = c->sq_img[k];
-            own.qpart = c->sq_qpart; own.qparta = c->sq_qparta; own.qparth = c->sq_qparth; own.stat = c->sq_stat;
-            own.pk3 = c->sq_pk3; own.pk5 = c->sq_pk5; own.pk1 = c->sq_pk1;
-            HIPCHK(hipEventRecord(c->sp_end, c->stream));                 // the other stages start behind whatever the context's stream holds
-            for (int k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(c->sp_stream[k], c->sp_end, 0));
-            uint64_t i = 0;
-            for (uint64_t t0 = 0; t0 < T && !rc; t0 += CH, i++) {
-                const int n = (int)(T - t0 < CH ? T - t0 : CH);
-                const int b = (int)(i % (uint64_t)ns);
-                for (int k = 0; k < ns && !rc; k++) {
-                    hipStream_t st = c->sp_stream[k];
-                    if (k == 0) { if (i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0)); }   // the last stage is done with this buffer (chunk i - ns)
-                    else HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                                        // the stage before has handed chunk i over
-                    const ChunkPart part{split_point(c, k, ns), split_point(c, k + 1, ns), st, k == 0 ? &own : c->sp_scratch[k]};
-                    if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, k == 0 ? tokens + t0 : nullptr, n, t0, true, b, &part);
-                    else rc = enqueue_pass(c, k == 0 ? tokens + t0 : nullptr, n, t0, b, part);
-                    HIPCHK(hipEventRecord(c->sp_done[k][b], st));
-                }
-            }
-            for (int k = 1; k < ns; k++) {                                // the context's stream owns the result again
-                HIPCHK(hipEventRecord(c->sp_end, c->sp_stream[k]));
-                HIPCHK(hipStreamWaitEvent(c->stream, c->sp_end, 0));
-            }
-            if (rc) return rc;
-        } else {
-            if (rc) return rc;
-            SeqScratch own;
-            own.state = c->sq_state; own.y = c->sq_y; own.imgh = c->sq_imgh;
-            for (int k = 0; k < 3; k++) own.img[k] = c->sq_img[k];
-            own.qpart = c->sq_qpart; own.qparta = c->sq_qparta; own.qparth = c->sq_qparth; own.stat = c->sq_stat;
-            own.pk3 = c->sq_pk3; own.pk5 = c->sq_pk5; own.pk1 = c->sq_pk1;
-            for (uint64_t t0 = 0; t0 < T; t0 += CH) {
-                const int n = (int)(T - t0 < CH ? T - t0 : CH);
-                if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tokens + t0, n, t0, true);
-                else rc = enqueue_pass(c, tokens + t0, n, t0, 0, ChunkPart{c->l0, c->l1, c->stream, &own});
-                if (rc) return rc;
-            }
-        }
+    if (T >= 2 && c->seq_ok && c->l0 == 0 && c->l1 == c->L) {   // prompt chunks (GPT) / batched decode step of T streams (PARRALEL): weights read once per <= 64 rows
+        const int rc = enqueue_rows(c, tokens, nullptr, T, mode);
+        if (rc) return rc;
         HIPCHK(hipStreamSynchronize(c->stream));
         return 0;
     }
@@ -1533,23 +1551,34 @@ int rwkv_decode_greedy(rwkv_ctx *c, uint64_t first_token, uint64_t n, uint64_t *
 }
 
 namespace {
-int launch_typical(rwkv_ctx *c, int row, float temp, float tau, double u, uint64_t seed, bool use_seed, int flags, bool feedback)
+// the sampler's arguments common to every launch: mode and exponent from temp / flags, the context's single-row scratch
+TypicalArgs typical_args(rwkv_ctx *c, float temp, float tau, int flags)
 {
-    const bool ban0 = (flags & RWKV_SAMPLE_BAN0) != 0;
-    TypicalArgs a;
+    TypicalArgs a{};
     // default: what typical.h computes -- no cut (typical.h:50 assigns into a temporary), integer exponent
     // uint8(1/temp) (nc::power, typical.h:52); RWKV_SAMPLE_RECIPE: the documented recipe
     a.recipe = (flags & RWKV_SAMPLE_RECIPE) ? 1 : 0;
     if (a.recipe) a.expo = temp == 1.0f ? 1.0 : 1.0 / (double)temp;
     else { const double e = 1.0 / (double)temp; a.expo = temp == 1.0f ? 1.0 : (e >= 255.0 ? 255.0 : (double)(unsigned char)e); }
-    a.logits = c->logits; a.row = row; a.ctl = c->ctl; a.gen = c->gen; a.gen_cap = c->gen_cap;
-    a.temp = temp; a.tau = tau; a.u = u; a.seed = seed; a.use_seed = use_seed ? 1 : 0; a.ban0 = ban0 ? 1 : 0;
-    a.feedback = feedback ? 1 : 0; a.pick = c->pick; a.part = c->ts_part; a.p = c->ts_p; a.pw = c->ts_pw; a.key = c->ts_key;
-    k_typical_stats<<<dim3(TS_G), dim3(TS_GT), 0, c->stream>>>(a);
-    k_typical_keys<<<dim3(TS_G), dim3(TS_GT), 0, c->stream>>>(a);
-    k_typical<<<dim3(1), dim3(TS_NT), 0, c->stream>>>(a);
+    a.logits = c->logits; a.ctl = c->ctl; a.gen = c->gen; a.gen_cap = c->gen_cap;
+    a.temp = temp; a.tau = tau; a.ban0 = (flags & RWKV_SAMPLE_BAN0) ? 1 : 0; a.step = -1; a.seeds = nullptr;
+    a.pick = c->pick; a.part = c->ts_part; a.p = c->ts_p; a.pw = c->ts_pw; a.key = c->ts_key;
+    return a;
+}
+// the sampler's three launches over `rows` logits rows (a.row onwards), each row with its own scratch slice and pick
+int enqueue_typical(rwkv_ctx *c, const TypicalArgs &a, unsigned rows)
+{
+    k_typical_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
+    k_typical_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
+    k_typical<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(a);
     HIPCHK(hipGetLastError());
     return 0;
+}
+int launch_typical(rwkv_ctx *c, int row, float temp, float tau, double u, uint64_t seed, bool use_seed, int flags, bool feedback)
+{
+    TypicalArgs a = typical_args(c, temp, tau, flags);
+    a.row = row; a.u = u; a.seed = seed; a.use_seed = use_seed ? 1 : 0; a.feedback = feedback ? 1 : 0;
+    return enqueue_typical(c, a, 1);
 }
 } // namespace
 
@@ -1590,6 +1619,113 @@ int rwkv_decode_typical(rwkv_ctx *c, uint64_t first_token, uint64_t n, float tem
     return device_check(c);
 }
 
+namespace {
+// grow a batched-decode buffer to `bytes` (contents are not kept); counted in rwkv_resident_bytes
+int bd_grow(rwkv_ctx *c, rwkv_ctx::Grown &g, size_t bytes)
+{
+    if (bytes <= g.bytes) return 0;
+    if (g.p) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        HIPCHK(hipFree(g.p));
+        c->alloc_bytes -= g.bytes;
+        g.p = nullptr; g.bytes = 0;
+    }
+    HIPCHK(hipMalloc(&g.p, bytes));
+    g.bytes = bytes; c->alloc_bytes += bytes;
+    return 0;
+}
+
+// rwkv_decode_batch_greedy / _typical: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
+// else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
+// pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.
+int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, bool typical, float temp, float tau,
+                 const uint64_t *seeds, int flags, uint64_t *out_tokens)
+{
+    if (!c || !first_tokens || !out_tokens || (typical && !seeds)) return fail(RWKV_E_ARG, "NULL argument");
+    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (c->l0 != 0 || c->l1 != c->L) return fail(RWKV_E_STATE, "needs a whole-model context (a pipeline stage has no embedding / head of its own)");
+    if (N == 0 || N > c->maxT) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu (max context)", (unsigned long long)c->maxT);
+    if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
+    for (uint64_t s = 0; s < N; s++)
+        if (first_tokens[s] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id %llu out of range", (unsigned long long)first_tokens[s]);
+    if (typical && !(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
+    if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0 or max context 1)");
+    if (N == 1)       // the decode path's kernels on slot 0
+        return typical ? rwkv_decode_typical(c, first_tokens[0], n_steps, temp, tau, seeds[0], flags, out_tokens)
+                       : rwkv_decode_greedy(c, first_tokens[0], n_steps, out_tokens);
+    HIPCHK(hipSetDevice(c->device));
+    { const int rcp = begin_call(c); if (rcp) return rcp; }
+    int rc = bd_grow(c, c->bd_ids, sizeof(unsigned long long) * N * (n_steps + 2));
+    if (!rc && !typical) rc = bd_grow(c, c->bd_val, sizeof(float) * N * AM_SLICES);
+    if (!rc && !typical) rc = bd_grow(c, c->bd_idx, sizeof(unsigned) * N * AM_SLICES);
+    if (!rc && typical) rc = bd_grow(c, c->bd_part, sizeof(double) * N * TS_PART_ROW);
+    if (!rc && typical) rc = bd_grow(c, c->bd_p, sizeof(float) * N * TS_ROW);
+    if (!rc && typical) rc = bd_grow(c, c->bd_pw, sizeof(float) * N * TS_ROW);
+    if (!rc && typical) rc = bd_grow(c, c->bd_key, sizeof(unsigned) * N * TS_ROW);
+    if (rc) return rc;
+    unsigned long long *dseeds = static_cast<unsigned long long *>(c->bd_ids.p), *ids = dseeds + N;   // ids row k: the ids fed at step k
+    c->bd_host.assign(N * (n_steps + 1), 0ull);
+    for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = typical ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
+    HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
+    TypicalArgs ta{};
+    if (typical) {
+        ta = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
+        ta.row = 0; ta.use_seed = 1; ta.seeds = dseeds; ta.feedback = 0;
+        ta.part = static_cast<double *>(c->bd_part.p); ta.p = static_cast<float *>(c->bd_p.p);
+        ta.pw = static_cast<float *>(c->bd_pw.p); ta.key = static_cast<unsigned *>(c->bd_key.p);
+    }
+    for (uint64_t k = 0; k < n_steps && !rc; k++) {
+        rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL);       // logits rows 0 .. N - 1, state slots 0 .. N - 1
+        if (rc) break;
+        unsigned long long *next = ids + (k + 1) * N;
+        if (typical) {
+            ta.step = (int)k; ta.pick = next;
+            rc = enqueue_typical(c, ta, (unsigned)N);
+        } else {
+            float *val = static_cast<float *>(c->bd_val.p);
+            unsigned *idx = static_cast<unsigned *>(c->bd_idx.p);
+            k_argmax_rows<<<dim3(AM_SLICES, (unsigned)N), dim3(AM_NT), 0, c->stream>>>(c->logits, val, idx);
+            k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
+            HIPCHK(hipGetLastError());
+        }
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * n_steps, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    rc = device_check(c);
+    if (rc) return rc;
+    for (uint64_t k = 0; k < n_steps; k++)              // [step][stream] -> [stream][step]
+        for (uint64_t s = 0; s < N; s++) out_tokens[s * n_steps + k] = c->bd_host[k * N + s];
+    return 0;
+}
+} // namespace
+
+int rwkv_decode_batch_greedy(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, uint64_t *out_tokens)
+{
+    return decode_batch(c, first_tokens, n_streams, n_steps, false, 1.0f, 0.0f, nullptr, 0, out_tokens);
+}
+
+int rwkv_decode_batch_typical(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, float temp, float tau,
+                              const uint64_t *seeds, int flags, uint64_t *out_tokens)
+{
+    return decode_batch(c, first_tokens, n_streams, n_steps, true, temp, tau, seeds, flags, out_tokens);
+}
+
+int rwkv_state_copy(rwkv_ctx *c, uint64_t dst, uint64_t src)
+{
+    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
+    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (dst >= c->maxT || src >= c->maxT)
+        return fail(RWKV_E_ARG, "state slot out of range (dst %llu, src %llu, max context %llu)", (unsigned long long)dst, (unsigned long long)src, (unsigned long long)c->maxT);
+    if (dst == src) return 0;
+    const size_t n = (size_t)c->L * c->D;
+    HIPCHK(hipSetDevice(c->device));
+    for (int s = 0; s < 5; s++)
+        HIPCHK(hipMemcpyAsync(c->state[s] + dst * n, c->state[s] + src * n, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return device_check(c);
+}
+
 void rwkv_free(rwkv_ctx *c)
 {
     if (!c) return;
@@ -1599,6 +1735,7 @@ void rwkv_free(rwkv_ctx *c)
     if (c->g_greedy) { (void)hipGraphExecDestroy(c->g_greedy); c->g_greedy = nullptr; }
     rwkv_pipe_free(c);        // (no graphs left to re-capture)
     for (void *p : c->allocs) (void)hipFree(p);
+    for (rwkv_ctx::Grown *g : {&c->bd_ids, &c->bd_val, &c->bd_idx, &c->bd_part, &c->bd_p, &c->bd_pw, &c->bd_key}) if (g->p) (void)hipFree(g->p);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);

@@ -1297,6 +1297,20 @@ struct HeadArgs {
     int D;
 };
 
+// the greedy pick's order, shared by every argmax here: a larger logit wins, equal logits go to the lower id, and NaN never
+// wins (every comparison with it is false)
+__device__ __forceinline__ bool am_better(float v, unsigned i, float best, unsigned besti) { return v > best || (v == best && i < besti); }
+// fold (best, besti) over the 64 lanes of a wave (every lane ends with the wave's winner)
+__device__ __forceinline__ void am_wave_fold(float &best, unsigned &besti)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const float ov = __shfl_xor(best, m, 64);
+        const unsigned oi = __shfl_xor(besti, m, 64);
+        if (am_better(ov, oi, best, besti)) { best = ov; besti = oi; }
+    }
+}
+
 // ln_out site -> head dequant-GEMV -> logits (rwkv.cu:585-589); also per-workgroup argmax partials
 template <int R> struct HeadIn { unsigned rsr[R]; int row0, shift; };
 template <int S, int NB, int R = RWKV_HEAD_R>
@@ -1340,7 +1354,7 @@ __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
             const int i = in.row0 + r;
             const float val = row_value(T[r], in.rsr[r], sc) + Sf;
             if (lane == r && r >= in.shift) lg[i] = val;
-            if (i != 0 && (val > best || (val == best && (unsigned)i < besti))) { best = val; besti = (unsigned)i; }
+            if (i != 0 && am_better(val, (unsigned)i, best, besti)) { best = val; besti = (unsigned)i; }
         }
     };
     u32x4 wA[R][S], wB[R][S];
@@ -1355,7 +1369,7 @@ __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
     __syncthreads();
     if (threadIdx.x == 0) {
         for (int i = 1; i < NW; i++)
-            if (bval[i] > best || (bval[i] == best && bidx[i] < besti)) { best = bval[i]; besti = bidx[i]; }
+            if (am_better(bval[i], bidx[i], best, besti)) { best = bval[i]; besti = bidx[i]; }
         a.blk_val[blockIdx.x] = best;
         a.blk_idx[blockIdx.x] = besti;
     }
@@ -1371,14 +1385,9 @@ __global__ void k_argmax_finish(const float *blk_val, const unsigned *blk_idx, i
     for (int i = threadIdx.x; i < n; i += 64) {
         const float v = blk_val[i];
         const unsigned id = blk_idx[i];
-        if (v > best || (v == best && id < besti)) { best = v; besti = id; }
+        if (am_better(v, id, best, besti)) { best = v; besti = id; }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const float ov = __shfl_xor(best, m, 64);
-        const unsigned oi = __shfl_xor(besti, m, 64);
-        if (ov > best || (ov == best && oi < besti)) { best = ov; besti = oi; }
-    }
+    am_wave_fold(best, besti);
     if (threadIdx.x == 0) {
         // all-NaN / all -inf logits leave no winner (the reference's un-stabilised WKV can overflow with unusual
         // weights): feed token 0 like the sampler's fallback instead of indexing the embedding out of bounds
@@ -1388,6 +1397,59 @@ __global__ void k_argmax_finish(const float *blk_val, const unsigned *blk_idx, i
         ctl->token = besti;
         ctl->step = st + 1;
     }
+}
+
+// ---- the greedy pick over N logits rows (batched decode, rwkv_decode_batch_greedy) ----
+// k_argmax_rows, grid (AM_SLICES, rows): workgroup (p, r) scans slice p of row r's 16-byte aligned body with float4 loads -- a row is
+// 201 108 bytes, so row r starts 4 r bytes past a 16-byte boundary -- and slice 0 also the <= 3 elements in front of the body and the
+// <= 3 behind it; id 0 is banned as in k_head.  A (slice, row) grid keeps every CU busy (16 x 32 workgroups at N = 32) where one
+// workgroup per row would leave most of them idle.  k_argmax_rows_finish, one wave per row: folds the row's partials into ids[r]
+// (no winner -- all logits NaN -- gives token 0, as k_argmax_finish).
+constexpr int AM_SLICES = 16;
+constexpr int AM_NT = 256;
+static_assert(AM_SLICES <= 64, "one lane per partial in the finish");
+__global__ __launch_bounds__(AM_NT) void k_argmax_rows(const float *__restrict__ logits, float *__restrict__ part_val, unsigned *__restrict__ part_idx)
+{
+    __shared__ float sv[AM_NT / 64];
+    __shared__ unsigned si[AM_NT / 64];
+    const int V = (int)VOCAB;
+    const float *lg = logits + (size_t)blockIdx.y * V;
+    const int h = (int)(((16u - ((unsigned)(uintptr_t)lg & 15u)) & 15u) >> 2);   // elements in front of the first 16-byte boundary
+    const int nv = (V - h) >> 2;                                                  // float4s of the aligned body
+    const f32x4 *body = reinterpret_cast<const f32x4 *>(lg + h);
+    float best = -INFINITY;
+    unsigned besti = 0xffffffffu;
+    const int v1 = block_hi(nv);
+#pragma unroll 4
+    for (int v = block_lo(nv) + (int)threadIdx.x; v < v1; v += AM_NT) {      // ~3 float4 per thread: all of them in flight
+        const f32x4 q = body[v];
+        const unsigned i = (unsigned)(h + 4 * v);
+#pragma unroll
+        for (int k = 0; k < 4; k++)
+            if (i + k != 0u && am_better(q[k], i + k, best, besti)) { best = q[k]; besti = i + k; }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 8) {      // head [0, h) on threads 0..3, tail [h + 4 nv, V) on threads 4..7
+        const int i = threadIdx.x < 4 ? (int)threadIdx.x : h + 4 * nv + (int)threadIdx.x - 4;
+        if (i != 0 && i < (threadIdx.x < 4 ? h : V) && am_better(lg[i], (unsigned)i, best, besti)) { best = lg[i]; besti = (unsigned)i; }
+    }
+    am_wave_fold(best, besti);
+    if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = best; si[threadIdx.x >> 6] = besti; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < AM_NT / 64; w++)
+            if (am_better(sv[w], si[w], best, besti)) { best = sv[w]; besti = si[w]; }
+        part_val[blockIdx.y * AM_SLICES + blockIdx.x] = best;
+        part_idx[blockIdx.y * AM_SLICES + blockIdx.x] = besti;
+    }
+}
+__global__ __launch_bounds__(64) void k_argmax_rows_finish(const float *__restrict__ part_val, const unsigned *__restrict__ part_idx, unsigned long long *__restrict__ ids)
+{
+    const int lane = threadIdx.x;
+    float best = -INFINITY;
+    unsigned besti = 0xffffffffu;
+    if (lane < AM_SLICES) { best = part_val[blockIdx.x * AM_SLICES + lane]; besti = part_idx[blockIdx.x * AM_SLICES + lane]; }
+    am_wave_fold(best, besti);
+    if (lane == 0) ids[blockIdx.x] = besti < VOCAB ? besti : 0u;
 }
 
 // ------------------------------------------------------------------------------------------

@@ -14,6 +14,8 @@
 // f32, every sum in f64) and k_typical (one workgroup of 1024 threads: select, weights, draw).  The draw is the inverse CDF in token order for a uniform
 // u supplied by the caller or derived from (seed, step) with splitmix64 -- include/rwkv_sampler.h has the
 // same deterministic draw on the host (typical_u), which is what the parity test compares against.
+// One launch covers `rows` consecutive logits rows (blockIdx.y = row, each with its own slice of the scratch arrays
+// and its own pick): the batched decode samples all of its streams with the same three launches.
 #pragma once
 #include "kernels.hip.h"
 
@@ -25,10 +27,12 @@ constexpr int TS_HIST = 4096;              // mass-histogram bins of a radix-sel
 constexpr int TS_G = 64;                   // workgroups of the two element-wise kernels
 constexpr int TS_GT = 256;                 // threads of those
 static_assert(TS_NT * TS_PER >= (int)VOCAB, "sampler tiling must cover the vocabulary");
+constexpr size_t TS_PART_ROW = (size_t)TS_G * 3;           // doubles of `part` per row
+constexpr size_t TS_ROW = (size_t)TS_NT * TS_PER;          // elements of `p` / `key` / `pw` per row
 
 struct TypicalArgs {
     const float *logits;          // [rows][V]
-    int row;                      // logits row; < 0: ctl->out_row
+    int row;                      // logits row of blockIdx.y = 0 (< 0: ctl->out_row); blockIdx.y = r samples the row r behind it
     Ctl *ctl;                     // token / step feedback (device-side generation loop)
     unsigned long long *gen;      // generated ids, gen[step]
     unsigned gen_cap;
@@ -37,17 +41,22 @@ struct TypicalArgs {
     double expo;                  // the exponent applied to p
     double u;                     // uniform in [0, 1) when use_seed == 0
     unsigned long long seed;      // else u = uniform(splitmix64(seed + step))
+    const unsigned long long *seeds;   // per-row seeds (device, [rows]); nullptr: `seed` for every row
+    int step;                     // the step of the draw; < 0: ctl->step
     int use_seed;
     int ban0;                     // logits[0] = -99 before sampling (storygen.cpp:66)
     int feedback;                 // write the pick into ctl->token and advance ctl->step
-    unsigned long long *pick;     // the sampled id (host-visible copy source)
-    double *part;                 // [TS_G][3] per-workgroup (max, sum exp(l - max), sum exp(l - max) (l - max))
-    float *p;                     // [TS_NT * TS_PER] probabilities, position (i % TS_PER) * TS_NT + i / TS_PER for token i
+    unsigned long long *pick;     // [rows] the sampled ids (nullptr: none)
+    double *part;                 // [rows][TS_G][3] per-workgroup (max, sum exp(l - max), sum exp(l - max) (l - max))
+    float *p;                     // [rows][TS_NT * TS_PER] probabilities, position (i % TS_PER) * TS_NT + i / TS_PER for token i
     unsigned *key;                // same layout: bit patterns of |-log p - H|
     float *pw;                    // same layout: p^(1/temp) (typical.h:49-52), zeroed for the tokens that are cut
 };
 
-__device__ __forceinline__ const float *ts_row(const TypicalArgs &a) { return a.logits + (size_t)(a.row >= 0 ? (unsigned)a.row : a.ctl->out_row) * VOCAB; }
+__device__ __forceinline__ const float *ts_row(const TypicalArgs &a) { return a.logits + (size_t)((a.row >= 0 ? (unsigned)a.row : a.ctl->out_row) + blockIdx.y) * VOCAB; }
+// this row's slices of the scratch arrays
+__device__ __forceinline__ double *ts_part(const TypicalArgs &a) { return a.part + blockIdx.y * TS_PART_ROW; }
+__device__ __forceinline__ size_t ts_off(int pos) { return blockIdx.y * TS_ROW + (size_t)pos; }
 __device__ __forceinline__ float ts_logit(const TypicalArgs &a, const float *lg, int i) { return (a.ban0 && i == 0) ? -99.0f : lg[i]; }
 
 // (1) per-workgroup online-softmax partials over a slice of the vocabulary
@@ -81,7 +90,8 @@ __global__ __launch_bounds__(TS_GT) void k_typical_stats(TypicalArgs a)
     if (threadIdx.x == 0) {
         double tz = 0.0, ts = 0.0;
         for (int k = 0; k < TS_GT / 64; k++) { tz += red[2 * k]; ts += red[2 * k + 1]; }
-        a.part[blockIdx.x * 3 + 0] = (double)mx[0]; a.part[blockIdx.x * 3 + 1] = tz; a.part[blockIdx.x * 3 + 2] = ts;
+        double *part = ts_part(a);
+        part[blockIdx.x * 3 + 0] = (double)mx[0]; part[blockIdx.x * 3 + 1] = tz; part[blockIdx.x * 3 + 2] = ts;
     }
 }
 
@@ -89,7 +99,8 @@ __global__ __launch_bounds__(TS_GT) void k_typical_stats(TypicalArgs a)
 __device__ __forceinline__ void ts_combine(const TypicalArgs &a, double &M, double &logZ, double &H)
 {
     const int lane = threadIdx.x & 63;
-    const double m = lane < TS_G ? a.part[lane * 3] : -INFINITY, z = lane < TS_G ? a.part[lane * 3 + 1] : 0.0, sl = lane < TS_G ? a.part[lane * 3 + 2] : 0.0;
+    const double *part = ts_part(a);
+    const double m = lane < TS_G ? part[lane * 3] : -INFINITY, z = lane < TS_G ? part[lane * 3 + 1] : 0.0, sl = lane < TS_G ? part[lane * 3 + 2] : 0.0;
     double mm = m;
     for (int off = 32; off >= 1; off >>= 1) mm = fmax(mm, __shfl_xor(mm, off, 64));
     const double sc = lane < TS_G ? exp(m - mm) : 0.0;
@@ -109,14 +120,14 @@ __global__ __launch_bounds__(TS_GT) void k_typical_keys(TypicalArgs a)
     const double it = a.expo;
     for (int i = i0 + threadIdx.x; i < i1; i += TS_GT) {
         const double nl = (M - (double)ts_logit(a, lg, i)) + logZ;          // -log p_i
-        const int pos = (i % TS_PER) * TS_NT + i / TS_PER;
+        const size_t pos = ts_off((i % TS_PER) * TS_NT + i / TS_PER);
         a.p[pos] = (float)exp(-nl);
         a.pw[pos] = it == 1.0 ? (float)exp(-nl) : it == 0.0 ? 1.0f : (float)exp(-nl * it);   // p^expo (p^0 = 1 even for p = 0, as nc::power), here: 64 workgroups share the exponentials
         a.key[pos] = __float_as_uint((float)fabs(nl - H));                  // typical.h:32
     }
     if (blockIdx.x == 0)       // padding positions: tokens V .. TS_NT * TS_PER - 1 carry no mass and the largest key
         for (int i = V + threadIdx.x; i < TS_NT * TS_PER; i += TS_GT) {
-            const int pos = (i % TS_PER) * TS_NT + i / TS_PER;
+            const size_t pos = ts_off((i % TS_PER) * TS_NT + i / TS_PER);
             a.p[pos] = 0.f; a.pw[pos] = 0.f; a.key[pos] = 0x7f800000u;
         }
 }
@@ -145,6 +156,9 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
     __shared__ double sel_before;
     __shared__ unsigned pick_s;
     const int t = threadIdx.x, i0 = t * TS_PER;
+    const unsigned *key = a.key + blockIdx.y * TS_ROW;     // this row's slices
+    const float *p = a.p + blockIdx.y * TS_ROW;
+    float *pw = a.pw + blockIdx.y * TS_ROW;
 
     // thr = min { v : sum_{key <= v} p >= tau }, found as a bit pattern (monotone for non-negative floats) by a
     // most-significant-digit-first radix select over mass histograms in LDS: 12 + 12 + 8 bits.  Tokens whose
@@ -162,8 +176,8 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         // unrolled by 10: twenty loads in flight per thread (one load per trip would expose an L2 latency per token)
 #pragma unroll 10
         for (int k = 0; k < TS_PER; k++) {
-            const unsigned kb = a.key[k * TS_NT + t];
-            const float pk = a.p[k * TS_NT + t];
+            const unsigned kb = key[k * TS_NT + t];
+            const float pk = p[k * TS_NT + t];
             const bool in = pass == 0 || (kb >> (shift + bits)) == (prefix >> (shift + bits));
             if (in && pk > 1e-30f) __hip_atomic_fetch_add(&hist[(kb >> shift) & (nb - 1)], (double)pk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
@@ -202,8 +216,8 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
     double wsum = 0.0;
 #pragma unroll 10
     for (int k = 0; k < TS_PER; k++) {
-        const float w = a.key[k * TS_NT + t] <= thr ? a.pw[k * TS_NT + t] : 0.f;
-        a.pw[k * TS_NT + t] = w;                       // own positions only
+        const float w = key[k * TS_NT + t] <= thr ? pw[k * TS_NT + t] : 0.f;
+        pw[k * TS_NT + t] = w;                       // own positions only
         wsum += (double)w;
     }
     scan[t] = wsum;
@@ -217,7 +231,9 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
     const double total = scan[TS_NT - 1], before = scan[t] - wsum;
     double u = a.u;
     if (a.use_seed) {
-        unsigned long long x = a.seed + (unsigned long long)a.ctl->step + 0x9E3779B97F4A7C15ull;   // splitmix64
+        const unsigned long long seed = a.seeds ? a.seeds[blockIdx.y] : a.seed;
+        const unsigned long long step = a.step >= 0 ? (unsigned long long)a.step : (unsigned long long)a.ctl->step;
+        unsigned long long x = seed + step + 0x9E3779B97F4A7C15ull;   // splitmix64
         x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
         x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
         x ^= x >> 31;
@@ -232,7 +248,7 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         int sel = -1, lastkept = -1;
 #pragma unroll 10
         for (int k = 0; k < TS_PER; k++) {
-            const float w = a.pw[k * TS_NT + t];
+            const float w = pw[k * TS_NT + t];
             if (w > 0.f) { c += (double)w; lastkept = i0 + k; if (sel < 0 && target < c) sel = i0 + k; }
         }
         if (sel < 0) sel = lastkept;               // rounding at the upper edge of this thread's range
@@ -244,7 +260,7 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         if (sel == 0xffffffffu) {                  // target == total by rounding, or a degenerate distribution
             sel = 0;
         }
-        if (a.pick) *a.pick = sel;
+        if (a.pick) a.pick[blockIdx.y] = sel;
         if (a.feedback) {
             const unsigned st = a.ctl->step;
             if (st < a.gen_cap) a.gen[st] = sel;

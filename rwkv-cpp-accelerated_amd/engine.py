@@ -30,6 +30,7 @@ ABI_SYMBOLS = [
     "rwkv_bytes_per_token", "rwkv_profile_token", "rwkv_debug_launch", "rwkv_debug_read", "rwkv_debug_write", "rwkv_debug_grid", "rwkv_debug_timeline", "rwkv_profile_batched", "rwkv_abi_version", "rwkv_resident_bytes", "rwkv_decode_form", "rwkv_set_layer_range", "rwkv_stage_forward", "rwkv_x_device", "rwkv_sample_typical", "rwkv_decode_typical",
     "rwkv_stage_chunk", "rwkv_xseq_device", "rwkv_xseq_copy", "rwkv_sync", "rwkv_pipe_rccl_path", "rwkv_pipe_unique_id", "rwkv_pipe_init", "rwkv_pipe_decode", "rwkv_pipe_decode_streams", "rwkv_pipe_profile", "rwkv_pipe_hop_stats",
     "rwkv_pipe_prefill", "rwkv_pipe_free", "rwkv_tensor_device", "rwkv_pipe_info", "rwkv_pipe_decode_dual",
+    "rwkv_decode_batch_greedy", "rwkv_decode_batch_typical", "rwkv_state_copy",
 ]
 
 _lib = None
@@ -97,6 +98,10 @@ def lib():
     L.rwkv_pipe_info.argtypes = [vp, C.c_char_p, u64]; L.rwkv_pipe_info.restype = i32
     L.rwkv_pipe_decode_dual.argtypes = [vp, C.POINTER(u64), u64, C.POINTER(u64)]; L.rwkv_pipe_decode_dual.restype = i32
     L.rwkv_tensor_device.argtypes = [vp, i32]; L.rwkv_tensor_device.restype = vp
+    L.rwkv_decode_batch_greedy.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(u64)]; L.rwkv_decode_batch_greedy.restype = i32
+    L.rwkv_decode_batch_typical.argtypes = [vp, C.POINTER(u64), u64, u64, C.c_float, C.c_float, C.POINTER(u64), i32, C.POINTER(u64)]
+    L.rwkv_decode_batch_typical.restype = i32
+    L.rwkv_state_copy.argtypes = [vp, u64, u64]; L.rwkv_state_copy.restype = i32
     _lib = L
     return L
 
@@ -353,6 +358,44 @@ class RWKV:
         if not self.resident:
             self.pull_state(1)
         return np.frombuffer(out, dtype=np.uint64).copy()
+
+    # -- batched decode: N streams on state slots 0 .. N - 1 ------------------------------------
+    def _decode_batch(self, first_tokens, n_steps: int, call):
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        ft = [int(t) for t in first_tokens]
+        n = len(ft)
+        out = (C.c_uint64 * max(1, n * n_steps))()
+        if not self.resident and 0 < n <= self.maxContext:
+            self.push_state(n)          # host state is authoritative: continue the N slots from it ...
+        _chk(call((C.c_uint64 * max(1, n))(*ft), n, out))
+        if not self.resident:
+            self.pull_state(n)          # ... and leave them where the generated tokens ended
+        return np.frombuffer(out, dtype=np.uint64)[: n * n_steps].reshape(n, n_steps).copy()
+
+    def decode_batch_greedy(self, first_tokens, n_steps: int) -> np.ndarray:
+        """device-side greedy continuation of len(first_tokens) independent streams (stream s on state slot s, logit 0 banned);
+        returns the picked ids [N][n_steps]"""
+        return self._decode_batch(first_tokens, n_steps, lambda ft, n, out: lib().rwkv_decode_batch_greedy(self._h, ft, n, n_steps, out))
+
+    def decode_batch_typical(self, first_tokens, n_steps: int, temp: float = 0.9, tau: float = 0.8, seeds=None, recipe: bool = False) -> np.ndarray:
+        """the same with the device sampler: stream s draws what decode_typical(seed=seeds[s]) draws (default seeds: 0 .. N - 1)"""
+        sd = list(range(len(first_tokens))) if seeds is None else [int(x) for x in seeds]
+        if len(sd) != len(first_tokens):
+            raise ValueError("need one seed per stream")
+        arr = (C.c_uint64 * max(1, len(sd)))(*sd)
+        return self._decode_batch(first_tokens, n_steps, lambda ft, n, out: lib().rwkv_decode_batch_typical(
+            self._h, ft, n, n_steps, float(temp), float(tau), arr, SAMPLE_RECIPE if recipe else 0, out))
+
+    def copy_state(self, dst: int, src: int):
+        """copy state slot src into slot dst (fork a prefilled prompt into the slots of a batched decode)"""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        _chk(lib().rwkv_state_copy(self._h, int(dst), int(src)))
+        if not self.resident:           # the host copy is the authoritative one
+            n = self.num_layers * self.num_embed
+            for a in self.state.arrays():
+                a[dst * n:(dst + 1) * n] = a[src * n:(src + 1) * n]
 
     def logits(self, n_tokens: int = 1) -> np.ndarray:
         _chk(lib().rwkv_get_output(self._h, _ptr(self.out), None, None, None, None, None, n_tokens))

@@ -1,0 +1,96 @@
+#!/usr/bin/env python3
+"""Batched decode at 7B shapes: what N streams cost per step when the caller generates text with them.
+
+    python tools/batch_decode_bench.py [--model 7B] [--streams 32,64,96] [--steps 24] [--warmup 4]
+
+Per N (synthetic weights, state slots 0 .. N - 1, maxGPT = the largest N):
+  (a) bare_step      rwkv_forward(N tokens, PARRALEL) alone -- the GPU step, ids fixed
+  (b) host_loop      (a) + rwkv_get_output of the N logits rows + numpy argmax (logit 0 banned) + the next ids: what a caller without
+                     the batched entry points has to do
+  (c) batch_greedy   rwkv_decode_batch_greedy(N, steps): picks on the device, one upload and one download per call
+  (d) batch_typical  rwkv_decode_batch_typical(N, steps), default mode and RWKV_SAMPLE_RECIPE
+ms per step and aggregate tokens/s (N / step time), one JSON line on stdout."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np
+import torch
+
+from rwkv_cpp_accelerated_amd import engine, modelfile as mf
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="7B")
+    ap.add_argument("--streams", default="32,64,96")
+    ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--warmup", type=int, default=4)
+    args = ap.parse_args()
+    ns = [int(x) for x in args.streams.split(",")]
+    L, D = mf.SHAPES[args.model]
+    lib = engine.lib()
+    t = mf.synthetic_tensors_torch(L, D, seed=0)
+    m = engine.RWKV(resident=True)
+    m.loadTensors(L, D, t, maxGPT=max(ns))
+    del t
+    torch.cuda.empty_cache()
+    V = mf.VOCAB
+    line = dict(tool="batch_decode_bench", model=args.model, n_layers=L, n_embed=D, steps=args.steps, maxGPT=max(ns),
+                device=torch.cuda.get_device_name(0), results={})
+
+    def chk(rc):
+        if rc != 0:
+            raise RuntimeError(lib.rwkv_last_error().decode())
+
+    for n in ns:
+        rng = np.random.default_rng(n)
+        first = [int(v) for v in rng.integers(1, V, n)]
+        ids = (C.c_uint64 * n)(*first)
+        logits = np.zeros(n * V, np.float32)
+
+        def bare(k):
+            for _ in range(k):
+                chk(lib.rwkv_forward(m._h, ids, n, engine.MODE_PARRALEL))
+
+        def host(k):
+            cur = list(first)
+            for _ in range(k):
+                chk(lib.rwkv_forward(m._h, (C.c_uint64 * n)(*cur), n, engine.MODE_PARRALEL))
+                chk(lib.rwkv_get_output(m._h, C.c_void_p(logits.ctypes.data), None, None, None, None, None, n))
+                lg = logits.reshape(n, V)
+                lg[:, 0] = -np.inf
+                cur = [int(x) for x in lg.argmax(axis=1)]
+
+        def timed(fn, k):
+            m.reset_state()
+            fn(args.warmup)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(k)
+            return (time.perf_counter() - t0) / k
+
+        r = {}
+        r["bare_step"] = timed(bare, args.steps)
+        r["host_loop"] = timed(host, args.steps)
+        r["batch_greedy"] = timed(lambda k: m.decode_batch_greedy(first, k), args.steps)
+        r["batch_typical"] = timed(lambda k: m.decode_batch_typical(first, k, seeds=list(range(n))), args.steps)
+        r["batch_typical_recipe"] = timed(lambda k: m.decode_batch_typical(first, k, seeds=list(range(n)), recipe=True), args.steps)
+        out = {k: dict(ms_per_step=round(v * 1e3, 3), aggregate_tokens_per_s=round(n / v, 1)) for k, v in r.items()}
+        b = r["bare_step"]
+        out["vs_bare_step"] = {k: round(v / b - 1.0, 4) for k, v in r.items() if k != "bare_step"}
+        line["results"][str(n)] = out
+        print(f"[batch_decode_bench] N={n}: " + ", ".join(f"{k} {v * 1e3:.3f} ms" for k, v in r.items()), file=sys.stderr, flush=True)
+    line["resident_bytes"] = m.resident_bytes()
+    m.close()
+    print(json.dumps(line), flush=True)
+
+
+if __name__ == "__main__":
+    main()
