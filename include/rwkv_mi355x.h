@@ -139,7 +139,8 @@ int rwkv_decode_typical(rwkv_ctx *ctx, uint64_t first_token, uint64_t n_tokens, 
  * the first call, grown to the largest n_streams x n_steps seen, counted by rwkv_resident_bytes, freed by rwkv_free.
  * Status: RWKV_E_ARG for a NULL pointer, n_streams == 0 or > max_ctx, n_steps == 0 or > RWKV_MAX_DECODE_STEPS, a token id >= 50277
  * or !(temp > 0); RWKV_E_STATE when not loaded, on a pipeline-stage context, or for n_streams >= 2 without the chunk path (env
- * RWKV_SEQ=0 at load time, or max_ctx 1).  Every check runs before anything is launched: a rejected call leaves the state as it was. */
+ * RWKV_SEQ=0 at load time, max_ctx 1, or an n_embed that is not a multiple of 64: the chunk path exists for the 80 widths 64, 128,
+ * ... 5120, and the other multiples of 16 that load run every call token by token).  Every check runs before anything is launched: a rejected call leaves the state as it was. */
 #define RWKV_MAX_DECODE_STEPS 65536u
 int rwkv_decode_batch_greedy(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps,
                              uint64_t *out_tokens);

@@ -892,6 +892,9 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     // chunked path scratch
     {
         if (want_seq) {
+            // k_seq_resid covers its octant with three channels per thread (seq.hip.h SEQ_RJ): the longest octant has to fit
+            if ((D / 64 + 7) / 8 * 64 > 3 * (uint64_t)SEQ_ENT)
+                return fail(RWKV_E_ARG, "n_embed=%llu: an octant of the chunk path is longer than %d channels", (unsigned long long)D, 3 * SEQ_ENT);
             if ((rc = dalloc(c, &c->sq_tokens, (size_t)SQ_RING * SEQ_TM))) return rc;
             HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_sq_tokens), sizeof(unsigned long long) * SQ_RING * SEQ_TM, hipHostMallocDefault));
             for (int r = 0; r < SQ_RING; r++) HIPCHK(hipEventCreateWithFlags(&c->sq_ev[r], hipEventDisableTiming));
@@ -1649,7 +1652,7 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
     for (uint64_t s = 0; s < N; s++)
         if (first_tokens[s] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id %llu out of range", (unsigned long long)first_tokens[s]);
     if (typical && !(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
-    if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0 or max context 1)");
+    if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
     if (N == 1)       // the decode path's kernels on slot 0
         return typical ? rwkv_decode_typical(c, first_tokens[0], n_steps, temp, tau, seeds[0], flags, out_tokens)
                        : rwkv_decode_greedy(c, first_tokens[0], n_steps, out_tokens);
@@ -2455,7 +2458,7 @@ int rwkv_stage_chunk(rwkv_ctx *c, const uint64_t *tokens, uint64_t n, uint64_t r
 {
     if (!c) return fail(RWKV_E_ARG, "NULL ctx");
     if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (!c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx > 1)");
+    if (!c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx > 1; off with RWKV_SEQ=0 or n_embed not a multiple of 64)");
     if (n == 0 || n > (uint64_t)SEQ_TM || row0 + n > c->maxT || (buf != 0 && buf != 1)) return fail(RWKV_E_ARG, "bad chunk (n %llu <= 64, row0 %llu, buf %d)", (unsigned long long)n, (unsigned long long)row0, buf);
     if (c->l0 == 0) {
         if (!tokens) return fail(RWKV_E_ARG, "stage 0 needs the token ids");
@@ -2503,7 +2506,7 @@ int rwkv_pipe_prefill(rwkv_ctx *c, const uint64_t *tokens, uint64_t n_tokens)
 {
     if (!c) return fail(RWKV_E_ARG, "NULL ctx");
     if (!c->loaded || !c->pipe) return fail(RWKV_E_STATE, "needs a loaded context with rwkv_pipe_init done");
-    if (!c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx >= 32)");
+    if (!c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx >= 32; off with RWKV_SEQ=0 or n_embed not a multiple of 64)");
     if (c->maxT < (uint64_t)SEQ_T) return fail(RWKV_E_ARG, "needs max_ctx >= %d", SEQ_T);
     Pipe *p = c->pipe;
     const int S = p->world, rank = p->rank;

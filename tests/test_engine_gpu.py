@@ -339,6 +339,44 @@ def test_abi_version_and_small_grid_is_rejected(eng_mod, monkeypatch):
     a.close(); b.close()
 
 
+def _decodes_like_the_oracle(eng_mod, oracle, m, what):
+    """a valid load on handle m, then two tokens against the oracle"""
+    L, D = 1, 80
+    t = mf.synthetic_tensors(L, D, seed=81)
+    m.loadTensors(L, D, t)
+    om = oracle.from_tensors(L, D, t)
+    st = om.new_state()
+    for tk in (5, mf.VOCAB - 1):
+        parity.check_logits(m.forward(tk)[: mf.VOCAB], om.forward([tk], st)[0], what)
+    om.close()
+
+
+@pytest.mark.parametrize("L,D", [(1, 8), (1, 24), (1, 1032), (1, 5136), (0, 64)])
+def test_a_model_shape_outside_the_accepted_set_is_refused_before_anything_is_read(eng_mod, oracle, L, D):
+    """n_embed must be a multiple of 16 up to 5120 and n_layers at least 1: anything else is RWKV_E_ARG with a message, and the handle
+    takes a valid model afterwards.  The tensors have the size the call states (for n_layers 0: a one-layer model's, which is more),
+    so a shape check that moved behind an upload would upload garbage and fail here instead of reading out of bounds."""
+    t = mf.synthetic_tensors(max(L, 1), D, seed=5)
+    m = eng_mod.RWKV(resident=True)
+    with pytest.raises(eng_mod.RWKVError, match=r"unsupported model shape.*status -1"):
+        m.loadTensors(L, D, t)
+    assert not m.ready
+    del t
+    _decodes_like_the_oracle(eng_mod, oracle, m, f"after the refusal of L{L} D{D}")
+    m.close()
+
+
+def test_the_smallest_grid_is_exact_at_the_widest_model(eng_mod, oracle, monkeypatch):
+    """RWKV_GRID = 9 at D = 5120 is one workgroup short of 512 channels each (10 is accepted: test_kernels_gpu.py)"""
+    monkeypatch.setenv("RWKV_GRID", "9")
+    m = eng_mod.RWKV(resident=True)
+    with pytest.raises(eng_mod.RWKVError, match=r"RWKV_GRID=9 is too small.*need >= 10.*status -1"):
+        m.loadTensors(1, 5120, mf.synthetic_tensors(1, 5120, seed=6))
+    assert m.debug_grid() == 9
+    _decodes_like_the_oracle(eng_mod, oracle, m, "after the refusal of RWKV_GRID=9")       # (9 workgroups are enough for D = 80)
+    m.close()
+
+
 def test_load_file_streams_through_pinned_staging(eng_mod, tmp_path):
     """rwkv_load_file (rwkv.cu:638-717): a model.bin read through two pinned staging buffers in 32 MiB pieces, no device wait
     per tensor -- the context must compute exactly what a context loaded from the same tensors in memory computes.  D = 2048,

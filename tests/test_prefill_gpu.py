@@ -23,9 +23,7 @@ def _toks(n, seed):
     return [int(v) for v in np.random.default_rng(seed).integers(2, mf.VOCAB, n)]
 
 
-# ragged chunk, exactly one MFMA tile, exactly 32, more than one chunk, the widest / narrowest models
-@pytest.mark.parametrize("L,D,T", [(2, 768, 5), (2, 768, 16), (2, 1024, 32), (1, 2048, 33), (1, 2560, 2), (1, 4096, 32), (1, 5120, 17), (2, 64, 40)])
-def test_chunk_logits_and_state_vs_oracle(eng_mod, oracle, L, D, T):
+def _chunk_vs_oracle(eng_mod, oracle, L, D, T):
     t = mf.synthetic_tensors(L, D, seed=300 + D + T)
     m = eng_mod.RWKV(resident=True)
     m.loadTensors(L, D, t, maxGPT=max(T, 2))
@@ -48,6 +46,22 @@ def test_chunk_logits_and_state_vs_oracle(eng_mod, oracle, L, D, T):
     om.close(); m.close()
 
 
+# ragged chunk, exactly one MFMA tile, exactly 32, more than one chunk, the widest / narrowest models; then the widths between them.  The
+# chunk path takes every multiple of 64; its GEMMs split the KB = D / 64 k-blocks over 8 octants.  KB = 2, 7, 9, 17, 47: empty and uneven
+# octants; KB = 63, 65, 79: both sides of the switch from the 8-k-block instances to the 10-k-block ones (D > 4096), with 7/8, 8/9 and
+# 9/10 k-blocks per octant
+@pytest.mark.parametrize("L,D,T", [(2, 768, 5), (2, 768, 16), (2, 1024, 32), (1, 2048, 33), (1, 2560, 2), (1, 4096, 32), (1, 5120, 17), (2, 64, 40),
+                                   (2, 128, 40), (2, 448, 33), (2, 576, 17), (1, 1088, 64), (1, 3008, 32), (1, 4032, 33), (1, 4160, 64), (1, 5056, 47)])
+def test_chunk_logits_and_state_vs_oracle(eng_mod, oracle, L, D, T):
+    _chunk_vs_oracle(eng_mod, oracle, L, D, T)
+
+
+def test_chunk_under_a_small_grid_vs_oracle(eng_mod, oracle, monkeypatch):
+    """RWKV_GRID=96: the chunk path's head GEMM (k_seq_gemm_ks) and the continuation's decode kernels run on the context's grid"""
+    monkeypatch.setenv("RWKV_GRID", "96")
+    _chunk_vs_oracle(eng_mod, oracle, 1, 1088, 40)
+
+
 def test_chunk_is_deterministic(eng_mod):
     L, D, T = 2, 1024, 32
     t = mf.synthetic_tensors(L, D, seed=77)
@@ -61,7 +75,8 @@ def test_chunk_is_deterministic(eng_mod):
     m.close()
 
 
-@pytest.mark.parametrize("L,D,T", [(2, 768, 3), (2, 1024, 32), (1, 4096, 17), (2, 256, 40), (2, 768, 70), (1, 1024, 96)])
+@pytest.mark.parametrize("L,D,T", [(2, 768, 3), (2, 1024, 32), (1, 4096, 17), (2, 256, 40), (2, 768, 70), (1, 1024, 96),
+                                   (2, 448, 70), (1, 1088, 96), (1, 4160, 40)])
 def test_parralel_batch_vs_oracle(eng_mod, oracle, L, D, T):
     """PARRALEL mode (rwkv.cu:236-240): T independent sequences advance one token per call, state slot t;
     the engine runs the batch through the MFMA path (weights read once for all streams)."""
@@ -198,7 +213,8 @@ def test_seq_stages_1_to_4_are_bit_identical_and_match_the_oracle(eng_mod, oracl
 
 
 
-@pytest.mark.parametrize("mode,T,L,D", [("gpt", 150, 3, 768), ("gpt", 64, 2, 2048), ("gpt", 47, 2, 1024), ("par", 96, 3, 768), ("par", 70, 2, 2560), ("gpt", 70, 1, 5120), ("gpt", 96, 1, 4096)])
+@pytest.mark.parametrize("mode,T,L,D", [("gpt", 150, 3, 768), ("gpt", 64, 2, 2048), ("gpt", 47, 2, 1024), ("par", 96, 3, 768), ("par", 70, 2, 2560), ("gpt", 70, 1, 5120), ("gpt", 96, 1, 4096),
+                                        ("gpt", 70, 1, 1088), ("gpt", 64, 1, 4160), ("par", 96, 1, 5056), ("gpt", 47, 2, 448)])
 def test_64_row_passes_are_bit_identical_to_32_row_chunks(eng_mod, oracle, mode, T, L, D, monkeypatch):
     """Round 4: a forward call of more than 32 rows runs in passes of up to 64 rows = TWO halves that share every weight fragment
     (seq.hip.h SEQ_TM; k_seq_gemm_p with NH = 2, the element-wise kernels on a global row index, k_seq_wkv over 64 rows) -- weights
@@ -230,7 +246,9 @@ def test_64_row_passes_are_bit_identical_to_32_row_chunks(eng_mod, oracle, mode,
     om.close()
 
 
-@pytest.mark.parametrize("T,L,D", [(70, 2, 2560), (96, 1, 4096)])
+# k_seq_gemm_b needs octants of at least RWKV_SEQ_BDEPTH = 3 k-blocks: D = 1536 (KB = 24) is the narrowest width that has them, 4160 and 5056
+# have 8/9 and 9/10.  At 1088 (2/3 k-blocks per octant) and 128 (0/1) forcing it must fall back to k_seq_gemm_p<.., 2> and still agree.
+@pytest.mark.parametrize("T,L,D", [(70, 2, 2560), (96, 1, 4096), (64, 1, 1536), (64, 1, 4160), (96, 1, 5056), (70, 1, 1088), (40, 2, 128)])
 def test_64_row_gemm_forms_agree(eng_mod, T, L, D, monkeypatch):
     """The 64-row pass has two forms of its K/V/R and ffn k/r GEMMs: k_seq_gemm_p<.., true, 2> (image re-staged per two k-blocks, plain
     workgroup ranges; RWKV_SEQ_B=0) and k_seq_gemm_b (one vector's image resident, workgroup ranges aligned to the vector groups, a wave's
