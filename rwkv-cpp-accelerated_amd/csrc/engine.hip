@@ -470,7 +470,7 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                           (k_att_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
                           (k_att_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
-        else DISPATCH_S(S, k_att<S_, nb_att(S_)><<<dim3(grid), dim3(NT), smem_att(S), c->stream>>>(aa));
+        else DISPATCH_S(S, k_att<S_><<<dim3(grid), dim3(NT), smem_att(S), c->stream>>>(aa));
     } break;
     case 2: {
         AttOutArgs ao = mk.attout(l);
@@ -483,7 +483,7 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                           (k_attout_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
                           (k_attout_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
-        else DISPATCH_S(S, k_attout<S_, ATTOUT_R, nb_attout(S_)><<<dim3(grid), dim3(NT), smem_attout(S), c->stream>>>(ao));
+        else DISPATCH_S(S, k_attout<S_, ATTOUT_R><<<dim3(grid), dim3(NT), smem_attout(S), c->stream>>>(ao));
     } break;
     case 3: {
         FfnRKArgs fa = mk.frk(l);
@@ -496,7 +496,7 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                           (k_ffn_rk_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
                           (k_ffn_rk_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
-        else DISPATCH_S(S, k_ffn_rk<S_, nb_frk(S_)><<<dim3(grid), dim3(NT), smem_frk(S), c->stream>>>(fa));
+        else DISPATCH_S(S, k_ffn_rk<S_><<<dim3(grid), dim3(NT), smem_frk(S), c->stream>>>(fa));
     } break;
     case 4: {
         FfnVArgs fv = mk.fv(l);
@@ -515,14 +515,14 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
                               (k_ffnv_t<2, 4, 32, 4, 2, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
         }
         else if (mk.fv_next_att(l)) {
-            DISPATCH_S(S, k_ffnv<S_, 3, nb_fv(S_)><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
+            DISPATCH_S(S, k_ffnv<S_, 3><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
         } else {
-            DISPATCH_S(S, k_ffnv<S_, 1, nb_fv(S_)><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
+            DISPATCH_S(S, k_ffnv<S_, 1><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
         }
     } break;
     case 5: {
         HeadArgs ha = mk.head();
-        DISPATCH_S(S, k_head<S_, nb_head(S_)><<<dim3(grid), dim3(NT), smem_head(S), c->stream>>>(ha));
+        DISPATCH_S(S, k_head<S_><<<dim3(grid), dim3(NT), smem_head(S), c->stream>>>(ha));
     } break;
     default:
         k_argmax_finish<<<dim3(1), dim3(64), 0, c->stream>>>(c->blk_val, c->blk_idx, grid, c->ctl, c->gen, c->gen_cap);
@@ -632,12 +632,12 @@ int set_smem_limits(rwkv_ctx *c)
 {
     const int S = c->S;
     int rc = 0;
-    DISPATCH_S(S, rc = allow_smem(k_att<S_, nb_att(S_)>, smem_att(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_attout<S_, ATTOUT_R, nb_attout(S_)>, smem_attout(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffn_rk<S_, nb_frk(S_)>, smem_frk(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 3, nb_fv(S_)>, smem_fv(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 1, nb_fv(S_)>, smem_fv(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_head<S_, nb_head(S_)>, smem_head(S))); if (rc) return rc;
+    DISPATCH_S(S, rc = allow_smem(k_att<S_>, smem_att(S))); if (rc) return rc;
+    DISPATCH_S(S, rc = allow_smem(k_attout<S_, ATTOUT_R>, smem_attout(S))); if (rc) return rc;
+    DISPATCH_S(S, rc = allow_smem(k_ffn_rk<S_>, smem_frk(S))); if (rc) return rc;
+    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 3>, smem_fv(S))); if (rc) return rc;
+    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 1>, smem_fv(S))); if (rc) return rc;
+    DISPATCH_S(S, rc = allow_smem(k_head<S_>, smem_head(S))); if (rc) return rc;
     if (c->tile_th) {
 #define TILE_ALLOW(K16, K45, K42, CLS)                                                                   \
         do {                                                                                             \

@@ -179,7 +179,7 @@ __device__ __forceinline__ void block_max(float (&v)[K], double *redd)
     }
 }
 // scratch regions (in doubles) of the RED_BYTES block: NW*K <= 24 doubles each
-constexpr int RED_STATS = 0, RED_MAX = 24, RED_OFFS = 48, RED_PART = 72, RED_AUX = 96;
+constexpr int RED_STATS = 0, RED_MAX = 24, RED_OFFS = 48, RED_PART = 72;
 
 // ------------------------------------------------------------------------------------------
 // Staged activation vectors.  Element j of a vector belongs to the 16-element piece c = j/16,
@@ -189,7 +189,6 @@ constexpr int RED_STATS = 0, RED_MAX = 24, RED_OFFS = 48, RED_PART = 72, RED_AUX
 // needs against dword q of the lane's 16 weight bytes.  A lane's ds_read_b128 of one limb plane is
 // lane-consecutive (conflict-free).  S*768 dwords (3 KiB per step) per vector.
 template <int S> __device__ __forceinline__ constexpr int xvd() { return S * 768; }
-template <int S> __device__ __forceinline__ constexpr int nquads() { return (S * 256 + NT - 1) / NT; }   // per thread
 
 // quantise 4 consecutive elements (quad qd = j/4) with 1/scale `inv_s` and store their 3 limb dwords.
 // real == false writes zero limbs: padding must contribute nothing to the integer sums (it is
@@ -283,7 +282,7 @@ template <int S> __device__ __forceinline__ constexpr int pre_steps() { return R
 //    and wait for the refill itself; two template copies in sibling branches get their common
 //    code hoisted and spilled): after a wave's LAST group, `next_valid` = false degrades the refill
 //    to R*S loads of one and the same 16-byte piece (one L1-resident line), which nobody waits for.
-template <int R, int S, int PAT, bool REFILL = true>
+template <int R, int S, int PAT>
 __device__ __forceinline__ void group_dot(u32x4 (&w)[R][S], const unsigned *xq, int lane, unsigned long long (&T)[R],
                                           const uint8_t *__restrict__ next, size_t stride, int chunks, bool next_valid)
 {
@@ -320,7 +319,7 @@ __device__ __forceinline__ void group_dot(u32x4 (&w)[R][S], const unsigned *xq, 
                 asm volatile("" : "+v"(acc[r][0]), "+v"(acc[r][1]), "+v"(acc[r][2]));
             }
         __builtin_amdgcn_sched_barrier(0);
-        if (REFILL && v == NV - 1) {
+        if (v == NV - 1) {
             step_load<R, S>(w, s, next, nstride, chunks, lane, mask);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -582,20 +581,6 @@ constexpr int RED_BC = 96;     // doubles: scalars published by the prologue wav
 #ifndef RWKV_HEAD_R
 #define RWKV_HEAD_R 2      // rows per group in k_head (measured: 2 -> 35.8, 3 -> 36.2, 4 -> 36.8, 5 -> 38.0 us at 7B)
 #endif
-// Row-group buffers per wave: 1, or 2 (a wave holds TWO groups of weight registers, A and B, and alternates between
-// them: R*S*2 loads requested ahead).  Measured on MI355X (profiles/r02/decode_variants.txt) two buffers LOSE 8 % at 7B
-// (485 vs 528 tokens/s): the CU's memory pipe accepts only ~16 KB of requests, so a loader wave that asks for two groups
-// sits blocked at issue twice as long and the "staged" barrier, which it must reach too, moves from 5 to 10 us, while the
-// stream was never starved with one (the loaders' 80 KB per CU last until the vector is staged).  Kept as a knob.
-#ifndef RWKV_NBUF
-#define RWKV_NBUF 1
-#endif
-constexpr int NBUF = RWKV_NBUF;          // default; a kernel whose two buffers would not fit 256 registers (R*S*8 of them) takes 1
-constexpr int nb_att(int) { return NBUF; }                        // 3 rows:  254 registers at S = 5
-constexpr int nb_attout(int) { return NBUF; }
-constexpr int nb_frk(int S) { return S <= 4 ? NBUF : 1; }         // 5 rows:  245 at S = 4, spills at S = 5
-constexpr int nb_fv(int S) { return S <= 4 ? NBUF : 1; }          // 4 rows:  229 at S = 4, spills at S = 5
-constexpr int nb_head(int) { return NBUF; }
 __device__ __forceinline__ unsigned *group_counter(double *red) { return reinterpret_cast<unsigned *>(red + RED_BC) + 9; }
 __device__ __forceinline__ int next_group(unsigned *ctr)
 {
@@ -609,40 +594,27 @@ __device__ __forceinline__ int next_group(unsigned *ctr)
 // pre(g) requests the epilogue's inputs (before the dot issues the refills: a load placed after them would, by in-order
 // vmcnt, wait for the whole next group to land), group_dot consumes the group's registers and refills them step by step
 // with the group drawn now, epi(g, T, in) finishes the rows.  base(g) = weight address of a valid group.
-template <int R, int S, int PAT, int NB, class Base, class Pre, class Epi>
-__device__ __forceinline__ void stream_groups(u32x4 (&wA)[R][S], u32x4 (&wB)[R][S], int gA, int gB, int g0, int g1, unsigned *gctr,
+// One buffer of weight registers per wave: the CU's memory pipe accepts only ~16 KB of requests, and a second buffer kept a loader
+// wave blocked at issue twice as long -- 8 % slower at 7B (485 vs 528 tokens/s, profiles/r02/decode_variants_nbuf.txt).
+template <int R, int S, int PAT, class Base, class Pre, class Epi>
+__device__ __forceinline__ void stream_groups(u32x4 (&wA)[R][S], int gA, int g0, int g1, unsigned *gctr,
                                               const unsigned *xq, int lane, size_t stride, int chunks, Base base, Pre pre, Epi epi)
 {
-    for (;;) {
-        if (!(gA < g1)) break;
-        {
-            const int gn = next_group(gctr);
-            const bool nv = gn < g1;
-            const auto in = pre(gA);
-            unsigned long long T[R];
-            group_dot<R, S, PAT>(wA, xq, lane, T, base(nv ? gn : g0), stride, chunks, nv);
-            epi(gA, T, in);
-            gA = gn;
-        }
-        if (NB == 2) {
-            if (!(gB < g1)) break;
-            const int gn = next_group(gctr);
-            const bool nv = gn < g1;
-            const auto in = pre(gB);
-            unsigned long long T[R];
-            group_dot<R, S, PAT>(wB, xq, lane, T, base(nv ? gn : g0), stride, chunks, nv);
-            epi(gB, T, in);
-            gB = gn;
-        }
+    while (gA < g1) {
+        const int gn = next_group(gctr);
+        const bool nv = gn < g1;
+        const auto in = pre(gA);
+        unsigned long long T[R];
+        group_dot<R, S, PAT>(wA, xq, lane, T, base(nv ? gn : g0), stride, chunks, nv);
+        epi(gA, T, in);
+        gA = gn;
     }
 }
-// first groups of a wave (A: g0 + wave, B: g0 + NW + wave) and the counter's start; set by thread 0 before the prologue's barriers
-template <int NB>
-__device__ __forceinline__ void first_groups(int g0, int wave, unsigned *gctr, int &gA, int &gB)
+// first group of a wave (g0 + wave) and the counter's start; set by thread 0 before the prologue's barriers
+__device__ __forceinline__ void first_groups(int g0, int wave, unsigned *gctr, int &gA)
 {
     gA = g0 + wave;
-    gB = NB == 2 ? g0 + NW + wave : 0x7fffffff;
-    if (threadIdx.x == 0) *gctr = (unsigned)(g0 + NB * NW);
+    if (threadIdx.x == 0) *gctr = (unsigned)(g0 + NW);
 }
 // workgroup-wide sum of one double and max of one non-negative float in ONE barrier (the kernels' closing reduction)
 __device__ __forceinline__ void block_sum_max(double &sv, float &mv, double *red)
@@ -661,9 +633,9 @@ __device__ __forceinline__ void block_sum_max(double &sv, float &mv, double *red
 
 // LayerNorm-site consumer (k_att, k_ffn_rk, k_head): on return the NV vectors are staged in xq,
 // sr.S / sr.amax are valid in every wave and w holds (requests for) the wave's first row group.
-template <int NV, int R, int S, bool SPLIT, int NB>
+template <int NV, int R, int S, bool SPLIT>
 __device__ __forceinline__ void site_open(const SiteStatic &st, const SiteDyn &dy, const double *x, int D, double *red, unsigned *xq,
-                                          u32x4 (&w)[R][S], u32x4 (&w2)[R][S], const uint8_t *wb, const uint8_t *wb2, size_t stride,
+                                          u32x4 (&w)[R][S], const uint8_t *wb, size_t stride,
                                           SiteRed<NV> &sr, bool publish_stats, unsigned long long *tl)
 {
     const int lane = threadIdx.x & 63, wave = wave_id();
@@ -674,7 +646,6 @@ __device__ __forceinline__ void site_open(const SiteStatic &st, const SiteDyn &d
     if (SPLIT && wave >= NWP) {
         __syncthreads();   // order: the prologue waves' requests are in the memory pipe
         group_load<R, S, 0, S>(w, wb, stride, chunks, lane);
-        if (NB == 2) group_load<R, S, 0, S>(w2, wb2, stride, chunks, lane);
         tl_stamp(tl, 2);
         __syncthreads();   // staged
     } else {
@@ -718,7 +689,6 @@ __device__ __forceinline__ void site_open(const SiteStatic &st, const SiteDyn &d
         }
         __syncthreads();   // staged
         group_load<R, S, SPLIT ? 0 : pre_steps<S>(), S>(w, wb, stride, chunks, lane);
-        if (NB == 2) group_load<R, S, 0, S>(w2, wb2, stride, chunks, lane);
     }
     if (SPLIT) {
 #pragma unroll
@@ -729,9 +699,9 @@ __device__ __forceinline__ void site_open(const SiteStatic &st, const SiteDyn &d
 
 // Plain-vector consumer (k_attout: NVEC = 1; k_ffnv: the four quarter vectors of the hidden vector).
 // The producer left the pre-scaled vector and per-workgroup partials of the offset sum and of max|.|.
-template <int NVEC, int R, int S, bool SPLIT, int NB>
+template <int NVEC, int R, int S, bool SPLIT>
 __device__ __forceinline__ void vec_open(const float *vec, const double *partS, const float *partM, int n_part, int D, double *red,
-                                         unsigned *xq, u32x4 (&w)[R][S], u32x4 (&w2)[R][S], const uint8_t *wb, const uint8_t *wb2, size_t stride,
+                                         unsigned *xq, u32x4 (&w)[R][S], const uint8_t *wb, size_t stride,
                                          float &Sf, float &amax, unsigned long long *tl)
 {
     constexpr int XVD = xvd<S>();
@@ -743,7 +713,6 @@ __device__ __forceinline__ void vec_open(const float *vec, const double *partS, 
     if (SPLIT && wave >= NWP) {
         __syncthreads();   // order
         group_load<R, S, 0, S>(w, wb, stride, chunks, lane);
-        if (NB == 2) group_load<R, S, 0, S>(w2, wb2, stride, chunks, lane);
         tl_stamp(tl, 2);
         __syncthreads();   // staged
     } else {
@@ -795,7 +764,6 @@ __device__ __forceinline__ void vec_open(const float *vec, const double *partS, 
         if (SPLIT && threadIdx.x == 0) { bc[0] = Sf; bc[4] = amax; }
         __syncthreads();   // staged
         group_load<R, S, SPLIT ? 0 : pre_steps<S>(), S>(w, wb, stride, chunks, lane);
-        if (NB == 2) group_load<R, S, 0, S>(w2, wb2, stride, chunks, lane);
     }
     if (SPLIT) { Sf = bc[0]; amax = bc[4]; }
     tl_stamp(tl, 5);
@@ -805,7 +773,7 @@ __device__ __forceinline__ void vec_open(const float *vec, const double *partS, 
 // LDS-DMA primitives (the tile-form loaders, tile.hip.h, and the chunk path's staging, seq.hip.h).
 // Loads into registers top out at ~10 B/clk per CU on this chip whatever is kept in flight;
 // global_load_lds_dwordx4 -- the CU's DMA path from memory into LDS -- does not return through the vector register file.
-// A loader wave issues the DMA of one unit (S KiB) as ONE asm statement (dma_unit), READS its vmcnt instead of waiting on it, keeps up to
+// A loader wave issues the DMA of one unit (S KiB) as ONE asm statement (dma_unit_s, tile.hip.h), READS its vmcnt instead of waiting on it, keeps up to
 // RWKV_RING_DEPTH pieces in flight and issues its first units in front of the workgroup's order barrier (RWKV_RING_PRE; per class in
 // tile.hip.h); its consumers meet it on LDS counters only, and every wait loop is bounded (GLDS_SPIN) and reported through the
 // context's error word (ring_report).
@@ -815,12 +783,6 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 {
     return (unsigned)(unsigned long long)(const __attribute__((address_space(3))) void *)p;
 }
-__device__ __forceinline__ void dma_piece(const uint8_t *src, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
-}
 // the same for data that OTHER workgroups of the XCD read as well (the chunk path's activation image): no "nt", it should stay in L2
 __device__ __forceinline__ void dma_piece_shared(const uint8_t *src, unsigned lds_dst)
 {
@@ -828,28 +790,6 @@ __device__ __forceinline__ void dma_piece_shared(const uint8_t *src, unsigned ld
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
 }
-// One row of S KiB as S DMA instructions that share ONE address register pair and one M0 value: the instruction offset advances
-// the global address AND the LDS address (tools/dmabench.hip, modes 2 / 6: every word verified).  A one-wave DMA stream is bounded
-// by the loader wave's instruction count -- at 7 instructions per piece it stood at 5.7 TB/s chip-wide, at 2 per piece 7.0 TB/s.
-template <int S> __device__ __forceinline__ void dma_unit(const uint8_t *src, unsigned lds_dst);
-#define RWKV_DMA_UNIT(S_, BODY)                                                                                                        \
-    template <> __device__ __forceinline__ void dma_unit<S_>(const uint8_t *src, unsigned lds_dst)                                     \
-    {                                                                                                                                  \
-        unsigned keep;                                                                                                                 \
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t" BODY "s_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory"); \
-    }
-#define RWKV_DMA_L(OFF) "global_load_lds_dwordx4 %1, off offset:" #OFF " nt\n\t"
-RWKV_DMA_UNIT(1, RWKV_DMA_L(0))
-RWKV_DMA_UNIT(2, RWKV_DMA_L(0) RWKV_DMA_L(1024))
-RWKV_DMA_UNIT(3, RWKV_DMA_L(0) RWKV_DMA_L(1024) RWKV_DMA_L(2048))
-RWKV_DMA_UNIT(4, RWKV_DMA_L(0) RWKV_DMA_L(1024) RWKV_DMA_L(2048) RWKV_DMA_L(3072))
-template <> __device__ __forceinline__ void dma_unit<5>(const uint8_t *src, unsigned lds_dst)      // the offset field ends at 4095
-{
-    dma_unit<4>(src, lds_dst);
-    dma_unit<1>(src + 4096, lds_dst + 4096);
-}
-#undef RWKV_DMA_L
-#undef RWKV_DMA_UNIT
 // First statement of every loader wave.  hipcc does not see the loader's DMA (inline asm), but it does remember every vector memory
 // operation the wave issued BEFORE the role branch -- the debug timeline's store, a kernel-entry load -- and guards the registers those
 // were given with s_waitcnt vmcnt(0) wherever the loader's code first reuses them: by the luck of register allocation that was inside
@@ -876,9 +816,7 @@ __device__ __forceinline__ void wait_count(const unsigned *p, unsigned least, un
 }
 __device__ __forceinline__ void ring_report(unsigned fail, unsigned *herr)
 {
-#ifndef RWKV_NO_HERR      // (A/B knob: what recording the failures costs; without the report the compiler drops every `fail` update)
     if (fail != 0u && herr != nullptr && (threadIdx.x & 63) == 0) __hip_atomic_store(herr, fail, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
 }
 // DMA pieces (1 KiB) the loader keeps in flight.  By Little's law the queueing delay of EVERY access of the CU is in-flight bytes /
 // stream rate: 63 KiB at 23 KB/us = 2.7 us -- paid by the prologue's loads and, after the last issue, by the kernel's tail --
@@ -973,7 +911,7 @@ struct AttArgs {
 
 // ln1 site -> K,V,R dequant-GEMV -> WKV (rwkv.cu:535-545; kernels :351-392, :58-100, :221-259)
 struct AttIn { unsigned rs[3]; double aa, bb, uw, ew; float ra, oa; };
-template <int S, int NB>
+template <int S>
 __global__ __launch_bounds__(NT) void k_att(AttArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1025,14 +963,14 @@ __global__ __launch_bounds__(NT) void k_att(AttArgs a)
             pmax = fmaxf(pmax, fabsf(ys));
         }
     };
-    u32x4 wA[3][S], wB[3][S];
-    int gA, gB;
+    u32x4 wA[3][S];
+    int gA;
     unsigned *gctr = group_counter(red);
-    first_groups<NB>(g0, wave, gctr, gA, gB);   // the counter is visible behind the prologue's barriers
+    first_groups(g0, wave, gctr, gA);   // the counter is visible behind the prologue's barriers
     SiteRed<3> sr;
-    site_open<3, 3, S, (RWKV_SPLIT & 1) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, true, a.tl);
+    site_open<3, 3, S, (RWKV_SPLIT & 1) != 0>(a.st, a.dy, a.x, D, red, xq, wA, base(gA), (size_t)D, sr, true, a.tl);
     scalars(sr);
-    stream_groups<3, S, PAT_PER_ROW, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
+    stream_groups<3, S, PAT_PER_ROW>(wA, gA, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     tl_stamp(a.tl, 6);
     __syncthreads();   // every wave is past its last read of the reduction scratch
     block_sum_max(part, pmax, red + RED_PART);
@@ -1066,7 +1004,7 @@ struct AttOutArgs {
 // att_out dequant-GEMV + residual through f32 (rwkv.cu:548-553), R rows per group; commits state xy;
 // opens the ln2 site for the rows it owns
 template <int R> struct AttOutIn { unsigned rsum; double xold, lw, lb, prev2; SitePre<2> pre; int mi, shift; };
-template <int S, int R, int NB>
+template <int S, int R>
 __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1113,13 +1051,13 @@ __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
             }
         }
     };
-    u32x4 wA[R][S], wB[R][S];
-    int gA, gB;
+    u32x4 wA[R][S];
+    int gA;
     unsigned *gctr = group_counter(red);
-    first_groups<NB>(g0, wave, gctr, gA, gB);
-    vec_open<1, R, S, (RWKV_SPLIT & 2) != 0, NB>(a.ybuf, a.partS, a.partM, a.n_part, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, Sf, amax, a.tl);
+    first_groups(g0, wave, gctr, gA);
+    vec_open<1, R, S, (RWKV_SPLIT & 2) != 0>(a.ybuf, a.partS, a.partM, a.n_part, D, red, xq, wA, base(gA), (size_t)D, Sf, amax, a.tl);
     sc = scale_of(amax);
-    stream_groups<R, S, PAT_SHARED, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
+    stream_groups<R, S, PAT_SHARED>(wA, gA, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     __syncthreads();   // every wave is past its last read of the reduction scratch (and of the staged vector)
     tl_stamp(a.tl, 6);
     site_publish<2, R>(acc, a.dy, xq);   // the staged vector is dead: its LDS is the scratch
@@ -1147,7 +1085,7 @@ struct FfnRKArgs {
 
 // ln2 site -> ffn_r GEMV + sigmoid, ffn_k GEMV + relu^2 (rwkv.cu:557-573)
 struct FfnRKIn { unsigned rsum; float rq, oq; };
-template <int S, int NB>
+template <int S>
 __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1192,14 +1130,14 @@ __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
             a.rgate[g] = (float)(1.0 / (1.0 + exp(-(double)val)));   // rwkv.cu:212
         }
     };
-    u32x4 wA[5][S], wB[5][S];
-    int gA, gB;
+    u32x4 wA[5][S];
+    int gA;
     unsigned *gctr = group_counter(red);
-    first_groups<NB>(g0, wave, gctr, gA, gB);
+    first_groups(g0, wave, gctr, gA);
     SiteRed<2> sr;
-    site_open<2, 5, S, (RWKV_SPLIT & 4) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, true, a.tl);
+    site_open<2, 5, S, (RWKV_SPLIT & 4) != 0>(a.st, a.dy, a.x, D, red, xq, wA, base(gA), (size_t)D, sr, true, a.tl);
     scalars(sr);
-    stream_groups<5, S, PAT_FFN_RK, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
+    stream_groups<5, S, PAT_FFN_RK>(wA, gA, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     tl_stamp(a.tl, 6);
     __syncthreads();   // every wave is past its last read of the reduction scratch
     block_sum_max(part, pmax, red + RED_PART);
@@ -1233,7 +1171,7 @@ struct FfnVArgs {
 
 // ffn_v dequant-GEMV, x += v * sigmoid(r) (rwkv.cu:574-577); commits state dd; opens the next site
 template <int NVN> struct FfnVIn { unsigned rsum; double xold, lw, lb, prevn; float rg; SitePre<NVN> pre; };
-template <int S, int NVN, int NB>
+template <int S, int NVN>
 __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1270,13 +1208,13 @@ __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
             site_emit<NVN>(in.pre, a.dy, D, g, xnew, in.prevn, acc);
         }
     };
-    u32x4 wA[4][S], wB[4][S];
-    int gA, gB;
+    u32x4 wA[4][S];
+    int gA;
     unsigned *gctr = group_counter(red);
-    first_groups<NB>(g0, wave, gctr, gA, gB);
-    vec_open<4, 4, S, (RWKV_SPLIT & 8) != 0, NB>(a.hbuf, a.partS, a.partM, a.n_part, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, Sf, amax, a.tl);
+    first_groups(g0, wave, gctr, gA);
+    vec_open<4, 4, S, (RWKV_SPLIT & 8) != 0>(a.hbuf, a.partS, a.partM, a.n_part, D, red, xq, wA, base(gA), (size_t)D, Sf, amax, a.tl);
     sc = scale_of(amax);
-    stream_groups<4, S, PAT_PER_ROW, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
+    stream_groups<4, S, PAT_PER_ROW>(wA, gA, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     __syncthreads();   // every wave is past its last read of the reduction scratch
     tl_stamp(a.tl, 6);
     site_publish<NVN, 1>(acc, a.dy, xq);   // the staged vector is dead: its LDS is the scratch
@@ -1313,7 +1251,7 @@ __device__ __forceinline__ void am_wave_fold(float &best, unsigned &besti)
 
 // ln_out site -> head dequant-GEMV -> logits (rwkv.cu:585-589); also per-workgroup argmax partials
 template <int R> struct HeadIn { unsigned rsr[R]; int row0, shift; };
-template <int S, int NB, int R = RWKV_HEAD_R>
+template <int S, int R = RWKV_HEAD_R>
 __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1357,14 +1295,14 @@ __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
             if (i != 0 && am_better(val, (unsigned)i, best, besti)) { best = val; besti = (unsigned)i; }
         }
     };
-    u32x4 wA[R][S], wB[R][S];
-    int gA, gB;
+    u32x4 wA[R][S];
+    int gA;
     unsigned *gctr = group_counter(red);
-    first_groups<NB>(g0, wave, gctr, gA, gB);
+    first_groups(g0, wave, gctr, gA);
     SiteRed<1> sr;
-    site_open<1, R, S, (RWKV_SPLIT & 16) != 0, NB>(a.st, a.dy, a.x, D, red, xq, wA, wB, base(gA), base(gB), (size_t)D, sr, false, nullptr);
+    site_open<1, R, S, (RWKV_SPLIT & 16) != 0>(a.st, a.dy, a.x, D, red, xq, wA, base(gA), (size_t)D, sr, false, nullptr);
     Sf = (float)sr.S[0]; sc = scale_of(sr.amax[0]);
-    stream_groups<R, S, PAT_SHARED, NB>(wA, wB, gA, gB, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
+    stream_groups<R, S, PAT_SHARED>(wA, gA, g0, g1, gctr, xq, lane, (size_t)D, chunks, base, pre, epi);
     if (lane == 0) { bval[wave] = best; bidx[wave] = besti; }
     __syncthreads();
     if (threadIdx.x == 0) {

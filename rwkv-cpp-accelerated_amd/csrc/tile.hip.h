@@ -1,31 +1,29 @@
-// tile.hip.h -- TILE-FORM decode kernels (round 5): the four per-layer kernels of a token on a TILE image of the matrices instead of the
-// row-per-output re-tiling of kernels.hip.h.  Built for k_ffn_rk first -- the gate the round-4 review set ("decode on the MFMA B-operand
-// image" against the row-form ring kernel on one box) --, then for all four classes; DESIGN.md 4.7 has the measurements, including those
-// that decide which class runs in which form at which width (engine.hip tile_cfg_for / rwkv_ctx::tile).
+// tile.hip.h -- TILE-FORM decode kernels: the four per-layer kernels of a token on a TILE image of the matrices instead of the
+// row-per-output re-tiling of kernels.hip.h.  DESIGN.md 4.7 has the measurements, including those that decide which class runs in which
+// form at which width (engine.hip tile_cfg_for / rwkv_ctx::tile).
 //
 // The row-form decode kernels stream a matrix re-tiled to row-per-output order: a wave owns whole rows, a lane 16 bytes of a row per
 // step, every row ends in three 6-step DPP reductions and an epilogue on one lane.  These kernels stream the image k_bimage (seq.hip.h)
 // makes: [TH-row tile][k-fragment of 1 KiB][lane][16 B], lane = TH * (piece along k) + row, bytes SIGNED (u - 128).  TH = 16 is the
 // chunk path's MFMA B-operand image itself (4096 channels: one tile per class and workgroup, 64 inputs per fragment); TH = 4 is the
 // same layout for widths where 16 channels per workgroup do not divide (5120: five tiles per class, 256 inputs per fragment; 2048: two).
-//   * a wave instruction's 1 KiB is 1024 / TH inputs of TH rows: lane l accumulates row l % TH over piece l / TH of every fragment it
-//     meets -- TH = 16: no cross-lane reduction per row at all, TH = 4: two DPP steps --; the pieces of a row and the k-ranges of
-//     different waves meet as exact integer adds in LDS (ds_add_u32: the sums are integers, so the order they arrive in changes nothing);
-//   * the ring unit is S KiB = S fragments of ONE tile (contiguous in the image: one dma_unit), units go to the 7 consumer waves round
+//   * the integer contraction runs on the matrix cores (tile_consume): a 16-row fragment IS v_mfma_i32_16x16x64_i8's B operand as it lies
+//     in the ring, with the staged vector as the A operand (its three limbs = rows 0..2 of 16); a 4-row fragment is the B operand of 16
+//     virtual rows (row, piece % 4) against an A whose twelve rows are (limb, piece % 4), the diagonal blocks of the product being what
+//     belongs together.  One 16-byte LDS read and one matrix instruction per fragment; a wave's accumulators of a tile and the k-ranges
+//     of different waves meet as exact integer adds in LDS (ds_add_u32: the sums are integers, so the order they arrive in changes
+//     nothing).  Not a reshaping of the GEMV into a GEMM: a launch streams the same bytes once and stays HBM-bound; the consumers leave
+//     the LDS pipe to the DMA.  Against VALU dot products (v_dot4_i32_i8, three reads and twelve instructions per fragment; removed):
+//     +1.2 % on the 7B token, +2.8 % at 14B, +1.7 % at 1B5 (profiles/r06/mfma_consumer_ab.txt);
+//   * the ring unit is S KiB = S fragments of ONE tile (contiguous in the image: one dma_unit_s), units go to the 7 consumer waves round
 //     robin (or in runs, tile_run), every unit is freed as soon as its S ds_read_b128 are in the LDS queue: fine-grained turnover, all
-//     waves busy from the first unit on (the row form's retired LDS ring held 5 groups of 20 KiB for 7 waves);
+//     waves busy from the first unit on;
 //   * the wave whose add completes a tile runs that tile's TH epilogues side by side on TH lanes;
-//   * activations: the same 23-bit fixed point, limbs stored SIGNED (limb - 128) so that v_dot4_i32_i8 multiplies the image's bytes as
-//     they are: sum u l = dot + 128 rowsum(u) + 128 sum(l) - 16384 N, folded into one constant per vector (cA) and the row-sum
+//   * activations: the same 23-bit fixed point, limbs stored SIGNED (limb - 128) so that the signed 8-bit multiply takes the image's
+//     bytes as they are: sum u l = dot + 128 rowsum(u) + 128 sum(l) - 16384 N, folded into one constant per vector (cA) and the row-sum
 //     coefficient 4227200 the chunk path uses (seq.hip.h SEQ_CU).  Every row value is the SAME exact integer as in row form: logits and
 //     state are bit-identical to the row-form kernels' for every mix of forms (tests/test_engine_gpu.py);
-//   * staged vector layout [16-byte piece along k][limb][16 B]: a lane's operand is one ds_read_b128, TH lanes share an address (broadcast).
-// Integer contraction, since round 6 on the matrix cores: a 16-row fragment IS v_mfma_i32_16x16x64_i8's B operand as it lies in the ring, with the staged
-// vector as the A operand (its three limbs = rows 0..2 of 16); a 4-row fragment is the B operand of 16 virtual rows (row, piece % 4) against an A whose
-// twelve rows are (limb, piece % 4), the diagonal blocks of the product being what belongs together (tile_consume).  Per fragment one 16-byte LDS read and
-// one instruction where the VALU form (v_dot4_i32_i8, kept behind RWKV_TILE_MFMA / RWKV_TILE_MFMA4 = 0) needs three reads and twelve dot instructions.
-// Not a reshaping of the GEMV into a GEMM: a launch streams the same bytes once and stays HBM-bound; the consumers leave the LDS pipe to the DMA and
-// follow the stream more closely (+1.2 % on the 7B token, +2.8 % at 14B, +1.7 % at 1B5).
+//   * staged vector layout [16-byte piece along k][limb][16 B]: a lane's operand is one ds_read_b128.
 #pragma once
 #include "kernels.hip.h"
 
@@ -42,16 +40,6 @@ constexpr double TILE_CN = -1077952512.0;      // -16384 * 65793: coefficient of
 #else
 #define TL_BAR(tl, ph)
 #endif
-// Tiles are multiplied on the matrix cores (1; round 6, profiles/r06/mfma_consumer_ab.txt: 16-row tiles 614.4 -> 621.8 tokens/s at 7B; 4-row tiles
-// 355.4 -> 365.4 at 14B, 1351 -> 1374 at 1B5) or with v_dot4 on the VALU (0: round 5's form).  Same exact integers either way; tile form == row form
-// bit for bit is a GPU test (tests/test_engine_gpu.py).
-#ifndef RWKV_TILE_MFMA           // 16-row tiles
-#define RWKV_TILE_MFMA 1
-#endif
-#ifndef RWKV_TILE_MFMA4          // 4-row tiles
-#define RWKV_TILE_MFMA4 1
-#endif
-constexpr bool TILE_MFMA = RWKV_TILE_MFMA != 0, TILE_MFMA4 = RWKV_TILE_MFMA4 != 0;
 typedef int tile_i32x4 __attribute__((ext_vector_type(4)));
 constexpr int TILE_NWP = NT / 2 / 64;          // prologue waves (0 .. 3)
 constexpr int TILE_NSTASH = NC - TILE_NWP;     // consumer waves that fetch the epilogues' inputs meanwhile (4 .. 6)
@@ -446,54 +434,43 @@ __device__ __forceinline__ void tile_consume(int NU, const unsigned char *ring, 
     static_assert(HEAD == 0 || (RUN == 1 && HEAD % TILE_NSTASH == 0), "a head of the stream: round robin only, whole rounds of the three waves");
     constexpr int PPB = 64 / TH;                         // 16-byte pieces of k per row and fragment
     const int pc = lane / TH, r = lane % TH;
-    int acc0 = 0, acc1 = 0, acc2 = 0, cnt = 0;
+    int cnt = 0;
     tile_i32x4 ma = tile_i32x4{0, 0, 0, 0}, mb = tile_i32x4{0, 0, 0, 0};
     // multiply unit u (in registers) and, when this wave's next unit `un` lies in another tile (or nowhere), add the tile's partial sums up
     auto mul = [&](const u32x4 (&w)[S], int u, int un) {
         const int t = u / UPT, c = u - t * UPT;
-        if constexpr (TILE_MFMA && TH == 16) {
-            // a 16-row fragment IS the B operand of v_mfma_i32_16x16x64_i8 and the staged vector's (k-block, piece, limb) order its A operand with
-            // the three limbs as rows 0..2: one 16-byte LDS read and one matrix instruction per fragment where the VALU form needs three reads and
-            // twelve dot instructions.  Rows 3..15 of A are whatever those lanes read (limb 2 again): their outputs are never looked at.
-            // The sums are the same exact integers.
-            const u32x4 *xp = reinterpret_cast<const u32x4 *>(xq + vec_of(t) * xvd_t) + ((c * S) * PPB + pc) * 3 + (r < 3 ? r : 2);
-#pragma unroll
-            for (int s = 0; s < S; s++) {
-                const u32x4 x = xp[s * PPB * 3];
-                const tile_i32x4 af = tile_i32x4{(int)x[0], (int)x[1], (int)x[2], (int)x[3]}, bf = tile_i32x4{(int)w[s][0], (int)w[s][1], (int)w[s][2], (int)w[s][3]};
-                if (s & 1) mb = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, mb, 0, 0, 0);
-                else ma = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, ma, 0, 0, 0);
-            }
-        } else if constexpr (TILE_MFMA4 && TH == 4) {
+        // One 16-byte LDS read and one v_mfma_i32_16x16x64_i8 per fragment: the fragment as it lies in the ring is the B operand, the staged
+        // vector's (k-block, piece, limb) order the A operand; the two tile heights differ in which (piece, limb) a lane reads.
+        const u32x4 *xp = reinterpret_cast<const u32x4 *>(xq + vec_of(t) * xvd_t);
+        if constexpr (TH == 16) {
+            // a 16-row fragment IS the B operand; A's rows 0..2 are the three limbs.  Rows 3..15 of A are whatever those lanes read (limb 2
+            // again): their outputs are never looked at.
+            xp += ((c * S) * PPB + pc) * 3 + (r < 3 ? r : 2);
+        } else {
             // a 4-row fragment (lane l = piece l / 4 of row l % 4; 16 pieces = 256 inputs) read as a B operand is 16 VIRTUAL rows n = (row, piece % 4)
             // whose k-piece j is the row's piece 4 j + (piece % 4).  A's rows are (limb b, q): A[(b, q)][j] = limb b of piece 4 j + q, so that
             // D[(b, q)][(row, q)] -- the diagonal blocks -- are the products that belong together; a row's limb sum is the sum of its four q.
-            // Twelve of A's sixteen rows carry data; one instruction per fragment, like the 16-row form.
+            // Twelve of A's sixteen rows carry data.
             const int m = (lane & 15) < 12 ? (lane & 15) : 11;
-            const u32x4 *xp = reinterpret_cast<const u32x4 *>(xq + vec_of(t) * xvd_t) + ((c * S) * PPB + 4 * (lane >> 4) + (m & 3)) * 3 + (m >> 2);
+            xp += ((c * S) * PPB + 4 * (lane >> 4) + (m & 3)) * 3 + (m >> 2);
+        }
 #pragma unroll
-            for (int s = 0; s < S; s++) {
-                const u32x4 x = xp[s * PPB * 3];
-                const tile_i32x4 af = tile_i32x4{(int)x[0], (int)x[1], (int)x[2], (int)x[3]}, bf = tile_i32x4{(int)w[s][0], (int)w[s][1], (int)w[s][2], (int)w[s][3]};
-                if (s & 1) mb = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, mb, 0, 0, 0);
-                else ma = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, ma, 0, 0, 0);
-            }
-        } else {
-            const u32x4 *xp = reinterpret_cast<const u32x4 *>(xq + vec_of(t) * xvd_t) + ((c * S) * PPB + pc) * 3;
-#pragma unroll
-            for (int s = 0; s < S; s++) {
-                const u32x4 x0 = xp[s * PPB * 3], x1 = xp[s * PPB * 3 + 1], x2 = xp[s * PPB * 3 + 2];
-#pragma unroll
-                for (int d = 0; d < 4; d++) {
-                    acc0 = __builtin_amdgcn_sdot4((int)w[s][d], (int)x0[d], acc0, false);
-                    acc1 = __builtin_amdgcn_sdot4((int)w[s][d], (int)x1[d], acc1, false);
-                    acc2 = __builtin_amdgcn_sdot4((int)w[s][d], (int)x2[d], acc2, false);
-                }
-            }
+        for (int s = 0; s < S; s++) {
+            const u32x4 x = xp[s * PPB * 3];
+            const tile_i32x4 af = tile_i32x4{(int)x[0], (int)x[1], (int)x[2], (int)x[3]}, bf = tile_i32x4{(int)w[s][0], (int)w[s][1], (int)w[s][2], (int)w[s][3]};
+            if (s & 1) mb = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, mb, 0, 0, 0);
+            else ma = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, ma, 0, 0, 0);
         }
         cnt++;
         if (un >= NU || un / UPT != t) {
-            if constexpr (TILE_MFMA4 && TH == 4) {
+            if constexpr (TH == 16) {      // (accumulator image: lane n < 16 holds row n's three limb sums in registers 0..2)
+                if (lane < 16) {
+                    int *ts = tsum + (t * TH + lane) * 3;
+                    __hip_atomic_fetch_add(ts + 0, ma[0] + mb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(ts + 1, ma[1] + mb[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    __hip_atomic_fetch_add(ts + 2, ma[2] + mb[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                }
+            } else {
                 // accumulator image: lane (n = l % 16, g = l / 16) holds D[(g, i)][n] in register i: limb g of virtual row n = (row n % 4, q = n / 4)
                 // is register n / 4; the four q of a row sit 4 lanes apart inside the 16 lanes
                 const int n = lane & 15;
@@ -501,34 +478,13 @@ __device__ __forceinline__ void tile_consume(int NU, const unsigned char *ring, 
                 int v = n < 4 ? sa[0] : n < 8 ? sa[1] : n < 12 ? sa[2] : sa[3];
                 v += __builtin_amdgcn_update_dpp(0, v, 0x124, 0xf, 0xf, true); v += __builtin_amdgcn_update_dpp(0, v, 0x128, 0xf, 0xf, true);
                 if (n < 4 && lane < 48) __hip_atomic_fetch_add(tsum + (t * TH + n) * 3 + (lane >> 4), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                ma = mb = tile_i32x4{0, 0, 0, 0};
-            } else if (TH == 4) {
-                // 16 lanes hold pieces of one row: fold the pieces 4 apart inside every row of 16 lanes first (DPP), then the four rows of
-                // 16 lanes meet in LDS like the four k-quarters of the 16-row form
-                acc0 += __builtin_amdgcn_update_dpp(0, acc0, 0x124, 0xf, 0xf, true); acc0 += __builtin_amdgcn_update_dpp(0, acc0, 0x128, 0xf, 0xf, true);
-                acc1 += __builtin_amdgcn_update_dpp(0, acc1, 0x124, 0xf, 0xf, true); acc1 += __builtin_amdgcn_update_dpp(0, acc1, 0x128, 0xf, 0xf, true);
-                acc2 += __builtin_amdgcn_update_dpp(0, acc2, 0x124, 0xf, 0xf, true); acc2 += __builtin_amdgcn_update_dpp(0, acc2, 0x128, 0xf, 0xf, true);
             }
-            if constexpr (TILE_MFMA && TH == 16) {      // (accumulator image: lane n < 16 holds row n's three limb sums in registers 0..2)
-                if (lane < 16) {
-                    int *ts = tsum + (t * TH + lane) * 3;
-                    __hip_atomic_fetch_add(ts + 0, ma[0] + mb[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(ts + 1, ma[1] + mb[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_fetch_add(ts + 2, ma[2] + mb[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                }
-                ma = mb = tile_i32x4{0, 0, 0, 0};
-            } else if constexpr (TILE_MFMA4 && TH == 4) {
-            } else if (TH == 16 || (lane & 15) < 4) {
-                int *ts = tsum + (t * TH + r) * 3;
-                __hip_atomic_fetch_add(ts + 0, acc0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(ts + 1, acc1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                __hip_atomic_fetch_add(ts + 2, acc2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            }
+            ma = mb = tile_i32x4{0, 0, 0, 0};
             unsigned old = 0u;
             if (lane == 0) old = __hip_atomic_fetch_add(&tc->tcnt[t], (unsigned)cnt, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
             old = (unsigned)__builtin_amdgcn_readfirstlane((int)old);
             if (old + (unsigned)cnt == (unsigned)UPT) on_tile(t);
-            acc0 = acc1 = acc2 = 0; cnt = 0;
+            cnt = 0;
         }
     };
     if constexpr (HEAD > 0) {

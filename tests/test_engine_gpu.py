@@ -493,7 +493,7 @@ def test_two_contexts_decoding_at_once_are_independent(built, tile, monkeypatch)
 
 def test_tile_form_decode_is_the_row_form_bit_for_bit_on_one_weight_image(built, monkeypatch):
     """A 4096-wide model on 256 CUs decodes in TILE form by default (csrc/tile.hip.h: the four per-layer kernels stream the MFMA B-operand
-    image the chunk path uses, v_dot4_i32_i8 on signed limbs, exact integer sums met in LDS) and holds ONLY that image of the per-layer
+    image the chunk path uses, v_mfma_i32_16x16x64_i8 on signed limbs, exact integer sums met in LDS) and holds ONLY that image of the per-layer
     matrices.  Every row value is the same exact integer as in row form (RWKV_TILE=0), so greedy ids AND logits must be identical, step
     after step -- also on a second state slot (PARRALEL mode through the token-by-token path, RWKV_SEQ=0) and on a context that owns a layer
     range (pipeline stage) -- and the resident bytes must be those of ONE copy of the matrices."""
