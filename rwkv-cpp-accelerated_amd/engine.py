@@ -226,6 +226,10 @@ class RWKV:
     def x_device_ptr(self) -> int:
         return int(lib().rwkv_x_device(self._h) or 0)
 
+    def xseq_device_ptr(self, buf: int = 0) -> int:
+        """device address of residual-stream buffer `buf` (0 / 1) of the chunk path: [rows][n_embed] f64, what stage_chunk reads and leaves"""
+        return int(lib().rwkv_xseq_device(self._h, int(buf)) or 0)
+
     def stage_chunk(self, tokens, n: int, row0: int = 0, buf: int = 0):
         """one prompt chunk (n <= 32 tokens) through this stage's layers on the mm8_seq path (asynchronous)"""
         arr = (C.c_uint64 * n)(*[int(t) for t in tokens]) if tokens is not None else None

@@ -29,6 +29,7 @@ class Oracle:
         L.oracle_n_layers.argtypes = [vp]; L.oracle_n_layers.restype = u64
         L.oracle_n_embed.argtypes = [vp]; L.oracle_n_embed.restype = u64
         L.oracle_forward.argtypes = [vp, C.POINTER(u64), u64, i32, C.POINTER(vp), vp]; L.oracle_forward.restype = i32
+        L.oracle_stage_forward.argtypes = [vp, u64, vp, u64, u64, C.POINTER(vp), u64, vp]; L.oracle_stage_forward.restype = i32
         L.oracle_mm8_one_f64.argtypes = [u64, u64, vp, vp, vp, vp, vp, u64, u64]
         L.oracle_mm8_one_f32.argtypes = [u64, u64, vp, vp, vp, vp, vp, u64, u64]
         L.oracle_meanvar.argtypes = [u64, vp, u64, vp, vp]
@@ -152,6 +153,16 @@ class OracleModel:
         if rc:
             raise RuntimeError(f"oracle_forward rc={rc}")
         return logits
+
+    def stage_forward(self, token, x, l0, l1, state, slot=0, logits=None):
+        """one token through layers [l0, l1) on state slot `slot` (oracle_stage_forward): x f64[D] is the residual vector, in and out
+        (l0 == 0: it is filled from the embedding row of `token` first); logits f32[VOCAB] is filled when l1 is the last layer"""
+        assert x.dtype == np.float64 and x.flags.c_contiguous and x.shape == (self.D,)
+        assert logits is None or (logits.dtype == np.float32 and logits.flags.c_contiguous and logits.size == VOCAB)
+        sp = (vp * 5)(*[s.ctypes.data for s in state])
+        rc = self.lib.L.oracle_stage_forward(self.h, int(token), _p(x), l0, l1, sp, slot, None if logits is None else _p(logits))
+        if rc:
+            raise RuntimeError(f"oracle_stage_forward rc={rc}")
 
     def close(self):
         if self.h:

@@ -1,9 +1,21 @@
 """shared parity helpers.  Tolerance = BASELINE.json north_star: logits within 1e-3 relative fp32
 (max|d| <= 1e-3 * max|ref| and element-wise |d| <= 1e-3*|ref| + 1e-3*rms(ref)),
-greedy ids identical wherever the reference's own top-2 margin exceeds that band."""
+greedy ids identical wherever the reference's own top-2 margin exceeds that band.  TOL / _close: the tighter bound of the suites that check one
+launch (tests/test_kernels_gpu.py) or one layer (tests/test_chunk_layers_gpu.py) against the oracle's piece for it."""
 import numpy as np
 
 REL = 1e-3
+TOL = 3e-5          # relative to the vector's max |.|: an f32 GEMV of <= 20480 terms is good to ~1e-6, a wrong row or scale is O(1)
+
+
+def _close(got, ref, what, tol=TOL):
+    """one kernel's (or one layer's) output vector against its reference, relative to the reference's max |.|; returns the error"""
+    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
+    assert np.isfinite(got).all(), what
+    scale = max(float(np.abs(ref).max()), 1e-30)
+    err = float(np.abs(got - ref).max()) / scale
+    assert err <= tol, f"{what}: max |d| / max |ref| = {err:.3e} > {tol:.0e}"
+    return err
 
 
 def check_logits(got, ref, what=""):

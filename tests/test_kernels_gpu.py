@@ -19,17 +19,9 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
+from parity import TOL, _close  # noqa: F401  (one number and one reason for it, shared with tests/test_chunk_layers_gpu.py)
+
 pytestmark = pytest.mark.gpu
-TOL = 3e-5          # relative to the vector's max |.|: an f32 GEMV of <= 20480 terms is good to ~1e-6, a wrong row or scale is O(1)
-
-
-def _close(got, ref, what, tol=TOL):
-    got = np.asarray(got, np.float64); ref = np.asarray(ref, np.float64)
-    assert np.isfinite(got).all(), what
-    scale = max(float(np.abs(ref).max()), 1e-30)
-    err = float(np.abs(got - ref).max()) / scale
-    assert err <= tol, f"{what}: max |d| / max |ref| = {err:.3e} > {tol:.0e}"
-    return err
 
 
 def _check_token(oracle, monkeypatch, D, tile=None, L=2, grid=None, slot=0, token=4242, n_slots=1):

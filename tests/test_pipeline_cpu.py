@@ -32,12 +32,8 @@ class OracleStage:
     """pipeline stage computed by the CPU oracle (test backend)"""
 
     def __init__(self, tensors, l0, l1, n_slots):
-        import ctypes as C
         import oracle_lib
-        self.C, self.o = C, oracle_lib.Oracle()
-        self.o.L.oracle_stage_forward.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64,
-                                                  C.POINTER(C.c_void_p), C.c_uint64, C.c_void_p]
-        self.o.L.oracle_stage_forward.restype = C.c_int
+        self.o = oracle_lib.Oracle()
         self.m = self.o.from_tensors(L, D, tensors)
         self.l0, self.l1 = l0, l1
         self.state = self.m.new_state(slots=n_slots)
@@ -45,12 +41,7 @@ class OracleStage:
         self.logits = np.zeros(mf.VOCAB, np.float32)
 
     def forward(self, token, slot, want_pick):
-        C = self.C
-        xn = self.x.numpy()
-        sp = (C.c_void_p * 5)(*[s.ctypes.data for s in self.state])
-        rc = self.o.L.oracle_stage_forward(self.m.h, int(token), xn.ctypes.data, self.l0, self.l1, sp, slot,
-                                           self.logits.ctypes.data if self.l1 == L else None)
-        assert rc == 0
+        self.m.stage_forward(token, self.x.numpy(), self.l0, self.l1, self.state, slot, self.logits if self.l1 == L else None)
         return parity.argmax_ban0(self.logits) if want_pick else None
 
 
