@@ -287,7 +287,6 @@ size_t smem_attout(int S) { return RED_BYTES + (size_t)S * 3072; }
 size_t smem_frk(int S) { return RED_BYTES + 2 * (size_t)S * 3072; }
 size_t smem_fv(int S) { return RED_BYTES + 4 * (size_t)S * 3072; }
 size_t smem_head(int S) { return RED_BYTES + (size_t)S * 3072 + NW * 8; }
-constexpr size_t LDS_BYTES = 160 * 1024;     // LDS of one CU
 
 // tile-form decode kernels (tile.hip.h; classes 1 att, 2 att_out, 3 ffn_rk, 4 ffn_v): ring of S KiB units behind each kernel's fixed LDS.
 // Which widths have a tile form: those whose channels split into whole TH-row tiles per workgroup on this grid --
@@ -303,17 +302,12 @@ TileCfg tile_cfg_for(uint64_t D, int grid)
     if (D == 2048) return TileCfg{4, 4, 2};
     return TileCfg{0, 0, 0};
 }
-size_t tile_fixed(const rwkv_ctx *c, int cls)
-{
-    const int D = (int)c->D, cpw = c->tile_th * c->tile_tpc;
-    return cls == 1 ? tile_fixed_att(D, cpw) : cls == 2 ? tile_fixed_attout(D, cpw) : cls == 3 ? tile_fixed_frk(D, cpw) : tile_fixed_fv(D, cpw);
-}
+// fixed LDS bytes, ring units and launch bytes of a class, from the kernels' own description of their LDS (tile.hip.h tile_lds_of)
+size_t tile_fixed(const rwkv_ctx *c, int cls) { return tile_lds_of(cls, (int)c->D, c->tile_th * c->tile_tpc).ring; }
 int tile_units(const rwkv_ctx *c, int cls)
 {
     const int kbt = (int)((cls == 4 ? 4 * c->D : c->D) * c->tile_th / 1024);                         // fragments of a tile along K
-    const int nu = (cls == 1 ? 3 : cls == 3 ? 5 : 1) * c->tile_tpc * kbt / c->tile_s;                 // units a workgroup streams
-    const int fit = (int)((LDS_BYTES - tile_fixed(c, cls)) / ((size_t)c->tile_s * 1024)) & ~1;         // (even: the loader moves pairs of units)
-    return std::min(fit, nu);
+    return tile_ring_units(tile_fixed(c, cls), c->tile_s, tile_nu(cls, c->tile_tpc, kbt, c->tile_s));
 }
 size_t tile_smem(const rwkv_ctx *c, int cls) { return tile_fixed(c, cls) + (size_t)tile_units(c, cls) * c->tile_s * 1024; }
 // a class runs in tile form when asked to (RWKV_TILE bit cls - 1) and its image is there

@@ -909,6 +909,24 @@ struct AttArgs {
     unsigned *herr;                       // tile form: the context's error word (ring_report)
 };
 
+// The epilogue of one channel g of the K/V/R class, for both forms (k_att: inputs in registers; k_att_t, tile.hip.h: in its LDS stash): the
+// WKV recurrence and the receptance gate (rwkv.cu:242-255) from k's two exponentials e1 = exp(u + w + k), ek = exp(k), the values v and r
+// and the channel's state, decay and att_out constants.  Scalars, not a struct of everything: k_att_t has no registers to spare.  saa, sbb: the
+// state arrays of the call's slot (as pointers, so that the slot's offset stays one scalar add per array: it is wave-uniform, g is not).
+__device__ __forceinline__ void att_epilogue(double *saa, double *sbb, float *ybuf, int g, double aa, double bb, double e1, double ek, float v, float r, double ew, float ra, float oa, double &part, float &pmax)
+{
+    const double vv = (double)v;
+    double y = (aa + e1 * vv) / (bb + e1);
+    y = (1.0 / (1.0 + (double)expf(-r))) * y;       // rwkv.cu:250: exp of a float argument
+    saa[g] = (aa + ek * vv) * ew;
+    sbb[g] = (bb + ek) * ew;
+    const float yf = (float)y;                       // att_out GEMV casts its input to f32 (rwkv.cu:290)
+    const float ys = yf * ra;
+    ybuf[g] = ys;
+    part += (double)(yf * oa);
+    pmax = fmaxf(pmax, fabsf(ys));
+}
+
 // ln1 site -> K,V,R dequant-GEMV -> WKV (rwkv.cu:535-545; kernels :351-392, :58-100, :221-259)
 struct AttIn { unsigned rs[3]; double aa, bb, uw, ew; float ra, oa; };
 template <int S>
@@ -949,18 +967,7 @@ __global__ __launch_bounds__(NT) void k_att(AttArgs a)
         if (lane == 0) {
             const float k = row_value(T[0], in.rs[0], sc[0]) + S0, v = row_value(T[1], in.rs[1], sc[1]) + S1;
             const float r = row_value(T[2], in.rs[2], sc[2]) + S2;
-            const double vv = (double)v;
-            const double e1 = exp(in.uw + (double)k);
-            double y = (in.aa + e1 * vv) / (in.bb + e1);
-            y = (1.0 / (1.0 + (double)expf(-r))) * y;       // rwkv.cu:250: exp of a float argument
-            const double ek = exp((double)k);
-            a.saa[so + g] = (in.aa + ek * vv) * in.ew;
-            a.sbb[so + g] = (in.bb + ek) * in.ew;
-            const float yf = (float)y;                       // att_out GEMV casts its input to f32 (rwkv.cu:290)
-            const float ys = yf * in.ra;
-            a.ybuf[g] = ys;
-            part += (double)(yf * in.oa);
-            pmax = fmaxf(pmax, fabsf(ys));
+            att_epilogue(a.saa + so, a.sbb + so, a.ybuf, g, in.aa, in.bb, exp(in.uw + (double)k), exp((double)k), v, r, in.ew, in.ra, in.oa, part, pmax);
         }
     };
     u32x4 wA[3][S];
@@ -1000,6 +1007,18 @@ struct AttOutArgs {
     unsigned long long *tl;
     unsigned *herr;        // tile form: the context's error word (ring_report)
 };
+
+// The epilogue of one row mi of the att_out class, for both forms (k_attout; k_attout_t, tile.hip.h): the residual through f32 from the row's
+// value val, the state xy, and the row's share of the ln2 site it opens (left in acc).  pre: the row's producer constants of that site, where the
+// form holds them
+__device__ __forceinline__ void attout_epilogue(const AttOutArgs &a, size_t so, int D, int mi, float val, double xold, double lw, double lb, double prev2, double mean1, double rstd1, const SitePre<2> &pre, SiteAcc<2> &acc)
+{
+    const float accf = (float)xold + val;                        // f32 accumulator pre-loaded with x (:548)
+    const double xnew = (double)accf;                            // :553
+    a.x[mi] = xnew;
+    a.sxy[so + mi] = lw * ((xold - mean1) * rstd1) + lb;         // mixatt's state write (:385): ln1 output
+    site_emit<2>(pre, a.dy, D, mi, xnew, prev2, acc);
+}
 
 // att_out dequant-GEMV + residual through f32 (rwkv.cu:548-553), R rows per group; commits state xy;
 // opens the ln2 site for the rows it owns
@@ -1042,13 +1061,8 @@ __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
     auto epi = [&](int, const unsigned long long (&T)[R], const AttOutIn<R> &in) {
 #pragma unroll
         for (int r = 0; r < R; r++) {
-            if (lane == r && r >= in.shift) {
-                const float accf = (float)in.xold + (row_value(T[r], in.rsum, sc) + Sf);   // f32 accumulator pre-loaded with x (:548)
-                const double xnew = (double)accf;                                           // :553
-                a.x[in.mi] = xnew;
-                a.sxy[so + in.mi] = in.lw * ((in.xold - mean1) * rstd1) + in.lb;           // mixatt's state write (:385): ln1 output
-                site_emit<2>(in.pre, a.dy, D, in.mi, xnew, in.prev2, acc);
-            }
+            if (lane == r && r >= in.shift)
+                attout_epilogue(a, so, D, in.mi, row_value(T[r], in.rsum, sc) + Sf, in.xold, in.lw, in.lb, in.prev2, mean1, rstd1, in.pre, acc);
         }
     };
     u32x4 wA[R][S];
@@ -1082,6 +1096,19 @@ struct FfnRKArgs {
     unsigned long long *tl;           // optional phase timeline (see tl_stamp)
     unsigned *herr;                   // tile form: the context's error word (ring_report)
 };
+
+// The epilogues of the ffn k/r class, for both forms (k_ffn_rk; k_ffn_rk_t, tile.hip.h), from a row's value val.  An ffn_k row (hidden unit i; rq / oq =
+// ffn_v's scale / offset of that unit): relu^2, pre-scaled for ffn_v.  The ffn_r row of channel i: the gate.
+__device__ __forceinline__ void ffn_k_epilogue(const FfnRKArgs &a, int i, float val, float rq, float oq, double &part, float &pmax)
+{
+    float h = val * (float)(val > 0.f);   // rwkv.cu:189-190
+    h = h * h;
+    const float hs = h * rq;
+    a.hbuf[i] = hs;
+    part += (double)(h * oq);
+    pmax = fmaxf(pmax, fabsf(hs));
+}
+__device__ __forceinline__ void ffn_r_epilogue(const FfnRKArgs &a, int i, float val) { a.rgate[i] = (float)(1.0 / (1.0 + exp(-(double)val))); }   // rwkv.cu:212
 
 // ln2 site -> ffn_r GEMV + sigmoid, ffn_k GEMV + relu^2 (rwkv.cu:557-573)
 struct FfnRKIn { unsigned rsum; float rq, oq; };
@@ -1119,16 +1146,8 @@ __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
             const float vr = row_value(T[r], in.rsum, r < 4 ? sck : scr) + (r < 4 ? Sk : Sr);
             val = lane == r ? vr : val;
         }
-        if (lane < 4) {
-            float h = val * (float)(val > 0.f);   // rwkv.cu:189-190
-            h = h * h;
-            const float hs = h * in.rq;
-            a.hbuf[4 * g + lane] = hs;
-            part += (double)(h * in.oq);
-            pmax = fmaxf(pmax, fabsf(hs));
-        } else if (lane == 4) {
-            a.rgate[g] = (float)(1.0 / (1.0 + exp(-(double)val)));   // rwkv.cu:212
-        }
+        if (lane < 4) ffn_k_epilogue(a, 4 * g + lane, val, in.rq, in.oq, part, pmax);
+        else if (lane == 4) ffn_r_epilogue(a, g, val);
     };
     u32x4 wA[5][S];
     int gA;
@@ -1169,6 +1188,17 @@ struct FfnVArgs {
     unsigned *herr;        // tile form: the context's error word (ring_report)
 };
 
+// The epilogue of one row g of the ffn_v class, for both forms (k_ffnv; k_ffnv_t, tile.hip.h): blockout from the row's value v and the gate rg,
+// the state dd, and the row's share of the next site (left in acc; pre as in attout_epilogue)
+template <int NVN>
+__device__ __forceinline__ void ffnv_epilogue(const FfnVArgs &a, size_t so, int D, int g, float v, float rg, double xold, double lw, double lb, double prevn, double mean2, double rstd2, const SitePre<NVN> &pre, SiteAcc<NVN> &acc)
+{
+    const double xnew = xold + (double)(v * rg);                 // blockout, rwkv.cu:407 (f32 product)
+    a.x[g] = xnew;
+    a.sdd[so + g] = lw * ((xold - mean2) * rstd2) + lb;          // mixffn's state write (:344): ln2 output
+    site_emit<NVN>(pre, a.dy, D, g, xnew, prevn, acc);
+}
+
 // ffn_v dequant-GEMV, x += v * sigmoid(r) (rwkv.cu:574-577); commits state dd; opens the next site
 template <int NVN> struct FfnVIn { unsigned rsum; double xold, lw, lb, prevn; float rg; SitePre<NVN> pre; };
 template <int S, int NVN>
@@ -1200,13 +1230,8 @@ __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
         return in;
     };
     auto epi = [&](int g, const unsigned long long (&T)[4], const FfnVIn<NVN> &in) {
-        if (lane == 0) {
-            const float v = row_value((T[0] + T[1]) + (T[2] + T[3]), in.rsum, sc) + Sf;
-            const double xnew = in.xold + (double)(v * in.rg);               // blockout, rwkv.cu:407 (f32 product)
-            a.x[g] = xnew;
-            a.sdd[so + g] = in.lw * ((in.xold - mean2) * rstd2) + in.lb;     // mixffn's state write (:344): ln2 output
-            site_emit<NVN>(in.pre, a.dy, D, g, xnew, in.prevn, acc);
-        }
+        if (lane == 0)
+            ffnv_epilogue<NVN>(a, so, D, g, row_value((T[0] + T[1]) + (T[2] + T[3]), in.rsum, sc) + Sf, in.rg, in.xold, in.lw, in.lb, in.prevn, mean2, rstd2, in.pre, acc);
     };
     u32x4 wA[4][S];
     int gA;

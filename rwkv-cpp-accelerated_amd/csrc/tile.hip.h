@@ -23,7 +23,13 @@
 //     bytes as they are: sum u l = dot + 128 rowsum(u) + 128 sum(l) - 16384 N, folded into one constant per vector (cA) and the row-sum
 //     coefficient 4227200 the chunk path uses (seq.hip.h SEQ_CU).  Every row value is the SAME exact integer as in row form: logits and
 //     state are bit-identical to the row-form kernels' for every mix of forms (tests/test_engine_gpu.py);
-//   * staged vector layout [16-byte piece along k][limb][16 B]: a lane's operand is one ds_read_b128.
+//   * staged vector layout [16-byte piece along k][limb][16 B]: a lane's operand is one ds_read_b128;
+//   * what the four kernels have in common is written once: the geometry of an instance (TileGeo), where a unit lies in the image
+//     (tile_unit_src), the consumers' opening (tile_consumer_open), the row value (tile_row_value), and each kernel's dynamic LDS as a
+//     constexpr list of regions (tile_lds_of) that the kernel takes its pointers from, engine.hip its ring length and launch bytes,
+//     and whose alignment and fit every instance asserts at compile time.  The arithmetic behind a row value --
+//     the class's epilogue -- is the row form's own function (kernels.hip.h att_epilogue, attout_epilogue, ffn_k_epilogue /
+//     ffn_r_epilogue, ffnv_epilogue): the forms differ in where its inputs come from (registers there, the LDS stash here), not in what is computed.
 #pragma once
 #include "kernels.hip.h"
 
@@ -373,6 +379,9 @@ __device__ __forceinline__ double tile_cA(const TileCtl *tc, int m, double n)
     return 128.0 * (double)__hip_atomic_load(&tc->sq[m], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) + TILE_CN * n;
 }
 
+// the row's value in the signed-limb form (row form: row_value), without the vector's offset: scale * (M + cA + TILE_CU * rowsum(u))
+__device__ __forceinline__ float tile_row_value(long long M, double cA, unsigned rowsum, double scale) { return (float)(scale * ((double)M + cA + TILE_CU * (double)rowsum)); }
+
 // per-wave state of a consumer's walk through the ring: units it has copied out (what it announces in freed[wave]), the last `landed` it saw
 struct TileWalk { unsigned taken = 0, seen = 0; unsigned long long waited = 0; };
 // wait for unit u, copy its S KiB out of ring slot p, hand the slot back
@@ -565,7 +574,8 @@ __device__ __forceinline__ void tile_consume(int NU, const unsigned char *ring, 
 // Every tile-form kernel: workgroup b owns CPW = TH * TPC consecutive channels -- TPC tiles of TH rows per row class (TH = 16, TPC = 1: D = 4096
 // on 256 CUs, the chunk path's own image; TH = 4: a decode-only image, TPC = 5 at D = 5120, 2 at D = 2048).  KBT = fragments (1 KiB) of a
 // tile along K (K TH / 1024), S = fragments (KiB) per ring unit, SD = ceil(D / 1024).  The argument blocks are the row-form kernels' (site,
-// epilogue inputs and outputs, D, ns = ring units, tl, herr; w unused) + the image.
+// epilogue inputs and outputs, D, ns = ring units, tl, herr; w unused) + the image.  The stash fetch / hold / store blocks of waves 4..6 stay
+// per kernel: what they fetch differs, and how (lanes, registers) was measured per kernel.
 struct TileImage {
     const uint8_t *bimg;          // tile image of this layer's matrix (k_bimage: tile id = class * CB + block, TH rows per tile, signed bytes)
     int CB;                       // TH-row blocks per row class (channels / TH)
@@ -578,11 +588,79 @@ struct FfnVTArgs { FfnVArgs a; TileImage im; };
 // K/V/R over 7 waves in whole tiles is 3 : 2); at 1B5 (two tiles of 8 KiB per class) whole tiles are the better of three slower-than-row-form
 // choices (profiles/r05/tile_run_ab.txt)
 constexpr int tile_run(int TH, int UPT, int TPC) { return TH == 16 || TPC > 2 ? 1 : (UPT < 4 ? UPT : 4); }
-// LDS in front of the ring (bytes), per kernel: must match the carving at the head of each kernel (CPW = channels per workgroup)
-constexpr size_t tile_fixed_frk(int D, int CPW) { return RED_BYTES + (size_t)2 * (D / 16) * 48 + (size_t)13 * CPW * 4 + (size_t)5 * CPW * 12 + sizeof(TileCtl); }
-constexpr size_t tile_fixed_att(int D, int CPW) { return RED_BYTES + (size_t)3 * (D / 16) * 48 + (size_t)3 * CPW * 4 + (size_t)4 * CPW * 8 + (size_t)2 * CPW * 4 + (size_t)2 * CPW * 8 + (size_t)2 * CPW * 4 + (size_t)3 * CPW * 12 + sizeof(TileCtl); }
-constexpr size_t tile_fixed_attout(int D, int CPW) { return RED_BYTES + (size_t)(D / 16) * 48 + (size_t)4 * CPW * 8 + (size_t)CPW * 12 * 4 + (size_t)CPW * 4 + (size_t)CPW * 10 * 8 + (size_t)CPW * 12 + sizeof(TileCtl); }
-constexpr size_t tile_fixed_fv(int D, int CPW) { return RED_BYTES + (size_t)(4 * D / 16) * 48 + (size_t)4 * CPW * 8 + (size_t)CPW * 16 * 4 + (size_t)CPW * 4 + (size_t)CPW * 4 + (size_t)CPW * 10 * 8 + (size_t)CPW * 12 + sizeof(TileCtl); }
+// ---- the geometry and the dynamic LDS of the four kernels, each written once, by class: 1 K/V/R, 2 att_out, 3 ffn k/r, 4 ffn_v (engine.hip's numbering)
+constexpr size_t TILE_LDS_BYTES = 160 * 1024;      // LDS of one CU
+__host__ __device__ constexpr int tile_ncls(int cls) { return cls == 1 ? 3 : cls == 3 ? 5 : 1; }       // row classes of the matrix: K, V, R; four ffn_k + ffn_r
+// units a workgroup streams: row classes x TPC tiles x KBT / S units (the kernels' NU, the bound of engine.hip's ring)
+__host__ __device__ constexpr int tile_nu(int cls, int TPC, int KBT, int S) { return tile_ncls(cls) * TPC * (KBT / S); }
+__host__ __device__ constexpr int tile_xvd(int K) { return (K >> 4) * 12; }      // dwords of one staged vector of K elements: [16-byte piece][limb][4]
+// The LDS of a kernel as byte offsets, regions in address order with nothing between them (a region the class does not have stays 0).  The kernel takes
+// its pointers from here; engine.hip takes the fixed size (= ring), from it the ring's length (tile_ring_units) and the launch's bytes.
+struct TileLds {
+    size_t xq = 0, rs = 0, sd = 0, sf = 0, ed = 0, ef = 0, sp = 0, rg = 0, scr = 0, tsum = 0, tc = 0, ring = 0;
+    bool aligned = true;         // every region begins on the boundary its accesses need
+    __host__ __device__ constexpr size_t take(size_t bytes, size_t align = 4) { aligned = aligned && ring % align == 0; const size_t o = ring; ring += bytes; return o; }
+};
+__host__ __device__ constexpr TileLds tile_lds_of(int cls, int D, int CPW)       // D = width, CPW = channels per workgroup
+{
+    TileLds l;
+    l.take(RED_BYTES, 16);                                       // reduction scratch (kernels.hip.h RED_*)
+    // the staged vectors: k, v, r | the gated wkv | ffn k, ffn r | the 4 D hidden units as ONE vector
+    l.xq = l.take((size_t)(cls == 1 ? 3 : cls == 3 ? 2 : 1) * tile_xvd(cls == 4 ? 4 * D : D) * 4, 16);
+    if (cls == 1) {              // the stash of the epilogues' inputs (waves 4..6) ...
+        l.rs = l.take((size_t)3 * CPW * 4);                      // row sums [CPW][3] u32
+        l.sd = l.take((size_t)4 * CPW * 8, 8);                   // aa, bb, uw, ew [4][CPW] f64
+        l.sf = l.take((size_t)2 * CPW * 4);                      // ra, oa [2][CPW] f32
+        l.ed = l.take((size_t)2 * CPW * 8, 8);                   // ... and what the K finishers leave: e1, ek [2][CPW] f64,
+        l.ef = l.take((size_t)2 * CPW * 4);                      // the V and R finishers: v, r [2][CPW] f32
+    } else if (cls == 3) {
+        l.rs = l.take((size_t)5 * CPW * 4);                      // row sums [CPW][5] u32
+        l.sf = l.take((size_t)2 * 4 * CPW * 4);                  // ffn_v's scale, offset of the 4 CPW hidden units [2][4 CPW] f32
+    } else {
+        l.sd = l.take((size_t)4 * CPW * 8, 8);                   // xold, lw, lb, prev of the site this kernel opens [4][CPW] f64
+        l.sp = l.take((size_t)CPW * (cls == 2 ? 12 : 16) * 4, 16);   // that site's producer constants P [CPW][12 | up to 16] f32, read as f32x4
+        l.rs = l.take((size_t)CPW * 4);                          // row sums [CPW] u32
+        if (cls == 4) l.rg = l.take((size_t)CPW * 4);            // rgate [CPW] f32 (behind rs: one wave stores both)
+        l.scr = l.take((size_t)CPW * 10 * 8, 8);                 // publish scratch (tile_site_leave): [CPW][8] f64 | [CPW][4] f32
+    }
+    l.tsum = l.take((size_t)tile_ncls(cls) * CPW * 12);          // tile sums [rows][3 limbs] i32
+    l.tc = l.take(sizeof(TileCtl), 16);
+    l.take(0, 16);                                               // the ring: the DMA writes 16-byte pieces
+    return l;
+}
+template <class T> __device__ __forceinline__ T *tile_lds(unsigned char *smem, size_t off) { return reinterpret_cast<T *>(smem + off); }
+// a ring's length in units: what fits behind the fixed part (even: the loader moves pairs of units), at most the whole stream
+__host__ __device__ constexpr int tile_ring_units(size_t fixed, int S, int nu)
+{
+    const int fit = (int)((TILE_LDS_BYTES - fixed) / ((size_t)S * 1024)) & ~1;
+    return fit < nu ? fit : nu;
+}
+// The geometry of a kernel instance; D = the width it is compiled for.  Asserts what the code relies on silently: whole units, the control block's
+// arrays, f64 regions on 8 bytes, f32x4 regions / TileCtl / the ring on 16, and a ring of at least two units that holds the head.
+template <int CLS_, int S_, int KBT_, int TH_, int TPC_> struct TileGeo {
+    static constexpr int CLS = CLS_, NCLS = tile_ncls(CLS), S = S_, KBT = KBT_, TH = TH_, TPC = TPC_, D = KBT * 1024 / TH / (CLS == 4 ? 4 : 1);
+    static constexpr int CPW = TH * TPC, NTILE = NCLS * TPC, UPT = KBT / S, NU = tile_nu(CLS, TPC, KBT, S), RUN = tile_run(TH, UPT, TPC);
+    static constexpr int HEAD_KNOB = CLS == 1 ? RWKV_TILE_HEAD_ATT : CLS == 2 ? RWKV_TILE_HEAD_ATTOUT : CLS == 3 ? RWKV_TILE_HEAD_FRK : RWKV_TILE_HEAD_FV;
+    static constexpr int HEAD = TH == 16 && RUN == 1 ? HEAD_KNOB : 0, NE = HEAD / TILE_NSTASH > 0 ? HEAD / TILE_NSTASH : 1;
+    static_assert(HEAD <= NU && HEAD % TILE_NSTASH == 0, "the head: whole rounds of the three non-staging waves, inside the stream");
+    static_assert(KBT % S == 0 && NTILE <= 32 && TPC <= 8, "whole units per tile; TileCtl::tcnt / done");
+    static_assert(tile_lds_of(CLS, D, CPW).aligned && tile_ring_units(tile_lds_of(CLS, D, CPW).ring, S, NU) >= (HEAD > 2 ? HEAD : 2), "LDS layout");
+};
+// where unit u of the workgroup's stream lies in the image: tile t = class t / TPC, block cb0 + t % TPC (one class: tile t = block cb0 + t)
+template <class G> __device__ __forceinline__ const uint8_t *tile_unit_src(const TileImage &im, int cb0, int u)
+{
+    const int t = u / G::UPT, c = u - t * G::UPT, cls = G::NCLS == 1 ? 0 : t / G::TPC, sub = G::NCLS == 1 ? t : t % G::TPC;
+    return im.bimg + ((size_t)(cls * im.CB + cb0 + sub) * G::KBT + (size_t)c * G::S) * 1024;
+}
+// what every consumer wave does between its part of the prologue and its first unit: the non-staging waves take the stream's head into
+// registers, all wait for the vectors and the stash.  Returns the prologue's published scalars (offsets [0..3], amax [4..7] per vector).
+template <class G> __device__ __forceinline__ const float *tile_consumer_open(double *red, const unsigned char *ring, int ns, TileCtl *tc, int wave, int lane,
+                                                                            TileWalk &wk, unsigned &fail, u32x4 (&wpre)[G::NE][G::S])
+{
+    if (wave >= TILE_NWP) tile_pretake<G::S, G::HEAD>(G::NU, ring, ns, tc, wave, lane, wk, fail, wpre);
+    wait_count(&tc->staged, TILE_NWP + TILE_NSTASH, fail);
+    return reinterpret_cast<const float *>(red + RED_BC);
+}
 
 // ln2 site -> ffn_r GEMV + sigmoid, ffn_k GEMV + relu^2 (rwkv.cu:557-573): 5 row classes (0..3 = ffn_k outputs 4 i + q, 4 = ffn_r output i) x TPC tiles
 template <int SD, int S, int KBT, int TH, int TPC>
@@ -590,31 +668,24 @@ __global__ __launch_bounds__(NT) void k_ffn_rk_t(FfnRKTArgs ta)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FfnRKArgs &a = ta.a;
-    constexpr int CPW = TH * TPC, NTILE = 5 * TPC, UPT = KBT / S, NU = NTILE * UPT, RUN = tile_run(TH, UPT, TPC);
-    constexpr int HEAD = TH == 16 && RUN == 1 ? RWKV_TILE_HEAD_FRK : 0, NE = HEAD / TILE_NSTASH > 0 ? HEAD / TILE_NSTASH : 1;
-    static_assert(HEAD <= NU && HEAD % TILE_NSTASH == 0, "the head: whole rounds of the three non-staging waves, inside the stream");
-    static_assert(KBT % S == 0 && NTILE <= 32, "whole units per tile; TileCtl::tcnt");
+    using G = TileGeo<3, S, KBT, TH, TPC>;
+    constexpr int CPW = G::CPW;
     double *red = reinterpret_cast<double *>(smem);
-    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
-    const int xvd_t = (D >> 4) * 12;                       // dwords of one staged vector: [16-byte piece][limb][4]
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
-    // LDS: [scratch][2 staged vectors][stash: rs[5 CPW], r_fv[4 CPW], o_fv[4 CPW]][tile sums][TileCtl][ring]
-    unsigned *stash = xq + 2 * xvd_t;
-    int *tsum = reinterpret_cast<int *>(stash + 13 * CPW);
-    TileCtl *tc = reinterpret_cast<TileCtl *>(tsum + NTILE * TH * 3);
-    unsigned char *ring = reinterpret_cast<unsigned char *>(tc + 1);
+    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id(), xvd_t = tile_xvd(D);
+    const TileLds L = tile_lds_of(G::CLS, D, CPW);
+    unsigned *xq = tile_lds<unsigned>(smem, L.xq), *srs = tile_lds<unsigned>(smem, L.rs);
+    float *sf = tile_lds<float>(smem, L.sf);                 // r_fv | o_fv
+    int *tsum = tile_lds<int>(smem, L.tsum);
+    TileCtl *tc = tile_lds<TileCtl>(smem, L.tc);
+    unsigned char *ring = smem + L.ring;
     RWKV_ARGS_NOW(a.x, a.st.C, a.st.TC, a.st.maxC, a.dy.B, a.dy.pd, a.dy.pf, a.dy.n_part);
     const int cb0 = blockIdx.x * TPC, ch0 = blockIdx.x * CPW;
     tl_stamp(a.tl, 0);
-    auto unit_src = [&](int u) {          // tile t = class t / TPC, block cb0 + t % TPC
-        const int t = u / UPT, c = u - t * UPT;
-        return ta.im.bimg + ((size_t)((t / TPC) * ta.im.CB + cb0 + t % TPC) * KBT + (size_t)c * S) * 1024;
-    };
     double part = 0.0;
     float pmax = 0.f;
     unsigned fail = 0u;
     if (wave == NC) {
-        fail = tile_loader<S, UPT, RUN, TH, RWKV_TILE_PRE_FRK, HEAD>(NU, NTILE, ring, a.ns, tc, tsum, lane, unit_src, a.tl);
+        fail = tile_loader<S, G::UPT, G::RUN, TH, RWKV_TILE_PRE_FRK, G::HEAD>(G::NU, G::NTILE, ring, a.ns, tc, tsum, lane, [&](int u) { return tile_unit_src<G>(ta.im, cb0, u); }, a.tl);
         tl_stamp(a.tl, 2);
     } else {
         if (wave < TILE_NWP) {
@@ -631,16 +702,14 @@ __global__ __launch_bounds__(NT) void k_ffn_rk_t(FfnRKTArgs ta)
             TL_BAR(a.tl, 1);
             __syncthreads();   // order
             TL_BAR(a.tl, 2);
-            unsigned *dst = stash + (wave == 4 ? 0 : wave == 5 ? 5 * CPW : 9 * CPW);
+            unsigned *dst = wave == 4 ? srs : reinterpret_cast<unsigned *>(sf) + (wave == 5 ? 0 : 4 * CPW);
             if (lane < n) dst[lane] = v0;
             if (lane + 64 < n) dst[lane + 64] = v1;
             tile_stash_done(tc, lane);
         }
-        float *bc = reinterpret_cast<float *>(red + RED_BC);
         TileWalk wk;
-        u32x4 wpre[NE][S];
-        if (wave >= TILE_NWP) tile_pretake<S, HEAD>(NU, ring, a.ns, tc, wave, lane, wk, fail, wpre);
-        wait_count(&tc->staged, TILE_NWP + TILE_NSTASH, fail);
+        u32x4 wpre[G::NE][S];
+        const float *bc = tile_consumer_open<G>(red, ring, a.ns, tc, wave, lane, wk, fail, wpre);
         const double sck = scale_of(bc[4]), scr = scale_of(bc[5]);
         const float Sk = bc[0], Sr = bc[1];
         const double cAk = tile_cA(tc, 0, (double)D), cAr = tile_cA(tc, 1, (double)D);
@@ -649,23 +718,18 @@ __global__ __launch_bounds__(NT) void k_ffn_rk_t(FfnRKTArgs ta)
             if (lane < TH) {
                 const int q = t / TPC, li = (t % TPC) * TH + lane;
                 const long long M = tile_row_sum<TH>(tsum, t, lane);
-                const unsigned rs = stash[li * 5 + q];
+                const unsigned rs = srs[li * 5 + q];
                 if (q < 4) {
-                    const float val = (float)(sck * ((double)M + cAk + TILE_CU * (double)rs)) + Sk;
-                    float h = val * (float)(val > 0.f);   // rwkv.cu:189-190
-                    h = h * h;
+                    const float val = tile_row_value(M, cAk, rs, sck) + Sk;
                     const int hi = li * 4 + q;
-                    const float hs = h * __uint_as_float(stash[5 * CPW + hi]);
-                    a.hbuf[4 * ch0 + hi] = hs;
-                    part += (double)(h * __uint_as_float(stash[9 * CPW + hi]));
-                    pmax = fmaxf(pmax, fabsf(hs));
+                    ffn_k_epilogue(a, 4 * ch0 + hi, val, sf[hi], sf[4 * CPW + hi], part, pmax);
                 } else {
-                    const float val = (float)(scr * ((double)M + cAr + TILE_CU * (double)rs)) + Sr;
-                    a.rgate[ch0 + li] = (float)(1.0 / (1.0 + exp(-(double)val)));   // rwkv.cu:212
+                    const float val = tile_row_value(M, cAr, rs, scr) + Sr;
+                    ffn_r_epilogue(a, ch0 + li, val);
                 }
             }
         };
-        tile_consume<TH, S, UPT, RUN, HEAD>(NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int t) { return t / TPC < 4 ? 0 : 1; }, on_tile, a.tl);
+        tile_consume<TH, S, G::UPT, G::RUN, G::HEAD>(G::NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int t) { return t / TPC < 4 ? 0 : 1; }, on_tile, a.tl);
     }
     tl_stamp(a.tl, 6);
     __syncthreads();   // every wave is past its last read of the reduction scratch
@@ -682,35 +746,25 @@ __global__ __launch_bounds__(NT) void k_att_t(AttTArgs ta)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const AttArgs &a = ta.a;
-    constexpr int CPW = TH * TPC, NTILE = 3 * TPC, UPT = KBT / S, NU = NTILE * UPT, RUN = tile_run(TH, UPT, TPC);
-    constexpr int HEAD = TH == 16 && RUN == 1 ? RWKV_TILE_HEAD_ATT : 0, NE = HEAD / TILE_NSTASH > 0 ? HEAD / TILE_NSTASH : 1;
-    static_assert(HEAD <= NU && HEAD % TILE_NSTASH == 0, "the head: whole rounds of the three non-staging waves, inside the stream");
-    static_assert(KBT % S == 0 && NTILE <= 32 && TPC <= 8, "whole units per tile; TileCtl::tcnt / done");
+    using G = TileGeo<1, S, KBT, TH, TPC>;
+    constexpr int CPW = G::CPW;
     double *red = reinterpret_cast<double *>(smem);
-    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
-    const int xvd_t = (D >> 4) * 12;
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
-    // LDS: [scratch][3 staged vectors][stash: rs[3 CPW] | aa, bb, uw, ew [4][CPW] f64 | ra, oa [2][CPW] f32 | e1, ek [2][CPW] f64 | v, r [2][CPW] f32][tile sums][TileCtl][ring]
-    unsigned *stash = xq + 3 * xvd_t;
-    double *sd = reinterpret_cast<double *>(stash + 3 * CPW);       // aa, bb, uw, ew    (3 CPW words: CPW is a multiple of 4, 8-byte aligned)
-    float *sf = reinterpret_cast<float *>(sd + 4 * CPW);            // ra, oa
-    double *ed = reinterpret_cast<double *>(sf + 2 * CPW);          // e1, ek
-    float *ef = reinterpret_cast<float *>(ed + 2 * CPW);            // v, r
-    int *tsum = reinterpret_cast<int *>(ef + 2 * CPW);
-    TileCtl *tc = reinterpret_cast<TileCtl *>(tsum + NTILE * TH * 3);
-    unsigned char *ring = reinterpret_cast<unsigned char *>(tc + 1);
+    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id(), xvd_t = tile_xvd(D);
+    const TileLds L = tile_lds_of(G::CLS, D, CPW);
+    unsigned *xq = tile_lds<unsigned>(smem, L.xq), *stash = tile_lds<unsigned>(smem, L.rs);
+    double *sd = tile_lds<double>(smem, L.sd), *ed = tile_lds<double>(smem, L.ed);
+    float *sf = tile_lds<float>(smem, L.sf), *ef = tile_lds<float>(smem, L.ef);
+    int *tsum = tile_lds<int>(smem, L.tsum);
+    TileCtl *tc = tile_lds<TileCtl>(smem, L.tc);
+    unsigned char *ring = smem + L.ring;
     RWKV_ARGS_NOW(a.x, a.st.C, a.st.TC, a.st.maxC, a.dy.B, a.dy.pd, a.dy.pf, a.dy.n_part);
     const int cb0 = blockIdx.x * TPC, ch0 = blockIdx.x * CPW;
     tl_stamp(a.tl, 0);
-    auto unit_src = [&](int u) {
-        const int t = u / UPT, c = u - t * UPT;
-        return ta.im.bimg + ((size_t)((t / TPC) * ta.im.CB + cb0 + t % TPC) * KBT + (size_t)c * S) * 1024;
-    };
     double part = 0.0;
     float pmax = 0.f;
     unsigned fail = 0u;
     if (wave == NC) {
-        fail = tile_loader<S, UPT, RUN, TH, (TH == 16 ? RWKV_TILE_PRE_ATT : RWKV_TILE_PRE4_ATT), HEAD>(NU, NTILE, ring, a.ns, tc, tsum, lane, unit_src, a.tl);
+        fail = tile_loader<S, G::UPT, G::RUN, TH, (TH == 16 ? RWKV_TILE_PRE_ATT : RWKV_TILE_PRE4_ATT), G::HEAD>(G::NU, G::NTILE, ring, a.ns, tc, tsum, lane, [&](int u) { return tile_unit_src<G>(ta.im, cb0, u); }, a.tl);
         tl_stamp(a.tl, 2);
     } else {
         const size_t so = (size_t)a.ctl->slot * a.slot_stride;
@@ -718,13 +772,12 @@ __global__ __launch_bounds__(NT) void k_att_t(AttTArgs ta)
             tile_site<3, SD>(a.st, a.dy, a.x, D, red, xq, xvd_t, true, tc, a.tl);
         } else {
             // epilogue inputs of the CPW channels: wave 4 the 3 CPW row sums, wave 5 the state (aa | bb) and the decay terms (uw | ew), wave 6 att_out's scale / offset
-            unsigned v0 = 0u, v1 = 0u;
+            unsigned v0 = 0u;
             double d0 = 0.0, d1 = 0.0;
             auto dsrc = [&](int i) { const int g = i / CPW, j = i - g * CPW; return g == 0 ? a.saa[so + ch0 + j] : g == 1 ? a.sbb[so + ch0 + j] : g == 2 ? a.uw[ch0 + j] : a.ew[ch0 + j]; };
             if (wave == 4) { if (lane < 3 * CPW) v0 = a.rs[ch0 * 3 + lane]; }
             else if (wave == 5) { if (lane < 4 * CPW) d0 = dsrc(lane); if (lane + 64 < 4 * CPW) d1 = dsrc(lane + 64); }
             else if (lane < 2 * CPW) v0 = __float_as_uint(lane < CPW ? a.r_att[ch0 + lane] : a.o_att[ch0 + lane - CPW]);
-            (void)v1;
             TL_BAR(a.tl, 1);
             __syncthreads();   // order
             TL_BAR(a.tl, 2);
@@ -733,11 +786,9 @@ __global__ __launch_bounds__(NT) void k_att_t(AttTArgs ta)
             else if (lane < 2 * CPW) sf[lane] = __uint_as_float(v0);
             tile_stash_done(tc, lane);
         }
-        float *bc = reinterpret_cast<float *>(red + RED_BC);
         TileWalk wk;
-        u32x4 wpre[NE][S];
-        if (wave >= TILE_NWP) tile_pretake<S, HEAD>(NU, ring, a.ns, tc, wave, lane, wk, fail, wpre);
-        wait_count(&tc->staged, TILE_NWP + TILE_NSTASH, fail);
+        u32x4 wpre[G::NE][S];
+        const float *bc = tile_consumer_open<G>(red, ring, a.ns, tc, wave, lane, wk, fail, wpre);
         tl_stamp(a.tl, 5);
         auto on_tile = [&](int t) {
             const int q = t / TPC, sub = t % TPC;
@@ -747,7 +798,7 @@ __global__ __launch_bounds__(NT) void k_att_t(AttTArgs ta)
                 // (the class's scale, offset scalar and cA constant come out of LDS with the tile's sums, in the same batch of reads: a tile
                 // completes 3 TPC times per workgroup, and nine more live registers through the streaming loop made this kernel spill)
                 const double scq = scale_of(bc[4 + q]), cAq = tile_cA(tc, q, (double)D);
-                const float val = (float)(scq * ((double)M + cAq + TILE_CU * (double)stash[li * 3 + q])) + bc[q];
+                const float val = tile_row_value(M, cAq, stash[li * 3 + q], scq) + bc[q];
                 if (q == 0) { ed[li] = exp(sd[2 * CPW + li] + (double)val); ed[CPW + li] = exp((double)val); }      // exp(u + w + k), exp(k)
                 else ef[(q - 1) * CPW + li] = val;
             }
@@ -759,22 +810,13 @@ __global__ __launch_bounds__(NT) void k_att_t(AttTArgs ta)
                 const double aa = sd[li], bb = sd[CPW + li], ew = sd[3 * CPW + li];
                 const double e1 = *reinterpret_cast<volatile double *>(ed + li), ek = *reinterpret_cast<volatile double *>(ed + CPW + li);
                 const float v = *reinterpret_cast<volatile float *>(ef + li), r = *reinterpret_cast<volatile float *>(ef + CPW + li);
-                const double vv = (double)v;
-                double y = (aa + e1 * vv) / (bb + e1);
-                y = (1.0 / (1.0 + (double)expf(-r))) * y;       // rwkv.cu:250: exp of a float argument
-                a.saa[so + g] = (aa + ek * vv) * ew;
-                a.sbb[so + g] = (bb + ek) * ew;
-                const float yf = (float)y;                       // att_out GEMV casts its input to f32 (rwkv.cu:290)
-                const float ys = yf * sf[li];
-                a.ybuf[g] = ys;
-                part += (double)(yf * sf[CPW + li]);
-                pmax = fmaxf(pmax, fabsf(ys));
+                att_epilogue(a.saa + so, a.sbb + so, a.ybuf, g, aa, bb, e1, ek, v, r, ew, sf[li], sf[CPW + li], part, pmax);
             }
         };
-        tile_consume<TH, S, UPT, RUN, HEAD>(NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int t) { return t / TPC; }, on_tile, a.tl);
+        tile_consume<TH, S, G::UPT, G::RUN, G::HEAD>(G::NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int t) { return t / TPC; }, on_tile, a.tl);
     }
     tl_stamp(a.tl, 6);
-    __syncthreads();
+    __syncthreads();   // every wave is past its last read of the reduction scratch
     block_sum_max(part, pmax, red + RED_PART);
     if (threadIdx.x == 0) { a.partS[blockIdx.x] = part; a.partM[blockIdx.x] = pmax; }
     ring_report(fail, a.herr);
@@ -812,31 +854,23 @@ __global__ __launch_bounds__(NT) void k_attout_t(AttOutTArgs ta)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const AttOutArgs &a = ta.a;
-    constexpr int CPW = TH * TPC, NTILE = TPC, UPT = KBT / S, NU = NTILE * UPT, RUN = tile_run(TH, UPT, TPC);
-    constexpr int HEAD = TH == 16 && RUN == 1 ? RWKV_TILE_HEAD_ATTOUT : 0, NE = HEAD / TILE_NSTASH > 0 ? HEAD / TILE_NSTASH : 1;
-    static_assert(HEAD <= NU && HEAD % TILE_NSTASH == 0, "the head: whole rounds of the three non-staging waves, inside the stream");
+    using G = TileGeo<2, S, KBT, TH, TPC>;
+    constexpr int CPW = G::CPW;
     double *red = reinterpret_cast<double *>(smem);
-    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
-    const int xvd_t = (D >> 4) * 12;
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
-    // LDS: [scratch][1 staged vector][stash: xold, lw, lb, prev2 [4][CPW] f64 | P [CPW][12] f32 | rs[CPW]][publish scratch CPW x 10 f64][tile sums][TileCtl][ring]
-    double *sd = reinterpret_cast<double *>(xq + xvd_t);
-    float *sp = reinterpret_cast<float *>(sd + 4 * CPW);
-    unsigned *srs = reinterpret_cast<unsigned *>(sp + CPW * 12);
-    double *scr = reinterpret_cast<double *>(srs + CPW);
-    int *tsum = reinterpret_cast<int *>(scr + CPW * 10);
-    TileCtl *tc = reinterpret_cast<TileCtl *>(tsum + NTILE * TH * 3);
-    unsigned char *ring = reinterpret_cast<unsigned char *>(tc + 1);
+    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id(), xvd_t = tile_xvd(D);
+    const TileLds L = tile_lds_of(G::CLS, D, CPW);
+    unsigned *xq = tile_lds<unsigned>(smem, L.xq), *srs = tile_lds<unsigned>(smem, L.rs);
+    double *sd = tile_lds<double>(smem, L.sd), *scr = tile_lds<double>(smem, L.scr);
+    float *sp = tile_lds<float>(smem, L.sp);
+    int *tsum = tile_lds<int>(smem, L.tsum);
+    TileCtl *tc = tile_lds<TileCtl>(smem, L.tc);
+    unsigned char *ring = smem + L.ring;
     RWKV_ARGS_NOW(a.ybuf, a.partS, a.partM, a.n_part);
     const int cb0 = blockIdx.x * TPC, ch0 = blockIdx.x * CPW;
     tl_stamp(a.tl, 0);
-    auto unit_src = [&](int u) {
-        const int t = u / UPT, c = u - t * UPT;
-        return ta.im.bimg + ((size_t)(cb0 + t) * KBT + (size_t)c * S) * 1024;
-    };
     unsigned fail = 0u;
     if (wave == NC) {
-        fail = tile_loader<S, UPT, RUN, TH, RWKV_TILE_PRE_ATTOUT, HEAD>(NU, NTILE, ring, a.ns, tc, tsum, lane, unit_src, a.tl);
+        fail = tile_loader<S, G::UPT, G::RUN, TH, RWKV_TILE_PRE_ATTOUT, G::HEAD>(G::NU, G::NTILE, ring, a.ns, tc, tsum, lane, [&](int u) { return tile_unit_src<G>(ta.im, cb0, u); }, a.tl);
         tl_stamp(a.tl, 2);
     } else {
         const double mean1 = a.lnstat[0], rstd1 = a.lnstat[1];
@@ -859,11 +893,9 @@ __global__ __launch_bounds__(NT) void k_attout_t(AttOutTArgs ta)
             else if (lane < CPW) srs[lane] = v0;
             tile_stash_done(tc, lane);
         }
-        float *bc = reinterpret_cast<float *>(red + RED_BC);
         TileWalk wk;
-        u32x4 wpre[NE][S];
-        if (wave >= TILE_NWP) tile_pretake<S, HEAD>(NU, ring, a.ns, tc, wave, lane, wk, fail, wpre);
-        wait_count(&tc->staged, TILE_NWP + TILE_NSTASH, fail);
+        u32x4 wpre[G::NE][S];
+        const float *bc = tile_consumer_open<G>(red, ring, a.ns, tc, wave, lane, wk, fail, wpre);
         const float Sf = bc[0];
         const double sc = scale_of(bc[4]), cA = tile_cA(tc, 0, (double)D);
         tl_stamp(a.tl, 5);
@@ -871,21 +903,14 @@ __global__ __launch_bounds__(NT) void k_attout_t(AttOutTArgs ta)
             if (lane < TH) {
                 const int li = t * TH + lane, mi = ch0 + li;
                 const long long M = tile_row_sum<TH>(tsum, t, lane);
-                const double xold = sd[li];
-                const float accf = (float)xold + ((float)(sc * ((double)M + cA + TILE_CU * (double)srs[li])) + Sf);   // f32 accumulator pre-loaded with x (:548)
-                const double xnew = (double)accf;                                                                    // :553
-                a.x[mi] = xnew;
-                a.sxy[so + mi] = sd[CPW + li] * ((xold - mean1) * rstd1) + sd[2 * CPW + li];                         // mixatt's state write (:385): ln1 output
-                SitePre<2> pre;
-#pragma unroll
-                for (int k = 0; k < 3; k++) pre.p[k] = reinterpret_cast<const f32x4 *>(sp + li * 12)[k];
                 SiteAcc<2> acc;
                 acc.clear();
-                site_emit<2>(pre, a.dy, D, mi, xnew, sd[3 * CPW + li], acc);
+                attout_epilogue(a, so, D, mi, tile_row_value(M, cA, srs[li], sc) + Sf, sd[li], sd[CPW + li], sd[2 * CPW + li], sd[3 * CPW + li], mean1, rstd1,
+                                *reinterpret_cast<const SitePre<2> *>(sp + li * 12), acc);
                 tile_site_leave<2>(acc, scr, CPW, li);
             }
         };
-        tile_consume<TH, S, UPT, RUN, HEAD>(NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int) { return 0; }, on_tile, a.tl);
+        tile_consume<TH, S, G::UPT, G::RUN, G::HEAD>(G::NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int) { return 0; }, on_tile, a.tl);
     }
     tl_stamp(a.tl, 6);
     __syncthreads();
@@ -900,32 +925,23 @@ __global__ __launch_bounds__(NT) void k_ffnv_t(FfnVTArgs ta)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const FfnVArgs &a = ta.a;
-    constexpr int CPW = TH * TPC, NTILE = TPC, UPT = KBT / S, NU = NTILE * UPT, RUN = tile_run(TH, UPT, TPC), PW = site_pw<NVN>();
-    constexpr int HEAD = TH == 16 && RUN == 1 ? RWKV_TILE_HEAD_FV : 0, NE = HEAD / TILE_NSTASH > 0 ? HEAD / TILE_NSTASH : 1;
-    static_assert(HEAD <= NU && HEAD % TILE_NSTASH == 0, "the head: whole rounds of the three non-staging waves, inside the stream");
+    using G = TileGeo<4, S, KBT, TH, TPC>;
+    constexpr int CPW = G::CPW, PW = site_pw<NVN>();
     double *red = reinterpret_cast<double *>(smem);
-    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
-    const int xvd_t = (D >> 2) * 12;                       // the 4 D hidden units as ONE vector
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
-    // LDS: [scratch][1 staged vector of 4 D][stash: xold, lw, lb, prevn [4][CPW] f64 | P [CPW][16] f32 | rs[CPW] | rgate[CPW]][publish scratch][tile sums][TileCtl][ring]
-    double *sd = reinterpret_cast<double *>(xq + xvd_t);
-    float *sp = reinterpret_cast<float *>(sd + 4 * CPW);
-    unsigned *srs = reinterpret_cast<unsigned *>(sp + CPW * 16);
-    float *srg = reinterpret_cast<float *>(srs + CPW);
-    double *scr = reinterpret_cast<double *>(srg + CPW);
-    int *tsum = reinterpret_cast<int *>(scr + CPW * 10);
-    TileCtl *tc = reinterpret_cast<TileCtl *>(tsum + NTILE * TH * 3);
-    unsigned char *ring = reinterpret_cast<unsigned char *>(tc + 1);
+    const int D = a.D, lane = threadIdx.x & 63, wave = wave_id(), xvd_t = tile_xvd(4 * D);       // (the 4 D hidden units as ONE vector)
+    const TileLds L = tile_lds_of(G::CLS, D, CPW);
+    unsigned *xq = tile_lds<unsigned>(smem, L.xq), *srs = tile_lds<unsigned>(smem, L.rs);
+    double *sd = tile_lds<double>(smem, L.sd), *scr = tile_lds<double>(smem, L.scr);
+    float *sp = tile_lds<float>(smem, L.sp), *srg = tile_lds<float>(smem, L.rg);
+    int *tsum = tile_lds<int>(smem, L.tsum);
+    TileCtl *tc = tile_lds<TileCtl>(smem, L.tc);
+    unsigned char *ring = smem + L.ring;
     RWKV_ARGS_NOW(a.hbuf, a.partS, a.partM, a.n_part);
     const int cb0 = blockIdx.x * TPC, ch0 = blockIdx.x * CPW;
     tl_stamp(a.tl, 0);
-    auto unit_src = [&](int u) {
-        const int t = u / UPT, c = u - t * UPT;
-        return ta.im.bimg + ((size_t)(cb0 + t) * KBT + (size_t)c * S) * 1024;
-    };
     unsigned fail = 0u;
     if (wave == NC) {
-        fail = tile_loader<S, UPT, RUN, TH, (TH == 16 ? RWKV_TILE_PRE_FV : RWKV_TILE_PRE_FV4), HEAD>(NU, NTILE, ring, a.ns, tc, tsum, lane, unit_src, a.tl);
+        fail = tile_loader<S, G::UPT, G::RUN, TH, (TH == 16 ? RWKV_TILE_PRE_FV : RWKV_TILE_PRE_FV4), G::HEAD>(G::NU, G::NTILE, ring, a.ns, tc, tsum, lane, [&](int u) { return tile_unit_src<G>(ta.im, cb0, u); }, a.tl);
         tl_stamp(a.tl, 2);
     } else {
         const double mean2 = a.lnstat[0], rstd2 = a.lnstat[1];
@@ -949,11 +965,9 @@ __global__ __launch_bounds__(NT) void k_ffnv_t(FfnVTArgs ta)
             else if (lane < 2 * CPW) srs[lane] = v0;          // (rs[CPW] and rgate[CPW] are adjacent)
             tile_stash_done(tc, lane);
         }
-        float *bc = reinterpret_cast<float *>(red + RED_BC);
         TileWalk wk;
-        u32x4 wpre[NE][S];
-        if (wave >= TILE_NWP) tile_pretake<S, HEAD>(NU, ring, a.ns, tc, wave, lane, wk, fail, wpre);
-        wait_count(&tc->staged, TILE_NWP + TILE_NSTASH, fail);
+        u32x4 wpre[G::NE][S];
+        const float *bc = tile_consumer_open<G>(red, ring, a.ns, tc, wave, lane, wk, fail, wpre);
         const float Sf = bc[0];
         const double sc = scale_of(bc[4]), cA = tile_cA(tc, 0, 4.0 * (double)D);
         tl_stamp(a.tl, 5);
@@ -961,21 +975,14 @@ __global__ __launch_bounds__(NT) void k_ffnv_t(FfnVTArgs ta)
             if (lane < TH) {
                 const int li = t * TH + lane, g = ch0 + li;
                 const long long M = tile_row_sum<TH>(tsum, t, lane);
-                const float v = (float)(sc * ((double)M + cA + TILE_CU * (double)srs[li])) + Sf;
-                const double xold = sd[li];
-                const double xnew = xold + (double)(v * srg[li]);                         // blockout, rwkv.cu:407 (f32 product)
-                a.x[g] = xnew;
-                a.sdd[so + g] = sd[CPW + li] * ((xold - mean2) * rstd2) + sd[2 * CPW + li];   // mixffn's state write (:344): ln2 output
-                SitePre<NVN> pre;
-#pragma unroll
-                for (int k = 0; k < PW / 4; k++) pre.p[k] = reinterpret_cast<const f32x4 *>(sp + li * PW)[k];
                 SiteAcc<NVN> acc;
                 acc.clear();
-                site_emit<NVN>(pre, a.dy, D, g, xnew, sd[3 * CPW + li], acc);
+                ffnv_epilogue<NVN>(a, so, D, g, tile_row_value(M, cA, srs[li], sc) + Sf, srg[li], sd[li], sd[CPW + li], sd[2 * CPW + li], sd[3 * CPW + li], mean2, rstd2,
+                                   *reinterpret_cast<const SitePre<NVN> *>(sp + li * PW), acc);
                 tile_site_leave<NVN>(acc, scr, CPW, li);
             }
         };
-        tile_consume<TH, S, UPT, RUN, HEAD>(NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int) { return 0; }, on_tile, a.tl);
+        tile_consume<TH, S, G::UPT, G::RUN, G::HEAD>(G::NU, ring, a.ns, tc, tsum, xq, xvd_t, wave, lane, fail, wk, wpre, [](int) { return 0; }, on_tile, a.tl);
     }
     tl_stamp(a.tl, 6);
     __syncthreads();
