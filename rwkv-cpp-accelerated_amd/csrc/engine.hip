@@ -151,14 +151,24 @@ struct Pipe {
     std::string info;            // one JSON object describing this rank's end of the transport (rwkv_pipe_info)
 };
 
-// per-chunk scratch of the chunk path (one set per pipeline stage that may be in flight)
+// per-chunk scratch of the chunk path (one set per pipeline stage that may be in flight).  Everything per chunk is sized for a pass of
+// SEQ_TM = 64 rows = two halves: half 1's images / records / partial values sit right behind half 0's (seq.hip.h SEQ_TM)
 struct SeqScratch {
     double *state = nullptr;            // [D] LayerNorm output of the chunk's last token
-    float *y = nullptr;                 // gated wkv output [SEQ_T][D]
-    unsigned *img[3] = {nullptr, nullptr, nullptr}, *imgh = nullptr;
-    SeqPart *qpart = nullptr, *qparta = nullptr, *qparth = nullptr;
-    SeqStat *stat = nullptr;
-    float *pk3 = nullptr, *pk5 = nullptr, *pk1 = nullptr;
+    float *y = nullptr;                 // gated wkv output [SEQ_TM][D]
+    unsigned *img[3] = {nullptr, nullptr, nullptr}, *imgh = nullptr;   // MFMA A-operand images (K = D; K = 4D)
+    SeqPart *qpart = nullptr, *qparta = nullptr, *qparth = nullptr;    // quantisation records: site vectors [3][SEQ_T][SEQ_O], att_out input [SEQ_T][SEQ_O], ffn_v input [SEQ_T][SEQ_O]
+    SeqStat *stat = nullptr;            // [SEQ_TM][SEQ_O] LayerNorm partial statistics
+    float *pk3 = nullptr, *pk5 = nullptr, *pk1 = nullptr;   // per-slice partial values of the K/V/R, ffn k/r, att_out | ffn_v GEMMs (accumulator images, seq.hip.h pk_index)
+};
+// Elements of ONE half of a scratch set at width D: the allocation holds two of each, and a pass of two halves finds half 1 at these offsets
+struct SeqHalf {
+    size_t img, imgh;                   // A-image 32-bit words for K = D and K = 4 D
+    size_t part3, part1;                // records of a 3-vector and a 1-vector site
+    size_t pk3, pk5, pk1;               // partial values [slice][tile][2][4][64] of 3, 5 and 1 row classes, tiles = classes x 16-channel blocks
+    explicit SeqHalf(size_t D)
+        : img(a_image_bytes(D) / 4), imgh(a_image_bytes(4 * D) / 4), part3((size_t)3 * SEQ_T * SEQ_O), part1((size_t)SEQ_T * SEQ_O),
+          pk3((size_t)SEQ_O * 3 * ((D + 15) / 16) * 512), pk5((size_t)SEQ_O * 5 * ((D + 15) / 16) * 512), pk1((size_t)SEQ_O * ((D + 15) / 16) * 512) {}
 };
 
 struct rwkv_ctx {
@@ -235,7 +245,7 @@ struct rwkv_ctx {
     static constexpr int SPLIT_MAX = 4;
     int n_split = 0;                                          // stages in use (0: not set up)
     hipStream_t sp_stream[SPLIT_MAX] = {};                    // [0] = stream
-    struct SeqScratch *sp_scratch[SPLIT_MAX] = {};            // [0] = the context's own set (built on the fly)
+    SeqScratch sp_scratch[SPLIT_MAX];                         // [0] = the context's own set (load_common), the others at first use (split_setup)
     hipEvent_t sp_done[SPLIT_MAX][SPLIT_MAX] = {};            // [stage][buffer]: the stage has finished the chunk in that buffer
     hipEvent_t sp_end = nullptr;
     double *x_in = nullptr;                       // decode: residual vector received from the previous stage (nullptr: c->x)
@@ -246,12 +256,6 @@ struct rwkv_ctx {
     double hop_stats[4] = {0.0, 0.0, 0.0, 0.0};
     Ctl *pipe_ring = nullptr;                     // pinned control blocks of rwkv_pipe_decode's items (grown on demand, kept)
     uint64_t pipe_ring_cap = 0;
-    double *sq_state = nullptr;                   // [D] LayerNorm output of the chunk's last token
-    float *sq_y = nullptr;                        // gated wkv output [SEQ_T][D]
-    unsigned *sq_img[3] = {nullptr, nullptr, nullptr}, *sq_imgh = nullptr;   // MFMA A-operand images (K = D; K = 4D)
-    SeqPart *sq_qpart = nullptr, *sq_qparta = nullptr, *sq_qparth = nullptr;   // quantisation records: site vectors [3][SEQ_T][SEQ_O], att_out input [SEQ_T][SEQ_O], ffn_v input [SEQ_T][SEQ_O]
-    SeqStat *sq_stat = nullptr;                          // [SEQ_T][SEQ_O] LayerNorm partial statistics
-    float *sq_pk3 = nullptr, *sq_pk5 = nullptr, *sq_pk1 = nullptr;   // per-slice partial values [SEQ_O][SEQ_T][3D / 5D / D] of the K/V/R, ffn k/r, att_out | ffn_v GEMMs
     // second resident copy of the matrices (chunked path only): MFMA B-operand images, row sums per octant of K
     uint8_t *b_kvr = nullptr, *b_att = nullptr, *b_frk = nullptr, *b_fv = nullptr, *b_head = nullptr;
     // tile images the tile-form DECODE kernels stream (tile.hip.h): the chunk path's own (16-row tiles) where a workgroup owns one 16-channel
@@ -603,23 +607,78 @@ template <typename T> int upload(rwkv_ctx *c, Source &src, int slot, T **dst)
     return src.to_device(slot, 0, n * sizeof(T), *dst, c->stream);
 }
 
+// The chunk path's GEMM instances, ONE table: which k_seq_gemm_p instance runs kind 0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v for a pass of one or
+// two halves at octants of up to 8 k-blocks or more (`big`: D > 4096, the NKB = 10 instances), with its LDS bytes (the kernel's own description,
+// seq.hip.h seq_lds_image) and the row tiles a wave has registers for.  Template arguments: TAG, NTW, NKB, NVS, DEPTH, MULTI, NH.
+//  * two halves: both per weight fragment -- short k-block groups re-staged into the other LDS buffer (the image of two halves is twice as large;
+//    twice the accumulators per weight tile);
+//  * one half: the GEMM as a software pipeline over k-blocks, the slice's whole image resident (seq.hip.h k_seq_gemm_p) -- except ffn_v, whose
+//    activation image (K = 4 D) is staged per 4 k-blocks into alternating LDS buffers instead of per slice, so that the first MFMA does not wait for
+//    the whole slice's image (3.36 -> 3.30 ms per 7B chunk; for the other kinds it measured +-0 or a loss: profiles/r04/seq_small_ab.txt).
+template <class A> struct SeqGemmInst { void (*fn)(A); size_t smem; int ntw; };
+template <int TAG, int NTW, int NKB, int NVS, int DEPTH, bool MULTI, int NH> SeqGemmInst<SeqGemmArgs> seq_p_inst()
+{
+    return {k_seq_gemm_p<TAG, NTW, NKB, NVS, DEPTH, MULTI, NH>, seq_lds_image(MULTI ? 2 : 1, NH, NVS, NKB).bytes, NTW};
+}
+// (The order of the lines below is the order in which hipcc instantiates the kernels, and that is their order in the code object: one half before two,
+// 8 k-blocks before 10, as it always was.  With the two-half instances first the SAME kernels ran a 32-token 7B chunk in 3.28 ms for 3.25,
+// profiles/seq_gemm/ab.txt.)
+SeqGemmInst<SeqGemmArgs> seq_gemm_p_for(int kind, bool two, bool big)
+{
+    if (!two) switch (kind) {
+        case 0: return !big ? seq_p_inst<0, 3, 8, 3, RWKV_SEQ_DEPTH0, false, 1>() : seq_p_inst<0, 3, 10, 2, 2, false, 1>();
+        case 1: return !big ? seq_p_inst<1, 1, 8, 1, 8, false, 1>() : seq_p_inst<1, 1, 10, 1, 10, false, 1>();
+        case 2: return !big ? seq_p_inst<2, 5, 8, 2, RWKV_SEQ_DEPTH2, false, 1>() : seq_p_inst<2, 4, 10, 2, 2, false, 1>();
+        default: return seq_p_inst<3, 1, 4, 1, 4, true, 1>();
+    }
+    switch (kind) {
+        case 0: return seq_p_inst<0, 3, 2, 3, 2, true, 2>();
+        case 1: return !big ? seq_p_inst<1, 1, 8, 1, 8, false, 2>() : seq_p_inst<1, 1, 10, 1, 10, false, 2>();
+        case 2: return seq_p_inst<2, 3, 2, 2, 2, true, 2>();
+        default: return seq_p_inst<3, 1, 4, 1, 4, true, 2>();
+    }
+}
+// k_seq_gemm_b (two halves; kinds 0 and 2): `smem` is the largest launch, a slice of SEQ_B_NKB_MAX k-blocks; a launch asks for its own slice length
+SeqGemmInst<SeqGemmBArgs> seq_gemm_b_for(int kind)
+{
+    const size_t smem = seq_lds_image(1, 2, 1, SEQ_B_NKB_MAX).bytes;
+    if (kind == 0) return {k_seq_gemm_b<0, 3, RWKV_SEQ_BDEPTH, 2>, smem, 3};
+    return {k_seq_gemm_b<2, 3, RWKV_SEQ_BDEPTH, 2>, smem, 3};
+}
 int seq_smem_limits()
 {
     int rc = 0;
-#define SEQ_ALLOW_P(TAG, NTW, NKB, NVS, DEPTH, MULTI) if (!rc) rc = allow_smem(k_seq_gemm_p<TAG, NTW, NKB, NVS, DEPTH, MULTI>, seq_gemm_p_smem(NKB, NVS, MULTI))
-    SEQ_ALLOW_P(0, 3, 8, 3, RWKV_SEQ_DEPTH0, false); SEQ_ALLOW_P(0, 3, 10, 2, 2, false);
-    SEQ_ALLOW_P(1, 1, 8, 1, 8, false); SEQ_ALLOW_P(1, 1, 10, 1, 10, false);
-    SEQ_ALLOW_P(2, 5, 8, 2, RWKV_SEQ_DEPTH2, false); SEQ_ALLOW_P(2, 4, 10, 2, 2, false);
-    SEQ_ALLOW_P(3, 1, 4, 1, 4, true);
-#undef SEQ_ALLOW_P
-#define SEQ_ALLOW_P2(TAG, NTW, NKB, NVS, DEPTH, MULTI) if (!rc) rc = allow_smem(k_seq_gemm_p<TAG, NTW, NKB, NVS, DEPTH, MULTI, 2>, seq_gemm_p_smem(NKB, NVS, MULTI, 2))
-    SEQ_ALLOW_P2(0, 3, 2, 3, 2, true); SEQ_ALLOW_P2(1, 1, 8, 1, 8, false); SEQ_ALLOW_P2(1, 1, 10, 1, 10, false);
-    SEQ_ALLOW_P2(2, 3, 2, 2, 2, true); SEQ_ALLOW_P2(3, 1, 4, 1, 4, true);
-#undef SEQ_ALLOW_P2
-    if (!rc) rc = allow_smem(k_seq_gemm_b<0, 3, RWKV_SEQ_BDEPTH, 2>, seq_gemm_b_smem(SEQ_B_NKB_MAX, 2));
-    if (!rc) rc = allow_smem(k_seq_gemm_b<2, 3, RWKV_SEQ_BDEPTH, 2>, seq_gemm_b_smem(SEQ_B_NKB_MAX, 2));
-    if (!rc) rc = allow_smem(k_seq_gemm_ks, SEQ_KS_SMEM);
+    for (int i = 0; i < 16 && !rc; i++) {      // (an instance that serves two cases is set twice: harmless)
+        const auto p = seq_gemm_p_for(i >> 2, i & 1, i & 2);
+        rc = allow_smem(p.fn, p.smem);
+    }
+    for (int kind = 0; kind <= 2 && !rc; kind += 2) rc = allow_smem(seq_gemm_b_for(kind).fn, seq_gemm_b_for(kind).smem);
+    if (!rc) rc = allow_smem(k_seq_gemm_ks, seq_lds_ks().bytes);
     return rc;
+}
+// one scratch set of the chunk path for the context's width: two halves of everything (SeqHalf), images and records zeroed
+int alloc_scratch(rwkv_ctx *c, SeqScratch &S)
+{
+    const size_t D = c->D;
+    const SeqHalf h(D);
+    int rc = 0;
+    auto zeroed = [&](auto **p, size_t count) -> int {
+        if (const int e = dalloc(c, p, count)) return e;
+        HIPCHK(hipMemsetAsync(*p, 0, count * sizeof(**p), c->stream));
+        return 0;
+    };
+    if ((rc = dalloc(c, &S.state, D))) return rc;
+    if ((rc = dalloc(c, &S.y, (size_t)SEQ_TM * D))) return rc;
+    for (int k = 0; k < 3; k++)
+        if ((rc = zeroed(&S.img[k], 2 * h.img))) return rc;
+    if ((rc = zeroed(&S.imgh, 2 * h.imgh))) return rc;
+    if ((rc = zeroed(&S.qpart, 2 * h.part3))) return rc;
+    if ((rc = zeroed(&S.qparta, 2 * h.part1))) return rc;
+    if ((rc = zeroed(&S.qparth, 2 * h.part1))) return rc;
+    if ((rc = dalloc(c, &S.stat, (size_t)SEQ_TM * SEQ_O))) return rc;
+    if ((rc = dalloc(c, &S.pk3, 2 * h.pk3))) return rc;
+    if ((rc = dalloc(c, &S.pk5, 2 * h.pk5))) return rc;
+    return dalloc(c, &S.pk1, 2 * h.pk1);
 }
 
 int set_smem_limits(rwkv_ctx *c)
@@ -892,31 +951,9 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
             if ((rc = dalloc(c, &c->sq_tokens, (size_t)SQ_RING * SEQ_TM))) return rc;
             HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_sq_tokens), sizeof(unsigned long long) * SQ_RING * SEQ_TM, hipHostMallocDefault));
             for (int r = 0; r < SQ_RING; r++) HIPCHK(hipEventCreateWithFlags(&c->sq_ev[r], hipEventDisableTiming));
-            // (everything per chunk is sized for a pass of SEQ_TM = 64 rows = two halves: half 1's images / records / partial values sit
-            // right behind half 0's, seq.hip.h SEQ_TM)
             if ((rc = dalloc(c, &c->sq_x[0], (size_t)SEQ_TM * D))) return rc;
             if ((rc = dalloc(c, &c->sq_x[1], (size_t)SEQ_TM * D))) return rc;
-            if ((rc = dalloc(c, &c->sq_state, (size_t)D))) return rc;
-            if ((rc = dalloc(c, &c->sq_y, (size_t)SEQ_TM * D))) return rc;
-            for (int k = 0; k < 3; k++) {
-                if ((rc = dalloc(c, &c->sq_img[k], 2 * a_image_bytes(D) / 4))) return rc;
-                HIPCHK(hipMemsetAsync(c->sq_img[k], 0, 2 * a_image_bytes(D), c->stream));
-            }
-            if ((rc = dalloc(c, &c->sq_imgh, 2 * a_image_bytes(4 * D) / 4))) return rc;
-            HIPCHK(hipMemsetAsync(c->sq_imgh, 0, 2 * a_image_bytes(4 * D), c->stream));
-            if ((rc = dalloc(c, &c->sq_qpart, (size_t)2 * 3 * SEQ_T * SEQ_O))) return rc;
-            if ((rc = dalloc(c, &c->sq_qparta, (size_t)2 * SEQ_T * SEQ_O))) return rc;
-            if ((rc = dalloc(c, &c->sq_qparth, (size_t)2 * SEQ_T * SEQ_O))) return rc;
-            HIPCHK(hipMemsetAsync(c->sq_qpart, 0, sizeof(SeqPart) * 2 * 3 * SEQ_T * SEQ_O, c->stream));
-            HIPCHK(hipMemsetAsync(c->sq_qparta, 0, sizeof(SeqPart) * 2 * SEQ_T * SEQ_O, c->stream));
-            HIPCHK(hipMemsetAsync(c->sq_qparth, 0, sizeof(SeqPart) * 2 * SEQ_T * SEQ_O, c->stream));
-            if ((rc = dalloc(c, &c->sq_stat, (size_t)SEQ_TM * SEQ_O))) return rc;
-            {   // accumulator images: [half][slice][tile][2][4][64] floats, tiles = classes x 16-channel blocks
-                const size_t cbd = ((size_t)D + 15) / 16;
-                if ((rc = dalloc(c, &c->sq_pk3, (size_t)2 * SEQ_O * 3 * cbd * 512))) return rc;
-                if ((rc = dalloc(c, &c->sq_pk5, (size_t)2 * SEQ_O * 5 * cbd * 512))) return rc;
-                if ((rc = dalloc(c, &c->sq_pk1, (size_t)2 * SEQ_O * cbd * 512))) return rc;
-            }
+            if ((rc = alloc_scratch(c, c->sp_scratch[0]))) return rc;
             c->seq_ok = true;
         }
     }
@@ -963,12 +1000,7 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
     const uint64_t la = part ? part->la : c->l0, lb = part ? part->lb : c->l1;
     const bool first = c->l0 == 0 && la == c->l0, last = c->l1 == c->L && lb == c->l1;
     hipStream_t st = part ? part->st : c->stream;
-    SeqScratch own;
-    own.state = c->sq_state; own.y = c->sq_y; own.imgh = c->sq_imgh;
-    for (int k = 0; k < 3; k++) own.img[k] = c->sq_img[k];
-    own.qpart = c->sq_qpart; own.qparta = c->sq_qparta; own.qparth = c->sq_qparth; own.stat = c->sq_stat;
-    own.pk3 = c->sq_pk3; own.pk5 = c->sq_pk5; own.pk1 = c->sq_pk1;
-    const SeqScratch &S = part ? *part->S : own;
+    const SeqScratch &S = part ? *part->S : c->sp_scratch[0];
     double *x = c->sq_x[buf];
     if (first) {
         if (buf < 0 || buf >= SQ_RING) return fail(RWKV_E_ARG, "residual buffer %d out of range", buf);
@@ -984,41 +1016,44 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
     // a pass of 33 .. 64 rows has two halves (seq.hip.h SEQ_TM): the GEMMs read the weights ONCE for both, everything per half sits
     // at these element offsets behind half 0's
     const bool two = n > SEQ_T;
-    const size_t cbd_ = ((size_t)D + 15) / 16;
-    const size_t h_img = a_image_bytes(D) / 4, h_imgh = a_image_bytes(4 * (size_t)D) / 4;                  // 32-bit words
-    const size_t h_part3 = (size_t)3 * SEQ_T * SEQ_O, h_part1 = (size_t)SEQ_T * SEQ_O;                     // records
-    const size_t h_pk3 = (size_t)SEQ_O * 3 * cbd_ * 512, h_pk5 = (size_t)SEQ_O * 5 * cbd_ * 512, h_pk1 = (size_t)SEQ_O * cbd_ * 512;   // floats
+    const SeqHalf h((size_t)D);
     const bool big = (D >> 6) > 8 * SEQ_O;       // octants of K = D longer than 8 k-blocks (D > 4096): the NKB = 10 instances
-    static const int v012[5] = {0, 1, 2, 0, 0}, v0[5] = {0, 0, 0, 0, 0}, v00001[5] = {0, 0, 0, 0, 1};
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
-    // kind 0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v: tile-per-wave GEMM over the 8 K-slices, partial values into pk
-    auto gemm = [&](int kind, const uint8_t *bimg, const unsigned *rs8, int N, int K, int Q, const int *voq, unsigned *const *img, const SeqPart *qpart,
-                    float *pk, double *state_dst, size_t gh_img, size_t gh_part, size_t gh_pk) {
+    // What follows from a GEMM's kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v): row classes, K, the vector each class multiplies (padded with the
+    // last), the images and records it reads, the partial values it writes, and where half 1 of each lies
+    struct GemmKind { int Q, K, voq[5]; unsigned *img[3]; const SeqPart *part; float *pk; size_t img_h, part_h, pk_h; };
+    const GemmKind kinds[4] = {
+        {3, D, {0, 1, 2, 2, 2}, {S.img[0], S.img[1], S.img[2]}, S.qpart, S.pk3, h.img, h.part3, h.pk3},
+        {1, D, {0, 0, 0, 0, 0}, {S.img[0], S.img[1], S.img[2]}, S.qparta, S.pk1, h.img, h.part1, h.pk1},
+        {5, D, {0, 0, 0, 0, 1}, {S.img[0], S.img[1], S.img[2]}, S.qpart, S.pk5, h.img, h.part3, h.pk5},
+        {1, 4 * D, {0, 0, 0, 0, 0}, {S.imgh, S.imgh, S.imgh}, S.qparth, S.pk1, h.imgh, h.part1, h.pk1},
+    };
+    // tile-per-wave GEMM of layer matrix `bimg` (row sums `rs8`) over the 8 K-slices, partial values into the kind's pk; state_dst: GPT mode commits the
+    // state of the site in front of it behind it
+    auto gemm = [&](int kind, const uint8_t *bimg, const unsigned *rs8, double *state_dst) {
+        const GemmKind &k = kinds[kind];
+        const int Q = k.Q, N = Q * D, K = k.K;
         SeqGemmArgs g{};
         g.bimg = reinterpret_cast<const u32x4 *>(bimg); g.rs8 = rs8; g.N = N; g.K = K; g.Q = Q;
-        for (int q = 0; q < 5; q++) g.vec_of_q[q] = q < Q ? voq[q] : voq[Q - 1];
-        for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(img[k]);
-        g.part = qpart; g.pk = pk; g.out = nullptr; g.T = n;
-        g.img_h = gh_img / 4; g.part_h = gh_part; g.pk_h = gh_pk;      // (images: 16-byte units)
+        for (int q = 0; q < 5; q++) g.vec_of_q[q] = k.voq[q];
+        for (int v = 0; v < 3; v++) g.img[v] = reinterpret_cast<const u32x4 *>(k.img[v]);
+        g.part = k.part; g.pk = k.pk; g.out = nullptr; g.T = n;
+        g.img_h = k.img_h / 4; g.part_h = k.part_h; g.pk_h = k.pk_h;      // (images: 16-byte units)
         g.tl = (c->tl_on && c->tl_cls == 10 + kind && tl_layer) ? c->tl : nullptr;
-        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par) ? D : 0;   // GPT: commit the site's state behind it
+        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par) ? D : 0;
         const int nch = (N + Q - 1) / Q, ntiles = Q * ((nch + 15) / 16);
-        const int ntw_max = kind == 0 ? 3 : kind == 2 ? (two ? 3 : big ? 4 : 5) : 1;      // (two halves: twice the accumulators per weight tile)
-        const int RB = (ntiles + SEQ_NW * ntw_max - 1) / (SEQ_NW * ntw_max);
-        g.ntw = (ntiles + SEQ_NW * RB - 1) / (SEQ_NW * RB);
-        const dim3 grid(SEQ_O * RB), blk(SEQ_NT);
-#define SEQ_LAUNCH_P(TAG, NTW, NKB, NVS, DEPTH, MULTI) k_seq_gemm_p<TAG, NTW, NKB, NVS, DEPTH, MULTI><<<grid, blk, seq_gemm_p_smem(NKB, NVS, MULTI), st>>>(g)
-#define SEQ_LAUNCH_P2(TAG, NTW, NKB, NVS, DEPTH, MULTI) k_seq_gemm_p<TAG, NTW, NKB, NVS, DEPTH, MULTI, 2><<<grid, blk, seq_gemm_p_smem(NKB, NVS, MULTI, 2), st>>>(g)
+        const dim3 blk(SEQ_NT);
         if (two && (kind == 0 || kind == 2) && ((c->seq_b >= 0 ? c->seq_b : (4 | (D >= 4096 ? 1 : 0))) & (1 << kind))) {
             // k_seq_gemm_b: one vector's image of the slice resident, a wave's tiles in batches of <= 3.  The 32 workgroups of a slice are
             // shared out to the matrix's VECTOR GROUPS (runs of row classes on the same vector) so that no workgroup straddles one and the
             // largest tile count of a wave is as small as it gets.  Its conditions: slices of DEPTH .. SEQ_B_NKB_MAX k-blocks (the
             // resident image; row sums prefetched one batch ahead), at most three batches per wave, at most three groups
+            const auto inst = seq_gemm_b_for(kind);
             const int KB = K >> 6, nkb_min = KB / SEQ_O, nkb_max = (KB + SEQ_O - 1) / SEQ_O, CBt = (nch + 15) / 16;
             SeqGemmBArgs b{};
             int ngrp = 0, gq[4] = {0, 0, 0, 0};
             for (int q = 0; q < Q && ngrp < 4; q++)
-                if (q == 0 || voq[q] != voq[q - 1]) gq[ngrp++] = q;
+                if (q == 0 || k.voq[q] != k.voq[q - 1]) gq[ngrp++] = q;
             bool okb = ngrp <= 3 && nkb_min >= RWKV_SEQ_BDEPTH && nkb_max <= SEQ_B_NKB_MAX;
             if (okb) {
                 int T[3] = {0, 0, 0}, best[3] = {0, 0, 0};
@@ -1049,40 +1084,24 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
                     if (pw > per_wave_max) per_wave_max = pw;
                 }
                 b.grp_rb[ngrp] = rb0; b.ngrp = ngrp;
-                okb = per_wave_max <= 9 && rb0 >= 1;
+                okb = per_wave_max <= 3 * inst.ntw && rb0 >= 1;
                 if (okb) {
                     b.g = g; b.g.ntw = per_wave_max;
-                    const dim3 gridb(SEQ_O * rb0);
-                    const size_t smem = seq_gemm_b_smem(nkb_max, 2);
-                    if (kind == 0) k_seq_gemm_b<0, 3, RWKV_SEQ_BDEPTH, 2><<<gridb, blk, smem, st>>>(b);
-                    else k_seq_gemm_b<2, 3, RWKV_SEQ_BDEPTH, 2><<<gridb, blk, smem, st>>>(b);
+                    inst.fn<<<dim3(SEQ_O * rb0), blk, seq_lds_image(1, 2, 1, nkb_max).bytes, st>>>(b);
                     return;
                 }
             }
         }
-        if (two) {      // both halves per weight fragment: short k-block groups re-staged into the other LDS buffer (the image of two halves is twice as large)
-            if (kind == 0) SEQ_LAUNCH_P2(0, 3, 2, 3, 2, true);
-            else if (kind == 1) { if (big) SEQ_LAUNCH_P2(1, 1, 10, 1, 10, false); else SEQ_LAUNCH_P2(1, 1, 8, 1, 8, false); }
-            else if (kind == 2) SEQ_LAUNCH_P2(2, 3, 2, 2, 2, true);
-            else SEQ_LAUNCH_P2(3, 1, 4, 1, 4, true);
-            return;
-        }
-#undef SEQ_LAUNCH_P2
-        // passes of <= 32 rows: ffn_v's activation image (K = 4 D) is staged per 4 k-blocks into alternating LDS buffers instead of per slice, so that
-        // the first MFMA does not wait for the whole slice's image (3.36 -> 3.30 ms per 7B chunk; for the other kinds it measured +-0 or a loss:
-        // profiles/r04/seq_small_ab.txt)
-        if (kind == 3) { SEQ_LAUNCH_P(3, 1, 4, 1, 4, true); return; }
-        // the GEMM as a software pipeline over k-blocks, the slice's whole image resident (seq.hip.h k_seq_gemm_p)
-        if (kind == 0) { if (big) SEQ_LAUNCH_P(0, 3, 10, 2, 2, false); else SEQ_LAUNCH_P(0, 3, 8, 3, RWKV_SEQ_DEPTH0, false); }
-        else if (kind == 1) { if (big) SEQ_LAUNCH_P(1, 1, 10, 1, 10, false); else SEQ_LAUNCH_P(1, 1, 8, 1, 8, false); }
-        else { if (big) SEQ_LAUNCH_P(2, 4, 10, 2, 2, false); else SEQ_LAUNCH_P(2, 5, 8, 2, RWKV_SEQ_DEPTH2, false); }
-#undef SEQ_LAUNCH_P
+        const auto inst = seq_gemm_p_for(kind, two, big);
+        const int RB = (ntiles + SEQ_NW * inst.ntw - 1) / (SEQ_NW * inst.ntw);
+        g.ntw = (ntiles + SEQ_NW * RB - 1) / (SEQ_NW * RB);
+        inst.fn<<<dim3(SEQ_O * RB), blk, inst.smem, st>>>(g);
     };
     auto resid = [&](int mode, const SeqPart *qpart) {
         SeqResidArgs r{};
         r.x = x; r.pk = S.pk1; r.qpart = qpart; r.pk_gate = S.pk5; r.qpart_gate = S.qpart + (size_t)1 * SEQ_T * SEQ_O;   // ffn r = vector 1 of the ln2 site
         r.stat = S.stat; r.D = D; r.T = n;
-        r.pk_h = h_pk1; r.pkg_h = h_pk5; r.part_h = h_part1; r.partg_h = h_part3;
+        r.pk_h = h.pk1; r.pkg_h = h.pk5; r.part_h = h.part1; r.partg_h = h.part3;
         if (mode == 0) k_seq_resid<0><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
         else if (mode == 1) k_seq_resid<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
         else k_seq_resid<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
@@ -1095,12 +1114,11 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
         s.par = par && state; s.state_par = state; s.slot_stride = LD; s.slot0 = (int)row0;
         for (int q = 0; q < 3; q++) s.img[q] = S.img[q];
         s.part = S.qpart; s.D = D; s.T = n;
-        s.img_h = h_img; s.part_h = h_part3;
+        s.img_h = h.img; s.part_h = h.part3;
         if (nv == 3) k_seq_site<3><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else if (nv == 2) k_seq_site<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else k_seq_site<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
     };
-    unsigned *imgh3[3] = {S.imgh, S.imgh, S.imgh};
     const int n_wkv = (D + WKV_CH - 1) / WKV_CH;
     const uint64_t CBd = ((uint64_t)D + 15) / 16;
     resid(0, nullptr);     // LayerNorm statistics of the incoming residual stream (embedding rows, or the previous stage's output)
@@ -1111,13 +1129,13 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
             const double *mix[3] = {c->mixk + lo, c->mixv + lo, c->mixr + lo};
             const float *r[3] = {c->kr + lo, c->vr + lo, c->rr + lo}, *o[3] = {c->o1 + lo, c->o2 + lo, c->o3 + lo};
             site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo);
-            gemm(0, c->b_kvr + wl * 3 * CBd * 16 * D, c->r8_kvr + wl * SEQ_O * 3 * (size_t)D, 3 * D, D, 3, v012, S.img, S.qpart, S.pk3, c->state[0] + lo, h_img, h_part3, h_pk3);
-            SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, par ? 1 : 0, LD, (int)row0, h_pk3, h_part3};
+            gemm(0, c->b_kvr + wl * 3 * CBd * 16 * D, c->r8_kvr + wl * SEQ_O * 3 * (size_t)D, c->state[0] + lo);
+            SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, par ? 1 : 0, LD, (int)row0, h.pk3, h.part3};
             if (two) k_seq_wkv<SEQ_TM><<<dim3(n_wkv), dim3(SEQ_TM * WKV_CH), 0, st>>>(wa);
             else k_seq_wkv<SEQ_T><<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
-            SeqStageArgs sa{S.y, nullptr, nullptr, c->attr + lo, c->atto + lo, S.img[0], S.qparta, D, n, 0, 0, h_img, h_part1};
+            SeqStageArgs sa{S.y, nullptr, nullptr, c->attr + lo, c->atto + lo, S.img[0], S.qparta, D, n, 0, 0, h.img, h.part1};
             k_seq_stage<0><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sa);
-            gemm(1, c->b_att + wl * CBd * 16 * D, c->r8_att + wl * SEQ_O * (size_t)D, D, D, 1, v0, S.img, S.qparta, S.pk1, nullptr, h_img, h_part1, h_pk1);
+            gemm(1, c->b_att + wl * CBd * 16 * D, c->r8_att + wl * SEQ_O * (size_t)D, nullptr);
             // x = f32(x) + att_out; statistics for ln2.  (Round 3 tried this launch and the site behind it as ONE launch whose (row, octant)
             // workgroups meet on a per-row arrival counter: +3.6 us per fused launch, profiles/r03/prefill_fuse.txt -- the in-launch
             // all-to-all costs more than the kernel boundary it replaces.)
@@ -1127,10 +1145,10 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
             const double *mix[3] = {c->fmixk + lo, c->fmixr + lo, nullptr};
             const float *r[3] = {c->fkr + lo, c->frr + lo, nullptr}, *o[3] = {c->fko + lo, c->fro + lo, nullptr};
             site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo);
-            gemm(2, c->b_frk + wl * 5 * CBd * 16 * D, c->r8_frk + wl * SEQ_O * 5 * (size_t)D, 5 * D, D, 5, v00001, S.img, S.qpart, S.pk5, c->state[4] + lo, h_img, h_part3, h_pk5);
-            SeqStageArgs sh{nullptr, S.pk5, S.qpart, c->fvr + 4 * lo, c->fvo + 4 * lo, S.imgh, S.qparth, 4 * D, n, h_pk5, h_part3, h_imgh, h_part1};
+            gemm(2, c->b_frk + wl * 5 * CBd * 16 * D, c->r8_frk + wl * SEQ_O * 5 * (size_t)D, c->state[4] + lo);
+            SeqStageArgs sh{nullptr, S.pk5, S.qpart, c->fvr + 4 * lo, c->fvo + 4 * lo, S.imgh, S.qparth, 4 * D, n, h.pk5, h.part3, h.imgh, h.part1};
             k_seq_stage<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sh);
-            gemm(3, c->b_fv + wl * CBd * 16 * 4 * D, c->r8_fv + wl * SEQ_O * (size_t)D, D, 4 * D, 1, v0, imgh3, S.qparth, S.pk1, nullptr, h_imgh, h_part1, h_pk1);
+            gemm(3, c->b_fv + wl * CBd * 16 * 4 * D, c->r8_fv + wl * SEQ_O * (size_t)D, nullptr);
             resid(2, S.qparth);     // x += ffn_v * sigmoid(r); statistics for the next site
         }
     }
@@ -1141,11 +1159,11 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
         g.bimg = reinterpret_cast<const u32x4 *>(c->b_head); g.rs8 = c->r8_head; g.N = (int)V; g.K = D; g.Q = 1;
         for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k]);
         g.part = S.qpart; g.out = c->logits + row0 * V; g.T = two ? SEQ_T : n;
-        k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), SEQ_KS_SMEM, st>>>(g);
+        k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), seq_lds_ks().bytes, st>>>(g);
         if (two) {      // the head once per half (its weights are 3 % of a pass's bytes; 240 accumulator registers would not fit one wave)
-            for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k] + h_img);
-            g.part = S.qpart + h_part3; g.out = c->logits + (row0 + SEQ_T) * V; g.T = n - SEQ_T;
-            k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), SEQ_KS_SMEM, st>>>(g);
+            for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k] + h.img);
+            g.part = S.qpart + h.part3; g.out = c->logits + (row0 + SEQ_T) * V; g.T = n - SEQ_T;
+            k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), seq_lds_ks().bytes, st>>>(g);
         }
     }
     HIPCHK(hipGetLastError());
@@ -1162,7 +1180,6 @@ int split_setup(rwkv_ctx *c)
     if (want > rwkv_ctx::SPLIT_MAX) want = rwkv_ctx::SPLIT_MAX;
     if ((uint64_t)want > c->L) want = (int)c->L;
     if (want < 2 || !c->seq_ok || c->l0 != 0 || c->l1 != c->L) { c->n_split = 1; return 0; }
-    const uint64_t D = c->D;
     c->sp_stream[0] = c->stream;
     HIPCHK(hipEventCreateWithFlags(&c->sp_end, hipEventDisableTiming));
     for (int k = 0; k < want; k++) {
@@ -1170,32 +1187,8 @@ int split_setup(rwkv_ctx *c)
         for (int b = 0; b < want; b++) HIPCHK(hipEventCreateWithFlags(&c->sp_done[k][b], hipEventDisableTiming));
     }
     int rc = 0;
-    for (int k = 2; k < want && !rc; k++) rc = dalloc(c, &c->sq_x[k], (size_t)SEQ_TM * D);
-    for (int k = 1; k < want && !rc; k++) {
-        SeqScratch *S = new SeqScratch();
-        c->sp_scratch[k] = S;
-        if (!rc) rc = dalloc(c, &S->state, (size_t)D);
-        if (!rc) rc = dalloc(c, &S->y, (size_t)SEQ_TM * D);
-        for (int q = 0; q < 3 && !rc; q++) {
-            rc = dalloc(c, &S->img[q], 2 * a_image_bytes(D) / 4);
-            if (!rc) HIPCHK(hipMemsetAsync(S->img[q], 0, 2 * a_image_bytes(D), c->stream));
-        }
-        if (!rc) rc = dalloc(c, &S->imgh, 2 * a_image_bytes(4 * D) / 4);
-        if (!rc) HIPCHK(hipMemsetAsync(S->imgh, 0, 2 * a_image_bytes(4 * D), c->stream));
-        if (!rc) rc = dalloc(c, &S->qpart, (size_t)2 * 3 * SEQ_T * SEQ_O);
-        if (!rc) rc = dalloc(c, &S->qparta, (size_t)2 * SEQ_T * SEQ_O);
-        if (!rc) rc = dalloc(c, &S->qparth, (size_t)2 * SEQ_T * SEQ_O);
-        if (!rc) {
-            HIPCHK(hipMemsetAsync(S->qpart, 0, sizeof(SeqPart) * 2 * 3 * SEQ_T * SEQ_O, c->stream));
-            HIPCHK(hipMemsetAsync(S->qparta, 0, sizeof(SeqPart) * 2 * SEQ_T * SEQ_O, c->stream));
-            HIPCHK(hipMemsetAsync(S->qparth, 0, sizeof(SeqPart) * 2 * SEQ_T * SEQ_O, c->stream));
-        }
-        if (!rc) rc = dalloc(c, &S->stat, (size_t)SEQ_TM * SEQ_O);
-        const size_t cbd = ((size_t)D + 15) / 16;
-        if (!rc) rc = dalloc(c, &S->pk3, (size_t)2 * SEQ_O * 3 * cbd * 512);
-        if (!rc) rc = dalloc(c, &S->pk5, (size_t)2 * SEQ_O * 5 * cbd * 512);
-        if (!rc) rc = dalloc(c, &S->pk1, (size_t)2 * SEQ_O * cbd * 512);
-    }
+    for (int k = 2; k < want && !rc; k++) rc = dalloc(c, &c->sq_x[k], (size_t)SEQ_TM * c->D);
+    for (int k = 1; k < want && !rc; k++) rc = alloc_scratch(c, c->sp_scratch[k]);
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
     c->n_split = want;
@@ -1269,11 +1262,6 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
     // rows per weight pass: 64 (two halves sharing every weight fragment) for calls of more than 32 rows, else 32
     const uint64_t CH = (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T;
     const uint64_t nchunks = (T + CH - 1) / CH;
-    SeqScratch own;      // stage 0 (or the one-stream schedule) uses the context's own scratch
-    own.state = c->sq_state; own.y = c->sq_y; own.imgh = c->sq_imgh;
-    for (int k = 0; k < 3; k++) own.img[k] = c->sq_img[k];
-    own.qpart = c->sq_qpart; own.qparta = c->sq_qparta; own.qparth = c->sq_qparth; own.stat = c->sq_stat;
-    own.pk3 = c->sq_pk3; own.pk5 = c->sq_pk5; own.pk1 = c->sq_pk1;
     int rc = 0;
     if (nchunks >= 2 && (rc = split_setup(c)) == 0 && c->n_split >= 2) {
         // Software pipeline over the chunks: stage k = an equal share of the layers (the last one with the head) on its
@@ -1292,7 +1280,7 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
                 hipStream_t st = c->sp_stream[k];
                 if (k == 0) { if (i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0)); }   // the last stage is done with this buffer (chunk i - ns)
                 else HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                                        // the stage before has handed chunk i over
-                ChunkPart part{split_point(c, k, ns), split_point(c, k + 1, ns), st, k == 0 ? &own : c->sp_scratch[k]};
+                ChunkPart part{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k]};      // (stage 0: the context's own scratch)
                 if (k == 0 && dtok) part.dtok = dtok + t0;
                 const uint64_t *tk = (k == 0 && tokens) ? tokens + t0 : nullptr;
                 if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tk, n, t0, true, b, &part);
@@ -1309,7 +1297,7 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
     if (rc) return rc;
     for (uint64_t t0 = 0; t0 < T; t0 += CH) {
         const int n = (int)(T - t0 < CH ? T - t0 : CH);
-        ChunkPart part{c->l0, c->l1, c->stream, &own};
+        ChunkPart part{c->l0, c->l1, c->stream, &c->sp_scratch[0]};
         if (dtok) part.dtok = dtok + t0;
         if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tokens ? tokens + t0 : nullptr, n, t0, true, 0, &part);
         else rc = enqueue_pass(c, tokens + t0, n, t0, 0, part);
@@ -1739,7 +1727,7 @@ void rwkv_free(rwkv_ctx *c)
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);
     for (auto &row : c->sp_done) for (auto &e : row) if (e) (void)hipEventDestroy(e);
     if (c->sp_end) (void)hipEventDestroy(c->sp_end);
-    for (int k = 1; k < rwkv_ctx::SPLIT_MAX; k++) { if (c->sp_stream[k]) (void)hipStreamDestroy(c->sp_stream[k]); delete c->sp_scratch[k]; }
+    for (int k = 1; k < rwkv_ctx::SPLIT_MAX; k++) { if (c->sp_stream[k]) (void)hipStreamDestroy(c->sp_stream[k]); }
     for (auto &kv : c->sq_graphs) (void)hipGraphExecDestroy(kv.second);
     c->sq_graphs.clear();
     if (c->h_sq_tokens) (void)hipHostFree(c->h_sq_tokens);

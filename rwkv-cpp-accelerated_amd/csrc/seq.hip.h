@@ -77,12 +77,11 @@ __device__ __forceinline__ size_t pk_index(int ntiles, int slice, int id, int t,
 {
     return ((((size_t)slice * ntiles + id) * 2 + (t >> 4)) * 4 + (t & 3)) * 64 + 16 * ((t & 15) >> 2) + c16;
 }
-// where a wave's lane stores accumulator register r of (slice j, tile id, row tile mt): base pointer + r * pk_rstride(ntiles)
+// where a wave's lane stores accumulator register r of (slice j, tile id, row tile mt): base pointer + r * 64 (the register stride of the image)
 __device__ __forceinline__ size_t pk_lane_base(int ntiles, int j, int id, int mt, int lane)
 {
     return ((((size_t)j * ntiles + id) * 2 + mt) * 4) * 64 + lane;
 }
-__device__ __forceinline__ size_t pk_rstride(int) { return (size_t)64; }
 // value of a GEMM output from its per-slice partials (each already scaled and corrected) and the offset term
 __device__ __forceinline__ float seq_val(const float *pk, int ntiles, int id, int t, int c16, float so)
 {
@@ -589,19 +588,99 @@ struct SeqGemmArgs {
     size_t img_h, part_h, pk_h;  // second half of a pass (k_seq_gemm_p with NH = 2; k_seq_gemm_ks is launched per half): offsets of its images
                                  // (16-byte units), records and partial values
     unsigned long long *tl;      // optional phase timeline (tl_stamp; tools/gemm_timeline.py): 0 entry, 1 requests issued, 2 activation image
-                                 // staged, 3 first batch / chunk multiplied and emitted, 4 last weights multiplied, 5 end
+                                 // staged, 3 first batch / chunk multiplied and emitted, 4 last weights multiplied (k_seq_gemm_p; k_seq_gemm_b ends there: 5), 5 end
 };
 constexpr int SEQ_NT = 512;      // GEMM workgroup: 8 waves, two per SIMD
-// dynamic LDS of the GEMM kernels
-constexpr size_t seq_gemm_p_smem(int nkb, int nvs, bool multi, int nh = 1) { return (size_t)(multi ? 2 : 1) * nh * nvs * nkb * 384 * 16 + (size_t)nh * nvs * SEQ_T * 16; }
 constexpr int SEQ_TB = 5;        // weight tiles (16 rows each) per workgroup pass of k_seq_gemm_ks
-constexpr size_t SEQ_KS_SMEM = sizeof(float) * SEQ_O * SEQ_TB * 2 * 4 * 64 + sizeof(float) * SEQ_T;
 constexpr int SEQ_NW = SEQ_NT / 64;
 
+// ---- what the three GEMMs share, each written once
+// The dynamic LDS of a GEMM form as byte offsets, regions in address order with nothing between them (the model is tile.hip.h's tile_lds_of).  The
+// kernel takes its pointers from here, engine.hip its launch bytes and the limit it raises (`bytes`).
+constexpr size_t SEQ_LDS_BYTES = 160 * 1024;       // LDS of one CU
+struct SeqLds {
+    size_t img = 0, recl = 0, accl = 0, sol = 0, bytes = 0;
+    bool aligned = true;         // every region begins on the boundary its accesses need
+    __host__ __device__ constexpr size_t take(size_t b, size_t align) { aligned = aligned && bytes % align == 0; const size_t o = bytes; bytes += b; return o; }
+    __host__ __device__ constexpr bool ok() const { return aligned && bytes <= SEQ_LDS_BYTES; }
+};
+constexpr int SEQ_KBU = 2 * 3 * 64;     // 16-byte units of one k-block of an activation image: [row tile][limb][lane] (a_unit)
+// k_seq_gemm_p / _b: `nbuf` buffers of the activation image [half][vector][k-block] (u32x4, written by 16-byte DMA pieces), behind them the record
+// table [half][vector][SEQ_T]{scale, cA} (f64) of the slice
+__host__ __device__ constexpr SeqLds seq_lds_image(int nbuf, int nh, int nvs, int nkb)
+{
+    SeqLds l;
+    l.img = l.take((size_t)nbuf * nh * nvs * nkb * SEQ_KBU * 16, 16);
+    l.recl = l.take((size_t)nh * nvs * SEQ_T * 2 * sizeof(double), 8);
+    return l;
+}
+// k_seq_gemm_ks: the octants' values [octant][tile][row tile][reg][lane] (f32, 80 KiB), the offset terms of the pass's vector [SEQ_T] (f32)
+__host__ __device__ constexpr SeqLds seq_lds_ks()
+{
+    SeqLds l;
+    l.accl = l.take(sizeof(float) * SEQ_O * SEQ_TB * 2 * 4 * 64, 4);
+    l.sol = l.take(sizeof(float) * SEQ_T, 4);
+    return l;
+}
+
+// Tile geometry of a GEMM over w_t[N][K] with Q interleaved row classes (k_bimage): channels per class, 16-channel blocks per class, 16-row tiles
+struct SeqGeo {
+    int N, Q, KB, nch, CB, ntiles;
+    __device__ __forceinline__ SeqGeo(int N_, int K_, int Q_) : N(N_), Q(Q_), KB(K_ >> 6), nch((N_ + Q_ - 1) / Q_), CB((nch + 15) >> 4), ntiles(Q_ * CB) {}
+    // first k-block of K-slice = octant o: the slice is [kb_of(o), kb_of(o + 1))
+    __device__ __forceinline__ int kb_of(int o) const { return (int)(((long long)o * KB) / SEQ_O); }
+    // the matrix row whose values lane `lane` of tile `id` finishes (D[m][n]: n = lane & 15), `pad` where that is the tile's padding
+    __device__ __forceinline__ int row_of(int id, int lane, int pad) const
+    {
+        const int q = id / CB, ch = 16 * (id % CB) + (lane & 15), row = Q * ch + q;
+        return (ch < nch && row < N) ? row : pad;
+    }
+};
+// piggy-back copy of the last workgroup: the chunk's last LayerNorm output -> recurrent state (SeqGemmArgs::cp_*)
+__device__ __forceinline__ void seq_commit_state(const SeqGemmArgs &a)
+{
+    if (blockIdx.x == gridDim.x - 1)
+        for (int q = threadIdx.x; q < a.cp_n; q += SEQ_NT) a.cp_dst[q] = a.cp_src[q];
+}
+template <int NT_> __device__ __forceinline__ void seq_zero(i32x4 (&acc)[NT_][2][3])
+{
+#pragma unroll
+    for (int i = 0; i < NT_; i++)
+#pragma unroll
+        for (int mt = 0; mt < 2; mt++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) acc[i][mt][b] = i32x4{0, 0, 0, 0};
+}
+__device__ __forceinline__ i32x4 seq_i32(const u32x4 &v) { return i32x4{(int)v[0], (int)v[1], (int)v[2], (int)v[3]}; }
+// one multiply step: a weight fragment against the activation fragments of one half's two row tiles x three limbs.  `w` is a REFERENCE into the
+// caller's register buffer: k_seq_gemm_b calls this behind its explicit wait for that register and makes no copy of it before (see there).
+// k_seq_gemm_p keeps these lines in place of the call, for the reason given there.
+__device__ __forceinline__ void seq_mfma(const u32x4 &w, const u32x4 (&av)[2][3], i32x4 (&acc)[2][3])
+{
+    const i32x4 bf = seq_i32(w);
+#pragma unroll
+    for (int ms = 0; ms < 2; ms++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) acc[ms][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(seq_i32(av[ms][b]), bf, acc[ms][b], 0, 0, 0);
+}
+// the exact integer of accumulator register r from its three limbs (< 2^53: exact in f64)
+__device__ __forceinline__ double seq_fold(const i32x4 (&acc)[3], int r)
+{
+    return (double)acc[0][r] + 256.0 * (double)acc[1][r] + 65536.0 * (double)acc[2][r];
+}
 // value of one slice: scale_o (M + cA_o + CU * rowsum_o)
 __device__ __forceinline__ double seq_slice_value(const SeqPart &rc, double M, unsigned rs)
 {
     return scale_of(rc.amax) * (M + rc.cA + SEQ_CU * (double)rs);
+}
+// Partial-value epilogue of k_seq_gemm_p / _b for one (tile, row tile): the lane's four accumulator registers = chunk rows mt * 16 + 4 (lane / 16) + r
+// of weight row lane % 16, scaled with rows `hv * SEQ_T + ...` of the record table and stored into the accumulator image at `dst` (pk_lane_base).
+// ONE copy: the two kernels' partial values are bit-identical because this arithmetic and its order are.
+__device__ __forceinline__ void seq_emit(const i32x4 (&acc)[3], const double *recl, size_t hv, int mt, int lane, unsigned rs, float *dst)
+{
+    const double *rl = recl + 2 * (hv * SEQ_T + mt * 16 + 4 * (lane >> 4));
+#pragma unroll
+    for (int r = 0; r < 4; r++) dst[r * 64] = (float)(rl[2 * r] * (seq_fold(acc, r) + rl[2 * r + 1] + SEQ_CU * (double)rs));   // scale_o (M + cA_o + CU rowsum_o)
 }
 
 // k_seq_gemm_p -- "tile per wave, K over the XCDs": workgroup (rb, j): j = blockIdx % 8 = K-slice = octant (and the XCD the workgroup is
@@ -640,12 +719,13 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert(NKB % DEPTH == 0, "the rolling buffer's slot of a k-block must be a compile-time value");
-    constexpr int NBUF = MULTI ? 2 : 1;
-    constexpr int CHU = NH * NVS * NKB * 384;           // units of one LDS buffer: [half][vector][k][row tile][limb][lane]
+    constexpr SeqLds LDS = seq_lds_image(MULTI ? 2 : 1, NH, NVS, NKB);
+    static_assert(LDS.ok(), "k_seq_gemm_p: LDS layout");
+    constexpr int CHU = NH * NVS * NKB * SEQ_KBU;       // units of one LDS buffer: [half][vector][k][row tile][limb][lane]
     constexpr int PW = (NH * NVS * NKB * 6 + SEQ_NW - 1) / SEQ_NW;      // DMA pieces (1 KiB) per wave and chunk; the last round is padded with duplicates
     static_assert(PW + DEPTH * NTW + 2 + NTW <= 63, "k_seq_gemm_p: more than 63 vector memory operations in flight");
-    u32x4 *abuf = reinterpret_cast<u32x4 *>(smem);
-    double *recl = reinterpret_cast<double *>(smem + (size_t)NBUF * CHU * 16);   // [NH][NVS][SEQ_T]{scale, cA} of this slice
+    u32x4 *abuf = reinterpret_cast<u32x4 *>(smem + LDS.img);
+    double *recl = reinterpret_cast<double *>(smem + LDS.recl);     // [NH][NVS][SEQ_T]{scale, cA} of this slice
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // every pointer and the class -> vector table with the kernel's FIRST scalar loads (round 6: the ISA of this kernel's head was a chain of ten
     // dependent scalar-cache round trips in front of the first request -- arguments fetched where they are first used, and `vec_of_q[dynamic index]`
@@ -657,13 +737,12 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
     const u32x4 *const im0 = a.img[0], *const im1 = a.img[1], *const im2 = a.img[2];
     auto img_of = [&](int v) { return v <= 0 ? im0 : v == 1 ? im1 : im2; };      // (a.img[dynamic index] is one scalar load per DMA piece)
     tl_stamp(a.tl, 0);
-    const int K = a.K, KB = K >> 6, N = a.N, Q = a.Q;
-    const int nch = (N + Q - 1) / Q, CB = (nch + 15) >> 4, ntiles = Q * CB;
+    const SeqGeo G(a.N, a.K, a.Q);
+    const int KB = G.KB, N = G.N, CB = G.CB, ntiles = G.ntiles;
     const int j = blockIdx.x % SEQ_O, rb = blockIdx.x / SEQ_O;
-    const int kb0 = (int)(((long long)j * KB) / SEQ_O), kb1 = (int)(((long long)(j + 1) * KB) / SEQ_O);
+    const int kb0 = G.kb_of(j), kb1 = G.kb_of(j + 1);
     const int nkb = kb1 - kb0, nchunk = (nkb + NKB - 1) / NKB;
-    if (blockIdx.x == gridDim.x - 1)
-        for (int q = threadIdx.x; q < a.cp_n; q += SEQ_NT) a.cp_dst[q] = a.cp_src[q];
+    seq_commit_state(a);
     const int ntw = a.ntw;
     const int id0 = (rb * SEQ_NW + wave) * ntw;          // this wave's tiles: id0 .. id0 + ntw - 1
     const int wg0 = rb * SEQ_NW * ntw, wg1 = min(wg0 + SEQ_NW * ntw, ntiles) - 1;
@@ -683,10 +762,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
         const int id = id0 + i;
         tv[i] = i < ntw && id < ntiles;
         const int idc = tv[i] ? id : 0;
-        {
-            const int q = idc / CB, ch = 16 * (idc % CB) + (lane & 15), row = Q * ch + q;
-            rsv[i] = a.rs8[(size_t)j * N + ((ch < nch && row < N) ? row : 0)];
-        }
+        rsv[i] = a.rs8[(size_t)j * N + G.row_of(idc, lane, 0)];
         wt[i] = a.bimg + ((size_t)idc * KB) * 64 + lane;
         vi[i] = vec_of(idc / CB) - vlo;
         vi[i] = vi[i] < 0 ? 0 : (vi[i] >= NVS ? NVS - 1 : vi[i]);
@@ -704,8 +780,8 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
         int hv = p / (NKB * 6), pc = p % (NKB * 6);
         int hh = hv / NVS, v = hv % NVS;
         if (hh >= NH || v >= nvec || pc >= np) { hh = 0; v = 0; pc = 0; }
-        const uint8_t *src = reinterpret_cast<const uint8_t *>(img_of(vlo + v) + hh * a.img_h + (size_t)kbs * 384) + lane * 16 + (size_t)pc * 1024;
-        const unsigned dst = abuf_lds + (unsigned)(((size_t)buf * CHU + (size_t)(hh * NVS + v) * NKB * 384) * 16) + (unsigned)pc * 1024u;
+        const uint8_t *src = reinterpret_cast<const uint8_t *>(img_of(vlo + v) + hh * a.img_h + (size_t)kbs * SEQ_KBU) + lane * 16 + (size_t)pc * 1024;
+        const unsigned dst = abuf_lds + (unsigned)(((size_t)buf * CHU + (size_t)(hh * NVS + v) * NKB * SEQ_KBU) * 16) + (unsigned)pc * 1024u;
         dma_piece_shared(np > 0 ? src : reinterpret_cast<const uint8_t *>(img_of(vlo)) + lane * 16, (unsigned)__builtin_amdgcn_readfirstlane((int)dst));
     };
     auto stage_a = [&](int c, int buf) {
@@ -732,13 +808,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
     };
     i32x4 acc[NH][NTW][2][3];
 #pragma unroll
-    for (int hh = 0; hh < NH; hh++)
-#pragma unroll
-        for (int i = 0; i < NTW; i++)
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int b = 0; b < 3; b++) acc[hh][i][mt][b] = i32x4{0, 0, 0, 0};
+    for (int hh = 0; hh < NH; hh++) seq_zero(acc[hh]);
 
     stage_a(0, 0);
 #pragma unroll
@@ -784,15 +854,14 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
 #pragma unroll
                 for (int i = 0; i < NTW; i++) {
                     if (NVS > 1 && i > 0 && vi[i] != vi[i - 1]) read_a(vi[i]);
-                    const u32x4 w = bwr[k % DEPTH][i];
-                    const i32x4 bf = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+                    // (seq_mfma's body in place.  Through the call hipcc lays out the unrolled k steps of <1, 1, 8, 1, 8, false, 2> differently: the same
+                    // loads, waits and MFMAs, but 4 more SGPRs and the second half's LDS addresses added up per step -- a helper is simplified
+                    // before it is inlined, this text together with the loops around it)
+                    const i32x4 bf = seq_i32(bwr[k % DEPTH][i]);
 #pragma unroll
                     for (int ms = 0; ms < 2; ms++)
 #pragma unroll
-                        for (int b = 0; b < 3; b++) {
-                            const i32x4 af = i32x4{(int)av[ms][b][0], (int)av[ms][b][1], (int)av[ms][b][2], (int)av[ms][b][3]};
-                            acc[hh][i][ms][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, acc[hh][i][ms][b], 0, 0, 0);
-                        }
+                        for (int b = 0; b < 3; b++) acc[hh][i][ms][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(seq_i32(av[ms][b]), bf, acc[hh][i][ms][b], 0, 0, 0);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -818,15 +887,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_p(SeqGemmArgs a)
 #pragma unroll
             for (int i = 0; i < NTW; i++) {
                 if (!tv[i]) continue;
-                const int id = id0 + i;
-                const double *rl = recl + 2 * (((size_t)hh * NVS + vi[i]) * SEQ_T + mt * 16 + 4 * (lane >> 4));
-                float *dst = a.pk + hh * a.pk_h + pk_lane_base(ntiles, j, id, mt, lane);
-                const size_t rst = pk_rstride(ntiles);
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const double M = (double)acc[hh][i][mt][0][r] + 256.0 * (double)acc[hh][i][mt][1][r] + 65536.0 * (double)acc[hh][i][mt][2][r];
-                    dst[r * rst] = (float)(rl[2 * r] * (M + rl[2 * r + 1] + SEQ_CU * (double)rsv[i]));   // scale_o (M + cA_o + CU rowsum_o)
-                }
+                seq_emit(acc[hh][i][mt], recl, (size_t)hh * NVS + vi[i], mt, lane, rsv[i], a.pk + hh * a.pk_h + pk_lane_base(ntiles, j, id0 + i, mt, lane));
             }
     tl_stamp(a.tl, 5);
 }
@@ -861,7 +922,6 @@ template <int MAXN> __device__ __forceinline__ void wait_vm_dyn(int n)
 #define RWKV_SEQ_BDEPTH 3
 #endif
 constexpr int SEQ_B_NKB_MAX = 10;        // longest slice whose two-half image fits: 2 x 10 x 6 KiB = 120 KiB (D = 5120)
-constexpr size_t seq_gemm_b_smem(int nkbm, int nh) { return (size_t)nh * nkbm * 384 * 16 + (size_t)nh * SEQ_T * 16; }
 struct SeqGemmBArgs {
     SeqGemmArgs g;
     int grp_tile[4];             // first tile of vector group i (i < ngrp), ntiles behind the last
@@ -873,20 +933,21 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_b(SeqGemmBArgs ba)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     static_assert((DEPTH - 1) * 2 * NTW <= 40, "k_seq_gemm_b: the wait dispatch covers 40 requests");
+    static_assert(seq_lds_image(1, NH, 1, SEQ_B_NKB_MAX).ok(), "k_seq_gemm_b: LDS layout of the longest slice it is launched for");
     const SeqGemmArgs &a = ba.g;
     RWKV_ARGS_NOW(a.bimg, a.rs8, a.img[0], a.img[1], a.img[2], a.part, a.pk, a.tl);      // (see k_seq_gemm_p)
-    const int K = a.K, KB = K >> 6, N = a.N, Q = a.Q;
-    const int nkbm = (KB + SEQ_O - 1) / SEQ_O;                    // longest slice
-    u32x4 *abuf = reinterpret_cast<u32x4 *>(smem);
-    double *recl = reinterpret_cast<double *>(smem + (size_t)NH * nkbm * 384 * 16);   // [NH][SEQ_T]{scale, cA} of this slice
+    const SeqGeo G(a.N, a.K, a.Q);
+    const int KB = G.KB, N = G.N, CB = G.CB, ntiles = G.ntiles;
+    const int nkbm = (KB + SEQ_O - 1) / SEQ_O;                    // longest slice: what the host sized the image by
+    const SeqLds LDS = seq_lds_image(1, NH, 1, nkbm);
+    u32x4 *abuf = reinterpret_cast<u32x4 *>(smem + LDS.img);
+    double *recl = reinterpret_cast<double *>(smem + LDS.recl);               // [NH][SEQ_T]{scale, cA} of this slice
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     tl_stamp(a.tl, 0);
-    const int nch = (N + Q - 1) / Q, CB = (nch + 15) >> 4, ntiles = Q * CB;
     const int j = blockIdx.x % SEQ_O, rb = blockIdx.x / SEQ_O;
-    const int kb0 = (int)(((long long)j * KB) / SEQ_O), kb1 = (int)(((long long)(j + 1) * KB) / SEQ_O);
+    const int kb0 = G.kb_of(j), kb1 = G.kb_of(j + 1);
     const int nkb = kb1 - kb0;
-    if (blockIdx.x == gridDim.x - 1)
-        for (int q = threadIdx.x; q < a.cp_n; q += SEQ_NT) a.cp_dst[q] = a.cp_src[q];
+    seq_commit_state(a);
     // this workgroup's vector group, this wave's tiles id0 .. id0 + tpw - 1 of it
     int gi = 0;
     while (gi + 1 < ba.ngrp && rb >= ba.grp_rb[gi + 1]) gi++;
@@ -916,21 +977,15 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_b(SeqGemmBArgs ba)
     i32x4 acc[NH][NTW][2][3];
     auto zero_acc = [&]() {
 #pragma unroll
-        for (int hh = 0; hh < NH; hh++)
-#pragma unroll
-            for (int i = 0; i < NTW; i++)
-#pragma unroll
-                for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                    for (int b = 0; b < 3; b++) acc[hh][i][mt][b] = i32x4{0, 0, 0, 0};
+        for (int hh = 0; hh < NH; hh++) seq_zero(acc[hh]);
     };
     // the slice's image of vector v, both halves: 1 KiB pieces round-robin over the waves
     {
         const int np = nkb * 6;
         for (int hh = 0; hh < NH; hh++)
             for (int pc = wave; pc < np; pc += SEQ_NW) {
-                const uint8_t *src = reinterpret_cast<const uint8_t *>(a.img[v] + hh * a.img_h + (size_t)kb0 * 384) + lane * 16 + (size_t)pc * 1024;
-                const unsigned dst = abuf_lds + (unsigned)(hh * nkbm * 384 * 16) + (unsigned)pc * 1024u;
+                const uint8_t *src = reinterpret_cast<const uint8_t *>(a.img[v] + hh * a.img_h + (size_t)kb0 * SEQ_KBU) + lane * 16 + (size_t)pc * 1024;
+                const unsigned dst = abuf_lds + (unsigned)(hh * nkbm * SEQ_KBU * 16) + (unsigned)pc * 1024u;
                 dma_piece_shared(src, (unsigned)__builtin_amdgcn_readfirstlane((int)dst));
             }
     }
@@ -945,9 +1000,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_b(SeqGemmBArgs ba)
 #pragma unroll
                 for (int i = 0; i < NTW; i++)
                     if (m >> i & 1) {
-                        const int id = id0 + lb * bs + i;
-                        const int q = id / CB, ch = 16 * (id % CB) + (lane & 15), row = Q * ch + q;
-                        rsn[i] = load_u32_asm(a.rs8 + (size_t)j * N + ((ch < nch && row < N) ? row : 0));
+                        rsn[i] = load_u32_asm(a.rs8 + (size_t)j * N + G.row_of(id0 + lb * bs + i, lane, 0));
                         n++;
                     }
             }
@@ -998,26 +1051,17 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_b(SeqGemmBArgs ba)
                 for (int i = 0; i < NTW; i++) { asm volatile("" : "+v"(rsn[i])); rsv[i] = rsn[i]; }
             }
             __builtin_amdgcn_sched_barrier(0);
-            const u32x4 *ab = abuf + lane + (size_t)cf * 384;
+            const u32x4 *ab = abuf + lane + (size_t)cf * SEQ_KBU;
 #pragma unroll
             for (int hh = 0; hh < NH; hh++) {
                 u32x4 av[2][3];
 #pragma unroll
                 for (int ms = 0; ms < 2; ms++)
 #pragma unroll
-                    for (int b = 0; b < 3; b++) av[ms][b] = ab[(size_t)hh * nkbm * 384 + (ms * 3 + b) * 64];
+                    for (int b = 0; b < 3; b++) av[ms][b] = ab[(size_t)hh * nkbm * SEQ_KBU + (ms * 3 + b) * 64];
 #pragma unroll
                 for (int i = 0; i < NTW; i++) {
-                    if (!(m >> i & 1)) continue;
-                    const u32x4 w = bwr[s][i];
-                    const i32x4 bf = i32x4{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
-#pragma unroll
-                    for (int ms = 0; ms < 2; ms++)
-#pragma unroll
-                        for (int b = 0; b < 3; b++) {
-                            const i32x4 af = i32x4{(int)av[ms][b][0], (int)av[ms][b][1], (int)av[ms][b][2], (int)av[ms][b][3]};
-                            acc[hh][i][ms][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, acc[hh][i][ms][b], 0, 0, 0);
-                        }
+                    if (m >> i & 1) seq_mfma(bwr[s][i], av, acc[hh][i]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1030,15 +1074,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_b(SeqGemmBArgs ba)
 #pragma unroll
                         for (int i = 0; i < NTW; i++) {
                             if (!(m >> i & 1)) continue;
-                            const int id = id0 + cb * bs + i;
-                            const double *rl = recl + 2 * ((size_t)hh * SEQ_T + mt * 16 + 4 * (lane >> 4));
-                            float *dst = a.pk + hh * a.pk_h + pk_lane_base(ntiles, j, id, mt, lane);
-                            const size_t rst = pk_rstride(ntiles);
-#pragma unroll
-                            for (int r = 0; r < 4; r++) {
-                                const double M = (double)acc[hh][i][mt][0][r] + 256.0 * (double)acc[hh][i][mt][1][r] + 65536.0 * (double)acc[hh][i][mt][2][r];
-                                dst[r * rst] = (float)(rl[2 * r] * (M + rl[2 * r + 1] + SEQ_CU * (double)rsv[i]));   // scale_o (M + cA_o + CU rowsum_o)
-                            }
+                            seq_emit(acc[hh][i][mt], recl, hh, mt, lane, rsv[i], a.pk + hh * a.pk_h + pk_lane_base(ntiles, j, id0 + cb * bs + i, mt, lane));
                         }
                 zero_acc();
                 cf = 0; cb++;
@@ -1046,7 +1082,6 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_b(SeqGemmBArgs ba)
             }
         }
     }
-    tl_stamp(a.tl, 4);
     tl_stamp(a.tl, 5);
 }
 
@@ -1067,16 +1102,7 @@ template <int NTL>
 __device__ __forceinline__ void seq_frag_mfma(const SeqFrag<NTL> &f, i32x4 (&acc)[SEQ_TB][2][3])
 {
 #pragma unroll
-    for (int i = 0; i < NTL; i++) {
-        const i32x4 bf = i32x4{(int)f.bw[i][0], (int)f.bw[i][1], (int)f.bw[i][2], (int)f.bw[i][3]};
-#pragma unroll
-        for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-            for (int b = 0; b < 3; b++) {
-                const i32x4 af = i32x4{(int)f.af[mt][b][0], (int)f.af[mt][b][1], (int)f.af[mt][b][2], (int)f.af[mt][b][3]};
-                acc[i][mt][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(af, bf, acc[i][mt][b], 0, 0, 0);
-            }
-    }
+    for (int i = 0; i < NTL; i++) seq_mfma(f.bw[i], f.af, acc[i]);
 }
 // K loop of one pass over NTL tiles: wave w multiplies the k-blocks [kb0, kb1) of ITS octant; operands of the next
 // k-block(s) are requested before the MFMAs of the current one issue.
@@ -1108,17 +1134,16 @@ __device__ __forceinline__ void seq_pass(i32x4 (&acc)[SEQ_TB][2][3], const u32x4
 __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_ks(SeqGemmArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    float (*accl)[SEQ_TB][2][4][64] = reinterpret_cast<float (*)[SEQ_TB][2][4][64]>(smem);   // [octant][tile][row tile][reg][lane], 80 KiB
-    float *sol = reinterpret_cast<float *>(smem + sizeof(float) * SEQ_O * SEQ_TB * 2 * 4 * 64);
+    constexpr SeqLds LDS = seq_lds_ks();
+    static_assert(LDS.ok(), "k_seq_gemm_ks: LDS layout");
+    float (*accl)[SEQ_TB][2][4][64] = reinterpret_cast<float (*)[SEQ_TB][2][4][64]>(smem + LDS.accl);      // [octant][tile][row tile][reg][lane]
+    float *sol = reinterpret_cast<float *>(smem + LDS.sol);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int K = a.K, KB = K >> 6, N = a.N, Q = a.Q;
-    const int nch = (N + Q - 1) / Q;                    // channels per class
-    const int CB = (nch + 15) >> 4;                     // 16-channel blocks per class
-    const int ntiles = Q * CB;
-    const int tb0 = block_lo(ntiles), tb1 = block_hi(ntiles);
-    const int kb0 = (int)(((long long)wave * KB) / SEQ_O), kb1 = (int)(((long long)(wave + 1) * KB) / SEQ_O);
-    if (blockIdx.x == gridDim.x - 1)
-        for (int j = threadIdx.x; j < a.cp_n; j += SEQ_NT) a.cp_dst[j] = a.cp_src[j];
+    const SeqGeo G(a.N, a.K, a.Q);
+    const int KB = G.KB, N = G.N, CB = G.CB;
+    const int tb0 = block_lo(G.ntiles), tb1 = block_hi(G.ntiles);
+    const int kb0 = G.kb_of(wave), kb1 = G.kb_of(wave + 1);
+    seq_commit_state(a);
 
     int tg = tb0;
     int vcur = -1;
@@ -1136,12 +1161,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_ks(SeqGemmArgs a)
         for (int i = 0; i < SEQ_TB; i++) wt[i] = a.bimg + ((size_t)(tg + (i < nt ? i : 0)) * KB) * 64 + lane;
         const u32x4 *img = a.img[v0];
         i32x4 acc[SEQ_TB][2][3];
-#pragma unroll
-        for (int i = 0; i < SEQ_TB; i++)
-#pragma unroll
-            for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-                for (int b = 0; b < 3; b++) acc[i][mt][b] = i32x4{0, 0, 0, 0};
+        seq_zero(acc);
         switch (nt) {
         case 1: seq_pass<1, 4>(acc, wt, img, kb0, kb1, lane); break;
         case 2: seq_pass<2, 3>(acc, wt, img, kb0, kb1, lane); break;
@@ -1154,8 +1174,8 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_ks(SeqGemmArgs a)
 #pragma unroll
         for (int i = 0; i < SEQ_TB; i++)
             if (i < nt) {
-                const int id = tg + i, q = id / CB, ch = 16 * (id % CB) + (lane & 15), row = Q * ch + q;
-                const bool rok = ch < nch && row < N;
+                const int row = G.row_of(tg + i, lane, -1);
+                const bool rok = row >= 0;
                 const unsigned rs = rok ? a.rs8[(size_t)wave * N + row] : 0u;
 #pragma unroll
                 for (int mt = 0; mt < 2; mt++)
@@ -1165,8 +1185,7 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_ks(SeqGemmArgs a)
                         float val = 0.f;
                         if (t < a.T && rok) {
                             const SeqPart rc = a.part[((size_t)v0 * SEQ_T + t) * SEQ_O + wave];
-                            const double M = (double)acc[i][mt][0][r] + 256.0 * (double)acc[i][mt][1][r] + 65536.0 * (double)acc[i][mt][2][r];
-                            val = (float)seq_slice_value(rc, M, rs);
+                            val = (float)seq_slice_value(rc, seq_fold(acc[i][mt], r), rs);
                         }
                         accl[wave][i][mt][r][lane] = val;
                     }
@@ -1176,9 +1195,8 @@ __global__ __launch_bounds__(SEQ_NT) void k_seq_gemm_ks(SeqGemmArgs a)
         for (int e = threadIdx.x; e < nt * 2 * 4 * 64; e += SEQ_NT) {
             const int ln = e & 63, r = (e >> 6) & 3, mt = (e >> 8) & 1, i = e >> 9;
             const int t = mt * 16 + 4 * (ln >> 4) + r;
-            const int id = tg + i, q = id / CB, ch = 16 * (id % CB) + (ln & 15);
-            const int row = Q * ch + q;
-            if (t < a.T && ch < nch && row < N) {
+            const int row = G.row_of(tg + i, ln, -1);
+            if (t < a.T && row >= 0) {
                 double v = 0.0;
 #pragma unroll
                 for (int o = 0; o < SEQ_O; o++) v += (double)accl[o][i][mt][r][ln];
