@@ -23,6 +23,7 @@
 #include <map>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 using namespace rwkvk;
@@ -171,6 +172,35 @@ struct SeqHalf {
           pk3((size_t)SEQ_O * 3 * ((D + 15) / 16) * 512), pk5((size_t)SEQ_O * 5 * ((D + 15) / 16) * 512), pk1((size_t)SEQ_O * ((D + 15) / 16) * 512) {}
 };
 
+// One weight class: the uint8 matrices one decode kernel streams and one GEMM of the chunk path multiplies with.  N = Q row classes x `rows`
+// outputs (rows = D, or the vocabulary for the head), K = kd D inputs.  What a layer of it occupies follows from those three; which tensors of the
+// file make its row form -- row q + RS j of the class's matrix = row j of the tensor's matrix -- is the `src` list (k_retile's arguments).
+struct WSrc { int slot, n, m, G, RS, off; };     // file tensor [n D][m D] (m = 0: [D][vocabulary]), re-tiled with (G, RS, off)
+struct WClass {
+    int Q, kd;
+    bool vocab;
+    int nsrc;
+    WSrc src[3];
+    // device, [layers of the stage] each (the head: one): row form (nullptr: the class runs in tile form) and its row sums; the chunk
+    // path's image of 16-row tiles and the row sums per octant of K; the image the tile-form decode kernel streams (= b where its tiles are 16 rows)
+    uint8_t *w = nullptr, *b = nullptr, *t = nullptr;
+    unsigned *rs = nullptr, *r8 = nullptr;
+    uint64_t rows(uint64_t D) const { return vocab ? (uint64_t)RWKV_VOCAB : D; }
+    uint64_t N(uint64_t D) const { return Q * rows(D); }
+    uint64_t K(uint64_t D) const { return kd * D; }
+    // per layer: bytes of the row form (and of an image of 4-row tiles: D is a multiple of 16), bytes of the 16-row image, row sums, octant row sums
+    uint64_t row_bytes(uint64_t D) const { return N(D) * K(D); }
+    uint64_t img_bytes(uint64_t D) const { return Q * ((rows(D) + 15) / 16) * 16 * K(D); }
+    uint64_t sums(uint64_t D) const { return N(D); }
+    uint64_t sums8(uint64_t D) const { return SEQ_O * N(D); }
+    // layer wl of the stage
+    const uint8_t *w_at(uint64_t wl, uint64_t D) const { return w ? w + wl * row_bytes(D) : nullptr; }
+    const uint8_t *b_at(uint64_t wl, uint64_t D) const { return b + wl * img_bytes(D); }
+    const uint8_t *t_at(uint64_t wl, uint64_t D) const { return t + wl * row_bytes(D); }      // (a layer's images are as large as its row form: D is a multiple of 16)
+    const unsigned *rs_at(uint64_t wl, uint64_t D) const { return rs + wl * sums(D); }
+    const unsigned *r8_at(uint64_t wl, uint64_t D) const { return r8 + wl * sums8(D); }
+};
+
 struct rwkv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -203,8 +233,14 @@ struct rwkv_ctx {
     double *sitePD[3] = {nullptr, nullptr, nullptr};  // [grid][8] per-workgroup partial tuples
     float *sitePF[3] = {nullptr, nullptr, nullptr};   // [grid][4]
     double *lnstat = nullptr;                         // [3][2] mean, rstd per site
-    uint8_t *w_kvr = nullptr, *w_att = nullptr, *w_frk = nullptr, *w_fv = nullptr, *w_head = nullptr;
-    unsigned *rs_kvr = nullptr, *rs_att = nullptr, *rs_frk = nullptr, *rs_fv = nullptr, *rs_head = nullptr;   // row sums
+    // the matrices: index = decode kernel class - 1 (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v), 4 = the head
+    WClass wc[5] = {
+        {3, 1, false, 3, {{KM, 1, 1, 1, 3, 0}, {VM, 1, 1, 1, 3, 1}, {RM, 1, 1, 1, 3, 2}}},
+        {1, 1, false, 1, {{ATTOUT, 1, 1, 1, 1, 0}}},
+        {5, 1, false, 2, {{FFNK, 1, 4, 4, 5, 0}, {FFNR, 1, 1, 1, 5, 4}}},      // rows 5 i + q = ffn_k output 4 i + q, row 5 i + 4 = ffn_r output i
+        {1, 4, false, 1, {{FFNV, 4, 1, 1, 1, 0}}},
+        {1, 1, true, 1, {{HEAD, 1, 0, 1, 1, 0}}},
+    };
     // state + scratch (device)
     double *state[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     double *x = nullptr, *partA = nullptr, *partF = nullptr;
@@ -256,13 +292,9 @@ struct rwkv_ctx {
     double hop_stats[4] = {0.0, 0.0, 0.0, 0.0};
     Ctl *pipe_ring = nullptr;                     // pinned control blocks of rwkv_pipe_decode's items (grown on demand, kept)
     uint64_t pipe_ring_cap = 0;
-    // second resident copy of the matrices (chunked path only): MFMA B-operand images, row sums per octant of K
-    uint8_t *b_kvr = nullptr, *b_att = nullptr, *b_frk = nullptr, *b_fv = nullptr, *b_head = nullptr;
-    // tile images the tile-form DECODE kernels stream (tile.hip.h): the chunk path's own (16-row tiles) where a workgroup owns one 16-channel
-    // block, else a decode-only image of 4-row tiles
-    uint8_t *t_kvr = nullptr, *t_att = nullptr, *t_frk = nullptr, *t_fv = nullptr;
+    // tile-form decode kernels (tile.hip.h): they stream the chunk path's own image (16-row tiles) where a workgroup owns one 16-channel block,
+    // else a decode-only image of 4-row tiles (WClass::t)
     int tile_th = 0, tile_s = 0, tile_tpc = 0;     // rows per tile, KiB per ring unit, tiles per row class and workgroup (0: no tile form at this width)
-    unsigned *r8_kvr = nullptr, *r8_att = nullptr, *r8_frk = nullptr, *r8_fv = nullptr, *r8_head = nullptr;
     // batched decode (rwkv_decode_batch_*): allocated at the first call, grown to the largest one seen, freed by rwkv_free
     struct Grown { void *p = nullptr; size_t bytes = 0; };
     Grown bd_ids;                                 // u64 [n seeds][n_steps + 1][n]: row 0 = the first tokens, row k + 1 = the picks of step k
@@ -285,25 +317,28 @@ template <typename T> int dalloc(rwkv_ctx *c, T **p, size_t count)
     return 0;
 }
 
-// one staged vector = 3 limb planes of S x 1 KiB
-size_t smem_att(int S) { return RED_BYTES + 3 * (size_t)S * 3072; }
-size_t smem_attout(int S) { return RED_BYTES + (size_t)S * 3072; }
-size_t smem_frk(int S) { return RED_BYTES + 2 * (size_t)S * 3072; }
-size_t smem_fv(int S) { return RED_BYTES + 4 * (size_t)S * 3072; }
-size_t smem_head(int S) { return RED_BYTES + (size_t)S * 3072 + NW * 8; }
-
 // tile-form decode kernels (tile.hip.h; classes 1 att, 2 att_out, 3 ffn_rk, 4 ffn_v): ring of S KiB units behind each kernel's fixed LDS.
-// Which widths have a tile form: those whose channels split into whole TH-row tiles per workgroup on this grid --
+// Which widths have a tile form: those whose channels split into whole TH-row tiles per workgroup on this grid.  The three instances, each
+// written once -- width, KiB per ring unit, rows per tile, tiles per row class and workgroup; the kernels' other template arguments follow:
 //   D = 4096 on 256 CUs: 16 channels = ONE 16-row tile per class (the chunk path's own image; the default there)
 //   D = 5120 on 256 CUs: 20 channels = five 4-row tiles (a decode-only image of 4-row tiles)
 //   D = 2048 on 256 CUs:  8 channels = two 4-row tiles
+template <int D_, int S_, int TH_, int TPC_> struct TileInst {
+    static constexpr int D = D_, S = S_, TH = TH_, TPC = TPC_, SD = D / 1024;
+    static constexpr int KBT = D * TH / 1024, KBT_FV = 4 * KBT;      // fragments (1 KiB) of a tile along K = D, and along ffn_v's K = 4 D
+    static_assert(TH * TPC * 256 == D, "a workgroup's tiles are its share of the channels on 256 workgroups");
+};
+using Tile4096 = TileInst<4096, 4, 16, 1>;
+using Tile5120 = TileInst<5120, 5, 4, 5>;
+using Tile2048 = TileInst<2048, 4, 4, 2>;
 struct TileCfg { int th, s, tpc; };
+template <class T> TileCfg tile_cfg_of() { return TileCfg{T::TH, T::S, T::TPC}; }
 TileCfg tile_cfg_for(uint64_t D, int grid)
 {
     if (grid != 256) return TileCfg{0, 0, 0};
-    if (D == 4096) return TileCfg{16, 4, 1};
-    if (D == 5120) return TileCfg{4, 5, 5};
-    if (D == 2048) return TileCfg{4, 4, 2};
+    if (D == Tile4096::D) return tile_cfg_of<Tile4096>();
+    if (D == Tile5120::D) return tile_cfg_of<Tile5120>();
+    if (D == Tile2048::D) return tile_cfg_of<Tile2048>();
     return TileCfg{0, 0, 0};
 }
 // fixed LDS bytes, ring units and launch bytes of a class, from the kernels' own description of their LDS (tile.hip.h tile_lds_of)
@@ -317,16 +352,26 @@ size_t tile_smem(const rwkv_ctx *c, int cls) { return tile_fixed(c, cls) + (size
 // a class runs in tile form when asked to (RWKV_TILE bit cls - 1) and its image is there
 bool tile_ok(const rwkv_ctx *c, int cls)
 {
-    const uint8_t *img = cls == 1 ? c->t_kvr : cls == 2 ? c->t_att : cls == 3 ? c->t_frk : c->t_fv;
-    return c->tile > 0 && ((c->tile >> (cls - 1)) & 1) && img != nullptr;
+    return c->tile > 0 && ((c->tile >> (cls - 1)) & 1) && c->wc[cls - 1].t != nullptr;
 }
-// launch of a tile-form kernel template for the context's configuration
-#define TILE_DISPATCH(c, CALL16, CALL4_5, CALL4_2)                                  \
-    do {                                                                            \
-        if ((c)->tile_th == 16) { CALL16; }                                         \
-        else if ((c)->tile_tpc == 5) { CALL4_5; }                                   \
-        else { CALL4_2; }                                                           \
-    } while (0)
+// f(the context's tile instance); f(1 .. 5 as a type): how a run-time configuration becomes template arguments
+template <class F> auto by_tile(const rwkv_ctx *c, F f)
+{
+    if (c->tile_th == Tile4096::TH) return f(Tile4096{});
+    if (c->tile_tpc == Tile5120::TPC) return f(Tile5120{});
+    return f(Tile2048{});
+}
+template <int S> using SConst = std::integral_constant<int, S>;
+template <class F> auto by_s(int S, F f)
+{
+    switch (S) {
+    case 1: return f(SConst<1>{});
+    case 2: return f(SConst<2>{});
+    case 3: return f(SConst<3>{});
+    case 4: return f(SConst<4>{});
+    default: return f(SConst<5>{});
+    }
+}
 
 // k-blocks a wave of k_seq_gemm_p keeps in flight (K/V/R, ffn k/r at up to 4 KiB rows; a divisor of 8)
 #ifndef RWKV_SEQ_DEPTH0
@@ -343,15 +388,6 @@ constexpr int SITE_NV[3] = {3, 2, 1};
 constexpr int SQ_RING = 8;   // prompt chunks whose token ids may be in flight between host and device
 constexpr int SITE_PW[3] = {site_pw<3>(), site_pw<2>(), site_pw<1>()};
 
-#define DISPATCH_S(S, ...)                                           \
-    switch (S) {                                                     \
-    case 1: { constexpr int S_ = 1; __VA_ARGS__; } break;            \
-    case 2: { constexpr int S_ = 2; __VA_ARGS__; } break;            \
-    case 3: { constexpr int S_ = 3; __VA_ARGS__; } break;            \
-    case 4: { constexpr int S_ = 4; __VA_ARGS__; } break;            \
-    default: { constexpr int S_ = 5; __VA_ARGS__; } break;           \
-    }
-
 template <typename K> int allow_smem(K kernel, size_t bytes)
 {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -365,6 +401,7 @@ struct ArgMaker {
     rwkv_ctx *c;
     int D, grid, n_first;
     size_t LD;
+    uint64_t wl(uint64_t l) const { return l - c->l0; }      // vectors are indexed by the model's layer, matrices by the stage's
     explicit ArgMaker(rwkv_ctx *c_) : c(c_), D((int)c_->D), grid(c_->grid), LD((size_t)c_->L * c_->D) { n_first = grid < 32 ? grid : 32; }
     unsigned long long *tl_of(int k, uint64_t l) const { return (c->tl_on && k == c->tl_cls && l == (c->l0 + c->l1) / 2) ? c->tl : nullptr; }
     SiteStatic site_static(int k, uint64_t ll) const
@@ -394,7 +431,7 @@ struct ArgMaker {
         const size_t lo = (size_t)l * D;
         AttArgs aa;
         aa.x = c->x; aa.st = site_static(0, l); aa.dy = site_dyn(0, l == c->l0 ? n_first : grid);
-        aa.w = c->w_kvr ? c->w_kvr + (size_t)(l - c->l0) * 3 * D * D : nullptr; aa.rs = c->rs_kvr + (size_t)(l - c->l0) * D * 3;
+        aa.w = c->wc[0].w_at(wl(l), D); aa.rs = c->wc[0].rs_at(wl(l), D);
         aa.uw = c->uw + lo; aa.ew = c->ew + lo;
         aa.r_att = c->attr + lo; aa.o_att = c->atto + lo;
         aa.saa = c->state[1] + lo; aa.sbb = c->state[2] + lo;
@@ -406,7 +443,7 @@ struct ArgMaker {
     {
         const size_t lo = (size_t)l * D;
         AttOutArgs ao;
-        ao.w = c->w_att ? c->w_att + (size_t)(l - c->l0) * D * D : nullptr; ao.rs = c->rs_att + (size_t)(l - c->l0) * D; ao.ybuf = c->ybuf; ao.partS = c->partA; ao.partM = c->partMA; ao.n_part = grid;
+        ao.w = c->wc[1].w_at(wl(l), D); ao.rs = c->wc[1].rs_at(wl(l), D); ao.ybuf = c->ybuf; ao.partS = c->partA; ao.partM = c->partMA; ao.n_part = grid;
         ao.x = c->x; ao.lnw = c->ln + (4 * l + 2) * D; ao.lnb = c->ln + (4 * l + 3) * D; ao.lnstat = c->lnstat + 0;
         ao.sxy = c->state[0] + lo; ao.st = site_static(1, l); ao.dy = site_dyn(1, grid); ao.sdd = c->state[4] + lo;
         ao.slot_stride = LD; ao.ctl = c->ctl; ao.D = D; ao.ns = 0; ao.tl = tl_of(2, l); ao.herr = c->d_herr;
@@ -417,7 +454,7 @@ struct ArgMaker {
         const size_t lo = (size_t)l * D;
         FfnRKArgs fa;
         fa.x = c->x; fa.st = site_static(1, l); fa.dy = site_dyn(1, grid);
-        fa.w = c->w_frk ? c->w_frk + (size_t)(l - c->l0) * 5 * D * D : nullptr; fa.rs = c->rs_frk + (size_t)(l - c->l0) * D * 5;
+        fa.w = c->wc[2].w_at(wl(l), D); fa.rs = c->wc[2].rs_at(wl(l), D);
         fa.r_fv = c->fvr + 4 * lo; fa.o_fv = c->fvo + 4 * lo;
         fa.hbuf = c->hbuf; fa.rgate = c->rgate; fa.partS = c->partF; fa.partM = c->partMF; fa.ctl = c->ctl; fa.D = D;
         fa.ns = 0; fa.tl = tl_of(3, l); fa.herr = c->d_herr;
@@ -430,7 +467,7 @@ struct ArgMaker {
     {
         const size_t lo = (size_t)l * D;
         FfnVArgs fv;
-        fv.w = c->w_fv ? c->w_fv + (size_t)(l - c->l0) * 4 * D * D : nullptr; fv.rs = c->rs_fv + (size_t)(l - c->l0) * D; fv.hbuf = c->hbuf; fv.partS = c->partF; fv.partM = c->partMF; fv.n_part = grid;
+        fv.w = c->wc[3].w_at(wl(l), D); fv.rs = c->wc[3].rs_at(wl(l), D); fv.hbuf = c->hbuf; fv.partS = c->partF; fv.partM = c->partMF; fv.n_part = grid;
         fv.rgate = c->rgate; fv.x = c->x; fv.lnw = c->ln + (4 * l + 4) * D; fv.lnb = c->ln + (4 * l + 5) * D; fv.lnstat = c->lnstat + 2;
         fv.sdd = c->state[4] + lo; fv.slot_stride = LD; fv.ctl = c->ctl; fv.D = D; fv.tl = tl_of(4, l);
         fv.ns = 0; fv.herr = c->d_herr;
@@ -441,89 +478,79 @@ struct ArgMaker {
     HeadArgs head() const
     {
         HeadArgs ha;
-        ha.x = c->x; ha.st = site_static(2, 0); ha.dy = site_dyn(2, grid); ha.w = c->w_head; ha.rs = c->rs_head; ha.logits = c->logits;
+        ha.x = c->x; ha.st = site_static(2, 0); ha.dy = site_dyn(2, grid); ha.w = c->wc[4].w; ha.rs = c->wc[4].rs; ha.logits = c->logits;
         ha.blk_val = c->blk_val; ha.blk_idx = c->blk_idx; ha.ctl = c->ctl; ha.D = D;
         return ha;
     }
 };
 
+// The decode kernels' instances, ONE table: which kernel runs a class for the context's configuration -- the tile form (tile_ok) at the context's
+// tile instance, else the row form at S = ceil(D / 1024) -- with its dynamic LDS bytes (the kernels' own descriptions: tile.hip.h tile_lds_of,
+// kernels.hip.h row_lds_of).  A = the row form's argument block, TA = the tile form's (A + the image); exactly one of row / tile is set.
+// (The order of the functions and of the forms inside them is the order in which hipcc instantiates the kernels, and that is their order in the
+// code object -- per class the tile instances, then the row instances, as it always was: profiles/decode_host/isa_compare.txt.)
+template <class A, class TA = A> struct DecodeInst { void (*row)(A); void (*tile)(TA); size_t smem; };
+DecodeInst<AttArgs, AttTArgs> att_inst(const rwkv_ctx *c)
+{
+    if (tile_ok(c, 1)) return {nullptr, by_tile(c, [](auto t) { using T = decltype(t); return &k_att_t<T::SD, T::S, T::KBT, T::TH, T::TPC>; }), tile_smem(c, 1)};
+    return {by_s(c->S, [](auto s) { return &k_att<decltype(s)::value>; }), nullptr, row_lds_of(1, c->S).bytes};
+}
+DecodeInst<AttOutArgs, AttOutTArgs> attout_inst(const rwkv_ctx *c)
+{
+    if (tile_ok(c, 2)) return {nullptr, by_tile(c, [](auto t) { using T = decltype(t); return &k_attout_t<T::SD, T::S, T::KBT, T::TH, T::TPC>; }), tile_smem(c, 2)};
+    return {by_s(c->S, [](auto s) { return &k_attout<decltype(s)::value, ATTOUT_R>; }), nullptr, row_lds_of(2, c->S).bytes};
+}
+DecodeInst<FfnRKArgs, FfnRKTArgs> frk_inst(const rwkv_ctx *c)
+{
+    if (tile_ok(c, 3)) return {nullptr, by_tile(c, [](auto t) { using T = decltype(t); return &k_ffn_rk_t<T::SD, T::S, T::KBT, T::TH, T::TPC>; }), tile_smem(c, 3)};
+    return {by_s(c->S, [](auto s) { return &k_ffn_rk<decltype(s)::value>; }), nullptr, row_lds_of(3, c->S).bytes};
+}
+// ffn_v opens the next site: NVN = 3 vectors (ln1 of the next layer) or 1 (ln_out, ArgMaker::fv_next_att)
+DecodeInst<FfnVArgs, FfnVTArgs> fv_inst(const rwkv_ctx *c, bool next_att)
+{
+    if (tile_ok(c, 4)) {
+        const auto k3 = by_tile(c, [](auto t) { using T = decltype(t); return &k_ffnv_t<T::SD, T::S, T::KBT_FV, T::TH, T::TPC, 3>; });
+        const auto k1 = by_tile(c, [](auto t) { using T = decltype(t); return &k_ffnv_t<T::SD, T::S, T::KBT_FV, T::TH, T::TPC, 1>; });
+        return {nullptr, next_att ? k3 : k1, tile_smem(c, 4)};
+    }
+    const auto k3 = by_s(c->S, [](auto s) { return &k_ffnv<decltype(s)::value, 3>; });
+    const auto k1 = by_s(c->S, [](auto s) { return &k_ffnv<decltype(s)::value, 1>; });
+    return {next_att ? k3 : k1, nullptr, row_lds_of(4, c->S).bytes};
+}
+DecodeInst<HeadArgs> head_inst(const rwkv_ctx *c)      // (row form only)
+{
+    return {by_s(c->S, [](auto s) { return &k_head<decltype(s)::value>; }), nullptr, row_lds_of(5, c->S).bytes};
+}
+template <class A, class TA> int allow_smem(const DecodeInst<A, TA> &k) { return k.tile ? allow_smem(k.tile, k.smem) : allow_smem(k.row, k.smem); }
+
 // ---- one launch helper per kernel class (0 embed, 1 att, 2 att_out, 3 ffn_rk, 4 ffn_v, 5 head, 6 argmax) ----
+// a per-layer class: the instance's row form on the class's argument block, or its tile form on the block + the ring's length and the layer's image
+template <class A, class TA> void launch_inst(rwkv_ctx *c, const DecodeInst<A, TA> &k, const A &a, int cls, uint64_t l)
+{
+    if (!k.tile) { k.row<<<dim3(c->grid), dim3(NT), k.smem, c->stream>>>(a); return; }
+    TA ta;
+    ta.a = a; ta.a.ns = tile_units(c, cls);
+    ta.im.CB = (int)c->D / c->tile_th; ta.im.bimg = c->wc[cls - 1].t_at(l - c->l0, c->D);
+    k.tile<<<dim3(c->grid), dim3(NT), k.smem, c->stream>>>(ta);
+}
 void launch_class(rwkv_ctx *c, int cls, uint64_t l)
 {
-    const int S = c->S, grid = c->grid;
     const ArgMaker mk(c);
     switch (cls) {
     case 0: {
         FirstArgs fa = mk.first();
         k_first<<<dim3(mk.n_first), dim3(NT), 0, c->stream>>>(fa);
     } break;
-    case 1: {
-        AttArgs aa = mk.att(l);
-        if (tile_ok(c, 1)) {
-            AttTArgs ta;
-            ta.a = aa; ta.a.ns = tile_units(c, 1);
-            ta.im.CB = mk.D / c->tile_th; ta.im.bimg = c->t_kvr + (size_t)(l - c->l0) * 3 * (size_t)mk.D * mk.D;
-            const size_t sm = tile_smem(c, 1);
-            TILE_DISPATCH(c, (k_att_t<4, 4, 64, 16, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                          (k_att_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                          (k_att_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
-        }
-        else DISPATCH_S(S, k_att<S_><<<dim3(grid), dim3(NT), smem_att(S), c->stream>>>(aa));
-    } break;
-    case 2: {
-        AttOutArgs ao = mk.attout(l);
-        if (tile_ok(c, 2)) {
-            AttOutTArgs ta;
-            ta.a = ao; ta.a.ns = tile_units(c, 2);
-            ta.im.CB = mk.D / c->tile_th; ta.im.bimg = c->t_att + (size_t)(l - c->l0) * (size_t)mk.D * mk.D;
-            const size_t sm = tile_smem(c, 2);
-            TILE_DISPATCH(c, (k_attout_t<4, 4, 64, 16, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                          (k_attout_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                          (k_attout_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
-        }
-        else DISPATCH_S(S, k_attout<S_, ATTOUT_R><<<dim3(grid), dim3(NT), smem_attout(S), c->stream>>>(ao));
-    } break;
-    case 3: {
-        FfnRKArgs fa = mk.frk(l);
-        if (tile_ok(c, 3)) {
-            FfnRKTArgs ta;
-            ta.a = fa; ta.a.ns = tile_units(c, 3);
-            ta.im.CB = mk.D / c->tile_th; ta.im.bimg = c->t_frk + (size_t)(l - c->l0) * 5 * (size_t)mk.D * mk.D;
-            const size_t sm = tile_smem(c, 3);
-            TILE_DISPATCH(c, (k_ffn_rk_t<4, 4, 64, 16, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                          (k_ffn_rk_t<5, 5, 20, 4, 5><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                          (k_ffn_rk_t<2, 4, 8, 4, 2><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
-        }
-        else DISPATCH_S(S, k_ffn_rk<S_><<<dim3(grid), dim3(NT), smem_frk(S), c->stream>>>(fa));
-    } break;
-    case 4: {
-        FfnVArgs fv = mk.fv(l);
-        if (tile_ok(c, 4)) {
-            FfnVTArgs ta;
-            ta.a = fv; ta.a.ns = tile_units(c, 4);
-            ta.im.CB = mk.D / c->tile_th; ta.im.bimg = c->t_fv + (size_t)(l - c->l0) * 4 * (size_t)mk.D * mk.D;
-            const size_t sm = tile_smem(c, 4);
-            if (mk.fv_next_att(l))
-                TILE_DISPATCH(c, (k_ffnv_t<4, 4, 256, 16, 1, 3><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                              (k_ffnv_t<5, 5, 80, 4, 5, 3><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                              (k_ffnv_t<2, 4, 32, 4, 2, 3><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
-            else
-                TILE_DISPATCH(c, (k_ffnv_t<4, 4, 256, 16, 1, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                              (k_ffnv_t<5, 5, 80, 4, 5, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)),
-                              (k_ffnv_t<2, 4, 32, 4, 2, 1><<<dim3(grid), dim3(NT), sm, c->stream>>>(ta)));
-        }
-        else if (mk.fv_next_att(l)) {
-            DISPATCH_S(S, k_ffnv<S_, 3><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
-        } else {
-            DISPATCH_S(S, k_ffnv<S_, 1><<<dim3(grid), dim3(NT), smem_fv(S), c->stream>>>(fv));
-        }
-    } break;
+    case 1: launch_inst(c, att_inst(c), mk.att(l), 1, l); break;
+    case 2: launch_inst(c, attout_inst(c), mk.attout(l), 2, l); break;
+    case 3: launch_inst(c, frk_inst(c), mk.frk(l), 3, l); break;
+    case 4: launch_inst(c, fv_inst(c, mk.fv_next_att(l)), mk.fv(l), 4, l); break;
     case 5: {
-        HeadArgs ha = mk.head();
-        DISPATCH_S(S, k_head<S_><<<dim3(grid), dim3(NT), smem_head(S), c->stream>>>(ha));
+        const auto k = head_inst(c);
+        k.row<<<dim3(c->grid), dim3(NT), k.smem, c->stream>>>(mk.head());
     } break;
     default:
-        k_argmax_finish<<<dim3(1), dim3(64), 0, c->stream>>>(c->blk_val, c->blk_idx, grid, c->ctl, c->gen, c->gen_cap);
+        k_argmax_finish<<<dim3(1), dim3(64), 0, c->stream>>>(c->blk_val, c->blk_idx, c->grid, c->ctl, c->gen, c->gen_cap);
     }
 }
 
@@ -681,32 +708,16 @@ int alloc_scratch(rwkv_ctx *c, SeqScratch &S)
     return dalloc(c, &S.pk1, 2 * h.pk1);
 }
 
+// the instances this context launches (its configuration is fixed by now) may ask for their dynamic LDS
 int set_smem_limits(rwkv_ctx *c)
 {
-    const int S = c->S;
-    int rc = 0;
-    DISPATCH_S(S, rc = allow_smem(k_att<S_>, smem_att(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_attout<S_, ATTOUT_R>, smem_attout(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffn_rk<S_>, smem_frk(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 3>, smem_fv(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_ffnv<S_, 1>, smem_fv(S))); if (rc) return rc;
-    DISPATCH_S(S, rc = allow_smem(k_head<S_>, smem_head(S))); if (rc) return rc;
-    if (c->tile_th) {
-#define TILE_ALLOW(K16, K45, K42, CLS)                                                                   \
-        do {                                                                                             \
-            if (c->tile_th == 16) rc = allow_smem(K16, tile_smem(c, CLS));                               \
-            else if (c->tile_tpc == 5) rc = allow_smem(K45, tile_smem(c, CLS));                          \
-            else rc = allow_smem(K42, tile_smem(c, CLS));                                                \
-            if (rc) return rc;                                                                           \
-        } while (0)
-        TILE_ALLOW((k_att_t<4, 4, 64, 16, 1>), (k_att_t<5, 5, 20, 4, 5>), (k_att_t<2, 4, 8, 4, 2>), 1);
-        TILE_ALLOW((k_attout_t<4, 4, 64, 16, 1>), (k_attout_t<5, 5, 20, 4, 5>), (k_attout_t<2, 4, 8, 4, 2>), 2);
-        TILE_ALLOW((k_ffn_rk_t<4, 4, 64, 16, 1>), (k_ffn_rk_t<5, 5, 20, 4, 5>), (k_ffn_rk_t<2, 4, 8, 4, 2>), 3);
-        TILE_ALLOW((k_ffnv_t<4, 4, 256, 16, 1, 3>), (k_ffnv_t<5, 5, 80, 4, 5, 3>), (k_ffnv_t<2, 4, 32, 4, 2, 3>), 4);
-        TILE_ALLOW((k_ffnv_t<4, 4, 256, 16, 1, 1>), (k_ffnv_t<5, 5, 80, 4, 5, 1>), (k_ffnv_t<2, 4, 32, 4, 2, 1>), 4);
-#undef TILE_ALLOW
-    }
-    return 0;
+    int rc = allow_smem(att_inst(c));
+    if (!rc) rc = allow_smem(attout_inst(c));
+    if (!rc) rc = allow_smem(frk_inst(c));
+    if (!rc) rc = allow_smem(fv_inst(c, true));
+    if (!rc) rc = allow_smem(fv_inst(c, false));
+    if (!rc) rc = allow_smem(head_inst(c));
+    return rc;
 }
 
 int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_ctx)
@@ -806,100 +817,53 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     auto in_tile = [&](int cls) { return ((c->tile >> (cls - 1)) & 1) != 0; };
     const bool own_t = tcfg.th != 16;                         // the decode kernels' tile image is not the chunk path's
     auto need_b = [&](int cls) { return want_seq || (in_tile(cls) && !own_t); };
-    if (!in_tile(1) && (rc = dalloc(c, &c->w_kvr, nl * 3 * D * D))) return rc;
-    if (!in_tile(2) && (rc = dalloc(c, &c->w_att, nl * D * D))) return rc;
-    if (!in_tile(3) && (rc = dalloc(c, &c->w_frk, nl * 5 * D * D))) return rc;
-    if (!in_tile(4) && (rc = dalloc(c, &c->w_fv, nl * 4 * D * D))) return rc;
-    if (last && (rc = dalloc(c, &c->w_head, V * D))) return rc;
-    if (!rc) rc = dalloc(c, &c->rs_kvr, nl * 3 * D);
-    if (!rc) rc = dalloc(c, &c->rs_att, nl * D);
-    if (!rc) rc = dalloc(c, &c->rs_frk, nl * 5 * D);
-    if (!rc) rc = dalloc(c, &c->rs_fv, nl * D);
-    if (!rc) rc = dalloc(c, &c->rs_head, V);
-    if (rc) return rc;
-    // tile images (+ octant row sums for the chunk path): per = bytes of one layer's image
-    const uint64_t cbD = (D + 15) / 16;
-    const uint64_t per_kvr = 3 * cbD * 16 * D, per_att = cbD * 16 * D, per_frk = 5 * cbD * 16 * D, per_fv = cbD * 16 * 4 * D;
-    if (need_b(1) && (rc = dalloc(c, &c->b_kvr, nl * per_kvr))) return rc;
-    if (need_b(2) && (rc = dalloc(c, &c->b_att, nl * per_att))) return rc;
-    if (need_b(3) && (rc = dalloc(c, &c->b_frk, nl * per_frk))) return rc;
-    if (need_b(4) && (rc = dalloc(c, &c->b_fv, nl * per_fv))) return rc;
-    if (want_seq) {
-        if ((rc = dalloc(c, &c->r8_kvr, nl * SEQ_O * 3 * D))) return rc;
-        if ((rc = dalloc(c, &c->r8_att, nl * SEQ_O * D))) return rc;
-        if ((rc = dalloc(c, &c->r8_frk, nl * SEQ_O * 5 * D))) return rc;
-        if ((rc = dalloc(c, &c->r8_fv, nl * SEQ_O * D))) return rc;
+    WClass *const wc = c->wc, &head = c->wc[4];
+    // (all row forms, then all row sums, images, octant row sums, decode-only images: the order of the allocations is the order of the addresses)
+    for (int k = 0; k < 4; k++)
+        if (!in_tile(k + 1) && (rc = dalloc(c, &wc[k].w, nl * wc[k].row_bytes(D)))) return rc;
+    if (last && (rc = dalloc(c, &head.w, head.row_bytes(D)))) return rc;
+    for (int k = 0; k < 5; k++)
+        if ((rc = dalloc(c, &wc[k].rs, (k < 4 ? nl : 1) * wc[k].sums(D)))) return rc;
+    for (int k = 0; k < 4; k++)
+        if (need_b(k + 1) && (rc = dalloc(c, &wc[k].b, nl * wc[k].img_bytes(D)))) return rc;
+    for (int k = 0; k < 4 && want_seq; k++)
+        if ((rc = dalloc(c, &wc[k].r8, nl * wc[k].sums8(D)))) return rc;
+    for (int k = 0; k < 4; k++) {
+        if (!in_tile(k + 1)) continue;
+        if (!own_t) wc[k].t = wc[k].b;
+        else if ((rc = dalloc(c, &wc[k].t, nl * wc[k].row_bytes(D)))) return rc;
     }
-    if (own_t) {
-        if (in_tile(1) && (rc = dalloc(c, &c->t_kvr, nl * 3 * D * D))) return rc;
-        if (in_tile(2) && (rc = dalloc(c, &c->t_att, nl * D * D))) return rc;
-        if (in_tile(3) && (rc = dalloc(c, &c->t_frk, nl * 5 * D * D))) return rc;
-        if (in_tile(4) && (rc = dalloc(c, &c->t_fv, nl * 4 * D * D))) return rc;
-    } else {
-        if (in_tile(1)) c->t_kvr = c->b_kvr;
-        if (in_tile(2)) c->t_att = c->b_att;
-        if (in_tile(3)) c->t_frk = c->b_frk;
-        if (in_tile(4)) c->t_fv = c->b_fv;
-    }
-    auto rowsum = [&](const uint8_t *w, unsigned *rs, uint64_t rows, uint64_t N) {
-        k_rowsum<<<dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, c->stream>>>(w, rs, (size_t)rows, (int)N);
-    };
-    // one layer's matrix in row form (w_t[N][K]) -> its tile image (and octant row sums)
-    auto image = [&](const uint8_t *w_t, uint8_t *bdst, unsigned *r8dst, uint64_t N, uint64_t K, int Q, uint64_t per, int TH = 16) {
-        k_bimage<<<dim3((unsigned)((per / 16 + 255) / 256)), dim3(256), 0, c->stream>>>(w_t, bdst, (int)N, (int)K, Q, (int)((((N + Q - 1) / Q) + TH - 1) / TH), TH);
-        if (r8dst) k_rowsum8<<<dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream>>>(w_t, r8dst, (int)N, (int)K);
-    };
     // load-time scratch (not part of the context): freed on every way out of this function, behind the stream's work
     struct Scratch {
         hipStream_t st; uint8_t *p = nullptr;
         ~Scratch() { if (p) { (void)hipStreamSynchronize(st); (void)hipFree(p); } }
     } staging_s{c->stream}, rowtmp_s{c->stream};
     if (!src.on_device) HIPCHK(hipMalloc(reinterpret_cast<void **>(&staging_s.p), std::max<uint64_t>(4 * D * D, V * D)));
-    if (c->tile) HIPCHK(hipMalloc(reinterpret_cast<void **>(&rowtmp_s.p), 5 * D * D));
+    if (c->tile) HIPCHK(hipMalloc(reinterpret_cast<void **>(&rowtmp_s.p), wc[2].row_bytes(D)));      // one layer of the largest class
     uint8_t *const staging = staging_s.p, *const rowtmp = rowtmp_s.p;
-    for (uint64_t l = l0; l < l1 && !rc; l++) {
-        const uint64_t lr = l - l0;
-        uint8_t *kvr = in_tile(1) ? rowtmp : c->w_kvr + lr * 3 * D * D;
-        if (!rc) rc = retile(c, src, KM, l, D, D, kvr, 1, 3, 0, staging);
-        if (!rc) rc = retile(c, src, VM, l, D, D, kvr, 1, 3, 1, staging);
-        if (!rc) rc = retile(c, src, RM, l, D, D, kvr, 1, 3, 2, staging);
-        if (!rc) {
-            rowsum(kvr, c->rs_kvr + lr * 3 * D, 3 * D, D);
-            if (need_b(1)) image(kvr, c->b_kvr + lr * per_kvr, want_seq ? c->r8_kvr + lr * SEQ_O * 3 * D : nullptr, 3 * D, D, 3, per_kvr);
-            if (own_t && in_tile(1)) image(kvr, c->t_kvr + lr * 3 * D * D, nullptr, 3 * D, D, 3, 3 * D * D, tcfg.th);
+    // One layer (wl of the stage, l of the model) of one class: its file tensors -> row form at `row` -> row sums, and from the row form
+    // (w_t[N][K]) the image of 16-row tiles with its octant row sums, and the decode-only image of TH-row tiles
+    auto image = [&](const uint8_t *w_t, uint8_t *dst, const WClass &k, int TH) {
+        const uint64_t tiles = k.Q * ((k.rows(D) + TH - 1) / TH);
+        k_bimage<<<dim3((unsigned)((tiles * TH * k.K(D) / 16 + 255) / 256)), dim3(256), 0, c->stream>>>(w_t, dst, (int)k.N(D), (int)k.K(D), k.Q, (int)(tiles / k.Q), TH);
+    };
+    auto build = [&](WClass &k, uint64_t l, uint64_t wl, uint8_t *row, bool with_b, bool with_t) -> int {
+        for (int i = 0; i < k.nsrc; i++) {
+            const WSrc &f = k.src[i];
+            if (const int e = retile(c, src, f.slot, l, f.n * D, f.m ? f.m * D : V, row, f.G, f.RS, f.off, staging)) return e;
         }
-        uint8_t *att = in_tile(2) ? rowtmp : c->w_att + lr * D * D;
-        if (!rc) rc = retile(c, src, ATTOUT, l, D, D, att, 1, 1, 0, staging);
-        if (!rc) {
-            rowsum(att, c->rs_att + lr * D, D, D);
-            if (need_b(2)) image(att, c->b_att + lr * per_att, want_seq ? c->r8_att + lr * SEQ_O * D : nullptr, D, D, 1, per_att);
-            if (own_t && in_tile(2)) image(att, c->t_att + lr * D * D, nullptr, D, D, 1, D * D, tcfg.th);
-        }
-        uint8_t *frk = in_tile(3) ? rowtmp : c->w_frk + lr * 5 * D * D;
-        if (!rc) rc = retile(c, src, FFNK, l, D, 4 * D, frk, 4, 5, 0, staging);
-        if (!rc) rc = retile(c, src, FFNR, l, D, D, frk, 1, 5, 4, staging);
-        if (!rc) {
-            rowsum(frk, c->rs_frk + lr * 5 * D, 5 * D, D);
-            if (need_b(3)) image(frk, c->b_frk + lr * per_frk, want_seq ? c->r8_frk + lr * SEQ_O * 5 * D : nullptr, 5 * D, D, 5, per_frk);
-            if (own_t && in_tile(3)) image(frk, c->t_frk + lr * 5 * D * D, nullptr, 5 * D, D, 5, 5 * D * D, tcfg.th);
-        }
-        uint8_t *fvm = in_tile(4) ? rowtmp : c->w_fv + lr * 4 * D * D;
-        if (!rc) rc = retile(c, src, FFNV, l, 4 * D, D, fvm, 1, 1, 0, staging);
-        if (!rc) {
-            rowsum(fvm, c->rs_fv + lr * D, D, 4 * D);
-            if (need_b(4)) image(fvm, c->b_fv + lr * per_fv, want_seq ? c->r8_fv + lr * SEQ_O * D : nullptr, D, 4 * D, 1, per_fv);
-            if (own_t && in_tile(4)) image(fvm, c->t_fv + lr * 4 * D * D, nullptr, D, 4 * D, 1, 4 * D * D, tcfg.th);
-        }
-    }
-    if (!rc && last) {
-        rc = retile(c, src, HEAD, 0, D, V, c->w_head, 1, 1, 0, staging);
-        if (!rc) rowsum(c->w_head, c->rs_head, V, D);
-        if (!rc && want_seq) {
-            const uint64_t cbV = (V + 15) / 16, per_head = cbV * 16 * D;
-            rc = dalloc(c, &c->b_head, per_head);
-            if (!rc) rc = dalloc(c, &c->r8_head, SEQ_O * V);
-            if (!rc) image(c->w_head, c->b_head, c->r8_head, V, D, 1, per_head);
-        }
+        k_rowsum<<<dim3((unsigned)((k.N(D) + 3) / 4)), dim3(256), 0, c->stream>>>(row, k.rs + wl * k.sums(D), (size_t)k.N(D), (int)k.K(D));
+        if (with_b) image(row, k.b + wl * k.img_bytes(D), k, 16);
+        if (with_b && k.r8) k_rowsum8<<<dim3((unsigned)((k.N(D) + 3) / 4)), dim3(256), 0, c->stream>>>(row, k.r8 + wl * k.sums8(D), (int)k.N(D), (int)k.K(D));
+        if (with_t) image(row, k.t + wl * k.row_bytes(D), k, tcfg.th);
+        return 0;
+    };
+    for (uint64_t l = l0; l < l1 && !rc; l++)
+        for (int k = 0; k < 4 && !rc; k++)
+            rc = build(wc[k], l, l - l0, in_tile(k + 1) ? rowtmp : wc[k].w + (l - l0) * wc[k].row_bytes(D), need_b(k + 1), own_t && in_tile(k + 1));
+    if (!rc && last) {      // the head stays in row form (k_head); its image is the chunk path's alone
+        if (want_seq && !(rc = dalloc(c, &head.b, head.img_bytes(D)))) rc = dalloc(c, &head.r8, head.sums8(D));
+        if (!rc) rc = build(head, 0, 0, head.w, want_seq, false);
     }
     if (rc) return rc;
     HIPCHK(hipStreamSynchronize(c->stream));
@@ -1120,22 +1084,22 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
         else k_seq_site<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
     };
     const int n_wkv = (D + WKV_CH - 1) / WKV_CH;
-    const uint64_t CBd = ((uint64_t)D + 15) / 16;
     resid(0, nullptr);     // LayerNorm statistics of the incoming residual stream (embedding rows, or the previous stage's output)
     for (uint64_t l = la; l < lb; l++) {
         tl_layer = l == (c->l0 + c->l1) / 2;
-        const size_t lo = (size_t)l * D, wl = (size_t)(l - c->l0);   // vectors are indexed by the model's layer, matrices by the stage's
+        const size_t lo = (size_t)l * D;
+        const uint64_t wl = l - c->l0;   // vectors are indexed by the model's layer, matrices by the stage's
         {   // time mix
             const double *mix[3] = {c->mixk + lo, c->mixv + lo, c->mixr + lo};
             const float *r[3] = {c->kr + lo, c->vr + lo, c->rr + lo}, *o[3] = {c->o1 + lo, c->o2 + lo, c->o3 + lo};
             site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo);
-            gemm(0, c->b_kvr + wl * 3 * CBd * 16 * D, c->r8_kvr + wl * SEQ_O * 3 * (size_t)D, c->state[0] + lo);
+            gemm(0, c->wc[0].b_at(wl, D), c->wc[0].r8_at(wl, D), c->state[0] + lo);
             SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, par ? 1 : 0, LD, (int)row0, h.pk3, h.part3};
             if (two) k_seq_wkv<SEQ_TM><<<dim3(n_wkv), dim3(SEQ_TM * WKV_CH), 0, st>>>(wa);
             else k_seq_wkv<SEQ_T><<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
             SeqStageArgs sa{S.y, nullptr, nullptr, c->attr + lo, c->atto + lo, S.img[0], S.qparta, D, n, 0, 0, h.img, h.part1};
             k_seq_stage<0><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sa);
-            gemm(1, c->b_att + wl * CBd * 16 * D, c->r8_att + wl * SEQ_O * (size_t)D, nullptr);
+            gemm(1, c->wc[1].b_at(wl, D), c->wc[1].r8_at(wl, D), nullptr);
             // x = f32(x) + att_out; statistics for ln2.  (Round 3 tried this launch and the site behind it as ONE launch whose (row, octant)
             // workgroups meet on a per-row arrival counter: +3.6 us per fused launch, profiles/r03/prefill_fuse.txt -- the in-launch
             // all-to-all costs more than the kernel boundary it replaces.)
@@ -1145,10 +1109,10 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
             const double *mix[3] = {c->fmixk + lo, c->fmixr + lo, nullptr};
             const float *r[3] = {c->fkr + lo, c->frr + lo, nullptr}, *o[3] = {c->fko + lo, c->fro + lo, nullptr};
             site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo);
-            gemm(2, c->b_frk + wl * 5 * CBd * 16 * D, c->r8_frk + wl * SEQ_O * 5 * (size_t)D, c->state[4] + lo);
+            gemm(2, c->wc[2].b_at(wl, D), c->wc[2].r8_at(wl, D), c->state[4] + lo);
             SeqStageArgs sh{nullptr, S.pk5, S.qpart, c->fvr + 4 * lo, c->fvo + 4 * lo, S.imgh, S.qparth, 4 * D, n, h.pk5, h.part3, h.imgh, h.part1};
             k_seq_stage<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sh);
-            gemm(3, c->b_fv + wl * CBd * 16 * 4 * D, c->r8_fv + wl * SEQ_O * (size_t)D, nullptr);
+            gemm(3, c->wc[3].b_at(wl, D), c->wc[3].r8_at(wl, D), nullptr);
             resid(2, S.qparth);     // x += ffn_v * sigmoid(r); statistics for the next site
         }
     }
@@ -1156,7 +1120,7 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
         const float *r[3] = {c->headr, nullptr, nullptr}, *o[3] = {c->heado, nullptr, nullptr};
         site(1, c->ln + (4 * L + 2) * D, c->ln + (4 * L + 3) * D, nullptr, r, o, nullptr);
         SeqGemmArgs g{};
-        g.bimg = reinterpret_cast<const u32x4 *>(c->b_head); g.rs8 = c->r8_head; g.N = (int)V; g.K = D; g.Q = 1;
+        g.bimg = reinterpret_cast<const u32x4 *>(c->wc[4].b); g.rs8 = c->wc[4].r8; g.N = (int)V; g.K = D; g.Q = 1;
         for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k]);
         g.part = S.qpart; g.out = c->logits + row0 * V; g.T = two ? SEQ_T : n;
         k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), seq_lds_ks().bytes, st>>>(g);
@@ -1315,6 +1279,14 @@ int begin_call(rwkv_ctx *c)
     return 0;
 }
 
+// the token's control block (every launch of the token reads token / slot / out_row from it): staged in pinned memory, copied behind the stream's work
+int set_ctl(rwkv_ctx *c, uint64_t token, unsigned slot, unsigned out_row)
+{
+    c->h_ctl[0].token = token; c->h_ctl[0].slot = slot; c->h_ctl[0].out_row = out_row; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
+    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+
 int run_token(rwkv_ctx *c, bool with_argmax)
 {
     hipGraphExec_t g = with_argmax ? c->g_greedy : c->g_fwd;
@@ -1461,8 +1433,7 @@ int rwkv_stage_forward(rwkv_ctx *c, uint64_t token, uint32_t slot, uint64_t *pic
     if (c->l0 == 0 && token >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
     HIPCHK(hipSetDevice(c->device));
     { const int rcp = begin_call(c); if (rcp) return rcp; }
-    c->h_ctl[0].token = token; c->h_ctl[0].slot = slot; c->h_ctl[0].out_row = slot; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    if (const int rcc = set_ctl(c, token, slot, slot)) return rcc;
     const bool last = c->l1 == c->L;
     int rc = run_token(c, last && pick != nullptr);
     if (rc) return rc;
@@ -1524,8 +1495,7 @@ int rwkv_decode_greedy(rwkv_ctx *c, uint64_t first_token, uint64_t n, uint64_t *
     if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
     HIPCHK(hipSetDevice(c->device));
     { const int rcp = begin_call(c); if (rcp) return rcp; }
-    c->h_ctl[0].token = first_token; c->h_ctl[0].slot = 0; c->h_ctl[0].out_row = 0; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    if (const int rcc = set_ctl(c, first_token, 0, 0)) return rcc;
     for (uint64_t i = 0; i < n; i++) {
         int rc = run_token(c, true);
         if (rc) return rc;
@@ -1592,8 +1562,7 @@ int rwkv_decode_typical(rwkv_ctx *c, uint64_t first_token, uint64_t n, float tem
     if (!(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
     HIPCHK(hipSetDevice(c->device));
     { const int rcp = begin_call(c); if (rcp) return rcp; }
-    c->h_ctl[0].token = first_token; c->h_ctl[0].slot = 0; c->h_ctl[0].out_row = 0; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    if (const int rcc = set_ctl(c, first_token, 0, 0)) return rcc;
     for (uint64_t i = 0; i < n; i++) {
         int rc = run_token(c, false);                                   // the token graph without the argmax node
         if (!rc) rc = launch_typical(c, -1, temp, tau, 0.0, seed, true, flags | RWKV_SAMPLE_BAN0, true);
@@ -1762,8 +1731,7 @@ int rwkv_profile_token(rwkv_ctx *c, uint64_t token, int reps, double *ms, uint64
     std::vector<hipEvent_t> ev(nev);
     for (auto &e : ev) HIPCHK(hipEventCreate(&e));
     for (int k = 0; k < RWKV_N_KCLASS; k++) ms[k] = 0.0;
-    c->h_ctl[0].token = token; c->h_ctl[0].slot = 0; c->h_ctl[0].out_row = 0; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    if (const int rcc = set_ctl(c, token, 0, 0)) return rcc;
     int rc = 0;
     for (int rep = 0; rep < reps && !rc; rep++) {
         rc = enqueue_token(c, true, ev.data());
@@ -1783,8 +1751,8 @@ int rwkv_profile_token(rwkv_ctx *c, uint64_t token, int reps, double *ms, uint64
     }
     for (auto &e : ev) (void)hipEventDestroy(e);
     if (bytes) {
-        bytes[0] = 4 * D; bytes[1] = 3 * D * D; bytes[2] = D * D; bytes[3] = 5 * D * D; bytes[4] = 4 * D * D;
-        bytes[5] = V * D; bytes[6] = 0;
+        bytes[0] = 4 * D; bytes[6] = 0;
+        for (int k = 0; k < 5; k++) bytes[1 + k] = c->wc[k].row_bytes(D);
     }
     if (launches) {
         launches[0] = 1; launches[1] = launches[2] = launches[3] = launches[4] = (uint32_t)(c->l1 - c->l0); launches[5] = 1; launches[6] = 1;
@@ -1802,8 +1770,7 @@ int rwkv_profile_batched(rwkv_ctx *c, uint64_t token, int reps, double *ms, uint
     if (token >= RWKV_VOCAB || reps <= 0) return fail(RWKV_E_ARG, "bad token / reps");
     HIPCHK(hipSetDevice(c->device));
     { const int rcp = begin_call(c); if (rcp) return rcp; }
-    c->h_ctl[0].token = token; c->h_ctl[0].slot = 0; c->h_ctl[0].out_row = 0; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    if (const int rcc = set_ctl(c, token, 0, 0)) return rcc;
     int rc = enqueue_token(c, true, nullptr);   // valid inputs for every class
     if (rc) return rc;
     hipEvent_t a, b;
@@ -1857,8 +1824,7 @@ int rwkv_debug_timeline(rwkv_ctx *c, uint64_t token, unsigned long long *out, ui
     { const int rcp = begin_call(c); if (rcp) return rcp; }
     if (!c->tl) { int rc = dalloc(c, &c->tl, n); if (rc) return rc; }
     HIPCHK(hipMemsetAsync(c->tl, 0, n * 8, c->stream));
-    c->h_ctl[0].token = token; c->h_ctl[0].slot = 0; c->h_ctl[0].out_row = 0; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-    HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+    if (const int rcc = set_ctl(c, token, 0, 0)) return rcc;
     { const char *e = getenv("RWKV_TL_CLASS"); c->tl_cls = e ? atoi(e) : 3; }
     c->tl_on = true;
     int rc;
@@ -1892,8 +1858,7 @@ int rwkv_debug_launch(rwkv_ctx *c, int cls, uint64_t layer, uint64_t token, uint
     HIPCHK(hipSetDevice(c->device));
     { const int rcp = begin_call(c); if (rcp) return rcp; }
     if (cls == 0) {      // the token's control block: every later launch of the token reads slot / out_row from it
-        c->h_ctl[0].token = token; c->h_ctl[0].slot = slot; c->h_ctl[0].out_row = slot; c->h_ctl[0].step = 0; c->h_ctl[0].pad = 0;
-        HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[0], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+        if (const int rcc = set_ctl(c, token, slot, slot)) return rcc;
     }
     launch_class(c, cls, layer);
     HIPCHK(hipGetLastError());

@@ -188,7 +188,7 @@ constexpr int RED_STATS = 0, RED_MAX = 24, RED_OFFS = 48, RED_PART = 72;
 // elements 16c+4q .. 16c+4q+3 (byte e = element 4q+e), i.e. exactly the operand v_dot4_u32_u8
 // needs against dword q of the lane's 16 weight bytes.  A lane's ds_read_b128 of one limb plane is
 // lane-consecutive (conflict-free).  S*768 dwords (3 KiB per step) per vector.
-template <int S> __device__ __forceinline__ constexpr int xvd() { return S * 768; }
+template <int S> __host__ __device__ __forceinline__ constexpr int xvd() { return S * 768; }
 
 // quantise 4 consecutive elements (quad qd = j/4) with 1/scale `inv_s` and store their 3 limb dwords.
 // real == false writes zero limbs: padding must contribute nothing to the integer sums (it is
@@ -573,7 +573,12 @@ __device__ __forceinline__ void site_stage(const double (&xl)[NQ][4], const f32x
 #ifndef RWKV_SPLIT
 #define RWKV_SPLIT 23
 #endif
-constexpr int RED_BC = 96;     // doubles: scalars published by the prologue waves (8 floats) + spin counter
+// The small overlay at double RED_BC of the reduction scratch, as 32-bit words: [0..7] the scalars the prologue waves publish (offsets [0..3],
+// amax [4..7] per vector), [8] the word the prologue waves meet on, [9] the row-group counter (below).  Every reader goes through these three.
+constexpr int RED_BC = 96;
+static_assert(RED_BC * 8 + 10 * 4 <= RED_BYTES, "the overlay lies inside the reduction scratch");
+__device__ __forceinline__ float *red_bc(double *red) { return reinterpret_cast<float *>(red + RED_BC); }
+__device__ __forceinline__ unsigned *red_spin(double *red) { return reinterpret_cast<unsigned *>(red + RED_BC) + 8; }
 
 // Row groups of a workgroup are handed out through an LDS counter (DYN): the waves that ran the
 // prologue start their first group late, the others take more of the remaining groups.  The counter
@@ -641,8 +646,8 @@ __device__ __forceinline__ void site_open(const SiteStatic &st, const SiteDyn &d
     const int lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4, nqd = D >> 2;
     constexpr int NTP = SPLIT ? NT / 2 : NT, NWP = NTP / 64, NQP = (S * 256 + NTP - 1) / NTP;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    unsigned *spin = reinterpret_cast<unsigned *>(bc + 8);
+    float *bc = red_bc(red);
+    unsigned *spin = red_spin(red);
     if (SPLIT && wave >= NWP) {
         __syncthreads();   // order: the prologue waves' requests are in the memory pipe
         group_load<R, S, 0, S>(w, wb, stride, chunks, lane);
@@ -708,8 +713,8 @@ __device__ __forceinline__ void vec_open(const float *vec, const double *partS, 
     const int lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4, nqd = D >> 2;
     constexpr int NTP = SPLIT ? NT / 2 : NT, NWP = NTP / 64, NQP = (S * 256 + NTP - 1) / NTP;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    unsigned *spin = reinterpret_cast<unsigned *>(bc + 8);
+    float *bc = red_bc(red);
+    unsigned *spin = red_spin(red);
     if (SPLIT && wave >= NWP) {
         __syncthreads();   // order
         group_load<R, S, 0, S>(w, wb, stride, chunks, lane);
@@ -768,6 +773,30 @@ __device__ __forceinline__ void vec_open(const float *vec, const double *partS, 
     if (SPLIT) { Sf = bc[0]; amax = bc[4]; }
     tl_stamp(tl, 5);
 }
+
+// The dynamic LDS of a row-form decode kernel as byte offsets, regions in address order with nothing between them, by class (engine.hip's
+// numbering: 1 k_att, 2 k_attout, 3 k_ffn_rk, 4 k_ffnv, 5 k_head): the reduction scratch, the staged vectors (k, v, r | the gated wkv | ffn k,
+// ffn r | the four quarters of the hidden vector | ln_out), and k_head's argmax pair per wave.  The kernel takes its pointers from here,
+// engine.hip the launch's bytes.  (The kernels add the offsets to the LDS array itself, smem + L.xq: through a helper that takes smem as a
+// pointer the same constants compiled to other address arithmetic in 27 of the 30 instances, profiles/decode_host/isa_compare.txt.)
+constexpr size_t CU_LDS_BYTES = 160 * 1024;
+__host__ __device__ constexpr int row_nvec(int cls) { return cls == 1 ? 3 : cls == 3 ? 2 : cls == 4 ? 4 : 1; }
+struct RowLds { size_t red = 0, xq = 0, bval = 0, bidx = 0, bytes = 0; };
+__host__ __device__ constexpr RowLds row_lds_of(int cls, int S)
+{
+    RowLds l;
+    l.xq = l.red + RED_BYTES;
+    l.bval = l.xq + (size_t)row_nvec(cls) * S * xvd<1>() * 4;    // one staged vector = xvd<S>() words: 3 limb planes of S x 1 KiB
+    l.bidx = l.bval + (cls == 5 ? NW * sizeof(float) : 0);
+    l.bytes = l.bidx + (cls == 5 ? NW * sizeof(unsigned) : 0);
+    return l;
+}
+// a kernel instance's description; asserts what the code relies on: u32x4 reads of the staged vectors, and that the widest model fits a CU
+template <int CLS, int S> struct RowGeo {
+    static constexpr RowLds L = row_lds_of(CLS, S);
+    static_assert(L.xq % 16 == 0 && L.bval == L.xq + (size_t)row_nvec(CLS) * xvd<S>() * 4, "the staged vectors: 16-byte pieces, xvd<S>() words each");
+    static_assert(row_lds_of(CLS, 5).bytes <= CU_LDS_BYTES, "LDS layout at S = 5");
+};
 
 // ------------------------------------------------------------------------------------------
 // LDS-DMA primitives (the tile-form loaders, tile.hip.h, and the chunk path's staging, seq.hip.h).
@@ -933,8 +962,9 @@ template <int S>
 __global__ __launch_bounds__(NT) void k_att(AttArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *red = reinterpret_cast<double *>(smem);
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
+    constexpr RowLds L = RowGeo<1, S>::L;
+    double *red = reinterpret_cast<double *>(smem + L.red);
+    unsigned *xq = reinterpret_cast<unsigned *>(smem + L.xq);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
     const int g0 = block_lo(D);
@@ -1027,8 +1057,9 @@ template <int S, int R>
 __global__ __launch_bounds__(NT) void k_attout(AttOutArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *red = reinterpret_cast<double *>(smem);
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
+    constexpr RowLds L = RowGeo<2, S>::L;
+    double *red = reinterpret_cast<double *>(smem + L.red);
+    unsigned *xq = reinterpret_cast<unsigned *>(smem + L.xq);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
     tl_stamp(a.tl, 0);
@@ -1116,8 +1147,9 @@ template <int S>
 __global__ __launch_bounds__(NT) void k_ffn_rk(FfnRKArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *red = reinterpret_cast<double *>(smem);
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
+    constexpr RowLds L = RowGeo<3, S>::L;
+    double *red = reinterpret_cast<double *>(smem + L.red);
+    unsigned *xq = reinterpret_cast<unsigned *>(smem + L.xq);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
     const int g0 = block_lo(D);
@@ -1205,8 +1237,9 @@ template <int S, int NVN>
 __global__ __launch_bounds__(NT) void k_ffnv(FfnVArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    double *red = reinterpret_cast<double *>(smem);
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
+    constexpr RowLds L = RowGeo<4, S>::L;
+    double *red = reinterpret_cast<double *>(smem + L.red);
+    unsigned *xq = reinterpret_cast<unsigned *>(smem + L.xq);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
     tl_stamp(a.tl, 0);
@@ -1280,11 +1313,11 @@ template <int S, int R = RWKV_HEAD_R>
 __global__ __launch_bounds__(NT) void k_head(HeadArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    constexpr int XVD = xvd<S>();
-    double *red = reinterpret_cast<double *>(smem);
-    unsigned *xq = reinterpret_cast<unsigned *>(smem + RED_BYTES);
-    float *bval = reinterpret_cast<float *>(xq + XVD);
-    unsigned *bidx = reinterpret_cast<unsigned *>(bval + NW);
+    constexpr RowLds L = RowGeo<5, S>::L;
+    double *red = reinterpret_cast<double *>(smem + L.red);
+    unsigned *xq = reinterpret_cast<unsigned *>(smem + L.xq);
+    float *bval = reinterpret_cast<float *>(smem + L.bval);
+    unsigned *bidx = reinterpret_cast<unsigned *>(smem + L.bidx);
     const int D = a.D, lane = threadIdx.x & 63, wave = wave_id();
     const int chunks = D >> 4;
     const int V = (int)VOCAB;

@@ -91,8 +91,8 @@ __device__ __forceinline__ void tile_site(const SiteStatic &st, const SiteDyn &d
 {
     constexpr int NTP = NT / 2, NWP = NTP / 64, NQP = (SD * 256 + NTP - 1) / NTP;
     const int nqd = D >> 2;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    unsigned *spin = reinterpret_cast<unsigned *>(bc + 8);
+    float *bc = red_bc(red);
+    unsigned *spin = red_spin(red);
     double tcs[NV];
     float mc[NV];
 #pragma unroll
@@ -273,8 +273,8 @@ __device__ __forceinline__ void tile_vec(const float *vec, const double *partS, 
 {
     constexpr int NTP = NT / 2, NWP = NTP / 64;
     const int lane = threadIdx.x & 63, wave = wave_id(), nqd = n >> 2;
-    float *bc = reinterpret_cast<float *>(red + RED_BC);
-    unsigned *spin = reinterpret_cast<unsigned *>(bc + 8);
+    float *bc = red_bc(red);
+    unsigned *spin = red_spin(red);
     double ps = partS[(int)threadIdx.x < n_part ? threadIdx.x : 0];
     float pm = partM[(int)threadIdx.x < n_part ? threadIdx.x : 0];
     f32x4 vl[NQ];
@@ -659,7 +659,7 @@ template <class G> __device__ __forceinline__ const float *tile_consumer_open(do
 {
     if (wave >= TILE_NWP) tile_pretake<G::S, G::HEAD>(G::NU, ring, ns, tc, wave, lane, wk, fail, wpre);
     wait_count(&tc->staged, TILE_NWP + TILE_NSTASH, fail);
-    return reinterpret_cast<const float *>(red + RED_BC);
+    return red_bc(red);
 }
 
 // ln2 site -> ffn_r GEMV + sigmoid, ffn_k GEMV + relu^2 (rwkv.cu:557-573): 5 row classes (0..3 = ffn_k outputs 4 i + q, 4 = ffn_r output i) x TPC tiles

@@ -593,3 +593,47 @@ def test_each_decode_class_is_resident_in_the_one_layout_it_streams(built, monke
                 assert np.array_equal(x, y), mask
     for mask, b in sizes.items():
         assert abs(b - sizes[0]) < 0.02 * weights, sizes
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D,default_mask", [(2048, 13), (4096, 15)])
+def test_the_load_keeps_the_images_both_paths_need_whatever_the_mask(built, monkeypatch, D, default_mask):
+    """With max_ctx > 1 the chunk path's 16-row tile image of every class is resident beside whatever the decode kernels stream, so the
+    load has three cases per class: row form + image (class in row form), the image alone (tile form at 4096, where the decode kernels
+    stream the chunk path's image), image + a decode-only image of 4-row tiles (tile form at 2048).  Whatever the mask, six greedy
+    forward steps, decode_greedy and a 5-token GPT-mode call give the same bits, and the resident bytes are what the layouts say: at
+    4096 a class in tile form drops its row form -- L D^2 Q bytes, Q = 3, 1, 5, 4 for K/V/R, att_out, ffn k/r, ffn_v -- and nothing
+    else changes; at 2048 a 4-row image replaces a row form of the same size.  (max_ctx is 5, not 2: the smallest context that holds the
+    5-token call; the byte counts asserted do not depend on it.)"""
+    import torch
+    from rwkv_cpp_accelerated_amd import engine
+    if torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the tile forms are laid out for 256 workgroups")
+    L, Q = 2, (3, 1, 5, 4)
+    t = mf.synthetic_tensors(L, D, seed=9 + D)
+    ref, sizes = None, {}
+    for mask in (0, 5, None):
+        if mask is None:
+            monkeypatch.delenv("RWKV_TILE", raising=False)
+        else:
+            monkeypatch.setenv("RWKV_TILE", str(mask))
+        m = engine.RWKV(resident=True); m.loadTensors(L, D, t, maxGPT=5)
+        mask = default_mask if mask is None else mask
+        assert m.decode_form() == mask
+        sizes[mask] = m.resident_bytes()
+        out, tk = [], 11
+        for step in range(6):
+            a = m.forward(tk)[: mf.VOCAB].copy()
+            out.append(a); tk = parity.argmax_ban0(a)
+        out.append(m.decode_greedy(tk, 8))
+        out.append(m.forward([7, 50000, 11, 4242, 3], engine.MODE_GPT)[: 5 * mf.VOCAB].copy())
+        m.close()
+        if ref is None:
+            ref = out
+        else:
+            for x, y in zip(ref, out):
+                assert np.array_equal(x, y), mask
+    for mask, b in sizes.items():
+        print(f"D {D} mask {mask}: resident bytes {b} (row form - this: {sizes[0] - b})")
+        dropped = L * D * D * sum(q for k, q in enumerate(Q) if mask >> k & 1) if D == 4096 else 0
+        assert sizes[0] - b == dropped, sizes
