@@ -89,6 +89,7 @@ def make_case(name: str, D: int, n: int, seed: int) -> Case:
         rows[:, ch] = REST_D * OUTLIER_D * rng.choice([-1.0, 1.0], (n, N_OUT)) * (1.0 + 0.1 * rng.random((n, N_OUT)))
         rest = np.delete(rows, ch, axis=1)
         claims["k_blocks"] = sorted(set(int(c) // 64 for c in ch))
+        claims["channels"] = sorted(int(c) for c in ch)
         claims["outlier_over_rest_rms"] = float((np.abs(rows[:, ch]).min(axis=1) / np.sqrt((rest ** 2).mean(axis=1))).min())
     elif name == "e":
         for v in (xy, dd):
@@ -134,6 +135,32 @@ def check_case(c: Case):
         assert k["bb_decades"] >= 2 * SPAN_F - 1e-9 and k["aa_decades"] >= 2 * SPAN_F - 2 and k["bb_min"] > 0, k
     elif c.name == "g":
         assert 2 <= k["hot_channels"] <= max(2, D // 8) and k["hot_ratio"] == HOT_G, k
+
+
+def check_rows(c: Case, x):
+    """the claims of case c that are made on its ROWS, measured again on x [n][D]: the vectors a kernel was actually handed (read back
+    behind k_first in tests/test_kernels_gpu.py, or the oracle's ln0 output), which are not bit-equal to c.rows"""
+    x = np.asarray(x, np.float64)
+    assert np.isfinite(x).all() and (x.std(axis=1) > 0).all(), c.name
+    if c.name == "c":
+        m = float(np.abs(x.mean(axis=1) / x.std(axis=1)).min())
+        assert m >= 0.5 * OFFSET_C, f"case c: |mean| / std = {m:.3g} on the planted vector"
+    elif c.name == "d":
+        ch = c.claims["channels"]
+        rest = np.delete(x, ch, axis=1)
+        m = float((np.abs(x[:, ch]).min(axis=1) / np.sqrt((rest ** 2).mean(axis=1))).min())
+        assert len(c.claims["k_blocks"]) == 1 and m >= 0.75 * OUTLIER_D, f"case d: outlier / rms of the rest = {m:.3g} on the planted vector"
+
+
+def check_state(c: Case, state):
+    """the claims of case c that are made on its STATE, measured again on the five [D] vectors a context was handed"""
+    xy, aa, bb, pp, dd = (np.asarray(a, np.float64) for a in state)
+    assert all(np.isfinite(a).all() for a in (xy, aa, bb, pp, dd)) and (bb > 0).all(), c.name
+    if c.name == "e":
+        assert min(np.abs(xy).max(), np.abs(dd).max()) >= OUTLIER_E > c.claims["ln_output_cap"], "case e: the pushed xy / dd state lost its outliers"
+    elif c.name == "f":
+        assert np.log10(bb.max() / bb.min()) >= 2 * SPAN_F - 1e-9 and np.log10(np.abs(aa).max() / np.abs(aa).min()) >= 2 * SPAN_F - 2, \
+            "case f: the pushed aa / bb state lost its span"
 
 
 def apply_ln2_mul(t, L, D, layer, mul):
