@@ -115,7 +115,13 @@ int rwkv_decode_greedy(rwkv_ctx *ctx, uint64_t first_token, uint64_t n_tokens, u
  * at tau assigns into a temporary and has no effect (typical.h:50) and nc::power takes an integer exponent
  * (typical.h:52); n = 0 (temp > 1) is the uniform distribution.  RWKV_SAMPLE_RECIPE instead applies the recipe its
  * header comment documents (entropy, |-log p - H| ordering, smallest prefix with cumulative probability >= tau,
- * p^(1/temp)).  RWKV_SAMPLE_BAN0 first sets logit 0 to -99 as storygen does (examples/storygen/storygen.cpp:66). */
+ * p^(1/temp)).  RWKV_SAMPLE_BAN0 first sets logit 0 to -99 as storygen does (examples/storygen/storygen.cpp:66).
+ * GUARANTEED for every temp > 0: the weights are formed relative to the largest one of the kept set, which is therefore never
+ * lost to underflow -- near-greedy temperatures (temp 0.01, n = 100) draw from the kept set like any other, where p^n itself is
+ * below f32 and f64 for every token (the host typical_u() returns 0 there: include/rwkv_sampler.h).  The pick is a kept token;
+ * id 0 comes back only where the reference's arithmetic picks it (with BAN0: when -99 still is the largest logit, or in default
+ * mode at temp > 1, where n = 0 weighs every id alike).  Held draw by draw to a log-space f64 evaluation on planted logits by
+ * tests/test_sampler_cases_gpu.py. */
 #define RWKV_SAMPLE_BAN0 1
 #define RWKV_SAMPLE_RECIPE 2
 int rwkv_sample_typical(rwkv_ctx *ctx, uint64_t row, float temp, float tau, double u, int flags, uint64_t *token);

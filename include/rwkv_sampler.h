@@ -17,6 +17,11 @@
 // So typical(logits, temp, tau) draws from softmax(logits)^n, n = uint8(1/temp).  A drop-in has to give the
 // reference's results, so THAT is the default here (recipe = false); recipe = true (or
 // -DRWKV_TYPICAL_RECIPE=1 for the plain typical() calls) gives what the comment documents.
+// LIMIT of this host restatement: like the reference it forms p^(1/temp) itself, in f64, so for near-greedy temperatures the weights
+// underflow -- all of them once p_max^(1/temp) < 4.9e-324 (p_max < 1e-3 at temp 0.01, say), and then typical_u() returns 0 (`last`)
+// and typical() draws from an all-zero discrete_distribution; short of that, the small weights are lost first.  The device sampler
+// (csrc/sampler.hip.h) forms its weights relative to the largest kept one and has no such limit; tests/sampler_cases.py holds both to a
+// log-space evaluation and compares this header only where the total of its weights is a normal number.
 // Off the hot path; kept because the pybind surface exposes it.
 #ifndef RWKV_SAMPLER_H
 #define RWKV_SAMPLER_H

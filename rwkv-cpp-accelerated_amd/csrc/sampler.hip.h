@@ -29,6 +29,7 @@ constexpr int TS_GT = 256;                 // threads of those
 static_assert(TS_NT * TS_PER >= (int)VOCAB, "sampler tiling must cover the vocabulary");
 constexpr size_t TS_PART_ROW = (size_t)TS_G * 3;           // doubles of `part` per row
 constexpr size_t TS_ROW = (size_t)TS_NT * TS_PER;          // elements of `p` / `key` / `pw` per row
+constexpr double TS_RESCALE = 0x1p-60;     // a total of the relative weights below this: form them again relative to the kept maximum (k_typical)
 
 struct TypicalArgs {
     const float *logits;          // [rows][V]
@@ -50,7 +51,7 @@ struct TypicalArgs {
     double *part;                 // [rows][TS_G][3] per-workgroup (max, sum exp(l - max), sum exp(l - max) (l - max))
     float *p;                     // [rows][TS_NT * TS_PER] probabilities, position (i % TS_PER) * TS_NT + i / TS_PER for token i
     unsigned *key;                // same layout: bit patterns of |-log p - H|
-    float *pw;                    // same layout: p^(1/temp) (typical.h:49-52), zeroed for the tokens that are cut
+    float *pw;                    // same layout: (p / p_max)^expo, the weight of typical.h:49-52 relative to the largest one; k_typical zeroes the tokens that are cut
 };
 
 __device__ __forceinline__ const float *ts_row(const TypicalArgs &a) { return a.logits + (size_t)((a.row >= 0 ? (unsigned)a.row : a.ctl->out_row) + blockIdx.y) * VOCAB; }
@@ -119,10 +120,13 @@ __global__ __launch_bounds__(TS_GT) void k_typical_keys(TypicalArgs a)
     ts_combine(a, M, logZ, H);
     const double it = a.expo;
     for (int i = i0 + threadIdx.x; i < i1; i += TS_GT) {
-        const double nl = (M - (double)ts_logit(a, lg, i)) + logZ;          // -log p_i
+        const double d = (double)ts_logit(a, lg, i) - M;                    // <= 0, and 0 for the largest logit
+        const double nl = logZ - d;                                         // -log p_i
         const size_t pos = ts_off((i % TS_PER) * TS_NT + i / TS_PER);
         a.p[pos] = (float)exp(-nl);
-        a.pw[pos] = it == 1.0 ? (float)exp(-nl) : it == 0.0 ? 1.0f : (float)exp(-nl * it);   // p^expo (p^0 = 1 even for p = 0, as nc::power), here: 64 workgroups share the exponentials
+        // (p_i / p_max)^expo: the weight RELATIVE to the largest one, which is exactly 1 whatever temp is (p^expo itself is below
+        // f32 for every token once p_max^expo is); p^0 = 1 even for p = 0, as nc::power.  Here: 64 workgroups share the exponentials
+        a.pw[pos] = it == 0.0 ? 1.0f : (float)exp(d * it);
         a.key[pos] = __float_as_uint((float)fabs(nl - H));                  // typical.h:32
     }
     if (blockIdx.x == 0)       // padding positions: tokens V .. TS_NT * TS_PER - 1 carry no mass and the largest key
@@ -145,6 +149,34 @@ __device__ __forceinline__ double ts_block_sum(double v, double *red)
     return s;
 }
 
+__device__ __forceinline__ double ts_block_max(double v, double *red)
+{
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int off = 32; off >= 1; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    __syncthreads();              // previous users of `red` are done
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    double m = red[0];
+#pragma unroll
+    for (int i = 1; i < TS_NT / 64; i++) m = fmax(m, red[i]);
+    return m;
+}
+
+// inclusive scan of the per-thread values into scan[TS_NT]: Hillis-Steele in LDS
+__device__ __forceinline__ void ts_block_scan(double v, double *scan)
+{
+    const int t = threadIdx.x;
+    __syncthreads();              // previous readers of `scan` are done
+    scan[t] = v;
+    __syncthreads();
+    for (int off = 1; off < TS_NT; off <<= 1) {
+        const double a = t >= off ? scan[t - off] : 0.0;
+        __syncthreads();
+        scan[t] += a;
+        __syncthreads();
+    }
+}
+
 // (3) threshold by radix select, weights, inverse-CDF draw.  Thread t owns tokens [50 t, 50 t + 50); its k-th
 // token sits at position k * TS_NT + t, so every pass over the (L2-resident) arrays is coalesced.
 __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
@@ -154,7 +186,7 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
     __shared__ double hist[TS_HIST];
     __shared__ int sel_bin;
     __shared__ double sel_before;
-    __shared__ unsigned pick_s;
+    __shared__ unsigned pick_s, last_s;
     const int t = threadIdx.x, i0 = t * TS_PER;
     const unsigned *key = a.key + blockIdx.y * TS_ROW;     // this row's slices
     const float *p = a.p + blockIdx.y * TS_ROW;
@@ -212,7 +244,10 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         __syncthreads();
     }
     const unsigned thr = open_end ? 0x7f800000u : prefix;
-    // weights of the kept set (already raised to 1/temp) and the inverse-CDF draw in token order
+    // weights of the kept set (already raised to expo, relative to the largest of ALL tokens) and the inverse-CDF draw in token order.
+    // GUARANTEED: the kept token of largest weight has a normal f32 weight whatever temp is -- 1 in default mode, and in recipe mode
+    // either the total is at least TS_RESCALE or the weights are formed again below with that token at 1 -- so the pick is a kept
+    // token unless the kept set is empty.
     double wsum = 0.0;
 #pragma unroll 10
     for (int k = 0; k < TS_PER; k++) {
@@ -220,13 +255,24 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         pw[k * TS_NT + t] = w;                       // own positions only
         wsum += (double)w;
     }
-    scan[t] = wsum;
-    __syncthreads();
-    for (int off = 1; off < TS_NT; off <<= 1) {        // inclusive scan of the per-thread totals: Hillis-Steele in LDS
-        const double v = t >= off ? scan[t - off] : 0.0;
-        __syncthreads();
-        scan[t] += v;
-        __syncthreads();
+    ts_block_scan(wsum, scan);
+    if (scan[TS_NT - 1] < TS_RESCALE) {
+        // (block-uniform branch) the kept set lies so far below the largest logit -- which the cut may well drop, being the least
+        // typical token -- that its weights relative to p_max leave f32: form them again relative to the largest KEPT logit, from the
+        // logits.  Never taken in default mode (everything is kept, the largest weight is 1) nor with expo = 0 (every weight is 1).
+        const float *lg = ts_row(a);
+        double mx = -INFINITY;
+        for (int k = 0; k < TS_PER; k++)
+            if (i0 + k < (int)VOCAB && key[k * TS_NT + t] <= thr) mx = fmax(mx, (double)ts_logit(a, lg, i0 + k));
+        mx = ts_block_max(mx, red);
+        wsum = 0.0;
+        for (int k = 0; k < TS_PER; k++) {
+            const bool kept = i0 + k < (int)VOCAB && key[k * TS_NT + t] <= thr;
+            const float w = kept ? (float)exp(((double)ts_logit(a, lg, i0 + k) - mx) * a.expo) : 0.f;
+            pw[k * TS_NT + t] = w;
+            wsum += (double)w;
+        }
+        ts_block_scan(wsum, scan);
     }
     const double total = scan[TS_NT - 1], before = scan[t] - wsum;
     double u = a.u;
@@ -240,7 +286,7 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
     }
     const double target = u * total;
-    if (t == 0) pick_s = 0xffffffffu;
+    if (t == 0) { pick_s = 0xffffffffu; last_s = 0u; }
     __syncthreads();
     // the owner of the target: before <= target < before + wsum
     if (wsum > 0.0 && target >= before && target < before + wsum) {
@@ -255,9 +301,19 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         atomicMin(&pick_s, (unsigned)sel);
     }
     __syncthreads();
+    if (pick_s == 0xffffffffu && total > 0.0) {
+        // (block-uniform branch) no owner although tokens are kept: the ranges [before, before + wsum) of two neighbouring threads can
+        // leave a gap of one rounding of the scan (~1e-16 of the total) and the target fell into one.  The last kept token, which is
+        // what typical_u returns when its running sum ends short of the target.
+        int lastkept = -1;
+        for (int k = 0; k < TS_PER; k++) if (pw[k * TS_NT + t] > 0.f) lastkept = i0 + k;
+        if (lastkept >= 0) atomicMax(&last_s, (unsigned)lastkept);
+        __syncthreads();
+        if (t == 0) pick_s = last_s;
+    }
     if (t == 0) {
         unsigned sel = pick_s;
-        if (sel == 0xffffffffu) {                  // target == total by rounding, or a degenerate distribution
+        if (sel == 0xffffffffu) {                  // the kept set is empty (total == 0 or NaN: logits that are no numbers); an underflow of the weights does not come here
             sel = 0;
         }
         if (a.pick) a.pick[blockIdx.y] = sel;

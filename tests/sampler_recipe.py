@@ -22,12 +22,19 @@ def sampler_weights(logits, temp, tau, recipe):
 
 
 def sampler_u(logits, temp, tau, u, recipe, ban0=False):
-    """inverse CDF in token order for the uniform u: the draw include/rwkv_sampler.h typical_u() and the device sampler make"""
+    """inverse CDF in token order for the uniform u (a sequence of uniforms: the list of their draws, from one evaluation of the weights):
+    the draw include/rwkv_sampler.h typical_u() and the device sampler make.
+    Where the f64 weights all vanish (p_max^(1/temp) below 4.9e-324) the result is typical_u()'s there: 0, its `last`."""
     l = np.array(logits, np.float32, copy=True)
     if ban0:
         l[0] = -99.0
     w = sampler_weights(l, temp, tau, recipe)
-    c = np.cumsum(w)
-    i = int(np.searchsorted(c, u * c[-1], side="right"))
     nz = np.nonzero(w)[0]
-    return int(nz[-1]) if i >= len(w) else int(i if w[i] > 0 else nz[nz > i][0])
+    c = np.cumsum(w)
+
+    def draw(u):
+        if not len(nz):
+            return 0
+        i = int(np.searchsorted(c, u * c[-1], side="right"))
+        return int(nz[-1]) if i >= len(w) else int(i if w[i] > 0 else nz[nz > i][0])
+    return draw(u) if np.isscalar(u) else [draw(x) for x in u]

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from sampler_recipe import sampler_weights, sampler_u
+from sampler_cases import logits_view
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
@@ -90,16 +91,6 @@ def test_decode_typical_equals_host_loop_and_is_reproducible(eng_mod, recipe):
     m.close()
 
 
-def _logits_view(m):
-    """the engine's device logits buffer (row 0) as a torch tensor, to plant a chosen logits vector"""
-    import torch
-    from rwkv_cpp_accelerated_amd import engine
-
-    class _A:
-        __cuda_array_interface__ = dict(shape=(mf.VOCAB,), typestr="<f4", data=(int(engine.lib().rwkv_logits_device(m._h)), False), version=2)
-    return torch.as_tensor(_A(), device="cuda:0")
-
-
 @pytest.mark.parametrize("k,j", [(0, 0), (1, 4), (2, 2), (0, 3)])
 def test_device_sampler_fits_the_reference_histograms(eng_mod, k, j):
     """PIN to the reference's own typical(): the device sampler (default mode), driven with a stratified grid of uniforms on
@@ -110,7 +101,7 @@ def test_device_sampler_fits_the_reference_histograms(eng_mod, k, j):
     m = eng_mod.RWKV(resident=True)
     m.loadTensors(2, 64, mf.synthetic_tensors(2, 64, seed=3))
     m.forward(5)
-    _logits_view(m).copy_(torch.from_numpy(np.ascontiguousarray(gold["logits"][k])).cuda())
+    logits_view(m)[0].copy_(torch.from_numpy(np.ascontiguousarray(gold["logits"][k])).cuda())
     torch.cuda.synchronize()
     M = 6000
     dev = np.zeros(mf.VOCAB)
