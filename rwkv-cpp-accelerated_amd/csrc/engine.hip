@@ -171,6 +171,13 @@ struct SeqHalf {
         : img(a_image_bytes(D) / 4), imgh(a_image_bytes(4 * D) / 4), part3((size_t)3 * SEQ_T * SEQ_O), part1((size_t)SEQ_T * SEQ_O),
           pk3((size_t)SEQ_O * 3 * ((D + 15) / 16) * 512), pk5((size_t)SEQ_O * 5 * ((D + 15) / 16) * 512), pk1((size_t)SEQ_O * ((D + 15) / 16) * 512) {}
 };
+// One GEMM of the chunk path as a context launches it: everything that follows from the width, RWKV_SEQ_B, the GEMM's kind (0 K/V/R, 1 att_out,
+// 2 ffn k/r, 3 ffn_v) and whether the pass has one or two halves -- and not from the pass.  seq_gemm_plan() fills it, load_common keeps the table.
+//   args          the argument block but for what a pass and a layer set (enqueue_chunk's gemm); k_seq_gemm_p takes args.g
+//   fn_p | fn_b   the form and its instance: k_seq_gemm_p or k_seq_gemm_b (the other is null)
+//   smem          the instance's LDS bytes (k_seq_gemm_b: of its longest slice; a launch asks for its own, nkb_max k-blocks)
+//   grid          workgroups
+struct SeqGemmPlan { SeqGemmBArgs args{}; void (*fn_p)(SeqGemmArgs) = nullptr; void (*fn_b)(SeqGemmBArgs) = nullptr; size_t smem = 0; int grid = 0, nkb_max = 0; };
 
 // One weight class: the uint8 matrices one decode kernel streams and one GEMM of the chunk path multiplies with.  N = Q row classes x `rows`
 // outputs (rows = D, or the vocabulary for the head), K = kd D inputs.  What a layer of it occupies follows from those three; which tensors of the
@@ -263,8 +270,10 @@ struct rwkv_ctx {
     int tl_cls = 3;                     // kernel class the timeline instruments (env RWKV_TL_CLASS, 1..4)
     // chunked (prompt prefill) path, seq.hip.h: allocated when max_ctx > 1 on a whole-model context
     bool seq_ok = false;
-    unsigned long long *sq_tokens = nullptr;      // device [SQ_RING][SEQ_T]: token ids of the chunks in flight
-    unsigned long long *h_sq_tokens = nullptr;    // pinned, same shape
+    SeqGemmPlan seq_plan[8];                      // [4 (halves of the pass - 1) + kind]: how this context launches each GEMM (fixed at load)
+    unsigned long long *sq_tokens = nullptr;      // device, [SEQ_TM] per RESIDUAL BUFFER (token_slot): the ids of the pass in sq_x[b], what its k_seq_embed reads
+                                                  // (allocated as [SQ_RING][SEQ_TM], of which slots 0 .. SPLIT_MAX - 1 are used)
+    unsigned long long *h_sq_tokens = nullptr;    // pinned [SQ_RING][SEQ_TM]: the ring of staging slots the ids are uploaded from
     hipEvent_t sq_ev[8] = {};                     // slot r of the ring is free once sq_ev[r] has completed
     uint64_t sq_n = 0;                            // chunks enqueued so far
     // captured passes of the chunk path (GPT mode): one hipGraph per (layer range, residual buffer, rows, logits row of the last part);
@@ -274,13 +283,13 @@ struct rwkv_ctx {
     std::map<SeqGraphKey, hipGraphExec_t> sq_graphs;
     bool seq_graph = true;
     int graphs = 3;                               // env RWKV_GRAPH: bit 0 = a decode token is a hipGraph replay, bit 1 = so is a GPT-mode pass of the chunk path (0: direct launches)
-    double *sq_x[4] = {nullptr, nullptr, nullptr, nullptr};   // residual stream [SEQ_T][D]; two buffers: a pipeline stage receives chunk c + 1 while chunk c is sent on; [2], [3]: more chunks in flight in rwkv_forward's pipeline
+    static constexpr int SPLIT_MAX = 4;                       // stages of the one-GPU pipeline at most, and residual buffers: a chunk in flight per stage
+    double *sq_x[SPLIT_MAX] = {nullptr, nullptr, nullptr, nullptr};   // residual stream [SEQ_TM][D]; two buffers: a pipeline stage receives chunk c + 1 while chunk c is sent on; [2], [3]: more chunks in flight in rwkv_forward's pipeline
     hipEvent_t xs_ev[2] = {nullptr, nullptr};     // rwkv_xseq_copy: "source chunk done" / "copied"
     // long prompts on one GPU: the chunk path as a two-stage software pipeline (layers [l0, mid) on `stream`, [mid, l1) + head on
     // `stream2`, stage 2 on chunk c while stage 1 is on chunk c + 1); the second stage has its own scratch set
-    static constexpr int SPLIT_MAX = 4;
     int n_split = 0;                                          // stages in use (0: not set up)
-    hipStream_t sp_stream[SPLIT_MAX] = {};                    // [0] = stream
+    hipStream_t sp_stream[SPLIT_MAX] = {};                    // [0] = stream (load_common)
     SeqScratch sp_scratch[SPLIT_MAX];                         // [0] = the context's own set (load_common), the others at first use (split_setup)
     hipEvent_t sp_done[SPLIT_MAX][SPLIT_MAX] = {};            // [stage][buffer]: the stage has finished the chunk in that buffer
     hipEvent_t sp_end = nullptr;
@@ -672,15 +681,90 @@ SeqGemmInst<SeqGemmBArgs> seq_gemm_b_for(int kind)
     if (kind == 0) return {k_seq_gemm_b<0, 3, RWKV_SEQ_BDEPTH, 2>, smem, 3};
     return {k_seq_gemm_b<2, 3, RWKV_SEQ_BDEPTH, 2>, smem, 3};
 }
-int seq_smem_limits()
+// How a context of width D with RWKV_SEQ_B = seq_b (-1: the default mask) launches GEMM `kind` in a pass of one or two halves: form, instance, grid
+// and, for k_seq_gemm_b, the split of a slice's workgroups.  Plain host arithmetic over the two tables above: no context, no HIP call, no environment.
+SeqGemmPlan seq_gemm_plan(int D, int seq_b, int kind, bool two)
 {
-    int rc = 0;
-    for (int i = 0; i < 16 && !rc; i++) {      // (an instance that serves two cases is set twice: harmless)
-        const auto p = seq_gemm_p_for(i >> 2, i & 1, i & 2);
-        rc = allow_smem(p.fn, p.smem);
+    const SeqHalf h((size_t)D);
+    const bool big = (D >> 6) > 8 * SEQ_O;       // octants of K = D longer than 8 k-blocks (D > 4096): the NKB = 10 instances
+    // What follows from a GEMM's kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v): row classes, K, the vector each class multiplies (padded with the
+    // last), and where half 1 of the images and records it reads and of the partial values it writes lies
+    struct GemmKind { int Q, K, voq[5]; size_t img_h, part_h, pk_h; };
+    const GemmKind kinds[4] = {
+        {3, D, {0, 1, 2, 2, 2}, h.img, h.part3, h.pk3},
+        {1, D, {0, 0, 0, 0, 0}, h.img, h.part1, h.pk1},
+        {5, D, {0, 0, 0, 0, 1}, h.img, h.part3, h.pk5},
+        {1, 4 * D, {0, 0, 0, 0, 0}, h.imgh, h.part1, h.pk1},
+    };
+    const GemmKind &k = kinds[kind];
+    const int Q = k.Q, N = Q * D, K = k.K;
+    SeqGemmPlan p;
+    SeqGemmArgs &g = p.args.g;
+    g.N = N; g.K = K; g.Q = Q;
+    for (int q = 0; q < 5; q++) g.vec_of_q[q] = k.voq[q];
+    g.img_h = k.img_h / 4; g.part_h = k.part_h; g.pk_h = k.pk_h;      // (images: 16-byte units)
+    const int nch = (N + Q - 1) / Q, ntiles = Q * ((nch + 15) / 16);
+    if (two && (kind == 0 || kind == 2) && ((seq_b >= 0 ? seq_b : (4 | (D >= 4096 ? 1 : 0))) & (1 << kind))) {
+        // k_seq_gemm_b: one vector's image of the slice resident, a wave's tiles in batches of <= 3.  The 32 workgroups of a slice are
+        // shared out to the matrix's VECTOR GROUPS (runs of row classes on the same vector) so that no workgroup straddles one and the
+        // largest tile count of a wave is as small as it gets.  Its conditions: slices of DEPTH .. SEQ_B_NKB_MAX k-blocks (the
+        // resident image; row sums prefetched one batch ahead), at most three batches per wave, at most three groups
+        const auto inst = seq_gemm_b_for(kind);
+        const int KB = K >> 6, nkb_min = KB / SEQ_O, nkb_max = (KB + SEQ_O - 1) / SEQ_O, CBt = (nch + 15) / 16;
+        SeqGemmBArgs b{};
+        int ngrp = 0, gq[4] = {0, 0, 0, 0};
+        for (int q = 0; q < Q && ngrp < 4; q++)
+            if (q == 0 || k.voq[q] != k.voq[q - 1]) gq[ngrp++] = q;
+        bool okb = ngrp <= 3 && nkb_min >= RWKV_SEQ_BDEPTH && nkb_max <= SEQ_B_NKB_MAX;
+        if (okb) {
+            int T[3] = {0, 0, 0}, best[3] = {0, 0, 0};
+            for (int i = 0; i < ngrp; i++) { b.grp_tile[i] = gq[i] * CBt; T[i] = ((i + 1 < ngrp ? gq[i + 1] : Q) - gq[i]) * CBt; }
+            b.grp_tile[ngrp] = ntiles;
+            const int WG = 32;                 // workgroups per slice: 8 slices x 32 = one per CU
+            double best_cost = 1e30;
+            for (int w0 = 1; w0 <= WG; w0++)
+                for (int w1 = (ngrp > 1 ? 1 : 0); w0 + w1 <= WG; w1 += 1) {
+                    const int w2 = ngrp > 2 ? WG - w0 - w1 : 0;
+                    if (ngrp == 1 && (w1 || w0 != WG)) continue;
+                    if (ngrp == 2 && w0 + w1 != WG) continue;
+                    if (ngrp == 3 && w2 < 1) continue;
+                    const int w[3] = {w0, w1, w2};
+                    double cost = 0;
+                    for (int i = 0; i < ngrp; i++) {
+                        const int per_wave = (T[i] + SEQ_NW * w[i] - 1) / (SEQ_NW * w[i]);
+                        const double c2 = per_wave * 1000.0 + (double)T[i] / (SEQ_NW * w[i]);
+                        if (c2 > cost) cost = c2;
+                    }
+                    if (cost < best_cost) { best_cost = cost; for (int i = 0; i < 3; i++) best[i] = w[i]; }
+                    if (ngrp == 1) break;
+                }
+            int rb0 = 0, per_wave_max = 0;
+            for (int i = 0; i < ngrp; i++) {
+                b.grp_rb[i] = rb0; rb0 += best[i];
+                const int pw = (T[i] + SEQ_NW * best[i] - 1) / (SEQ_NW * best[i]);
+                if (pw > per_wave_max) per_wave_max = pw;
+            }
+            b.grp_rb[ngrp] = rb0; b.ngrp = ngrp;
+            okb = per_wave_max <= 3 * inst.ntw && rb0 >= 1;
+            if (okb) {
+                b.g = g; b.g.ntw = per_wave_max;
+                p.args = b; p.fn_b = inst.fn; p.smem = inst.smem; p.grid = SEQ_O * rb0; p.nkb_max = nkb_max;
+                return p;
+            }
+        }
     }
-    for (int kind = 0; kind <= 2 && !rc; kind += 2) rc = allow_smem(seq_gemm_b_for(kind).fn, seq_gemm_b_for(kind).smem);
-    if (!rc) rc = allow_smem(k_seq_gemm_ks, seq_lds_ks().bytes);
+    const auto inst = seq_gemm_p_for(kind, two, big);
+    const int RB = (ntiles + SEQ_NW * inst.ntw - 1) / (SEQ_NW * inst.ntw);
+    g.ntw = (ntiles + SEQ_NW * RB - 1) / (SEQ_NW * RB);
+    p.fn_p = inst.fn; p.smem = inst.smem; p.grid = SEQ_O * RB;
+    return p;
+}
+// the GEMM instances this context launches, and the head's, may ask for their dynamic LDS
+int seq_smem_limits(const rwkv_ctx *c)
+{
+    int rc = allow_smem(k_seq_gemm_ks, seq_lds_ks().bytes);
+    for (const SeqGemmPlan &p : c->seq_plan)
+        if (!rc) rc = p.fn_b ? allow_smem(p.fn_b, p.smem) : allow_smem(p.fn_p, p.smem);
     return rc;
 }
 // one scratch set of the chunk path for the context's width: two halves of everything (SeqHalf), images and records zeroed
@@ -918,12 +1002,14 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
             if ((rc = dalloc(c, &c->sq_x[0], (size_t)SEQ_TM * D))) return rc;
             if ((rc = dalloc(c, &c->sq_x[1], (size_t)SEQ_TM * D))) return rc;
             if ((rc = alloc_scratch(c, c->sp_scratch[0]))) return rc;
+            for (int i = 0; i < 8; i++) c->seq_plan[i] = seq_gemm_plan((int)D, c->seq_b, i & 3, i >> 2);
+            c->sp_stream[0] = c->stream;
             c->seq_ok = true;
         }
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     if ((rc = set_smem_limits(c))) return rc;
-    if (c->seq_ok && (rc = seq_smem_limits())) return rc;
+    if (c->seq_ok && (rc = seq_smem_limits(c))) return rc;
     if (c->graphs & 1) {
         if ((rc = build_graph(c, false, &c->g_fwd))) return rc;
         if ((rc = build_graph(c, true, &c->g_greedy))) return rc;
@@ -932,47 +1018,46 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     return 0;
 }
 
-// One pass (n <= SEQ_TM = 64 rows: one or two halves of <= 32) through the MFMA path (seq.hip.h) for THIS context's layers [l0, l1); logits rows
-// [row0, row0 + n) on the stage that holds the head.
+// One pass (n <= SEQ_TM = 64 rows: one or two halves of <= 32) through the MFMA path (seq.hip.h) for layers [la, lb) of THIS context's [l0, l1);
+// logits rows [row0, row0 + n) where the pass holds the head.
 // par == false: GPT-mode semantics of rwkv.cu:493-593 -- n tokens of one sequence, state slot 0, token
 // shift along the chunk.  par == true: PARRALEL mode (rwkv.cu:236-240) -- n independent sequences, one
 // token each, row t uses state slot row0 + t: the batched decode step, weights read once for all.
-// The residual stream of the chunk lives in sq_x[buf]: the first stage fills it from the embedding table, a later
+// The residual stream of the chunk lives in sq_x[buf]: the pass that holds the embedding fills it from the table, a later
 // pipeline stage finds the previous stage's output there (placed by an RCCL recv or a copy) and every stage leaves its
-// own output in it.  Nothing here waits for the device: token ids go through a ring of pinned slots.
-// part: nullptr = the context's whole layer range on its stream with its own scratch; else layers [la, lb) on part->st with
-// scratch part->S (the two-stage software pipeline of rwkv_forward: the embedding belongs to the part that starts at l0, the
-// head to the part that ends at l1)
-struct ChunkPart { uint64_t la, lb; hipStream_t st; const SeqScratch *S; bool no_upload = false; const unsigned long long *dtok = nullptr; };
-// a pass's token ids: host -> pinned ring slot -> the device slot of the pass's residual buffer (what k_seq_embed reads; the copy is
-// stream-ordered behind the embedding kernel of the pass that used the buffer before)
+// own output in it.  The layers run on `st` with scratch set `S` (the software pipeline of rwkv_forward: a stream and a set per stage).
+// dtok: the pass's n token ids on the device, read where the pass holds the embedding -- token_slot(c, buf) behind upload_chunk_tokens, or wherever
+// they already are (the batched decode's picks of the previous step)
+struct SeqPass {
+    uint64_t la, lb; hipStream_t st; const SeqScratch *S; int buf, n; uint64_t row0; bool par; const unsigned long long *dtok;
+    bool embeds(const rwkv_ctx *c) const { return c->l0 == 0 && la == c->l0; }
+    bool heads(const rwkv_ctx *c) const { return c->l1 == c->L && lb == c->l1; }
+};
+unsigned long long *token_slot(const rwkv_ctx *c, int buf) { return c->sq_tokens + (size_t)buf * SEQ_TM; }
+// a pass's token ids: host -> pinned ring slot -> the device slot of the pass's residual buffer (the copy is stream-ordered behind the
+// embedding kernel of the pass that used the buffer before).  Nothing here waits for the device: the ids go through a ring of pinned slots.
 int upload_chunk_tokens(rwkv_ctx *c, const uint64_t *tokens, int n, int buf, hipStream_t st)
 {
     const int slot = (int)(c->sq_n % SQ_RING);
     if (c->sq_n >= SQ_RING) HIPCHK(hipEventSynchronize(c->sq_ev[slot]));   // the copy that last used this pinned slot is done
-    unsigned long long *h = c->h_sq_tokens + (size_t)slot * SEQ_TM, *d = c->sq_tokens + (size_t)buf * SEQ_TM;
+    unsigned long long *h = c->h_sq_tokens + (size_t)slot * SEQ_TM;
     for (int t = 0; t < n; t++) h[t] = tokens[t];
-    HIPCHK(hipMemcpyAsync(d, h, sizeof(unsigned long long) * n, hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(token_slot(c, buf), h, sizeof(unsigned long long) * n, hipMemcpyHostToDevice, st));
     HIPCHK(hipEventRecord(c->sq_ev[slot], st));
     c->sq_n++;
     return 0;
 }
-int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, bool par, int buf = 0, const ChunkPart *part = nullptr)
+int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 {
-    const int D = (int)c->D;
-    const uint64_t L = c->L, V = RWKV_VOCAB;
-    const uint64_t la = part ? part->la : c->l0, lb = part ? part->lb : c->l1;
-    const bool first = c->l0 == 0 && la == c->l0, last = c->l1 == c->L && lb == c->l1;
-    hipStream_t st = part ? part->st : c->stream;
-    const SeqScratch &S = part ? *part->S : c->sp_scratch[0];
-    double *x = c->sq_x[buf];
-    if (first) {
-        if (buf < 0 || buf >= SQ_RING) return fail(RWKV_E_ARG, "residual buffer %d out of range", buf);
-        // part->dtok: the pass's ids are already on the device (the batched decode's picks of the previous step)
-        const bool dev = part && part->dtok;
-        if (!(part && part->no_upload) && !dev) { const int rcu = upload_chunk_tokens(c, tokens, n, buf, st); if (rcu) return rcu; }
-        const unsigned long long *d = dev ? part->dtok : c->sq_tokens + (size_t)buf * SEQ_TM;
-        SeqEmbedArgs ea{c->embed, c->ln, d, x, D};
+    if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
+    const int D = (int)c->D, n = pass.n;
+    const uint64_t L = c->L, V = RWKV_VOCAB, row0 = pass.row0;
+    const bool par = pass.par;
+    hipStream_t st = pass.st;
+    const SeqScratch &S = *pass.S;
+    double *x = c->sq_x[pass.buf];
+    if (pass.embeds(c)) {
+        SeqEmbedArgs ea{c->embed, c->ln, pass.dtok, x, D};
         k_seq_embed<<<dim3(n), dim3(NT), 0, st>>>(ea);
     }
     const size_t LD = (size_t)L * D;
@@ -981,85 +1066,23 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
     // at these element offsets behind half 0's
     const bool two = n > SEQ_T;
     const SeqHalf h((size_t)D);
-    const bool big = (D >> 6) > 8 * SEQ_O;       // octants of K = D longer than 8 k-blocks (D > 4096): the NKB = 10 instances
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
-    // What follows from a GEMM's kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v): row classes, K, the vector each class multiplies (padded with the
-    // last), the images and records it reads, the partial values it writes, and where half 1 of each lies
-    struct GemmKind { int Q, K, voq[5]; unsigned *img[3]; const SeqPart *part; float *pk; size_t img_h, part_h, pk_h; };
-    const GemmKind kinds[4] = {
-        {3, D, {0, 1, 2, 2, 2}, {S.img[0], S.img[1], S.img[2]}, S.qpart, S.pk3, h.img, h.part3, h.pk3},
-        {1, D, {0, 0, 0, 0, 0}, {S.img[0], S.img[1], S.img[2]}, S.qparta, S.pk1, h.img, h.part1, h.pk1},
-        {5, D, {0, 0, 0, 0, 1}, {S.img[0], S.img[1], S.img[2]}, S.qpart, S.pk5, h.img, h.part3, h.pk5},
-        {1, 4 * D, {0, 0, 0, 0, 0}, {S.imgh, S.imgh, S.imgh}, S.qparth, S.pk1, h.imgh, h.part1, h.pk1},
-    };
-    // tile-per-wave GEMM of layer matrix `bimg` (row sums `rs8`) over the 8 K-slices, partial values into the kind's pk; state_dst: GPT mode commits the
-    // state of the site in front of it behind it
+    // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
+    const SeqPart *const parts[4] = {S.qpart, S.qparta, S.qpart, S.qparth};
+    float *const pks[4] = {S.pk3, S.pk1, S.pk5, S.pk1};
+    // tile-per-wave GEMM of layer matrix `bimg` (row sums `rs8`) over the 8 K-slices, partial values into the kind's pk, launched as the context's
+    // plan says (seq_gemm_plan); state_dst: GPT mode commits the state of the site in front of it behind it
     auto gemm = [&](int kind, const uint8_t *bimg, const unsigned *rs8, double *state_dst) {
-        const GemmKind &k = kinds[kind];
-        const int Q = k.Q, N = Q * D, K = k.K;
-        SeqGemmArgs g{};
-        g.bimg = reinterpret_cast<const u32x4 *>(bimg); g.rs8 = rs8; g.N = N; g.K = K; g.Q = Q;
-        for (int q = 0; q < 5; q++) g.vec_of_q[q] = k.voq[q];
-        for (int v = 0; v < 3; v++) g.img[v] = reinterpret_cast<const u32x4 *>(k.img[v]);
-        g.part = k.part; g.pk = k.pk; g.out = nullptr; g.T = n;
-        g.img_h = k.img_h / 4; g.part_h = k.part_h; g.pk_h = k.pk_h;      // (images: 16-byte units)
+        const SeqGemmPlan &p = c->seq_plan[4 * two + kind];
+        SeqGemmBArgs b = p.args;
+        SeqGemmArgs &g = b.g;
+        g.bimg = reinterpret_cast<const u32x4 *>(bimg); g.rs8 = rs8;
+        for (int v = 0; v < 3; v++) g.img[v] = reinterpret_cast<const u32x4 *>(kind == 3 ? S.imgh : S.img[v]);
+        g.part = parts[kind]; g.pk = pks[kind]; g.out = nullptr; g.T = n;
         g.tl = (c->tl_on && c->tl_cls == 10 + kind && tl_layer) ? c->tl : nullptr;
         g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par) ? D : 0;
-        const int nch = (N + Q - 1) / Q, ntiles = Q * ((nch + 15) / 16);
-        const dim3 blk(SEQ_NT);
-        if (two && (kind == 0 || kind == 2) && ((c->seq_b >= 0 ? c->seq_b : (4 | (D >= 4096 ? 1 : 0))) & (1 << kind))) {
-            // k_seq_gemm_b: one vector's image of the slice resident, a wave's tiles in batches of <= 3.  The 32 workgroups of a slice are
-            // shared out to the matrix's VECTOR GROUPS (runs of row classes on the same vector) so that no workgroup straddles one and the
-            // largest tile count of a wave is as small as it gets.  Its conditions: slices of DEPTH .. SEQ_B_NKB_MAX k-blocks (the
-            // resident image; row sums prefetched one batch ahead), at most three batches per wave, at most three groups
-            const auto inst = seq_gemm_b_for(kind);
-            const int KB = K >> 6, nkb_min = KB / SEQ_O, nkb_max = (KB + SEQ_O - 1) / SEQ_O, CBt = (nch + 15) / 16;
-            SeqGemmBArgs b{};
-            int ngrp = 0, gq[4] = {0, 0, 0, 0};
-            for (int q = 0; q < Q && ngrp < 4; q++)
-                if (q == 0 || k.voq[q] != k.voq[q - 1]) gq[ngrp++] = q;
-            bool okb = ngrp <= 3 && nkb_min >= RWKV_SEQ_BDEPTH && nkb_max <= SEQ_B_NKB_MAX;
-            if (okb) {
-                int T[3] = {0, 0, 0}, best[3] = {0, 0, 0};
-                for (int i = 0; i < ngrp; i++) { b.grp_tile[i] = gq[i] * CBt; T[i] = ((i + 1 < ngrp ? gq[i + 1] : Q) - gq[i]) * CBt; }
-                b.grp_tile[ngrp] = ntiles;
-                const int WG = 32;                 // workgroups per slice: 8 slices x 32 = one per CU
-                double best_cost = 1e30;
-                for (int w0 = 1; w0 <= WG; w0++)
-                    for (int w1 = (ngrp > 1 ? 1 : 0); w0 + w1 <= WG; w1 += 1) {
-                        const int w2 = ngrp > 2 ? WG - w0 - w1 : 0;
-                        if (ngrp == 1 && (w1 || w0 != WG)) continue;
-                        if (ngrp == 2 && w0 + w1 != WG) continue;
-                        if (ngrp == 3 && w2 < 1) continue;
-                        const int w[3] = {w0, w1, w2};
-                        double cost = 0;
-                        for (int i = 0; i < ngrp; i++) {
-                            const int per_wave = (T[i] + SEQ_NW * w[i] - 1) / (SEQ_NW * w[i]);
-                            const double c2 = per_wave * 1000.0 + (double)T[i] / (SEQ_NW * w[i]);
-                            if (c2 > cost) cost = c2;
-                        }
-                        if (cost < best_cost) { best_cost = cost; for (int i = 0; i < 3; i++) best[i] = w[i]; }
-                        if (ngrp == 1) break;
-                    }
-                int rb0 = 0, per_wave_max = 0;
-                for (int i = 0; i < ngrp; i++) {
-                    b.grp_rb[i] = rb0; rb0 += best[i];
-                    const int pw = (T[i] + SEQ_NW * best[i] - 1) / (SEQ_NW * best[i]);
-                    if (pw > per_wave_max) per_wave_max = pw;
-                }
-                b.grp_rb[ngrp] = rb0; b.ngrp = ngrp;
-                okb = per_wave_max <= 3 * inst.ntw && rb0 >= 1;
-                if (okb) {
-                    b.g = g; b.g.ntw = per_wave_max;
-                    inst.fn<<<dim3(SEQ_O * rb0), blk, seq_lds_image(1, 2, 1, nkb_max).bytes, st>>>(b);
-                    return;
-                }
-            }
-        }
-        const auto inst = seq_gemm_p_for(kind, two, big);
-        const int RB = (ntiles + SEQ_NW * inst.ntw - 1) / (SEQ_NW * inst.ntw);
-        g.ntw = (ntiles + SEQ_NW * RB - 1) / (SEQ_NW * RB);
-        inst.fn<<<dim3(SEQ_O * RB), blk, inst.smem, st>>>(g);
+        if (p.fn_b) p.fn_b<<<dim3(p.grid), dim3(SEQ_NT), seq_lds_image(1, 2, 1, p.nkb_max).bytes, st>>>(b);
+        else p.fn_p<<<dim3(p.grid), dim3(SEQ_NT), p.smem, st>>>(g);
     };
     auto resid = [&](int mode, const SeqPart *qpart) {
         SeqResidArgs r{};
@@ -1085,7 +1108,7 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
     };
     const int n_wkv = (D + WKV_CH - 1) / WKV_CH;
     resid(0, nullptr);     // LayerNorm statistics of the incoming residual stream (embedding rows, or the previous stage's output)
-    for (uint64_t l = la; l < lb; l++) {
+    for (uint64_t l = pass.la; l < pass.lb; l++) {
         tl_layer = l == (c->l0 + c->l1) / 2;
         const size_t lo = (size_t)l * D;
         const uint64_t wl = l - c->l0;   // vectors are indexed by the model's layer, matrices by the stage's
@@ -1116,22 +1139,26 @@ int enqueue_chunk(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, boo
             resid(2, S.qparth);     // x += ffn_v * sigmoid(r); statistics for the next site
         }
     }
-    if (last) {   // ln_out and the head
+    if (pass.heads(c)) {   // ln_out and the head
         const float *r[3] = {c->headr, nullptr, nullptr}, *o[3] = {c->heado, nullptr, nullptr};
         site(1, c->ln + (4 * L + 2) * D, c->ln + (4 * L + 3) * D, nullptr, r, o, nullptr);
         SeqGemmArgs g{};
         g.bimg = reinterpret_cast<const u32x4 *>(c->wc[4].b); g.rs8 = c->wc[4].r8; g.N = (int)V; g.K = D; g.Q = 1;
-        for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k]);
-        g.part = S.qpart; g.out = c->logits + row0 * V; g.T = two ? SEQ_T : n;
-        k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), seq_lds_ks().bytes, st>>>(g);
-        if (two) {      // the head once per half (its weights are 3 % of a pass's bytes; 240 accumulator registers would not fit one wave)
-            for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k] + h.img);
-            g.part = S.qpart + h.part3; g.out = c->logits + (row0 + SEQ_T) * V; g.T = n - SEQ_T;
+        for (int hf = 0; hf < (two ? 2 : 1); hf++) {      // the head once per half (its weights are 3 % of a pass's bytes; 240 accumulator registers would not fit one wave)
+            for (int k = 0; k < 3; k++) g.img[k] = reinterpret_cast<const u32x4 *>(S.img[k] + hf * h.img);
+            g.part = S.qpart + hf * h.part3; g.out = c->logits + (row0 + hf * SEQ_T) * V; g.T = hf ? n - SEQ_T : (two ? SEQ_T : n);
             k_seq_gemm_ks<<<dim3(c->grid), dim3(SEQ_NT), seq_lds_ks().bytes, st>>>(g);
         }
     }
     HIPCHK(hipGetLastError());
     return 0;
+}
+// a GPT-mode pass over the context's whole layer range on its own stream with its own scratch, the ids (where it holds the embedding) from the host
+int enqueue_whole(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, int buf)
+{
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], buf, n, row0, false, token_slot(c, buf)};
+    if (pass.embeds(c)) { const int rcu = upload_chunk_tokens(c, tokens, n, buf, c->stream); if (rcu) return rcu; }
+    return enqueue_chunk(c, pass);
 }
 
 // the chunk path's software pipeline on one GPU: streams, events, one more scratch set and residual-stream buffer per extra
@@ -1144,7 +1171,6 @@ int split_setup(rwkv_ctx *c)
     if (want > rwkv_ctx::SPLIT_MAX) want = rwkv_ctx::SPLIT_MAX;
     if ((uint64_t)want > c->L) want = (int)c->L;
     if (want < 2 || !c->seq_ok || c->l0 != 0 || c->l1 != c->L) { c->n_split = 1; return 0; }
-    c->sp_stream[0] = c->stream;
     HIPCHK(hipEventCreateWithFlags(&c->sp_end, hipEventDisableTiming));
     for (int k = 0; k < want; k++) {
         if (k > 0) HIPCHK(hipStreamCreateWithFlags(&c->sp_stream[k], hipStreamNonBlocking));
@@ -1183,24 +1209,21 @@ void trim_pass_graphs(rwkv_ctx *c)
     c->sq_graphs.clear();
 }
 
-// one pass of the chunk path (GPT mode) over layers [part.la, part.lb) on part.st: replay of the captured graph of exactly this pass
-// shape, captured at first use.  The token upload stays outside (host memory changes per pass); everything else a pass launches
-// depends only on the key.  A capture that fails turns the graphs off for the context and the pass is launched directly.
-int enqueue_pass(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, int buf, ChunkPart part)
+// one pass of the chunk path (GPT mode): replay of the captured graph of exactly this pass shape, captured at first use.  The token
+// upload stays outside (the caller's: host memory changes per pass; the pass reads the ids from its buffer's device slot); everything
+// else a pass launches depends only on the key.  A capture that fails turns the graphs off for the context and the pass is launched directly.
+int enqueue_pass(rwkv_ctx *c, const SeqPass &pass)
 {
-    const bool first = c->l0 == 0 && part.la == c->l0, last = c->l1 == c->L && part.lb == c->l1;
-    if (!c->seq_graph || c->tl_on) return enqueue_chunk(c, tokens, n, row0, false, buf, &part);
-    if (first) { const int rcu = upload_chunk_tokens(c, tokens, n, buf, part.st); if (rcu) return rcu; }
-    part.no_upload = true;
-    const rwkv_ctx::SeqGraphKey key{part.la, part.lb, last ? row0 : 0, buf, n};
+    if (!c->seq_graph || c->tl_on) return enqueue_chunk(c, pass);
+    const rwkv_ctx::SeqGraphKey key{pass.la, pass.lb, pass.heads(c) ? pass.row0 : 0, pass.buf, pass.n};
     auto it = c->sq_graphs.find(key);
     if (it == c->sq_graphs.end()) {
         hipGraph_t g = nullptr;
         hipGraphExec_t ge = nullptr;
-        bool ok = hipStreamBeginCapture(part.st, hipStreamCaptureModeRelaxed) == hipSuccess;
+        bool ok = hipStreamBeginCapture(pass.st, hipStreamCaptureModeRelaxed) == hipSuccess;
         if (ok) {
-            const int rc = enqueue_chunk(c, nullptr, n, row0, false, buf, &part);
-            const hipError_t e = hipStreamEndCapture(part.st, &g);
+            const int rc = enqueue_chunk(c, pass);
+            const hipError_t e = hipStreamEndCapture(pass.st, &g);
             ok = rc == 0 && e == hipSuccess && g != nullptr;
         }
         if (ok) ok = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0) == hipSuccess;
@@ -1208,11 +1231,11 @@ int enqueue_pass(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, int 
         if (!ok) {
             (void)hipGetLastError();
             c->seq_graph = false;
-            return enqueue_chunk(c, nullptr, n, row0, false, buf, &part);
+            return enqueue_chunk(c, pass);
         }
         it = c->sq_graphs.emplace(key, ge).first;
     }
-    HIPCHK(hipGraphLaunch(it->second, part.st));
+    HIPCHK(hipGraphLaunch(it->second, pass.st));
     return 0;
 }
 
@@ -1227,47 +1250,37 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
     const uint64_t CH = (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T;
     const uint64_t nchunks = (T + CH - 1) / CH;
     int rc = 0;
-    if (nchunks >= 2 && (rc = split_setup(c)) == 0 && c->n_split >= 2) {
-        // Software pipeline over the chunks: stage k = an equal share of the layers (the last one with the head) on its
-        // own stream with its own scratch, stage k on chunk i while stage k - 1 is on chunk i + 1.  Every launch of this path
-        // costs ~4.5 us of start-up and tail whatever it moves; with independent kernel sequences on the GPU those run under the
-        // other stages' streams (7B, 512-token prompt: 9.1k -> 12k tokens/s with three stages).  A chunk's residual stream stays
-        // in its buffer (sq_x[i % n], updated in place by every stage); results are bit-identical to the one-stream schedule.
-        const int ns = c->n_split;
-        HIPCHK(hipEventRecord(c->sp_end, c->stream));                 // the other stages start behind whatever the context's stream holds
-        for (int k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(c->sp_stream[k], c->sp_end, 0));
-        uint64_t i = 0;
-        for (uint64_t t0 = 0; t0 < T && !rc; t0 += CH, i++) {
-            const int n = (int)(T - t0 < CH ? T - t0 : CH);
-            const int b = (int)(i % (uint64_t)ns);
-            for (int k = 0; k < ns && !rc; k++) {
-                hipStream_t st = c->sp_stream[k];
-                if (k == 0) { if (i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0)); }   // the last stage is done with this buffer (chunk i - ns)
-                else HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                                        // the stage before has handed chunk i over
-                ChunkPart part{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k]};      // (stage 0: the context's own scratch)
-                if (k == 0 && dtok) part.dtok = dtok + t0;
-                const uint64_t *tk = (k == 0 && tokens) ? tokens + t0 : nullptr;
-                if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tk, n, t0, true, b, &part);
-                else rc = enqueue_pass(c, tk, n, t0, b, part);
-                HIPCHK(hipEventRecord(c->sp_done[k][b], st));
-            }
-        }
-        for (int k = 1; k < ns; k++) {                                // the context's stream owns the result again
-            HIPCHK(hipEventRecord(c->sp_end, c->sp_stream[k]));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->sp_end, 0));
-        }
-        return rc;
-    }
-    if (rc) return rc;
-    for (uint64_t t0 = 0; t0 < T; t0 += CH) {
+    // Software pipeline over the chunks: stage k = an equal share of the layers (the last one with the head) on its
+    // own stream with its own scratch, stage k on chunk i while stage k - 1 is on chunk i + 1.  Every launch of this path
+    // costs ~4.5 us of start-up and tail whatever it moves; with independent kernel sequences on the GPU those run under the
+    // other stages' streams (7B, 512-token prompt: 9.1k -> 12k tokens/s with three stages).  A chunk's residual stream stays
+    // in its buffer (sq_x[i % ns], updated in place by every stage); results are bit-identical to the one-stream schedule, which is
+    // this loop with ONE stage -- a single pass, or RWKV_SEQ_STAGES = 1: the whole layer range on the context's stream with its own
+    // scratch, every pass in buffer 0, nothing to hand over and so no event (and no split_setup for a single pass: nothing is allocated).
+    if (nchunks >= 2 && (rc = split_setup(c))) return rc;
+    const int ns = nchunks >= 2 ? c->n_split : 1;
+    if (ns >= 2) HIPCHK(hipEventRecord(c->sp_end, c->stream));        // the other stages start behind whatever the context's stream holds
+    for (int k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(c->sp_stream[k], c->sp_end, 0));
+    uint64_t i = 0;
+    for (uint64_t t0 = 0; t0 < T && !rc; t0 += CH, i++) {
         const int n = (int)(T - t0 < CH ? T - t0 : CH);
-        ChunkPart part{c->l0, c->l1, c->stream, &c->sp_scratch[0]};
-        if (dtok) part.dtok = dtok + t0;
-        if (mode == RWKV_MODE_PARRALEL) rc = enqueue_chunk(c, tokens ? tokens + t0 : nullptr, n, t0, true, 0, &part);
-        else rc = enqueue_pass(c, tokens + t0, n, t0, 0, part);
-        if (rc) return rc;
+        const int b = (int)(i % (uint64_t)ns);
+        for (int k = 0; k < ns && !rc; k++) {
+            hipStream_t st = c->sp_stream[k];
+            if (k > 0) HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                    // the stage before has handed chunk i over
+            else if (ns >= 2 && i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0));   // the last stage is done with this buffer (chunk i - ns)
+            // (stage 0: the context's own stream and scratch)
+            const SeqPass pass{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k], b, n, t0, mode == RWKV_MODE_PARRALEL, dtok ? dtok + t0 : token_slot(c, b)};
+            if (pass.embeds(c) && !dtok) rc = upload_chunk_tokens(c, tokens + t0, n, b, st);
+            if (!rc) rc = pass.par ? enqueue_chunk(c, pass) : enqueue_pass(c, pass);
+            if (ns >= 2) HIPCHK(hipEventRecord(c->sp_done[k][b], st));
+        }
     }
-    return 0;
+    for (int k = 1; k < ns; k++) {                                // the context's stream owns the result again
+        HIPCHK(hipEventRecord(c->sp_end, c->sp_stream[k]));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->sp_end, 0));
+    }
+    return rc;
 }
 
 // Start of every entry point that launches kernels: the device error word belongs to ONE call.  An entry point that left early
@@ -1834,7 +1847,7 @@ int rwkv_debug_timeline(rwkv_ctx *c, uint64_t token, unsigned long long *out, ui
         for (int t = 0; t < SEQ_TM; t++) toks[t] = token;
         int rows = SEQ_T;
         if (c->tl_cls >= 20) { c->tl_cls -= 10; if (c->seq_rows > SEQ_T && c->maxT >= (uint64_t)SEQ_TM) rows = SEQ_TM; }
-        rc = enqueue_chunk(c, toks, rows, 0, false);
+        rc = enqueue_whole(c, toks, rows, 0, 0);
     } else rc = enqueue_token(c, false, nullptr);
     c->tl_on = false;
     if (rc) return rc;
@@ -2412,7 +2425,7 @@ int rwkv_stage_chunk(rwkv_ctx *c, const uint64_t *tokens, uint64_t n, uint64_t r
         for (uint64_t t = 0; t < n; t++) if (tokens[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
     }
     HIPCHK(hipSetDevice(c->device));
-    return enqueue_chunk(c, tokens, (int)n, row0, false, buf);
+    return enqueue_whole(c, tokens, (int)n, row0, buf);
 }
 double *rwkv_xseq_device(rwkv_ctx *c, int buf) { return (c && (buf == 0 || buf == 1)) ? c->sq_x[buf] : nullptr; }
 int rwkv_sync(rwkv_ctx *c)
@@ -2489,7 +2502,7 @@ int rwkv_pipe_prefill(rwkv_ctx *c, const uint64_t *tokens, uint64_t n_tokens)
             const int r2 = p->GroupEnd();
             if (r || r2) { rc = pipe_fail(p, r ? r : r2, "RCCL hop"); break; }
         }
-        if (work) rc = enqueue_chunk(c, rank == 0 ? tokens + ci * CH : nullptr, (int)rows_of(ci), 0, false, (int)(ci & 1));
+        if (work) rc = enqueue_whole(c, rank == 0 ? tokens + ci * CH : nullptr, (int)rows_of(ci), 0, (int)(ci & 1));
     }
     hipError_t e = hipStreamSynchronize(c->stream);
     if (!rc && e != hipSuccess) rc = fail(RWKV_E_DEVICE, "pipeline prefill: %s", hipGetErrorString(e));
