@@ -311,6 +311,33 @@ public:
         rwkv_detail::check(rwkv_state_copy(ctx_, dst, src));
         if (!residentState) { RWKVState sub = state->getSubState(src); state->setSubState(sub, dst); }
     }
+    // scoring on the device (rwkv_mi355x.h "scoring"): log-probability (f64 log-softmax), entropy in nats and argmax per query, without
+    // the 201 KB logits download per position
+    struct Scores { std::vector<double> logprob, entropy; std::vector<unsigned long long> argmax; };
+    // query i = (logits row rows[i] of the last forward, target id targets[i]); logits and state stay as they are
+    Scores scoreRows(const std::vector<unsigned long long> &rows, const std::vector<unsigned long long> &targets)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (rows.size() != targets.size()) throw std::runtime_error("need one target per query");
+        return score_call(rwkv_score_rows, rows, targets);
+    }
+    // feed `tokens` in GPT mode from the current state (any length: pieces of maxContext tokens, as loadContext runs them) and score
+    // targets[t] under the logits that follow tokens[t].  In the host-authoritative mode slot 0 is pushed before and pulled after.
+    Scores score(const std::vector<unsigned long long> &tokens, const std::vector<unsigned long long> &targets)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (tokens.size() != targets.size()) throw std::runtime_error("need one target per token");
+        if (!residentState) rwkv_detail::check(rwkv_set_state(ctx_, state->statexy, state->stateaa, state->statebb, state->statepp, state->statedd, 1));
+        Scores s = score_call(rwkv_score, tokens, targets);
+        if (!residentState) rwkv_detail::check(rwkv_get_output(ctx_, nullptr, state->statexy, state->stateaa, state->statebb, state->statepp, state->statedd, 1));
+        return s;
+    }
+    // a document: doc[0 .. m - 1) fed against doc[1 .. m)
+    Scores score(const std::vector<unsigned long long> &doc)
+    {
+        if (doc.size() < 2) throw std::runtime_error("a document of at least two tokens");
+        return score(std::vector<unsigned long long>(doc.begin(), doc.end() - 1), std::vector<unsigned long long>(doc.begin() + 1, doc.end()));
+    }
     rwkv_ctx *handle() { return ctx_; }
 
     ~RWKV()
@@ -325,6 +352,17 @@ private:
     rwkv_ctx *ctx_ = nullptr;
     int device_ = 0;
     template <typename T> static std::vector<long long> widen(const std::vector<T> &v) { return std::vector<long long>(v.begin(), v.end()); }
+    Scores score_call(int (*fn)(rwkv_ctx *, const uint64_t *, const uint64_t *, uint64_t, double *, double *, uint64_t *),
+                      const std::vector<unsigned long long> &first, const std::vector<unsigned long long> &targets)
+    {
+        const std::vector<uint64_t> a(first.begin(), first.end()), g(targets.begin(), targets.end());
+        std::vector<uint64_t> am(a.size());
+        Scores s;
+        s.logprob.resize(a.size()); s.entropy.resize(a.size());
+        rwkv_detail::check(fn(ctx_, a.data(), g.data(), a.size(), s.logprob.data(), s.entropy.data(), am.data()));
+        s.argmax.assign(am.begin(), am.end());
+        return s;
+    }
     void ensure_ctx()
     {
         if (!ctx_) rwkv_detail::check(rwkv_create(&ctx_, device_));

@@ -159,6 +159,42 @@ int rwkv_decode_batch_typical(rwkv_ctx *ctx, const uint64_t *first_tokens, uint6
  * slots of a batched decode.  RWKV_E_ARG for a slot >= max_ctx, RWKV_E_STATE when not loaded. */
 int rwkv_state_copy(rwkv_ctx *ctx, uint64_t dst_slot, uint64_t src_slot);
 
+/* ---- scoring: how probable is a given token, on the device (no reference counterpart: the reference only generates) ----
+ * What they replace is a download: rwkv_forward, rwkv_get_output of [n][50277] f32 logits (201 KB per position) and a log-softmax on
+ * the host.  A query is (logits row r, target id g).  With l_i the f32 logits of row r widened to f64, M = max_i l_i, d_i = l_i - M
+ * and Z = sum_i exp(d_i):
+ *     logprob = d_g - log Z                                      a target whose logit is -inf gives -inf
+ *     entropy = log Z - (sum_{i: d_i > -inf} exp(d_i) d_i) / Z   in nats; a -inf logit carries no mass and contributes 0
+ *     argmax  = the lowest id with l_i == M                      nothing is banned here: id 0 can win
+ * Every sum, exp and log is f64 (csrc/score.hip.h); held to |d logprob| <= 1e-10 and |d entropy| <= 1e-9 against numpy f64 on planted
+ * rows by tests/test_score_gpu.py.  With NaN or +inf logits the numbers are unspecified; nothing faults.
+ *
+ * rwkv_score_rows scores n queries against the logits rows the LAST forward left, the way rwkv_sample_typical samples from them: query i
+ * reads row rows[i] and target targets[i] (rows need not be consecutive, ascending or distinct); logprob, entropy and argmax are host
+ * arrays [n], entropy and argmax may be NULL.  It changes neither logits nor state.  One upload of rows and targets, one launch
+ * sequence over all queries, one download; synchronous on return.  Works on any context that holds a head (whole model or last stage).
+ *
+ * rwkv_score feeds tokens[0 .. n_tokens) in GPT mode on state slot 0 from the current state; logprob[t] (entropy[t], argmax[t]) is that of
+ * targets[t] under the logits that follow tokens[t].  A document doc[0 .. m) is scored with tokens = doc, targets = doc + 1,
+ * n_tokens = m - 1.  n_tokens may exceed max_ctx: the call runs exactly the forwards a caller's loop over pieces of max_ctx tokens would
+ * (t0 = 0, max_ctx, 2 max_ctx, ...), each through the path rwkv_forward takes for that piece -- the chunk path, token by token at the
+ * widths without one, the decode kernels for a last piece of one token -- so the logits are bit-identical to that loop's.  The score
+ * launches of a piece sit on the context's stream behind the piece and in front of the next one, which overwrites the rows.  Inside the
+ * call there is no host synchronisation and no host <-> device copy but the token-id ring of the chunk path, one upload (targets, and
+ * the control blocks of the tokens that run one by one) and one download of the results.  On return state and logits buffer are what
+ * the last piece left.  Whole-model contexts only.
+ *
+ * Scratch (per-query partial tuples, the device arrays of rows, targets and results) belongs to the context: allocated at the first
+ * call, grown to the largest n seen, counted by rwkv_resident_bytes, freed by rwkv_free.
+ * Status: RWKV_E_ARG for a NULL ctx, rows, tokens, targets or logprob, n == 0 or n > RWKV_MAX_SCORE, a row >= max_ctx, a token or target
+ * >= 50277; RWKV_E_STATE when not loaded, for rwkv_score_rows on a context without a head, for rwkv_score on a pipeline-stage context.
+ * Every check runs before anything is launched: a rejected call leaves state and logits as they were. */
+#define RWKV_MAX_SCORE 65536u
+int rwkv_score_rows(rwkv_ctx *ctx, const uint64_t *rows, const uint64_t *targets, uint64_t n,
+                    double *logprob, double *entropy, uint64_t *argmax);
+int rwkv_score(rwkv_ctx *ctx, const uint64_t *tokens, const uint64_t *targets, uint64_t n_tokens,
+               double *logprob, double *entropy, uint64_t *argmax);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

@@ -8,6 +8,7 @@
 #include "tile.hip.h"
 #include "seq.hip.h"
 #include "sampler.hip.h"
+#include "score.hip.h"
 #include "../../include/rwkv_mi355x.h"
 
 #include <dlfcn.h>
@@ -310,6 +311,11 @@ struct rwkv_ctx {
     Grown bd_val, bd_idx;                         // greedy partials [n][AM_SLICES] (k_argmax_rows)
     Grown bd_part, bd_p, bd_pw, bd_key;           // sampler scratch per row [n][...] (sampler.hip.h)
     std::vector<unsigned long long> bd_host;      // staging of the one upload and the one download
+    // scoring (rwkv_score_rows / rwkv_score, score.hip.h): allocated at the first call, grown to the largest n seen, freed by rwkv_free
+    Grown sc_in;                                  // u64 [2][n]: rows | targets; behind them the control blocks of rwkv_score's token-by-token pieces
+    Grown sc_part;                                // f64 [queries of one launch sequence][SC_G][4] per-workgroup tuples
+    Grown sc_out;                                 // [3][n]: logprob f64 | entropy f64 | argmax u64
+    std::vector<unsigned long long> sc_host;      // staging of the one upload and the one download
     std::vector<void *> allocs;
     size_t alloc_bytes = 0;                       // device bytes behind `allocs` and the Grown buffers (rwkv_resident_bytes)
 };
@@ -1693,6 +1699,116 @@ int rwkv_state_copy(rwkv_ctx *c, uint64_t dst, uint64_t src)
     return device_check(c);
 }
 
+namespace {
+// Scoring.  The call's device arrays: sc_in = rows [N] | targets [N] (| control blocks), sc_out = logprob [N] | entropy [N] | argmax [N].
+int score_grow(rwkv_ctx *c, uint64_t N, uint64_t n_ctl, uint64_t n_part)
+{
+    int rc = bd_grow(c, c->sc_in, sizeof(unsigned long long) * 2 * N + sizeof(Ctl) * n_ctl);
+    if (!rc) rc = bd_grow(c, c->sc_part, sizeof(double) * SC_PART_Q * n_part);
+    if (!rc) rc = bd_grow(c, c->sc_out, sizeof(double) * 3 * N);
+    return rc;
+}
+// the two score launches over queries [q0, q0 + n) of a call of N, their tuples in sc_part from its start on (one launch sequence
+// per SC_MAX_Y queries: gridDim.y)
+int enqueue_score(rwkv_ctx *c, uint64_t N, uint64_t q0, uint64_t n)
+{
+    const unsigned long long *in = static_cast<const unsigned long long *>(c->sc_in.p);
+    double *out = static_cast<double *>(c->sc_out.p), *part = static_cast<double *>(c->sc_part.p);
+    for (uint64_t k = 0; k < n; k += SC_MAX_Y) {
+        const unsigned m = (unsigned)std::min<uint64_t>(n - k, SC_MAX_Y);
+        const uint64_t q = q0 + k;
+        const ScoreArgs a{c->logits, in + q, in + N + q, part + k * SC_PART_Q, out + q, out + N + q, reinterpret_cast<unsigned long long *>(out + 2 * N) + q};
+        k_score_part<<<dim3(SC_G, m), dim3(SC_NT), 0, c->stream>>>(a);
+        k_score_finish<<<dim3(m), dim3(64), 0, c->stream>>>(a);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the one download of a call's results (into the last 3 N words of sc_host, behind what was uploaded from it), the wait for it, and the
+// results into the caller's arrays
+int score_finish(rwkv_ctx *c, uint64_t N, double *logprob, double *entropy, uint64_t *argmax)
+{
+    unsigned long long *h = c->sc_host.data() + (c->sc_host.size() - 3 * N);
+    HIPCHK(hipMemcpyAsync(h, c->sc_out.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (const int rc = device_check(c)) return rc;
+    memcpy(logprob, h, sizeof(double) * N);
+    if (entropy) memcpy(entropy, h + N, sizeof(double) * N);
+    if (argmax) for (uint64_t i = 0; i < N; i++) argmax[i] = h[2 * N + i];
+    return 0;
+}
+} // namespace
+
+int rwkv_score_rows(rwkv_ctx *c, const uint64_t *rows, const uint64_t *targets, uint64_t n, double *logprob, double *entropy, uint64_t *argmax)
+{
+    if (!c || !rows || !targets || !logprob) return fail(RWKV_E_ARG, "NULL argument");
+    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (c->l1 != c->L) return fail(RWKV_E_STATE, "this pipeline stage does not hold the head");
+    if (n == 0 || n > RWKV_MAX_SCORE) return fail(RWKV_E_ARG, "n must be in 1..%u", RWKV_MAX_SCORE);
+    for (uint64_t i = 0; i < n; i++) {
+        if (rows[i] >= c->maxT) return fail(RWKV_E_ARG, "logits row %llu out of range (max context %llu)", (unsigned long long)rows[i], (unsigned long long)c->maxT);
+        if (targets[i] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "target id %llu out of range", (unsigned long long)targets[i]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (const int rc = score_grow(c, n, 0, n)) return rc;
+    c->sc_host.resize(5 * n);                       // the upload | the download
+    for (uint64_t i = 0; i < n; i++) { c->sc_host[i] = rows[i]; c->sc_host[n + i] = targets[i]; }
+    HIPCHK(hipMemcpyAsync(c->sc_in.p, c->sc_host.data(), sizeof(unsigned long long) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    if (const int rc = enqueue_score(c, n, 0, n)) { (void)hipStreamSynchronize(c->stream); return rc; }
+    return score_finish(c, n, logprob, entropy, argmax);
+}
+
+int rwkv_score(rwkv_ctx *c, const uint64_t *tokens, const uint64_t *targets, uint64_t n, double *logprob, double *entropy, uint64_t *argmax)
+{
+    if (!c || !tokens || !targets || !logprob) return fail(RWKV_E_ARG, "NULL argument");
+    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (c->l0 != 0 || c->l1 != c->L) return fail(RWKV_E_STATE, "needs a whole-model context (a pipeline stage has no embedding / head of its own)");
+    if (n == 0 || n > RWKV_MAX_SCORE) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", RWKV_MAX_SCORE);
+    for (uint64_t t = 0; t < n; t++) {
+        if (tokens[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id %llu out of range", (unsigned long long)tokens[t]);
+        if (targets[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "target id %llu out of range", (unsigned long long)targets[t]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    { const int rcp = begin_call(c); if (rcp) return rcp; }
+    trim_pass_graphs(c);
+    // the pieces a caller's loop of rwkv_forward(max_ctx tokens, GPT) would make, each through the path rwkv_forward takes for it: the chunk
+    // path for >= 2 tokens where the context has one, else token by token through the decode kernels
+    const uint64_t P = c->maxT;
+    auto chunked = [&](uint64_t np) { return np >= 2 && c->seq_ok; };
+    uint64_t n_ctl = 0;
+    for (uint64_t t0 = 0; t0 < n; t0 += P) { const uint64_t np = std::min(P, n - t0); if (!chunked(np)) n_ctl += np; }
+    if (const int rc = score_grow(c, n, n_ctl, std::min(P, n))) return rc;
+    // one upload: the logits row of every query (its position in its piece), the targets, and the control block of every token that runs
+    // token by token (rwkv_forward stages those one by one in pinned memory; here they reach c->ctl by device-to-device copies)
+    static_assert(sizeof(Ctl) % sizeof(unsigned long long) == 0, "control blocks sit behind the u64 arrays");
+    constexpr size_t CW = sizeof(Ctl) / sizeof(unsigned long long);
+    const size_t up = 2 * n + CW * n_ctl;
+    c->sc_host.assign(up + 3 * n, 0ull);             // the upload | the download
+    Ctl *h_ctl = reinterpret_cast<Ctl *>(c->sc_host.data() + 2 * n);
+    const Ctl *d_ctl = reinterpret_cast<const Ctl *>(static_cast<unsigned long long *>(c->sc_in.p) + 2 * n);
+    for (uint64_t t0 = 0, k = 0; t0 < n; t0 += P) {
+        const uint64_t np = std::min(P, n - t0);
+        for (uint64_t t = 0; t < np; t++) {
+            c->sc_host[t0 + t] = t; c->sc_host[n + t0 + t] = targets[t0 + t];
+            if (!chunked(np)) { Ctl &h = h_ctl[k++]; h.token = tokens[t0 + t]; h.slot = 0u; h.out_row = (unsigned)t; h.step = 0; h.pad = 0; }
+        }
+    }
+    HIPCHK(hipMemcpyAsync(c->sc_in.p, c->sc_host.data(), sizeof(unsigned long long) * up, hipMemcpyHostToDevice, c->stream));
+    int rc = 0;
+    for (uint64_t t0 = 0, k = 0; t0 < n && !rc; t0 += P) {
+        const uint64_t np = std::min(P, n - t0);
+        if (chunked(np)) rc = enqueue_rows(c, tokens + t0, nullptr, np, RWKV_MODE_GPT);
+        else
+            for (uint64_t t = 0; t < np && !rc; t++) {
+                if (hipMemcpyAsync(c->ctl, d_ctl + k++, sizeof(Ctl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) rc = fail(RWKV_E_DEVICE, "control block copy failed");
+                if (!rc) rc = run_token(c, false);
+            }
+        if (!rc) rc = enqueue_score(c, n, t0, np);      // behind the piece, in front of the next one, which overwrites the rows
+    }
+    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
+    return score_finish(c, n, logprob, entropy, argmax);
+}
+
 void rwkv_free(rwkv_ctx *c)
 {
     if (!c) return;
@@ -1702,7 +1818,7 @@ void rwkv_free(rwkv_ctx *c)
     if (c->g_greedy) { (void)hipGraphExecDestroy(c->g_greedy); c->g_greedy = nullptr; }
     rwkv_pipe_free(c);        // (no graphs left to re-capture)
     for (void *p : c->allocs) (void)hipFree(p);
-    for (rwkv_ctx::Grown *g : {&c->bd_ids, &c->bd_val, &c->bd_idx, &c->bd_part, &c->bd_p, &c->bd_pw, &c->bd_key}) if (g->p) (void)hipFree(g->p);
+    for (rwkv_ctx::Grown *g : {&c->bd_ids, &c->bd_val, &c->bd_idx, &c->bd_part, &c->bd_p, &c->bd_pw, &c->bd_key, &c->sc_in, &c->sc_part, &c->sc_out}) if (g->p) (void)hipFree(g->p);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);

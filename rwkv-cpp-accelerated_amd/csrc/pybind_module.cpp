@@ -83,4 +83,10 @@ PYBIND11_MODULE(rwkv, m)
     m.def("setResident", [](std::uintptr_t h, bool on) { M(h)->residentState = on; }, "keep state on the device (engine extension)");
     m.def("decodeGreedy", [](std::uintptr_t h, int64_t first, int64_t n) { return M(h)->decodeGreedy(first, n); },
           "device-side greedy continuation (engine extension)");
+    m.def("scoreTokens", [](std::uintptr_t h, const std::vector<int64_t> &tokens) {
+        const RWKV::Scores s = M(h)->score(std::vector<unsigned long long>(tokens.begin(), tokens.end()));
+        py::array_t<double> a(s.logprob.size());
+        std::copy(s.logprob.begin(), s.logprob.end(), a.mutable_data());
+        return a;
+    }, "f64 log-probabilities of tokens[1:], each under the logits that follow its predecessor, computed on the device (engine extension)");
 }

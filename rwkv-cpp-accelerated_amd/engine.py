@@ -31,7 +31,9 @@ ABI_SYMBOLS = [
     "rwkv_stage_chunk", "rwkv_xseq_device", "rwkv_xseq_copy", "rwkv_sync", "rwkv_pipe_rccl_path", "rwkv_pipe_unique_id", "rwkv_pipe_init", "rwkv_pipe_decode", "rwkv_pipe_decode_streams", "rwkv_pipe_profile", "rwkv_pipe_hop_stats",
     "rwkv_pipe_prefill", "rwkv_pipe_free", "rwkv_tensor_device", "rwkv_pipe_info", "rwkv_pipe_decode_dual",
     "rwkv_decode_batch_greedy", "rwkv_decode_batch_typical", "rwkv_state_copy",
+    "rwkv_score_rows", "rwkv_score",
 ]
+MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 
 _lib = None
 
@@ -102,6 +104,9 @@ def lib():
     L.rwkv_decode_batch_typical.argtypes = [vp, C.POINTER(u64), u64, u64, C.c_float, C.c_float, C.POINTER(u64), i32, C.POINTER(u64)]
     L.rwkv_decode_batch_typical.restype = i32
     L.rwkv_state_copy.argtypes = [vp, u64, u64]; L.rwkv_state_copy.restype = i32
+    for f in ("rwkv_score_rows", "rwkv_score"):
+        getattr(L, f).argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
+        getattr(L, f).restype = i32
     _lib = L
     return L
 
@@ -400,6 +405,40 @@ class RWKV:
             n = self.num_layers * self.num_embed
             for a in self.state.arrays():
                 a[dst * n:(dst + 1) * n] = a[src * n:(src + 1) * n]
+
+    # -- scoring: log-probability, entropy and argmax per logits row, on the device --------------
+    def _score(self, call, first, targets):
+        a, g = [int(v) for v in first], [int(v) for v in targets]
+        if len(a) != len(g):
+            raise ValueError("need one target per query")
+        n = len(a)
+        lp, ent, am = (C.c_double * max(1, n))(), (C.c_double * max(1, n))(), (C.c_uint64 * max(1, n))()
+        _chk(call(self._h, (C.c_uint64 * max(1, n))(*a), (C.c_uint64 * max(1, n))(*g), n, lp, ent, am))
+        return (np.frombuffer(lp, dtype=np.float64)[:n].copy(), np.frombuffer(ent, dtype=np.float64)[:n].copy(),
+                np.frombuffer(am, dtype=np.uint64)[:n].astype(np.int64))
+
+    def score_rows(self, rows, targets):
+        """(logprob, entropy, argmax) of targets[i] under logits row rows[i] of the LAST forward (rwkv_score_rows): f64 log-softmax,
+        entropy in nats and the lowest id of the largest logit, computed on the device; logits and state stay as they are"""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        return self._score(lib().rwkv_score_rows, rows, targets)
+
+    def score(self, tokens, targets=None):
+        """feed `tokens` in GPT mode on slot 0 from the current state and score targets[t] under the logits that follow tokens[t]
+        (rwkv_score; any length, in pieces of maxContext tokens as a loop of forward() would run them).  targets=None scores a document:
+        tokens[:-1] are fed against tokens[1:].  Returns (logprob, entropy, argmax)."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        toks = [int(t) for t in tokens]
+        if targets is None:
+            toks, targets = toks[:-1], toks[1:]
+        if not self.resident:
+            self.push_state(1)          # host state is authoritative: continue from it ...
+        out = self._score(lib().rwkv_score, toks, targets)
+        if not self.resident:
+            self.pull_state(1)          # ... and leave it where the scored tokens ended
+        return out
 
     def logits(self, n_tokens: int = 1) -> np.ndarray:
         _chk(lib().rwkv_get_output(self._h, _ptr(self.out), None, None, None, None, None, n_tokens))
