@@ -209,6 +209,18 @@ struct WClass {
     const unsigned *r8_at(uint64_t wl, uint64_t D) const { return r8 + wl * sums8(D); }
 };
 
+// The device buffers of batched decode (rwkv_decode_batch_*) and scoring (rwkv_score_rows / rwkv_score, score.hip.h) that belong to the context:
+// allocated at the first call, grown to the largest one seen (grow_buffer), freed by rwkv_free
+enum GrownBuf {
+    BD_IDS,                           // u64 [n seeds][n_steps + 1][n]: row 0 = the first tokens, row k + 1 = the picks of step k
+    BD_VAL, BD_IDX,                   // greedy partials [n][AM_SLICES] (k_argmax_rows)
+    BD_PART, BD_P, BD_PW, BD_KEY,     // sampler scratch per row [n][...] (sampler.hip.h)
+    SC_IN,                            // u64 [2][n]: rows | targets; behind them the control blocks of rwkv_score's token-by-token pieces
+    SC_PART,                          // f64 [queries of one launch sequence][SC_G][4] per-workgroup tuples
+    SC_OUT,                           // [3][n]: logprob f64 | entropy f64 | argmax u64
+    N_GROWN
+};
+
 struct rwkv_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -305,17 +317,9 @@ struct rwkv_ctx {
     // tile-form decode kernels (tile.hip.h): they stream the chunk path's own image (16-row tiles) where a workgroup owns one 16-channel block,
     // else a decode-only image of 4-row tiles (WClass::t)
     int tile_th = 0, tile_s = 0, tile_tpc = 0;     // rows per tile, KiB per ring unit, tiles per row class and workgroup (0: no tile form at this width)
-    // batched decode (rwkv_decode_batch_*): allocated at the first call, grown to the largest one seen, freed by rwkv_free
-    struct Grown { void *p = nullptr; size_t bytes = 0; };
-    Grown bd_ids;                                 // u64 [n seeds][n_steps + 1][n]: row 0 = the first tokens, row k + 1 = the picks of step k
-    Grown bd_val, bd_idx;                         // greedy partials [n][AM_SLICES] (k_argmax_rows)
-    Grown bd_part, bd_p, bd_pw, bd_key;           // sampler scratch per row [n][...] (sampler.hip.h)
-    std::vector<unsigned long long> bd_host;      // staging of the one upload and the one download
-    // scoring (rwkv_score_rows / rwkv_score, score.hip.h): allocated at the first call, grown to the largest n seen, freed by rwkv_free
-    Grown sc_in;                                  // u64 [2][n]: rows | targets; behind them the control blocks of rwkv_score's token-by-token pieces
-    Grown sc_part;                                // f64 [queries of one launch sequence][SC_G][4] per-workgroup tuples
-    Grown sc_out;                                 // [3][n]: logprob f64 | entropy f64 | argmax u64
-    std::vector<unsigned long long> sc_host;      // staging of the one upload and the one download
+    struct Grown { void *p = nullptr; size_t bytes = 0; } grown[N_GROWN];      // (enum GrownBuf)
+    template <class T> T *buf(GrownBuf which) const { return static_cast<T *>(grown[which].p); }
+    std::vector<unsigned long long> bd_host, sc_host;   // staging of a call's one upload and one download
     std::vector<void *> allocs;
     size_t alloc_bytes = 0;                       // device bytes behind `allocs` and the Grown buffers (rwkv_resident_bytes)
 };
@@ -571,13 +575,25 @@ void launch_class(rwkv_ctx *c, int cls, uint64_t l)
 
 // after a synchronisation: did a bounded wait inside a kernel give up?  (a tile-form LDS hand-off that never arrived: the GPU is
 // shared or preempted, or a workgroup died.)  The token's results are not to be trusted: fail loudly instead of returning them.
-int device_check(rwkv_ctx *c)
+// rc: the call has failed already -- the word is consumed all the same, the call's own status and message stay.
+int device_check(rwkv_ctx *c, int rc = 0)
 {
-    if (!c->herr || *c->herr == 0u) return 0;
+    if (!c->herr || *c->herr == 0u) return rc;
     const unsigned code = *c->herr;
     *c->herr = 0u;
+    if (rc) return rc;
     return fail(RWKV_E_DEVICE, "a device-side wait gave up (code %u: an LDS hand-off timed out; is the GPU shared or preempted?) -- "
                                "the results of this call are invalid; RWKV_TILE=0 selects kernels without bounded waits", code);
+}
+
+// The exit of every synchronous entry point, with the status of what it enqueued (its downloads last): the context's stream is drained also
+// when the call has failed -- what it did enqueue reads the pinned control blocks and the caller's arrays -- and the error word is consumed.
+// The call's answer is the first failure: its own, the synchronisation's, the error word's.
+int finish(rwkv_ctx *c, int rc)
+{
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (!rc && e != hipSuccess) rc = fail(RWKV_E_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    return device_check(c, rc);
 }
 
 // enqueue the kernels of one token on the context's stream.  ev: optional array of
@@ -1289,12 +1305,34 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
     return rc;
 }
 
-// Start of every entry point that launches kernels: the device error word belongs to ONE call.  An entry point that left early
-// (a failed HIP call) never consumed it, and a code raised then would surface -- attributed to the wrong operation -- from whatever
-// synchronises next; so it is cleared here.
-int begin_call(rwkv_ctx *c)
+// The start of every entry point, in this order: the context and the call's pointer arguments (`ptrs`) are there; the context is in the state
+// the call needs; its device is current; and, for a call that launches kernels, the device error word is clear.  The word belongs to ONE call:
+// an entry point that left early (a failed HIP call) never consumed it, and a code raised then would surface -- attributed to the wrong
+// operation -- from whatever synchronises next.  The call's own argument checks follow behind.
+enum : unsigned {
+    NEED_LOADED = 1,
+    NEED_WHOLE = 2,     // loaded with every layer, so with the embedding and the head too
+    NEED_HEAD = 4,      // loaded as the last stage of a pipeline, or as a whole model
+    NEED_SEQ = 8,       // loaded with the chunk path
+    LAUNCHES = 16,
+};
+int guard(rwkv_ctx *c, unsigned need, bool ptrs = true)
 {
-    if (c->herr) *c->herr = 0u;
+    if (!c || !ptrs) return fail(RWKV_E_ARG, "NULL argument");
+    if ((need & ~LAUNCHES) && !c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");                                   // rwkv.h:342-345
+    if ((need & NEED_WHOLE) && (c->l0 != 0 || c->l1 != c->L)) return fail(RWKV_E_STATE, "needs a whole-model context (a pipeline stage has no embedding / head of its own)");
+    if ((need & NEED_HEAD) && c->l1 != c->L) return fail(RWKV_E_STATE, "this pipeline stage does not hold the head");
+    if ((need & NEED_SEQ) && !c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx > 1; off with RWKV_SEQ=0 or n_embed not a multiple of 64)");
+    HIPCHK(hipSetDevice(c->device));
+    if ((need & LAUNCHES) && c->herr) *c->herr = 0u;
+    return 0;
+}
+
+// every id of the array is one of the vocabulary's (`what`: "token" or "target")
+int check_ids(const uint64_t *ids, uint64_t n, const char *what)
+{
+    for (uint64_t i = 0; i < n; i++)
+        if (ids[i] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "%s id %llu out of range", what, (unsigned long long)ids[i]);
     return 0;
 }
 
@@ -1374,7 +1412,7 @@ int rwkv_create(rwkv_ctx **out, int device)
 
 int rwkv_set_layer_range(rwkv_ctx *c, uint64_t l0, uint64_t l1)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
+    if (const int rc = guard(c, 0)) return rc;
     if (c->loaded) return fail(RWKV_E_STATE, "RWKV already loaded");
     if (l0 >= l1) return fail(RWKV_E_ARG, "empty layer range");
     c->l0 = l0; c->l1 = l1;
@@ -1383,7 +1421,7 @@ int rwkv_set_layer_range(rwkv_ctx *c, uint64_t l0, uint64_t l1)
 
 int rwkv_load_file(rwkv_ctx *c, const char *path, uint64_t max_ctx)
 {
-    if (!c || !path) return fail(RWKV_E_ARG, "NULL argument");
+    if (const int rc = guard(c, 0, path)) return rc;
     Source src;
     src.f = fopen(path, "rb");
     if (!src.f) return fail(RWKV_E_IO, "Error opening file %s", path);   // reference: rwkv.cu:641-645
@@ -1403,7 +1441,7 @@ int rwkv_load_file(rwkv_ctx *c, const char *path, uint64_t max_ctx)
 int rwkv_load_tensors(rwkv_ctx *c, uint64_t n_layers, uint64_t n_embed, const void *const *ptrs,
                       int on_device, uint64_t max_ctx)
 {
-    if (!c || !ptrs) return fail(RWKV_E_ARG, "NULL argument");
+    if (const int rc = guard(c, 0, ptrs)) return rc;
     Source src;
     src.ptrs = ptrs;
     src.on_device = on_device != 0;
@@ -1416,49 +1454,38 @@ uint64_t rwkv_max_ctx(const rwkv_ctx *c) { return c ? c->maxT : 0; }
 
 int rwkv_forward(rwkv_ctx *c, const uint64_t *tokens, uint64_t T, int mode)
 {
-    if (!c || !tokens) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");                                   // rwkv.h:342-345
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, tokens)) return rc;
     if (T > c->maxT) return fail(RWKV_E_ARG, "Context too large, max context is %llu", (unsigned long long)c->maxT);   // rwkv.h:347-350
     if (mode != RWKV_MODE_PARRALEL && mode != RWKV_MODE_GPT) return fail(RWKV_E_ARG, "bad mode %d", mode);
-    for (uint64_t t = 0; t < T; t++)
-        if (tokens[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id %llu out of range", (unsigned long long)tokens[t]);
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
+    if (const int rc = check_ids(tokens, T, "token")) return rc;
     trim_pass_graphs(c);
-    if (T >= 2 && c->seq_ok && c->l0 == 0 && c->l1 == c->L) {   // prompt chunks (GPT) / batched decode step of T streams (PARRALEL): weights read once per <= 64 rows
-        const int rc = enqueue_rows(c, tokens, nullptr, T, mode);
-        if (rc) return rc;
-        HIPCHK(hipStreamSynchronize(c->stream));
+    if (T >= 2 && c->seq_ok && c->l0 == 0 && c->l1 == c->L)   // prompt chunks (GPT) / batched decode step of T streams (PARRALEL): weights read once per <= 64 rows
+        return finish(c, enqueue_rows(c, tokens, nullptr, T, mode));
+    return finish(c, [&]() -> int {
+        for (uint64_t t = 0; t < T; t++) {
+            c->h_ctl[t].token = tokens[t];
+            c->h_ctl[t].slot = (mode == RWKV_MODE_PARRALEL) ? (unsigned)t : 0u;   // rwkv.cu:236-240
+            c->h_ctl[t].out_row = (unsigned)t;
+            c->h_ctl[t].step = 0; c->h_ctl[t].pad = 0;
+            HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[t], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
+            if (const int rc = run_token(c, false)) return rc;
+        }
         return 0;
-    }
-    for (uint64_t t = 0; t < T; t++) {
-        c->h_ctl[t].token = tokens[t];
-        c->h_ctl[t].slot = (mode == RWKV_MODE_PARRALEL) ? (unsigned)t : 0u;   // rwkv.cu:236-240
-        c->h_ctl[t].out_row = (unsigned)t;
-        c->h_ctl[t].step = 0; c->h_ctl[t].pad = 0;
-        HIPCHK(hipMemcpyAsync(c->ctl, &c->h_ctl[t], sizeof(Ctl), hipMemcpyHostToDevice, c->stream));
-        int rc = run_token(c, false);
-        if (rc) return rc;
-    }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    }());
 }
 
 int rwkv_stage_forward(rwkv_ctx *c, uint64_t token, uint32_t slot, uint64_t *pick)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES)) return rc;
     if (slot >= c->maxT) return fail(RWKV_E_ARG, "state slot %u out of range (max context %llu)", slot, (unsigned long long)c->maxT);
-    if (c->l0 == 0 && token >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    if (const int rcc = set_ctl(c, token, slot, slot)) return rcc;
+    if (const int rc = check_ids(&token, c->l0 == 0, "token")) return rc;      // (a later stage takes the residual vector, not the id)
     const bool last = c->l1 == c->L;
-    int rc = run_token(c, last && pick != nullptr);
-    if (rc) return rc;
-    if (last && pick) HIPCHK(hipMemcpyAsync(pick, c->gen, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    return finish(c, [&]() -> int {
+        if (const int rc = set_ctl(c, token, slot, slot)) return rc;
+        if (const int rc = run_token(c, last && pick != nullptr)) return rc;
+        if (last && pick) HIPCHK(hipMemcpyAsync(pick, c->gen, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
 }
 
 double *rwkv_x_device(rwkv_ctx *c) { return c ? c->x : nullptr; }
@@ -1466,65 +1493,40 @@ double *rwkv_x_device(rwkv_ctx *c) { return c ? c->x : nullptr; }
 int rwkv_set_state(rwkv_ctx *c, const double *xy, const double *aa, const double *bb, const double *pp,
                    const double *dd, uint64_t n_slots)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED)) return rc;
     if (n_slots > c->maxT) return fail(RWKV_E_ARG, "n_slots %llu > max context %llu", (unsigned long long)n_slots, (unsigned long long)c->maxT);
     const double *h[5] = {xy, aa, bb, pp, dd};
     const size_t bytes = n_slots * c->L * c->D * sizeof(double);
-    HIPCHK(hipSetDevice(c->device));
-    for (int s = 0; s < 5; s++)
-        if (h[s]) HIPCHK(hipMemcpyAsync(c->state[s], h[s], bytes, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    return finish(c, [&]() -> int {
+        for (int s = 0; s < 5; s++)
+            if (h[s]) HIPCHK(hipMemcpyAsync(c->state[s], h[s], bytes, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }());
 }
 
 int rwkv_get_output(rwkv_ctx *c, float *logits, double *xy, double *aa, double *bb, double *pp, double *dd,
                     uint64_t T)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED)) return rc;
     if (T > c->maxT) return fail(RWKV_E_ARG, "n_tokens %llu > max context %llu", (unsigned long long)T, (unsigned long long)c->maxT);
     double *h[5] = {xy, aa, bb, pp, dd};
-    HIPCHK(hipSetDevice(c->device));
-    if (logits) HIPCHK(hipMemcpyAsync(logits, c->logits, T * RWKV_VOCAB * sizeof(float), hipMemcpyDeviceToHost, c->stream));
     const size_t bytes = T * c->L * c->D * sizeof(double);
-    for (int s = 0; s < 5; s++)
-        if (h[s]) HIPCHK(hipMemcpyAsync(h[s], c->state[s], bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
-}
-
-int rwkv_reset_state(rwkv_ctx *c)
-{
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    HIPCHK(hipSetDevice(c->device));
-    for (int s = 0; s < 5; s++)
-        HIPCHK(hipMemsetAsync(c->state[s], 0, c->maxT * c->L * c->D * sizeof(double), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
-}
-
-int rwkv_decode_greedy(rwkv_ctx *c, uint64_t first_token, uint64_t n, uint64_t *out_tokens)
-{
-    if (!c || !out_tokens) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (c->l0 != 0 || c->l1 != c->L) return fail(RWKV_E_STATE, "needs a whole-model context (a pipeline stage has no embedding / head of its own)");
-    if (first_token >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
-    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    if (const int rcc = set_ctl(c, first_token, 0, 0)) return rcc;
-    for (uint64_t i = 0; i < n; i++) {
-        int rc = run_token(c, true);
-        if (rc) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    return finish(c, [&]() -> int {
+        if (logits) HIPCHK(hipMemcpyAsync(logits, c->logits, T * RWKV_VOCAB * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+        for (int s = 0; s < 5; s++)
+            if (h[s]) HIPCHK(hipMemcpyAsync(h[s], c->state[s], bytes, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
 }
 
 namespace {
+int enqueue_reset(rwkv_ctx *c)
+{
+    for (int s = 0; s < 5; s++)
+        HIPCHK(hipMemsetAsync(c->state[s], 0, c->maxT * c->L * c->D * sizeof(double), c->stream));
+    return 0;
+}
+
 // the sampler's arguments common to every launch: mode and exponent from temp / flags, the context's single-row scratch
 TypicalArgs typical_args(rwkv_ctx *c, float temp, float tau, int flags)
 {
@@ -1548,54 +1550,65 @@ int enqueue_typical(rwkv_ctx *c, const TypicalArgs &a, unsigned rows)
     HIPCHK(hipGetLastError());
     return 0;
 }
-int launch_typical(rwkv_ctx *c, int row, float temp, float tau, double u, uint64_t seed, bool use_seed, int flags, bool feedback)
+// The device decode loop: n tokens on slot 0, `first` and then each token's pick, and the download of the n picks.  The pick is the argmax
+// node of the token graph, or (`typical`) the sampler's three launches behind the token graph without that node: u of step k from seed + k,
+// logit 0 banned, the id fed back through the control block.
+int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, bool typical, float temp, float tau, uint64_t seed, int flags, uint64_t *out_tokens)
 {
-    TypicalArgs a = typical_args(c, temp, tau, flags);
-    a.row = row; a.u = u; a.seed = seed; a.use_seed = use_seed ? 1 : 0; a.feedback = feedback ? 1 : 0;
-    return enqueue_typical(c, a, 1);
+    TypicalArgs a = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
+    a.row = -1; a.seed = seed; a.use_seed = 1; a.feedback = 1;
+    if (const int rc = set_ctl(c, first, 0, 0)) return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        if (const int rc = run_token(c, !typical)) return rc;
+        if (const int rc = typical ? enqueue_typical(c, a, 1) : 0) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    return 0;
 }
 } // namespace
 
+int rwkv_reset_state(rwkv_ctx *c)
+{
+    if (const int rc = guard(c, NEED_LOADED)) return rc;
+    return finish(c, enqueue_reset(c));
+}
+
+int rwkv_decode_greedy(rwkv_ctx *c, uint64_t first_token, uint64_t n, uint64_t *out_tokens)
+{
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, out_tokens)) return rc;
+    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
+    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
+    return finish(c, enqueue_decode(c, first_token, n, false, 1.0f, 0.0f, 0, 0, out_tokens));
+}
+
 int rwkv_sample_typical(rwkv_ctx *c, uint64_t row, float temp, float tau, double u, int flags, uint64_t *token)
 {
-    if (!c || !token) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (c->l1 != c->L) return fail(RWKV_E_STATE, "this pipeline stage does not hold the head");
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, token)) return rc;
     if (row >= c->maxT) return fail(RWKV_E_ARG, "logits row %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)c->maxT);
     if (!(temp > 0.f) || !(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need temp > 0 and 0 <= u < 1");
-    HIPCHK(hipSetDevice(c->device));
-    int rc = launch_typical(c, (int)row, temp, tau, u, 0, false, flags, false);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    TypicalArgs a = typical_args(c, temp, tau, flags);
+    a.row = (int)row; a.u = u;
+    return finish(c, [&]() -> int {
+        if (const int rc = enqueue_typical(c, a, 1)) return rc;
+        HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
 }
 
 int rwkv_decode_typical(rwkv_ctx *c, uint64_t first_token, uint64_t n, float temp, float tau, uint64_t seed, int flags, uint64_t *out_tokens)
 {
-    if (!c || !out_tokens) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (c->l0 != 0 || c->l1 != c->L) return fail(RWKV_E_STATE, "needs a whole-model context");
-    if (first_token >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, out_tokens)) return rc;
+    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
     if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
     if (!(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    if (const int rcc = set_ctl(c, first_token, 0, 0)) return rcc;
-    for (uint64_t i = 0; i < n; i++) {
-        int rc = run_token(c, false);                                   // the token graph without the argmax node
-        if (!rc) rc = launch_typical(c, -1, temp, tau, 0.0, seed, true, flags | RWKV_SAMPLE_BAN0, true);
-        if (rc) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    return finish(c, enqueue_decode(c, first_token, n, true, temp, tau, seed, flags, out_tokens));
 }
 
 namespace {
-// grow a batched-decode buffer to `bytes` (contents are not kept); counted in rwkv_resident_bytes
-int bd_grow(rwkv_ctx *c, rwkv_ctx::Grown &g, size_t bytes)
+// grow one of the context's buffers to `bytes` (contents are not kept); counted in rwkv_resident_bytes
+int grow_buffer(rwkv_ctx *c, GrownBuf which, size_t bytes)
 {
+    rwkv_ctx::Grown &g = c->grown[which];
     if (bytes <= g.bytes) return 0;
     if (g.p) {
         HIPCHK(hipStreamSynchronize(c->stream));
@@ -1614,58 +1627,51 @@ int bd_grow(rwkv_ctx *c, rwkv_ctx::Grown &g, size_t bytes)
 int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, bool typical, float temp, float tau,
                  const uint64_t *seeds, int flags, uint64_t *out_tokens)
 {
-    if (!c || !first_tokens || !out_tokens || (typical && !seeds)) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (c->l0 != 0 || c->l1 != c->L) return fail(RWKV_E_STATE, "needs a whole-model context (a pipeline stage has no embedding / head of its own)");
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!typical || seeds))) return rc;
     if (N == 0 || N > c->maxT) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu (max context)", (unsigned long long)c->maxT);
     if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
-    for (uint64_t s = 0; s < N; s++)
-        if (first_tokens[s] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id %llu out of range", (unsigned long long)first_tokens[s]);
+    if (const int rc = check_ids(first_tokens, N, "token")) return rc;
     if (typical && !(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
     if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
     if (N == 1)       // the decode path's kernels on slot 0
-        return typical ? rwkv_decode_typical(c, first_tokens[0], n_steps, temp, tau, seeds[0], flags, out_tokens)
-                       : rwkv_decode_greedy(c, first_tokens[0], n_steps, out_tokens);
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    int rc = bd_grow(c, c->bd_ids, sizeof(unsigned long long) * N * (n_steps + 2));
-    if (!rc && !typical) rc = bd_grow(c, c->bd_val, sizeof(float) * N * AM_SLICES);
-    if (!rc && !typical) rc = bd_grow(c, c->bd_idx, sizeof(unsigned) * N * AM_SLICES);
-    if (!rc && typical) rc = bd_grow(c, c->bd_part, sizeof(double) * N * TS_PART_ROW);
-    if (!rc && typical) rc = bd_grow(c, c->bd_p, sizeof(float) * N * TS_ROW);
-    if (!rc && typical) rc = bd_grow(c, c->bd_pw, sizeof(float) * N * TS_ROW);
-    if (!rc && typical) rc = bd_grow(c, c->bd_key, sizeof(unsigned) * N * TS_ROW);
-    if (rc) return rc;
-    unsigned long long *dseeds = static_cast<unsigned long long *>(c->bd_ids.p), *ids = dseeds + N;   // ids row k: the ids fed at step k
-    c->bd_host.assign(N * (n_steps + 1), 0ull);
-    for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = typical ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
-    HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
-    TypicalArgs ta{};
-    if (typical) {
-        ta = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
-        ta.row = 0; ta.use_seed = 1; ta.seeds = dseeds; ta.feedback = 0;
-        ta.part = static_cast<double *>(c->bd_part.p); ta.p = static_cast<float *>(c->bd_p.p);
-        ta.pw = static_cast<float *>(c->bd_pw.p); ta.key = static_cast<unsigned *>(c->bd_key.p);
-    }
-    for (uint64_t k = 0; k < n_steps && !rc; k++) {
-        rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL);       // logits rows 0 .. N - 1, state slots 0 .. N - 1
-        if (rc) break;
-        unsigned long long *next = ids + (k + 1) * N;
+        return finish(c, enqueue_decode(c, first_tokens[0], n_steps, typical, temp, tau, typical ? seeds[0] : 0, flags, out_tokens));
+    const int rc = finish(c, [&]() -> int {
+        int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * N * (n_steps + 2));
+        if (!rc && !typical) rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES);
+        if (!rc && !typical) rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
+        if (!rc && typical) rc = grow_buffer(c, BD_PART, sizeof(double) * N * TS_PART_ROW);
+        if (!rc && typical) rc = grow_buffer(c, BD_P, sizeof(float) * N * TS_ROW);
+        if (!rc && typical) rc = grow_buffer(c, BD_PW, sizeof(float) * N * TS_ROW);
+        if (!rc && typical) rc = grow_buffer(c, BD_KEY, sizeof(unsigned) * N * TS_ROW);
+        if (rc) return rc;
+        unsigned long long *dseeds = c->buf<unsigned long long>(BD_IDS), *ids = dseeds + N;   // ids row k: the ids fed at step k
+        c->bd_host.assign(N * (n_steps + 1), 0ull);
+        for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = typical ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
+        HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
+        TypicalArgs ta{};
         if (typical) {
-            ta.step = (int)k; ta.pick = next;
-            rc = enqueue_typical(c, ta, (unsigned)N);
-        } else {
-            float *val = static_cast<float *>(c->bd_val.p);
-            unsigned *idx = static_cast<unsigned *>(c->bd_idx.p);
-            k_argmax_rows<<<dim3(AM_SLICES, (unsigned)N), dim3(AM_NT), 0, c->stream>>>(c->logits, val, idx);
-            k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
-            HIPCHK(hipGetLastError());
+            ta = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
+            ta.row = 0; ta.use_seed = 1; ta.seeds = dseeds; ta.feedback = 0;
+            ta.part = c->buf<double>(BD_PART); ta.p = c->buf<float>(BD_P);
+            ta.pw = c->buf<float>(BD_PW); ta.key = c->buf<unsigned>(BD_KEY);
         }
-    }
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * n_steps, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    rc = device_check(c);
+        for (uint64_t k = 0; k < n_steps; k++) {
+            if ((rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL))) return rc;       // logits rows 0 .. N - 1, state slots 0 .. N - 1
+            unsigned long long *next = ids + (k + 1) * N;
+            if (typical) {
+                ta.step = (int)k; ta.pick = next;
+                if ((rc = enqueue_typical(c, ta, (unsigned)N))) return rc;
+            } else {
+                float *val = c->buf<float>(BD_VAL);
+                unsigned *idx = c->buf<unsigned>(BD_IDX);
+                k_argmax_rows<<<dim3(AM_SLICES, (unsigned)N), dim3(AM_NT), 0, c->stream>>>(c->logits, val, idx);
+                k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
+                HIPCHK(hipGetLastError());
+            }
+        }
+        HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * n_steps, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
     if (rc) return rc;
     for (uint64_t k = 0; k < n_steps; k++)              // [step][stream] -> [stream][step]
         for (uint64_t s = 0; s < N; s++) out_tokens[s * n_steps + k] = c->bd_host[k * N + s];
@@ -1686,34 +1692,33 @@ int rwkv_decode_batch_typical(rwkv_ctx *c, const uint64_t *first_tokens, uint64_
 
 int rwkv_state_copy(rwkv_ctx *c, uint64_t dst, uint64_t src)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED)) return rc;
     if (dst >= c->maxT || src >= c->maxT)
         return fail(RWKV_E_ARG, "state slot out of range (dst %llu, src %llu, max context %llu)", (unsigned long long)dst, (unsigned long long)src, (unsigned long long)c->maxT);
     if (dst == src) return 0;
     const size_t n = (size_t)c->L * c->D;
-    HIPCHK(hipSetDevice(c->device));
-    for (int s = 0; s < 5; s++)
-        HIPCHK(hipMemcpyAsync(c->state[s] + dst * n, c->state[s] + src * n, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    return finish(c, [&]() -> int {
+        for (int s = 0; s < 5; s++)
+            HIPCHK(hipMemcpyAsync(c->state[s] + dst * n, c->state[s] + src * n, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    }());
 }
 
 namespace {
-// Scoring.  The call's device arrays: sc_in = rows [N] | targets [N] (| control blocks), sc_out = logprob [N] | entropy [N] | argmax [N].
+// Scoring.  The call's device arrays: SC_IN = rows [N] | targets [N] (| control blocks), SC_OUT = logprob [N] | entropy [N] | argmax [N].
 int score_grow(rwkv_ctx *c, uint64_t N, uint64_t n_ctl, uint64_t n_part)
 {
-    int rc = bd_grow(c, c->sc_in, sizeof(unsigned long long) * 2 * N + sizeof(Ctl) * n_ctl);
-    if (!rc) rc = bd_grow(c, c->sc_part, sizeof(double) * SC_PART_Q * n_part);
-    if (!rc) rc = bd_grow(c, c->sc_out, sizeof(double) * 3 * N);
+    int rc = grow_buffer(c, SC_IN, sizeof(unsigned long long) * 2 * N + sizeof(Ctl) * n_ctl);
+    if (!rc) rc = grow_buffer(c, SC_PART, sizeof(double) * SC_PART_Q * n_part);
+    if (!rc) rc = grow_buffer(c, SC_OUT, sizeof(double) * 3 * N);
     return rc;
 }
 // the two score launches over queries [q0, q0 + n) of a call of N, their tuples in sc_part from its start on (one launch sequence
 // per SC_MAX_Y queries: gridDim.y)
 int enqueue_score(rwkv_ctx *c, uint64_t N, uint64_t q0, uint64_t n)
 {
-    const unsigned long long *in = static_cast<const unsigned long long *>(c->sc_in.p);
-    double *out = static_cast<double *>(c->sc_out.p), *part = static_cast<double *>(c->sc_part.p);
+    const unsigned long long *in = c->buf<unsigned long long>(SC_IN);
+    double *out = c->buf<double>(SC_OUT), *part = c->buf<double>(SC_PART);
     for (uint64_t k = 0; k < n; k += SC_MAX_Y) {
         const unsigned m = (unsigned)std::min<uint64_t>(n - k, SC_MAX_Y);
         const uint64_t q = q0 + k;
@@ -1724,14 +1729,14 @@ int enqueue_score(rwkv_ctx *c, uint64_t N, uint64_t q0, uint64_t n)
     HIPCHK(hipGetLastError());
     return 0;
 }
-// the one download of a call's results (into the last 3 N words of sc_host, behind what was uploaded from it), the wait for it, and the
-// results into the caller's arrays
-int score_finish(rwkv_ctx *c, uint64_t N, double *logprob, double *entropy, uint64_t *argmax)
+// The exit of a scoring call: the one download of its results (into the last 3 N words of sc_host, behind what was uploaded from it) where
+// `rc` says that everything before it was enqueued, the wait, and the results into the caller's arrays
+int score_finish(rwkv_ctx *c, uint64_t N, int rc, double *logprob, double *entropy, uint64_t *argmax)
 {
-    unsigned long long *h = c->sc_host.data() + (c->sc_host.size() - 3 * N);
-    HIPCHK(hipMemcpyAsync(h, c->sc_out.p, sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (const int rc = device_check(c)) return rc;
+    unsigned long long *h = rc ? nullptr : c->sc_host.data() + (c->sc_host.size() - 3 * N);
+    if (!rc && hipMemcpyAsync(h, c->buf<void>(SC_OUT), sizeof(double) * 3 * N, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+        rc = fail(RWKV_E_DEVICE, "download of the scores failed");
+    if ((rc = finish(c, rc))) return rc;
     memcpy(logprob, h, sizeof(double) * N);
     if (entropy) memcpy(entropy, h + N, sizeof(double) * N);
     if (argmax) for (uint64_t i = 0; i < N; i++) argmax[i] = h[2 * N + i];
@@ -1741,35 +1746,26 @@ int score_finish(rwkv_ctx *c, uint64_t N, double *logprob, double *entropy, uint
 
 int rwkv_score_rows(rwkv_ctx *c, const uint64_t *rows, const uint64_t *targets, uint64_t n, double *logprob, double *entropy, uint64_t *argmax)
 {
-    if (!c || !rows || !targets || !logprob) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (c->l1 != c->L) return fail(RWKV_E_STATE, "this pipeline stage does not hold the head");
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, rows && targets && logprob)) return rc;
     if (n == 0 || n > RWKV_MAX_SCORE) return fail(RWKV_E_ARG, "n must be in 1..%u", RWKV_MAX_SCORE);
-    for (uint64_t i = 0; i < n; i++) {
+    for (uint64_t i = 0; i < n; i++)
         if (rows[i] >= c->maxT) return fail(RWKV_E_ARG, "logits row %llu out of range (max context %llu)", (unsigned long long)rows[i], (unsigned long long)c->maxT);
-        if (targets[i] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "target id %llu out of range", (unsigned long long)targets[i]);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    if (const int rc = score_grow(c, n, 0, n)) return rc;
-    c->sc_host.resize(5 * n);                       // the upload | the download
-    for (uint64_t i = 0; i < n; i++) { c->sc_host[i] = rows[i]; c->sc_host[n + i] = targets[i]; }
-    HIPCHK(hipMemcpyAsync(c->sc_in.p, c->sc_host.data(), sizeof(unsigned long long) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    if (const int rc = enqueue_score(c, n, 0, n)) { (void)hipStreamSynchronize(c->stream); return rc; }
-    return score_finish(c, n, logprob, entropy, argmax);
+    if (const int rc = check_ids(targets, n, "target")) return rc;
+    return score_finish(c, n, [&]() -> int {
+        if (const int rc = score_grow(c, n, 0, n)) return rc;
+        c->sc_host.resize(5 * n);                       // the upload | the download
+        for (uint64_t i = 0; i < n; i++) { c->sc_host[i] = rows[i]; c->sc_host[n + i] = targets[i]; }
+        HIPCHK(hipMemcpyAsync(c->buf<void>(SC_IN), c->sc_host.data(), sizeof(unsigned long long) * 2 * n, hipMemcpyHostToDevice, c->stream));
+        return enqueue_score(c, n, 0, n);
+    }(), logprob, entropy, argmax);
 }
 
 int rwkv_score(rwkv_ctx *c, const uint64_t *tokens, const uint64_t *targets, uint64_t n, double *logprob, double *entropy, uint64_t *argmax)
 {
-    if (!c || !tokens || !targets || !logprob) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (c->l0 != 0 || c->l1 != c->L) return fail(RWKV_E_STATE, "needs a whole-model context (a pipeline stage has no embedding / head of its own)");
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, tokens && targets && logprob)) return rc;
     if (n == 0 || n > RWKV_MAX_SCORE) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", RWKV_MAX_SCORE);
-    for (uint64_t t = 0; t < n; t++) {
-        if (tokens[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id %llu out of range", (unsigned long long)tokens[t]);
-        if (targets[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "target id %llu out of range", (unsigned long long)targets[t]);
-    }
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
+    if (const int rc = check_ids(tokens, n, "token")) return rc;
+    if (const int rc = check_ids(targets, n, "target")) return rc;
     trim_pass_graphs(c);
     // the pieces a caller's loop of rwkv_forward(max_ctx tokens, GPT) would make, each through the path rwkv_forward takes for it: the chunk
     // path for >= 2 tokens where the context has one, else token by token through the decode kernels
@@ -1777,36 +1773,36 @@ int rwkv_score(rwkv_ctx *c, const uint64_t *tokens, const uint64_t *targets, uin
     auto chunked = [&](uint64_t np) { return np >= 2 && c->seq_ok; };
     uint64_t n_ctl = 0;
     for (uint64_t t0 = 0; t0 < n; t0 += P) { const uint64_t np = std::min(P, n - t0); if (!chunked(np)) n_ctl += np; }
-    if (const int rc = score_grow(c, n, n_ctl, std::min(P, n))) return rc;
-    // one upload: the logits row of every query (its position in its piece), the targets, and the control block of every token that runs
-    // token by token (rwkv_forward stages those one by one in pinned memory; here they reach c->ctl by device-to-device copies)
-    static_assert(sizeof(Ctl) % sizeof(unsigned long long) == 0, "control blocks sit behind the u64 arrays");
-    constexpr size_t CW = sizeof(Ctl) / sizeof(unsigned long long);
-    const size_t up = 2 * n + CW * n_ctl;
-    c->sc_host.assign(up + 3 * n, 0ull);             // the upload | the download
-    Ctl *h_ctl = reinterpret_cast<Ctl *>(c->sc_host.data() + 2 * n);
-    const Ctl *d_ctl = reinterpret_cast<const Ctl *>(static_cast<unsigned long long *>(c->sc_in.p) + 2 * n);
-    for (uint64_t t0 = 0, k = 0; t0 < n; t0 += P) {
-        const uint64_t np = std::min(P, n - t0);
-        for (uint64_t t = 0; t < np; t++) {
-            c->sc_host[t0 + t] = t; c->sc_host[n + t0 + t] = targets[t0 + t];
-            if (!chunked(np)) { Ctl &h = h_ctl[k++]; h.token = tokens[t0 + t]; h.slot = 0u; h.out_row = (unsigned)t; h.step = 0; h.pad = 0; }
-        }
-    }
-    HIPCHK(hipMemcpyAsync(c->sc_in.p, c->sc_host.data(), sizeof(unsigned long long) * up, hipMemcpyHostToDevice, c->stream));
-    int rc = 0;
-    for (uint64_t t0 = 0, k = 0; t0 < n && !rc; t0 += P) {
-        const uint64_t np = std::min(P, n - t0);
-        if (chunked(np)) rc = enqueue_rows(c, tokens + t0, nullptr, np, RWKV_MODE_GPT);
-        else
-            for (uint64_t t = 0; t < np && !rc; t++) {
-                if (hipMemcpyAsync(c->ctl, d_ctl + k++, sizeof(Ctl), hipMemcpyDeviceToDevice, c->stream) != hipSuccess) rc = fail(RWKV_E_DEVICE, "control block copy failed");
-                if (!rc) rc = run_token(c, false);
+    return score_finish(c, n, [&]() -> int {
+        if (const int rc = score_grow(c, n, n_ctl, std::min(P, n))) return rc;
+        // one upload: the logits row of every query (its position in its piece), the targets, and the control block of every token that runs
+        // token by token (rwkv_forward stages those one by one in pinned memory; here they reach c->ctl by device-to-device copies)
+        static_assert(sizeof(Ctl) % sizeof(unsigned long long) == 0, "control blocks sit behind the u64 arrays");
+        constexpr size_t CW = sizeof(Ctl) / sizeof(unsigned long long);
+        const size_t up = 2 * n + CW * n_ctl;
+        c->sc_host.assign(up + 3 * n, 0ull);             // the upload | the download
+        Ctl *h_ctl = reinterpret_cast<Ctl *>(c->sc_host.data() + 2 * n);
+        const Ctl *d_ctl = reinterpret_cast<const Ctl *>(c->buf<unsigned long long>(SC_IN) + 2 * n);
+        for (uint64_t t0 = 0, k = 0; t0 < n; t0 += P) {
+            const uint64_t np = std::min(P, n - t0);
+            for (uint64_t t = 0; t < np; t++) {
+                c->sc_host[t0 + t] = t; c->sc_host[n + t0 + t] = targets[t0 + t];
+                if (!chunked(np)) { Ctl &h = h_ctl[k++]; h.token = tokens[t0 + t]; h.slot = 0u; h.out_row = (unsigned)t; h.step = 0; h.pad = 0; }
             }
-        if (!rc) rc = enqueue_score(c, n, t0, np);      // behind the piece, in front of the next one, which overwrites the rows
-    }
-    if (rc) { (void)hipStreamSynchronize(c->stream); return rc; }
-    return score_finish(c, n, logprob, entropy, argmax);
+        }
+        HIPCHK(hipMemcpyAsync(c->buf<void>(SC_IN), c->sc_host.data(), sizeof(unsigned long long) * up, hipMemcpyHostToDevice, c->stream));
+        for (uint64_t t0 = 0, k = 0; t0 < n; t0 += P) {
+            const uint64_t np = std::min(P, n - t0);
+            if (chunked(np)) { if (const int rc = enqueue_rows(c, tokens + t0, nullptr, np, RWKV_MODE_GPT)) return rc; }
+            else
+                for (uint64_t t = 0; t < np; t++) {
+                    HIPCHK(hipMemcpyAsync(c->ctl, d_ctl + k++, sizeof(Ctl), hipMemcpyDeviceToDevice, c->stream));
+                    if (const int rc = run_token(c, false)) return rc;
+                }
+            if (const int rc = enqueue_score(c, n, t0, np)) return rc;      // behind the piece, in front of the next one, which overwrites the rows
+        }
+        return 0;
+    }(), logprob, entropy, argmax);
 }
 
 void rwkv_free(rwkv_ctx *c)
@@ -1818,7 +1814,7 @@ void rwkv_free(rwkv_ctx *c)
     if (c->g_greedy) { (void)hipGraphExecDestroy(c->g_greedy); c->g_greedy = nullptr; }
     rwkv_pipe_free(c);        // (no graphs left to re-capture)
     for (void *p : c->allocs) (void)hipFree(p);
-    for (rwkv_ctx::Grown *g : {&c->bd_ids, &c->bd_val, &c->bd_idx, &c->bd_part, &c->bd_p, &c->bd_pw, &c->bd_key, &c->sc_in, &c->sc_part, &c->sc_out}) if (g->p) (void)hipFree(g->p);
+    for (const rwkv_ctx::Grown &g : c->grown) if (g.p) (void)hipFree(g.p);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
@@ -1848,37 +1844,46 @@ uint64_t rwkv_bytes_per_token(const rwkv_ctx *c)
     return 13 * nl * D * D + (c->l1 == c->L || c->l1 == UINT64_MAX ? V * D : 0) + 168 * nl * D + 40 * D;   // SURVEY.md section 8(d), this stage's share
 }
 
+namespace {
+// the events of a profiling call: destroyed however the call ends (as load_common's Scratch frees its staging)
+struct Events {
+    std::vector<hipEvent_t> ev;
+    int create(size_t n)
+    {
+        for (ev.reserve(n); ev.size() < n;) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); ev.push_back(e); }
+        return 0;
+    }
+    ~Events() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
+};
+} // namespace
+
 int rwkv_profile_token(rwkv_ctx *c, uint64_t token, int reps, double *ms, uint64_t *bytes, uint32_t *launches)
 {
-    if (!c || !ms) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, ms)) return rc;
     if (token >= RWKV_VOCAB || reps <= 0) return fail(RWKV_E_ARG, "bad token / reps");
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    const uint64_t L = c->L, D = c->D, V = RWKV_VOCAB;
-    const int nev = (int)(4 * (c->l1 - c->l0) + 4);
-    std::vector<hipEvent_t> ev(nev);
-    for (auto &e : ev) HIPCHK(hipEventCreate(&e));
+    const uint64_t D = c->D;
+    const int nlay = (int)(c->l1 - c->l0), nev = 4 * nlay + 4;
+    Events evs;
     for (int k = 0; k < RWKV_N_KCLASS; k++) ms[k] = 0.0;
-    if (const int rcc = set_ctl(c, token, 0, 0)) return rcc;
-    int rc = 0;
-    for (int rep = 0; rep < reps && !rc; rep++) {
-        rc = enqueue_token(c, true, ev.data());
-        if (rc) break;
-        if (hipStreamSynchronize(c->stream) != hipSuccess) { rc = fail(RWKV_E_DEVICE, "sync failed"); break; }
-        for (int i = 0; i + 1 < nev; i++) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, ev[i], ev[i + 1]) != hipSuccess) { rc = fail(RWKV_E_DEVICE, "hipEventElapsedTime failed"); break; }
-            const int nlay = (int)(c->l1 - c->l0);
-            int cls;
-            if (i == 0) cls = 0;
-            else if (i <= 4 * nlay) cls = 1 + (i - 1) % 4;
-            else if (i == 4 * nlay + 1) cls = 5;
-            else cls = 6;
-            ms[cls] += (double)t;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = evs.create(nev)) return rc;
+        if (const int rc = set_ctl(c, token, 0, 0)) return rc;
+        for (int rep = 0; rep < reps; rep++) {
+            if (const int rc = enqueue_token(c, true, evs.ev.data())) return rc;
+            HIPCHK(hipStreamSynchronize(c->stream));
+            for (int i = 0; i + 1 < nev; i++) {
+                float t = 0.f;
+                HIPCHK(hipEventElapsedTime(&t, evs.ev[i], evs.ev[i + 1]));
+                int cls;
+                if (i == 0) cls = 0;
+                else if (i <= 4 * nlay) cls = 1 + (i - 1) % 4;
+                else if (i == 4 * nlay + 1) cls = 5;
+                else cls = 6;
+                ms[cls] += (double)t;
+            }
         }
-    }
-    for (auto &e : ev) (void)hipEventDestroy(e);
+        return 0;
+    }());
     if (bytes) {
         bytes[0] = 4 * D; bytes[6] = 0;
         for (int k = 0; k < 5; k++) bytes[1 + k] = c->wc[k].row_bytes(D);
@@ -1894,82 +1899,75 @@ int rwkv_profile_token(rwkv_ctx *c, uint64_t token, int reps, double *ms, uint64
 // figure is comparable with rocprofv3's kernel durations.  ms[c] = total ms, n[c] = launches.
 int rwkv_profile_batched(rwkv_ctx *c, uint64_t token, int reps, double *ms, uint32_t *n)
 {
-    if (!c || !ms || !n) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, ms && n)) return rc;
     if (token >= RWKV_VOCAB || reps <= 0) return fail(RWKV_E_ARG, "bad token / reps");
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    if (const int rcc = set_ctl(c, token, 0, 0)) return rcc;
-    int rc = enqueue_token(c, true, nullptr);   // valid inputs for every class
-    if (rc) return rc;
-    hipEvent_t a, b;
-    HIPCHK(hipEventCreate(&a)); HIPCHK(hipEventCreate(&b));
-    for (int cls = 0; cls < RWKV_N_KCLASS; cls++) {
-        const bool per_layer = cls >= 1 && cls <= 4;
-        // a class with ONE launch per token gets 8 x as many repetitions (4 launches in a bracket measured +10 % on k_head) and a
-        // warm-up launch.  k_head's 206 MB would stay in the 256 MiB Infinity Cache between back-to-back launches (33.6 us against
-        // 35.7 us inside the real token, rocprofv3): every head launch is preceded by ffn_v launches of four rotating layers (what a
-        // token puts in front of it) and the same sequence WITHOUT the head is timed as well; the difference is the head.
-        const int nrep = per_layer ? reps : reps * 8;
-        const uint64_t nl = c->l1 - c->l0;
-        const bool flush = cls == 5 && nl >= 4;
-        float t = 0.f, t0 = 0.f;
-        uint32_t cnt = 0;
-        for (int pass = flush ? 0 : 1; pass < 2; pass++) {      // pass 0: the flushing launches alone
-            launch_class(c, cls, per_layer ? c->l0 : 0);
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipEventRecord(a, c->stream));
-            cnt = 0;
-            for (int r = 0; r < nrep; r++)
-                for (uint64_t l = (per_layer ? c->l0 : 0); l < (per_layer ? c->l1 : 1); l++) {
-                    if (flush) for (int q = 0; q < 4; q++) launch_class(c, 4, c->l0 + (uint64_t)(4 * r + q) % nl);
-                    if (pass == 1) launch_class(c, cls, l);
-                    cnt++;
-                }
-            HIPCHK(hipEventRecord(b, c->stream));
-            HIPCHK(hipEventSynchronize(b));
-            HIPCHK(hipEventElapsedTime(pass == 0 ? &t0 : &t, a, b));
+    Events evs;
+    return finish(c, [&]() -> int {
+        if (const int rc = set_ctl(c, token, 0, 0)) return rc;
+        if (const int rc = enqueue_token(c, true, nullptr)) return rc;   // valid inputs for every class
+        if (const int rc = evs.create(2)) return rc;
+        const hipEvent_t a = evs.ev[0], b = evs.ev[1];
+        for (int cls = 0; cls < RWKV_N_KCLASS; cls++) {
+            const bool per_layer = cls >= 1 && cls <= 4;
+            // a class with ONE launch per token gets 8 x as many repetitions (4 launches in a bracket measured +10 % on k_head) and a
+            // warm-up launch.  k_head's 206 MB would stay in the 256 MiB Infinity Cache between back-to-back launches (33.6 us against
+            // 35.7 us inside the real token, rocprofv3): every head launch is preceded by ffn_v launches of four rotating layers (what a
+            // token puts in front of it) and the same sequence WITHOUT the head is timed as well; the difference is the head.
+            const int nrep = per_layer ? reps : reps * 8;
+            const uint64_t nl = c->l1 - c->l0;
+            const bool flush = cls == 5 && nl >= 4;
+            float t = 0.f, t0 = 0.f;
+            uint32_t cnt = 0;
+            for (int pass = flush ? 0 : 1; pass < 2; pass++) {      // pass 0: the flushing launches alone
+                launch_class(c, cls, per_layer ? c->l0 : 0);
+                HIPCHK(hipStreamSynchronize(c->stream));
+                HIPCHK(hipEventRecord(a, c->stream));
+                cnt = 0;
+                for (int r = 0; r < nrep; r++)
+                    for (uint64_t l = (per_layer ? c->l0 : 0); l < (per_layer ? c->l1 : 1); l++) {
+                        if (flush) for (int q = 0; q < 4; q++) launch_class(c, 4, c->l0 + (uint64_t)(4 * r + q) % nl);
+                        if (pass == 1) launch_class(c, cls, l);
+                        cnt++;
+                    }
+                HIPCHK(hipEventRecord(b, c->stream));
+                HIPCHK(hipEventSynchronize(b));
+                HIPCHK(hipEventElapsedTime(pass == 0 ? &t0 : &t, a, b));
+            }
+            ms[cls] = (double)(t - t0); n[cls] = cnt;
         }
-        ms[cls] = (double)(t - t0); n[cls] = cnt;
-    }
-    (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-    HIPCHK(hipGetLastError());
-    // the batches above advanced the recurrent state with a scrambled schedule: reset it
-    for (int st = 0; st < 5; st++)
-        HIPCHK(hipMemsetAsync(c->state[st], 0, c->maxT * c->L * c->D * sizeof(double), c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+        HIPCHK(hipGetLastError());
+        // the batches above advanced the recurrent state with a scrambled schedule: reset it
+        return enqueue_reset(c);
+    }());
 }
 
 // debug: run one eager token with the phase timeline of the middle layer's ffn_rk kernel enabled;
 // out receives grid*NW*8 100-MHz wall-clock stamps (see tl_stamp in kernels.hip.h)
 int rwkv_debug_timeline(rwkv_ctx *c, uint64_t token, unsigned long long *out, uint64_t cap)
 {
-    if (!c || !out) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, out)) return rc;
     const size_t n = (size_t)(c->grid > 512 ? c->grid : 512) * NW * 8;      // (a chunk GEMM may launch more workgroups than the decode grid)
     if (cap < n) return fail(RWKV_E_ARG, "need room for %zu stamps", n);
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    if (!c->tl) { int rc = dalloc(c, &c->tl, n); if (rc) return rc; }
-    HIPCHK(hipMemsetAsync(c->tl, 0, n * 8, c->stream));
-    if (const int rcc = set_ctl(c, token, 0, 0)) return rcc;
-    { const char *e = getenv("RWKV_TL_CLASS"); c->tl_cls = e ? atoi(e) : 3; }
-    c->tl_on = true;
-    int rc;
-    if (c->tl_cls >= 10) {          // a GEMM of the chunk path (10 + kind: one 32-row GPT chunk of this token; 20 + kind: a 64-row pass, the two-half GEMMs)
-        if (!c->seq_ok) { c->tl_on = false; return fail(RWKV_E_STATE, "the chunk path is not loaded (max_ctx 1)"); }
-        uint64_t toks[SEQ_TM];
-        for (int t = 0; t < SEQ_TM; t++) toks[t] = token;
-        int rows = SEQ_T;
-        if (c->tl_cls >= 20) { c->tl_cls -= 10; if (c->seq_rows > SEQ_T && c->maxT >= (uint64_t)SEQ_TM) rows = SEQ_TM; }
-        rc = enqueue_whole(c, toks, rows, 0, 0);
-    } else rc = enqueue_token(c, false, nullptr);
-    c->tl_on = false;
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(out, c->tl, n * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    return finish(c, [&]() -> int {
+        if (!c->tl) { int rc = dalloc(c, &c->tl, n); if (rc) return rc; }
+        HIPCHK(hipMemsetAsync(c->tl, 0, n * 8, c->stream));
+        if (const int rc = set_ctl(c, token, 0, 0)) return rc;
+        { const char *e = getenv("RWKV_TL_CLASS"); c->tl_cls = e ? atoi(e) : 3; }
+        c->tl_on = true;
+        int rc;
+        if (c->tl_cls >= 10) {          // a GEMM of the chunk path (10 + kind: one 32-row GPT chunk of this token; 20 + kind: a 64-row pass, the two-half GEMMs)
+            if (!c->seq_ok) { c->tl_on = false; return fail(RWKV_E_STATE, "the chunk path is not loaded (max_ctx 1)"); }
+            uint64_t toks[SEQ_TM];
+            for (int t = 0; t < SEQ_TM; t++) toks[t] = token;
+            int rows = SEQ_T;
+            if (c->tl_cls >= 20) { c->tl_cls -= 10; if (c->seq_rows > SEQ_T && c->maxT >= (uint64_t)SEQ_TM) rows = SEQ_TM; }
+            rc = enqueue_whole(c, toks, rows, 0, 0);
+        } else rc = enqueue_token(c, false, nullptr);
+        c->tl_on = false;
+        if (rc) return rc;
+        HIPCHK(hipMemcpyAsync(out, c->tl, n * 8, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
 }
 
 // ---- per-kernel parity hooks (tests/test_kernels_gpu.py): the PRODUCTION launch of one decode kernel class, eagerly, on whatever the
@@ -1977,22 +1975,20 @@ int rwkv_debug_timeline(rwkv_ctx *c, uint64_t token, unsigned long long *out, ui
 // then (1, 2, 3, 4) per layer, then 5: exactly what enqueue_token launches, one kernel at a time. ----
 int rwkv_debug_launch(rwkv_ctx *c, int cls, uint64_t layer, uint64_t token, uint32_t slot)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES)) return rc;
     if (cls < 0 || cls > 6) return fail(RWKV_E_ARG, "kernel class %d out of range (0 first, 1 att, 2 att_out, 3 ffn r+k, 4 ffn_v, 5 head, 6 argmax)", cls);
     if (cls >= 1 && cls <= 4 && (layer < c->l0 || layer >= c->l1)) return fail(RWKV_E_ARG, "layer %llu is not one of this context's", (unsigned long long)layer);
     if (cls >= 5 && c->l1 != c->L) return fail(RWKV_E_STATE, "this context does not hold the head");
     if (slot >= c->maxT) return fail(RWKV_E_ARG, "state slot %u out of range", slot);
-    if (c->l0 == 0 && token >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
-    HIPCHK(hipSetDevice(c->device));
-    { const int rcp = begin_call(c); if (rcp) return rcp; }
-    if (cls == 0) {      // the token's control block: every later launch of the token reads slot / out_row from it
-        if (const int rcc = set_ctl(c, token, slot, slot)) return rcc;
-    }
-    launch_class(c, cls, layer);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    if (const int rc = check_ids(&token, c->l0 == 0, "token")) return rc;
+    return finish(c, [&]() -> int {
+        if (cls == 0) {      // the token's control block: every later launch of the token reads slot / out_row from it
+            if (const int rc = set_ctl(c, token, slot, slot)) return rc;
+        }
+        launch_class(c, cls, layer);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }());
 }
 
 namespace {
@@ -2018,28 +2014,26 @@ int debug_buf(rwkv_ctx *c, int which, void **p, size_t *bytes)
 
 int rwkv_debug_read(rwkv_ctx *c, int which, void *dst, uint64_t cap)
 {
-    if (!c || !dst) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED, dst)) return rc;
     void *p = nullptr; size_t n = 0;
-    { const int rc = debug_buf(c, which, &p, &n); if (rc) return rc; }
+    if (const int rc = debug_buf(c, which, &p, &n)) return rc;
     if (cap < n) return fail(RWKV_E_ARG, "debug buffer %d holds %zu bytes", which, n);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(dst, p, n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return finish(c, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(dst, p, n, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
 }
 
 int rwkv_debug_write(rwkv_ctx *c, int which, const void *src, uint64_t bytes)
 {
-    if (!c || !src) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED, src)) return rc;
     void *p = nullptr; size_t n = 0;
-    { const int rc = debug_buf(c, which, &p, &n); if (rc) return rc; }
+    if (const int rc = debug_buf(c, which, &p, &n)) return rc;
     if (bytes != n) return fail(RWKV_E_ARG, "debug buffer %d holds %zu bytes", which, n);
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return 0;
+    return finish(c, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(p, src, n, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }());
 }
 
 uint64_t rwkv_debug_grid(const rwkv_ctx *c) { return c ? (uint64_t)c->grid : 0; }
@@ -2129,14 +2123,12 @@ int rwkv_pipe_unique_id(void *out128)
 
 int rwkv_pipe_init(rwkv_ctx *c, const void *id128, int rank, int world)
 {
-    if (!c || !id128) return fail(RWKV_E_ARG, "NULL argument");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
+    if (const int rc = guard(c, NEED_LOADED, id128)) return rc;
     if (world < 1 || rank < 0 || rank >= world) return fail(RWKV_E_ARG, "bad rank %d of %d", rank, world);
     if (c->pipe) return fail(RWKV_E_STATE, "pipeline transport already initialised");
     if ((rank == 0) != (c->l0 == 0) || (rank == world - 1) != (c->l1 == c->L))
         return fail(RWKV_E_ARG, "rank %d of %d does not match this context's layer range [%llu, %llu) of %llu", rank, world,
                     (unsigned long long)c->l0, (unsigned long long)c->l1, (unsigned long long)c->L);
-    HIPCHK(hipSetDevice(c->device));
     Pipe *p = new Pipe();
     int rc = pipe_open(p);
     if (rc) { delete p; return rc; }
@@ -2235,7 +2227,7 @@ int rwkv_pipe_init(rwkv_ctx *c, const void *id128, int rank, int world)
 // version code and the path of the shared object that holds ncclSend, HIP runtime version, agreed prefill micro-batch rows)
 int rwkv_pipe_info(rwkv_ctx *c, char *out, uint64_t cap)
 {
-    if (!c || !out || cap == 0) return fail(RWKV_E_ARG, "NULL argument");
+    if (const int rc = guard(c, 0, out && cap)) return rc;
     if (!c->pipe) return fail(RWKV_E_STATE, "needs rwkv_pipe_init done");
     snprintf(out, (size_t)cap, "%s", c->pipe->info.c_str());
     return 0;
@@ -2252,8 +2244,8 @@ int rwkv_pipe_info(rwkv_ctx *c, char *out, uint64_t cap)
 // With rwkv_pipe_profile(ctx, 1) every tick whose RCCL group holds a receive is bracketed by an event pair (rwkv_pipe_hop_stats).
 int rwkv_pipe_decode_streams(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_steps, uint64_t n_streams, uint64_t *picks)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded || !c->pipe) return fail(RWKV_E_STATE, "needs a loaded context with rwkv_pipe_init done");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES)) return rc;
+    if (!c->pipe) return fail(RWKV_E_STATE, "needs rwkv_pipe_init done");
     Pipe *p = c->pipe;
     const int S = p->world, rank = p->rank;
     const bool lastr = rank == S - 1;
@@ -2268,10 +2260,6 @@ int rwkv_pipe_decode_streams(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t
     bool bad_id = false;
     if (rank == 0)
         for (int k = 0; k < (int)n_streams; k++) bad_id = bad_id || first_tokens[k] >= RWKV_VOCAB;
-    HIPCHK(hipSetDevice(c->device));
-    // (a failure here must not strand the peers in their ncclRecv either: it is reported once the schedule has drained; without
-    // re-captured graphs run_token launches the kernels one by one)
-    const int rc_begin = begin_call(c);
     if (c->pipe_ring_cap < n_items) {
         if (c->pipe_ring) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipHostFree(c->pipe_ring); c->pipe_ring = nullptr; c->pipe_ring_cap = 0; }
         HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->pipe_ring), sizeof(Ctl) * n_items, hipHostMallocDefault));
@@ -2320,7 +2308,6 @@ int rwkv_pipe_decode_streams(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t
         else for (uint64_t j = 0; j < n_items; j++) picks[(j % S) * n_steps + j / S] = active(j) ? g[j] : 0;     // (rows of streams that did not run: zero)
     }
     { const int dc = device_check(c); if (!rc) rc = dc; }      // always consumed: a code raised here must not surface from a later call
-    if (!rc && rc_begin) rc = rc_begin;
     if (!rc && c->pipe_prof) {
         double sum = 0.0, mn = 1e30, mx = 0.0;
         for (size_t i = 0; i < hop_n; i++) {
@@ -2421,8 +2408,8 @@ int pipe_dual_setup(rwkv_ctx *c)
 // first_tokens: [2 * world] (read on rank 0); picks: [2 * world][n_steps] (written on the last rank).  Needs max_ctx >= 2 * world state slots.
 int rwkv_pipe_decode_dual(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_steps, uint64_t *picks)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded || !c->pipe) return fail(RWKV_E_STATE, "needs a loaded context with rwkv_pipe_init done");
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES)) return rc;
+    if (!c->pipe) return fail(RWKV_E_STATE, "needs rwkv_pipe_init done");
     Pipe *p = c->pipe;
     const int S = p->world, rank = p->rank;
     const bool lastr = rank == S - 1;
@@ -2434,8 +2421,6 @@ int rwkv_pipe_decode_dual(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_
     bool bad_id = false;
     if (rank == 0)
         for (int g = 0; g < 2 * S; g++) bad_id = bad_id || first_tokens[g] >= RWKV_VOCAB;
-    HIPCHK(hipSetDevice(c->device));
-    const int rc_begin = begin_call(c);
     { const int rs = pipe_dual_setup(c); if (rs) return rs; }
     if (c->pipe_ring_cap < 2 * n_sub) {
         if (c->pipe_ring) { HIPCHK(hipStreamSynchronize(c->stream)); (void)hipHostFree(c->pipe_ring); c->pipe_ring = nullptr; c->pipe_ring_cap = 0; }
@@ -2500,7 +2485,6 @@ int rwkv_pipe_decode_dual(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_
                 for (int k = 0; k < 2; k++) picks[(2 * (i % S) + k) * n_steps + i / S] = g[2 * i + k];
     }
     { const int dc = device_check(c); if (!rc) rc = dc; }
-    if (!rc && rc_begin) rc = rc_begin;
     if (!rc && bad_id) rc = fail(RWKV_E_ARG, "token id out of range (the schedule ran with id 0 in its place)");
     return rc;
 }
@@ -2515,13 +2499,13 @@ int rwkv_pipe_decode(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_steps
 // whose group held a receive.  The MIN is the hop itself (the peer's data was waiting); the mean includes waiting for the peer.
 int rwkv_pipe_profile(rwkv_ctx *c, int on)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
+    if (const int rc = guard(c, 0)) return rc;
     c->pipe_prof = on != 0;
     return 0;
 }
 int rwkv_pipe_hop_stats(rwkv_ctx *c, double *out4)
 {
-    if (!c || !out4) return fail(RWKV_E_ARG, "NULL argument");
+    if (const int rc = guard(c, 0, out4)) return rc;
     for (int k = 0; k < 4; k++) out4[k] = c->hop_stats[k];
     return 0;
 }
@@ -2532,24 +2516,19 @@ int rwkv_pipe_hop_stats(rwkv_ctx *c, double *out4)
 // output there (rwkv_xseq_device / rwkv_xseq_copy, or the RCCL recv of rwkv_pipe_prefill).  Asynchronous.
 int rwkv_stage_chunk(rwkv_ctx *c, const uint64_t *tokens, uint64_t n, uint64_t row0, int buf)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded) return fail(RWKV_E_STATE, "RWKV not loaded");
-    if (!c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx > 1; off with RWKV_SEQ=0 or n_embed not a multiple of 64)");
+    if (const int rc = guard(c, NEED_SEQ)) return rc;      // (not LAUNCHES: asynchronous -- what the device error word holds is rwkv_sync's to report)
     if (n == 0 || n > (uint64_t)SEQ_TM || row0 + n > c->maxT || (buf != 0 && buf != 1)) return fail(RWKV_E_ARG, "bad chunk (n %llu <= 64, row0 %llu, buf %d)", (unsigned long long)n, (unsigned long long)row0, buf);
     if (c->l0 == 0) {
         if (!tokens) return fail(RWKV_E_ARG, "stage 0 needs the token ids");
-        for (uint64_t t = 0; t < n; t++) if (tokens[t] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "token id out of range");
+        if (const int rc = check_ids(tokens, n, "token")) return rc;
     }
-    HIPCHK(hipSetDevice(c->device));
     return enqueue_whole(c, tokens, (int)n, row0, buf);
 }
 double *rwkv_xseq_device(rwkv_ctx *c, int buf) { return (c && (buf == 0 || buf == 1)) ? c->sq_x[buf] : nullptr; }
 int rwkv_sync(rwkv_ctx *c)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return device_check(c);
+    if (const int rc = guard(c, 0)) return rc;
+    return finish(c, 0);
 }
 // hand a chunk's residual stream from one stage context to the next ON THE SAME DEVICE (virtual stages: tests, and
 // several stages per GPU); ordered behind src's work, and dst's later work is ordered behind the copy
@@ -2580,15 +2559,12 @@ int rwkv_xseq_copy(rwkv_ctx *dst, int dbuf, rwkv_ctx *src, int sbuf, uint64_t ro
 // what RWKV::loadContext's caller reads; returns after the stage's stream has drained.
 int rwkv_pipe_prefill(rwkv_ctx *c, const uint64_t *tokens, uint64_t n_tokens)
 {
-    if (!c) return fail(RWKV_E_ARG, "NULL ctx");
-    if (!c->loaded || !c->pipe) return fail(RWKV_E_STATE, "needs a loaded context with rwkv_pipe_init done");
-    if (!c->seq_ok) return fail(RWKV_E_STATE, "chunked path not available (load with max_ctx >= 32; off with RWKV_SEQ=0 or n_embed not a multiple of 64)");
+    if (const int rc = guard(c, NEED_SEQ | LAUNCHES)) return rc;
+    if (!c->pipe) return fail(RWKV_E_STATE, "needs rwkv_pipe_init done");
     if (c->maxT < (uint64_t)SEQ_T) return fail(RWKV_E_ARG, "needs max_ctx >= %d", SEQ_T);
     Pipe *p = c->pipe;
     const int S = p->world, rank = p->rank;
     if (n_tokens == 0 || (rank == 0 && !tokens)) return fail(RWKV_E_ARG, "empty prompt");
-    HIPCHK(hipSetDevice(c->device));
-    if (c->herr) *c->herr = 0u;
     // k_seq_embed indexes the table with the id: validate the whole prompt on rank 0.  A bad id must not strand the other ranks in
     // their ncclRecv, so the schedule runs with id 0 in its place and the error is reported once it has drained.
     std::vector<uint64_t> clean;
