@@ -304,6 +304,55 @@ public:
         if (!residentState) pullState();
         return std::vector<unsigned long long>(ids.begin(), ids.end());
     }
+    // nucleus sampling with repetition penalties on the device (rwkv_mi355x.h "nucleus sampling"): temperature, top-p, top-k, presence and
+    // frequency penalties on the occurrence counts the context keeps per state slot.  The plain values of one call:
+    struct Nucleus { float temp = 1.0f, top_p = 0.9f; unsigned top_k = 0; float presence = 0.f, frequency = 0.f, decay = 1.0f; };
+    static rwkv_nucleus_params nucleusParams(const Nucleus &s, unsigned flags) { return rwkv_nucleus_params{s.temp, s.top_p, s.top_k, s.presence, s.frequency, s.decay, flags, 0u}; }
+    // one draw from logits row `row` of the last forward with the counts of slot `slot`; update: count the pick (counts * decay, then + 1)
+    int sampleNucleus(const Nucleus &s, double u, bool ban0 = false, bool update = false, unsigned long long row = 0, unsigned long long slot = 0)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        uint64_t tok = 0;
+        const rwkv_nucleus_params p = nucleusParams(s, (ban0 ? RWKV_NUCLEUS_BAN0 : 0u) | (update ? RWKV_NUCLEUS_UPDATE : 0u));
+        rwkv_detail::check(rwkv_sample_nucleus(ctx_, row, slot, &p, u, &tok));
+        return (int)tok;
+    }
+    // device-side sampled continuation on slot 0 (logit 0 banned, counts updated every step); keep: go on from the counts the last call left
+    std::vector<unsigned long long> decodeNucleus(unsigned long long first, unsigned long long n, const Nucleus &s, unsigned long long seed = 0, bool keep = false)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> ids(n);
+        const rwkv_nucleus_params p = nucleusParams(s, keep ? RWKV_NUCLEUS_KEEP : 0u);
+        if (!residentState) pushState();
+        rwkv_detail::check(rwkv_decode_nucleus(ctx_, first, n, &p, seed, ids.data()));
+        if (!residentState) pullState();
+        return std::vector<unsigned long long>(ids.begin(), ids.end());
+    }
+    // the same for first.size() streams: stream s on slot s draws what decodeNucleus(first[s], n, s, seeds[s]) draws
+    std::vector<unsigned long long> decodeBatchNucleus(const std::vector<unsigned long long> &first, unsigned long long n,
+                                                       const std::vector<unsigned long long> &seeds, const Nucleus &s, bool keep = false)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (seeds.size() != first.size()) throw std::runtime_error("need one seed per stream");
+        std::vector<uint64_t> ft(first.begin(), first.end()), sd(seeds.begin(), seeds.end()), ids(first.size() * n);
+        const rwkv_nucleus_params p = nucleusParams(s, keep ? RWKV_NUCLEUS_KEEP : 0u);
+        if (!residentState) pushState();
+        rwkv_detail::check(rwkv_decode_batch_nucleus(ctx_, ft.data(), ft.size(), n, &p, sd.data(), ids.data()));
+        if (!residentState) pullState();
+        return std::vector<unsigned long long>(ids.begin(), ids.end());
+    }
+    // the occurrence counts of one slot (50277 floats): save / restore a session, or upload a prompt's counts; empty = zero them
+    void setPenaltyCounts(unsigned long long slot, const std::vector<float> &counts)
+    {
+        if (!counts.empty() && counts.size() != 50277) throw std::runtime_error("need 50277 counts");
+        rwkv_detail::check(rwkv_penalty_set(ctx_, slot, counts.empty() ? nullptr : counts.data()));
+    }
+    std::vector<float> getPenaltyCounts(unsigned long long slot)
+    {
+        std::vector<float> counts(50277);
+        rwkv_detail::check(rwkv_penalty_get(ctx_, slot, counts.data()));
+        return counts;
+    }
     // copy state slot src into slot dst (fork a prefilled prompt); the host copy too when it is the authoritative one
     void copyState(unsigned long long dst, unsigned long long src)
     {

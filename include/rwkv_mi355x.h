@@ -159,6 +159,55 @@ int rwkv_decode_batch_typical(rwkv_ctx *ctx, const uint64_t *first_tokens, uint6
  * slots of a batched decode.  RWKV_E_ARG for a slot >= max_ctx, RWKV_E_STATE when not loaded. */
 int rwkv_state_copy(rwkv_ctx *ctx, uint64_t dst_slot, uint64_t src_slot);
 
+/* ---- nucleus sampling with repetition penalties, on the device (no reference counterpart: the reference ships typical() only) ----
+ * What the front ends of RWKV-4 models sample with: temperature, top-p, optionally top-k, presence and frequency penalties on a decaying
+ * occurrence count.  For one logits row l (f32, widened to f64) and one count vector c (f32 [50277], the occurrence counts of one stream):
+ *   1. penalty  l'_i = l_i - (presence + c_i * frequency) where c_i > 0, l'_i = l_i otherwise; with RWKV_NUCLEUS_BAN0 then l'_0 = -99 (storygen's
+ *               out[0] = -99, applied after the penalty).  With presence == 0 and frequency == 0 counts are not read, updated or allocated
+ *   2. softmax  p = softmax(l'), f64
+ *   3. top-p    order by descending p (stable in token id); v = p at the first position where the running mass reaches top_p; every token with
+ *               p_i >= v is kept (ties at the cut too).  top_p <= 0 keeps the most probable token and its ties; a mass that never reaches top_p
+ *               (top_p >= 1) keeps everything
+ *   4. top-k    with 0 < top_k < 50277 only tokens with p_i >= the top_k-th largest p are kept (ties too); 0 or >= 50277: off; 1 is penalised
+ *               greedy (among exact ties u decides)
+ *   5. kept     the intersection of 3 and 4; the most probable token is always in it
+ *   6. weights  exp((l'_i - max l') / temp) on the kept set: the largest weight is exactly 1 at every temp > 0, nothing underflows
+ *   7. draw     inverse CDF in token order for u in [0, 1); in the loops u of step k = uniform(splitmix64(seed + k)), the generator of the typical loops
+ *   8. counts   after the pick g, when updating: c_i <- f32(c_i * decay) for every i, then c_g <- c_g + 1, in f32 (a host restatement is bit-exact)
+ * On the device the cuts compare -log p as f32 (csrc/nucleus.hip.h): tokens whose p agree to 2^-23 relative tie.  Held draw by draw to a log-space
+ * f64 evaluation on planted logits by tests/test_nucleus_gpu.py; include/rwkv_sampler.h nucleus_u is the same draw on the host.  With NaN or +inf
+ * logits the pick is unspecified but below 50277, and nothing faults.
+ *
+ * The counts are one [max_ctx][50277] f32 buffer of the context, one vector per state slot: allocated and zeroed at the first call that needs it,
+ * counted by rwkv_resident_bytes, freed with the context; they persist across steps and calls.  The two copy calls below move one vector (201 KB)
+ * from / to host memory -- save and restore a chat session, count a prompt's tokens on the host and upload them; counts == NULL in the set call zeroes the vector.
+ *
+ * The sample call draws from logits row `row` of the LAST forward with the counts of state slot `slot` (independent of each other), updates
+ * the counts only with RWKV_NUCLEUS_UPDATE, and leaves logits and state alone.  The two decode calls follow the contracts of the typical loops above
+ * (stream s on slot s, logit 0 always banned, one upload and one download, no host synchronisation inside, n_streams == 1 on the decode kernels,
+ * more on the chunk path); they always update the counts, and zero those of their slots first unless RWKV_NUCLEUS_KEEP is set: with it a 16-step
+ * call gives exactly the ids of an 8-step call followed by an 8-step KEEP call with seed + 8.
+ * Status: RWKV_E_ARG for a NULL pointer, !(temp > 0), a non-finite top_p, presence or frequency, decay outside [0, 1], unknown flag bits or
+ * reserved != 0, u outside [0, 1), a row or slot >= max_ctx, a token id >= 50277, a step or stream count out of range; RWKV_E_STATE as for the
+ * typical calls.  Every check runs before anything is launched or allocated: a rejected call leaves state, logits and counts as they were. */
+#define RWKV_NUCLEUS_BAN0 1u
+#define RWKV_NUCLEUS_KEEP 2u
+#define RWKV_NUCLEUS_UPDATE 4u
+typedef struct rwkv_nucleus_params {
+    float temp, top_p;
+    uint32_t top_k;
+    float presence, frequency, decay;
+    uint32_t flags;    /* RWKV_NUCLEUS_BAN0 | RWKV_NUCLEUS_KEEP | RWKV_NUCLEUS_UPDATE */
+    uint32_t reserved; /* must be 0 */
+} rwkv_nucleus_params;
+int rwkv_sample_nucleus(rwkv_ctx *ctx, uint64_t row, uint64_t slot, const rwkv_nucleus_params *params, double u, uint64_t *token);
+int rwkv_decode_nucleus(rwkv_ctx *ctx, uint64_t first_token, uint64_t n_tokens, const rwkv_nucleus_params *params, uint64_t seed,
+                        uint64_t *out_tokens);
+int rwkv_decode_batch_nucleus(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps,
+                              const rwkv_nucleus_params *params, const uint64_t *seeds, uint64_t *out_tokens);
+int rwkv_penalty_set(rwkv_ctx *ctx, uint64_t slot, const float *counts /* host [50277]; NULL: zero */);
+int rwkv_penalty_get(rwkv_ctx *ctx, uint64_t slot, float *counts /* host [50277] */);
+
 /* ---- scoring: how probable is a given token, on the device (no reference counterpart: the reference only generates) ----
  * What they replace is a download: rwkv_forward, rwkv_get_output of [n][50277] f32 logits (201 KB per position) and a log-softmax on
  * the host.  A query is (logits row r, target id g).  With l_i the f32 logits of row r widened to f64, M = max_i l_i, d_i = l_i - M

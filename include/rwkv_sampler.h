@@ -109,6 +109,64 @@ inline int typical_u(const float *_logits, float _temp, float _tau, double u, bo
     return last;
 }
 
+// ---- nucleus sampling with repetition penalties: the host twin of the device sampler (csrc/nucleus.hip.h; the semantics are those of
+// include/rwkv_mi355x.h) as a plain sort-based restatement, the counterpart of typical_weights / typical_u.  counts: the f32 [50277]
+// occurrence counts of the stream, or nullptr (none).  Weights are formed relative to the largest logit, which is always kept: no limit at
+// near-greedy temperatures.
+inline std::vector<double> nucleus_weights(const float *_logits, const float *counts, float _temp, float top_p, unsigned top_k,
+                                           float presence = 0.f, float frequency = 0.f, bool ban0 = false)
+{
+    const int len = 50277;
+    std::vector<double> l(len), probs(len);
+    for (int i = 0; i < len; i++) {
+        l[i] = _logits[i];
+        if (counts && (presence != 0.f || frequency != 0.f) && counts[i] > 0.f) l[i] -= (double)presence + (double)counts[i] * (double)frequency;
+    }
+    if (ban0) l[0] = -99.0;
+    const double mx = *std::max_element(l.begin(), l.end());
+    double z = 0;
+    for (int i = 0; i < len; i++) { probs[i] = std::exp(l[i] - mx); z += probs[i]; }
+    for (int i = 0; i < len; i++) probs[i] /= z;
+    std::vector<int> ids(len);
+    std::iota(ids.begin(), ids.end(), 0);
+    std::stable_sort(ids.begin(), ids.end(), [&](int a, int b) { return probs[a] > probs[b]; });
+    double cum = 0;
+    int cutoff = 0;
+    for (int i = 0; i < len; i++) { cum += probs[ids[i]]; if (cum < (double)top_p) cutoff++; }
+    if (cutoff >= len) cutoff = len - 1;
+    double thr = probs[ids[cutoff]];                                                  // ties at the cut are kept
+    if (top_k > 0 && top_k < (unsigned)len) thr = std::max(thr, probs[ids[top_k - 1]]);
+    for (int i = 0; i < len; i++) {
+        const double d = l[i] - mx;
+        probs[i] = probs[i] >= thr ? std::exp(_temp == 1.0f ? d : d / (double)_temp) : 0.0;
+    }
+    return probs;
+}
+
+// deterministic draw for a given uniform u in [0, 1): inverse CDF in token order, the draw rwkv_sample_nucleus makes
+inline int nucleus_u(const float *_logits, const float *counts, float _temp, float top_p, unsigned top_k, double u,
+                     float presence = 0.f, float frequency = 0.f, bool ban0 = false)
+{
+    const std::vector<double> w = nucleus_weights(_logits, counts, _temp, top_p, top_k, presence, frequency, ban0);
+    double total = 0;
+    for (double v : w) total += v;
+    const double target = u * total;
+    double c = 0;
+    int last = 0;
+    for (int i = 0; i < (int)w.size(); i++) {
+        if (w[i] > 0) { c += w[i]; last = i; if (target < c) return i; }
+    }
+    return last;
+}
+
+// the count update behind a pick, in f32 as the device does it: counts <- f32(counts * decay), counts[pick] += 1
+inline void nucleus_count(float *counts, int pick, float decay)
+{
+    if (decay != 1.0f)
+        for (int i = 0; i < 50277; i++) counts[i] = counts[i] * decay;
+    counts[pick] += 1.0f;
+}
+
 inline int typical(float *_logits, float _temp = 0.9, float _tau = 0.8)
 {
     const std::vector<double> probs = typical_weights(_logits, _temp, _tau);

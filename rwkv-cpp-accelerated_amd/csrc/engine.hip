@@ -8,6 +8,7 @@
 #include "tile.hip.h"
 #include "seq.hip.h"
 #include "sampler.hip.h"
+#include "nucleus.hip.h"
 #include "score.hip.h"
 #include "../../include/rwkv_mi355x.h"
 
@@ -218,6 +219,7 @@ enum GrownBuf {
     SC_IN,                            // u64 [2][n]: rows | targets; behind them the control blocks of rwkv_score's token-by-token pieces
     SC_PART,                          // f64 [queries of one launch sequence][SC_G][4] per-workgroup tuples
     SC_OUT,                           // [3][n]: logprob f64 | entropy f64 | argmax u64
+    PEN_COUNTS,                       // f32 [max_ctx][V]: occurrence counts per state slot (nucleus.hip.h); allocated ONCE, zeroed, at the first call that needs them
     N_GROWN
 };
 
@@ -1565,6 +1567,79 @@ int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, bool typical, float 
     HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
+
+// ---- nucleus sampling (nucleus.hip.h) ----
+static_assert(sizeof(rwkv_nucleus_params) == 32, "rwkv_nucleus_params is 32 bytes in the C ABI");
+constexpr uint32_t NUCLEUS_FLAGS = RWKV_NUCLEUS_BAN0 | RWKV_NUCLEUS_KEEP | RWKV_NUCLEUS_UPDATE;
+int check_nucleus(const rwkv_nucleus_params *p)
+{
+    if (!(p->temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
+    if (!std::isfinite(p->top_p) || !std::isfinite(p->presence) || !std::isfinite(p->frequency)) return fail(RWKV_E_ARG, "top_p, presence and frequency must be finite");
+    if (!(p->decay >= 0.f && p->decay <= 1.f)) return fail(RWKV_E_ARG, "decay must be in [0, 1]");
+    if ((p->flags & ~NUCLEUS_FLAGS) || p->reserved) return fail(RWKV_E_ARG, "unknown flag bits (0x%x) or reserved != 0", p->flags);
+    return 0;
+}
+bool nucleus_penalty(const rwkv_nucleus_params &p) { return p.presence != 0.f || p.frequency != 0.f; }
+// the count vectors (device [max_ctx][V] f32): allocated and zeroed once
+int counts_alloc(rwkv_ctx *c)
+{
+    if (c->grown[PEN_COUNTS].p) return 0;
+    const size_t bytes = sizeof(float) * c->maxT * RWKV_VOCAB;
+    void *q = nullptr;
+    HIPCHK(hipMalloc(&q, bytes));
+    c->grown[PEN_COUNTS].p = q; c->grown[PEN_COUNTS].bytes = bytes; c->alloc_bytes += bytes;
+    HIPCHK(hipMemsetAsync(q, 0, bytes, c->stream));
+    return 0;
+}
+// what a call with these parameters needs of the counts of slots [slot0, slot0 + n): nothing without a penalty; else the buffer, and (`zero`: the
+// loops) those vectors cleared unless the caller keeps them
+int nucleus_counts(rwkv_ctx *c, const rwkv_nucleus_params &p, uint64_t slot0, uint64_t n, bool zero)
+{
+    if (!nucleus_penalty(p)) return 0;
+    const bool fresh = !c->grown[PEN_COUNTS].p;
+    if (const int rc = counts_alloc(c)) return rc;
+    if (zero && !fresh && !(p.flags & RWKV_NUCLEUS_KEEP))
+        HIPCHK(hipMemsetAsync(c->buf<float>(PEN_COUNTS) + slot0 * RWKV_VOCAB, 0, sizeof(float) * n * RWKV_VOCAB, c->stream));
+    return 0;
+}
+// the arguments common to every launch; `loop`: the decode loops always ban logit 0 and update the counts.  Call behind nucleus_counts.
+NucleusArgs nucleus_args(rwkv_ctx *c, const rwkv_nucleus_params &p, bool loop)
+{
+    NucleusArgs a{};
+    a.logits = c->logits; a.ctl = c->ctl; a.gen = c->gen; a.gen_cap = c->gen_cap;
+    a.inv_temp = p.temp == 1.0f ? 1.0 : 1.0 / (double)p.temp;
+    a.top_p = p.top_p; a.top_k = p.top_k >= RWKV_VOCAB ? 0u : p.top_k;
+    a.presence = p.presence; a.frequency = p.frequency; a.decay = p.decay;
+    a.penalty = nucleus_penalty(p) ? 1 : 0;
+    a.update = (loop || (p.flags & RWKV_NUCLEUS_UPDATE)) ? 1 : 0;
+    a.ban0 = (loop || (p.flags & RWKV_NUCLEUS_BAN0)) ? 1 : 0;
+    a.step = -1; a.seeds = nullptr;
+    a.counts = a.penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
+    a.pick = c->pick; a.part = c->ts_part; a.p = c->ts_p; a.pw = c->ts_pw; a.key = c->ts_key;
+    return a;
+}
+int enqueue_nucleus(rwkv_ctx *c, const NucleusArgs &a, unsigned rows)
+{
+    k_nucleus_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
+    k_nucleus_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
+    k_nucleus<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// enqueue_decode with the nucleus sampler behind the token graph, on slot 0 and its counts
+int enqueue_decode_nucleus(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_nucleus_params &p, uint64_t seed, uint64_t *out_tokens)
+{
+    if (const int rc = nucleus_counts(c, p, 0, 1, true)) return rc;
+    NucleusArgs a = nucleus_args(c, p, true);
+    a.row = -1; a.slot = 0; a.seed = seed; a.use_seed = 1; a.feedback = 1;
+    if (const int rc = set_ctl(c, first, 0, 0)) return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        if (const int rc = run_token(c, false)) return rc;
+        if (const int rc = enqueue_nucleus(c, a, 1)) return rc;
+    }
+    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
 } // namespace
 
 int rwkv_reset_state(rwkv_ctx *c)
@@ -1621,32 +1696,38 @@ int grow_buffer(rwkv_ctx *c, GrownBuf which, size_t bytes)
     return 0;
 }
 
-// rwkv_decode_batch_greedy / _typical: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
+// rwkv_decode_batch_greedy / _typical / _nucleus: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
 // else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
 // pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.
-int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, bool typical, float temp, float tau,
-                 const uint64_t *seeds, int flags, uint64_t *out_tokens)
+enum class Pick { GREEDY, TYPICAL, NUCLEUS };      // how a step of the batched decode picks: k_argmax_rows, sampler.hip.h (temp, tau, flags), nucleus.hip.h (np)
+int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, Pick kind, float temp, float tau,
+                 const uint64_t *seeds, int flags, const rwkv_nucleus_params *np, uint64_t *out_tokens)
 {
-    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!typical || seeds))) return rc;
+    const bool typical = kind == Pick::TYPICAL, nucleus = kind == Pick::NUCLEUS;
+    const bool sampled = kind != Pick::GREEDY;     // the sampler's scratch per row, one seed per stream
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!sampled || seeds) && (!nucleus || np))) return rc;
     if (N == 0 || N > c->maxT) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu (max context)", (unsigned long long)c->maxT);
     if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
     if (const int rc = check_ids(first_tokens, N, "token")) return rc;
     if (typical && !(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
+    if (const int rc = nucleus ? check_nucleus(np) : 0) return rc;
     if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
+    if (nucleus && N == 1) return finish(c, enqueue_decode_nucleus(c, first_tokens[0], n_steps, *np, seeds[0], out_tokens));
     if (N == 1)       // the decode path's kernels on slot 0
         return finish(c, enqueue_decode(c, first_tokens[0], n_steps, typical, temp, tau, typical ? seeds[0] : 0, flags, out_tokens));
     const int rc = finish(c, [&]() -> int {
         int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * N * (n_steps + 2));
-        if (!rc && !typical) rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES);
-        if (!rc && !typical) rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
-        if (!rc && typical) rc = grow_buffer(c, BD_PART, sizeof(double) * N * TS_PART_ROW);
-        if (!rc && typical) rc = grow_buffer(c, BD_P, sizeof(float) * N * TS_ROW);
-        if (!rc && typical) rc = grow_buffer(c, BD_PW, sizeof(float) * N * TS_ROW);
-        if (!rc && typical) rc = grow_buffer(c, BD_KEY, sizeof(unsigned) * N * TS_ROW);
+        if (!rc && !sampled) rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES);
+        if (!rc && !sampled) rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
+        if (!rc && sampled) rc = grow_buffer(c, BD_PART, sizeof(double) * N * TS_PART_ROW);
+        if (!rc && sampled) rc = grow_buffer(c, BD_P, sizeof(float) * N * TS_ROW);
+        if (!rc && sampled) rc = grow_buffer(c, BD_PW, sizeof(float) * N * TS_ROW);
+        if (!rc && sampled) rc = grow_buffer(c, BD_KEY, sizeof(unsigned) * N * TS_ROW);
+        if (!rc && nucleus) rc = nucleus_counts(c, *np, 0, N, true);
         if (rc) return rc;
         unsigned long long *dseeds = c->buf<unsigned long long>(BD_IDS), *ids = dseeds + N;   // ids row k: the ids fed at step k
         c->bd_host.assign(N * (n_steps + 1), 0ull);
-        for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = typical ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
+        for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = sampled ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
         HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
         TypicalArgs ta{};
         if (typical) {
@@ -1655,12 +1736,22 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
             ta.part = c->buf<double>(BD_PART); ta.p = c->buf<float>(BD_P);
             ta.pw = c->buf<float>(BD_PW); ta.key = c->buf<unsigned>(BD_KEY);
         }
+        NucleusArgs na{};
+        if (nucleus) {
+            na = nucleus_args(c, *np, true);
+            na.row = 0; na.slot = 0; na.use_seed = 1; na.seeds = dseeds; na.feedback = 0;
+            na.part = c->buf<double>(BD_PART); na.p = c->buf<float>(BD_P);
+            na.pw = c->buf<float>(BD_PW); na.key = c->buf<unsigned>(BD_KEY);
+        }
         for (uint64_t k = 0; k < n_steps; k++) {
             if ((rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL))) return rc;       // logits rows 0 .. N - 1, state slots 0 .. N - 1
             unsigned long long *next = ids + (k + 1) * N;
             if (typical) {
                 ta.step = (int)k; ta.pick = next;
                 if ((rc = enqueue_typical(c, ta, (unsigned)N))) return rc;
+            } else if (nucleus) {
+                na.step = (int)k; na.pick = next;
+                if ((rc = enqueue_nucleus(c, na, (unsigned)N))) return rc;
             } else {
                 float *val = c->buf<float>(BD_VAL);
                 unsigned *idx = c->buf<unsigned>(BD_IDX);
@@ -1681,13 +1772,70 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
 
 int rwkv_decode_batch_greedy(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, false, 1.0f, 0.0f, nullptr, 0, out_tokens);
+    return decode_batch(c, first_tokens, n_streams, n_steps, Pick::GREEDY, 1.0f, 0.0f, nullptr, 0, nullptr, out_tokens);
 }
 
 int rwkv_decode_batch_typical(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, float temp, float tau,
                               const uint64_t *seeds, int flags, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, true, temp, tau, seeds, flags, out_tokens);
+    return decode_batch(c, first_tokens, n_streams, n_steps, Pick::TYPICAL, temp, tau, seeds, flags, nullptr, out_tokens);
+}
+
+int rwkv_sample_nucleus(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_nucleus_params *p, double u, uint64_t *token)
+{
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, p && token)) return rc;
+    if (row >= c->maxT || slot >= c->maxT)
+        return fail(RWKV_E_ARG, "logits row %llu or slot %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (const int rc = check_nucleus(p)) return rc;
+    if (!(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need 0 <= u < 1");
+    return finish(c, [&]() -> int {
+        if (const int rc = nucleus_counts(c, *p, slot, 1, false)) return rc;
+        NucleusArgs a = nucleus_args(c, *p, false);
+        a.row = (int)row; a.slot = (unsigned)slot; a.u = u;
+        if (const int rc = enqueue_nucleus(c, a, 1)) return rc;
+        HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+}
+
+int rwkv_decode_nucleus(rwkv_ctx *c, uint64_t first_token, uint64_t n, const rwkv_nucleus_params *p, uint64_t seed, uint64_t *out_tokens)
+{
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, p && out_tokens)) return rc;
+    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
+    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
+    if (const int rc = check_nucleus(p)) return rc;
+    return finish(c, enqueue_decode_nucleus(c, first_token, n, *p, seed, out_tokens));
+}
+
+int rwkv_decode_batch_nucleus(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_nucleus_params *p,
+                              const uint64_t *seeds, uint64_t *out_tokens)
+{
+    return decode_batch(c, first_tokens, n_streams, n_steps, Pick::NUCLEUS, 1.0f, 0.0f, seeds, 0, p, out_tokens);
+}
+
+int rwkv_penalty_set(rwkv_ctx *c, uint64_t slot, const float *counts)
+{
+    if (const int rc = guard(c, NEED_LOADED)) return rc;
+    if (slot >= c->maxT) return fail(RWKV_E_ARG, "slot %llu out of range (max context %llu)", (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (!counts && !c->grown[PEN_COUNTS].p) return 0;        // zero is what an unallocated buffer holds
+    return finish(c, [&]() -> int {
+        if (const int rc = counts_alloc(c)) return rc;
+        float *dst = c->buf<float>(PEN_COUNTS) + slot * RWKV_VOCAB;
+        if (counts) HIPCHK(hipMemcpyAsync(dst, counts, sizeof(float) * RWKV_VOCAB, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(hipMemsetAsync(dst, 0, sizeof(float) * RWKV_VOCAB, c->stream));
+        return 0;
+    }());
+}
+
+int rwkv_penalty_get(rwkv_ctx *c, uint64_t slot, float *counts)
+{
+    if (const int rc = guard(c, NEED_LOADED, counts)) return rc;
+    if (slot >= c->maxT) return fail(RWKV_E_ARG, "slot %llu out of range (max context %llu)", (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (!c->grown[PEN_COUNTS].p) { std::fill(counts, counts + RWKV_VOCAB, 0.f); return 0; }
+    return finish(c, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(counts, c->buf<float>(PEN_COUNTS) + slot * RWKV_VOCAB, sizeof(float) * RWKV_VOCAB, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
 }
 
 int rwkv_state_copy(rwkv_ctx *c, uint64_t dst, uint64_t src)

@@ -83,6 +83,19 @@ PYBIND11_MODULE(rwkv, m)
     m.def("setResident", [](std::uintptr_t h, bool on) { M(h)->residentState = on; }, "keep state on the device (engine extension)");
     m.def("decodeGreedy", [](std::uintptr_t h, int64_t first, int64_t n) { return M(h)->decodeGreedy(first, n); },
           "device-side greedy continuation (engine extension)");
+    m.def("nucleusSample", [](std::uintptr_t h, float temp, float top_p, unsigned top_k, float presence, float frequency, float decay, bool ban0) {
+        const double u = std::generate_canonical<double, 53>(rwkv_sampler_rng());
+        return M(h)->sampleNucleus(RWKV::Nucleus{temp, top_p, top_k, presence, frequency, decay}, u < 1.0 ? u : 0.0, ban0, true);
+    }, "draw the next token ON THE DEVICE from the logits of the last modelForward: temperature, top-p, top-k, presence / frequency penalties on the "
+       "context's decaying occurrence counts, which the pick updates (engine extension)",
+          py::arg("rwkvp"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u, py::arg("presence") = 0.f,
+          py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("ban0") = false);
+    m.def("decodeNucleus", [](std::uintptr_t h, int64_t first, int64_t n, float temp, float top_p, unsigned top_k, float presence, float frequency,
+                              float decay, uint64_t seed, bool keep) {
+        return M(h)->decodeNucleus(first, n, RWKV::Nucleus{temp, top_p, top_k, presence, frequency, decay}, seed, keep);
+    }, "device-side continuation with the nucleus sampler (engine extension)",
+          py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u,
+          py::arg("presence") = 0.f, py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("seed") = 0ull, py::arg("keep") = false);
     m.def("scoreTokens", [](std::uintptr_t h, const std::vector<int64_t> &tokens) {
         const RWKV::Scores s = M(h)->score(std::vector<unsigned long long>(tokens.begin(), tokens.end()));
         py::array_t<double> a(s.logprob.size());

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("RWKV_LIB") or os.path.join(_HERE, "csrc", "librwkv_mi
 
 MODE_PARRALEL, MODE_GPT = 0, 1   # reference enums/enum.h:2-5
 SAMPLE_BAN0, SAMPLE_RECIPE = 1, 2   # include/rwkv_mi355x.h
+NUCLEUS_BAN0, NUCLEUS_KEEP, NUCLEUS_UPDATE = 1, 2, 4
 N_KCLASS = 7
 ABI_VERSION = 6                   # RWKV_MI355X_ABI_VERSION of include/rwkv_mi355x.h
 KCLASS_NAMES = ["first", "att_kvr_wkv", "att_out", "ffn_rk", "ffn_v", "head", "argmax"]
@@ -32,10 +33,21 @@ ABI_SYMBOLS = [
     "rwkv_pipe_prefill", "rwkv_pipe_free", "rwkv_tensor_device", "rwkv_pipe_info", "rwkv_pipe_decode_dual",
     "rwkv_decode_batch_greedy", "rwkv_decode_batch_typical", "rwkv_state_copy",
     "rwkv_score_rows", "rwkv_score",
+    "rwkv_sample_nucleus", "rwkv_decode_nucleus", "rwkv_decode_batch_nucleus", "rwkv_penalty_set", "rwkv_penalty_get",
 ]
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 
 _lib = None
+
+
+class NucleusParams(C.Structure):
+    """rwkv_nucleus_params of include/rwkv_mi355x.h (32 bytes)"""
+    _fields_ = [("temp", C.c_float), ("top_p", C.c_float), ("top_k", C.c_uint32), ("presence", C.c_float), ("frequency", C.c_float),
+                ("decay", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def nucleus_params(temp=1.0, top_p=0.9, top_k=0, presence=0.0, frequency=0.0, decay=1.0, flags=0) -> NucleusParams:
+    return NucleusParams(float(temp), float(top_p), int(top_k), float(presence), float(frequency), float(decay), int(flags), 0)
 
 
 class RWKVError(RuntimeError):
@@ -107,6 +119,12 @@ def lib():
     for f in ("rwkv_score_rows", "rwkv_score"):
         getattr(L, f).argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
         getattr(L, f).restype = i32
+    npp = C.POINTER(NucleusParams)
+    L.rwkv_sample_nucleus.argtypes = [vp, u64, u64, npp, C.c_double, C.POINTER(u64)]; L.rwkv_sample_nucleus.restype = i32
+    L.rwkv_decode_nucleus.argtypes = [vp, u64, u64, npp, u64, C.POINTER(u64)]; L.rwkv_decode_nucleus.restype = i32
+    L.rwkv_decode_batch_nucleus.argtypes = [vp, C.POINTER(u64), u64, u64, npp, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_decode_batch_nucleus.restype = i32
+    L.rwkv_penalty_set.argtypes = [vp, u64, vp]; L.rwkv_penalty_set.restype = i32
+    L.rwkv_penalty_get.argtypes = [vp, u64, vp]; L.rwkv_penalty_get.restype = i32
     _lib = L
     return L
 
@@ -395,6 +413,53 @@ class RWKV:
         arr = (C.c_uint64 * max(1, len(sd)))(*sd)
         return self._decode_batch(first_tokens, n_steps, lambda ft, n, out: lib().rwkv_decode_batch_typical(
             self._h, ft, n, n_steps, float(temp), float(tau), arr, SAMPLE_RECIPE if recipe else 0, out))
+
+    # -- nucleus sampling with repetition penalties (include/rwkv_mi355x.h rwkv_sample_nucleus) --------
+    def sample_nucleus(self, temp: float = 1.0, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0, frequency: float = 0.0,
+                       decay: float = 1.0, u: float = 0.5, row: int = 0, slot: int = 0, ban0: bool = False, update: bool = False) -> int:
+        """temperature / top-p / top-k draw ON THE DEVICE from logits row `row` of the last forward, penalised by the occurrence counts of
+        state slot `slot`; u in [0, 1) is the caller's uniform; update=True counts the pick (counts * decay, then + 1)"""
+        tok = C.c_uint64(0)
+        p = nucleus_params(temp, top_p, top_k, presence, frequency, decay, (NUCLEUS_BAN0 if ban0 else 0) | (NUCLEUS_UPDATE if update else 0))
+        _chk(lib().rwkv_sample_nucleus(self._h, int(row), int(slot), C.byref(p), float(u), C.byref(tok)))
+        return int(tok.value)
+
+    def decode_nucleus(self, first_token: int, n_tokens: int, temp: float = 1.0, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
+                       frequency: float = 0.0, decay: float = 1.0, seed: int = 0, keep: bool = False) -> np.ndarray:
+        """device-side sampled continuation on slot 0 with the nucleus sampler (logit 0 banned, counts updated every step; keep=False
+        starts from zero counts)"""
+        out = (C.c_uint64 * n_tokens)()
+        p = nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_KEEP if keep else 0)
+        if not self.resident:
+            self.push_state(1)
+        _chk(lib().rwkv_decode_nucleus(self._h, int(first_token), n_tokens, C.byref(p), int(seed), out))
+        if not self.resident:
+            self.pull_state(1)
+        return np.frombuffer(out, dtype=np.uint64).copy()
+
+    def decode_batch_nucleus(self, first_tokens, n_steps: int, temp: float = 1.0, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
+                             frequency: float = 0.0, decay: float = 1.0, seeds=None, keep: bool = False) -> np.ndarray:
+        """the same for len(first_tokens) streams: stream s on slot s draws what decode_nucleus(seed=seeds[s]) draws (default seeds: 0 .. N - 1)"""
+        sd = list(range(len(first_tokens))) if seeds is None else [int(x) for x in seeds]
+        if len(sd) != len(first_tokens):
+            raise ValueError("need one seed per stream")
+        arr = (C.c_uint64 * max(1, len(sd)))(*sd)
+        p = nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_KEEP if keep else 0)
+        return self._decode_batch(first_tokens, n_steps, lambda ft, n, out: lib().rwkv_decode_batch_nucleus(
+            self._h, ft, n, n_steps, C.byref(p), arr, out))
+
+    def penalty_set(self, slot: int, counts=None):
+        """upload the occurrence counts of state slot `slot` (float32 [50277]; None: zero them)"""
+        a = None if counts is None else np.ascontiguousarray(counts, dtype=np.float32)
+        if a is not None and a.shape != (mf.VOCAB,):
+            raise ValueError(f"counts must have shape ({mf.VOCAB},)")
+        _chk(lib().rwkv_penalty_set(self._h, int(slot), _ptr(a)))
+
+    def penalty_get(self, slot: int) -> np.ndarray:
+        """the occurrence counts of state slot `slot` (float32 [50277])"""
+        out = np.zeros(mf.VOCAB, dtype=np.float32)
+        _chk(lib().rwkv_penalty_get(self._h, int(slot), _ptr(out)))
+        return out
 
     def copy_state(self, dst: int, src: int):
         """copy state slot src into slot dst (fork a prefilled prompt into the slots of a batched decode)"""

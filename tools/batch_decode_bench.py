@@ -9,6 +9,7 @@ Per N (synthetic weights, state slots 0 .. N - 1, maxGPT = the largest N):
                      the batched entry points has to do
   (c) batch_greedy   rwkv_decode_batch_greedy(N, steps): picks on the device, one upload and one download per call
   (d) batch_typical  rwkv_decode_batch_typical(N, steps), default mode and RWKV_SAMPLE_RECIPE
+  (e) batch_nucleus  rwkv_decode_batch_nucleus(N, steps): top_p 0.9 alone, and the full form (top_p 0.9, top_k 40, penalties 0.4 / 0.4, decay 0.996)
 ms per step and aggregate tokens/s (N / step time), one JSON line on stdout."""
 import argparse
 import ctypes as C
@@ -82,6 +83,9 @@ def main():
         r["batch_greedy"] = timed(lambda k: m.decode_batch_greedy(first, k), args.steps)
         r["batch_typical"] = timed(lambda k: m.decode_batch_typical(first, k, seeds=list(range(n))), args.steps)
         r["batch_typical_recipe"] = timed(lambda k: m.decode_batch_typical(first, k, seeds=list(range(n)), recipe=True), args.steps)
+        r["batch_nucleus"] = timed(lambda k: m.decode_batch_nucleus(first, k, temp=1.0, top_p=0.9, seeds=list(range(n))), args.steps)
+        r["batch_nucleus_full"] = timed(lambda k: m.decode_batch_nucleus(first, k, temp=1.0, top_p=0.9, top_k=40, presence=0.4, frequency=0.4,
+                                                                         decay=0.996, seeds=list(range(n))), args.steps)
         out = {k: dict(ms_per_step=round(v * 1e3, 3), aggregate_tokens_per_s=round(n / v, 1)) for k, v in r.items()}
         b = r["bare_step"]
         out["vs_bare_step"] = {k: round(v / b - 1.0, 4) for k, v in r.items() if k != "bare_step"}
