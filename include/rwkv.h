@@ -341,6 +341,44 @@ public:
         if (!residentState) pullState();
         return std::vector<unsigned long long>(ids.begin(), ids.end());
     }
+    // stop sequences and per-stream budgets in the device loops (rwkv_mi355x.h "stop sequences"): stream s ends at the first of `sequences`
+    // (token ids, each 1 .. 8 long) that its newest ids spell, or after max_new[s] tokens (empty: no budgets); keep: the match history and --
+    // for a nucleus pick with penalties -- the counts go on from the previous call.  Every slot is left as it was when its stream stopped:
+    // continue a stream by feeding ids[s * n + len[s] - 1].
+    struct Stop { std::vector<std::vector<unsigned long long>> sequences; std::vector<unsigned> max_new; bool keep = false; };
+    // how a step picks: Pick::greedy(), Pick::typical(temp, tau, recipe) or Pick::nucleus(s), as the three decodeBatch* calls do
+    struct Pick {
+        int kind = RWKV_PICK_GREEDY; float temp = 0.9f, tau = 0.8f; bool recipe = false; Nucleus s{};
+        static Pick greedy() { return Pick{}; }
+        static Pick typical(float temp = 0.9f, float tau = 0.8f, bool recipe = RWKV_TYPICAL_RECIPE != 0) { Pick p; p.kind = RWKV_PICK_TYPICAL; p.temp = temp; p.tau = tau; p.recipe = recipe; return p; }
+        static Pick nucleus(const Nucleus &s) { Pick p; p.kind = RWKV_PICK_NUCLEUS; p.s = s; return p; }
+    };
+    // ids[s * n + k] (0 behind a stream's end), len[s] tokens of stream s count, reason[s]: 0 ran all n, 1 budget, 2 + j sequence j;
+    // steps_run: the steps the device was given (rwkv_mi355x.h "bounded run-ahead")
+    struct Until { std::vector<unsigned long long> ids; std::vector<unsigned> len, reason; unsigned long long steps_run = 0; };
+    Until decodeBatchUntil(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                           const std::vector<unsigned long long> &seeds, const Stop &stop)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (pick.kind != RWKV_PICK_GREEDY && seeds.size() != first.size()) throw std::runtime_error("need one seed per stream");
+        if (!stop.max_new.empty() && stop.max_new.size() != first.size()) throw std::runtime_error("need one budget per stream");
+        std::vector<uint64_t> ft(first.begin(), first.end()), sd(seeds.begin(), seeds.end()), ids(first.size() * n), flat;
+        std::vector<uint32_t> lens, len(first.size()), reason(first.size());
+        for (const auto &q : stop.sequences) { lens.push_back((uint32_t)q.size()); flat.insert(flat.end(), q.begin(), q.end()); }
+        rwkv_pick p{};
+        p.kind = pick.kind; p.temp = pick.temp; p.tau = pick.tau; p.typical_flags = pick.recipe ? RWKV_SAMPLE_RECIPE : 0;
+        p.nucleus = nucleusParams(pick.s, stop.keep ? RWKV_NUCLEUS_KEEP : 0u);
+        const rwkv_stop_params sp{flat.data(), lens.data(), (uint32_t)lens.size(), stop.keep ? RWKV_STOP_KEEP : 0u,
+                                  stop.max_new.empty() ? nullptr : stop.max_new.data(), 0};
+        Until r;
+        uint64_t ran = 0;
+        if (!residentState) pushState();      // host state is authoritative: continue from it ...
+        rwkv_detail::check(rwkv_decode_batch_until(ctx_, ft.data(), ft.size(), n, &p, pick.kind == RWKV_PICK_GREEDY ? nullptr : sd.data(), &sp,
+                                                   ids.data(), len.data(), reason.data(), &ran));
+        if (!residentState) pullState();      // ... and leave every slot where its stream stopped
+        r.ids.assign(ids.begin(), ids.end()); r.len.assign(len.begin(), len.end()); r.reason.assign(reason.begin(), reason.end()); r.steps_run = ran;
+        return r;
+    }
     // the occurrence counts of one slot (50277 floats): save / restore a session, or upload a prompt's counts; empty = zero them
     void setPenaltyCounts(unsigned long long slot, const std::vector<float> &counts)
     {

@@ -208,6 +208,73 @@ int rwkv_decode_batch_nucleus(rwkv_ctx *ctx, const uint64_t *first_tokens, uint6
 int rwkv_penalty_set(rwkv_ctx *ctx, uint64_t slot, const float *counts /* host [50277]; NULL: zero */);
 int rwkv_penalty_get(rwkv_ctx *ctx, uint64_t slot, float *counts /* host [50277] */);
 
+/* ---- stop sequences and per-stream budgets in the device decode loops (no reference counterpart: its chat loops stop on the host) ----
+ * The three batch calls above run every stream for exactly n_steps tokens.  This one ends each stream where a serving caller wants it
+ * ended -- at a stop sequence ("\n\n", "Bob:", "User:": one to a few tokens) or at the stream's own token budget -- still without a host
+ * round trip per token, and leaves every stream in exactly the condition it had when it stopped.
+ *
+ * Picks.  Stream s runs on slot s and produces the picks g_0, g_1, ... of the matching rwkv_decode_batch_greedy / _typical / _nucleus
+ * call: the same kernels, the same seeds and u of step k, logit 0 always banned; n_streams == 1 runs the decode kernels, as there.
+ * Stopping.  After pick g_k stream s stops when some stop sequence j equals the newest seq_len[j] ids of its history ..., first_token,
+ * g_0 ... g_k, or when k + 1 == max_new[s].  A match ends at a generated token; it may begin in first_token or, with RWKV_STOP_KEEP, in
+ * earlier calls.  out_len[s] = k + 1.  out_reason[s]: 0 the stream ran all n_steps (a budget equal to n_steps is this case too), 1 it
+ * reached its budget, 2 + j it matched sequence j; of several matches at one step the lowest j wins, and a sequence wins over the budget.
+ * out_tokens[s][k] is 0 for k >= out_len[s].
+ * The invariant.  After the call slot s is bit for bit what the matching rwkv_decode_batch_* call with the same n_streams and
+ * n_steps = out_len[s] leaves for that slot: its five state arrays, its logits row s and, with penalties, its count vector.  Every
+ * returned token but the last has been fed, the last pick has not, and its count is in: a stopped stream is continued by feeding
+ * out_tokens[s][out_len[s] - 1].
+ * Match history.  The newest RWKV_STOP_MAX_LEN - 1 ids per slot live on the device, one 32-byte record per slot of max_ctx, allocated
+ * by the first call that can stop a stream.  Without RWKV_STOP_KEEP a call starts its slots' histories with first_tokens[s]; with it
+ * the history continues, unless its newest id is not first_tokens[s] (the caller fed something in between): then it restarts.  So a
+ * 16-step call gives exactly the ids, lengths, reasons and final slots of an 8-step call followed by an 8-step KEEP call, a sequence
+ * across the boundary included (with nucleus penalties the second call also takes RWKV_NUCLEUS_KEEP and seed + 8).
+ * How.  No decode kernel skips a stopped stream -- its row keeps running on its own picks -- so the step at which a stream stops copies
+ * its state, logits row and counts into a park buffer, and one launch behind the last step copies every parked stream back
+ * (csrc/stop.hip.h).  The park buffer belongs to the context like the other per-call buffers (grown, counted by rwkv_resident_bytes,
+ * freed with it): 5 L D f64 + 201 KB per stream, + 201 KB with penalties -- 5.4 MB per stream at 7B (L 32, D 4096), 5.6 MB with penalties.
+ * Only a call that can stop a stream (n_seqs > 0 or max_new != NULL) allocates it, launches anything extra -- two small launches per
+ * step -- or touches the histories; any other call is the plain loop.
+ * Bounded run-ahead.  The host never drains the stream inside the call.  After every block of RWKV_STOP_POLL steps it enqueues an
+ * 8-byte copy of the device's count of active streams into a pinned ring, and an event; before enqueuing block b >= 2 it waits for the
+ * event of block b - 2 and enqueues nothing more when that word is 0.  The device keeps 8 - 16 steps queued, and a call whose streams
+ * have all stopped wastes at most two blocks: *steps_run, the steps enqueued, is at most
+ * min(n_steps, RWKV_STOP_POLL * (floor((Lmax - 1) / RWKV_STOP_POLL) + 2)) with Lmax the largest out_len.  The results do not depend on it.
+ * Status: RWKV_E_ARG for what the batch calls reject, an unknown kind, a NULL pick, stop or out_len, n_seqs > RWKV_STOP_MAX_SEQS, n_seqs > 0
+ * with a NULL seq_ids or seq_len, a seq_len of 0 or above RWKV_STOP_MAX_LEN, a stop id >= 50277, a max_new of 0 or above n_steps, unknown
+ * flag bits or reserved != 0; RWKV_E_STATE as for the batch calls.  Every check runs before anything is launched or allocated: a rejected
+ * call leaves state, logits, counts and histories as they were.
+ * Out of scope: token 0 (<|endoftext|>) is never generated here and so stops nothing -- the greedy pick bans it inside the captured token
+ * graph, as every loop above does.
+ *
+ * rwkv_debug_stop_scan runs the stop test alone over PLANTED picks -- ids is host [n][steps], stream s on slot s and its history, no model
+ * step in between, state and logits untouched -- the way the sampler suites plant logits (tests/test_stop_gpu.py). */
+#define RWKV_STOP_MAX_SEQS 16u
+#define RWKV_STOP_MAX_LEN 8u
+#define RWKV_STOP_POLL 8u /* steps per block of the bounded run-ahead */
+#define RWKV_STOP_KEEP 1u /* continue the slots' match history from the previous call */
+enum rwkv_pick_kind { RWKV_PICK_GREEDY = 0, RWKV_PICK_TYPICAL = 1, RWKV_PICK_NUCLEUS = 2 };
+typedef struct rwkv_pick {
+    int kind;
+    float temp, tau;
+    int typical_flags;           /* TYPICAL: as rwkv_decode_batch_typical */
+    rwkv_nucleus_params nucleus; /* NUCLEUS: as rwkv_decode_batch_nucleus */
+} rwkv_pick;
+typedef struct rwkv_stop_params {
+    const uint64_t *seq_ids; /* host: the stop sequences, concatenated */
+    const uint32_t *seq_len; /* host [n_seqs], each 1 .. RWKV_STOP_MAX_LEN */
+    uint32_t n_seqs;         /* 0 .. RWKV_STOP_MAX_SEQS */
+    uint32_t flags;          /* RWKV_STOP_KEEP */
+    const uint32_t *max_new; /* host [n_streams], each 1 .. n_steps; NULL: n_steps for every stream */
+    uint64_t reserved;       /* must be 0 */
+} rwkv_stop_params;
+int rwkv_decode_batch_until(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                            const uint64_t *seeds /* NULL for greedy */, const rwkv_stop_params *stop,
+                            uint64_t *out_tokens /* [n_streams][n_steps] */, uint32_t *out_len /* [n_streams] */,
+                            uint32_t *out_reason /* [n_streams], may be NULL */, uint64_t *steps_run /* may be NULL */);
+int rwkv_debug_stop_scan(rwkv_ctx *ctx, const uint64_t *ids /* host [n][steps] */, const uint64_t *first_tokens, uint64_t n, uint64_t steps,
+                         const rwkv_stop_params *stop, uint32_t *out_len, uint32_t *out_reason);
+
 /* ---- scoring: how probable is a given token, on the device (no reference counterpart: the reference only generates) ----
  * What they replace is a download: rwkv_forward, rwkv_get_output of [n][50277] f32 logits (201 KB per position) and a log-softmax on
  * the host.  A query is (logits row r, target id g).  With l_i the f32 logits of row r widened to f64, M = max_i l_i, d_i = l_i - M

@@ -167,6 +167,33 @@ inline void nucleus_count(float *counts, int pick, float decay)
     counts[pick] += 1.0f;
 }
 
+// ---- stop sequences and budgets: the host twin of the scan the device decode loops make behind every pick (csrc/stop.hip.h; the semantics
+// are those of include/rwkv_mi355x.h rwkv_decode_batch_until) for ONE stream.  ids: the picks g_0 .. g_{n-1} of an n-step call fed `first`;
+// stops: the stop sequences (each 1 .. 8 ids); max_new: the budget (0: none; n is none too).  history: the stream's newest ids, oldest first,
+// as the previous call left them -- pass it again to continue (RWKV_STOP_KEEP: it goes on only if it ends in `first`), pass an empty one
+// to start with `first`; on return it ends with the last id scanned, at most 7 long.  len = ids counted up to and including the one that
+// stopped the stream (n when nothing did); reason 0 ran all n, 1 budget, 2 + j sequence j (the lowest j of several, a sequence before the budget).
+struct stop_result { unsigned len, reason; };
+inline stop_result stop_scan(const std::vector<unsigned long long> &ids, unsigned long long first,
+                             const std::vector<std::vector<unsigned long long>> &stops, unsigned max_new,
+                             std::vector<unsigned long long> &history)
+{
+    const size_t keep = 7;      // RWKV_STOP_MAX_LEN - 1: with the pick, the 8 ids the longest sequence covers
+    if (history.empty() || history.back() != first) history.assign(1, first);
+    for (size_t k = 0; k < ids.size(); k++) {
+        history.push_back(ids[k]);
+        unsigned reason = 0;
+        for (size_t j = 0; j < stops.size() && !reason; j++) {
+            const std::vector<unsigned long long> &q = stops[j];
+            if (!q.empty() && q.size() <= history.size() && std::equal(q.begin(), q.end(), history.end() - (std::ptrdiff_t)q.size())) reason = 2 + (unsigned)j;
+        }
+        if (!reason && max_new && k + 1 == max_new && k + 1 < ids.size()) reason = 1;
+        if (history.size() > keep) history.erase(history.begin(), history.end() - (std::ptrdiff_t)keep);
+        if (reason) return stop_result{(unsigned)(k + 1), reason};
+    }
+    return stop_result{(unsigned)ids.size(), 0u};
+}
+
 inline int typical(float *_logits, float _temp = 0.9, float _tau = 0.8)
 {
     const std::vector<double> probs = typical_weights(_logits, _temp, _tau);

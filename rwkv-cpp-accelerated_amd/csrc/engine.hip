@@ -10,6 +10,7 @@
 #include "sampler.hip.h"
 #include "nucleus.hip.h"
 #include "score.hip.h"
+#include "stop.hip.h"
 #include "../../include/rwkv_mi355x.h"
 
 #include <dlfcn.h>
@@ -220,6 +221,9 @@ enum GrownBuf {
     SC_PART,                          // f64 [queries of one launch sequence][SC_G][4] per-workgroup tuples
     SC_OUT,                           // [3][n]: logprob f64 | entropy f64 | argmax u64
     PEN_COUNTS,                       // f32 [max_ctx][V]: occurrence counts per state slot (nucleus.hip.h); allocated ONCE, zeroed, at the first call that needs them
+    STOP_RUN,                         // rwkv_decode_batch_until (stop.hip.h): u64 active | u64 first [n] | u32 len [n] | u32 reason [n] | u32 max_new [n]
+    STOP_PARK,                        // f32 [n][5 x 2 L D + PARK_ROW (+ PARK_ROW with penalties)]: what the streams held when they stopped
+    STOP_HISTORY,                     // u32 [max_ctx][STOP_HIST]: the newest ids per state slot; allocated ONCE, emptied, at the first call that can stop a stream
     N_GROWN
 };
 
@@ -322,6 +326,10 @@ struct rwkv_ctx {
     struct Grown { void *p = nullptr; size_t bytes = 0; } grown[N_GROWN];      // (enum GrownBuf)
     template <class T> T *buf(GrownBuf which) const { return static_cast<T *>(grown[which].p); }
     std::vector<unsigned long long> bd_host, sc_host;   // staging of a call's one upload and one download
+    static constexpr int STOP_RING = 4;           // rwkv_decode_batch_until: block b's count of active streams lands in word b % 4, read when block b + 2 is due
+    unsigned long long *stop_ring = nullptr;      // pinned
+    hipEvent_t stop_ev[STOP_RING] = {};
+    std::vector<unsigned> stop_host;              // host image of STOP_RUN: the call's upload, and the download of lengths and reasons
     std::vector<void *> allocs;
     size_t alloc_bytes = 0;                       // device bytes behind `allocs` and the Grown buffers (rwkv_resident_bytes)
 };
@@ -1552,19 +1560,57 @@ int enqueue_typical(rwkv_ctx *c, const TypicalArgs &a, unsigned rows)
     HIPCHK(hipGetLastError());
     return 0;
 }
-// The device decode loop: n tokens on slot 0, `first` and then each token's pick, and the download of the n picks.  The pick is the argmax
+// ---- stop sequences and budgets (stop.hip.h): what rwkv_decode_batch_until adds to the decode loops ----
+// One call's stopping, set up by stopper_setup (below decode_batch's checks).  The loops call after_step behind every step's pick and leave
+// when it says so; the caller ends with unpark.  The run-ahead is bounded, not drained: the active count of block b (RWKV_STOP_POLL steps)
+// travels into word b % STOP_RING of the pinned ring behind the block, and block b + 2 is enqueued only after that word has arrived non-zero.
+struct Stopper {
+    StopArgs a{};
+    ParkArgs p{};
+    uint64_t steps_run = 0;
+    // step k has been picked into picks[0 .. n); more: enqueue the next step
+    int after_step(rwkv_ctx *c, uint64_t k, const unsigned long long *picks, bool *more)
+    {
+        k_stop_step<<<dim3((a.n + STOP_NT - 1) / STOP_NT), dim3(STOP_NT), 0, c->stream>>>(a, picks, (unsigned)k);
+        k_stop_park<false><<<dim3(PARK_CHUNKS, a.n), dim3(PARK_NT), 0, c->stream>>>(p, (unsigned)k + 1);
+        HIPCHK(hipGetLastError());
+        steps_run = k + 1;
+        *more = true;
+        if (steps_run % RWKV_STOP_POLL) return 0;
+        const uint64_t b = steps_run / RWKV_STOP_POLL - 1;          // the block that ends here
+        HIPCHK(hipMemcpyAsync(&c->stop_ring[b % rwkv_ctx::STOP_RING], a.active, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipEventRecord(c->stop_ev[b % rwkv_ctx::STOP_RING], c->stream));
+        if (b >= 1) {                                               // block b + 1 >= 2 is next: it waits for block b - 1
+            HIPCHK(hipEventSynchronize(c->stop_ev[(b - 1) % rwkv_ctx::STOP_RING]));
+            *more = c->stop_ring[(b - 1) % rwkv_ctx::STOP_RING] != 0ull;
+        }
+        return 0;
+    }
+    // behind the last enqueued step: every stopped stream gets back what it held when it stopped
+    int unpark(rwkv_ctx *c)
+    {
+        k_stop_park<true><<<dim3(PARK_CHUNKS, a.n), dim3(PARK_NT), 0, c->stream>>>(p, 0u);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+};
+
+// The device decode loop: n tokens on slot 0, `first` and then each token's pick, and the download of the picks.  The pick is the argmax
 // node of the token graph, or (`typical`) the sampler's three launches behind the token graph without that node: u of step k from seed + k,
-// logit 0 banned, the id fed back through the control block.
-int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, bool typical, float temp, float tau, uint64_t seed, int flags, uint64_t *out_tokens)
+// logit 0 banned, the id fed back through the control block.  stop: the call can end early (the picks of the steps it ran are downloaded).
+int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, bool typical, float temp, float tau, uint64_t seed, int flags, uint64_t *out_tokens,
+                   Stopper *stop = nullptr)
 {
     TypicalArgs a = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
     a.row = -1; a.seed = seed; a.use_seed = 1; a.feedback = 1;
     if (const int rc = set_ctl(c, first, 0, 0)) return rc;
-    for (uint64_t i = 0; i < n; i++) {
+    bool more = true;
+    for (uint64_t i = 0; i < n && more; i++) {
         if (const int rc = run_token(c, !typical)) return rc;
         if (const int rc = typical ? enqueue_typical(c, a, 1) : 0) return rc;
+        if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
     }
-    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, (stop ? stop->steps_run : n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 
@@ -1627,17 +1673,20 @@ int enqueue_nucleus(rwkv_ctx *c, const NucleusArgs &a, unsigned rows)
     return 0;
 }
 // enqueue_decode with the nucleus sampler behind the token graph, on slot 0 and its counts
-int enqueue_decode_nucleus(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_nucleus_params &p, uint64_t seed, uint64_t *out_tokens)
+int enqueue_decode_nucleus(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_nucleus_params &p, uint64_t seed, uint64_t *out_tokens,
+                           Stopper *stop = nullptr)
 {
     if (const int rc = nucleus_counts(c, p, 0, 1, true)) return rc;
     NucleusArgs a = nucleus_args(c, p, true);
     a.row = -1; a.slot = 0; a.seed = seed; a.use_seed = 1; a.feedback = 1;
     if (const int rc = set_ctl(c, first, 0, 0)) return rc;
-    for (uint64_t i = 0; i < n; i++) {
+    bool more = true;
+    for (uint64_t i = 0; i < n && more; i++) {
         if (const int rc = run_token(c, false)) return rc;
         if (const int rc = enqueue_nucleus(c, a, 1)) return rc;
+        if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
     }
-    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, n * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, (stop ? stop->steps_run : n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 } // namespace
@@ -1696,12 +1745,81 @@ int grow_buffer(rwkv_ctx *c, GrownBuf which, size_t bytes)
     return 0;
 }
 
-// rwkv_decode_batch_greedy / _typical / _nucleus: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
+// ---- the host side of stopping (rwkv_decode_batch_until, rwkv_debug_stop_scan) ----
+static_assert(sizeof(rwkv_pick) == 48 && sizeof(rwkv_stop_params) == 40, "rwkv_pick is 48 bytes and rwkv_stop_params 40 in the C ABI");
+static_assert(STOP_MAX_SEQS == RWKV_STOP_MAX_SEQS && STOP_MAX_LEN == RWKV_STOP_MAX_LEN, "stop.hip.h holds the header's limits");
+// the stop parameters of a call over N streams and n_steps steps are acceptable; t: the sequences as the kernels read them (newest id first)
+int check_stop(const rwkv_stop_params *sp, uint64_t N, uint64_t n_steps, StopTable *t)
+{
+    if ((sp->flags & ~RWKV_STOP_KEEP) || sp->reserved) return fail(RWKV_E_ARG, "unknown stop flag bits (0x%x) or reserved != 0", sp->flags);
+    if (sp->n_seqs > RWKV_STOP_MAX_SEQS) return fail(RWKV_E_ARG, "at most %u stop sequences", RWKV_STOP_MAX_SEQS);
+    if (sp->n_seqs && (!sp->seq_ids || !sp->seq_len)) return fail(RWKV_E_ARG, "NULL argument");
+    t->n_seqs = sp->n_seqs;
+    const uint64_t *ids = sp->seq_ids;
+    for (uint32_t j = 0; j < sp->n_seqs; ids += sp->seq_len[j++]) {
+        const uint32_t len = sp->seq_len[j];
+        if (len == 0 || len > RWKV_STOP_MAX_LEN) return fail(RWKV_E_ARG, "stop sequence %u: length %u is not in 1..%u", j, len, RWKV_STOP_MAX_LEN);
+        if (const int rc = check_ids(ids, len, "stop")) return rc;
+        t->len[j] = len;
+        for (uint32_t i = 0; i < len; i++) t->ids[j][i] = (unsigned)ids[len - 1 - i];
+    }
+    for (uint64_t s = 0; sp->max_new && s < N; s++)
+        if (sp->max_new[s] == 0 || sp->max_new[s] > n_steps) return fail(RWKV_E_ARG, "max_new[%llu] = %u is not in 1..n_steps", (unsigned long long)s, sp->max_new[s]);
+    return 0;
+}
+
+// the buffers and the upload of one call's stopping: the run record (STOP_RUN), the histories (once), and -- `park`: a decode loop, not the
+// planted scan -- the park buffer, the poll ring and, with `penalty`, the count vectors that are parked with the state
+int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_params &sp, const uint64_t *first, uint64_t N, uint64_t n_steps,
+                  bool park, bool penalty)
+{
+    if (park && !c->stop_ring) {
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->stop_ring), sizeof(unsigned long long) * rwkv_ctx::STOP_RING, hipHostMallocDefault));
+        for (auto &e : c->stop_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    if (!c->grown[STOP_HISTORY].p) {
+        if (const int rc = grow_buffer(c, STOP_HISTORY, sizeof(unsigned) * c->maxT * STOP_HIST)) return rc;
+        HIPCHK(hipMemsetAsync(c->grown[STOP_HISTORY].p, 0xFF, sizeof(unsigned) * c->maxT * STOP_HIST, c->stream));      // STOP_NONE everywhere
+    }
+    if (const int rc = grow_buffer(c, STOP_RUN, sizeof(unsigned) * (5 * N + 2))) return rc;
+    const size_t LD = (size_t)c->L * c->D, stride = 10 * LD + PARK_ROW * (penalty ? 2 : 1);
+    if (const int rc = park ? grow_buffer(c, STOP_PARK, sizeof(float) * stride * N) : 0) return rc;
+    if (const int rc = park && penalty ? counts_alloc(c) : 0) return rc;
+    // host image of STOP_RUN: active | first [N] | len [N] = 0 | reason [N] = 0 | max_new [N]
+    c->stop_host.assign(5 * N + 2, 0u);
+    const unsigned long long active = N;
+    memcpy(&c->stop_host[0], &active, 8);
+    memcpy(&c->stop_host[2], first, 8 * N);
+    for (uint64_t s = 0; s < N; s++) c->stop_host[2 + 4 * N + s] = sp.max_new ? sp.max_new[s] : (unsigned)n_steps;
+    unsigned *run = c->buf<unsigned>(STOP_RUN);
+    HIPCHK(hipMemcpyAsync(run, c->stop_host.data(), sizeof(unsigned) * (5 * N + 2), hipMemcpyHostToDevice, c->stream));
+    st.a.t = t; st.a.n = (unsigned)N; st.a.n_steps = (unsigned)n_steps; st.a.keep = (sp.flags & RWKV_STOP_KEEP) ? 1 : 0;
+    st.a.hist = c->buf<unsigned>(STOP_HISTORY);
+    st.a.active = reinterpret_cast<unsigned long long *>(run);
+    st.a.first = st.a.active + 1;
+    st.a.len = run + 2 + 2 * N; st.a.reason = st.a.len + N; st.a.max_new = st.a.reason + N;
+    for (int i = 0; i < 5; i++) st.p.state[i] = c->state[i];
+    st.p.logits = c->logits; st.p.counts = penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
+    st.p.park = c->buf<float>(STOP_PARK); st.p.LD = LD; st.p.stride = stride; st.p.len = st.a.len;
+    return 0;
+}
+// behind the call's last launch: lengths and reasons come back into the host image
+int stopper_download(rwkv_ctx *c, const Stopper &st)
+{
+    HIPCHK(hipMemcpyAsync(&c->stop_host[2 + 2 * st.a.n], st.a.len, sizeof(unsigned) * 2 * st.a.n, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
+// what rwkv_decode_batch_until adds to a call of decode_batch
+struct Until { const rwkv_stop_params *stop; uint32_t *out_len, *out_reason; uint64_t *steps_run; };
+
+// rwkv_decode_batch_greedy / _typical / _nucleus / _until: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
 // else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
-// pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.
+// pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.  until: streams stop at sequences and budgets
+// (Stopper: two small launches behind each step's pick, one behind the last); a call that cannot stop a stream is the plain loop.
 enum class Pick { GREEDY, TYPICAL, NUCLEUS };      // how a step of the batched decode picks: k_argmax_rows, sampler.hip.h (temp, tau, flags), nucleus.hip.h (np)
 int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, Pick kind, float temp, float tau,
-                 const uint64_t *seeds, int flags, const rwkv_nucleus_params *np, uint64_t *out_tokens)
+                 const uint64_t *seeds, int flags, const rwkv_nucleus_params *np, uint64_t *out_tokens, const Until *until = nullptr)
 {
     const bool typical = kind == Pick::TYPICAL, nucleus = kind == Pick::NUCLEUS;
     const bool sampled = kind != Pick::GREEDY;     // the sampler's scratch per row, one seed per stream
@@ -1711,12 +1829,37 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
     if (const int rc = check_ids(first_tokens, N, "token")) return rc;
     if (typical && !(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
     if (const int rc = nucleus ? check_nucleus(np) : 0) return rc;
+    StopTable table{};
+    if (const int rc = until ? check_stop(until->stop, N, n_steps, &table) : 0) return rc;
     if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
-    if (nucleus && N == 1) return finish(c, enqueue_decode_nucleus(c, first_tokens[0], n_steps, *np, seeds[0], out_tokens));
-    if (N == 1)       // the decode path's kernels on slot 0
-        return finish(c, enqueue_decode(c, first_tokens[0], n_steps, typical, temp, tau, typical ? seeds[0] : 0, flags, out_tokens));
+    Stopper stopper, *st = until && (until->stop->n_seqs || until->stop->max_new) ? &stopper : nullptr;
+    auto stop_setup = [&]() { return st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, nucleus && nucleus_penalty(*np)) : 0; };
+    auto stop_end = [&]() { const int rc = st ? st->unpark(c) : 0; return rc || !st ? rc : stopper_download(c, *st); };
+    // lengths, reasons and the steps enqueued; the ids behind a stream's end are 0 (out_tokens holds the picks of the steps that ran)
+    auto until_results = [&]() {
+        const uint64_t ran = st ? st->steps_run : n_steps;
+        for (uint64_t s = 0; s < N; s++) {
+            const unsigned len = st ? c->stop_host[2 + 2 * N + s] : 0u, reason = st ? c->stop_host[2 + 3 * N + s] : 0u;
+            until->out_len[s] = len ? len : (uint32_t)n_steps;
+            if (until->out_reason) until->out_reason[s] = reason;
+            for (uint64_t k = until->out_len[s]; k < n_steps; k++) out_tokens[s * n_steps + k] = 0;
+        }
+        if (until->steps_run) *until->steps_run = ran;
+        return 0;
+    };
+    if (N == 1) {     // the decode path's kernels on slot 0
+        const int rc = finish(c, [&]() -> int {
+            if (const int rc = stop_setup()) return rc;
+            if (const int rc = nucleus ? enqueue_decode_nucleus(c, first_tokens[0], n_steps, *np, seeds[0], out_tokens, st)
+                                       : enqueue_decode(c, first_tokens[0], n_steps, typical, temp, tau, typical ? seeds[0] : 0, flags, out_tokens, st)) return rc;
+            return stop_end();
+        }());
+        return rc || !until ? rc : until_results();
+    }
+    uint64_t ran = n_steps;                             // steps enqueued
     const int rc = finish(c, [&]() -> int {
         int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * N * (n_steps + 2));
+        if (!rc) rc = stop_setup();
         if (!rc && !sampled) rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES);
         if (!rc && !sampled) rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
         if (!rc && sampled) rc = grow_buffer(c, BD_PART, sizeof(double) * N * TS_PART_ROW);
@@ -1759,14 +1902,18 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
                 k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
                 HIPCHK(hipGetLastError());
             }
+            bool more = true;
+            if ((rc = st ? st->after_step(c, k, next, &more) : 0)) return rc;
+            if (!more) break;
         }
-        HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * n_steps, hipMemcpyDeviceToHost, c->stream));
-        return 0;
+        if (st) ran = st->steps_run;
+        HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * ran, hipMemcpyDeviceToHost, c->stream));
+        return stop_end();
     }());
     if (rc) return rc;
-    for (uint64_t k = 0; k < n_steps; k++)              // [step][stream] -> [stream][step]
+    for (uint64_t k = 0; k < ran; k++)                  // [step][stream] -> [stream][step]
         for (uint64_t s = 0; s < N; s++) out_tokens[s * n_steps + k] = c->bd_host[k * N + s];
-    return 0;
+    return until ? until_results() : 0;
 }
 } // namespace
 
@@ -1811,6 +1958,53 @@ int rwkv_decode_batch_nucleus(rwkv_ctx *c, const uint64_t *first_tokens, uint64_
                               const uint64_t *seeds, uint64_t *out_tokens)
 {
     return decode_batch(c, first_tokens, n_streams, n_steps, Pick::NUCLEUS, 1.0f, 0.0f, seeds, 0, p, out_tokens);
+}
+
+int rwkv_decode_batch_until(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                            const uint64_t *seeds, const rwkv_stop_params *stop, uint64_t *out_tokens, uint32_t *out_len, uint32_t *out_reason,
+                            uint64_t *steps_run)
+{
+    if (const int rc = guard(c, NEED_WHOLE, pick && stop && out_len)) return rc;
+    const Until until{stop, out_len, out_reason, steps_run};
+    switch (pick->kind) {
+    case RWKV_PICK_GREEDY: return decode_batch(c, first_tokens, n_streams, n_steps, Pick::GREEDY, 1.0f, 0.0f, nullptr, 0, nullptr, out_tokens, &until);
+    case RWKV_PICK_TYPICAL: return decode_batch(c, first_tokens, n_streams, n_steps, Pick::TYPICAL, pick->temp, pick->tau, seeds, pick->typical_flags, nullptr, out_tokens, &until);
+    case RWKV_PICK_NUCLEUS: return decode_batch(c, first_tokens, n_streams, n_steps, Pick::NUCLEUS, 1.0f, 0.0f, seeds, 0, &pick->nucleus, out_tokens, &until);
+    default: return fail(RWKV_E_ARG, "unknown pick kind %d", pick->kind);
+    }
+}
+
+int rwkv_debug_stop_scan(rwkv_ctx *c, const uint64_t *ids, const uint64_t *first_tokens, uint64_t n, uint64_t steps, const rwkv_stop_params *stop,
+                         uint32_t *out_len, uint32_t *out_reason)
+{
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, ids && first_tokens && stop && out_len && out_reason)) return rc;
+    if (n == 0 || n > c->maxT) return fail(RWKV_E_ARG, "n must be in 1..%llu (max context)", (unsigned long long)c->maxT);
+    if (steps == 0 || steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
+    if (const int rc = check_ids(first_tokens, n, "token")) return rc;
+    if (const int rc = check_ids(ids, n * steps, "planted")) return rc;
+    StopTable table{};
+    if (const int rc = check_stop(stop, n, steps, &table)) return rc;
+    Stopper st;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * n * steps)) return rc;
+        if (const int rc = stopper_setup(c, st, table, *stop, first_tokens, n, steps, false, false)) return rc;
+        c->bd_host.resize(n * steps);
+        for (uint64_t k = 0; k < steps; k++)            // [stream][step] -> [step][stream], as the batched loop leaves its picks
+            for (uint64_t s = 0; s < n; s++) c->bd_host[k * n + s] = ids[s * steps + k];
+        unsigned long long *picks = c->buf<unsigned long long>(BD_IDS);
+        HIPCHK(hipMemcpyAsync(picks, c->bd_host.data(), sizeof(unsigned long long) * n * steps, hipMemcpyHostToDevice, c->stream));
+        for (uint64_t k = 0; k < steps; k++)
+            k_stop_step<<<dim3((unsigned)(n + STOP_NT - 1) / STOP_NT), dim3(STOP_NT), 0, c->stream>>>(st.a, picks + k * n, (unsigned)k);
+        HIPCHK(hipGetLastError());
+        return stopper_download(c, st);
+    }());
+    if (rc) return rc;
+    for (uint64_t s = 0; s < n; s++) {
+        const unsigned len = c->stop_host[2 + 2 * n + s];
+        out_len[s] = len ? len : (uint32_t)steps;
+        out_reason[s] = c->stop_host[2 + 3 * n + s];
+    }
+    return 0;
 }
 
 int rwkv_penalty_set(rwkv_ctx *c, uint64_t slot, const float *counts)
@@ -1973,6 +2167,8 @@ void rwkv_free(rwkv_ctx *c)
     for (auto &kv : c->sq_graphs) (void)hipGraphExecDestroy(kv.second);
     c->sq_graphs.clear();
     if (c->h_sq_tokens) (void)hipHostFree(c->h_sq_tokens);
+    if (c->stop_ring) (void)hipHostFree(c->stop_ring);
+    for (auto &e : c->stop_ev) if (e) (void)hipEventDestroy(e);
     for (int r = 0; r < SQ_RING; r++) if (c->sq_ev[r]) (void)hipEventDestroy(c->sq_ev[r]);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;

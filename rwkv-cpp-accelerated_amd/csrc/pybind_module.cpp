@@ -96,6 +96,20 @@ PYBIND11_MODULE(rwkv, m)
     }, "device-side continuation with the nucleus sampler (engine extension)",
           py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u,
           py::arg("presence") = 0.f, py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("seed") = 0ull, py::arg("keep") = false);
+    m.def("decodeUntil", [](std::uintptr_t h, int64_t first, int64_t n, float temp, float top_p, unsigned top_k, float presence, float frequency,
+                            float decay, uint64_t seed, bool keep, const std::vector<std::vector<int64_t>> &stops) {
+        RWKV::Stop stop;
+        for (const auto &q : stops) stop.sequences.emplace_back(q.begin(), q.end());
+        stop.keep = keep;
+        RWKV::Until r = M(h)->decodeBatchUntil({(unsigned long long)first}, n, RWKV::Pick::nucleus(RWKV::Nucleus{temp, top_p, top_k, presence, frequency, decay}),
+                                               {seed}, stop);
+        r.ids.resize(r.len[0]);
+        return std::make_tuple(std::vector<int64_t>(r.ids.begin(), r.ids.end()), (int)r.reason[0]);
+    }, "decodeNucleus that ends at the first of the stop sequences `stops` (lists of token ids): returns (ids up to and including the end of the "
+       "match, reason: 0 ran all n, 2 + j matched stops[j]); the state is left where the stream stopped -- feed ids[-1] to go on (engine extension)",
+          py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u,
+          py::arg("presence") = 0.f, py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("seed") = 0ull, py::arg("keep") = false,
+          py::arg("stops") = std::vector<std::vector<int64_t>>{});
     m.def("scoreTokens", [](std::uintptr_t h, const std::vector<int64_t> &tokens) {
         const RWKV::Scores s = M(h)->score(std::vector<unsigned long long>(tokens.begin(), tokens.end()));
         py::array_t<double> a(s.logprob.size());

@@ -19,6 +19,8 @@ LIB_PATH = os.environ.get("RWKV_LIB") or os.path.join(_HERE, "csrc", "librwkv_mi
 MODE_PARRALEL, MODE_GPT = 0, 1   # reference enums/enum.h:2-5
 SAMPLE_BAN0, SAMPLE_RECIPE = 1, 2   # include/rwkv_mi355x.h
 NUCLEUS_BAN0, NUCLEUS_KEEP, NUCLEUS_UPDATE = 1, 2, 4
+STOP_MAX_SEQS, STOP_MAX_LEN, STOP_POLL, STOP_KEEP = 16, 8, 8, 1
+PICK_GREEDY, PICK_TYPICAL, PICK_NUCLEUS = 0, 1, 2
 N_KCLASS = 7
 ABI_VERSION = 6                   # RWKV_MI355X_ABI_VERSION of include/rwkv_mi355x.h
 KCLASS_NAMES = ["first", "att_kvr_wkv", "att_out", "ffn_rk", "ffn_v", "head", "argmax"]
@@ -34,6 +36,7 @@ ABI_SYMBOLS = [
     "rwkv_decode_batch_greedy", "rwkv_decode_batch_typical", "rwkv_state_copy",
     "rwkv_score_rows", "rwkv_score",
     "rwkv_sample_nucleus", "rwkv_decode_nucleus", "rwkv_decode_batch_nucleus", "rwkv_penalty_set", "rwkv_penalty_get",
+    "rwkv_decode_batch_until", "rwkv_debug_stop_scan",
 ]
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 
@@ -48,6 +51,28 @@ class NucleusParams(C.Structure):
 
 def nucleus_params(temp=1.0, top_p=0.9, top_k=0, presence=0.0, frequency=0.0, decay=1.0, flags=0) -> NucleusParams:
     return NucleusParams(float(temp), float(top_p), int(top_k), float(presence), float(frequency), float(decay), int(flags), 0)
+
+
+class Pick(C.Structure):
+    """rwkv_pick of include/rwkv_mi355x.h (48 bytes)"""
+    _fields_ = [("kind", C.c_int), ("temp", C.c_float), ("tau", C.c_float), ("typical_flags", C.c_int), ("nucleus", NucleusParams)]
+
+
+class StopParams(C.Structure):
+    """rwkv_stop_params of include/rwkv_mi355x.h (40 bytes)"""
+    _fields_ = [("seq_ids", C.POINTER(C.c_uint64)), ("seq_len", C.POINTER(C.c_uint32)), ("n_seqs", C.c_uint32), ("flags", C.c_uint32),
+                ("max_new", C.POINTER(C.c_uint32)), ("reserved", C.c_uint64)]
+
+
+def stop_params(sequences=(), max_new=None, keep=False):
+    """(StopParams, the arrays it points into -- keep them alive for the call)"""
+    seqs = [[int(t) for t in q] for q in sequences]
+    flat = [t for q in seqs for t in q]
+    ids = (C.c_uint64 * max(1, len(flat)))(*flat)
+    lens = (C.c_uint32 * max(1, len(seqs)))(*[len(q) for q in seqs])
+    mx = None if max_new is None else (C.c_uint32 * max(1, len(max_new)))(*[int(v) for v in max_new])
+    sp = StopParams(ids if seqs else None, lens if seqs else None, len(seqs), STOP_KEEP if keep else 0, mx, 0)
+    return sp, (ids, lens, mx)
 
 
 class RWKVError(RuntimeError):
@@ -125,6 +150,11 @@ def lib():
     L.rwkv_decode_batch_nucleus.argtypes = [vp, C.POINTER(u64), u64, u64, npp, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_decode_batch_nucleus.restype = i32
     L.rwkv_penalty_set.argtypes = [vp, u64, vp]; L.rwkv_penalty_set.restype = i32
     L.rwkv_penalty_get.argtypes = [vp, u64, vp]; L.rwkv_penalty_get.restype = i32
+    L.rwkv_decode_batch_until.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(StopParams), C.POINTER(u64),
+                                          C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]
+    L.rwkv_decode_batch_until.restype = i32
+    L.rwkv_debug_stop_scan.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, u64, C.POINTER(StopParams), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+    L.rwkv_debug_stop_scan.restype = i32
     _lib = L
     return L
 
@@ -447,6 +477,43 @@ class RWKV:
         p = nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_KEEP if keep else 0)
         return self._decode_batch(first_tokens, n_steps, lambda ft, n, out: lib().rwkv_decode_batch_nucleus(
             self._h, ft, n, n_steps, C.byref(p), arr, out))
+
+    # -- stop sequences and per-stream budgets in the device loops (include/rwkv_mi355x.h rwkv_decode_batch_until) --------
+    def decode_batch_until(self, first_tokens, n_steps: int, stops=(), max_new=None, keep: bool = False, pick: str = "greedy", seeds=None,
+                           temp: float = 1.0, tau: float = 0.8, recipe: bool = False, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
+                           frequency: float = 0.0, decay: float = 1.0):
+        """decode_batch_greedy / _typical / _nucleus (pick = "greedy", "typical", "nucleus", with that call's parameters) in which stream s ends
+        at the first of the stop sequences `stops` (lists of token ids, each 1 .. 8 long) that its newest ids spell, or after max_new[s] tokens.
+        keep: the match history (and the nucleus counts) continue from the previous call.  Returns (ids [N][n_steps], 0 behind a stream's end;
+        len [N]; reason [N]: 0 ran all n_steps, 1 budget, 2 + j matched stops[j]; steps_run).  Slot s is left as it was when stream s stopped:
+        feed ids[s][len[s] - 1] to continue it."""
+        kind = {"greedy": PICK_GREEDY, "typical": PICK_TYPICAL, "nucleus": PICK_NUCLEUS}[pick]
+        n = len(first_tokens)
+        sd = list(range(n)) if seeds is None else [int(x) for x in seeds]
+        if len(sd) != n:
+            raise ValueError("need one seed per stream")
+        if max_new is not None and len(max_new) != n:
+            raise ValueError("need one budget per stream")
+        arr = (C.c_uint64 * max(1, n))(*sd)
+        pk = Pick(kind, float(temp), float(tau), SAMPLE_RECIPE if recipe else 0,
+                  nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_KEEP if keep else 0))
+        sp, alive = stop_params(stops, max_new, keep)
+        ln, rs, ran = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))(), C.c_uint64(0)
+        ids = self._decode_batch(first_tokens, n_steps, lambda ft, n_, out: lib().rwkv_decode_batch_until(
+            self._h, ft, n_, n_steps, C.byref(pk), None if kind == PICK_GREEDY else arr, C.byref(sp), out, ln, rs, C.byref(ran)))
+        del alive
+        return (ids, np.frombuffer(ln, dtype=np.uint32)[:n].astype(np.int64), np.frombuffer(rs, dtype=np.uint32)[:n].astype(np.int64), int(ran.value))
+
+    def debug_stop_scan(self, ids, first_tokens, stops=(), max_new=None, keep: bool = False):
+        """the stop test alone over PLANTED picks ids [n][steps] (rwkv_debug_stop_scan): (len [n], reason [n]); stream s uses slot s's history"""
+        a = np.ascontiguousarray(ids, dtype=np.uint64)
+        n, steps = a.shape
+        ft = (C.c_uint64 * max(1, n))(*[int(t) for t in first_tokens])
+        sp, alive = stop_params(stops, max_new, keep)
+        ln, rs = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))()
+        _chk(lib().rwkv_debug_stop_scan(self._h, a.ctypes.data_as(C.POINTER(C.c_uint64)), ft, n, steps, C.byref(sp), ln, rs))
+        del alive
+        return np.frombuffer(ln, dtype=np.uint32)[:n].astype(np.int64), np.frombuffer(rs, dtype=np.uint32)[:n].astype(np.int64)
 
     def penalty_set(self, slot: int, counts=None):
         """upload the occurrence counts of state slot `slot` (float32 [50277]; None: zero them)"""

@@ -10,7 +10,16 @@ Per N (synthetic weights, state slots 0 .. N - 1, maxGPT = the largest N):
   (c) batch_greedy   rwkv_decode_batch_greedy(N, steps): picks on the device, one upload and one download per call
   (d) batch_typical  rwkv_decode_batch_typical(N, steps), default mode and RWKV_SAMPLE_RECIPE
   (e) batch_nucleus  rwkv_decode_batch_nucleus(N, steps): top_p 0.9 alone, and the full form (top_p 0.9, top_k 40, penalties 0.4 / 0.4, decay 0.996)
-ms per step and aggregate tokens/s (N / step time), one JSON line on stdout."""
+ms per step and aggregate tokens/s (N / step time), one JSON line on stdout.
+
+    python tools/batch_decode_bench.py --until [--streams 1,32,96] [--steps 64] [--reps 5]
+
+What stopping costs (rwkv_decode_batch_until): per N, interleaved A / B over --reps rounds,
+  (A) plain          rwkv_decode_batch_nucleus(N, steps), the full form (N = 1: the decode kernels, as rwkv_decode_nucleus)
+  (B) until          the same picks through rwkv_decode_batch_until with a stop sequence that never matches and budgets equal to steps:
+                     the stop test and the park launch behind every step, the poll every 8 steps, nothing parked
+median and min .. max of ms per step of each, and the added microseconds per step; then one call of 4096 steps whose streams all stop at
+step 20 -- its steps_run and wall time -- next to the same 20 tokens made one call of one step at a time (the host's loop)."""
 import argparse
 import ctypes as C
 import json
@@ -27,13 +36,71 @@ import torch
 from rwkv_cpp_accelerated_amd import engine, modelfile as mf
 
 
+NUC = dict(temp=1.0, top_p=0.9, top_k=40, presence=0.4, frequency=0.4, decay=0.996)      # the full form of (e)
+
+
+def until_bench(m, args, ns, line):
+    V = mf.VOCAB
+    for n in ns:
+        first = [int(v) for v in np.random.default_rng(n).integers(1, V, n)]
+        seeds = list(range(n))
+        never = [[V - 1] * 8]                       # eight times the last id in a row: not what a synthetic model says
+
+        def plain(k):
+            return m.decode_batch_nucleus(first, k, seeds=seeds, **NUC)
+
+        def until(k, stops=never, max_new=None):
+            return m.decode_batch_until(first, k, stops=stops, max_new=[k] * n if max_new is None else max_new, pick="nucleus", seeds=seeds, **NUC)
+
+        def timed(fn, k):
+            m.reset_state()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            out = fn(k)
+            return (time.perf_counter() - t0) / k, out
+
+        for fn in (plain, until):                   # warm every shape of the timed window
+            fn(args.steps)
+        a, b = [], []
+        for _ in range(args.reps):
+            ta, ids_a = timed(plain, args.steps)
+            tb, (ids_b, ln, rs, ran) = timed(until, args.steps)
+            assert np.array_equal(ids_a, ids_b) and ran == args.steps and not rs.any(), "the never-matching sequence matched"
+            a.append(ta * 1e3); b.append(tb * 1e3)
+        long, stop_at = 4096, 20
+        until(long, stops=[], max_new=[stop_at] * n)
+        m.reset_state(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        ids, ln, rs, ran = until(long, stops=[], max_new=[stop_at] * n)
+        t_until = time.perf_counter() - t0
+        assert ln.tolist() == [stop_at] * n
+        m.reset_state(); torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        cur = list(first)
+        for k in range(stop_at):                    # the host's loop: one token per call, one round trip each
+            cur = [int(v) for v in m.decode_batch_nucleus(cur, 1, seeds=[s + k for s in seeds], keep=k > 0, **NUC)[:, 0]]
+        t_host = time.perf_counter() - t0
+        assert cur == [int(v) for v in ids[:, stop_at - 1]]
+        r = dict(plain_ms_per_step=dict(median=round(float(np.median(a)), 4), min=round(min(a), 4), max=round(max(a), 4)),
+                 until_ms_per_step=dict(median=round(float(np.median(b)), 4), min=round(min(b), 4), max=round(max(b), 4)),
+                 added_us_per_step=round((float(np.median(b)) - float(np.median(a))) * 1e3, 2),
+                 spread_us=round(max(max(a) - min(a), max(b) - min(b)) * 1e3, 2),
+                 stop_at_20_of_4096=dict(steps_run=int(ran), until_ms=round(t_until * 1e3, 3), host_one_token_per_call_ms=round(t_host * 1e3, 3)))
+        line["results"][str(n)] = r
+        print(f"[batch_decode_bench] until N={n}: {json.dumps(r)}", file=sys.stderr, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="7B")
-    ap.add_argument("--streams", default="32,64,96")
-    ap.add_argument("--steps", type=int, default=24)
+    ap.add_argument("--streams", default=None)
+    ap.add_argument("--steps", type=int, default=None)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--until", action="store_true", help="measure rwkv_decode_batch_until against the plain nucleus loop")
+    ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
+    args.streams = args.streams or ("1,32,96" if args.until else "32,64,96")
+    args.steps = args.steps or (64 if args.until else 24)
     ns = [int(x) for x in args.streams.split(",")]
     L, D = mf.SHAPES[args.model]
     lib = engine.lib()
@@ -50,6 +117,11 @@ def main():
         if rc != 0:
             raise RuntimeError(lib.rwkv_last_error().decode())
 
+    if args.until:
+        line["mode"] = "until"
+        line["reps"] = args.reps
+        until_bench(m, args, ns, line)
+        ns = []
     for n in ns:
         rng = np.random.default_rng(n)
         first = [int(v) for v in rng.integers(1, V, n)]
