@@ -1537,29 +1537,6 @@ int enqueue_reset(rwkv_ctx *c)
     return 0;
 }
 
-// the sampler's arguments common to every launch: mode and exponent from temp / flags, the context's single-row scratch
-TypicalArgs typical_args(rwkv_ctx *c, float temp, float tau, int flags)
-{
-    TypicalArgs a{};
-    // default: what typical.h computes -- no cut (typical.h:50 assigns into a temporary), integer exponent
-    // uint8(1/temp) (nc::power, typical.h:52); RWKV_SAMPLE_RECIPE: the documented recipe
-    a.recipe = (flags & RWKV_SAMPLE_RECIPE) ? 1 : 0;
-    if (a.recipe) a.expo = temp == 1.0f ? 1.0 : 1.0 / (double)temp;
-    else { const double e = 1.0 / (double)temp; a.expo = temp == 1.0f ? 1.0 : (e >= 255.0 ? 255.0 : (double)(unsigned char)e); }
-    a.logits = c->logits; a.ctl = c->ctl; a.gen = c->gen; a.gen_cap = c->gen_cap;
-    a.temp = temp; a.tau = tau; a.ban0 = (flags & RWKV_SAMPLE_BAN0) ? 1 : 0; a.step = -1; a.seeds = nullptr;
-    a.pick = c->pick; a.part = c->ts_part; a.p = c->ts_p; a.pw = c->ts_pw; a.key = c->ts_key;
-    return a;
-}
-// the sampler's three launches over `rows` logits rows (a.row onwards), each row with its own scratch slice and pick
-int enqueue_typical(rwkv_ctx *c, const TypicalArgs &a, unsigned rows)
-{
-    k_typical_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
-    k_typical_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
-    k_typical<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(a);
-    HIPCHK(hipGetLastError());
-    return 0;
-}
 // ---- stop sequences and budgets (stop.hip.h): what rwkv_decode_batch_until adds to the decode loops ----
 // One call's stopping, set up by stopper_setup (below decode_batch's checks).  The loops call after_step behind every step's pick and leave
 // when it says so; the caller ends with unpark.  The run-ahead is bounded, not drained: the active count of block b (RWKV_STOP_POLL steps)
@@ -1595,27 +1572,11 @@ struct Stopper {
     }
 };
 
-// The device decode loop: n tokens on slot 0, `first` and then each token's pick, and the download of the picks.  The pick is the argmax
-// node of the token graph, or (`typical`) the sampler's three launches behind the token graph without that node: u of step k from seed + k,
-// logit 0 banned, the id fed back through the control block.  stop: the call can end early (the picks of the steps it ran are downloaded).
-int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, bool typical, float temp, float tau, uint64_t seed, int flags, uint64_t *out_tokens,
-                   Stopper *stop = nullptr)
-{
-    TypicalArgs a = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
-    a.row = -1; a.seed = seed; a.use_seed = 1; a.feedback = 1;
-    if (const int rc = set_ctl(c, first, 0, 0)) return rc;
-    bool more = true;
-    for (uint64_t i = 0; i < n && more; i++) {
-        if (const int rc = run_token(c, !typical)) return rc;
-        if (const int rc = typical ? enqueue_typical(c, a, 1) : 0) return rc;
-        if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, (stop ? stop->steps_run : n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    return 0;
-}
-
-// ---- nucleus sampling (nucleus.hip.h) ----
+// ---- how a call picks its tokens: rwkv_pick, the C ABI's record, is the internal description too (sampler.hip.h, nucleus.hip.h) ----
 static_assert(sizeof(rwkv_nucleus_params) == 32, "rwkv_nucleus_params is 32 bytes in the C ABI");
+rwkv_pick pick_greedy() { rwkv_pick pk{}; pk.kind = RWKV_PICK_GREEDY; return pk; }
+rwkv_pick pick_typical(float temp, float tau, int flags) { rwkv_pick pk{}; pk.kind = RWKV_PICK_TYPICAL; pk.temp = temp; pk.tau = tau; pk.typical_flags = flags; return pk; }
+rwkv_pick pick_nucleus(const rwkv_nucleus_params &np) { rwkv_pick pk{}; pk.kind = RWKV_PICK_NUCLEUS; pk.nucleus = np; return pk; }
 constexpr uint32_t NUCLEUS_FLAGS = RWKV_NUCLEUS_BAN0 | RWKV_NUCLEUS_KEEP | RWKV_NUCLEUS_UPDATE;
 int check_nucleus(const rwkv_nucleus_params *p)
 {
@@ -1625,7 +1586,17 @@ int check_nucleus(const rwkv_nucleus_params *p)
     if ((p->flags & ~NUCLEUS_FLAGS) || p->reserved) return fail(RWKV_E_ARG, "unknown flag bits (0x%x) or reserved != 0", p->flags);
     return 0;
 }
-bool nucleus_penalty(const rwkv_nucleus_params &p) { return p.presence != 0.f || p.frequency != 0.f; }
+// the pick's own parameters are acceptable
+int check_pick(const rwkv_pick &pk)
+{
+    switch (pk.kind) {
+    case RWKV_PICK_GREEDY: return 0;
+    case RWKV_PICK_TYPICAL: return pk.temp > 0.f ? 0 : fail(RWKV_E_ARG, "need temp > 0");
+    case RWKV_PICK_NUCLEUS: return check_nucleus(&pk.nucleus);
+    default: return fail(RWKV_E_ARG, "unknown pick kind %d", pk.kind);
+    }
+}
+bool pick_penalty(const rwkv_pick &pk) { return pk.kind == RWKV_PICK_NUCLEUS && (pk.nucleus.presence != 0.f || pk.nucleus.frequency != 0.f); }
 // the count vectors (device [max_ctx][V] f32): allocated and zeroed once
 int counts_alloc(rwkv_ctx *c)
 {
@@ -1637,53 +1608,95 @@ int counts_alloc(rwkv_ctx *c)
     HIPCHK(hipMemsetAsync(q, 0, bytes, c->stream));
     return 0;
 }
-// what a call with these parameters needs of the counts of slots [slot0, slot0 + n): nothing without a penalty; else the buffer, and (`zero`: the
+// what a call with this pick needs of the counts of slots [slot0, slot0 + n): nothing without a penalty; else the buffer, and (`zero`: the
 // loops) those vectors cleared unless the caller keeps them
-int nucleus_counts(rwkv_ctx *c, const rwkv_nucleus_params &p, uint64_t slot0, uint64_t n, bool zero)
+int pick_counts(rwkv_ctx *c, const rwkv_pick &pk, uint64_t slot0, uint64_t n, bool zero)
 {
-    if (!nucleus_penalty(p)) return 0;
+    if (!pick_penalty(pk)) return 0;
     const bool fresh = !c->grown[PEN_COUNTS].p;
     if (const int rc = counts_alloc(c)) return rc;
-    if (zero && !fresh && !(p.flags & RWKV_NUCLEUS_KEEP))
+    if (zero && !fresh && !(pk.nucleus.flags & RWKV_NUCLEUS_KEEP))
         HIPCHK(hipMemsetAsync(c->buf<float>(PEN_COUNTS) + slot0 * RWKV_VOCAB, 0, sizeof(float) * n * RWKV_VOCAB, c->stream));
     return 0;
 }
-// the arguments common to every launch; `loop`: the decode loops always ban logit 0 and update the counts.  Call behind nucleus_counts.
-NucleusArgs nucleus_args(rwkv_ctx *c, const rwkv_nucleus_params &p, bool loop)
+
+// One call's sampler: the kind (RWKV_PICK_TYPICAL or _NUCLEUS) and that kind's kernel arguments
+struct Sampler {
+    int kind = RWKV_PICK_GREEDY;
+    TypicalArgs t{};
+    NucleusArgs n{};
+    DrawArgs &draw() { return kind == RWKV_PICK_NUCLEUS ? static_cast<DrawArgs &>(n) : t; }
+};
+// The sampler of a call that picks by `pk` (not greedy), on the context's single-row scratch.  `loop`: as the decode loop of one stream runs it
+// (logit 0 always banned, the counts always updated, row and step from the control block, u from seed + step, the pick fed back); else the
+// caller sets row and u.  Call behind pick_counts.
+Sampler make_sampler(rwkv_ctx *c, const rwkv_pick &pk, bool loop)
 {
-    NucleusArgs a{};
-    a.logits = c->logits; a.ctl = c->ctl; a.gen = c->gen; a.gen_cap = c->gen_cap;
-    a.inv_temp = p.temp == 1.0f ? 1.0 : 1.0 / (double)p.temp;
-    a.top_p = p.top_p; a.top_k = p.top_k >= RWKV_VOCAB ? 0u : p.top_k;
-    a.presence = p.presence; a.frequency = p.frequency; a.decay = p.decay;
-    a.penalty = nucleus_penalty(p) ? 1 : 0;
-    a.update = (loop || (p.flags & RWKV_NUCLEUS_UPDATE)) ? 1 : 0;
-    a.ban0 = (loop || (p.flags & RWKV_NUCLEUS_BAN0)) ? 1 : 0;
-    a.step = -1; a.seeds = nullptr;
-    a.counts = a.penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
-    a.pick = c->pick; a.part = c->ts_part; a.p = c->ts_p; a.pw = c->ts_pw; a.key = c->ts_key;
-    return a;
+    Sampler s;
+    s.kind = pk.kind;
+    DrawArgs &d = s.draw();
+    d.logits = c->logits; d.ctl = c->ctl; d.gen = c->gen; d.gen_cap = c->gen_cap;
+    d.step = -1; d.seeds = nullptr;
+    d.pick = c->pick; d.part = c->ts_part; d.p = c->ts_p; d.pw = c->ts_pw; d.key = c->ts_key;
+    if (loop) { d.row = -1; d.use_seed = 1; d.feedback = 1; }
+    if (pk.kind == RWKV_PICK_TYPICAL) {
+        // default: what typical.h computes -- no cut (typical.h:50 assigns into a temporary), integer exponent
+        // uint8(1/temp) (nc::power, typical.h:52); RWKV_SAMPLE_RECIPE: the documented recipe
+        s.t.recipe = (pk.typical_flags & RWKV_SAMPLE_RECIPE) ? 1 : 0;
+        if (s.t.recipe) s.t.expo = pk.temp == 1.0f ? 1.0 : 1.0 / (double)pk.temp;
+        else { const double e = 1.0 / (double)pk.temp; s.t.expo = pk.temp == 1.0f ? 1.0 : (e >= 255.0 ? 255.0 : (double)(unsigned char)e); }
+        s.t.tau = pk.tau;
+        d.ban0 = (loop || (pk.typical_flags & RWKV_SAMPLE_BAN0)) ? 1 : 0;
+    } else {
+        const rwkv_nucleus_params &p = pk.nucleus;
+        s.n.inv_temp = p.temp == 1.0f ? 1.0 : 1.0 / (double)p.temp;
+        s.n.top_p = p.top_p; s.n.top_k = p.top_k >= RWKV_VOCAB ? 0u : p.top_k;
+        s.n.presence = p.presence; s.n.frequency = p.frequency; s.n.decay = p.decay;
+        s.n.penalty = pick_penalty(pk) ? 1 : 0;
+        s.n.update = (loop || (p.flags & RWKV_NUCLEUS_UPDATE)) ? 1 : 0;
+        d.ban0 = (loop || (p.flags & RWKV_NUCLEUS_BAN0)) ? 1 : 0;
+        s.n.counts = s.n.penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
+    }
+    return s;
 }
-int enqueue_nucleus(rwkv_ctx *c, const NucleusArgs &a, unsigned rows)
+// the batched decode's form of it: rows 0 .. N - 1 (slots 0 .. N - 1) with a scratch slice and a seed each, the picks not fed back
+void sampler_to_batch(rwkv_ctx *c, Sampler &s, const unsigned long long *dseeds)
 {
-    k_nucleus_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
-    k_nucleus_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(a);
-    k_nucleus<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(a);
+    DrawArgs &d = s.draw();
+    d.row = 0; d.use_seed = 1; d.seeds = dseeds; d.feedback = 0;
+    d.part = c->buf<double>(BD_PART); d.p = c->buf<float>(BD_P);
+    d.pw = c->buf<float>(BD_PW); d.key = c->buf<unsigned>(BD_KEY);
+}
+// the sampler's three launches over `rows` logits rows (row onwards), each row with its own scratch slice and pick
+int enqueue_pick(rwkv_ctx *c, const Sampler &s, unsigned rows)
+{
+    if (s.kind == RWKV_PICK_NUCLEUS) {
+        k_nucleus_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.n);
+        k_nucleus_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.n);
+        k_nucleus<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(s.n);
+    } else {
+        k_typical_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.t);
+        k_typical_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.t);
+        k_typical<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(s.t);
+    }
     HIPCHK(hipGetLastError());
     return 0;
 }
-// enqueue_decode with the nucleus sampler behind the token graph, on slot 0 and its counts
-int enqueue_decode_nucleus(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_nucleus_params &p, uint64_t seed, uint64_t *out_tokens,
-                           Stopper *stop = nullptr)
+
+// The device decode loop: n tokens on slot 0 (and its counts), `first` and then each token's pick, and the download of the picks.  The pick is
+// the argmax node of the token graph, or (`pk` not greedy) the sampler's three launches behind the token graph without that node: u of step k from
+// seed + k, logit 0 banned, the id fed back through the control block.  stop: the call can end early (the picks of the steps it ran are downloaded).
+int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_pick &pk, uint64_t seed, uint64_t *out_tokens, Stopper *stop = nullptr)
 {
-    if (const int rc = nucleus_counts(c, p, 0, 1, true)) return rc;
-    NucleusArgs a = nucleus_args(c, p, true);
-    a.row = -1; a.slot = 0; a.seed = seed; a.use_seed = 1; a.feedback = 1;
+    const bool sampled = pk.kind != RWKV_PICK_GREEDY;
+    if (const int rc = pick_counts(c, pk, 0, 1, true)) return rc;
+    Sampler s;                    // greedy: no arguments are built
+    if (sampled) { s = make_sampler(c, pk, true); s.draw().seed = seed; }
     if (const int rc = set_ctl(c, first, 0, 0)) return rc;
     bool more = true;
     for (uint64_t i = 0; i < n && more; i++) {
-        if (const int rc = run_token(c, false)) return rc;
-        if (const int rc = enqueue_nucleus(c, a, 1)) return rc;
+        if (const int rc = run_token(c, !sampled)) return rc;
+        if (const int rc = sampled ? enqueue_pick(c, s, 1) : 0) return rc;
         if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
     }
     HIPCHK(hipMemcpyAsync(out_tokens, c->gen, (stop ? stop->steps_run : n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
@@ -1702,7 +1715,7 @@ int rwkv_decode_greedy(rwkv_ctx *c, uint64_t first_token, uint64_t n, uint64_t *
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, out_tokens)) return rc;
     if (const int rc = check_ids(&first_token, 1, "token")) return rc;
     if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    return finish(c, enqueue_decode(c, first_token, n, false, 1.0f, 0.0f, 0, 0, out_tokens));
+    return finish(c, enqueue_decode(c, first_token, n, pick_greedy(), 0, out_tokens));
 }
 
 int rwkv_sample_typical(rwkv_ctx *c, uint64_t row, float temp, float tau, double u, int flags, uint64_t *token)
@@ -1710,10 +1723,10 @@ int rwkv_sample_typical(rwkv_ctx *c, uint64_t row, float temp, float tau, double
     if (const int rc = guard(c, NEED_HEAD | LAUNCHES, token)) return rc;
     if (row >= c->maxT) return fail(RWKV_E_ARG, "logits row %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)c->maxT);
     if (!(temp > 0.f) || !(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need temp > 0 and 0 <= u < 1");
-    TypicalArgs a = typical_args(c, temp, tau, flags);
-    a.row = (int)row; a.u = u;
+    Sampler s = make_sampler(c, pick_typical(temp, tau, flags), false);
+    s.t.row = (int)row; s.t.u = u;
     return finish(c, [&]() -> int {
-        if (const int rc = enqueue_typical(c, a, 1)) return rc;
+        if (const int rc = enqueue_pick(c, s, 1)) return rc;
         HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         return 0;
     }());
@@ -1724,8 +1737,9 @@ int rwkv_decode_typical(rwkv_ctx *c, uint64_t first_token, uint64_t n, float tem
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, out_tokens)) return rc;
     if (const int rc = check_ids(&first_token, 1, "token")) return rc;
     if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    if (!(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
-    return finish(c, enqueue_decode(c, first_token, n, true, temp, tau, seed, flags, out_tokens));
+    const rwkv_pick pk = pick_typical(temp, tau, flags);
+    if (const int rc = check_pick(pk)) return rc;
+    return finish(c, enqueue_decode(c, first_token, n, pk, seed, out_tokens));
 }
 
 namespace {
@@ -1768,6 +1782,10 @@ int check_stop(const rwkv_stop_params *sp, uint64_t N, uint64_t n_steps, StopTab
     return 0;
 }
 
+// The run record of N streams (STOP_RUN on the device, stop_host its image), in 32-bit words: active (2) | first [N] (2 each) | len [N] | reason [N] |
+// max_new [N].  Where len starts (reason and max_new follow it at N and 2 N) and the record's size
+constexpr size_t stop_run_len(uint64_t N) { return 2 + 2 * N; }
+constexpr size_t stop_run_words(uint64_t N) { return stop_run_len(N) + 3 * N; }
 // the buffers and the upload of one call's stopping: the run record (STOP_RUN), the histories (once), and -- `park`: a decode loop, not the
 // planted scan -- the park buffer, the poll ring and, with `penalty`, the count vectors that are parked with the state
 int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_params &sp, const uint64_t *first, uint64_t N, uint64_t n_steps,
@@ -1781,23 +1799,23 @@ int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_
         if (const int rc = grow_buffer(c, STOP_HISTORY, sizeof(unsigned) * c->maxT * STOP_HIST)) return rc;
         HIPCHK(hipMemsetAsync(c->grown[STOP_HISTORY].p, 0xFF, sizeof(unsigned) * c->maxT * STOP_HIST, c->stream));      // STOP_NONE everywhere
     }
-    if (const int rc = grow_buffer(c, STOP_RUN, sizeof(unsigned) * (5 * N + 2))) return rc;
+    if (const int rc = grow_buffer(c, STOP_RUN, sizeof(unsigned) * stop_run_words(N))) return rc;
     const size_t LD = (size_t)c->L * c->D, stride = 10 * LD + PARK_ROW * (penalty ? 2 : 1);
     if (const int rc = park ? grow_buffer(c, STOP_PARK, sizeof(float) * stride * N) : 0) return rc;
     if (const int rc = park && penalty ? counts_alloc(c) : 0) return rc;
-    // host image of STOP_RUN: active | first [N] | len [N] = 0 | reason [N] = 0 | max_new [N]
-    c->stop_host.assign(5 * N + 2, 0u);
+    // host image of STOP_RUN (stop_run_len, stop_run_words): active | first [N] | len [N] = 0 | reason [N] = 0 | max_new [N]
+    c->stop_host.assign(stop_run_words(N), 0u);
     const unsigned long long active = N;
     memcpy(&c->stop_host[0], &active, 8);
     memcpy(&c->stop_host[2], first, 8 * N);
-    for (uint64_t s = 0; s < N; s++) c->stop_host[2 + 4 * N + s] = sp.max_new ? sp.max_new[s] : (unsigned)n_steps;
+    for (uint64_t s = 0; s < N; s++) c->stop_host[stop_run_len(N) + 2 * N + s] = sp.max_new ? sp.max_new[s] : (unsigned)n_steps;
     unsigned *run = c->buf<unsigned>(STOP_RUN);
-    HIPCHK(hipMemcpyAsync(run, c->stop_host.data(), sizeof(unsigned) * (5 * N + 2), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(run, c->stop_host.data(), sizeof(unsigned) * stop_run_words(N), hipMemcpyHostToDevice, c->stream));
     st.a.t = t; st.a.n = (unsigned)N; st.a.n_steps = (unsigned)n_steps; st.a.keep = (sp.flags & RWKV_STOP_KEEP) ? 1 : 0;
     st.a.hist = c->buf<unsigned>(STOP_HISTORY);
     st.a.active = reinterpret_cast<unsigned long long *>(run);
     st.a.first = st.a.active + 1;
-    st.a.len = run + 2 + 2 * N; st.a.reason = st.a.len + N; st.a.max_new = st.a.reason + N;
+    st.a.len = run + stop_run_len(N); st.a.reason = st.a.len + N; st.a.max_new = st.a.reason + N;
     for (int i = 0; i < 5; i++) st.p.state[i] = c->state[i];
     st.p.logits = c->logits; st.p.counts = penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
     st.p.park = c->buf<float>(STOP_PARK); st.p.LD = LD; st.p.stride = stride; st.p.len = st.a.len;
@@ -1806,8 +1824,18 @@ int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_
 // behind the call's last launch: lengths and reasons come back into the host image
 int stopper_download(rwkv_ctx *c, const Stopper &st)
 {
-    HIPCHK(hipMemcpyAsync(&c->stop_host[2 + 2 * st.a.n], st.a.len, sizeof(unsigned) * 2 * st.a.n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(&c->stop_host[stop_run_len(st.a.n)], st.a.len, sizeof(unsigned) * 2 * st.a.n, hipMemcpyDeviceToHost, c->stream));
     return 0;
+}
+// behind the wait: the call's lengths (a stream that never stopped: all n_steps) and reasons out of the host image; `stopped` false: the call
+// could stop no stream and has no image
+void stop_results(const rwkv_ctx *c, bool stopped, uint64_t N, uint64_t n_steps, uint32_t *out_len, uint32_t *out_reason)
+{
+    for (uint64_t s = 0; s < N; s++) {
+        const unsigned len = stopped ? c->stop_host[stop_run_len(N) + s] : 0u, reason = stopped ? c->stop_host[stop_run_len(N) + N + s] : 0u;
+        out_len[s] = len ? len : (uint32_t)n_steps;
+        if (out_reason) out_reason[s] = reason;
+    }
 }
 
 // what rwkv_decode_batch_until adds to a call of decode_batch
@@ -1817,41 +1845,35 @@ struct Until { const rwkv_stop_params *stop; uint32_t *out_len, *out_reason; uin
 // else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
 // pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.  until: streams stop at sequences and budgets
 // (Stopper: two small launches behind each step's pick, one behind the last); a call that cannot stop a stream is the plain loop.
-enum class Pick { GREEDY, TYPICAL, NUCLEUS };      // how a step of the batched decode picks: k_argmax_rows, sampler.hip.h (temp, tau, flags), nucleus.hip.h (np)
-int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, Pick kind, float temp, float tau,
-                 const uint64_t *seeds, int flags, const rwkv_nucleus_params *np, uint64_t *out_tokens, const Until *until = nullptr)
+// `pk`: how a step picks -- k_argmax_rows, or the sampler's three launches (one seed per stream, the sampler's scratch per row)
+int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, const rwkv_pick &pk, const uint64_t *seeds, uint64_t *out_tokens,
+                 const Until *until = nullptr)
 {
-    const bool typical = kind == Pick::TYPICAL, nucleus = kind == Pick::NUCLEUS;
-    const bool sampled = kind != Pick::GREEDY;     // the sampler's scratch per row, one seed per stream
-    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!sampled || seeds) && (!nucleus || np))) return rc;
+    const bool sampled = pk.kind != RWKV_PICK_GREEDY;
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!sampled || seeds))) return rc;
     if (N == 0 || N > c->maxT) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu (max context)", (unsigned long long)c->maxT);
     if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
     if (const int rc = check_ids(first_tokens, N, "token")) return rc;
-    if (typical && !(temp > 0.f)) return fail(RWKV_E_ARG, "need temp > 0");
-    if (const int rc = nucleus ? check_nucleus(np) : 0) return rc;
+    if (const int rc = check_pick(pk)) return rc;
     StopTable table{};
     if (const int rc = until ? check_stop(until->stop, N, n_steps, &table) : 0) return rc;
     if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
     Stopper stopper, *st = until && (until->stop->n_seqs || until->stop->max_new) ? &stopper : nullptr;
-    auto stop_setup = [&]() { return st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, nucleus && nucleus_penalty(*np)) : 0; };
+    auto stop_setup = [&]() { return st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, pick_penalty(pk)) : 0; };
     auto stop_end = [&]() { const int rc = st ? st->unpark(c) : 0; return rc || !st ? rc : stopper_download(c, *st); };
     // lengths, reasons and the steps enqueued; the ids behind a stream's end are 0 (out_tokens holds the picks of the steps that ran)
     auto until_results = [&]() {
         const uint64_t ran = st ? st->steps_run : n_steps;
-        for (uint64_t s = 0; s < N; s++) {
-            const unsigned len = st ? c->stop_host[2 + 2 * N + s] : 0u, reason = st ? c->stop_host[2 + 3 * N + s] : 0u;
-            until->out_len[s] = len ? len : (uint32_t)n_steps;
-            if (until->out_reason) until->out_reason[s] = reason;
+        stop_results(c, st != nullptr, N, n_steps, until->out_len, until->out_reason);
+        for (uint64_t s = 0; s < N; s++)
             for (uint64_t k = until->out_len[s]; k < n_steps; k++) out_tokens[s * n_steps + k] = 0;
-        }
         if (until->steps_run) *until->steps_run = ran;
         return 0;
     };
     if (N == 1) {     // the decode path's kernels on slot 0
         const int rc = finish(c, [&]() -> int {
             if (const int rc = stop_setup()) return rc;
-            if (const int rc = nucleus ? enqueue_decode_nucleus(c, first_tokens[0], n_steps, *np, seeds[0], out_tokens, st)
-                                       : enqueue_decode(c, first_tokens[0], n_steps, typical, temp, tau, typical ? seeds[0] : 0, flags, out_tokens, st)) return rc;
+            if (const int rc = enqueue_decode(c, first_tokens[0], n_steps, pk, sampled ? seeds[0] : 0, out_tokens, st)) return rc;
             return stop_end();
         }());
         return rc || !until ? rc : until_results();
@@ -1866,35 +1888,20 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
         if (!rc && sampled) rc = grow_buffer(c, BD_P, sizeof(float) * N * TS_ROW);
         if (!rc && sampled) rc = grow_buffer(c, BD_PW, sizeof(float) * N * TS_ROW);
         if (!rc && sampled) rc = grow_buffer(c, BD_KEY, sizeof(unsigned) * N * TS_ROW);
-        if (!rc && nucleus) rc = nucleus_counts(c, *np, 0, N, true);
+        if (!rc) rc = pick_counts(c, pk, 0, N, true);
         if (rc) return rc;
         unsigned long long *dseeds = c->buf<unsigned long long>(BD_IDS), *ids = dseeds + N;   // ids row k: the ids fed at step k
         c->bd_host.assign(N * (n_steps + 1), 0ull);
         for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = sampled ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
         HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
-        TypicalArgs ta{};
-        if (typical) {
-            ta = typical_args(c, temp, tau, flags | RWKV_SAMPLE_BAN0);
-            ta.row = 0; ta.use_seed = 1; ta.seeds = dseeds; ta.feedback = 0;
-            ta.part = c->buf<double>(BD_PART); ta.p = c->buf<float>(BD_P);
-            ta.pw = c->buf<float>(BD_PW); ta.key = c->buf<unsigned>(BD_KEY);
-        }
-        NucleusArgs na{};
-        if (nucleus) {
-            na = nucleus_args(c, *np, true);
-            na.row = 0; na.slot = 0; na.use_seed = 1; na.seeds = dseeds; na.feedback = 0;
-            na.part = c->buf<double>(BD_PART); na.p = c->buf<float>(BD_P);
-            na.pw = c->buf<float>(BD_PW); na.key = c->buf<unsigned>(BD_KEY);
-        }
+        Sampler smp;
+        if (sampled) { smp = make_sampler(c, pk, true); sampler_to_batch(c, smp, dseeds); }
         for (uint64_t k = 0; k < n_steps; k++) {
             if ((rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL))) return rc;       // logits rows 0 .. N - 1, state slots 0 .. N - 1
             unsigned long long *next = ids + (k + 1) * N;
-            if (typical) {
-                ta.step = (int)k; ta.pick = next;
-                if ((rc = enqueue_typical(c, ta, (unsigned)N))) return rc;
-            } else if (nucleus) {
-                na.step = (int)k; na.pick = next;
-                if ((rc = enqueue_nucleus(c, na, (unsigned)N))) return rc;
+            if (sampled) {
+                smp.draw().step = (int)k; smp.draw().pick = next;
+                if ((rc = enqueue_pick(c, smp, (unsigned)N))) return rc;
             } else {
                 float *val = c->buf<float>(BD_VAL);
                 unsigned *idx = c->buf<unsigned>(BD_IDX);
@@ -1919,13 +1926,13 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
 
 int rwkv_decode_batch_greedy(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, Pick::GREEDY, 1.0f, 0.0f, nullptr, 0, nullptr, out_tokens);
+    return decode_batch(c, first_tokens, n_streams, n_steps, pick_greedy(), nullptr, out_tokens);
 }
 
 int rwkv_decode_batch_typical(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, float temp, float tau,
                               const uint64_t *seeds, int flags, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, Pick::TYPICAL, temp, tau, seeds, flags, nullptr, out_tokens);
+    return decode_batch(c, first_tokens, n_streams, n_steps, pick_typical(temp, tau, flags), seeds, out_tokens);
 }
 
 int rwkv_sample_nucleus(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_nucleus_params *p, double u, uint64_t *token)
@@ -1933,13 +1940,14 @@ int rwkv_sample_nucleus(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_nuc
     if (const int rc = guard(c, NEED_HEAD | LAUNCHES, p && token)) return rc;
     if (row >= c->maxT || slot >= c->maxT)
         return fail(RWKV_E_ARG, "logits row %llu or slot %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)slot, (unsigned long long)c->maxT);
-    if (const int rc = check_nucleus(p)) return rc;
+    const rwkv_pick pk = pick_nucleus(*p);
+    if (const int rc = check_pick(pk)) return rc;
     if (!(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need 0 <= u < 1");
     return finish(c, [&]() -> int {
-        if (const int rc = nucleus_counts(c, *p, slot, 1, false)) return rc;
-        NucleusArgs a = nucleus_args(c, *p, false);
-        a.row = (int)row; a.slot = (unsigned)slot; a.u = u;
-        if (const int rc = enqueue_nucleus(c, a, 1)) return rc;
+        if (const int rc = pick_counts(c, pk, slot, 1, false)) return rc;
+        Sampler s = make_sampler(c, pk, false);
+        s.n.row = (int)row; s.n.slot = (unsigned)slot; s.n.u = u;
+        if (const int rc = enqueue_pick(c, s, 1)) return rc;
         HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
         return 0;
     }());
@@ -1950,14 +1958,16 @@ int rwkv_decode_nucleus(rwkv_ctx *c, uint64_t first_token, uint64_t n, const rwk
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, p && out_tokens)) return rc;
     if (const int rc = check_ids(&first_token, 1, "token")) return rc;
     if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    if (const int rc = check_nucleus(p)) return rc;
-    return finish(c, enqueue_decode_nucleus(c, first_token, n, *p, seed, out_tokens));
+    const rwkv_pick pk = pick_nucleus(*p);
+    if (const int rc = check_pick(pk)) return rc;
+    return finish(c, enqueue_decode(c, first_token, n, pk, seed, out_tokens));
 }
 
 int rwkv_decode_batch_nucleus(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_nucleus_params *p,
                               const uint64_t *seeds, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, Pick::NUCLEUS, 1.0f, 0.0f, seeds, 0, p, out_tokens);
+    if (const int rc = guard(c, 0, p)) return rc;
+    return decode_batch(c, first_tokens, n_streams, n_steps, pick_nucleus(*p), seeds, out_tokens);
 }
 
 int rwkv_decode_batch_until(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
@@ -1966,12 +1976,8 @@ int rwkv_decode_batch_until(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t 
 {
     if (const int rc = guard(c, NEED_WHOLE, pick && stop && out_len)) return rc;
     const Until until{stop, out_len, out_reason, steps_run};
-    switch (pick->kind) {
-    case RWKV_PICK_GREEDY: return decode_batch(c, first_tokens, n_streams, n_steps, Pick::GREEDY, 1.0f, 0.0f, nullptr, 0, nullptr, out_tokens, &until);
-    case RWKV_PICK_TYPICAL: return decode_batch(c, first_tokens, n_streams, n_steps, Pick::TYPICAL, pick->temp, pick->tau, seeds, pick->typical_flags, nullptr, out_tokens, &until);
-    case RWKV_PICK_NUCLEUS: return decode_batch(c, first_tokens, n_streams, n_steps, Pick::NUCLEUS, 1.0f, 0.0f, seeds, 0, &pick->nucleus, out_tokens, &until);
-    default: return fail(RWKV_E_ARG, "unknown pick kind %d", pick->kind);
-    }
+    if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);      // an unknown kind: in front of decode_batch's checks
+    return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until);
 }
 
 int rwkv_debug_stop_scan(rwkv_ctx *c, const uint64_t *ids, const uint64_t *first_tokens, uint64_t n, uint64_t steps, const rwkv_stop_params *stop,
@@ -1999,11 +2005,7 @@ int rwkv_debug_stop_scan(rwkv_ctx *c, const uint64_t *ids, const uint64_t *first
         return stopper_download(c, st);
     }());
     if (rc) return rc;
-    for (uint64_t s = 0; s < n; s++) {
-        const unsigned len = c->stop_host[2 + 2 * n + s];
-        out_len[s] = len ? len : (uint32_t)steps;
-        out_reason[s] = c->stop_host[2 + 3 * n + s];
-    }
+    stop_results(c, true, n, steps, out_len, out_reason);
     return 0;
 }
 

@@ -1,7 +1,8 @@
 // nucleus.hip.h -- temperature / top-p / top-k sampling with presence and frequency penalties over the 50277 logits ON THE DEVICE
-// (gfx950): what the front ends of RWKV-4 models sample with, in the shape of the typical sampler (sampler.hip.h), whose helpers it uses
-// unchanged.  No reference counterpart (the reference ships typical() only).  include/rwkv_mi355x.h rwkv_sample_nucleus has the semantics;
-// include/rwkv_sampler.h nucleus_u is the same draw on the host.  For one logits row l and the f32 occurrence counts c of one state slot:
+// (gfx950): what the front ends of RWKV-4 models sample with, in the shape of the typical sampler (sampler.hip.h), with which it shares
+// the draw record (DrawArgs: row, uniform, pick, scratch) and the helpers on it (ts_row, ts_combine, ts_pad, ts_uniform, ts_emit) as well
+// as the block scan.  No reference counterpart (the reference ships typical() only).  include/rwkv_mi355x.h rwkv_sample_nucleus has the
+// semantics; include/rwkv_sampler.h nucleus_u is the same draw on the host.  For one logits row l and the f32 occurrence counts c of one state slot:
 //     l'_i = l_i - (presence + c_i frequency) where c_i > 0, l_i otherwise (f64); with the ban l'_0 = -99 afterwards
 //     p = softmax(l');  kept = { p_i >= the p where the descending running mass reaches top_p }  and  { p_i >= the top_k-th largest p }
 //     weight exp((l'_i - max l') / temp) on the kept set;  inverse CDF in token order;  c <- f32(c decay), c_pick += 1
@@ -24,35 +25,17 @@ static_assert(TS_PER % NU_GROUP == 0, "a thread's tokens are whole groups");
 constexpr int NU_LDS_BYTES = TS_NT * 8 + TS_HIST * 8 + TS_HIST * 4;      // scan, mass bins, count bins of k_nucleus (56 KiB)
 static_assert(NU_LDS_BYTES + 64 <= 64 * 1024, "k_nucleus keeps its two histograms in static LDS");
 
-struct NucleusArgs {
-    const float *logits;          // [rows][V]
-    int row;                      // logits row of blockIdx.y = 0 (< 0: ctl->out_row)
+struct NucleusArgs : DrawArgs {
     unsigned slot;                // count vector of blockIdx.y = 0
-    Ctl *ctl;
-    unsigned long long *gen;      // generated ids, gen[step] (feedback)
-    unsigned gen_cap;
     double inv_temp;              // 1 / temp (exactly 1 for temp == 1)
     float top_p;
     unsigned top_k;               // 0: off (the host maps top_k >= V to 0)
     float presence, frequency, decay;
     int penalty;                  // presence != 0 || frequency != 0: `counts` is read (and, with `update`, written)
     int update;                   // after the pick: counts <- f32(counts decay), counts[pick] += 1
-    int ban0;
-    double u;                     // uniform in [0, 1) when use_seed == 0
-    unsigned long long seed;      // else u = uniform(splitmix64(seed + step))
-    const unsigned long long *seeds;   // per-row seeds (device, [rows]); nullptr: `seed` for every row
-    int step;                     // the step of the draw; < 0: ctl->step
-    int use_seed;
-    int feedback;                 // write the pick into ctl->token and advance ctl->step
-    unsigned long long *pick;     // [rows]
     float *counts;                // [max_ctx][V] occurrence counts per state slot (nullptr without penalty)
-    double *part;                 // [rows][TS_G][3] per-workgroup (max, sum exp(l' - max), unused)
-    float *p;                     // [rows][TS_NT * TS_PER] probabilities, k_typical's layout
-    unsigned *key;                // same layout: bit patterns of -log p
-    float *pw;                    // same layout: exp((l' - M) / temp)
 };
 
-__device__ __forceinline__ const float *nu_row(const NucleusArgs &a) { return a.logits + (size_t)((a.row >= 0 ? (unsigned)a.row : a.ctl->out_row) + blockIdx.y) * VOCAB; }
 __device__ __forceinline__ float *nu_counts(const NucleusArgs &a) { return a.counts + (size_t)(a.slot + blockIdx.y) * VOCAB; }
 // the penalised logit: every factor is an f32 widened to f64 (c frequency is exact there), the ban behind the penalty
 __device__ __forceinline__ double nu_logit(const NucleusArgs &a, const float *lg, const float *cnt, int i)
@@ -72,7 +55,7 @@ __global__ __launch_bounds__(TS_GT) void k_nucleus_stats(NucleusArgs a)
     __shared__ double red[RED_BYTES / 8];
     const int V = (int)VOCAB;
     const int i0 = block_lo(V), i1 = block_hi(V);
-    const float *lg = nu_row(a);
+    const float *lg = ts_row(a);
     const float *cnt = a.penalty ? nu_counts(a) : nullptr;
     double mx = -INFINITY;
     for (int i = i0 + threadIdx.x; i < i1; i += TS_GT) mx = fmax(mx, nu_logit(a, lg, cnt, i));
@@ -90,7 +73,7 @@ __global__ __launch_bounds__(TS_GT) void k_nucleus_stats(NucleusArgs a)
     if (threadIdx.x == 0) {
         double tz = 0.0;
         for (int k = 0; k < TS_GT / 64; k++) tz += red[k];
-        double *part = a.part + blockIdx.y * TS_PART_ROW;
+        double *part = ts_part(a);
         part[blockIdx.x * 3 + 0] = mx; part[blockIdx.x * 3 + 1] = tz; part[blockIdx.x * 3 + 2] = 0.0;
     }
 }
@@ -100,17 +83,10 @@ __global__ __launch_bounds__(TS_GT) void k_nucleus_keys(NucleusArgs a)
 {
     const int V = (int)VOCAB;
     const int i0 = block_lo(V), i1 = block_hi(V);
-    const float *lg = nu_row(a);
+    const float *lg = ts_row(a);
     const float *cnt = a.penalty ? nu_counts(a) : nullptr;
-    double M, logZ;
-    {   // combine the partials (one lane per partial): M = max l', Z = sum exp(l' - M) >= 1
-        const int lane = threadIdx.x & 63;
-        const double *part = a.part + blockIdx.y * TS_PART_ROW;
-        const double m = lane < TS_G ? part[lane * 3] : -INFINITY, z = lane < TS_G ? part[lane * 3 + 1] : 0.0;
-        double mm = m;
-        for (int off = 32; off >= 1; off >>= 1) mm = fmax(mm, __shfl_xor(mm, off, 64));
-        M = mm; logZ = log(wave_sum(lane < TS_G ? exp(m - mm) * z : 0.0));
-    }
+    double M, logZ, H;
+    ts_combine(a, M, logZ, H);      // M = max l', Z = sum exp(l' - M) >= 1; H is not used (the partials carry 0 in the third word)
     for (int i = i0 + threadIdx.x; i < i1; i += TS_GT) {
         const double d = nu_logit(a, lg, cnt, i) - M;                       // <= 0, and 0 for the largest logit
         const double nl = logZ - d;                                         // -log p_i >= 0
@@ -119,11 +95,7 @@ __global__ __launch_bounds__(TS_GT) void k_nucleus_keys(NucleusArgs a)
         a.pw[pos] = (float)exp(d * a.inv_temp);                             // exactly 1 for the largest logit
         a.key[pos] = __float_as_uint((float)nl);
     }
-    if (blockIdx.x == 0)       // padding positions: no mass, no weight, the largest key; k_nucleus does not count them
-        for (int i = V + threadIdx.x; i < TS_NT * TS_PER; i += TS_GT) {
-            const size_t pos = ts_off((i % TS_PER) * TS_NT + i / TS_PER);
-            a.p[pos] = 0.f; a.pw[pos] = 0.f; a.key[pos] = 0x7f800000u;
-        }
+    if (blockIdx.x == 0) ts_pad(a);       // k_nucleus does not count the padding positions
 }
 
 // (3) both thresholds by one radix select, the draw, the count update.  Thread t owns tokens [50 t, 50 t + 50), its k-th at position
@@ -255,17 +227,7 @@ __global__ __launch_bounds__(TS_NT) void k_nucleus(NucleusArgs a)
     }
     ts_block_scan(wsum, scan);
     const double total = scan[TS_NT - 1], before = scan[t] - wsum;
-    double u = a.u;
-    if (a.use_seed) {
-        const unsigned long long seed = a.seeds ? a.seeds[blockIdx.y] : a.seed;
-        const unsigned long long step = a.step >= 0 ? (unsigned long long)a.step : (unsigned long long)a.ctl->step;
-        unsigned long long x = seed + step + 0x9E3779B97F4A7C15ull;   // splitmix64
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        x ^= x >> 31;
-        u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
-    }
-    const double target = u * total;
+    const double target = ts_uniform(a) * total;
     if (t == 0) { pick_s = 0xffffffffu; last_s = 0u; }
     __syncthreads();
     if (wsum > 0.0 && target >= before && target < before + wsum) {       // the owner of the target
@@ -309,15 +271,7 @@ __global__ __launch_bounds__(TS_NT) void k_nucleus(NucleusArgs a)
             }
         } else if (t == 0) cnt[sel] = __fadd_rn(cnt[sel], 1.0f);
     }
-    if (t == 0) {
-        if (a.pick) a.pick[blockIdx.y] = sel;
-        if (a.feedback) {
-            const unsigned st = a.ctl->step;
-            if (st < a.gen_cap) a.gen[st] = sel;
-            a.ctl->token = sel;
-            a.ctl->step = st + 1;
-        }
-    }
+    if (t == 0) ts_emit(a, sel);
 }
 
 } // namespace rwkvk

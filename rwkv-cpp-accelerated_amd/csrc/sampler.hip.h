@@ -31,34 +31,70 @@ constexpr size_t TS_PART_ROW = (size_t)TS_G * 3;           // doubles of `part` 
 constexpr size_t TS_ROW = (size_t)TS_NT * TS_PER;          // elements of `p` / `key` / `pw` per row
 constexpr double TS_RESCALE = 0x1p-60;     // a total of the relative weights below this: form them again relative to the kept maximum (k_typical)
 
-struct TypicalArgs {
+// What every sampler's draw needs, whichever way the weights are formed: the row, the uniform, where the pick goes, the per-row scratch.
+// TypicalArgs (below) and NucleusArgs (nucleus.hip.h) embed it and add what is their own.
+struct DrawArgs {
     const float *logits;          // [rows][V]
     int row;                      // logits row of blockIdx.y = 0 (< 0: ctl->out_row); blockIdx.y = r samples the row r behind it
     Ctl *ctl;                     // token / step feedback (device-side generation loop)
-    unsigned long long *gen;      // generated ids, gen[step]
+    unsigned long long *gen;      // generated ids, gen[step] (feedback)
     unsigned gen_cap;
-    float temp, tau;
-    int recipe;                   // 1: the recipe typical.h documents (cut at tau, p^(1/temp)); 0: what it computes (no cut, p^uint8(1/temp))
-    double expo;                  // the exponent applied to p
+    int ban0;                     // logits[0] = -99 before sampling (storygen.cpp:66)
+    int feedback;                 // write the pick into ctl->token and advance ctl->step
+    unsigned long long *pick;     // [rows] the sampled ids (nullptr: none)
     double u;                     // uniform in [0, 1) when use_seed == 0
     unsigned long long seed;      // else u = uniform(splitmix64(seed + step))
     const unsigned long long *seeds;   // per-row seeds (device, [rows]); nullptr: `seed` for every row
     int step;                     // the step of the draw; < 0: ctl->step
     int use_seed;
-    int ban0;                     // logits[0] = -99 before sampling (storygen.cpp:66)
-    int feedback;                 // write the pick into ctl->token and advance ctl->step
-    unsigned long long *pick;     // [rows] the sampled ids (nullptr: none)
-    double *part;                 // [rows][TS_G][3] per-workgroup (max, sum exp(l - max), sum exp(l - max) (l - max))
+    double *part;                 // [rows][TS_G][3] per-workgroup (max, sum exp(l - max), sum exp(l - max) (l - max)); nucleus: l' for l, 0 in the third word
     float *p;                     // [rows][TS_NT * TS_PER] probabilities, position (i % TS_PER) * TS_NT + i / TS_PER for token i
-    unsigned *key;                // same layout: bit patterns of |-log p - H|
-    float *pw;                    // same layout: (p / p_max)^expo, the weight of typical.h:49-52 relative to the largest one; k_typical zeroes the tokens that are cut
+    unsigned *key;                // same layout: bit patterns of |-log p - H| (typical), of -log p (nucleus)
+    float *pw;                    // same layout: (p / p_max)^expo, the weight of typical.h:49-52 relative to the largest one; k_typical zeroes the tokens that are cut.  Nucleus: exp((l' - M) / temp)
 };
 
-__device__ __forceinline__ const float *ts_row(const TypicalArgs &a) { return a.logits + (size_t)((a.row >= 0 ? (unsigned)a.row : a.ctl->out_row) + blockIdx.y) * VOCAB; }
+struct TypicalArgs : DrawArgs {
+    float tau;
+    int recipe;                   // 1: the recipe typical.h documents (cut at tau, p^(1/temp)); 0: what it computes (no cut, p^uint8(1/temp))
+    double expo;                  // the exponent applied to p
+};
+
+__device__ __forceinline__ const float *ts_row(const DrawArgs &a) { return a.logits + (size_t)((a.row >= 0 ? (unsigned)a.row : a.ctl->out_row) + blockIdx.y) * VOCAB; }
 // this row's slices of the scratch arrays
-__device__ __forceinline__ double *ts_part(const TypicalArgs &a) { return a.part + blockIdx.y * TS_PART_ROW; }
+__device__ __forceinline__ double *ts_part(const DrawArgs &a) { return a.part + blockIdx.y * TS_PART_ROW; }
 __device__ __forceinline__ size_t ts_off(int pos) { return blockIdx.y * TS_ROW + (size_t)pos; }
-__device__ __forceinline__ float ts_logit(const TypicalArgs &a, const float *lg, int i) { return (a.ban0 && i == 0) ? -99.0f : lg[i]; }
+__device__ __forceinline__ float ts_logit(const DrawArgs &a, const float *lg, int i) { return (a.ban0 && i == 0) ? -99.0f : lg[i]; }
+// the padding positions: tokens V .. TS_NT * TS_PER - 1 carry no mass, no weight and the largest key (one workgroup of TS_GT threads per row)
+__device__ __forceinline__ void ts_pad(const DrawArgs &a)
+{
+    for (int i = (int)VOCAB + threadIdx.x; i < TS_NT * TS_PER; i += TS_GT) {
+        const size_t pos = ts_off((i % TS_PER) * TS_NT + i / TS_PER);
+        a.p[pos] = 0.f; a.pw[pos] = 0.f; a.key[pos] = 0x7f800000u;
+    }
+}
+// the uniform of this row and step: the caller's, or from (seed, step) -- include/rwkv_sampler.h has the same draw on the host
+__device__ __forceinline__ double ts_uniform(const DrawArgs &a)
+{
+    if (!a.use_seed) return a.u;
+    const unsigned long long seed = a.seeds ? a.seeds[blockIdx.y] : a.seed;
+    const unsigned long long step = a.step >= 0 ? (unsigned long long)a.step : (unsigned long long)a.ctl->step;
+    unsigned long long x = seed + step + 0x9E3779B97F4A7C15ull;   // splitmix64
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
+}
+// (one thread per row) the pick of this row goes out, and with `feedback` into the device-side generation loop
+__device__ __forceinline__ void ts_emit(const DrawArgs &a, unsigned sel)
+{
+    if (a.pick) a.pick[blockIdx.y] = sel;
+    if (a.feedback) {
+        const unsigned st = a.ctl->step;
+        if (st < a.gen_cap) a.gen[st] = sel;
+        a.ctl->token = sel;
+        a.ctl->step = st + 1;
+    }
+}
 
 // (1) per-workgroup online-softmax partials over a slice of the vocabulary
 __global__ __launch_bounds__(TS_GT) void k_typical_stats(TypicalArgs a)
@@ -97,7 +133,7 @@ __global__ __launch_bounds__(TS_GT) void k_typical_stats(TypicalArgs a)
 }
 
 // combine the partials: M = max, Z = sum exp(l - M), H = entropy = log Z - sum p (l - M)   (typical.h:29-31)
-__device__ __forceinline__ void ts_combine(const TypicalArgs &a, double &M, double &logZ, double &H)
+__device__ __forceinline__ void ts_combine(const DrawArgs &a, double &M, double &logZ, double &H)
 {
     const int lane = threadIdx.x & 63;
     const double *part = ts_part(a);
@@ -129,11 +165,7 @@ __global__ __launch_bounds__(TS_GT) void k_typical_keys(TypicalArgs a)
         a.pw[pos] = it == 0.0 ? 1.0f : (float)exp(d * it);
         a.key[pos] = __float_as_uint((float)fabs(nl - H));                  // typical.h:32
     }
-    if (blockIdx.x == 0)       // padding positions: tokens V .. TS_NT * TS_PER - 1 carry no mass and the largest key
-        for (int i = V + threadIdx.x; i < TS_NT * TS_PER; i += TS_GT) {
-            const size_t pos = ts_off((i % TS_PER) * TS_NT + i / TS_PER);
-            a.p[pos] = 0.f; a.pw[pos] = 0.f; a.key[pos] = 0x7f800000u;
-        }
+    if (blockIdx.x == 0) ts_pad(a);
 }
 
 __device__ __forceinline__ double ts_block_sum(double v, double *red)
@@ -275,17 +307,7 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         ts_block_scan(wsum, scan);
     }
     const double total = scan[TS_NT - 1], before = scan[t] - wsum;
-    double u = a.u;
-    if (a.use_seed) {
-        const unsigned long long seed = a.seeds ? a.seeds[blockIdx.y] : a.seed;
-        const unsigned long long step = a.step >= 0 ? (unsigned long long)a.step : (unsigned long long)a.ctl->step;
-        unsigned long long x = seed + step + 0x9E3779B97F4A7C15ull;   // splitmix64
-        x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-        x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-        x ^= x >> 31;
-        u = (double)(x >> 11) * (1.0 / 9007199254740992.0);
-    }
-    const double target = u * total;
+    const double target = ts_uniform(a) * total;
     if (t == 0) { pick_s = 0xffffffffu; last_s = 0u; }
     __syncthreads();
     // the owner of the target: before <= target < before + wsum
@@ -316,13 +338,7 @@ __global__ __launch_bounds__(TS_NT) void k_typical(TypicalArgs a)
         if (sel == 0xffffffffu) {                  // the kept set is empty (total == 0 or NaN: logits that are no numbers); an underflow of the weights does not come here
             sel = 0;
         }
-        if (a.pick) a.pick[blockIdx.y] = sel;
-        if (a.feedback) {
-            const unsigned st = a.ctl->step;
-            if (st < a.gen_cap) a.gen[st] = sel;
-            a.ctl->token = sel;
-            a.ctl->step = st + 1;
-        }
+        ts_emit(a, sel);
     }
 }
 

@@ -5,7 +5,7 @@ tests/test_sampler_cases_gpu.py (the kernels).  TEST INFRASTRUCTURE: nothing her
 THE REFERENCE (`reference`) evaluates typical_weights / typical_u of include/rwkv_sampler.h in log space, so that it has no underflow
 of its own: log p_i = l_i - M - log Z; the entropy over the terms with p_i > 0; the key |-log p_i - H|; the kept set as typical_weights
 defines it (stable order of keys, smallest prefix whose mass reaches tau, every token with key <= the cutoff key; default mode keeps
-everything); log-weights expo * log p_i on the kept set with expo as typical_args of csrc/engine.hip derives it (temp == 1 -> 1, default
+everything); log-weights expo * log p_i on the kept set with expo as make_sampler of csrc/engine.hip derives it (temp == 1 -> 1, default
 mode n = uint8(1 / temp) clamped at 255, n = 0 -> every weight 1); weights exp(lw - max lw); inverse CDF in token order.
 
 WHEN A DRAW IS EXCUSED (`Ref.excused`, from the reference alone).  A STEP is a point of [0, 1) where the reference's pick changes: the
@@ -52,7 +52,7 @@ EDGE_IDS = (0, 1, 49, 50, 51, V - 1)   # first / last token, both sides of the f
 
 
 def expo_of(temp, recipe):
-    """typical_args (csrc/engine.hip): the exponent applied to p"""
+    """make_sampler (csrc/engine.hip): the exponent applied to p"""
     t = np.float32(temp)
     if t == np.float32(1.0):
         return 1.0
