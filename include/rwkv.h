@@ -359,6 +359,48 @@ public:
     Until decodeBatchUntil(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
                            const std::vector<unsigned long long> &seeds, const Stop &stop)
     {
+        return until_call(first, n, pick, seeds, stop, nullptr);
+    }
+    // log-probs and top-n alternatives of the generated tokens (rwkv_mi355x.h "log-probs and top-n"): decodeBatchUntil that also returns, per
+    // stream and step, the log-prob of the pick under the MODEL's distribution (no penalty, no temperature, nothing banned), that row's entropy
+    // (entropy = false: left empty) and its top_n most probable ids with their log-probs; 0 / 0.0 behind a stream's end.  Shapes: logprob and
+    // entropy [s * n + k], top_ids and top_logprob [(s * n + k) * top_n + j].  Best-of-n ranks forks by the sum of logprob over a stream's len.
+    struct Logprobs { Until until; std::vector<double> logprob, entropy; std::vector<unsigned long long> top_ids; std::vector<double> top_logprob; unsigned top_n = 0; };
+    Logprobs decodeBatchLogprobs(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                                 const std::vector<unsigned long long> &seeds, const Stop &stop, unsigned top_n, bool entropy = true)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (top_n > RWKV_MAX_TOPN) throw std::runtime_error("top_n above RWKV_MAX_TOPN");
+        Logprobs r;
+        const size_t e = first.size() * n;
+        r.top_n = top_n;
+        r.logprob.resize(e);
+        if (entropy) r.entropy.resize(e);
+        std::vector<uint64_t> tid(e * top_n);
+        r.top_logprob.resize(e * top_n);
+        const rwkv_logprob_out lp{top_n, 0u, r.logprob.data(), entropy ? r.entropy.data() : nullptr, top_n ? tid.data() : nullptr,
+                                  top_n ? r.top_logprob.data() : nullptr};
+        r.until = until_call(first, n, pick, seeds, stop, &lp);
+        r.top_ids.assign(tid.begin(), tid.end());
+        return r;
+    }
+    // the top_n most probable ids of logits rows of the last forward, with their log-probs: ids and logprob [i * top_n + j]; logits and state stay
+    struct TopN { std::vector<unsigned long long> ids; std::vector<double> logprob; };
+    TopN topnRows(const std::vector<unsigned long long> &rows, unsigned top_n)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> r(rows.begin(), rows.end()), ids(rows.size() * top_n);
+        TopN t;
+        t.logprob.resize(rows.size() * top_n);
+        rwkv_detail::check(rwkv_topn_rows(ctx_, r.data(), r.size(), top_n, ids.data(), t.logprob.data()));
+        t.ids.assign(ids.begin(), ids.end());
+        return t;
+    }
+private:
+    // decodeBatchUntil, and with `lp` decodeBatchLogprobs: one preparation of the C ABI's records, one push / pull of host-authoritative state
+    Until until_call(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                     const std::vector<unsigned long long> &seeds, const Stop &stop, const rwkv_logprob_out *lp)
+    {
         if (!ready) throw std::runtime_error("RWKV not loaded");
         if (pick.kind != RWKV_PICK_GREEDY && seeds.size() != first.size()) throw std::runtime_error("need one seed per stream");
         if (!stop.max_new.empty() && stop.max_new.size() != first.size()) throw std::runtime_error("need one budget per stream");
@@ -373,12 +415,14 @@ public:
         Until r;
         uint64_t ran = 0;
         if (!residentState) pushState();      // host state is authoritative: continue from it ...
-        rwkv_detail::check(rwkv_decode_batch_until(ctx_, ft.data(), ft.size(), n, &p, pick.kind == RWKV_PICK_GREEDY ? nullptr : sd.data(), &sp,
-                                                   ids.data(), len.data(), reason.data(), &ran));
+        const uint64_t *sdp = pick.kind == RWKV_PICK_GREEDY ? nullptr : sd.data();
+        rwkv_detail::check(lp ? rwkv_decode_batch_logprobs(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
+                              : rwkv_decode_batch_until(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, ids.data(), len.data(), reason.data(), &ran));
         if (!residentState) pullState();      // ... and leave every slot where its stream stopped
         r.ids.assign(ids.begin(), ids.end()); r.len.assign(len.begin(), len.end()); r.reason.assign(reason.begin(), reason.end()); r.steps_run = ran;
         return r;
     }
+public:
     // the occurrence counts of one slot (50277 floats): save / restore a session, or upload a prompt's counts; empty = zero them
     void setPenaltyCounts(unsigned long long slot, const std::vector<float> &counts)
     {

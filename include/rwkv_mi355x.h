@@ -311,6 +311,55 @@ int rwkv_score_rows(rwkv_ctx *ctx, const uint64_t *rows, const uint64_t *targets
 int rwkv_score(rwkv_ctx *ctx, const uint64_t *tokens, const uint64_t *targets, uint64_t n_tokens,
                double *logprob, double *entropy, uint64_t *argmax);
 
+/* ---- log-probs and top-n alternatives of generated tokens, on the device (no reference counterpart: the reference only generates) ----
+ * What a completion server reports as `logprobs` / `top_logprobs`, and what best-of-n ranks by: what the MODEL thought of a token.  For one f32
+ * logits row l (widened to f64), M, Z, logprob_i = (l_i - M) - log Z and the entropy are exactly those of the scoring block above: nothing is
+ * banned, no penalty, no temperature -- whichever pick generated the token (greedy with logit 0 banned, typical, nucleus with penalties).  What
+ * is reported is the model's distribution, not the sampler's; log-probabilities under the penalised or tempered distribution are out of scope.
+ * The top-n of a row: the n ids with the largest f32 logits, in descending logit order, equal logits by ascending id, each with its logprob.
+ * Id 0 can appear, as in scoring.  A -inf logit can appear once fewer than n finite ones exist, with logprob -inf.  With NaN or +inf logits
+ * the result is unspecified, but every id is below 50277 and nothing faults.
+ * One definition on the device (csrc/topn.hip.h calls the score kernels' own slice tuple and fold): the logprob of an id of the top-n, the
+ * logprob of a pick and rwkv_score_rows of the same row and id are bitwise equal.  Held to ids equal and |d logprob| <= 1e-10 against numpy
+ * f64 on planted rows by tests/test_logprobs_gpu.py.
+ *
+ * rwkv_topn_rows: the top-n of n logits rows the LAST forward left, as rwkv_score_rows reads them (rows need not be consecutive, ascending or
+ * distinct).  ids and logprob are host arrays [n][top_n].  One upload of rows, one launch sequence (two launches), one download; synchronous;
+ * works on any context with a head; leaves logits and state alone.  n in 1 .. RWKV_MAX_SCORE, top_n in 1 .. RWKV_MAX_TOPN.
+ *
+ * rwkv_decode_batch_logprobs is rwkv_decode_batch_until with one more hook: the same picks, kernels, seeds, lengths, reasons and final slots as
+ * that call with the same arguments -- or, when stop is NULL or cannot stop a stream, as the matching plain batch call (out_len, which may
+ * then be NULL, is n_steps everywhere); n_streams == 1 runs the decode kernels, as there.  Behind step k's pick and in front of the stop test,
+ * two launches over rows 0 .. n_streams - 1 read the logits rows and the picks the step just wrote and write step k of a record on the device,
+ * nothing else: state, logits rows, counts and histories after the call are bit for bit those of the call without it.  lp->logprob[s][k] is the
+ * logprob of pick g_k of stream s under the row it was picked from, lp->entropy[s][k] that row's entropy, lp->top_ids / top_logprob [s][k][.]
+ * its top-n.  Every entry with k >= out_len[s] is 0 / 0.0.  No host synchronisation and no host <-> device copy inside the loop beyond what the
+ * until call does; one download of the record -- the steps that ran -- behind the last step.  The record belongs to the context like the other
+ * per-call buffers (grown to the largest call seen, counted by rwkv_resident_bytes, freed with it): 16 (1 + top_n) bytes per stream and step,
+ * plus 8 + 128 (4 + top_n) bytes of scratch per stream.  It is kept on the device for the whole call, hence the bound on
+ * n_streams * n_steps * (1 + top_n): 96 streams x 2048 steps x (1 + 20) fits, a longer generation is split into calls with the KEEP flags.
+ * Status: RWKV_E_ARG for whatever the until call rejects (but a NULL stop), a NULL lp or lp->logprob, top_n > RWKV_MAX_TOPN, top_ids /
+ * top_logprob not NULL exactly when top_n > 0, reserved != 0, a NULL out_len with a non-NULL stop, more than RWKV_MAX_LOGPROB_ENTRIES entries;
+ * for rwkv_topn_rows a NULL pointer, n or top_n out of range, a row >= max_ctx.  RWKV_E_STATE as for the batch calls (rwkv_topn_rows: not
+ * loaded, or a context without a head).  Every check runs before anything is launched or allocated: a rejected call leaves state, logits,
+ * counts, histories and buffers as they were. */
+#define RWKV_MAX_TOPN 32u
+#define RWKV_MAX_LOGPROB_ENTRIES (1u << 22) /* n_streams * n_steps * (1 + top_n) of one call */
+int rwkv_topn_rows(rwkv_ctx *ctx, const uint64_t *rows, uint64_t n, uint32_t top_n, uint64_t *ids /* host [n][top_n] */,
+                   double *logprob /* host [n][top_n] */);
+typedef struct rwkv_logprob_out {
+    uint32_t top_n;      /* 0 .. RWKV_MAX_TOPN; 0: no alternatives */
+    uint32_t reserved;   /* must be 0 */
+    double *logprob;     /* host [n_streams][n_steps]: log-prob of pick g_k under the row it was picked from */
+    double *entropy;     /* host [n_streams][n_steps], may be NULL */
+    uint64_t *top_ids;   /* host [n_streams][n_steps][top_n]; NULL exactly when top_n == 0 */
+    double *top_logprob; /* the same shape */
+} rwkv_logprob_out;
+int rwkv_decode_batch_logprobs(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                               const uint64_t *seeds, const rwkv_stop_params *stop /* may be NULL */, const rwkv_logprob_out *lp,
+                               uint64_t *out_tokens, uint32_t *out_len /* may be NULL when stop is NULL */, uint32_t *out_reason,
+                               uint64_t *steps_run);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

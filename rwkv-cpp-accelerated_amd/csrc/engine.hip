@@ -10,6 +10,7 @@
 #include "sampler.hip.h"
 #include "nucleus.hip.h"
 #include "score.hip.h"
+#include "topn.hip.h"
 #include "stop.hip.h"
 #include "../../include/rwkv_mi355x.h"
 
@@ -224,6 +225,8 @@ enum GrownBuf {
     STOP_RUN,                         // rwkv_decode_batch_until (stop.hip.h): u64 active | u64 first [n] | u32 len [n] | u32 reason [n] | u32 max_new [n]
     STOP_PARK,                        // f32 [n][5 x 2 L D + PARK_ROW (+ PARK_ROW with penalties)]: what the streams held when they stopped
     STOP_HISTORY,                     // u32 [max_ctx][STOP_HIST]: the newest ids per state slot; allocated ONCE, emptied, at the first call that can stop a stream
+    LP_REC,                           // rwkv_topn_rows / rwkv_decode_batch_logprobs (topn.hip.h), 8-byte words (LpLayout): rows [R] | score tuples [R][SC_G][4] |
+                                      // candidates [R][SC_G][n] | per step: logprob [R] | entropy [R] | top ids [R][n] | top logprob [R][n]
     N_GROWN
 };
 
@@ -325,7 +328,7 @@ struct rwkv_ctx {
     int tile_th = 0, tile_s = 0, tile_tpc = 0;     // rows per tile, KiB per ring unit, tiles per row class and workgroup (0: no tile form at this width)
     struct Grown { void *p = nullptr; size_t bytes = 0; } grown[N_GROWN];      // (enum GrownBuf)
     template <class T> T *buf(GrownBuf which) const { return static_cast<T *>(grown[which].p); }
-    std::vector<unsigned long long> bd_host, sc_host;   // staging of a call's one upload and one download
+    std::vector<unsigned long long> bd_host, sc_host, lp_host;   // staging of a call's one upload and one download
     static constexpr int STOP_RING = 4;           // rwkv_decode_batch_until: block b's count of active streams lands in word b % 4, read when block b + 2 is due
     unsigned long long *stop_ring = nullptr;      // pinned
     hipEvent_t stop_ev[STOP_RING] = {};
@@ -1572,6 +1575,37 @@ struct Stopper {
     }
 };
 
+// ---- log-probs and top-n alternatives of the picks (topn.hip.h): what rwkv_decode_batch_logprobs adds to the decode loops ----
+// LP_REC in 8-byte words for R rows per step, S steps and top-n n: where the score tuples, the candidates and step 0 of the record start, the words of
+// one step (logprob [R] | entropy [R] | top ids [R][n] | top logprob [R][n]) and of the whole buffer
+struct LpLayout {
+    size_t part, cand, rec, step, words;
+    LpLayout(uint64_t R, uint64_t S, uint64_t n) : part(R), cand(part + R * SC_PART_Q), rec(cand + R * SC_G * n), step(R * (2 + 2 * n)), words(rec + S * step) {}
+};
+// One call's record, set up by lp_setup (below decode_batch's checks).  The loops call record behind every step's pick and in front of
+// Stopper::after_step: two launches over rows 0 .. R - 1 that read the logits rows and the picks and write step k of the record, nothing else.
+struct LpRecorder {
+    TopnArgs a{};
+    double *rec = nullptr;
+    size_t step = 0;
+    unsigned R = 0;
+    static int launch(rwkv_ctx *c, const TopnArgs &t, unsigned rows)
+    {
+        k_topn_part<<<dim3(SC_G, rows), dim3(SC_NT), 0, c->stream>>>(t);
+        k_topn_finish<<<dim3(rows), dim3(std::max(64u, (SC_G * t.n + 63u) / 64u * 64u)), 0, c->stream>>>(t);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    int record(rwkv_ctx *c, uint64_t k, const unsigned long long *picks) const
+    {
+        TopnArgs t = a;
+        double *base = rec + k * step;
+        t.picks = picks; t.pick_logprob = base; t.entropy = base + R;
+        t.ids = reinterpret_cast<unsigned long long *>(base + 2 * (size_t)R); t.logprob = base + (2 + (size_t)t.n) * R;
+        return launch(c, t, R);
+    }
+};
+
 // ---- how a call picks its tokens: rwkv_pick, the C ABI's record, is the internal description too (sampler.hip.h, nucleus.hip.h) ----
 static_assert(sizeof(rwkv_nucleus_params) == 32, "rwkv_nucleus_params is 32 bytes in the C ABI");
 rwkv_pick pick_greedy() { rwkv_pick pk{}; pk.kind = RWKV_PICK_GREEDY; return pk; }
@@ -1686,7 +1720,9 @@ int enqueue_pick(rwkv_ctx *c, const Sampler &s, unsigned rows)
 // The device decode loop: n tokens on slot 0 (and its counts), `first` and then each token's pick, and the download of the picks.  The pick is
 // the argmax node of the token graph, or (`pk` not greedy) the sampler's three launches behind the token graph without that node: u of step k from
 // seed + k, logit 0 banned, the id fed back through the control block.  stop: the call can end early (the picks of the steps it ran are downloaded).
-int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_pick &pk, uint64_t seed, uint64_t *out_tokens, Stopper *stop = nullptr)
+// lp: every step's pick is recorded (in the greedy loop behind the token graph, whose last node is the pick: it reads gen[i]).
+int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_pick &pk, uint64_t seed, uint64_t *out_tokens, Stopper *stop = nullptr,
+                   const LpRecorder *lp = nullptr)
 {
     const bool sampled = pk.kind != RWKV_PICK_GREEDY;
     if (const int rc = pick_counts(c, pk, 0, 1, true)) return rc;
@@ -1697,6 +1733,7 @@ int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_pick &pk,
     for (uint64_t i = 0; i < n && more; i++) {
         if (const int rc = run_token(c, !sampled)) return rc;
         if (const int rc = sampled ? enqueue_pick(c, s, 1) : 0) return rc;
+        if (const int rc = lp ? lp->record(c, i, c->gen + i) : 0) return rc;
         if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
     }
     HIPCHK(hipMemcpyAsync(out_tokens, c->gen, (stop ? stop->steps_run : n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
@@ -1841,13 +1878,49 @@ void stop_results(const rwkv_ctx *c, bool stopped, uint64_t N, uint64_t n_steps,
 // what rwkv_decode_batch_until adds to a call of decode_batch
 struct Until { const rwkv_stop_params *stop; uint32_t *out_len, *out_reason; uint64_t *steps_run; };
 
+// the record of a call over R rows per step (rows 0 .. R - 1: rows == nullptr) and S steps: LP_REC, and the kernels' arguments
+int lp_setup(rwkv_ctx *c, LpRecorder &r, uint64_t R, uint64_t S, uint32_t top_n)
+{
+    const LpLayout lay(R, S, top_n);
+    if (const int rc = grow_buffer(c, LP_REC, sizeof(double) * lay.words)) return rc;
+    unsigned long long *w = c->buf<unsigned long long>(LP_REC);
+    r.a.logits = c->logits; r.a.rows = nullptr; r.a.picks = nullptr;
+    r.a.part = reinterpret_cast<double *>(w + lay.part); r.a.cand = w + lay.cand; r.a.n = top_n;
+    r.rec = reinterpret_cast<double *>(w + lay.rec); r.step = lay.step; r.R = (unsigned)R;
+    return 0;
+}
+// the one download of the record: the steps that ran
+int lp_download(rwkv_ctx *c, const LpRecorder &r, uint64_t ran)
+{
+    c->lp_host.resize(ran * r.step);
+    HIPCHK(hipMemcpyAsync(c->lp_host.data(), r.rec, sizeof(double) * ran * r.step, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+// behind the wait: [step][stream] -> [stream][step] into the caller's arrays; 0 / 0.0 from a stream's end on
+void lp_results(const rwkv_ctx *c, const rwkv_logprob_out &o, uint64_t N, uint64_t n_steps, const uint32_t *len)
+{
+    const uint64_t n = o.top_n, step = N * (2 + 2 * n);
+    for (uint64_t s = 0; s < N; s++)
+        for (uint64_t k = 0; k < n_steps; k++) {
+            const bool on = k < len[s];
+            const unsigned long long *h = on ? c->lp_host.data() + k * step : nullptr;
+            const size_t at = s * n_steps + k;
+            if (on) memcpy(&o.logprob[at], h + s, 8); else o.logprob[at] = 0.0;
+            if (o.entropy) { if (on) memcpy(&o.entropy[at], h + N + s, 8); else o.entropy[at] = 0.0; }
+            for (uint64_t j = 0; j < n; j++) {
+                o.top_ids[at * n + j] = on ? h[2 * N + s * n + j] : 0ull;
+                if (on) memcpy(&o.top_logprob[at * n + j], h + (2 + n) * N + s * n + j, 8); else o.top_logprob[at * n + j] = 0.0;
+            }
+        }
+}
+
 // rwkv_decode_batch_greedy / _typical / _nucleus / _until: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
 // else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
 // pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.  until: streams stop at sequences and budgets
 // (Stopper: two small launches behind each step's pick, one behind the last); a call that cannot stop a stream is the plain loop.
 // `pk`: how a step picks -- k_argmax_rows, or the sampler's three launches (one seed per stream, the sampler's scratch per row)
 int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, const rwkv_pick &pk, const uint64_t *seeds, uint64_t *out_tokens,
-                 const Until *until = nullptr)
+                 const Until *until = nullptr, const rwkv_logprob_out *lpo = nullptr)
 {
     const bool sampled = pk.kind != RWKV_PICK_GREEDY;
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!sampled || seeds))) return rc;
@@ -1857,7 +1930,10 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
     if (const int rc = check_pick(pk)) return rc;
     StopTable table{};
     if (const int rc = until ? check_stop(until->stop, N, n_steps, &table) : 0) return rc;
+    if (lpo && N * n_steps * (1 + (uint64_t)lpo->top_n) > RWKV_MAX_LOGPROB_ENTRIES)
+        return fail(RWKV_E_ARG, "n_streams * n_steps * (1 + top_n) must not exceed %u: split the generation into calls", RWKV_MAX_LOGPROB_ENTRIES);
     if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
+    LpRecorder recorder, *lp = lpo ? &recorder : nullptr;
     Stopper stopper, *st = until && (until->stop->n_seqs || until->stop->max_new) ? &stopper : nullptr;
     auto stop_setup = [&]() { return st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, pick_penalty(pk)) : 0; };
     auto stop_end = [&]() { const int rc = st ? st->unpark(c) : 0; return rc || !st ? rc : stopper_download(c, *st); };
@@ -1868,12 +1944,15 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
         for (uint64_t s = 0; s < N; s++)
             for (uint64_t k = until->out_len[s]; k < n_steps; k++) out_tokens[s * n_steps + k] = 0;
         if (until->steps_run) *until->steps_run = ran;
+        if (lpo) lp_results(c, *lpo, N, n_steps, until->out_len);
         return 0;
     };
     if (N == 1) {     // the decode path's kernels on slot 0
         const int rc = finish(c, [&]() -> int {
             if (const int rc = stop_setup()) return rc;
-            if (const int rc = enqueue_decode(c, first_tokens[0], n_steps, pk, sampled ? seeds[0] : 0, out_tokens, st)) return rc;
+            if (const int rc = lp ? lp_setup(c, *lp, 1, n_steps, lpo->top_n) : 0) return rc;
+            if (const int rc = enqueue_decode(c, first_tokens[0], n_steps, pk, sampled ? seeds[0] : 0, out_tokens, st, lp)) return rc;
+            if (const int rc = lp ? lp_download(c, *lp, st ? st->steps_run : n_steps) : 0) return rc;
             return stop_end();
         }());
         return rc || !until ? rc : until_results();
@@ -1882,6 +1961,7 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
     const int rc = finish(c, [&]() -> int {
         int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * N * (n_steps + 2));
         if (!rc) rc = stop_setup();
+        if (!rc && lp) rc = lp_setup(c, *lp, N, n_steps, lpo->top_n);
         if (!rc && !sampled) rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES);
         if (!rc && !sampled) rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
         if (!rc && sampled) rc = grow_buffer(c, BD_PART, sizeof(double) * N * TS_PART_ROW);
@@ -1909,11 +1989,13 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
                 k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
                 HIPCHK(hipGetLastError());
             }
+            if ((rc = lp ? lp->record(c, k, next) : 0)) return rc;
             bool more = true;
             if ((rc = st ? st->after_step(c, k, next, &more) : 0)) return rc;
             if (!more) break;
         }
         if (st) ran = st->steps_run;
+        if ((rc = lp ? lp_download(c, *lp, ran) : 0)) return rc;
         HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * ran, hipMemcpyDeviceToHost, c->stream));
         return stop_end();
     }());
@@ -1978,6 +2060,53 @@ int rwkv_decode_batch_until(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t 
     const Until until{stop, out_len, out_reason, steps_run};
     if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);      // an unknown kind: in front of decode_batch's checks
     return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until);
+}
+
+static_assert(TOPN_MAX == RWKV_MAX_TOPN, "topn.hip.h holds the header's limit");
+static_assert(sizeof(rwkv_logprob_out) == 40, "rwkv_logprob_out is 40 bytes in the C ABI");
+int rwkv_decode_batch_logprobs(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                               const uint64_t *seeds, const rwkv_stop_params *stop, const rwkv_logprob_out *lp, uint64_t *out_tokens,
+                               uint32_t *out_len, uint32_t *out_reason, uint64_t *steps_run)
+{
+    if (const int rc = guard(c, NEED_WHOLE, pick && lp && lp->logprob && (!stop || out_len))) return rc;
+    if (lp->top_n > RWKV_MAX_TOPN) return fail(RWKV_E_ARG, "top_n must be in 0..%u", RWKV_MAX_TOPN);
+    if ((lp->top_n > 0) != (lp->top_ids != nullptr) || (lp->top_n > 0) != (lp->top_logprob != nullptr))
+        return fail(RWKV_E_ARG, "top_ids and top_logprob go with top_n > 0, and only with it");
+    if (lp->reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);
+    const rwkv_stop_params none{};                      // no stop: the plain loop, every stream runs n_steps
+    std::vector<uint32_t> len(out_len ? 0 : std::min<uint64_t>(n_streams, c->maxT));
+    const Until until{stop ? stop : &none, out_len ? out_len : len.data(), out_reason, steps_run};
+    return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until, lp);
+}
+
+int rwkv_topn_rows(rwkv_ctx *c, const uint64_t *rows, uint64_t n, uint32_t top_n, uint64_t *ids, double *logprob)
+{
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, rows && ids && logprob)) return rc;
+    if (n == 0 || n > RWKV_MAX_SCORE) return fail(RWKV_E_ARG, "n must be in 1..%u", RWKV_MAX_SCORE);
+    if (top_n == 0 || top_n > RWKV_MAX_TOPN) return fail(RWKV_E_ARG, "top_n must be in 1..%u", RWKV_MAX_TOPN);
+    for (uint64_t i = 0; i < n; i++)
+        if (rows[i] >= c->maxT) return fail(RWKV_E_ARG, "logits row %llu out of range (max context %llu)", (unsigned long long)rows[i], (unsigned long long)c->maxT);
+    LpRecorder r;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = lp_setup(c, r, n, 1, top_n)) return rc;
+        unsigned long long *drows = c->buf<unsigned long long>(LP_REC);
+        c->lp_host.resize(n + 2 * n * top_n);               // the upload | the download (ids | logprob: the step's pick part stays unused)
+        std::copy(rows, rows + n, c->lp_host.begin());
+        HIPCHK(hipMemcpyAsync(drows, c->lp_host.data(), sizeof(unsigned long long) * n, hipMemcpyHostToDevice, c->stream));
+        for (uint64_t q = 0; q < n; q += SC_MAX_Y) {       // one launch sequence per SC_MAX_Y queries (gridDim.y)
+            TopnArgs t = r.a;
+            t.rows = drows + q; t.part += q * SC_PART_Q; t.cand += q * SC_G * top_n;
+            t.ids = reinterpret_cast<unsigned long long *>(r.rec + 2 * n) + q * top_n; t.logprob = r.rec + (2 + (size_t)top_n) * n + q * top_n;
+            if (const int rc = LpRecorder::launch(c, t, (unsigned)std::min<uint64_t>(n - q, SC_MAX_Y))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(c->lp_host.data() + n, r.rec + 2 * n, sizeof(double) * 2 * n * top_n, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+    if (rc) return rc;
+    memcpy(ids, c->lp_host.data() + n, sizeof(uint64_t) * n * top_n);
+    memcpy(logprob, c->lp_host.data() + n + n * top_n, sizeof(double) * n * top_n);
+    return 0;
 }
 
 int rwkv_debug_stop_scan(rwkv_ctx *c, const uint64_t *ids, const uint64_t *first_tokens, uint64_t n, uint64_t steps, const rwkv_stop_params *stop,

@@ -116,4 +116,12 @@ PYBIND11_MODULE(rwkv, m)
         std::copy(s.logprob.begin(), s.logprob.end(), a.mutable_data());
         return a;
     }, "f64 log-probabilities of tokens[1:], each under the logits that follow its predecessor, computed on the device (engine extension)");
+    m.def("topLogprobs", [](std::uintptr_t h, const std::vector<int64_t> &rows, unsigned top_n) {
+        const RWKV::TopN t = M(h)->topnRows(std::vector<unsigned long long>(rows.begin(), rows.end()), top_n);
+        py::array_t<int64_t> ids({rows.size(), (size_t)top_n});
+        py::array_t<double> lp({rows.size(), (size_t)top_n});
+        std::copy(t.ids.begin(), t.ids.end(), ids.mutable_data());
+        std::copy(t.logprob.begin(), t.logprob.end(), lp.mutable_data());
+        return py::make_tuple(ids, lp);
+    }, "(ids, f64 log-probabilities) [len(rows)][top_n]: the top_n most probable tokens of logits rows of the last forward, computed on the device (engine extension)");
 }

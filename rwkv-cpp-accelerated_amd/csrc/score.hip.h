@@ -37,23 +37,25 @@ struct ScoreArgs {
     unsigned long long *argmax;            // [n]
 };
 
-__global__ __launch_bounds__(SC_NT) void k_score_part(ScoreArgs a)
+// The tuple of one slice, and the slice itself: workgroup (b, .) loads slice b of the row `lg` into v (one dword per element; behind the slice: -inf)
+// and returns the slice's first id.  Every thread ends with the slice maximum `best` and the lowest id `besti` that holds it, thread 0 with
+// z = sum exp(l - best) and s = sum exp(l - best) (l - best) over the slice.  k_score_part and the top-n part kernel (topn.hip.h) both call this:
+// one way of summing, so one log-probability on the device.
+__device__ __forceinline__ int score_slice(const float *lg, float (&v)[SC_PER], float &best, unsigned &besti, double &tz, double &ts)
 {
     __shared__ float sv[SC_NT / 64];
     __shared__ unsigned si[SC_NT / 64];
     __shared__ double red[2 * (SC_NT / 64)];
     const int V = (int)VOCAB;
     const int i0 = block_lo(V), i1 = block_hi(V);
-    const float *lg = a.logits + (size_t)a.rows[blockIdx.y] * VOCAB;
-    float v[SC_PER];
 #pragma unroll
     for (int k = 0; k < SC_PER; k++) {       // all SC_PER loads in flight; behind the slice: -inf, which neither wins nor carries mass
         const int i = i0 + (int)threadIdx.x + k * SC_NT;
         v[k] = i < i1 ? lg[i] : -INFINITY;
     }
     // slice maximum and the lowest id that holds it ((value, id) fold of the greedy pick: wave_max is for non-negative values)
-    float best = -INFINITY;
-    unsigned besti = 0xffffffffu;
+    best = -INFINITY;
+    besti = 0xffffffffu;
 #pragma unroll
     for (int k = 0; k < SC_PER; k++)
         if (v[k] > best) { best = v[k]; besti = (unsigned)(i0 + (int)threadIdx.x + k * SC_NT); }
@@ -76,31 +78,50 @@ __global__ __launch_bounds__(SC_NT) void k_score_part(ScoreArgs a)
     z = wave_sum(z); s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) { red[(threadIdx.x >> 6) * 2] = z; red[(threadIdx.x >> 6) * 2 + 1] = s; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        double tz = 0.0, ts = 0.0;
+    tz = 0.0; ts = 0.0;
+    if (threadIdx.x == 0)
         for (int w = 0; w < SC_NT / 64; w++) { tz += red[2 * w]; ts += red[2 * w + 1]; }
+    return i0;
+}
+
+__global__ __launch_bounds__(SC_NT) void k_score_part(ScoreArgs a)
+{
+    float v[SC_PER], best;
+    unsigned besti;
+    double tz, ts;
+    score_slice(a.logits + (size_t)a.rows[blockIdx.y] * VOCAB, v, best, besti, tz, ts);
+    if (threadIdx.x == 0) {
         double *part = a.part + blockIdx.y * SC_PART_Q + blockIdx.x * 4;
-        part[0] = m; part[1] = tz; part[2] = ts; part[3] = (double)besti;
+        part[0] = (double)best; part[1] = tz; part[2] = ts; part[3] = (double)besti;
     }
+}
+
+// The fold of one row's SC_G tuples on one wave (the sampler's ts_combine with the -inf guards): every lane ends with M = mm, Z, S = sum exp(d) d
+// and `at`, the lowest id that holds M.  k_score_finish and the top-n finish (topn.hip.h) both call this.
+__device__ __forceinline__ void score_fold(const double *row_part, int lane, double &mm, double &Z, double &S, unsigned &at)
+{
+    const double *part = row_part + (lane < SC_G ? lane : 0) * 4;
+    const bool on = lane < SC_G;
+    const double m = on ? part[0] : -INFINITY, z = on ? part[1] : 0.0, s = on ? part[2] : 0.0;
+    at = on ? (unsigned)part[3] : 0xffffffffu;
+    mm = m;
+    for (int off = 32; off >= 1; off >>= 1) mm = fmax(mm, __shfl_xor(mm, off, 64));
+    // a slice without mass (m = -inf) adds nothing: not exp(-inf) * (-inf * 0)
+    const bool mass = on && m > -INFINITY;
+    const double sc = mass ? exp(m - mm) : 0.0;
+    Z = wave_sum(sc * z); S = wave_sum(mass ? sc * (s + (m - mm) * z) : 0.0);
+    if (!(on && m == mm)) at = 0xffffffffu;                      // the lowest id among the slices that hold the maximum
+    for (int off = 32; off >= 1; off >>= 1) at = min(at, (unsigned)__shfl_xor((int)at, off, 64));
 }
 
 __global__ __launch_bounds__(64) void k_score_finish(ScoreArgs a)
 {
     const int lane = threadIdx.x;
     const unsigned q = blockIdx.x;
-    const double *part = a.part + q * SC_PART_Q + (lane < SC_G ? lane : 0) * 4;
-    const bool on = lane < SC_G;
-    const double m = on ? part[0] : -INFINITY, z = on ? part[1] : 0.0, s = on ? part[2] : 0.0;
-    unsigned at = on ? (unsigned)part[3] : 0xffffffffu;
-    double mm = m;
-    for (int off = 32; off >= 1; off >>= 1) mm = fmax(mm, __shfl_xor(mm, off, 64));
-    // a slice without mass (m = -inf) adds nothing: not exp(-inf) * (-inf * 0)
-    const bool mass = on && m > -INFINITY;
-    const double sc = mass ? exp(m - mm) : 0.0;
-    const double Z = wave_sum(sc * z), S = wave_sum(mass ? sc * (s + (m - mm) * z) : 0.0);
+    double mm, Z, S;
+    unsigned at;
+    score_fold(a.part + q * SC_PART_Q, lane, mm, Z, S, at);
     const double logZ = log(Z);
-    if (!(on && m == mm)) at = 0xffffffffu;                      // the lowest id among the slices that hold the maximum
-    for (int off = 32; off >= 1; off >>= 1) at = min(at, (unsigned)__shfl_xor((int)at, off, 64));
     if (lane == 0) {
         const double lt = (double)a.logits[(size_t)a.rows[q] * VOCAB + a.targets[q]];
         a.logprob[q] = (lt - mm) - logZ;

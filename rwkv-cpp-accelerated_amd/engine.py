@@ -37,8 +37,11 @@ ABI_SYMBOLS = [
     "rwkv_score_rows", "rwkv_score",
     "rwkv_sample_nucleus", "rwkv_decode_nucleus", "rwkv_decode_batch_nucleus", "rwkv_penalty_set", "rwkv_penalty_get",
     "rwkv_decode_batch_until", "rwkv_debug_stop_scan",
+    "rwkv_topn_rows", "rwkv_decode_batch_logprobs",
 ]
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
+TOPN_MAX = 32                     # RWKV_MAX_TOPN
+LOGPROB_ENTRIES_MAX = 1 << 22     # RWKV_MAX_LOGPROB_ENTRIES: n_streams * n_steps * (1 + top_n) of one call
 
 _lib = None
 
@@ -73,6 +76,12 @@ def stop_params(sequences=(), max_new=None, keep=False):
     mx = None if max_new is None else (C.c_uint32 * max(1, len(max_new)))(*[int(v) for v in max_new])
     sp = StopParams(ids if seqs else None, lens if seqs else None, len(seqs), STOP_KEEP if keep else 0, mx, 0)
     return sp, (ids, lens, mx)
+
+
+class LogprobOut(C.Structure):
+    """rwkv_logprob_out of include/rwkv_mi355x.h (40 bytes)"""
+    _fields_ = [("top_n", C.c_uint32), ("reserved", C.c_uint32), ("logprob", C.POINTER(C.c_double)), ("entropy", C.POINTER(C.c_double)),
+                ("top_ids", C.POINTER(C.c_uint64)), ("top_logprob", C.POINTER(C.c_double))]
 
 
 class RWKVError(RuntimeError):
@@ -155,6 +164,10 @@ def lib():
     L.rwkv_decode_batch_until.restype = i32
     L.rwkv_debug_stop_scan.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, u64, C.POINTER(StopParams), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
     L.rwkv_debug_stop_scan.restype = i32
+    L.rwkv_topn_rows.argtypes = [vp, C.POINTER(u64), u64, C.c_uint32, C.POINTER(u64), C.POINTER(C.c_double)]; L.rwkv_topn_rows.restype = i32
+    L.rwkv_decode_batch_logprobs.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(StopParams), C.POINTER(LogprobOut),
+                                             C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]
+    L.rwkv_decode_batch_logprobs.restype = i32
     _lib = L
     return L
 
@@ -481,7 +494,7 @@ class RWKV:
     # -- stop sequences and per-stream budgets in the device loops (include/rwkv_mi355x.h rwkv_decode_batch_until) --------
     def decode_batch_until(self, first_tokens, n_steps: int, stops=(), max_new=None, keep: bool = False, pick: str = "greedy", seeds=None,
                            temp: float = 1.0, tau: float = 0.8, recipe: bool = False, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
-                           frequency: float = 0.0, decay: float = 1.0):
+                           frequency: float = 0.0, decay: float = 1.0, _logprobs=None):
         """decode_batch_greedy / _typical / _nucleus (pick = "greedy", "typical", "nucleus", with that call's parameters) in which stream s ends
         at the first of the stop sequences `stops` (lists of token ids, each 1 .. 8 long) that its newest ids spell, or after max_new[s] tokens.
         keep: the match history (and the nucleus counts) continue from the previous call.  Returns (ids [N][n_steps], 0 behind a stream's end;
@@ -499,10 +512,45 @@ class RWKV:
                   nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_KEEP if keep else 0))
         sp, alive = stop_params(stops, max_new, keep)
         ln, rs, ran = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))(), C.c_uint64(0)
-        ids = self._decode_batch(first_tokens, n_steps, lambda ft, n_, out: lib().rwkv_decode_batch_until(
-            self._h, ft, n_, n_steps, C.byref(pk), None if kind == PICK_GREEDY else arr, C.byref(sp), out, ln, rs, C.byref(ran)))
+        sdp = None if kind == PICK_GREEDY else arr
+        if _logprobs is None:
+            call = lambda ft, n_, out: lib().rwkv_decode_batch_until(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(sp), out, ln, rs, C.byref(ran))
+        else:       # decode_batch_logprobs: the same call with the record
+            call = lambda ft, n_, out: lib().rwkv_decode_batch_logprobs(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(sp), C.byref(_logprobs),
+                                                                        out, ln, rs, C.byref(ran))
+        ids = self._decode_batch(first_tokens, n_steps, call)
         del alive
         return (ids, np.frombuffer(ln, dtype=np.uint32)[:n].astype(np.int64), np.frombuffer(rs, dtype=np.uint32)[:n].astype(np.int64), int(ran.value))
+
+    # -- log-probs and top-n alternatives of generated tokens (include/rwkv_mi355x.h rwkv_decode_batch_logprobs) --------
+    def decode_batch_logprobs(self, first_tokens, n_steps: int, top_n: int = 0, entropy: bool = True, **kw):
+        """decode_batch_until (its arguments: stops, max_new, keep, pick, seeds and the pick's parameters) that also returns what the MODEL thought
+        of every generated token -- no penalty, no temperature, nothing banned, whichever pick generated it.  Returns (ids, len, reason,
+        steps_run, logprob [N][n_steps], entropy [N][n_steps] or None, top_ids [N][n_steps][top_n], top_logprob likewise); every entry behind a
+        stream's end is 0 / 0.0.  Best-of-n: rank streams by logprob[s, :len[s]].sum()."""
+        n, e = len(first_tokens), max(1, len(first_tokens) * int(n_steps))
+        top_n = int(top_n)
+        lp, ent = np.zeros(e, dtype=np.float64), (np.zeros(e, dtype=np.float64) if entropy else None)
+        tid, tlp = np.zeros(e * max(1, top_n), dtype=np.uint64), np.zeros(e * max(1, top_n), dtype=np.float64)
+        dp, up = C.POINTER(C.c_double), C.POINTER(C.c_uint64)
+        rec = LogprobOut(top_n, 0, lp.ctypes.data_as(dp), ent.ctypes.data_as(dp) if entropy else None,
+                         tid.ctypes.data_as(up) if top_n > 0 else None, tlp.ctypes.data_as(dp) if top_n > 0 else None)
+        ids, ln, rs, ran = self.decode_batch_until(first_tokens, n_steps, _logprobs=rec, **kw)
+        shape = (n, int(n_steps))
+        return (ids, ln, rs, ran, lp[: n * n_steps].reshape(shape), ent[: n * n_steps].reshape(shape) if entropy else None,
+                tid[: n * n_steps * top_n].astype(np.int64).reshape(shape + (top_n,)), tlp[: n * n_steps * top_n].reshape(shape + (top_n,)))
+
+    def topn_rows(self, rows, top_n: int):
+        """(ids [n][top_n], logprob [n][top_n]): the top_n most probable tokens of logits row rows[i] of the LAST forward (rwkv_topn_rows), in
+        descending logit order, equal logits by ascending id; the log-probs are bit for bit those of score_rows.  Logits and state stay."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        r = [int(v) for v in rows]
+        n, top_n = len(r), int(top_n)
+        ids, lp = np.zeros(max(1, n * max(0, top_n)), dtype=np.uint64), np.zeros(max(1, n * max(0, top_n)), dtype=np.float64)
+        _chk(lib().rwkv_topn_rows(self._h, (C.c_uint64 * max(1, n))(*r), n, top_n, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                  lp.ctypes.data_as(C.POINTER(C.c_double))))
+        return ids[: n * top_n].astype(np.int64).reshape(n, top_n), lp[: n * top_n].reshape(n, top_n)
 
     def debug_stop_scan(self, ids, first_tokens, stops=(), max_new=None, keep: bool = False):
         """the stop test alone over PLANTED picks ids [n][steps] (rwkv_debug_stop_scan): (len [n], reason [n]); stream s uses slot s's history"""
