@@ -396,6 +396,43 @@ public:
         t.ids.assign(ids.begin(), ids.end());
         return t;
     }
+    // beam search on the device (rwkv_mi355x.h "beam search"): the `width` most probable continuations of the prompt whose state slot 0 holds,
+    // fed `first`, n steps long; stop_ids: single-token stop ids that end a hypothesis.  tokens and token_logprob [m * n + k] (0 / 0.0 from
+    // len[m] on), len [m], score [m] = the sum of the token log-probs; hypothesis 0 is the best.  Slot m is left where live hypothesis m ended:
+    // feed tokens[m * n + len[m] - 1] to go on.  A length penalty is the caller's: rank by score[m] / pow(len[m], a).
+    struct Beam { unsigned width = 4; std::vector<unsigned long long> stop_ids; };
+    struct BeamResult { std::vector<unsigned long long> tokens; std::vector<unsigned> len; std::vector<double> score, token_logprob; };
+    BeamResult decodeBeam(unsigned long long first, unsigned long long n, const Beam &beam)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (beam.width < 2 || beam.width > RWKV_MAX_BEAM) throw std::runtime_error("beam width outside 2 .. RWKV_MAX_BEAM");
+        BeamResult r;
+        const size_t W = beam.width;
+        std::vector<uint64_t> tok(W * n), stops(beam.stop_ids.begin(), beam.stop_ids.end());
+        std::vector<uint32_t> len(W);
+        r.score.resize(W); r.token_logprob.resize(W * n);
+        const rwkv_beam_params bp{beam.width, (uint32_t)stops.size(), stops.empty() ? nullptr : stops.data(), 0};
+        const rwkv_beam_out bo{tok.data(), len.data(), r.score.data(), r.token_logprob.data()};
+        if (!residentState) pushState();      // host state is authoritative: the prompt's state is its slot 0 ...
+        rwkv_detail::check(rwkv_decode_beam(ctx_, first, n, &bp, &bo));
+        if (!residentState) pullState();      // ... and every slot is left where its hypothesis ended
+        r.tokens.assign(tok.begin(), tok.end()); r.len.assign(len.begin(), len.end());
+        return r;
+    }
+    // slot m <- what slot parents[m] held, for every m < parents.size() at once (any map: swaps, cycles, fan-out); the other slots stay.
+    // Re-fork the survivors of a best-of-n: permuteState({best, best, second, second}).  The host copy too when it is the authoritative one
+    void permuteState(const std::vector<unsigned> &parents)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint32_t> p(parents.begin(), parents.end());
+        for (uint32_t v : p) if (v >= p.size()) throw std::runtime_error("a parent outside the map");
+        if (!residentState) {
+            std::vector<RWKVState> old;
+            for (uint32_t v : p) old.push_back(state->getSubState(v));
+            for (size_t m = 0; m < p.size(); m++) state->setSubState(old[m], m);
+        }
+        rwkv_detail::check(rwkv_state_permute(ctx_, p.data(), p.size()));
+    }
 private:
     // decodeBatchUntil, and with `lp` decodeBatchLogprobs: one preparation of the C ABI's records, one push / pull of host-authoritative state
     Until until_call(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,

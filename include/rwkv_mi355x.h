@@ -360,6 +360,62 @@ int rwkv_decode_batch_logprobs(rwkv_ctx *ctx, const uint64_t *first_tokens, uint
                                uint64_t *out_tokens, uint32_t *out_len /* may be NULL when stop is NULL */, uint32_t *out_reason,
                                uint64_t *steps_run);
 
+/* ---- beam search on the device: width-W decode with state reordering (no reference counterpart: the reference only samples) ----
+ * The decoding mode that keeps the W most probable continuations instead of one.  What it replaces is a caller's loop of rwkv_forward(W, PARRALEL),
+ * rwkv_topn_rows, a selection on the host and a reordering of the W state slots through rwkv_get_output / rwkv_set_state (5 L D f64 per slot: 5.2 MB
+ * per beam at 7B).  Width W lies in 2 .. RWKV_MAX_BEAM and W <= max_ctx; the chunk path is required, as for every batch call with n_streams >= 2.
+ * Start.  Slot 0 holds the prompt's state: the call copies it, device to device, into slots 1 .. W - 1.  first_token is fed to all W rows at step 0.
+ * The cumulative scores start at c_0 = 0 and c_j = -inf for j >= 1, so step 0 selects among beam 0's candidates only, without a special case.
+ * Step k.  Rows 0 .. W - 1 run one PARRALEL step: the schedule of rwkv_forward(W, PARRALEL) with the same kernels, the ids read on the device.  For
+ * a live row j the candidates are (j, i) with i over the W ids of row j with the largest f32 logits other than id 0 (token 0 is banned in every
+ * device loop), ordered by descending logit, equal logits by ascending id: the row's top W + 1 of the top-n block above without id 0, or else
+ * without its last entry.  A candidate's score is c_j + logprob_j(i), ONE f64 add; logprob is the model's, exactly that of rwkv_score_rows: no ban
+ * in the normalisation, no temperature.  An ended row j contributes exactly one candidate: (j, its end token again, c_j, token log-prob 0).  The W
+ * best candidates become beams 0 .. W - 1 in that order: descending score, equal scores by ascending parent, then by the row's own candidate order.
+ * The beams are therefore always sorted and hypothesis 0 is the best.  Beam m records its parent p_m, token g_m, score c_m and the token's log-prob;
+ * it is ended if its parent was ended or if g_m is one of the n_stop <= RWKV_BEAM_MAX_STOP single-token stop ids, and its length is then fixed at
+ * k + 1, or at the parent's length.  Slot m receives the five state arrays that slot p_m held after this step, for all m simultaneously, and row m
+ * is fed g_m at step k + 1.
+ * End.  The tokens are backtracked on the host from the downloaded record: tokens[m][k] is 0 for k >= len[m], token_logprob likewise 0.0, score[m] =
+ * c_m.  For a live hypothesis slot m follows the contract of the other loops: every returned token but the last has been fed.  The state of an
+ * ended hypothesis's slot is unspecified.  The logits rows are left as the last step wrote them, not permuted.  With NaN or +inf logits the result
+ * is unspecified, but every id is below 50277, every parent is below W and nothing faults.
+ * Inside the loop there is no host synchronisation and no host <-> device copy: one upload (first_token, stop ids), one download of the record.
+ * Per step the call adds five launches to the PARRALEL step: the two top-n launches (n = W + 1), the selection across rows (one workgroup) and the
+ * two launches of the state gather (csrc/beam.hip.h).  The buffers belong to the context like the other per-call buffers (grown to the largest
+ * call seen, counted by rwkv_resident_bytes, freed with it): the record, 8 (5 W + 16 + 3 W n_steps) bytes; the staging buffer of the gather,
+ * 40 W L D bytes (84 MB at 7B and W = 16); the top-n scratch of the log-prob block for W rows and n = W + 1.
+ * Out of scope: a length penalty inside the search (the caller ranks score / len^a itself); ending the call early when all beams have ended (it
+ * runs n_steps); stop sequences longer than one token; sampling or penalties inside a beam.
+ *
+ * rwkv_state_permute is the gather on its own: slot m receives what slot parents[m] held at the call, for m = 0 .. n - 1 simultaneously; slots >= n
+ * and the logits stay as they are.  Any map works -- identity, swaps, cycles, fan-out: re-fork the survivors of a best-of-n, resample particles.
+ * rwkv_debug_beam_step runs ONE selection and state gather on whatever the logits rows 0 .. W - 1 and the state slots hold (planted by the tests, as
+ * rwkv_debug_stop_scan plants picks): in cum [W], ended [W], last [W] (the ids the rows were fed: an ended row's end token); out parent [W],
+ * token [W], score [W], token_logprob [W], ended_out [W].
+ * Status: RWKV_E_ARG for a NULL pointer (token_logprob may be NULL), a width outside 2 .. RWKV_MAX_BEAM or above max_ctx, n_steps == 0 or above
+ * RWKV_MAX_DECODE_STEPS, a token or stop id >= 50277 or a stop id of 0, n_stop > RWKV_BEAM_MAX_STOP or > 0 with NULL stop_ids, reserved != 0; for
+ * rwkv_state_permute a parent >= n, n == 0 or n > max_ctx.  RWKV_E_STATE when not loaded, on a pipeline-stage context or (rwkv_decode_beam) without the
+ * chunk path; rwkv_state_permute needs only a loaded context.  Every check runs before anything is launched or allocated: a rejected call leaves
+ * state, logits and buffers as they were. */
+#define RWKV_MAX_BEAM 16u
+#define RWKV_BEAM_MAX_STOP 16u
+typedef struct rwkv_beam_params {
+    uint32_t width, n_stop;   /* 2 .. RWKV_MAX_BEAM; 0 .. RWKV_BEAM_MAX_STOP */
+    const uint64_t *stop_ids; /* host [n_stop], each 1 .. 50276; may be NULL when n_stop == 0 */
+    uint64_t reserved;        /* must be 0 */
+} rwkv_beam_params;
+typedef struct rwkv_beam_out {
+    uint64_t *tokens;      /* host [W][n_steps] */
+    uint32_t *len;         /* host [W] */
+    double *score;         /* host [W] */
+    double *token_logprob; /* host [W][n_steps], may be NULL */
+} rwkv_beam_out;
+int rwkv_decode_beam(rwkv_ctx *ctx, uint64_t first_token, uint64_t n_steps, const rwkv_beam_params *params, const rwkv_beam_out *out);
+int rwkv_state_permute(rwkv_ctx *ctx, const uint32_t *parents, uint64_t n);
+int rwkv_debug_beam_step(rwkv_ctx *ctx, const rwkv_beam_params *params, const double *cum, const uint8_t *ended, const uint64_t *last,
+                         uint32_t *parent, uint64_t *token, double *score, double *token_logprob, uint8_t *ended_out);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

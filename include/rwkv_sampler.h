@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <numeric>
 #include <random>
 #include <vector>
@@ -192,6 +193,47 @@ inline stop_result stop_scan(const std::vector<unsigned long long> &ids, unsigne
         if (reason) return stop_result{(unsigned)(k + 1), reason};
     }
     return stop_result{(unsigned)ids.size(), 0u};
+}
+
+// ---- beam search: the host twin of the selection the device makes behind every step (csrc/beam.hip.h k_beam_select; the semantics are those of
+// include/rwkv_mi355x.h rwkv_decode_beam).  W beams; top_ids / top_lp: [W][W + 1], the top W + 1 of every row with their log-probabilities, as
+// RWKV::topnRows returns them; cum [W] the cumulative scores; ended [W]; last [W] the ids the rows were fed (an ended row's end token); stops: the
+// single-token stop ids.  A live row offers its W best ids other than id 0 at cum + logprob (one f64 add), an ended row its end token again at
+// cum, log-prob 0; the W best become beams 0 .. W - 1: descending score, equal scores by ascending parent, then by the row's own order.  The
+// order is taken on an order-preserving 64-bit image of the score, as the device takes it, so that the result is defined for every input.
+struct beam_pick { unsigned parent; unsigned long long token; double score, token_logprob; bool ended; };
+inline unsigned long long beam_score_key(double v)
+{
+    unsigned long long b = 0;
+    if (v != 0.0) std::memcpy(&b, &v, 8);                 // (-0.0 is keyed as +0.0: equal scores)
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+inline std::vector<beam_pick> beam_select(unsigned W, const unsigned long long *top_ids, const double *top_lp, const double *cum,
+                                          const unsigned char *ended, const unsigned long long *last,
+                                          const std::vector<unsigned long long> &stops)
+{
+    struct cand { unsigned long long key; beam_pick p; };
+    std::vector<cand> all;                                // in (parent, row order): what a stable sort keeps among equal scores
+    const unsigned n = W + 1;
+    for (unsigned j = 0; j < W; j++) {
+        if (ended[j]) { all.push_back(cand{beam_score_key(cum[j]), beam_pick{j, last[j] < 50277 ? last[j] : 0ull, cum[j], 0.0, true}}); continue; }
+        bool has0 = false;
+        for (unsigned i = 0; i < n; i++) has0 = has0 || top_ids[j * n + i] == 0;
+        for (unsigned i = 0; i < n; i++) {
+            const unsigned long long g = top_ids[j * n + i];
+            if (g == 0 || !(has0 || i < W)) continue;
+            const double lp = top_lp[j * n + i], s = cum[j] + lp;
+            all.push_back(cand{beam_score_key(s), beam_pick{j, g < 50277 ? g : 0ull, s, lp, false}});
+        }
+    }
+    std::stable_sort(all.begin(), all.end(), [](const cand &a, const cand &b) { return a.key > b.key; });
+    std::vector<beam_pick> out;
+    for (unsigned m = 0; m < W && m < all.size(); m++) {
+        beam_pick p = all[m].p;
+        p.ended = p.ended || std::find(stops.begin(), stops.end(), p.token) != stops.end();
+        out.push_back(p);
+    }
+    return out;
 }
 
 inline int typical(float *_logits, float _temp = 0.9, float _tau = 0.8)

@@ -12,6 +12,7 @@
 #include "score.hip.h"
 #include "topn.hip.h"
 #include "stop.hip.h"
+#include "beam.hip.h"
 #include "../../include/rwkv_mi355x.h"
 
 #include <dlfcn.h>
@@ -227,6 +228,10 @@ enum GrownBuf {
     STOP_HISTORY,                     // u32 [max_ctx][STOP_HIST]: the newest ids per state slot; allocated ONCE, emptied, at the first call that can stop a stream
     LP_REC,                           // rwkv_topn_rows / rwkv_decode_batch_logprobs (topn.hip.h), 8-byte words (LpLayout): rows [R] | score tuples [R][SC_G][4] |
                                       // candidates [R][SC_G][n] | per step: logprob [R] | entropy [R] | top ids [R][n] | top logprob [R][n]
+    BEAM_REC,                         // rwkv_decode_beam / rwkv_debug_beam_step (beam.hip.h), 8-byte words (BeamLayout): ids [2][W] | stop ids [16] | cum [W] |
+                                      // ended, len u32 [2][W] | parent map u32 [W] + padding | per step: parent, token u32 [2][W] | score [W] | token log-prob [W];
+                                      // rwkv_state_permute: the parent map u32 [n]
+    BEAM_STAGE,                       // f64 [n][5][L D]: where the state gather sets the parents' slots aside
     N_GROWN
 };
 
@@ -328,7 +333,7 @@ struct rwkv_ctx {
     int tile_th = 0, tile_s = 0, tile_tpc = 0;     // rows per tile, KiB per ring unit, tiles per row class and workgroup (0: no tile form at this width)
     struct Grown { void *p = nullptr; size_t bytes = 0; } grown[N_GROWN];      // (enum GrownBuf)
     template <class T> T *buf(GrownBuf which) const { return static_cast<T *>(grown[which].p); }
-    std::vector<unsigned long long> bd_host, sc_host, lp_host;   // staging of a call's one upload and one download
+    std::vector<unsigned long long> bd_host, sc_host, lp_host, beam_host;   // staging of a call's one upload and one download
     static constexpr int STOP_RING = 4;           // rwkv_decode_batch_until: block b's count of active streams lands in word b % 4, read when block b + 2 is due
     unsigned long long *stop_ring = nullptr;      // pinned
     hipEvent_t stop_ev[STOP_RING] = {};
@@ -2174,6 +2179,190 @@ int rwkv_state_copy(rwkv_ctx *c, uint64_t dst, uint64_t src)
         for (int s = 0; s < 5; s++)
             HIPCHK(hipMemcpyAsync(c->state[s] + dst * n, c->state[s] + src * n, n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
         return 0;
+    }());
+}
+
+namespace {
+// ---- beam search (beam.hip.h): rwkv_decode_beam, rwkv_debug_beam_step, rwkv_state_permute ----
+static_assert(BEAM_MAX == RWKV_MAX_BEAM && BEAM_MAX_STOP == RWKV_BEAM_MAX_STOP, "beam.hip.h holds the header's limits");
+static_assert(sizeof(rwkv_beam_params) == 24 && sizeof(rwkv_beam_out) == 32, "rwkv_beam_params is 24 bytes and rwkv_beam_out 32 in the C ABI");
+// BEAM_REC in 8-byte words for width W and S steps: where the two id rows, the stop ids, cum, the ended / len words, the parent map and step 0 of
+// the record start, the words of one step (parent, token u32 [2][W] | score [W] | token log-prob [W]) and of the whole buffer
+struct BeamLayout {
+    size_t ids, stop, cum, flags, parent, rec, step, words;
+    BeamLayout(uint64_t W, uint64_t S) : ids(0), stop(2 * W), cum(stop + RWKV_BEAM_MAX_STOP), flags(cum + W), parent(flags + W), rec(parent + W), step(3 * W), words(rec + S * step) {}
+};
+// the width and the stop ids of a call are acceptable
+int check_beam(const rwkv_ctx *c, const rwkv_beam_params *bp)
+{
+    if (bp->width < 2 || bp->width > RWKV_MAX_BEAM || bp->width > c->maxT)
+        return fail(RWKV_E_ARG, "beam width must be in 2..%llu", (unsigned long long)std::min<uint64_t>(RWKV_MAX_BEAM, c->maxT));
+    if (bp->n_stop > RWKV_BEAM_MAX_STOP) return fail(RWKV_E_ARG, "at most %u stop ids", RWKV_BEAM_MAX_STOP);
+    if (bp->n_stop && !bp->stop_ids) return fail(RWKV_E_ARG, "NULL argument");
+    if (bp->reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    if (const int rc = check_ids(bp->stop_ids, bp->n_stop, "stop")) return rc;
+    for (uint32_t s = 0; s < bp->n_stop; s++)
+        if (bp->stop_ids[s] == 0) return fail(RWKV_E_ARG, "stop id 0 is never generated");
+    return 0;
+}
+// the two launches of the gather over slots 0 .. g.n - 1
+int enqueue_gather(rwkv_ctx *c, const GatherArgs &g)
+{
+    const size_t total = 5 * g.LD / 2, per = (size_t)GATHER_NT * GATHER_PER;
+    const unsigned chunks = (unsigned)std::min<size_t>(GATHER_CHUNKS_MAX, std::max<size_t>(1, (total + per - 1) / per));
+    k_beam_gather<false><<<dim3(g.n, chunks), dim3(GATHER_NT), 0, c->stream>>>(g);
+    k_beam_gather<true><<<dim3(g.n, chunks), dim3(GATHER_NT), 0, c->stream>>>(g);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+GatherArgs gather_args(rwkv_ctx *c, const unsigned *parent, uint64_t n)
+{
+    GatherArgs g{};
+    for (int i = 0; i < 5; i++) g.state[i] = c->state[i];
+    g.stage = c->buf<double>(BEAM_STAGE); g.parent = parent; g.n = (unsigned)n; g.LD = (size_t)c->L * c->D;
+    return g;
+}
+// One call's search: the buffers (BEAM_REC, BEAM_STAGE, the top-n scratch of LP_REC), the host image of BEAM_REC's head and its upload -- row 0 of
+// the ids = `fed`, cum, ended, len 0, the parent map `parent0` -- and the kernels' arguments
+struct Beam {
+    BeamLayout lay{2, 1};
+    TopnArgs top{};
+    BeamArgs a{};
+    GatherArgs g{};
+    unsigned long long *w = nullptr, *ids = nullptr;
+    int setup(rwkv_ctx *c, const rwkv_beam_params &bp, uint64_t S, const uint64_t *fed, const double *cum, const uint8_t *ended, unsigned parent0)
+    {
+        const uint64_t W = bp.width;
+        lay = BeamLayout(W, S);
+        int rc = grow_buffer(c, BEAM_REC, sizeof(double) * lay.words);
+        if (!rc) rc = grow_buffer(c, BEAM_STAGE, sizeof(double) * W * 5 * c->L * c->D);
+        LpRecorder r;
+        if (!rc) rc = lp_setup(c, r, W, 1, (uint32_t)W + 1);
+        if (rc) return rc;
+        top = r.a;
+        top.ids = reinterpret_cast<unsigned long long *>(r.rec + 2 * W); top.logprob = r.rec + (2 + (W + 1)) * W;
+        w = c->buf<unsigned long long>(BEAM_REC); ids = w + lay.ids;
+        c->beam_host.assign(lay.words, 0ull);
+        unsigned long long *h = c->beam_host.data();
+        unsigned *flags = reinterpret_cast<unsigned *>(h + lay.flags), *parent = reinterpret_cast<unsigned *>(h + lay.parent);
+        for (uint64_t m = 0; m < W; m++) {
+            h[lay.ids + m] = fed[m];
+            memcpy(&h[lay.cum + m], &cum[m], 8);
+            flags[m] = ended && ended[m] ? 1u : 0u;
+            parent[m] = parent0 == ~0u ? (unsigned)m : parent0;
+        }
+        for (uint32_t s = 0; s < bp.n_stop; s++) h[lay.stop + s] = bp.stop_ids[s];
+        HIPCHK(hipMemcpyAsync(w, h, sizeof(double) * lay.rec, hipMemcpyHostToDevice, c->stream));
+        a.W = (unsigned)W; a.n_stop = bp.n_stop; a.stop = w + lay.stop;
+        a.top_ids = top.ids; a.top_lp = top.logprob;
+        a.cum = reinterpret_cast<double *>(w + lay.cum);
+        a.ended = reinterpret_cast<unsigned *>(w + lay.flags); a.len = a.ended + W;
+        a.parent = reinterpret_cast<unsigned *>(w + lay.parent);
+        g = gather_args(c, a.parent, W);
+        return 0;
+    }
+    // behind step k's logits (rows 0 .. W - 1, fed ids row k & 1): the rows' top W + 1, the selection into step k of the record and ids row
+    // (k + 1) & 1, and the gather
+    int step(rwkv_ctx *c, uint64_t k)
+    {
+        if (const int rc = LpRecorder::launch(c, top, a.W)) return rc;
+        BeamArgs s = a;
+        unsigned long long *rec = w + lay.rec + k * lay.step;
+        s.k = (unsigned)k; s.cur = ids + (k & 1) * a.W; s.next = ids + ((k + 1) & 1) * a.W;
+        s.rec_parent = reinterpret_cast<unsigned *>(rec); s.rec_token = s.rec_parent + a.W;
+        s.rec_score = reinterpret_cast<double *>(rec + a.W); s.rec_lp = s.rec_score + a.W;
+        k_beam_select<BEAM_NT><<<dim3(1), dim3((a.W * (a.W + 1) + 63u) / 64u * 64u), 0, c->stream>>>(s);
+        HIPCHK(hipGetLastError());
+        return enqueue_gather(c, g);
+    }
+    // the one download: cum, ended, len, the parent map and the steps that ran, into the host image
+    int download(rwkv_ctx *c, uint64_t ran)
+    {
+        HIPCHK(hipMemcpyAsync(c->beam_host.data() + lay.cum, w + lay.cum, sizeof(double) * (lay.rec - lay.cum + ran * lay.step), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }
+    // behind the wait: step k of the record in the host image
+    const unsigned *h_parent(const rwkv_ctx *c, uint64_t k) const { return reinterpret_cast<const unsigned *>(c->beam_host.data() + lay.rec + k * lay.step); }
+    const double *h_score(const rwkv_ctx *c, uint64_t k) const { return reinterpret_cast<const double *>(c->beam_host.data() + lay.rec + k * lay.step + a.W); }
+};
+} // namespace
+
+int rwkv_decode_beam(rwkv_ctx *c, uint64_t first_token, uint64_t n_steps, const rwkv_beam_params *bp, const rwkv_beam_out *out)
+{
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, bp && out && out->tokens && out->len && out->score)) return rc;
+    if (const int rc = check_beam(c, bp)) return rc;
+    if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
+    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
+    if (!c->seq_ok) return fail(RWKV_E_STATE, "beam search needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
+    const uint64_t W = bp->width;
+    Beam b;
+    const int rc = finish(c, [&]() -> int {
+        uint64_t fed[RWKV_MAX_BEAM];
+        double cum[RWKV_MAX_BEAM];
+        for (uint64_t m = 0; m < W; m++) { fed[m] = first_token; cum[m] = m ? -INFINITY : 0.0; }
+        if (const int rc = b.setup(c, *bp, n_steps, fed, cum, nullptr, 0u)) return rc;
+        if (const int rc = enqueue_gather(c, b.g)) return rc;                                  // the fork: slots 1 .. W - 1 <- slot 0
+        for (uint64_t k = 0; k < n_steps; k++) {
+            if (const int rc = enqueue_rows(c, nullptr, b.ids + (k & 1) * W, W, RWKV_MODE_PARRALEL)) return rc;     // logits rows 0 .. W - 1, state slots 0 .. W - 1
+            if (const int rc = b.step(c, k)) return rc;
+        }
+        return b.download(c, n_steps);
+    }());
+    if (rc) return rc;
+    // backtrack: hypothesis m ends in beam m of the last step
+    const unsigned long long *h = c->beam_host.data();
+    const unsigned *len = reinterpret_cast<const unsigned *>(h + b.lay.flags) + W;
+    for (uint64_t m = 0; m < W; m++) {
+        out->len[m] = len[m];
+        memcpy(&out->score[m], &h[b.lay.cum + m], 8);
+        unsigned at = (unsigned)m;
+        for (uint64_t k = n_steps; k-- > 0;) {
+            const unsigned *par = b.h_parent(c, k);
+            const bool on = k < len[m];
+            out->tokens[m * n_steps + k] = on ? par[W + at] : 0ull;
+            if (out->token_logprob) out->token_logprob[m * n_steps + k] = on ? b.h_score(c, k)[W + at] : 0.0;
+            at = par[at] < W ? par[at] : 0u;
+        }
+    }
+    return 0;
+}
+
+int rwkv_debug_beam_step(rwkv_ctx *c, const rwkv_beam_params *bp, const double *cum, const uint8_t *ended, const uint64_t *last,
+                         uint32_t *parent, uint64_t *token, double *score, double *token_logprob, uint8_t *ended_out)
+{
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, bp && cum && ended && last && parent && token && score && token_logprob && ended_out)) return rc;
+    if (const int rc = check_beam(c, bp)) return rc;
+    const uint64_t W = bp->width;
+    if (const int rc = check_ids(last, W, "token")) return rc;
+    Beam b;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = b.setup(c, *bp, 1, last, cum, ended, ~0u)) return rc;
+        if (const int rc = b.step(c, 0)) return rc;
+        return b.download(c, 1);
+    }());
+    if (rc) return rc;
+    const unsigned *par = b.h_parent(c, 0), *end = reinterpret_cast<const unsigned *>(c->beam_host.data() + b.lay.flags);
+    for (uint64_t m = 0; m < W; m++) {
+        parent[m] = par[m]; token[m] = par[W + m];
+        score[m] = b.h_score(c, 0)[m]; token_logprob[m] = b.h_score(c, 0)[W + m];
+        ended_out[m] = end[m] ? 1 : 0;
+    }
+    return 0;
+}
+
+int rwkv_state_permute(rwkv_ctx *c, const uint32_t *parents, uint64_t n)
+{
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, parents)) return rc;
+    if (n == 0 || n > c->maxT) return fail(RWKV_E_ARG, "n must be in 1..%llu (max context)", (unsigned long long)c->maxT);
+    for (uint64_t m = 0; m < n; m++)
+        if (parents[m] >= n) return fail(RWKV_E_ARG, "parents[%llu] = %u is not below n = %llu", (unsigned long long)m, parents[m], (unsigned long long)n);
+    return finish(c, [&]() -> int {
+        int rc = grow_buffer(c, BEAM_REC, sizeof(double) * ((n + 1) / 2));
+        if (!rc) rc = grow_buffer(c, BEAM_STAGE, sizeof(double) * n * 5 * c->L * c->D);
+        if (rc) return rc;
+        unsigned *map = c->buf<unsigned>(BEAM_REC);
+        HIPCHK(hipMemcpyAsync(map, parents, sizeof(unsigned) * n, hipMemcpyHostToDevice, c->stream));
+        return enqueue_gather(c, gather_args(c, map, n));
     }());
 }
 

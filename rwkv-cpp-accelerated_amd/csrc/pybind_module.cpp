@@ -30,10 +30,10 @@ PYBIND11_MODULE(rwkv, m)
 {
     m.def("initRwkv", []() { return reinterpret_cast<std::uintptr_t>(new RWKV()); }, "initRwkv");
     m.def("freeRwkv", [](std::uintptr_t h) { delete M(h); }, "destroy a handle (engine extension)");
-    m.def("loadModel", [](std::uintptr_t h, const std::string &filename) {
-        M(h)->loadFile(filename);
+    m.def("loadModel", [](std::uintptr_t h, const std::string &filename, unsigned long long maxGPT) {
+        M(h)->loadFile(filename, maxGPT);
         return std::make_tuple((int64_t)M(h)->num_layers, (int64_t)M(h)->num_embed);
-    }, "load");
+    }, "load (maxGPT: state slots and logits rows, 1 as in the reference; decodeBeam needs its width)", py::arg("rwkvp"), py::arg("filename"), py::arg("maxGPT") = 1ull);
     m.def("modelForward", [](std::uintptr_t h, int64_t token) { M(h)->forward((unsigned long long)token); }, "rwkvc");
     m.def("initState", [](std::uintptr_t h) {
         RWKV *r = M(h);
@@ -124,4 +124,37 @@ PYBIND11_MODULE(rwkv, m)
         std::copy(t.logprob.begin(), t.logprob.end(), lp.mutable_data());
         return py::make_tuple(ids, lp);
     }, "(ids, f64 log-probabilities) [len(rows)][top_n]: the top_n most probable tokens of logits rows of the last forward, computed on the device (engine extension)");
+    m.def("decodeBeam", [](std::uintptr_t h, int64_t first, int64_t n, unsigned width, const std::vector<int64_t> &stops) {
+        RWKV::Beam beam;
+        beam.width = width;
+        beam.stop_ids.assign(stops.begin(), stops.end());
+        const RWKV::BeamResult r = M(h)->decodeBeam((unsigned long long)first, (unsigned long long)n, beam);
+        py::array_t<int64_t> tokens({(size_t)width, (size_t)n}), len((size_t)width);
+        py::array_t<double> score((size_t)width), lp({(size_t)width, (size_t)n});
+        std::copy(r.tokens.begin(), r.tokens.end(), tokens.mutable_data());
+        std::copy(r.len.begin(), r.len.end(), len.mutable_data());
+        std::copy(r.score.begin(), r.score.end(), score.mutable_data());
+        std::copy(r.token_logprob.begin(), r.token_logprob.end(), lp.mutable_data());
+        return py::make_tuple(tokens, len, score, lp);
+    }, "beam search ON THE DEVICE from the state slot 0 holds (load with maxGPT >= width): (tokens [width][n], len [width], score [width], "
+       "token log-probs [width][n]); hypothesis 0 is the best, entries behind a hypothesis's end are 0 (engine extension)",
+          py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("width") = 4u, py::arg("stops") = std::vector<int64_t>{});
+    m.def("beamSelect", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> top_ids, py::array_t<double, py::array::c_style | py::array::forcecast> top_lp,
+                           py::array_t<double, py::array::c_style | py::array::forcecast> cum, const std::vector<int> &ended, const std::vector<int64_t> &last,
+                           const std::vector<int64_t> &stops) {
+        const size_t W = (size_t)cum.size();
+        if (W < 1 || (size_t)top_ids.size() != W * (W + 1) || (size_t)top_lp.size() != W * (W + 1) || ended.size() != W || last.size() != W)
+            throw py::value_error("beamSelect: top_ids and top_lp [W][W + 1], cum, ended and last [W]");
+        std::vector<unsigned long long> ids(top_ids.data(), top_ids.data() + W * (W + 1)), l(last.begin(), last.end()), st(stops.begin(), stops.end());
+        std::vector<unsigned char> e(ended.begin(), ended.end());
+        const std::vector<beam_pick> r = beam_select((unsigned)W, ids.data(), top_lp.data(), cum.data(), e.data(), l.data(), st);
+        py::array_t<int64_t> parent(r.size()), token(r.size()), end(r.size());
+        py::array_t<double> score(r.size()), lp(r.size());
+        for (size_t m = 0; m < r.size(); m++) {
+            parent.mutable_data()[m] = r[m].parent; token.mutable_data()[m] = (int64_t)r[m].token; end.mutable_data()[m] = r[m].ended ? 1 : 0;
+            score.mutable_data()[m] = r[m].score; lp.mutable_data()[m] = r[m].token_logprob;
+        }
+        return py::make_tuple(parent, token, score, lp, end);
+    }, "one beam-search selection ON THE HOST (include/rwkv_sampler.h beam_select, the twin of the device's): from the rows' top W + 1 ids and "
+       "log-probs, cum, ended and last [W] and the stop ids -> (parent, token, score, token log-prob, ended) [W] (engine extension)");
 }

@@ -38,7 +38,9 @@ ABI_SYMBOLS = [
     "rwkv_sample_nucleus", "rwkv_decode_nucleus", "rwkv_decode_batch_nucleus", "rwkv_penalty_set", "rwkv_penalty_get",
     "rwkv_decode_batch_until", "rwkv_debug_stop_scan",
     "rwkv_topn_rows", "rwkv_decode_batch_logprobs",
+    "rwkv_decode_beam", "rwkv_state_permute", "rwkv_debug_beam_step",
 ]
+BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 TOPN_MAX = 32                     # RWKV_MAX_TOPN
 LOGPROB_ENTRIES_MAX = 1 << 22     # RWKV_MAX_LOGPROB_ENTRIES: n_streams * n_steps * (1 + top_n) of one call
@@ -82,6 +84,24 @@ class LogprobOut(C.Structure):
     """rwkv_logprob_out of include/rwkv_mi355x.h (40 bytes)"""
     _fields_ = [("top_n", C.c_uint32), ("reserved", C.c_uint32), ("logprob", C.POINTER(C.c_double)), ("entropy", C.POINTER(C.c_double)),
                 ("top_ids", C.POINTER(C.c_uint64)), ("top_logprob", C.POINTER(C.c_double))]
+
+
+class BeamParams(C.Structure):
+    """rwkv_beam_params of include/rwkv_mi355x.h (24 bytes)"""
+    _fields_ = [("width", C.c_uint32), ("n_stop", C.c_uint32), ("stop_ids", C.POINTER(C.c_uint64)), ("reserved", C.c_uint64)]
+
+
+class BeamOut(C.Structure):
+    """rwkv_beam_out of include/rwkv_mi355x.h (32 bytes)"""
+    _fields_ = [("tokens", C.POINTER(C.c_uint64)), ("len", C.POINTER(C.c_uint32)), ("score", C.POINTER(C.c_double)),
+                ("token_logprob", C.POINTER(C.c_double))]
+
+
+def beam_params(width, stops=()):
+    """(BeamParams, the array it points into -- keep it alive for the call)"""
+    st = [int(t) for t in stops]
+    ids = (C.c_uint64 * max(1, len(st)))(*st)
+    return BeamParams(int(width), len(st), ids if st else None, 0), ids
 
 
 class RWKVError(RuntimeError):
@@ -168,6 +188,11 @@ def lib():
     L.rwkv_decode_batch_logprobs.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(StopParams), C.POINTER(LogprobOut),
                                              C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]
     L.rwkv_decode_batch_logprobs.restype = i32
+    L.rwkv_decode_beam.argtypes = [vp, u64, u64, C.POINTER(BeamParams), C.POINTER(BeamOut)]; L.rwkv_decode_beam.restype = i32
+    L.rwkv_state_permute.argtypes = [vp, C.POINTER(C.c_uint32), u64]; L.rwkv_state_permute.restype = i32
+    L.rwkv_debug_beam_step.argtypes = [vp, C.POINTER(BeamParams), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(u64), C.POINTER(C.c_uint32),
+                                       C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
+    L.rwkv_debug_beam_step.restype = i32
     _lib = L
     return L
 
@@ -551,6 +576,63 @@ class RWKV:
         _chk(lib().rwkv_topn_rows(self._h, (C.c_uint64 * max(1, n))(*r), n, top_n, ids.ctypes.data_as(C.POINTER(C.c_uint64)),
                                   lp.ctypes.data_as(C.POINTER(C.c_double))))
         return ids[: n * top_n].astype(np.int64).reshape(n, top_n), lp[: n * top_n].reshape(n, top_n)
+
+    # -- beam search on the device (include/rwkv_mi355x.h rwkv_decode_beam) ---------------------------------------------------
+    def decode_beam(self, first_token: int, n_steps: int, width: int = 4, stops=()):
+        """the `width` most probable continuations of the prompt whose state slot 0 holds, fed first_token, n_steps long; stops: single-token stop
+        ids that end a hypothesis.  Returns (tokens [W][n_steps], 0 behind a hypothesis's end; len [W]; score [W], the sum of the token
+        log-probs; token_logprob [W][n_steps]); hypothesis 0 is the best.  Slot m is left where live hypothesis m ended: feed
+        tokens[m][len[m] - 1] to go on.  A length penalty is the caller's: rank by score / len ** a."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        W, n = int(width), int(n_steps)
+        e = max(1, W * n)
+        tok, lp = np.zeros(e, dtype=np.uint64), np.zeros(e, dtype=np.float64)
+        ln, sc = np.zeros(max(1, W), dtype=np.uint32), np.zeros(max(1, W), dtype=np.float64)
+        bp, alive = beam_params(W, stops)
+        out = BeamOut(tok.ctypes.data_as(C.POINTER(C.c_uint64)), ln.ctypes.data_as(C.POINTER(C.c_uint32)), sc.ctypes.data_as(C.POINTER(C.c_double)),
+                      lp.ctypes.data_as(C.POINTER(C.c_double)))
+        if not self.resident:
+            self.push_state(1)          # host state is authoritative: the prompt's state is its slot 0 ...
+        _chk(lib().rwkv_decode_beam(self._h, int(first_token), n, C.byref(bp), C.byref(out)))
+        if not self.resident:
+            self.pull_state(W)          # ... and every slot is left where its hypothesis ended
+        del alive
+        return tok[: W * n].astype(np.int64).reshape(W, n), ln[:W].astype(np.int64), sc[:W].copy(), lp[: W * n].reshape(W, n)
+
+    def state_permute(self, parents):
+        """slot m <- what slot parents[m] held, for every m < len(parents) at once (rwkv_state_permute; any map: swaps, cycles, fan-out); the
+        other slots and the logits stay.  Re-fork the survivors of a best-of-n: state_permute([best, best, second, second])."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        p = [int(v) for v in parents]
+        _chk(lib().rwkv_state_permute(self._h, (C.c_uint32 * max(1, len(p)))(*p), len(p)))
+        if not self.resident:           # the host copy is the authoritative one
+            n = self.num_layers * self.num_embed
+            for a in self.state.arrays():
+                old = a.copy()
+                for m, q in enumerate(p):
+                    a[m * n:(m + 1) * n] = old[q * n:(q + 1) * n]
+
+    def debug_beam_step(self, cum, ended, last, stops=()):
+        """ONE selection and state gather on whatever logits rows 0 .. W - 1 and the state slots hold (rwkv_debug_beam_step), W = len(cum):
+        (parent [W], token [W], score [W], token_logprob [W], ended [W])"""
+        c = np.ascontiguousarray(cum, dtype=np.float64)
+        W = c.size
+        e = np.ascontiguousarray([1 if v else 0 for v in ended], dtype=np.uint8)
+        l = np.ascontiguousarray([int(v) for v in last], dtype=np.uint64)
+        if e.size != W or l.size != W:
+            raise ValueError("cum, ended and last have one entry per beam")
+        bp, alive = beam_params(W, stops)
+        par, tok = np.zeros(max(1, W), dtype=np.uint32), np.zeros(max(1, W), dtype=np.uint64)
+        sc, lp, eo = np.zeros(max(1, W), dtype=np.float64), np.zeros(max(1, W), dtype=np.float64), np.zeros(max(1, W), dtype=np.uint8)
+        dp = C.POINTER(C.c_double)
+        _chk(lib().rwkv_debug_beam_step(self._h, C.byref(bp), c.ctypes.data_as(dp), e.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                        l.ctypes.data_as(C.POINTER(C.c_uint64)), par.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        tok.ctypes.data_as(C.POINTER(C.c_uint64)), sc.ctypes.data_as(dp), lp.ctypes.data_as(dp),
+                                        eo.ctypes.data_as(C.POINTER(C.c_uint8))))
+        del alive
+        return par[:W].astype(np.int64), tok[:W].astype(np.int64), sc[:W].copy(), lp[:W].copy(), eo[:W].astype(np.int64)
 
     def debug_stop_scan(self, ids, first_tokens, stops=(), max_new=None, keep: bool = False):
         """the stop test alone over PLANTED picks ids [n][steps] (rwkv_debug_stop_scan): (len [n], reason [n]); stream s uses slot s's history"""
