@@ -433,10 +433,70 @@ public:
         }
         rwkv_detail::check(rwkv_state_permute(ctx_, p.data(), p.size()));
     }
+    // constrained decoding on the device (rwkv_mi355x.h "constrained decoding"): a token-level automaton in CSR form -- compiled from a regex,
+    // a grammar or a choice list by a library of the caller's; include/rwkv_sampler.h constraint_trie builds the choice-list case -- and a sparse
+    // logit bias per stream decide what may be generated at all.  setConstraint validates, uploads and puts every slot's automaton state to 0.
+    struct Automaton { std::vector<unsigned> row_ptr, tok, next; };      // the edges of state q: row_ptr[q] .. row_ptr[q + 1]; no edges: terminal
+    struct Bias { std::vector<unsigned> tok; std::vector<float> val; };  // ids strictly ascending, 1 .. 50276; finite or -inf (-inf bans the id)
+    void setConstraint(const Automaton &a)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (a.row_ptr.empty() || a.tok.size() != a.next.size()) throw std::runtime_error("an automaton needs row_ptr [S + 1] and as many next as tok");
+        const rwkv_automaton ra{(uint32_t)(a.row_ptr.size() - 1), 0u, (uint64_t)a.tok.size(), a.row_ptr.data(), a.tok.data(), a.next.data()};
+        rwkv_detail::check(rwkv_constraint_set(ctx_, &ra));
+    }
+    void clearConstraint() { rwkv_detail::check(rwkv_constraint_clear(ctx_)); }
+    // one constrained draw from logits row `row` of the last forward under the automaton state of slot `slot` (u: the nucleus pick's uniform);
+    // advance: the slot's state moves along the pick.  Returns (token, the slot's state on return)
+    std::pair<unsigned long long, unsigned> pickConstrained(const Pick &pick, const Bias &bias = Bias{}, double u = 0.0, bool advance = true,
+                                                            unsigned long long row = 0, unsigned long long slot = 0, bool update = false)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (bias.tok.size() != bias.val.size()) throw std::runtime_error("a bias list needs as many values as ids");
+        rwkv_pick p{};
+        p.kind = pick.kind; p.temp = pick.temp; p.tau = pick.tau;
+        p.nucleus = nucleusParams(pick.s, update ? RWKV_NUCLEUS_UPDATE : 0u);
+        const rwkv_bias b{(uint32_t)bias.tok.size(), 0u, bias.tok.data(), bias.val.data()};
+        uint64_t tok = 0;
+        uint32_t q = 0;
+        rwkv_detail::check(rwkv_pick_constrained(ctx_, row, slot, &p, bias.tok.empty() ? nullptr : &b, u, advance ? 1 : 0, &tok, &q));
+        return {tok, q};
+    }
+    // decodeBatchUntil under the constraint: stream s starts in start[s] (empty: in the slot's current state) with the bias list bias[s] (empty:
+    // none) and also ends where its automaton reaches a terminal state (reason RWKV_STOP_CONSTRAINT).  state[s]: the slot's automaton state after
+    // consuming the stream's len[s] tokens
+    struct Constrained { Until until; std::vector<unsigned> state; };
+    Constrained decodeConstrained(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                                  const std::vector<unsigned long long> &seeds)
+    {
+        return decodeConstrained(first, n, pick, seeds, Stop(), {}, {});      // no stops, the slots' current states, no bias
+    }
+    Constrained decodeConstrained(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                                  const std::vector<unsigned long long> &seeds, const Stop &stop, const std::vector<unsigned> &start,
+                                  const std::vector<Bias> &bias = {})
+    {
+        if (!start.empty() && start.size() != first.size()) throw std::runtime_error("need one start state per stream");
+        if (!bias.empty() && bias.size() != first.size()) throw std::runtime_error("need one bias list per stream");
+        std::vector<uint32_t> bptr(1, 0u), btok;
+        std::vector<float> bval;
+        btok.reserve(1); bval.reserve(1);      // (all lists empty: the arrays are still there)
+        for (const Bias &b : bias) {
+            if (b.tok.size() != b.val.size()) throw std::runtime_error("a bias list needs as many values as ids");
+            btok.insert(btok.end(), b.tok.begin(), b.tok.end()); bval.insert(bval.end(), b.val.begin(), b.val.end());
+            bptr.push_back((uint32_t)btok.size());
+        }
+        Constrained r;
+        r.state.resize(first.size());
+        const rwkv_constrain_params cp{start.empty() ? nullptr : start.data(), bias.empty() ? nullptr : bptr.data(), bias.empty() ? nullptr : btok.data(),
+                                       bias.empty() ? nullptr : bval.data(), r.state.data(), 0};
+        r.until = until_call(first, n, pick, seeds, stop, nullptr, &cp);
+        return r;
+    }
 private:
-    // decodeBatchUntil, and with `lp` decodeBatchLogprobs: one preparation of the C ABI's records, one push / pull of host-authoritative state
+    // decodeBatchUntil, with `lp` decodeBatchLogprobs and with `cp` decodeConstrained: one preparation of the C ABI's records, one push / pull of
+    // host-authoritative state
     Until until_call(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
-                     const std::vector<unsigned long long> &seeds, const Stop &stop, const rwkv_logprob_out *lp)
+                     const std::vector<unsigned long long> &seeds, const Stop &stop, const rwkv_logprob_out *lp, const rwkv_constrain_params *cp = nullptr)
     {
         if (!ready) throw std::runtime_error("RWKV not loaded");
         if (pick.kind != RWKV_PICK_GREEDY && seeds.size() != first.size()) throw std::runtime_error("need one seed per stream");
@@ -453,7 +513,8 @@ private:
         uint64_t ran = 0;
         if (!residentState) pushState();      // host state is authoritative: continue from it ...
         const uint64_t *sdp = pick.kind == RWKV_PICK_GREEDY ? nullptr : sd.data();
-        rwkv_detail::check(lp ? rwkv_decode_batch_logprobs(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
+        rwkv_detail::check(cp ? rwkv_decode_batch_constrained(ctx_, ft.data(), ft.size(), n, &p, sdp, cp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
+                           : lp ? rwkv_decode_batch_logprobs(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
                               : rwkv_decode_batch_until(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, ids.data(), len.data(), reason.data(), &ran));
         if (!residentState) pullState();      // ... and leave every slot where its stream stopped
         r.ids.assign(ids.begin(), ids.end()); r.len.assign(len.begin(), len.end()); r.reason.assign(reason.begin(), reason.end()); r.steps_run = ran;

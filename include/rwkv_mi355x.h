@@ -416,6 +416,96 @@ int rwkv_state_permute(rwkv_ctx *ctx, const uint32_t *parents, uint64_t n);
 int rwkv_debug_beam_step(rwkv_ctx *ctx, const rwkv_beam_params *params, const double *cum, const uint8_t *ended, const uint64_t *last,
                          uint32_t *parent, uint64_t *token, double *score, double *token_logprob, uint8_t *ended_out);
 
+/* ---- constrained decoding on the device: a token automaton and a logit bias (no reference counterpart: the reference only samples) ----
+ * The control of a completion API that restricts what may be generated at all: `logit_bias` and banned ids, "answer with one of these strings",
+ * JSON / regex / grammar output.  What it replaces is a caller's loop of rwkv_forward, a 201 KB download per stream, a mask on the host, an upload of
+ * the row and rwkv_sample_nucleus.  The project has no tokenizer: the caller compiles the regex / grammar / choice list to a token-level automaton
+ * with a library of their own and this engine runs it (include/rwkv_sampler.h constraint_trie builds the choice-list case).
+ * Automaton.  S states (1 .. RWKV_CONSTRAINT_MAX_STATES) in CSR form: row_ptr u32 [S + 1], tok u32 [nnz], next u32 [nnz], nnz <=
+ * RWKV_CONSTRAINT_MAX_EDGES.  The edges of state q are row_ptr[q] .. row_ptr[q + 1]; row_ptr[0] = 0, row_ptr is non-decreasing and row_ptr[S] = nnz;
+ * inside a row tok is strictly ascending; every tok lies in 1 .. 50276 (id 0 is never generated by a device loop, so an edge on it is rejected);
+ * every next < S.  A state without edges is TERMINAL.  Each state slot owns one automaton state q[max_ctx] (u32 on the device, with a host copy so
+ * that checks need no launch).
+ * Bias list.  Per stream and sparse: at most RWKV_CONSTRAINT_MAX_BIAS pairs (id strictly ascending, 1 .. 50276; f32 value, finite or -inf: -inf
+ * bans the id).
+ * Constrained row.  Of logits row l under state q and bias b: c_i = l_i + b_i where q has an edge on i -- ONE f32 add, b_i = 0 where i is not
+ * listed -- and c_i = -inf otherwise: i = 0 included, and a listed id that q does not allow too.
+ * Constrained pick.  The EXISTING pick run on c instead of l: greedy is k_argmax_rows and its finish (ties to the lowest id, id 0 skipped);
+ * nucleus is the three nucleus launches without the ban (the row already holds -inf at id 0); penalties, counts, seeds and u of step k are exactly
+ * those of the plain loops.  RWKV_PICK_TYPICAL under a constraint is RWKV_E_ARG.  After pick g the slot advances: q <- next[e] for the edge e of q
+ * with tok[e] == g.
+ * GUARANTEED: a pick is always an id that q allows (with NaN or +inf logits the pick is unspecified but below 50277, q then stays, and nothing
+ * faults); the model's logits buffer is never written -- c lives in a second buffer packed like it -- so the log-probs of the log-prob hook stay
+ * the MODEL's; rows, state and counts of an unconstrained call are bit for bit what they are without this block.
+ *
+ * rwkv_constraint_set validates on the host in O(nnz) (include/rwkv_sampler.h constraint_check is the one validator), uploads the CSR, builds a bit
+ * mask [S][1572] u32 on the device (6288 bytes per state; the row of a terminal state allows every id but 0: a row that keeps running behind its
+ * stream's end must still pick a valid id, and its picks are discarded) and puts every slot's q to 0; a rejected set leaves the previous automaton
+ * installed.  rwkv_constraint_clear removes it (and puts every q to 0).  The CSR, the mask, the second row buffer ([max_ctx][50277] f32, allocated by the
+ * first call that needs it) and q belong to the context: counted by rwkv_resident_bytes, freed with it.
+ * rwkv_constraint_state_set / _get write and read q[slot0 .. slot0 + n) (set: every state < S; without an automaton only 0).
+ * rwkv_pick_constrained is the single draw, as rwkv_sample_nucleus is for the plain sampler: it reads logits row `row` of the LAST forward under
+ * q[slot] and `bias` (may be NULL), with slot's counts for penalties (updated only with RWKV_NUCLEUS_UPDATE; RWKV_NUCLEUS_BAN0 changes nothing
+ * here), leaves logits and state alone and advances q[slot] only with `advance`; *state_out (may be NULL) is q[slot] on return.
+ * rwkv_debug_constrained_row downloads row `row` of the second buffer as the last constrained pick or step left it (tests).
+ * rwkv_decode_batch_constrained is rwkv_decode_batch_logprobs with the constraint hook: stream s on slot s starts in start[s] (NULL: in the slot's
+ * current q) under its own bias list -- bias_ptr [n_streams + 1] into bias_tok / bias_val; all three NULL for none -- and ends, besides at stop
+ * sequences and budgets (stop may be NULL) where its automaton reaches a terminal state: out_reason RWKV_STOP_CONSTRAINT, reported at the call's
+ * last step too.  Of several ends at one step a stop sequence (2 + j) wins over the constraint, and the constraint over the budget (1).  lp may
+ * be NULL (no record).  out_state (may be NULL) receives q[s].  n_streams == 1 runs the decode kernels, more streams the PARRALEL step, as
+ * everywhere else.  Without an installed automaton the call constrains by the bias lists alone: one implicit state that allows every id but 0
+ * (start must then be NULL or all 0).
+ * The invariant, as for the until call: after the call slot s holds bit for bit what the same call with n_steps = out_len[s] and no stops leaves --
+ * the five state arrays, logits row s (the model's), the counts and q[s], the state after consuming out_tokens[s][0 .. out_len[s]).  A
+ * constrained call always parks and unparks like a call that can stop a stream.  With the KEEP flags, start = NULL and seed + 8 a 16-step call equals
+ * an 8-step call followed by an 8-step call.
+ * Inside the loop there is no host synchronisation and no copy beyond what the until call does; per step the call adds two launches
+ * (k_constrain_rows: one read of 201 KB + 6.3 KB and one write of 201 KB per row, not a walk over the edges; k_constraint_advance) and one
+ * `done` word per stream for k_stop_step; the one-stream greedy loop also runs the row pick's two launches in place of the token graph's pick node.
+ * Status: RWKV_E_ARG for whatever the log-prob / until call rejects, a malformed automaton or bias list (each rule above), a start state >= S or
+ * terminal (also through a slot's kept state), RWKV_PICK_TYPICAL, reserved != 0; RWKV_E_STATE as for the batch calls.  Every check runs before
+ * anything is launched or allocated: a rejected call leaves state, logits, counts, histories, q, the installed automaton and the buffers as they were.
+ * Out of scope: beam search under a constraint; typical sampling under a constraint (k_typical_stats forms e * d with d = -inf); log-probs under
+ * the constrained distribution; compiling a grammar or regex (the caller brings the automaton); applying the mask inside the pick kernels instead
+ * of through a second row. */
+#define RWKV_CONSTRAINT_MAX_STATES 4096u
+#define RWKV_CONSTRAINT_MAX_EDGES (1u << 24)
+#define RWKV_CONSTRAINT_MAX_BIAS 300u
+#define RWKV_STOP_CONSTRAINT 32u /* out_reason: the stream's automaton reached a terminal state */
+typedef struct rwkv_automaton {
+    uint32_t n_states;       /* S: 1 .. RWKV_CONSTRAINT_MAX_STATES */
+    uint32_t reserved;       /* must be 0 */
+    uint64_t nnz;            /* <= RWKV_CONSTRAINT_MAX_EDGES */
+    const uint32_t *row_ptr; /* host [S + 1] */
+    const uint32_t *tok;     /* host [nnz]; may be NULL when nnz == 0 */
+    const uint32_t *next;    /* host [nnz]; likewise */
+} rwkv_automaton;
+typedef struct rwkv_bias {
+    uint32_t n;          /* 0 .. RWKV_CONSTRAINT_MAX_BIAS */
+    uint32_t reserved;   /* must be 0 */
+    const uint32_t *tok; /* host [n], strictly ascending, 1 .. 50276 */
+    const float *val;    /* host [n], finite or -inf */
+} rwkv_bias;
+typedef struct rwkv_constrain_params {
+    const uint32_t *start;    /* host [n_streams]; NULL: continue from the slots' current q */
+    const uint32_t *bias_ptr; /* host [n_streams + 1], bias_ptr[0] = 0, non-decreasing; NULL (with bias_tok and bias_val): no bias */
+    const uint32_t *bias_tok; /* host [bias_ptr[n_streams]] */
+    const float *bias_val;    /* the same shape */
+    uint32_t *out_state;      /* host [n_streams], may be NULL */
+    uint64_t reserved;        /* must be 0 */
+} rwkv_constrain_params;
+int rwkv_constraint_set(rwkv_ctx *ctx, const rwkv_automaton *automaton);
+int rwkv_constraint_clear(rwkv_ctx *ctx);
+int rwkv_constraint_state_set(rwkv_ctx *ctx, uint64_t slot0, uint64_t n, const uint32_t *states);
+int rwkv_constraint_state_get(rwkv_ctx *ctx, uint64_t slot0, uint64_t n, uint32_t *states);
+int rwkv_pick_constrained(rwkv_ctx *ctx, uint64_t row, uint64_t slot, const rwkv_pick *pick, const rwkv_bias *bias /* may be NULL */, double u,
+                          int advance, uint64_t *token, uint32_t *state_out /* may be NULL */);
+int rwkv_debug_constrained_row(rwkv_ctx *ctx, uint64_t row, float *dst /* host [50277] */);
+int rwkv_decode_batch_constrained(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                                  const uint64_t *seeds, const rwkv_constrain_params *constrain, const rwkv_stop_params *stop /* may be NULL */,
+                                  const rwkv_logprob_out *lp /* may be NULL */, uint64_t *out_tokens, uint32_t *out_len, uint32_t *out_reason,
+                                  uint64_t *steps_run);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

@@ -236,6 +236,103 @@ inline std::vector<beam_pick> beam_select(unsigned W, const unsigned long long *
     return out;
 }
 
+// ---- constrained decoding: the host twins of csrc/constrain.hip.h and the ONE validator of automata and bias lists (the semantics are those of
+// include/rwkv_mi355x.h rwkv_decode_batch_constrained).  An automaton is S states in CSR form -- the edges of state q are row_ptr[q] ..
+// row_ptr[q + 1], tok strictly ascending inside a row, 1 .. 50276, next < S; a state without edges is terminal -- a bias list at most 300 pairs
+// (id strictly ascending, 1 .. 50276; value finite or -inf).
+struct constraint_automaton {
+    std::vector<unsigned> row_ptr, tok, next;             // [S + 1], [nnz], [nnz]
+    unsigned states() const { return row_ptr.empty() ? 0u : (unsigned)row_ptr.size() - 1u; }
+};
+struct constraint_view { unsigned long long S; const unsigned *row_ptr; unsigned long long nnz; const unsigned *tok, *next; };
+struct bias_view { unsigned long long n; const unsigned *tok; const float *val; };
+// nullptr when the automaton (a != nullptr) and the bias list (b != nullptr) are well formed, else the NAME of the first rule broken:
+// "states" (S = 0 or above 4096), "edges" (nnz above 1 << 24), "row_ptr" (a NULL array, row_ptr[0] != 0 or not non-decreasing), "row_ptr_end"
+// (row_ptr[S] != nnz), "tok_range" (0 or >= 50277), "tok_order" (unsorted or duplicate inside a row), "next" (>= S), "bias_count" (above 300),
+// "bias_range", "bias_order", "bias_value" (NaN or +inf).  O(nnz + n).
+inline const char *constraint_check(const constraint_view *a, const bias_view *b)
+{
+    if (a) {
+        if (a->S == 0 || a->S > 4096ull) return "states";
+        if (a->nnz > (1ull << 24)) return "edges";
+        if (!a->row_ptr || (a->nnz && (!a->tok || !a->next)) || a->row_ptr[0] != 0u) return "row_ptr";
+        for (unsigned long long q = 0; q < a->S; q++)
+            if (a->row_ptr[q + 1] < a->row_ptr[q]) return "row_ptr";
+        if (a->row_ptr[a->S] != a->nnz) return "row_ptr_end";
+        for (unsigned long long q = 0; q < a->S; q++)
+            for (unsigned e = a->row_ptr[q]; e < a->row_ptr[q + 1]; e++) {
+                if (a->tok[e] == 0u || a->tok[e] >= 50277u) return "tok_range";
+                if (e > a->row_ptr[q] && a->tok[e] <= a->tok[e - 1]) return "tok_order";
+                if (a->next[e] >= a->S) return "next";
+            }
+    }
+    if (b) {
+        if (b->n > 300ull) return "bias_count";
+        if (b->n && (!b->tok || !b->val)) return "bias_range";
+        for (unsigned long long i = 0; i < b->n; i++) {
+            if (b->tok[i] == 0u || b->tok[i] >= 50277u) return "bias_range";
+            if (i && b->tok[i] <= b->tok[i - 1]) return "bias_order";
+            if (std::isnan(b->val[i]) || b->val[i] == INFINITY) return "bias_value";
+        }
+    }
+    return nullptr;
+}
+// the constrained row of logits row l under state q and bias b, bit for bit the device's (k_constrain_rows): c_i = l_i + b_i (one f32 add, b_i = 0
+// where i is not listed) where q has an edge on i, -inf otherwise.  a == nullptr: the implicit state that allows every id but 0.  A TERMINAL state
+// allows every id but 0 too: the row a stream keeps running on behind its end
+inline void constrained_row(const float *l, const constraint_view *a, unsigned q, const bias_view *b, float *c)
+{
+    const int len = 50277;
+    const bool all = !a || a->row_ptr[q] == a->row_ptr[q + 1];
+    std::vector<unsigned char> allowed(len, all ? 1 : 0);
+    allowed[0] = 0;
+    for (unsigned e = all ? 0u : a->row_ptr[q]; !all && e < a->row_ptr[q + 1]; e++) allowed[a->tok[e]] = 1;
+    std::vector<float> bias(len, 0.0f);
+    for (unsigned long long i = 0; b && i < b->n; i++) bias[b->tok[i]] = b->val[i];
+    for (int i = 0; i < len; i++) {
+        volatile float sum = l[i] + bias[i];                // (one rounding to f32, whatever the host's evaluation width)
+        c[i] = allowed[i] ? sum : -INFINITY;
+    }
+}
+// the state after pick g in state q (k_constraint_advance): next[e] for the edge e of q with tok[e] == g; q itself when q has no edge on g
+inline unsigned constraint_next(const constraint_view *a, unsigned q, unsigned g)
+{
+    const unsigned *lo = a->tok + a->row_ptr[q], *hi = a->tok + a->row_ptr[q + 1];
+    const unsigned *e = std::lower_bound(lo, hi, g);
+    return e != hi && *e == g ? a->next[e - a->tok] : q;
+}
+// The automaton that spells exactly one of the given token sequences (the multiple-choice case): a trie, shared prefixes merged, state 0 the root,
+// states numbered in the order the choices first reach them, every leaf terminal.  "Exactly one of" under greedy or sampled decoding means: the
+// stream ends (RWKV_STOP_CONSTRAINT) when it reaches a state WITHOUT edges.  A choice that is a proper prefix of another one ends in a state that
+// has edges, so the automaton cannot end there: such a choice is accepted as a path, but a stream that follows it goes on to one of its
+// extensions -- the caller ends the shorter choice with its own end-of-choice token if both must be reachable.  Empty choices and ids outside
+// 1 .. 50276 are skipped.
+inline constraint_automaton constraint_trie(const std::vector<std::vector<unsigned long long>> &choices)
+{
+    std::vector<std::vector<std::pair<unsigned, unsigned>>> kids(1);      // per state: (tok, next)
+    for (const auto &ch : choices) {
+        bool ok = !ch.empty();
+        for (unsigned long long t : ch) ok = ok && t >= 1 && t < 50277ull;
+        if (!ok) continue;
+        unsigned q = 0;
+        for (unsigned long long t : ch) {
+            unsigned nx = 0;
+            bool found = false;
+            for (const auto &kv : kids[q]) if (kv.first == (unsigned)t) { nx = kv.second; found = true; }
+            if (!found) { nx = (unsigned)kids.size(); kids[q].emplace_back((unsigned)t, nx); kids.emplace_back(); }
+            q = nx;
+        }
+    }
+    constraint_automaton A;
+    A.row_ptr.push_back(0u);
+    for (auto &k : kids) {
+        std::sort(k.begin(), k.end());
+        for (const auto &kv : k) { A.tok.push_back(kv.first); A.next.push_back(kv.second); }
+        A.row_ptr.push_back((unsigned)A.tok.size());
+    }
+    return A;
+}
+
 inline int typical(float *_logits, float _temp = 0.9, float _tau = 0.8)
 {
     const std::vector<double> probs = typical_weights(_logits, _temp, _tau);

@@ -13,7 +13,9 @@
 #include "topn.hip.h"
 #include "stop.hip.h"
 #include "beam.hip.h"
+#include "constrain.hip.h"
 #include "../../include/rwkv_mi355x.h"
+#include "../../include/rwkv_sampler.h"
 
 #include <dlfcn.h>
 
@@ -232,6 +234,12 @@ enum GrownBuf {
                                       // ended, len u32 [2][W] | parent map u32 [W] + padding | per step: parent, token u32 [2][W] | score [W] | token log-prob [W];
                                       // rwkv_state_permute: the parent map u32 [n]
     BEAM_STAGE,                       // f64 [n][5][L D]: where the state gather sets the parents' slots aside
+    CN_CSR,                           // constrained decoding (constrain.hip.h), u32: row_ptr [S + 1] | tok [nnz] | next [nnz] of the installed automaton
+    CN_MASK,                          // u32 [S][CN_WORDS]: the automaton's states as bit masks over the vocabulary
+    CN_MASK1,                         // u32 [CN_WORDS]: the implicit state of a constrained call without an automaton (every id but 0)
+    CN_ROWS,                          // f32 [max_ctx][V]: the constrained rows, packed like the logits buffer; allocated ONCE by the first call that needs it
+    CN_Q,                             // u32 [max_ctx]: the slots' automaton states (cn_q is the host copy); allocated ONCE, zeroed
+    CN_CALL,                          // u32, one call's upload: bias_ptr [n + 1] | bias tok [nb] | bias val f32 [nb]; behind it done [n]
     N_GROWN
 };
 
@@ -338,6 +346,11 @@ struct rwkv_ctx {
     unsigned long long *stop_ring = nullptr;      // pinned
     hipEvent_t stop_ev[STOP_RING] = {};
     std::vector<unsigned> stop_host;              // host image of STOP_RUN: the call's upload, and the download of lengths and reasons
+    // constrained decoding: the installed automaton's size and host copy of row_ptr (cn_S == 0: none), the host copy of the slots' states
+    // (kept equal to CN_Q by every call that writes it: checks need no launch) and the staging of a call's upload
+    unsigned cn_S = 0;
+    size_t cn_nnz = 0;
+    std::vector<unsigned> cn_row_ptr, cn_q, cn_host;
     std::vector<void *> allocs;
     size_t alloc_bytes = 0;                       // device bytes behind `allocs` and the Grown buffers (rwkv_resident_bytes)
 };
@@ -1722,22 +1735,58 @@ int enqueue_pick(rwkv_ctx *c, const Sampler &s, unsigned rows)
     return 0;
 }
 
+// ---- constrained decoding (constrain.hip.h): what rwkv_decode_batch_constrained / rwkv_pick_constrained add to a pick ----
+// One call's constraint, set up by constrainer_setup (below decode_batch's checks).  Per step: rows() writes the constrained rows into the second
+// buffer, the call's pick reads them there (argmax() is the greedy one), advance() moves the automaton states behind the pick.
+struct Constrainer {
+    ConstrainArgs r{};
+    AdvanceArgs v{};
+    int rows(rwkv_ctx *c, unsigned n) const
+    {
+        k_constrain_rows<0><<<dim3(CN_SLICES, n), dim3(CN_NT), 0, c->stream>>>(r);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    // k_argmax_rows and its finish over n rows from `base` on (BD_VAL / BD_IDX hold the partials)
+    int argmax(rwkv_ctx *c, const float *base, unsigned n, unsigned long long *ids) const
+    {
+        float *val = c->buf<float>(BD_VAL);
+        unsigned *idx = c->buf<unsigned>(BD_IDX);
+        k_argmax_rows<<<dim3(AM_SLICES, n), dim3(AM_NT), 0, c->stream>>>(base, val, idx);
+        k_argmax_rows_finish<<<dim3(n), dim3(64), 0, c->stream>>>(val, idx, ids);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    int advance(rwkv_ctx *c, const unsigned long long *picks) const
+    {
+        k_constraint_advance<0><<<dim3((v.n + CN_ADV_NT - 1) / CN_ADV_NT), dim3(CN_ADV_NT), 0, c->stream>>>(v, picks);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+};
+
 // The device decode loop: n tokens on slot 0 (and its counts), `first` and then each token's pick, and the download of the picks.  The pick is
 // the argmax node of the token graph, or (`pk` not greedy) the sampler's three launches behind the token graph without that node: u of step k from
 // seed + k, logit 0 banned, the id fed back through the control block.  stop: the call can end early (the picks of the steps it ran are downloaded).
 // lp: every step's pick is recorded (in the greedy loop behind the token graph, whose last node is the pick: it reads gen[i]).
+// cn: the picks are constrained (Constrainer) -- the step's row goes through k_constrain_rows into the second buffer, the pick reads that buffer
+// (greedy: the row pick's two launches behind the token graph without its pick node, as the sampled loops run it), and k_constraint_advance moves
+// the slot's automaton state in front of the stop test (in the greedy loop it also feeds the pick back).
 int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_pick &pk, uint64_t seed, uint64_t *out_tokens, Stopper *stop = nullptr,
-                   const LpRecorder *lp = nullptr)
+                   const LpRecorder *lp = nullptr, const Constrainer *cn = nullptr)
 {
     const bool sampled = pk.kind != RWKV_PICK_GREEDY;
     if (const int rc = pick_counts(c, pk, 0, 1, true)) return rc;
     Sampler s;                    // greedy: no arguments are built
     if (sampled) { s = make_sampler(c, pk, true); s.draw().seed = seed; }
+    if (sampled && cn) { s.draw().logits = cn->r.out; s.draw().ban0 = 0; }      // the row already holds -inf at id 0
     if (const int rc = set_ctl(c, first, 0, 0)) return rc;
     bool more = true;
     for (uint64_t i = 0; i < n && more; i++) {
-        if (const int rc = run_token(c, !sampled)) return rc;
-        if (const int rc = sampled ? enqueue_pick(c, s, 1) : 0) return rc;
+        if (const int rc = run_token(c, !sampled && !cn)) return rc;
+        if (const int rc = cn ? cn->rows(c, 1) : 0) return rc;
+        if (const int rc = sampled ? enqueue_pick(c, s, 1) : cn ? cn->argmax(c, cn->r.out, 1, c->pick) : 0) return rc;
+        if (const int rc = cn ? cn->advance(c, c->pick) : 0) return rc;
         if (const int rc = lp ? lp->record(c, i, c->gen + i) : 0) return rc;
         if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
     }
@@ -1919,13 +1968,121 @@ void lp_results(const rwkv_ctx *c, const rwkv_logprob_out &o, uint64_t N, uint64
         }
 }
 
+// ---- the host side of constrained decoding (rwkv_constraint_*, rwkv_pick_constrained, rwkv_decode_batch_constrained) ----
+static_assert(sizeof(rwkv_automaton) == 40 && sizeof(rwkv_bias) == 24 && sizeof(rwkv_constrain_params) == 48, "the constraint records of the C ABI");
+static_assert(CN_MAX_STATES == RWKV_CONSTRAINT_MAX_STATES && CN_MAX_BIAS == RWKV_CONSTRAINT_MAX_BIAS && CN_STOP_REASON == RWKV_STOP_CONSTRAINT &&
+              STOP_CONSTRAINT == RWKV_STOP_CONSTRAINT, "constrain.hip.h and stop.hip.h hold the header's limits");
+// the host copy of the slots' automaton states (all 0 until something writes them): no device work
+std::vector<unsigned> &cn_states(rwkv_ctx *c)
+{
+    if (c->cn_q.size() != c->maxT) c->cn_q.assign(c->maxT, 0u);
+    return c->cn_q;
+}
+bool cn_terminal(const rwkv_ctx *c, unsigned q) { return c->cn_row_ptr[q] == c->cn_row_ptr[q + 1]; }
+// a bias list is acceptable (include/rwkv_sampler.h constraint_check, the one validator)
+int check_bias(uint64_t n, const uint32_t *tok, const float *val)
+{
+    const bias_view b{n, tok, val};
+    if (const char *rule = constraint_check(nullptr, &b)) return fail(RWKV_E_ARG, "malformed bias list: %s", rule);
+    return 0;
+}
+// slot `slot` may start a constrained pick in state q
+int check_start(const rwkv_ctx *c, uint64_t slot, unsigned q)
+{
+    if (!c->cn_S) return q == 0u ? 0 : fail(RWKV_E_ARG, "slot %llu: automaton state %u without an installed automaton", (unsigned long long)slot, q);
+    if (q >= c->cn_S) return fail(RWKV_E_ARG, "slot %llu: automaton state %u is not below %u", (unsigned long long)slot, q, c->cn_S);
+    if (cn_terminal(c, q)) return fail(RWKV_E_ARG, "slot %llu: automaton state %u is terminal: nothing may follow", (unsigned long long)slot, q);
+    return 0;
+}
+// the constraint of a call over N streams is acceptable
+int check_constrain(rwkv_ctx *c, const rwkv_constrain_params &cp, const rwkv_pick &pk, uint64_t N)
+{
+    if (cp.reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    if (pk.kind == RWKV_PICK_TYPICAL) return fail(RWKV_E_ARG, "typical sampling under a constraint is out of scope: pick greedy or nucleus");
+    if ((cp.bias_ptr != nullptr) != (cp.bias_tok != nullptr) || (cp.bias_ptr != nullptr) != (cp.bias_val != nullptr))
+        return fail(RWKV_E_ARG, "bias_ptr, bias_tok and bias_val are all NULL or none");
+    if (cp.bias_ptr && cp.bias_ptr[0] != 0u) return fail(RWKV_E_ARG, "malformed bias list: bias_ptr[0] != 0");
+    for (uint64_t s = 0; cp.bias_ptr && s < N; s++) {
+        if (cp.bias_ptr[s + 1] < cp.bias_ptr[s]) return fail(RWKV_E_ARG, "malformed bias list: bias_ptr decreases at stream %llu", (unsigned long long)s);
+        if (const int rc = check_bias(cp.bias_ptr[s + 1] - cp.bias_ptr[s], cp.bias_tok + cp.bias_ptr[s], cp.bias_val + cp.bias_ptr[s])) return rc;
+    }
+    const std::vector<unsigned> &q = cn_states(c);
+    for (uint64_t s = 0; s < N; s++)
+        if (const int rc = check_start(c, s, cp.start ? cp.start[s] : q[s])) return rc;
+    return 0;
+}
+// what every constrained pick needs on the device: the second row buffer, the slots' states and, without an automaton, the implicit state's mask
+int constraint_buffers(rwkv_ctx *c)
+{
+    if (const int rc = grow_buffer(c, CN_ROWS, sizeof(float) * c->maxT * RWKV_VOCAB)) return rc;
+    if (!c->grown[CN_Q].p) {
+        if (const int rc = grow_buffer(c, CN_Q, sizeof(unsigned) * c->maxT)) return rc;
+        HIPCHK(hipMemsetAsync(c->grown[CN_Q].p, 0, sizeof(unsigned) * c->maxT, c->stream));
+    }
+    if (!c->cn_S && !c->grown[CN_MASK1].p) {
+        if (const int rc = grow_buffer(c, CN_MASK1, sizeof(unsigned) * CN_WORDS)) return rc;
+        k_constraint_mask<0><<<dim3(1), dim3(CN_NT), 0, c->stream>>>(CsrArgs{nullptr, nullptr, nullptr, 1u}, c->buf<unsigned>(CN_MASK1));
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+CsrArgs csr_args(const rwkv_ctx *c)
+{
+    const unsigned *w = c->buf<unsigned>(CN_CSR);
+    if (!c->cn_S) return CsrArgs{nullptr, nullptr, nullptr, 0u};
+    return CsrArgs{w, w + c->cn_S + 1, w + c->cn_S + 1 + c->cn_nnz, c->cn_S};
+}
+// The buffers and the one upload of a constrained pick over n rows: rows row0 .. row0 + n - 1 with slots slot0 .. slot0 + n - 1, the bias lists
+// (bias_ptr [n + 1] into tok / val; nullptr: none) as CN_CALL: bias_ptr | tok | val | done [n] (`done` with a stopper `st` only: it reads the words).
+int constrainer_setup(rwkv_ctx *c, Constrainer &cn, uint64_t row0, uint64_t slot0, uint64_t n, const uint32_t *bias_ptr, const uint32_t *bias_tok,
+                      const float *bias_val, Stopper *st)
+{
+    if (const int rc = constraint_buffers(c)) return rc;
+    const size_t nb = bias_ptr ? bias_ptr[n] : 0, words = n + 1 + 2 * nb;
+    if (const int rc = grow_buffer(c, CN_CALL, sizeof(unsigned) * (words + n))) return rc;
+    unsigned *call = c->buf<unsigned>(CN_CALL);
+    if (bias_ptr) {
+        c->cn_host.assign(words, 0u);
+        memcpy(c->cn_host.data(), bias_ptr, sizeof(unsigned) * (n + 1));
+        if (nb) { memcpy(c->cn_host.data() + n + 1, bias_tok, sizeof(unsigned) * nb); memcpy(c->cn_host.data() + n + 1 + nb, bias_val, sizeof(float) * nb); }
+        HIPCHK(hipMemcpyAsync(call, c->cn_host.data(), sizeof(unsigned) * words, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(hipMemsetAsync(call + words, 0, sizeof(unsigned) * n, c->stream));
+    cn.r.logits = c->logits; cn.r.out = c->buf<float>(CN_ROWS); cn.r.row = (int)row0; cn.r.ctl = c->ctl;
+    cn.r.mask = c->cn_S ? c->buf<unsigned>(CN_MASK) : c->buf<unsigned>(CN_MASK1);
+    cn.r.q = c->cn_S ? c->buf<unsigned>(CN_Q) : nullptr;
+    cn.r.slot = (unsigned)slot0;
+    cn.r.bias_ptr = bias_ptr ? call : nullptr; cn.r.bias_tok = call + n + 1; cn.r.bias_val = reinterpret_cast<const float *>(call + n + 1 + nb);
+    cn.v.csr = csr_args(c); cn.v.q = c->buf<unsigned>(CN_Q); cn.v.slot = (unsigned)slot0; cn.v.n = (unsigned)n;
+    cn.v.done = st ? call + words : nullptr; cn.v.len = st ? st->a.len : nullptr;
+    cn.v.feedback = 0; cn.v.ctl = c->ctl; cn.v.gen = c->gen; cn.v.gen_cap = c->gen_cap;
+    if (st) st->a.done = cn.v.done;
+    return 0;
+}
+// the start states of a decode call go up (host copy first: it is what the checks read), and behind the call's last launch q comes back
+int constrainer_start(rwkv_ctx *c, const uint32_t *start, uint64_t N)
+{
+    if (!start) return 0;
+    std::vector<unsigned> &q = cn_states(c);
+    std::copy(start, start + N, q.begin());
+    HIPCHK(hipMemcpyAsync(c->buf<unsigned>(CN_Q), q.data(), sizeof(unsigned) * N, hipMemcpyHostToDevice, c->stream));
+    return 0;
+}
+int constrainer_download(rwkv_ctx *c, uint64_t slot0, uint64_t n)
+{
+    HIPCHK(hipMemcpyAsync(cn_states(c).data() + slot0, c->buf<unsigned>(CN_Q) + slot0, sizeof(unsigned) * n, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+
 // rwkv_decode_batch_greedy / _typical / _nucleus / _until: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
 // else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
 // pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.  until: streams stop at sequences and budgets
 // (Stopper: two small launches behind each step's pick, one behind the last); a call that cannot stop a stream is the plain loop.
 // `pk`: how a step picks -- k_argmax_rows, or the sampler's three launches (one seed per stream, the sampler's scratch per row)
+// cp (with until): the picks are constrained -- per step k_constrain_rows in front of the pick, which then reads the second buffer, and
+// k_constraint_advance behind it; such a call always owns a Stopper (a stream ends where its automaton does)
 int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, const rwkv_pick &pk, const uint64_t *seeds, uint64_t *out_tokens,
-                 const Until *until = nullptr, const rwkv_logprob_out *lpo = nullptr)
+                 const Until *until = nullptr, const rwkv_logprob_out *lpo = nullptr, const rwkv_constrain_params *cp = nullptr)
 {
     const bool sampled = pk.kind != RWKV_PICK_GREEDY;
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!sampled || seeds))) return rc;
@@ -1938,10 +2095,24 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
     if (lpo && N * n_steps * (1 + (uint64_t)lpo->top_n) > RWKV_MAX_LOGPROB_ENTRIES)
         return fail(RWKV_E_ARG, "n_streams * n_steps * (1 + top_n) must not exceed %u: split the generation into calls", RWKV_MAX_LOGPROB_ENTRIES);
     if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
+    if (const int rc = cp ? check_constrain(c, *cp, pk, N) : 0) return rc;
     LpRecorder recorder, *lp = lpo ? &recorder : nullptr;
-    Stopper stopper, *st = until && (until->stop->n_seqs || until->stop->max_new) ? &stopper : nullptr;
-    auto stop_setup = [&]() { return st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, pick_penalty(pk)) : 0; };
-    auto stop_end = [&]() { const int rc = st ? st->unpark(c) : 0; return rc || !st ? rc : stopper_download(c, *st); };
+    Constrainer constrainer, *cn = cp ? &constrainer : nullptr;
+    Stopper stopper, *st = until && (cn || until->stop->n_seqs || until->stop->max_new) ? &stopper : nullptr;
+    auto stop_setup = [&]() -> int {
+        if (const int rc = st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, pick_penalty(pk)) : 0) return rc;
+        if (!cn) return 0;
+        if (const int rc = constrainer_setup(c, *cn, 0, 0, N, cp->bias_ptr, cp->bias_tok, cp->bias_val, st)) return rc;
+        if (const int rc = constrainer_start(c, cp->start, N)) return rc;
+        if (sampled) return 0;                          // the greedy pick over the second buffer's rows: its partials
+        if (const int rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES)) return rc;
+        return grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
+    };
+    auto stop_end = [&]() -> int {
+        if (const int rc = st ? st->unpark(c) : 0) return rc;
+        if (const int rc = st ? stopper_download(c, *st) : 0) return rc;
+        return cn ? constrainer_download(c, 0, N) : 0;
+    };
     // lengths, reasons and the steps enqueued; the ids behind a stream's end are 0 (out_tokens holds the picks of the steps that ran)
     auto until_results = [&]() {
         const uint64_t ran = st ? st->steps_run : n_steps;
@@ -1950,13 +2121,15 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
             for (uint64_t k = until->out_len[s]; k < n_steps; k++) out_tokens[s * n_steps + k] = 0;
         if (until->steps_run) *until->steps_run = ran;
         if (lpo) lp_results(c, *lpo, N, n_steps, until->out_len);
+        if (cn && cp->out_state) std::copy(c->cn_q.begin(), c->cn_q.begin() + N, cp->out_state);
         return 0;
     };
     if (N == 1) {     // the decode path's kernels on slot 0
         const int rc = finish(c, [&]() -> int {
             if (const int rc = stop_setup()) return rc;
             if (const int rc = lp ? lp_setup(c, *lp, 1, n_steps, lpo->top_n) : 0) return rc;
-            if (const int rc = enqueue_decode(c, first_tokens[0], n_steps, pk, sampled ? seeds[0] : 0, out_tokens, st, lp)) return rc;
+            if (cn) cn->v.feedback = sampled ? 0 : 1;      // the greedy loop's pick is fed back by k_constraint_advance
+            if (const int rc = enqueue_decode(c, first_tokens[0], n_steps, pk, sampled ? seeds[0] : 0, out_tokens, st, lp, cn)) return rc;
             if (const int rc = lp ? lp_download(c, *lp, st ? st->steps_run : n_steps) : 0) return rc;
             return stop_end();
         }());
@@ -1981,12 +2154,16 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
         HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
         Sampler smp;
         if (sampled) { smp = make_sampler(c, pk, true); sampler_to_batch(c, smp, dseeds); }
+        if (sampled && cn) { smp.draw().logits = cn->r.out; smp.draw().ban0 = 0; }      // the rows already hold -inf at id 0
         for (uint64_t k = 0; k < n_steps; k++) {
             if ((rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL))) return rc;       // logits rows 0 .. N - 1, state slots 0 .. N - 1
             unsigned long long *next = ids + (k + 1) * N;
+            if ((rc = cn ? cn->rows(c, (unsigned)N) : 0)) return rc;
             if (sampled) {
                 smp.draw().step = (int)k; smp.draw().pick = next;
                 if ((rc = enqueue_pick(c, smp, (unsigned)N))) return rc;
+            } else if (cn) {
+                if ((rc = cn->argmax(c, cn->r.out, (unsigned)N, next))) return rc;
             } else {
                 float *val = c->buf<float>(BD_VAL);
                 unsigned *idx = c->buf<unsigned>(BD_IDX);
@@ -1994,6 +2171,7 @@ int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t
                 k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
                 HIPCHK(hipGetLastError());
             }
+            if ((rc = cn ? cn->advance(c, next) : 0)) return rc;
             if ((rc = lp ? lp->record(c, k, next) : 0)) return rc;
             bool more = true;
             if ((rc = st ? st->after_step(c, k, next, &more) : 0)) return rc;
@@ -2083,6 +2261,144 @@ int rwkv_decode_batch_logprobs(rwkv_ctx *c, const uint64_t *first_tokens, uint64
     std::vector<uint32_t> len(out_len ? 0 : std::min<uint64_t>(n_streams, c->maxT));
     const Until until{stop ? stop : &none, out_len ? out_len : len.data(), out_reason, steps_run};
     return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until, lp);
+}
+
+int rwkv_constraint_set(rwkv_ctx *c, const rwkv_automaton *a)
+{
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, a)) return rc;
+    if (a->reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    const constraint_view view{a->n_states, a->row_ptr, a->nnz, a->tok, a->next};
+    if (const char *rule = constraint_check(&view, nullptr)) return fail(RWKV_E_ARG, "malformed automaton: %s", rule);
+    const size_t S = a->n_states, nnz = a->nnz;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = grow_buffer(c, CN_CSR, sizeof(unsigned) * (S + 1 + 2 * nnz))) return rc;
+        if (const int rc = grow_buffer(c, CN_MASK, sizeof(unsigned) * S * CN_WORDS)) return rc;
+        if (const int rc = grow_buffer(c, CN_Q, sizeof(unsigned) * c->maxT)) return rc;
+        unsigned *w = c->buf<unsigned>(CN_CSR);
+        HIPCHK(hipMemcpyAsync(w, a->row_ptr, sizeof(unsigned) * (S + 1), hipMemcpyHostToDevice, c->stream));
+        if (nnz) {
+            HIPCHK(hipMemcpyAsync(w + S + 1, a->tok, sizeof(unsigned) * nnz, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(w + S + 1 + nnz, a->next, sizeof(unsigned) * nnz, hipMemcpyHostToDevice, c->stream));
+        }
+        k_constraint_mask<0><<<dim3((unsigned)S), dim3(CN_NT), 0, c->stream>>>(CsrArgs{w, w + S + 1, w + S + 1 + nnz, (unsigned)S}, c->buf<unsigned>(CN_MASK));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemsetAsync(c->grown[CN_Q].p, 0, sizeof(unsigned) * c->maxT, c->stream));
+        return 0;
+    }());
+    if (rc) { c->cn_S = 0; c->cn_nnz = 0; c->cn_row_ptr.clear(); return rc; }      // (a failed upload: the buffers no longer hold the previous automaton)
+    c->cn_S = (unsigned)S; c->cn_nnz = nnz;
+    c->cn_row_ptr.assign(a->row_ptr, a->row_ptr + S + 1);
+    c->cn_q.assign(c->maxT, 0u);
+    return 0;
+}
+
+int rwkv_constraint_clear(rwkv_ctx *c)
+{
+    if (const int rc = guard(c, NEED_LOADED)) return rc;
+    const int rc = finish(c, [&]() -> int {
+        if (c->grown[CN_Q].p) HIPCHK(hipMemsetAsync(c->grown[CN_Q].p, 0, sizeof(unsigned) * c->maxT, c->stream));
+        return 0;
+    }());
+    for (const GrownBuf b : {CN_CSR, CN_MASK}) {       // (the stream is idle)
+        rwkv_ctx::Grown &g = c->grown[b];
+        if (g.p) { (void)hipFree(g.p); c->alloc_bytes -= g.bytes; g.p = nullptr; g.bytes = 0; }
+    }
+    c->cn_S = 0; c->cn_nnz = 0; c->cn_row_ptr.clear();
+    c->cn_q.assign(c->maxT, 0u);
+    return rc;
+}
+
+int rwkv_constraint_state_set(rwkv_ctx *c, uint64_t slot0, uint64_t n, const uint32_t *states)
+{
+    if (const int rc = guard(c, NEED_LOADED, states)) return rc;
+    if (n == 0 || slot0 >= c->maxT || n > c->maxT - slot0) return fail(RWKV_E_ARG, "slots %llu .. + %llu out of range (max context %llu)", (unsigned long long)slot0, (unsigned long long)n, (unsigned long long)c->maxT);
+    for (uint64_t i = 0; i < n; i++)
+        if (states[i] >= std::max(c->cn_S, 1u)) return fail(RWKV_E_ARG, "automaton state %u is not below %u", states[i], std::max(c->cn_S, 1u));
+    std::vector<unsigned> &q = cn_states(c);
+    const int rc = finish(c, [&]() -> int {
+        if (!c->grown[CN_Q].p) {
+            if (const int rc = grow_buffer(c, CN_Q, sizeof(unsigned) * c->maxT)) return rc;
+            HIPCHK(hipMemsetAsync(c->grown[CN_Q].p, 0, sizeof(unsigned) * c->maxT, c->stream));
+        }
+        HIPCHK(hipMemcpyAsync(c->buf<unsigned>(CN_Q) + slot0, states, sizeof(unsigned) * n, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }());
+    if (!rc) std::copy(states, states + n, q.begin() + slot0);
+    return rc;
+}
+
+int rwkv_constraint_state_get(rwkv_ctx *c, uint64_t slot0, uint64_t n, uint32_t *states)
+{
+    if (const int rc = guard(c, NEED_LOADED, states)) return rc;
+    if (n == 0 || slot0 >= c->maxT || n > c->maxT - slot0) return fail(RWKV_E_ARG, "slots %llu .. + %llu out of range (max context %llu)", (unsigned long long)slot0, (unsigned long long)n, (unsigned long long)c->maxT);
+    const std::vector<unsigned> &q = cn_states(c);
+    std::copy(q.begin() + slot0, q.begin() + slot0 + n, states);
+    return 0;
+}
+
+int rwkv_pick_constrained(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_pick *pick, const rwkv_bias *bias, double u, int advance, uint64_t *token,
+                          uint32_t *state_out)
+{
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, pick && token)) return rc;
+    if (row >= c->maxT || slot >= c->maxT)
+        return fail(RWKV_E_ARG, "logits row %llu or slot %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (pick->kind == RWKV_PICK_TYPICAL) return fail(RWKV_E_ARG, "typical sampling under a constraint is out of scope: pick greedy or nucleus");
+    if (const int rc = check_pick(*pick)) return rc;
+    const bool sampled = pick->kind == RWKV_PICK_NUCLEUS;
+    if (sampled && !(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need 0 <= u < 1");
+    if (bias && bias->reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    if (const int rc = bias ? check_bias(bias->n, bias->tok, bias->val) : 0) return rc;
+    if (const int rc = check_start(c, slot, cn_states(c)[slot])) return rc;
+    const uint32_t bptr[2] = {0u, bias ? bias->n : 0u};
+    const int rc = finish(c, [&]() -> int {
+        Constrainer cn;
+        if (const int rc = constrainer_setup(c, cn, row, slot, 1, bias ? bptr : nullptr, bias ? bias->tok : nullptr, bias ? bias->val : nullptr, nullptr)) return rc;
+        if (const int rc = cn.rows(c, 1)) return rc;
+        if (sampled) {
+            if (const int rc = pick_counts(c, *pick, slot, 1, false)) return rc;
+            Sampler s = make_sampler(c, *pick, false);
+            s.n.logits = cn.r.out; s.n.ban0 = 0; s.n.row = (int)row; s.n.slot = (unsigned)slot; s.n.u = u;
+            if (const int rc = enqueue_pick(c, s, 1)) return rc;
+        } else {
+            if (const int rc = grow_buffer(c, BD_VAL, sizeof(float) * AM_SLICES)) return rc;
+            if (const int rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * AM_SLICES)) return rc;
+            if (const int rc = cn.argmax(c, cn.r.out + row * RWKV_VOCAB, 1, c->pick)) return rc;
+        }
+        if (advance && c->cn_S) {
+            if (const int rc = cn.advance(c, c->pick)) return rc;
+            if (const int rc = constrainer_download(c, slot, 1)) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+    if (!rc && state_out) *state_out = c->cn_q[slot];
+    return rc;
+}
+
+int rwkv_debug_constrained_row(rwkv_ctx *c, uint64_t row, float *dst)
+{
+    if (const int rc = guard(c, NEED_LOADED, dst)) return rc;
+    if (row >= c->maxT) return fail(RWKV_E_ARG, "row %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)c->maxT);
+    if (!c->grown[CN_ROWS].p) return fail(RWKV_E_STATE, "no constrained pick has run on this context");
+    return finish(c, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(dst, c->buf<float>(CN_ROWS) + row * RWKV_VOCAB, sizeof(float) * RWKV_VOCAB, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+}
+
+int rwkv_decode_batch_constrained(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                                  const uint64_t *seeds, const rwkv_constrain_params *cp, const rwkv_stop_params *stop, const rwkv_logprob_out *lp,
+                                  uint64_t *out_tokens, uint32_t *out_len, uint32_t *out_reason, uint64_t *steps_run)
+{
+    if (const int rc = guard(c, NEED_WHOLE, pick && cp && out_len && (!lp || lp->logprob))) return rc;
+    if (lp && lp->top_n > RWKV_MAX_TOPN) return fail(RWKV_E_ARG, "top_n must be in 0..%u", RWKV_MAX_TOPN);
+    if (lp && ((lp->top_n > 0) != (lp->top_ids != nullptr) || (lp->top_n > 0) != (lp->top_logprob != nullptr)))
+        return fail(RWKV_E_ARG, "top_ids and top_logprob go with top_n > 0, and only with it");
+    if (lp && lp->reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);
+    const rwkv_stop_params none{};                      // no stop: every stream runs until its automaton ends it, or n_steps
+    const Until until{stop ? stop : &none, out_len, out_reason, steps_run};
+    return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until, lp, cp);
 }
 
 int rwkv_topn_rows(rwkv_ctx *c, const uint64_t *rows, uint64_t n, uint32_t top_n, uint64_t *ids, double *logprob)

@@ -66,7 +66,8 @@ __global__ __launch_bounds__(TS_GT) void k_nucleus_stats(NucleusArgs a)
     for (int k = 1; k < TS_GT / 64; k++) mx = fmax(mx, red[k]);
     __syncthreads();
     double z = 0.0;
-    for (int i = i0 + threadIdx.x; i < i1; i += TS_GT) z += exp(nu_logit(a, lg, cnt, i) - mx);
+    // (a -inf logit carries no mass: said outright, because under a constraint a whole slice can be -inf, and -inf - mx is then no number)
+    for (int i = i0 + threadIdx.x; i < i1; i += TS_GT) { const double l = nu_logit(a, lg, cnt, i); z += l > -INFINITY ? exp(l - mx) : 0.0; }
     z = wave_sum(z);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = z;
     __syncthreads();

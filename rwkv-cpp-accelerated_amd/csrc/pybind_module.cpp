@@ -139,6 +139,87 @@ PYBIND11_MODULE(rwkv, m)
     }, "beam search ON THE DEVICE from the state slot 0 holds (load with maxGPT >= width): (tokens [width][n], len [width], score [width], "
        "token log-probs [width][n]); hypothesis 0 is the best, entries behind a hypothesis's end are 0 (engine extension)",
           py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("width") = 4u, py::arg("stops") = std::vector<int64_t>{});
+    // ---- constrained decoding: the engine calls, and the host twins of include/rwkv_sampler.h for the suite ----
+    using u32arr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
+    using f32arr = py::array_t<float, py::array::c_style | py::array::forcecast>;
+    m.def("setConstraint", [](std::uintptr_t h, u32arr row_ptr, u32arr tok, u32arr next) {
+        RWKV::Automaton a;
+        a.row_ptr.assign(row_ptr.data(), row_ptr.data() + row_ptr.size()); a.tok.assign(tok.data(), tok.data() + tok.size());
+        a.next.assign(next.data(), next.data() + next.size());
+        M(h)->setConstraint(a);
+    }, "install a token-level automaton in CSR form (row_ptr [S + 1], tok [nnz], next [nnz]; a state without edges is terminal): every later "
+       "decodeConstrained generates only what it allows (engine extension)");
+    m.def("clearConstraint", [](std::uintptr_t h) { M(h)->clearConstraint(); }, "remove the installed automaton (engine extension)");
+    m.def("decodeConstrained", [](std::uintptr_t h, int64_t first, int64_t n, float temp, float top_p, unsigned top_k, float presence, float frequency,
+                                  float decay, uint64_t seed, bool greedy, const std::vector<uint32_t> &bias_tok, const std::vector<float> &bias_val) {
+        const RWKV::Pick pick = greedy ? RWKV::Pick::greedy() : RWKV::Pick::nucleus(RWKV::Nucleus{temp, top_p, top_k, presence, frequency, decay});
+        std::vector<RWKV::Bias> bias;
+        if (!bias_tok.empty()) bias.push_back(RWKV::Bias{bias_tok, bias_val});
+        RWKV::Constrained r = M(h)->decodeConstrained({(unsigned long long)first}, n, pick, {seed}, RWKV::Stop{}, {0u}, bias);
+        r.until.ids.resize(r.until.len[0]);
+        return std::make_tuple(std::vector<int64_t>(r.until.ids.begin(), r.until.ids.end()), (int)r.until.reason[0], (int)r.state[0]);
+    }, "device-side continuation under the installed automaton from its state 0, with an optional logit bias (ids ascending; -inf bans): returns "
+       "(ids, reason: 0 ran all n, 32 the automaton reached a terminal state, automaton state) (engine extension)",
+          py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u,
+          py::arg("presence") = 0.f, py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("seed") = 0ull, py::arg("greedy") = false,
+          py::arg("bias_tok") = std::vector<uint32_t>{}, py::arg("bias_val") = std::vector<float>{});
+    m.def("constraintCheck", [](py::object S, py::object row_ptr, py::object tok, py::object next, py::object bias_tok, py::object bias_val) -> py::object {
+        // the arrays as given: S and the lengths are NOT derived from each other, so that every malformed input reaches the validator
+        u32arr rp, tk, nx, bt;
+        f32arr bv;
+        constraint_view a{};
+        bias_view b{};
+        const bool has_a = !S.is_none(), has_b = !bias_tok.is_none();
+        if (has_a) {
+            rp = row_ptr.cast<u32arr>(); tk = tok.cast<u32arr>(); nx = next.cast<u32arr>();
+            const unsigned long long s = S.cast<unsigned long long>();
+            if ((unsigned long long)rp.size() != s + 1 && !(s == 0 || s > 4096ull)) throw py::value_error("constraintCheck: row_ptr has S + 1 entries");
+            if (tk.size() != nx.size()) throw py::value_error("constraintCheck: tok and next have nnz entries");
+            a = constraint_view{s, rp.data(), (unsigned long long)tk.size(), tk.data(), nx.data()};
+        }
+        if (has_b) {
+            bt = bias_tok.cast<u32arr>(); bv = bias_val.cast<f32arr>();
+            if (bt.size() != bv.size()) throw py::value_error("constraintCheck: one value per bias id");
+            b = bias_view{(unsigned long long)bt.size(), bt.data(), bv.data()};
+        }
+        const char *rule = constraint_check(has_a ? &a : nullptr, has_b ? &b : nullptr);
+        return rule ? py::object(py::str(rule)) : py::object(py::none());
+    }, "the ONE validator of automata and bias lists ON THE HOST (include/rwkv_sampler.h constraint_check): None when well formed, else the name "
+       "of the first rule broken (engine extension)",
+          py::arg("S") = py::none(), py::arg("row_ptr") = py::none(), py::arg("tok") = py::none(), py::arg("next") = py::none(),
+          py::arg("bias_tok") = py::none(), py::arg("bias_val") = py::none());
+    m.def("constrainedRow", [](f32arr logits, py::object row_ptr, py::object tok, py::object next, unsigned q, py::object bias_tok, py::object bias_val) {
+        if (logits.size() != 50277) throw py::value_error("constrainedRow: 50277 logits");
+        u32arr rp, tk, nx, bt;
+        f32arr bv;
+        constraint_view a{};
+        bias_view b{};
+        if (!row_ptr.is_none()) {
+            rp = row_ptr.cast<u32arr>(); tk = tok.cast<u32arr>(); nx = next.cast<u32arr>();
+            a = constraint_view{(unsigned long long)rp.size() - 1, rp.data(), (unsigned long long)tk.size(), tk.data(), nx.data()};
+            if (constraint_check(&a, nullptr) || q >= a.S) throw py::value_error("constrainedRow: malformed automaton or state");
+        }
+        if (!bias_tok.is_none()) {
+            bt = bias_tok.cast<u32arr>(); bv = bias_val.cast<f32arr>();
+            b = bias_view{(unsigned long long)bt.size(), bt.data(), bv.data()};
+            if (bt.size() != bv.size() || constraint_check(nullptr, &b)) throw py::value_error("constrainedRow: malformed bias list");
+        }
+        py::array_t<float> c(50277);
+        constrained_row(logits.data(), row_ptr.is_none() ? nullptr : &a, q, bias_tok.is_none() ? nullptr : &b, c.mutable_data());
+        return c;
+    }, "the constrained row ON THE HOST (include/rwkv_sampler.h constrained_row, the twin of the device's): f32 [50277] (engine extension)",
+          py::arg("logits"), py::arg("row_ptr") = py::none(), py::arg("tok") = py::none(), py::arg("next") = py::none(), py::arg("q") = 0u,
+          py::arg("bias_tok") = py::none(), py::arg("bias_val") = py::none());
+    m.def("constraintNext", [](u32arr row_ptr, u32arr tok, u32arr next, unsigned q, unsigned g) {
+        const constraint_view a{(unsigned long long)row_ptr.size() - 1, row_ptr.data(), (unsigned long long)tok.size(), tok.data(), next.data()};
+        if (constraint_check(&a, nullptr) || q >= a.S) throw py::value_error("constraintNext: malformed automaton or state");
+        return constraint_next(&a, q, g);
+    }, "the automaton state after pick g in state q ON THE HOST (include/rwkv_sampler.h constraint_next) (engine extension)");
+    m.def("constraintTrie", [](const std::vector<std::vector<unsigned long long>> &choices) {
+        const constraint_automaton A = constraint_trie(choices);
+        return py::make_tuple(py::array_t<uint32_t>(A.row_ptr.size(), A.row_ptr.data()), py::array_t<uint32_t>(A.tok.size(), A.tok.data()),
+                              py::array_t<uint32_t>(A.next.size(), A.next.data()));
+    }, "(row_ptr, tok, next) of the automaton that spells exactly one of the given token sequences (include/rwkv_sampler.h constraint_trie) (engine extension)");
     m.def("beamSelect", [](py::array_t<int64_t, py::array::c_style | py::array::forcecast> top_ids, py::array_t<double, py::array::c_style | py::array::forcecast> top_lp,
                            py::array_t<double, py::array::c_style | py::array::forcecast> cum, const std::vector<int> &ended, const std::vector<int64_t> &last,
                            const std::vector<int64_t> &stops) {

@@ -5,7 +5,8 @@
 // place, so a stopped stream cannot be skipped.  Its row keeps running on its own picks (valid ids), and what it had when it stopped is
 // set aside:
 //     k_stop_step   behind each step's pick, one thread per stream: append the pick to the slot's match history, test every stop sequence
-//                   against the newest ids and the budget; on a hit record length and reason and lower the count of active streams
+//                   against the newest ids, the constraint's `done` word and the budget; on a hit record length and reason and lower the
+//                   count of active streams
 //     k_stop_park   grid (chunks, streams): a stream that stopped THIS step copies its five state arrays, its logits row and, with
 //                   penalties, its count vector into the park buffer; every other workgroup exits at once
 //     unpark        k_stop_park<true>, once behind the last enqueued step: every stopped stream is copied back, so the slot is what it
@@ -21,6 +22,7 @@ namespace rwkvk {
 constexpr int STOP_MAX_SEQS = 16, STOP_MAX_LEN = 8;
 constexpr int STOP_HIST = 8;                   // u32 per slot: the newest STOP_MAX_LEN - 1 ids, newest first, and one word of padding (32 bytes)
 constexpr unsigned STOP_NONE = 0xFFFFFFFFu;    // an empty history entry (no token id)
+constexpr unsigned STOP_CONSTRAINT = 32u;      // RWKV_STOP_CONSTRAINT: the reason of a stream whose automaton reached a terminal state
 constexpr int STOP_NT = 64;                    // threads per workgroup of k_stop_step
 constexpr int PARK_NT = 256, PARK_CHUNKS = 32; // k_stop_park: workgroups per stream
 constexpr size_t PARK_ROW = (VOCAB + 3 + 3) / 4 * 4;    // floats of a parked logits row or count vector: the row behind the source's offset inside 16 bytes
@@ -42,6 +44,7 @@ struct StopArgs {
     const unsigned long long *first;     // [n] the first tokens
     unsigned *len, *reason;              // [n] 0 until the stream stops
     const unsigned *max_new;             // [n]
+    const unsigned *done;                // [n] constrained decoding (constrain.hip.h): the stream's automaton reached a terminal state at this step; nullptr: none
 };
 
 // picks: [n] the ids picked at step k.  At step 0 the history (re)starts from the first token unless it continues (keep) from that very id.
@@ -70,6 +73,7 @@ __global__ __launch_bounds__(STOP_NT) void k_stop_step(const StopArgs a, const u
         for (int i = 0; i < STOP_MAX_LEN; i++) hit = hit && (i >= (int)a.t.len[j] || w[i] == a.t.ids[j][i]);
         if (hit) reason = 2 + j;
     }
+    if (!reason && a.done && a.done[s]) reason = STOP_CONSTRAINT;       // behind the sequences, in front of the budget; reported at the call's last step too
     if (!reason && k + 1 == a.max_new[s] && k + 1 < a.n_steps) reason = 1;
 #pragma unroll
     for (int i = 0; i < STOP_MAX_LEN - 1; i++) h[i] = w[i];

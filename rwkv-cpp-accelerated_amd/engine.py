@@ -39,7 +39,10 @@ ABI_SYMBOLS = [
     "rwkv_decode_batch_until", "rwkv_debug_stop_scan",
     "rwkv_topn_rows", "rwkv_decode_batch_logprobs",
     "rwkv_decode_beam", "rwkv_state_permute", "rwkv_debug_beam_step",
+    "rwkv_constraint_set", "rwkv_constraint_clear", "rwkv_constraint_state_set", "rwkv_constraint_state_get", "rwkv_pick_constrained",
+    "rwkv_debug_constrained_row", "rwkv_decode_batch_constrained",
 ]
+CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 TOPN_MAX = 32                     # RWKV_MAX_TOPN
@@ -102,6 +105,53 @@ def beam_params(width, stops=()):
     st = [int(t) for t in stops]
     ids = (C.c_uint64 * max(1, len(st)))(*st)
     return BeamParams(int(width), len(st), ids if st else None, 0), ids
+
+
+class Automaton(C.Structure):
+    """rwkv_automaton of include/rwkv_mi355x.h (40 bytes)"""
+    _fields_ = [("n_states", C.c_uint32), ("reserved", C.c_uint32), ("nnz", C.c_uint64), ("row_ptr", C.POINTER(C.c_uint32)),
+                ("tok", C.POINTER(C.c_uint32)), ("next", C.POINTER(C.c_uint32))]
+
+
+class Bias(C.Structure):
+    """rwkv_bias of include/rwkv_mi355x.h (24 bytes)"""
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("tok", C.POINTER(C.c_uint32)), ("val", C.POINTER(C.c_float))]
+
+
+class ConstrainParams(C.Structure):
+    """rwkv_constrain_params of include/rwkv_mi355x.h (48 bytes)"""
+    _fields_ = [("start", C.POINTER(C.c_uint32)), ("bias_ptr", C.POINTER(C.c_uint32)), ("bias_tok", C.POINTER(C.c_uint32)),
+                ("bias_val", C.POINTER(C.c_float)), ("out_state", C.POINTER(C.c_uint32)), ("reserved", C.c_uint64)]
+
+
+def _bias_arrays(bias):
+    """one bias list -- a dict {id: value} or a sequence of (id, value) pairs, given in any order -- as (ids u32, values f32), ids ascending"""
+    pairs = sorted((int(t), float(v)) for t, v in (bias.items() if hasattr(bias, "items") else bias))
+    return np.array([t for t, _ in pairs], dtype=np.uint32), np.array([v for _, v in pairs], dtype=np.float32)
+
+
+def constraint_trie(choices):
+    """(row_ptr, tok, next) u32: the automaton that spells exactly one of the token sequences `choices` -- a trie with shared prefixes merged, state
+    0 the root, the states numbered in the order the choices first reach them, every leaf terminal (include/rwkv_sampler.h constraint_trie builds
+    the same arrays).  A stream ends where it reaches a state WITHOUT edges: a choice that is a proper prefix of another one is accepted as a
+    path, but a stream that follows it goes on to one of its extensions.  Empty choices and ids outside 1 .. 50276 are skipped."""
+    kids = [dict()]
+    for ch in choices:
+        ch = [int(t) for t in ch]
+        if not ch or any(t < 1 or t >= mf.VOCAB for t in ch):
+            continue
+        q = 0
+        for t in ch:
+            if t not in kids[q]:
+                kids[q][t] = len(kids)
+                kids.append(dict())
+            q = kids[q][t]
+    row_ptr, tok, nxt = [0], [], []
+    for k in kids:
+        for t in sorted(k):
+            tok.append(t); nxt.append(k[t])
+        row_ptr.append(len(tok))
+    return np.array(row_ptr, np.uint32), np.array(tok, np.uint32), np.array(nxt, np.uint32)
 
 
 class RWKVError(RuntimeError):
@@ -193,6 +243,17 @@ def lib():
     L.rwkv_debug_beam_step.argtypes = [vp, C.POINTER(BeamParams), C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(u64), C.POINTER(C.c_uint32),
                                        C.POINTER(u64), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
     L.rwkv_debug_beam_step.restype = i32
+    u32p = C.POINTER(C.c_uint32)
+    L.rwkv_constraint_set.argtypes = [vp, C.POINTER(Automaton)]; L.rwkv_constraint_set.restype = i32
+    L.rwkv_constraint_clear.argtypes = [vp]; L.rwkv_constraint_clear.restype = i32
+    L.rwkv_constraint_state_set.argtypes = [vp, u64, u64, u32p]; L.rwkv_constraint_state_set.restype = i32
+    L.rwkv_constraint_state_get.argtypes = [vp, u64, u64, u32p]; L.rwkv_constraint_state_get.restype = i32
+    L.rwkv_pick_constrained.argtypes = [vp, u64, u64, C.POINTER(Pick), C.POINTER(Bias), C.c_double, i32, C.POINTER(u64), u32p]
+    L.rwkv_pick_constrained.restype = i32
+    L.rwkv_debug_constrained_row.argtypes = [vp, u64, vp]; L.rwkv_debug_constrained_row.restype = i32
+    L.rwkv_decode_batch_constrained.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(ConstrainParams),
+                                                C.POINTER(StopParams), C.POINTER(LogprobOut), C.POINTER(u64), u32p, u32p, C.POINTER(u64)]
+    L.rwkv_decode_batch_constrained.restype = i32
     _lib = L
     return L
 
@@ -519,7 +580,7 @@ class RWKV:
     # -- stop sequences and per-stream budgets in the device loops (include/rwkv_mi355x.h rwkv_decode_batch_until) --------
     def decode_batch_until(self, first_tokens, n_steps: int, stops=(), max_new=None, keep: bool = False, pick: str = "greedy", seeds=None,
                            temp: float = 1.0, tau: float = 0.8, recipe: bool = False, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
-                           frequency: float = 0.0, decay: float = 1.0, _logprobs=None):
+                           frequency: float = 0.0, decay: float = 1.0, _logprobs=None, _constrain=None):
         """decode_batch_greedy / _typical / _nucleus (pick = "greedy", "typical", "nucleus", with that call's parameters) in which stream s ends
         at the first of the stop sequences `stops` (lists of token ids, each 1 .. 8 long) that its newest ids spell, or after max_new[s] tokens.
         keep: the match history (and the nucleus counts) continue from the previous call.  Returns (ids [N][n_steps], 0 behind a stream's end;
@@ -538,7 +599,10 @@ class RWKV:
         sp, alive = stop_params(stops, max_new, keep)
         ln, rs, ran = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))(), C.c_uint64(0)
         sdp = None if kind == PICK_GREEDY else arr
-        if _logprobs is None:
+        if _constrain is not None:      # decode_batch_constrained: the same call with the constraint hook (and the record, or none)
+            call = lambda ft, n_, out: lib().rwkv_decode_batch_constrained(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(_constrain), C.byref(sp),
+                                                                           None if _logprobs is None else C.byref(_logprobs), out, ln, rs, C.byref(ran))
+        elif _logprobs is None:
             call = lambda ft, n_, out: lib().rwkv_decode_batch_until(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(sp), out, ln, rs, C.byref(ran))
         else:       # decode_batch_logprobs: the same call with the record
             call = lambda ft, n_, out: lib().rwkv_decode_batch_logprobs(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(sp), C.byref(_logprobs),
@@ -564,6 +628,84 @@ class RWKV:
         shape = (n, int(n_steps))
         return (ids, ln, rs, ran, lp[: n * n_steps].reshape(shape), ent[: n * n_steps].reshape(shape) if entropy else None,
                 tid[: n * n_steps * top_n].astype(np.int64).reshape(shape + (top_n,)), tlp[: n * n_steps * top_n].reshape(shape + (top_n,)))
+
+    # -- constrained decoding: a token automaton and a logit bias (include/rwkv_mi355x.h rwkv_decode_batch_constrained) --------
+    def constraint_set(self, row_ptr, tok, next):
+        """install the token-level automaton (row_ptr [S + 1], tok [nnz], next [nnz], u32; a state without edges is terminal) -- what a regex,
+        grammar or choice-list compiler of the caller's produced, or constraint_trie(choices).  Every slot's automaton state becomes 0."""
+        rp, tk, nx = (np.ascontiguousarray(a, dtype=np.uint32) for a in (row_ptr, tok, next))
+        if rp.size < 1 or tk.size != nx.size:
+            raise ValueError("row_ptr has S + 1 entries, tok and next nnz each")
+        u32p = C.POINTER(C.c_uint32)
+        a = Automaton(rp.size - 1, 0, tk.size, rp.ctypes.data_as(u32p), tk.ctypes.data_as(u32p) if tk.size else None,
+                      nx.ctypes.data_as(u32p) if nx.size else None)
+        _chk(lib().rwkv_constraint_set(self._h, C.byref(a)))
+
+    def constraint_clear(self):
+        _chk(lib().rwkv_constraint_clear(self._h))
+
+    def constraint_state_get(self, slot0: int = 0, n: int | None = None) -> np.ndarray:
+        """the automaton states of slots slot0 .. slot0 + n - 1 (default: all)"""
+        n = self.maxContext - int(slot0) if n is None else int(n)
+        out = np.zeros(max(1, n), dtype=np.uint32)
+        _chk(lib().rwkv_constraint_state_get(self._h, int(slot0), n, out.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out[:n].astype(np.int64)
+
+    def constraint_state_set(self, states, slot0: int = 0):
+        a = np.ascontiguousarray([int(v) for v in states], dtype=np.uint32)
+        _chk(lib().rwkv_constraint_state_set(self._h, int(slot0), a.size, a.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+    def pick_constrained(self, pick: str = "greedy", bias=None, u: float = 0.5, advance: bool = True, row: int = 0, slot: int = 0, temp: float = 1.0,
+                         top_p: float = 0.9, top_k: int = 0, presence: float = 0.0, frequency: float = 0.0, decay: float = 1.0, update: bool = False):
+        """ONE constrained draw from logits row `row` of the last forward under the automaton state of slot `slot` and the bias list `bias`
+        ({id: value}; -inf bans), greedy or nucleus with that call's parameters; advance: the slot's state moves along the pick.  Returns
+        (token, the slot's automaton state on return).  Logits and state stay as they are."""
+        kind = {"greedy": PICK_GREEDY, "typical": PICK_TYPICAL, "nucleus": PICK_NUCLEUS}[pick]
+        pk = Pick(kind, float(temp), 0.8, 0, nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_UPDATE if update else 0))
+        b, alive = None, None
+        if bias is not None:
+            alive = _bias_arrays(bias)
+            b = Bias(alive[0].size, 0, alive[0].ctypes.data_as(C.POINTER(C.c_uint32)), alive[1].ctypes.data_as(C.POINTER(C.c_float)))
+        tok, q = C.c_uint64(0), C.c_uint32(0)
+        _chk(lib().rwkv_pick_constrained(self._h, int(row), int(slot), C.byref(pk), None if b is None else C.byref(b), float(u), 1 if advance else 0,
+                                         C.byref(tok), C.byref(q)))
+        del alive
+        return int(tok.value), int(q.value)
+
+    def debug_constrained_row(self, row: int = 0) -> np.ndarray:
+        """row `row` of the second buffer as the last constrained pick or step left it (float32 [50277])"""
+        out = np.zeros(mf.VOCAB, dtype=np.float32)
+        _chk(lib().rwkv_debug_constrained_row(self._h, int(row), _ptr(out)))
+        return out
+
+    def decode_batch_constrained(self, first_tokens, n_steps: int, start=None, bias=None, logprobs: bool = False, top_n: int = 0, **kw):
+        """decode_batch_until (its arguments: stops, max_new, keep, pick = "greedy" or "nucleus", seeds and the pick's parameters) under the installed
+        automaton and per-stream logit bias: stream s starts in automaton state start[s] (None: where slot s stands) with the bias list bias[s]
+        ({id: value}, -inf bans; None: no bias) and also ends where its automaton reaches a terminal state (reason STOP_CONSTRAINT = 32).  Returns
+        (ids, len, reason, steps_run, state [N]: the automaton state after the stream's len tokens); logprobs=True appends decode_batch_logprobs'
+        logprob, entropy, top_ids, top_logprob -- the MODEL's, nothing of the mask shows in them."""
+        n = len(first_tokens)
+        u32p = C.POINTER(C.c_uint32)
+        st = None if start is None else np.ascontiguousarray([int(v) for v in start], dtype=np.uint32)
+        if st is not None and st.size != n:
+            raise ValueError("need one start state per stream")
+        bp = bt = bv = None
+        if bias is not None:
+            if len(bias) != n:
+                raise ValueError("need one bias list per stream (an empty one for none)")
+            lists = [_bias_arrays(b if b is not None else {}) for b in bias]
+            bp = np.concatenate([[0], np.cumsum([t.size for t, _ in lists])]).astype(np.uint32)
+            bt = np.concatenate([t for t, _ in lists] + [np.zeros(1, np.uint32)])          # (one entry of padding: the arrays are there when every list is empty)
+            bv = np.concatenate([v for _, v in lists] + [np.zeros(1, np.float32)])
+        out_state = np.zeros(max(1, n), dtype=np.uint32)
+        cp = ConstrainParams(None if st is None else st.ctypes.data_as(u32p), None if bp is None else bp.ctypes.data_as(u32p),
+                             None if bt is None else bt.ctypes.data_as(u32p), None if bv is None else bv.ctypes.data_as(C.POINTER(C.c_float)),
+                             out_state.ctypes.data_as(u32p), 0)
+        if logprobs:
+            r = self.decode_batch_logprobs(first_tokens, n_steps, top_n=top_n, _constrain=cp, **kw)
+        else:
+            r = self.decode_batch_until(first_tokens, n_steps, _constrain=cp, **kw)
+        return r[:4] + (out_state[:n].astype(np.int64),) + r[4:]
 
     def topn_rows(self, rows, top_n: int):
         """(ids [n][top_n], logprob [n][top_n]): the top_n most probable tokens of logits row rows[i] of the LAST forward (rwkv_topn_rows), in
