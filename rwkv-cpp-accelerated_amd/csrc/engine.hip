@@ -1034,7 +1034,9 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     if ((rc = dalloc(c, &c->ctl, 1))) return rc;
     HIPCHK(hipMemsetAsync(c->ctl, 0, sizeof(Ctl), c->stream));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_ctl), sizeof(Ctl) * max_ctx, hipHostMallocDefault));
-    c->gen_cap = 1u << 16;
+    constexpr unsigned GEN_CAP = 1u << 16;
+    static_assert(GEN_CAP == RWKV_MAX_DECODE_STEPS, "the one-stream form of a generation call writes gen[k] for every k < n_steps");
+    c->gen_cap = GEN_CAP;
     if ((rc = dalloc(c, &c->gen, (size_t)c->gen_cap))) return rc;
     HIPCHK(hipMemsetAsync(c->gen, 0, (size_t)c->gen_cap * sizeof(unsigned long long), c->stream));
     if ((rc = dalloc(c, &c->pick, 1))) return rc;
@@ -1558,10 +1560,10 @@ int enqueue_reset(rwkv_ctx *c)
     return 0;
 }
 
-// ---- stop sequences and budgets (stop.hip.h): what rwkv_decode_batch_until adds to the decode loops ----
-// One call's stopping, set up by stopper_setup (below decode_batch's checks).  The loops call after_step behind every step's pick and leave
-// when it says so; the caller ends with unpark.  The run-ahead is bounded, not drained: the active count of block b (RWKV_STOP_POLL steps)
-// travels into word b % STOP_RING of the pinned ring behind the block, and block b + 2 is enqueued only after that word has arrived non-zero.
+// ---- stop sequences and budgets (stop.hip.h): the stop test of a generation call (DecodeRun, below) ----
+// One call's stopping, set up by stopper_setup.  after_step is the last part of a step and says whether another one follows; unpark belongs to the
+// call's end.  The run-ahead is bounded, not drained: the active count of block b (RWKV_STOP_POLL steps) travels into word b % STOP_RING of the
+// pinned ring behind the block, and block b + 2 is enqueued only after that word has arrived non-zero.
 struct Stopper {
     StopArgs a{};
     ParkArgs p{};
@@ -1593,15 +1595,15 @@ struct Stopper {
     }
 };
 
-// ---- log-probs and top-n alternatives of the picks (topn.hip.h): what rwkv_decode_batch_logprobs adds to the decode loops ----
+// ---- log-probs and top-n alternatives of the picks (topn.hip.h): the record of a generation call ----
 // LP_REC in 8-byte words for R rows per step, S steps and top-n n: where the score tuples, the candidates and step 0 of the record start, the words of
 // one step (logprob [R] | entropy [R] | top ids [R][n] | top logprob [R][n]) and of the whole buffer
 struct LpLayout {
     size_t part, cand, rec, step, words;
     LpLayout(uint64_t R, uint64_t S, uint64_t n) : part(R), cand(part + R * SC_PART_Q), rec(cand + R * SC_G * n), step(R * (2 + 2 * n)), words(rec + S * step) {}
 };
-// One call's record, set up by lp_setup (below decode_batch's checks).  The loops call record behind every step's pick and in front of
-// Stopper::after_step: two launches over rows 0 .. R - 1 that read the logits rows and the picks and write step k of the record, nothing else.
+// One call's record, set up by lp_setup.  record is the part of a step between the pick and the stop test: two launches over rows 0 .. R - 1
+// that read the logits rows and the picks and write step k of the record, nothing else.
 struct LpRecorder {
     TopnArgs a{};
     double *rec = nullptr;
@@ -1648,6 +1650,18 @@ int check_pick(const rwkv_pick &pk)
     default: return fail(RWKV_E_ARG, "unknown pick kind %d", pk.kind);
     }
 }
+// an unknown kind answers in front of decode_batch's checks
+int check_pick_kind(const rwkv_pick &pk) { return pk.kind < RWKV_PICK_GREEDY || pk.kind > RWKV_PICK_NUCLEUS ? check_pick(pk) : 0; }
+// the ranges that several entry points share, each in the caller's words
+int check_steps(uint64_t n, const char *name) { return n == 0 || n > RWKV_MAX_DECODE_STEPS ? fail(RWKV_E_ARG, "%s must be in 1..%u", name, RWKV_MAX_DECODE_STEPS) : 0; }
+int check_row_slot(const rwkv_ctx *c, uint64_t row, uint64_t slot)
+{
+    return row < c->maxT && slot < c->maxT ? 0 : fail(RWKV_E_ARG, "logits row %llu or slot %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)slot, (unsigned long long)c->maxT);
+}
+int check_slot_span(const rwkv_ctx *c, uint64_t slot0, uint64_t n)
+{
+    return n != 0 && slot0 < c->maxT && n <= c->maxT - slot0 ? 0 : fail(RWKV_E_ARG, "slots %llu .. + %llu out of range (max context %llu)", (unsigned long long)slot0, (unsigned long long)n, (unsigned long long)c->maxT);
+}
 bool pick_penalty(const rwkv_pick &pk) { return pk.kind == RWKV_PICK_NUCLEUS && (pk.nucleus.presence != 0.f || pk.nucleus.frequency != 0.f); }
 // the count vectors (device [max_ctx][V] f32): allocated and zeroed once
 int counts_alloc(rwkv_ctx *c)
@@ -1679,7 +1693,7 @@ struct Sampler {
     NucleusArgs n{};
     DrawArgs &draw() { return kind == RWKV_PICK_NUCLEUS ? static_cast<DrawArgs &>(n) : t; }
 };
-// The sampler of a call that picks by `pk` (not greedy), on the context's single-row scratch.  `loop`: as the decode loop of one stream runs it
+// The sampler of a call that picks by `pk` (not greedy), on the context's single-row scratch.  `loop`: as a generation call of one stream runs it
 // (logit 0 always banned, the counts always updated, row and step from the control block, u from seed + step, the pick fed back); else the
 // caller sets row and u.  Call behind pick_counts.
 Sampler make_sampler(rwkv_ctx *c, const rwkv_pick &pk, bool loop)
@@ -1711,7 +1725,7 @@ Sampler make_sampler(rwkv_ctx *c, const rwkv_pick &pk, bool loop)
     }
     return s;
 }
-// the batched decode's form of it: rows 0 .. N - 1 (slots 0 .. N - 1) with a scratch slice and a seed each, the picks not fed back
+// the form of it in a generation call of many streams: rows 0 .. N - 1 (slots 0 .. N - 1) with a scratch slice and a seed each, the picks not fed back
 void sampler_to_batch(rwkv_ctx *c, Sampler &s, const unsigned long long *dseeds)
 {
     DrawArgs &d = s.draw();
@@ -1735,9 +1749,20 @@ int enqueue_pick(rwkv_ctx *c, const Sampler &s, unsigned rows)
     return 0;
 }
 
-// ---- constrained decoding (constrain.hip.h): what rwkv_decode_batch_constrained / rwkv_pick_constrained add to a pick ----
-// One call's constraint, set up by constrainer_setup (below decode_batch's checks).  Per step: rows() writes the constrained rows into the second
-// buffer, the call's pick reads them there (argmax() is the greedy one), advance() moves the automaton states behind the pick.
+// the row pick of the greedy kind: k_argmax_rows and its finish over n rows from `base` on, the ids into `ids` (BD_VAL / BD_IDX hold the partials)
+int enqueue_argmax_rows(rwkv_ctx *c, const float *base, unsigned n, unsigned long long *ids)
+{
+    float *val = c->buf<float>(BD_VAL);
+    unsigned *idx = c->buf<unsigned>(BD_IDX);
+    k_argmax_rows<<<dim3(AM_SLICES, n), dim3(AM_NT), 0, c->stream>>>(base, val, idx);
+    k_argmax_rows_finish<<<dim3(n), dim3(64), 0, c->stream>>>(val, idx, ids);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- constrained decoding (constrain.hip.h): the constraint of a generation call, or of one rwkv_pick_constrained ----
+// One call's constraint, set up by constrainer_setup.  rows() writes the constrained rows into the second buffer, the pick reads them there (a
+// sampler after feed(), the greedy kind as enqueue_argmax_rows over that buffer), advance() moves the automaton states behind the pick.
 struct Constrainer {
     ConstrainArgs r{};
     AdvanceArgs v{};
@@ -1747,16 +1772,8 @@ struct Constrainer {
         HIPCHK(hipGetLastError());
         return 0;
     }
-    // k_argmax_rows and its finish over n rows from `base` on (BD_VAL / BD_IDX hold the partials)
-    int argmax(rwkv_ctx *c, const float *base, unsigned n, unsigned long long *ids) const
-    {
-        float *val = c->buf<float>(BD_VAL);
-        unsigned *idx = c->buf<unsigned>(BD_IDX);
-        k_argmax_rows<<<dim3(AM_SLICES, n), dim3(AM_NT), 0, c->stream>>>(base, val, idx);
-        k_argmax_rows_finish<<<dim3(n), dim3(64), 0, c->stream>>>(val, idx, ids);
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
+    // the sampler reads the constrained rows and bans nothing itself: they already hold -inf at id 0
+    void feed(Sampler &s) const { s.draw().logits = r.out; s.draw().ban0 = 0; }
     int advance(rwkv_ctx *c, const unsigned long long *picks) const
     {
         k_constraint_advance<0><<<dim3((v.n + CN_ADV_NT - 1) / CN_ADV_NT), dim3(CN_ADV_NT), 0, c->stream>>>(v, picks);
@@ -1765,33 +1782,28 @@ struct Constrainer {
     }
 };
 
-// The device decode loop: n tokens on slot 0 (and its counts), `first` and then each token's pick, and the download of the picks.  The pick is
-// the argmax node of the token graph, or (`pk` not greedy) the sampler's three launches behind the token graph without that node: u of step k from
-// seed + k, logit 0 banned, the id fed back through the control block.  stop: the call can end early (the picks of the steps it ran are downloaded).
-// lp: every step's pick is recorded (in the greedy loop behind the token graph, whose last node is the pick: it reads gen[i]).
-// cn: the picks are constrained (Constrainer) -- the step's row goes through k_constrain_rows into the second buffer, the pick reads that buffer
-// (greedy: the row pick's two launches behind the token graph without its pick node, as the sampled loops run it), and k_constraint_advance moves
-// the slot's automaton state in front of the stop test (in the greedy loop it also feeds the pick back).
-int enqueue_decode(rwkv_ctx *c, uint64_t first, uint64_t n, const rwkv_pick &pk, uint64_t seed, uint64_t *out_tokens, Stopper *stop = nullptr,
-                   const LpRecorder *lp = nullptr, const Constrainer *cn = nullptr)
+// ---- a generation call: what it is (here), and how it runs (DecodeRun, below the setup functions of its parts) ----
+// rwkv_decode_greedy / _typical / _nucleus and rwkv_decode_batch_greedy / _typical / _nucleus / _until / _logprobs / _constrained fill this and hand
+// it on.  A null member means that the part is absent (trailing members left out of the initialiser are null).
+struct DecodeCall {
+    uint64_t N, n_steps;                            // streams (on slots 0 .. N - 1) and steps
+    const uint64_t *first, *seeds;                  // [N] each; the seeds of a sampled pick
+    rwkv_pick pick;
+    uint64_t *out_tokens;                           // [N][n_steps]
+    const rwkv_stop_params *stop;                   // stop sequences and budgets
+    uint32_t *out_len, *out_reason;                 // [N] each
+    uint64_t *steps_run;
+    const rwkv_logprob_out *lp;                     // the record, with the caller's arrays for it
+    const rwkv_constrain_params *cp;                // the constraint, with the caller's out_state
+};
+int run_call(rwkv_ctx *c, const DecodeCall &d, const StopTable *table = nullptr);
+// the checks of rwkv_decode_greedy / _typical / _nucleus behind the guard: one stream on slot 0
+int decode_one(rwkv_ctx *c, uint64_t first_token, uint64_t n, const rwkv_pick &pk, uint64_t seed, uint64_t *out_tokens)
 {
-    const bool sampled = pk.kind != RWKV_PICK_GREEDY;
-    if (const int rc = pick_counts(c, pk, 0, 1, true)) return rc;
-    Sampler s;                    // greedy: no arguments are built
-    if (sampled) { s = make_sampler(c, pk, true); s.draw().seed = seed; }
-    if (sampled && cn) { s.draw().logits = cn->r.out; s.draw().ban0 = 0; }      // the row already holds -inf at id 0
-    if (const int rc = set_ctl(c, first, 0, 0)) return rc;
-    bool more = true;
-    for (uint64_t i = 0; i < n && more; i++) {
-        if (const int rc = run_token(c, !sampled && !cn)) return rc;
-        if (const int rc = cn ? cn->rows(c, 1) : 0) return rc;
-        if (const int rc = sampled ? enqueue_pick(c, s, 1) : cn ? cn->argmax(c, cn->r.out, 1, c->pick) : 0) return rc;
-        if (const int rc = cn ? cn->advance(c, c->pick) : 0) return rc;
-        if (const int rc = lp ? lp->record(c, i, c->gen + i) : 0) return rc;
-        if (const int rc = stop ? stop->after_step(c, i, c->gen + i, &more) : 0) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(out_tokens, c->gen, (stop ? stop->steps_run : n) * sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-    return 0;
+    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
+    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
+    if (const int rc = check_pick(pk)) return rc;
+    return run_call(c, DecodeCall{1, n, &first_token, &seed, pk, out_tokens});
 }
 } // namespace
 
@@ -1804,9 +1816,7 @@ int rwkv_reset_state(rwkv_ctx *c)
 int rwkv_decode_greedy(rwkv_ctx *c, uint64_t first_token, uint64_t n, uint64_t *out_tokens)
 {
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, out_tokens)) return rc;
-    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
-    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    return finish(c, enqueue_decode(c, first_token, n, pick_greedy(), 0, out_tokens));
+    return decode_one(c, first_token, n, pick_greedy(), 0, out_tokens);
 }
 
 int rwkv_sample_typical(rwkv_ctx *c, uint64_t row, float temp, float tau, double u, int flags, uint64_t *token)
@@ -1826,11 +1836,7 @@ int rwkv_sample_typical(rwkv_ctx *c, uint64_t row, float temp, float tau, double
 int rwkv_decode_typical(rwkv_ctx *c, uint64_t first_token, uint64_t n, float temp, float tau, uint64_t seed, int flags, uint64_t *out_tokens)
 {
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, out_tokens)) return rc;
-    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
-    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    const rwkv_pick pk = pick_typical(temp, tau, flags);
-    if (const int rc = check_pick(pk)) return rc;
-    return finish(c, enqueue_decode(c, first_token, n, pk, seed, out_tokens));
+    return decode_one(c, first_token, n, pick_typical(temp, tau, flags), seed, out_tokens);
 }
 
 namespace {
@@ -1877,9 +1883,10 @@ int check_stop(const rwkv_stop_params *sp, uint64_t N, uint64_t n_steps, StopTab
 // max_new [N].  Where len starts (reason and max_new follow it at N and 2 N) and the record's size
 constexpr size_t stop_run_len(uint64_t N) { return 2 + 2 * N; }
 constexpr size_t stop_run_words(uint64_t N) { return stop_run_len(N) + 3 * N; }
-// the buffers and the upload of one call's stopping: the run record (STOP_RUN), the histories (once), and -- `park`: a decode loop, not the
-// planted scan -- the park buffer, the poll ring and, with `penalty`, the count vectors that are parked with the state
-int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_params &sp, const uint64_t *first, uint64_t N, uint64_t n_steps,
+// the buffers and the upload of one call's stopping (sp == nullptr: no sequence, no budget, no flag -- only its automaton ends a stream): the run
+// record (STOP_RUN), the histories (once), and -- `park`: a generation call, not the planted scan -- the park buffer, the poll ring and, with
+// `penalty`, the count vectors that are parked with the state
+int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_params *sp, const uint64_t *first, uint64_t N, uint64_t n_steps,
                   bool park, bool penalty)
 {
     if (park && !c->stop_ring) {
@@ -1899,10 +1906,10 @@ int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_
     const unsigned long long active = N;
     memcpy(&c->stop_host[0], &active, 8);
     memcpy(&c->stop_host[2], first, 8 * N);
-    for (uint64_t s = 0; s < N; s++) c->stop_host[stop_run_len(N) + 2 * N + s] = sp.max_new ? sp.max_new[s] : (unsigned)n_steps;
+    for (uint64_t s = 0; s < N; s++) c->stop_host[stop_run_len(N) + 2 * N + s] = sp && sp->max_new ? sp->max_new[s] : (unsigned)n_steps;
     unsigned *run = c->buf<unsigned>(STOP_RUN);
     HIPCHK(hipMemcpyAsync(run, c->stop_host.data(), sizeof(unsigned) * stop_run_words(N), hipMemcpyHostToDevice, c->stream));
-    st.a.t = t; st.a.n = (unsigned)N; st.a.n_steps = (unsigned)n_steps; st.a.keep = (sp.flags & RWKV_STOP_KEEP) ? 1 : 0;
+    st.a.t = t; st.a.n = (unsigned)N; st.a.n_steps = (unsigned)n_steps; st.a.keep = sp && (sp->flags & RWKV_STOP_KEEP) ? 1 : 0;
     st.a.hist = c->buf<unsigned>(STOP_HISTORY);
     st.a.active = reinterpret_cast<unsigned long long *>(run);
     st.a.first = st.a.active + 1;
@@ -1918,19 +1925,16 @@ int stopper_download(rwkv_ctx *c, const Stopper &st)
     HIPCHK(hipMemcpyAsync(&c->stop_host[stop_run_len(st.a.n)], st.a.len, sizeof(unsigned) * 2 * st.a.n, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
-// behind the wait: the call's lengths (a stream that never stopped: all n_steps) and reasons out of the host image; `stopped` false: the call
-// could stop no stream and has no image
+// behind the wait: the call's lengths (a stream that never stopped: all n_steps) and reasons out of the host image, into those of the two arrays
+// that the caller gave; `stopped` false: the call could stop no stream and has no image
 void stop_results(const rwkv_ctx *c, bool stopped, uint64_t N, uint64_t n_steps, uint32_t *out_len, uint32_t *out_reason)
 {
     for (uint64_t s = 0; s < N; s++) {
         const unsigned len = stopped ? c->stop_host[stop_run_len(N) + s] : 0u, reason = stopped ? c->stop_host[stop_run_len(N) + N + s] : 0u;
-        out_len[s] = len ? len : (uint32_t)n_steps;
+        if (out_len) out_len[s] = len ? len : (uint32_t)n_steps;
         if (out_reason) out_reason[s] = reason;
     }
 }
-
-// what rwkv_decode_batch_until adds to a call of decode_batch
-struct Until { const rwkv_stop_params *stop; uint32_t *out_len, *out_reason; uint64_t *steps_run; };
 
 // the record of a call over R rows per step (rows 0 .. R - 1: rows == nullptr) and S steps: LP_REC, and the kernels' arguments
 int lp_setup(rwkv_ctx *c, LpRecorder &r, uint64_t R, uint64_t S, uint32_t top_n)
@@ -1950,13 +1954,13 @@ int lp_download(rwkv_ctx *c, const LpRecorder &r, uint64_t ran)
     HIPCHK(hipMemcpyAsync(c->lp_host.data(), r.rec, sizeof(double) * ran * r.step, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
-// behind the wait: [step][stream] -> [stream][step] into the caller's arrays; 0 / 0.0 from a stream's end on
+// behind the wait: [step][stream] -> [stream][step] into the caller's arrays; 0 / 0.0 from a stream's end on (len == nullptr: no stream ended)
 void lp_results(const rwkv_ctx *c, const rwkv_logprob_out &o, uint64_t N, uint64_t n_steps, const uint32_t *len)
 {
     const uint64_t n = o.top_n, step = N * (2 + 2 * n);
     for (uint64_t s = 0; s < N; s++)
         for (uint64_t k = 0; k < n_steps; k++) {
-            const bool on = k < len[s];
+            const bool on = !len || k < len[s];
             const unsigned long long *h = on ? c->lp_host.data() + k * step : nullptr;
             const size_t at = s * n_steps + k;
             if (on) memcpy(&o.logprob[at], h + s, 8); else o.logprob[at] = 0.0;
@@ -2034,8 +2038,9 @@ CsrArgs csr_args(const rwkv_ctx *c)
 }
 // The buffers and the one upload of a constrained pick over n rows: rows row0 .. row0 + n - 1 with slots slot0 .. slot0 + n - 1, the bias lists
 // (bias_ptr [n + 1] into tok / val; nullptr: none) as CN_CALL: bias_ptr | tok | val | done [n] (`done` with a stopper `st` only: it reads the words).
+// start: the states a generation call starts its slots in go up too (host copy first: it is what the checks read); nullptr: where they stand
 int constrainer_setup(rwkv_ctx *c, Constrainer &cn, uint64_t row0, uint64_t slot0, uint64_t n, const uint32_t *bias_ptr, const uint32_t *bias_tok,
-                      const float *bias_val, Stopper *st)
+                      const float *bias_val, Stopper *st, const uint32_t *start = nullptr)
 {
     if (const int rc = constraint_buffers(c)) return rc;
     const size_t nb = bias_ptr ? bias_ptr[n] : 0, words = n + 1 + 2 * nb;
@@ -2057,154 +2062,188 @@ int constrainer_setup(rwkv_ctx *c, Constrainer &cn, uint64_t row0, uint64_t slot
     cn.v.done = st ? call + words : nullptr; cn.v.len = st ? st->a.len : nullptr;
     cn.v.feedback = 0; cn.v.ctl = c->ctl; cn.v.gen = c->gen; cn.v.gen_cap = c->gen_cap;
     if (st) st->a.done = cn.v.done;
+    if (start) {
+        std::vector<unsigned> &q = cn_states(c);
+        std::copy(start, start + n, q.begin() + slot0);
+        HIPCHK(hipMemcpyAsync(c->buf<unsigned>(CN_Q) + slot0, q.data() + slot0, sizeof(unsigned) * n, hipMemcpyHostToDevice, c->stream));
+    }
     return 0;
 }
-// the start states of a decode call go up (host copy first: it is what the checks read), and behind the call's last launch q comes back
-int constrainer_start(rwkv_ctx *c, const uint32_t *start, uint64_t N)
-{
-    if (!start) return 0;
-    std::vector<unsigned> &q = cn_states(c);
-    std::copy(start, start + N, q.begin());
-    HIPCHK(hipMemcpyAsync(c->buf<unsigned>(CN_Q), q.data(), sizeof(unsigned) * N, hipMemcpyHostToDevice, c->stream));
-    return 0;
-}
+// behind the call's last launch q comes back
 int constrainer_download(rwkv_ctx *c, uint64_t slot0, uint64_t n)
 {
     HIPCHK(hipMemcpyAsync(cn_states(c).data() + slot0, c->buf<unsigned>(CN_Q) + slot0, sizeof(unsigned) * n, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
 
-// rwkv_decode_batch_greedy / _typical / _nucleus / _until: checks (all of them before anything is launched), then n_streams == 1 as the decode path's loop,
-// else n_steps x (one rwkv_forward(n_streams, PARRALEL) schedule whose embedding reads the previous step's picks on the device + the
-// pick over all rows).  One upload ([seeds | first tokens]) and one download (all picks) in all.  until: streams stop at sequences and budgets
-// (Stopper: two small launches behind each step's pick, one behind the last); a call that cannot stop a stream is the plain loop.
-// `pk`: how a step picks -- k_argmax_rows, or the sampler's three launches (one seed per stream, the sampler's scratch per row)
-// cp (with until): the picks are constrained -- per step k_constrain_rows in front of the pick, which then reads the second buffer, and
-// k_constraint_advance behind it; such a call always owns a Stopper (a stream ends where its automaton does)
-int decode_batch(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t N, uint64_t n_steps, const rwkv_pick &pk, const uint64_t *seeds, uint64_t *out_tokens,
-                 const Until *until = nullptr, const rwkv_logprob_out *lpo = nullptr, const rwkv_constrain_params *cp = nullptr)
+// what a pick of kind `kind` over `rows` rows needs besides the rows: the row argmax's partials, or a scratch slice per row for a sampler
+int grow_pick_buffers(rwkv_ctx *c, int kind, uint64_t rows)
 {
-    const bool sampled = pk.kind != RWKV_PICK_GREEDY;
-    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, first_tokens && out_tokens && (!sampled || seeds))) return rc;
-    if (N == 0 || N > c->maxT) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu (max context)", (unsigned long long)c->maxT);
-    if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
-    if (const int rc = check_ids(first_tokens, N, "token")) return rc;
-    if (const int rc = check_pick(pk)) return rc;
-    StopTable table{};
-    if (const int rc = until ? check_stop(until->stop, N, n_steps, &table) : 0) return rc;
-    if (lpo && N * n_steps * (1 + (uint64_t)lpo->top_n) > RWKV_MAX_LOGPROB_ENTRIES)
-        return fail(RWKV_E_ARG, "n_streams * n_steps * (1 + top_n) must not exceed %u: split the generation into calls", RWKV_MAX_LOGPROB_ENTRIES);
-    if (N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
-    if (const int rc = cp ? check_constrain(c, *cp, pk, N) : 0) return rc;
-    LpRecorder recorder, *lp = lpo ? &recorder : nullptr;
-    Constrainer constrainer, *cn = cp ? &constrainer : nullptr;
-    Stopper stopper, *st = until && (cn || until->stop->n_seqs || until->stop->max_new) ? &stopper : nullptr;
-    auto stop_setup = [&]() -> int {
-        if (const int rc = st ? stopper_setup(c, *st, table, *until->stop, first_tokens, N, n_steps, true, pick_penalty(pk)) : 0) return rc;
-        if (!cn) return 0;
-        if (const int rc = constrainer_setup(c, *cn, 0, 0, N, cp->bias_ptr, cp->bias_tok, cp->bias_val, st)) return rc;
-        if (const int rc = constrainer_start(c, cp->start, N)) return rc;
-        if (sampled) return 0;                          // the greedy pick over the second buffer's rows: its partials
-        if (const int rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES)) return rc;
-        return grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
-    };
-    auto stop_end = [&]() -> int {
+    if (kind == RWKV_PICK_GREEDY) {
+        if (const int rc = grow_buffer(c, BD_VAL, sizeof(float) * rows * AM_SLICES)) return rc;
+        return grow_buffer(c, BD_IDX, sizeof(unsigned) * rows * AM_SLICES);
+    }
+    if (const int rc = grow_buffer(c, BD_PART, sizeof(double) * rows * TS_PART_ROW)) return rc;
+    if (const int rc = grow_buffer(c, BD_P, sizeof(float) * rows * TS_ROW)) return rc;
+    if (const int rc = grow_buffer(c, BD_PW, sizeof(float) * rows * TS_ROW)) return rc;
+    return grow_buffer(c, BD_KEY, sizeof(unsigned) * rows * TS_ROW);
+}
+
+// ---- the run of a generation call (DecodeCall) ----
+// setup; per step k: forward -> constrained rows -> pick -> automaton advance -> record -> stop test (step); end; the wait; results on the host.
+// The parts a call does not ask for are absent from every one of these.  A call has one of two forms, one stream (the decode path's kernels on
+// slot 0) or many (the chunk path over rows and slots 0 .. N - 1), and they differ in three things only:
+//   the forward             one: the token graph, with its argmax node only where that node is the pick (greedy, no constraint);
+//                           many: one rwkv_forward(N, PARRALEL) schedule whose embedding reads ids row k on the device
+//   where step k's picks    one: written to c->pick and fed back through the control block -- by the graph's node, the sampler or, greedy under a
+//   land                    constraint, k_constraint_advance -- which also puts them to gen[k], where the record and the stop test read them;
+//                           many: ids row k + 1, which the next forward reads
+//   the sampler's scratch   one: the context's single-row set, u of step k from seed + k through the control block;
+//                           many: the BD_* slices, one seed per row
+// One upload (one: the control block; many: [seeds | first tokens]) and one download of all picks.  A call that can stop no stream owns no Stopper
+// (two small launches behind each step's pick, one behind the last) and runs all its steps; a constrained call always owns one: a stream ends
+// where its automaton does.
+struct DecodeRun {
+    const DecodeCall &d;
+    const bool one = d.N == 1, sampled = d.pick.kind != RWKV_PICK_GREEDY;
+    Stopper stopper, *st = d.cp || (d.stop && (d.stop->n_seqs || d.stop->max_new)) ? &stopper : nullptr;
+    LpRecorder recorder, *lp = d.lp ? &recorder : nullptr;
+    Constrainer constrainer, *cn = d.cp ? &constrainer : nullptr;
+    Sampler smp{};                                  // greedy: no arguments are built
+    unsigned long long *ids = nullptr;              // many: ids row k, the ids fed at step k (BD_IDS behind the seeds)
+    uint64_t ran() const { return st ? st->steps_run : d.n_steps; }      // steps enqueued
+
+    // buffers, stopper, constrainer with its start states, recorder, counts, the one upload; then the sampler's arguments (no device work)
+    int setup(rwkv_ctx *c, const StopTable *table)
+    {
+        const uint64_t N = d.N;
+        if (const int rc = one ? 0 : grow_buffer(c, BD_IDS, sizeof(unsigned long long) * N * (d.n_steps + 2))) return rc;
+        if (const int rc = !one || (cn && !sampled) ? grow_pick_buffers(c, d.pick.kind, N) : 0) return rc;      // (one stream: only the row argmax needs any)
+        if (const int rc = st ? stopper_setup(c, *st, *table, d.stop, d.first, N, d.n_steps, true, pick_penalty(d.pick)) : 0) return rc;
+        if (const int rc = cn ? constrainer_setup(c, *cn, 0, 0, N, d.cp->bias_ptr, d.cp->bias_tok, d.cp->bias_val, st, d.cp->start) : 0) return rc;
+        if (const int rc = lp ? lp_setup(c, *lp, N, d.n_steps, d.lp->top_n) : 0) return rc;
+        if (const int rc = pick_counts(c, d.pick, 0, N, true)) return rc;
+        c->bd_host.assign(N * (d.n_steps + 1), 0ull);       // many: the upload; both: the download of the picks, [step][stream]
+        if (one) {
+            if (const int rc = set_ctl(c, d.first[0], 0, 0)) return rc;
+        } else {
+            unsigned long long *dseeds = c->buf<unsigned long long>(BD_IDS);
+            ids = dseeds + N;
+            for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = sampled ? d.seeds[s] : 0ull; c->bd_host[N + s] = d.first[s]; }
+            HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
+        }
+        if (sampled) {
+            smp = make_sampler(c, d.pick, true);
+            if (one) smp.draw().seed = d.seeds[0];
+            else sampler_to_batch(c, smp, ids - N);
+            if (cn) cn->feed(smp);
+        }
+        if (cn) cn->v.feedback = one && !sampled ? 1 : 0;      // one stream, greedy: k_constraint_advance feeds the pick back
+        return 0;
+    }
+
+    // step k; more: enqueue the next one
+    int step(rwkv_ctx *c, uint64_t k, bool *more)
+    {
+        const unsigned n = (unsigned)d.N;
+        unsigned long long *to = one ? c->pick : ids + (k + 1) * n;       // where the pick writes,
+        const unsigned long long *picks = one ? c->gen + k : to;          // and where what follows it reads step k's picks
+        if (const int rc = one ? run_token(c, !sampled && !cn) : enqueue_rows(c, nullptr, ids + k * n, n, RWKV_MODE_PARRALEL)) return rc;      // logits rows and state slots 0 .. N - 1
+        if (const int rc = cn ? cn->rows(c, n) : 0) return rc;
+        if (sampled) {
+            smp.draw().step = one ? -1 : (int)k; smp.draw().pick = to;
+            if (const int rc = enqueue_pick(c, smp, n)) return rc;
+        } else if (cn || !one) {                                          // (else the token graph's last node was the pick)
+            if (const int rc = enqueue_argmax_rows(c, cn ? cn->r.out : c->logits, n, to)) return rc;
+        }
+        if (const int rc = cn ? cn->advance(c, to) : 0) return rc;
+        if (const int rc = lp ? lp->record(c, k, picks) : 0) return rc;
+        return st ? st->after_step(c, k, picks, more) : 0;
+    }
+
+    // behind the last step: record download, picks download (of the steps that ran), unpark, lengths and reasons, automaton states
+    int end(rwkv_ctx *c)
+    {
+        if (const int rc = lp ? lp_download(c, *lp, ran()) : 0) return rc;
+        HIPCHK(hipMemcpyAsync(c->bd_host.data(), one ? c->gen : ids + d.N, sizeof(unsigned long long) * d.N * ran(), hipMemcpyDeviceToHost, c->stream));
         if (const int rc = st ? st->unpark(c) : 0) return rc;
         if (const int rc = st ? stopper_download(c, *st) : 0) return rc;
-        return cn ? constrainer_download(c, 0, N) : 0;
-    };
-    // lengths, reasons and the steps enqueued; the ids behind a stream's end are 0 (out_tokens holds the picks of the steps that ran)
-    auto until_results = [&]() {
-        const uint64_t ran = st ? st->steps_run : n_steps;
-        stop_results(c, st != nullptr, N, n_steps, until->out_len, until->out_reason);
-        for (uint64_t s = 0; s < N; s++)
-            for (uint64_t k = until->out_len[s]; k < n_steps; k++) out_tokens[s * n_steps + k] = 0;
-        if (until->steps_run) *until->steps_run = ran;
-        if (lpo) lp_results(c, *lpo, N, n_steps, until->out_len);
-        if (cn && cp->out_state) std::copy(c->cn_q.begin(), c->cn_q.begin() + N, cp->out_state);
-        return 0;
-    };
-    if (N == 1) {     // the decode path's kernels on slot 0
-        const int rc = finish(c, [&]() -> int {
-            if (const int rc = stop_setup()) return rc;
-            if (const int rc = lp ? lp_setup(c, *lp, 1, n_steps, lpo->top_n) : 0) return rc;
-            if (cn) cn->v.feedback = sampled ? 0 : 1;      // the greedy loop's pick is fed back by k_constraint_advance
-            if (const int rc = enqueue_decode(c, first_tokens[0], n_steps, pk, sampled ? seeds[0] : 0, out_tokens, st, lp, cn)) return rc;
-            if (const int rc = lp ? lp_download(c, *lp, st ? st->steps_run : n_steps) : 0) return rc;
-            return stop_end();
-        }());
-        return rc || !until ? rc : until_results();
+        return cn ? constrainer_download(c, 0, d.N) : 0;
     }
-    uint64_t ran = n_steps;                             // steps enqueued
+
+    // behind the wait: [step][stream] -> [stream][step], lengths, reasons and the steps enqueued, 0 for the ids behind a stream's end, the record,
+    // the automaton states
+    void results(const rwkv_ctx *c) const
+    {
+        const uint64_t N = d.N, S = d.n_steps;
+        for (uint64_t k = 0; k < ran(); k++)
+            for (uint64_t s = 0; s < N; s++) d.out_tokens[s * S + k] = c->bd_host[k * N + s];
+        stop_results(c, st != nullptr, N, S, d.out_len, d.out_reason);
+        for (uint64_t s = 0; d.out_len && s < N; s++)
+            for (uint64_t k = d.out_len[s]; k < S; k++) d.out_tokens[s * S + k] = 0;
+        if (d.steps_run) *d.steps_run = ran();
+        if (lp) lp_results(c, *d.lp, N, S, d.out_len);
+        if (cn && d.cp->out_state) std::copy(c->cn_q.begin(), c->cn_q.begin() + N, d.cp->out_state);
+    }
+};
+
+int run_call(rwkv_ctx *c, const DecodeCall &d, const StopTable *table)
+{
+    DecodeRun r{d};
     const int rc = finish(c, [&]() -> int {
-        int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * N * (n_steps + 2));
-        if (!rc) rc = stop_setup();
-        if (!rc && lp) rc = lp_setup(c, *lp, N, n_steps, lpo->top_n);
-        if (!rc && !sampled) rc = grow_buffer(c, BD_VAL, sizeof(float) * N * AM_SLICES);
-        if (!rc && !sampled) rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * N * AM_SLICES);
-        if (!rc && sampled) rc = grow_buffer(c, BD_PART, sizeof(double) * N * TS_PART_ROW);
-        if (!rc && sampled) rc = grow_buffer(c, BD_P, sizeof(float) * N * TS_ROW);
-        if (!rc && sampled) rc = grow_buffer(c, BD_PW, sizeof(float) * N * TS_ROW);
-        if (!rc && sampled) rc = grow_buffer(c, BD_KEY, sizeof(unsigned) * N * TS_ROW);
-        if (!rc) rc = pick_counts(c, pk, 0, N, true);
-        if (rc) return rc;
-        unsigned long long *dseeds = c->buf<unsigned long long>(BD_IDS), *ids = dseeds + N;   // ids row k: the ids fed at step k
-        c->bd_host.assign(N * (n_steps + 1), 0ull);
-        for (uint64_t s = 0; s < N; s++) { c->bd_host[s] = sampled ? seeds[s] : 0ull; c->bd_host[N + s] = first_tokens[s]; }
-        HIPCHK(hipMemcpyAsync(dseeds, c->bd_host.data(), sizeof(unsigned long long) * 2 * N, hipMemcpyHostToDevice, c->stream));
-        Sampler smp;
-        if (sampled) { smp = make_sampler(c, pk, true); sampler_to_batch(c, smp, dseeds); }
-        if (sampled && cn) { smp.draw().logits = cn->r.out; smp.draw().ban0 = 0; }      // the rows already hold -inf at id 0
-        for (uint64_t k = 0; k < n_steps; k++) {
-            if ((rc = enqueue_rows(c, nullptr, ids + k * N, N, RWKV_MODE_PARRALEL))) return rc;       // logits rows 0 .. N - 1, state slots 0 .. N - 1
-            unsigned long long *next = ids + (k + 1) * N;
-            if ((rc = cn ? cn->rows(c, (unsigned)N) : 0)) return rc;
-            if (sampled) {
-                smp.draw().step = (int)k; smp.draw().pick = next;
-                if ((rc = enqueue_pick(c, smp, (unsigned)N))) return rc;
-            } else if (cn) {
-                if ((rc = cn->argmax(c, cn->r.out, (unsigned)N, next))) return rc;
-            } else {
-                float *val = c->buf<float>(BD_VAL);
-                unsigned *idx = c->buf<unsigned>(BD_IDX);
-                k_argmax_rows<<<dim3(AM_SLICES, (unsigned)N), dim3(AM_NT), 0, c->stream>>>(c->logits, val, idx);
-                k_argmax_rows_finish<<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(val, idx, next);
-                HIPCHK(hipGetLastError());
-            }
-            if ((rc = cn ? cn->advance(c, next) : 0)) return rc;
-            if ((rc = lp ? lp->record(c, k, next) : 0)) return rc;
-            bool more = true;
-            if ((rc = st ? st->after_step(c, k, next, &more) : 0)) return rc;
-            if (!more) break;
-        }
-        if (st) ran = st->steps_run;
-        if ((rc = lp ? lp_download(c, *lp, ran) : 0)) return rc;
-        HIPCHK(hipMemcpyAsync(c->bd_host.data(), ids + N, sizeof(unsigned long long) * N * ran, hipMemcpyDeviceToHost, c->stream));
-        return stop_end();
+        if (const int rc = r.setup(c, table)) return rc;
+        bool more = true;
+        for (uint64_t k = 0; k < d.n_steps && more; k++)
+            if (const int rc = r.step(c, k, &more)) return rc;
+        return r.end(c);
     }());
-    if (rc) return rc;
-    for (uint64_t k = 0; k < ran; k++)                  // [step][stream] -> [stream][step]
-        for (uint64_t s = 0; s < N; s++) out_tokens[s * n_steps + k] = c->bd_host[k * N + s];
-    return until ? until_results() : 0;
+    if (!rc) r.results(c);
+    return rc;
+}
+
+// the checks of rwkv_decode_batch_greedy / _typical / _nucleus / _until / _logprobs / _constrained, all of them before anything is launched
+int decode_batch(rwkv_ctx *c, const DecodeCall &d)
+{
+    if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, d.first && d.out_tokens && (d.pick.kind == RWKV_PICK_GREEDY || d.seeds))) return rc;
+    if (d.N == 0 || d.N > c->maxT) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu (max context)", (unsigned long long)c->maxT);
+    if (const int rc = check_steps(d.n_steps, "n_steps")) return rc;
+    if (const int rc = check_ids(d.first, d.N, "token")) return rc;
+    if (const int rc = check_pick(d.pick)) return rc;
+    StopTable table{};
+    if (const int rc = d.stop ? check_stop(d.stop, d.N, d.n_steps, &table) : 0) return rc;
+    if (d.lp && d.N * d.n_steps * (1 + (uint64_t)d.lp->top_n) > RWKV_MAX_LOGPROB_ENTRIES)
+        return fail(RWKV_E_ARG, "n_streams * n_steps * (1 + top_n) must not exceed %u: split the generation into calls", RWKV_MAX_LOGPROB_ENTRIES);
+    if (d.N >= 2 && !c->seq_ok) return fail(RWKV_E_STATE, "n_streams >= 2 needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
+    if (const int rc = d.cp ? check_constrain(c, *d.cp, d.pick, d.N) : 0) return rc;
+    return run_call(c, d, &table);
+}
+
+// the record's description is acceptable
+int check_logprob_out(const rwkv_logprob_out &lp)
+{
+    if (lp.top_n > RWKV_MAX_TOPN) return fail(RWKV_E_ARG, "top_n must be in 0..%u", RWKV_MAX_TOPN);
+    if ((lp.top_n > 0) != (lp.top_ids != nullptr) || (lp.top_n > 0) != (lp.top_logprob != nullptr))
+        return fail(RWKV_E_ARG, "top_ids and top_logprob go with top_n > 0, and only with it");
+    if (lp.reserved) return fail(RWKV_E_ARG, "reserved != 0");
+    return 0;
 }
 } // namespace
 
 int rwkv_decode_batch_greedy(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, pick_greedy(), nullptr, out_tokens);
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, nullptr, pick_greedy(), out_tokens});
 }
 
 int rwkv_decode_batch_typical(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, float temp, float tau,
                               const uint64_t *seeds, int flags, uint64_t *out_tokens)
 {
-    return decode_batch(c, first_tokens, n_streams, n_steps, pick_typical(temp, tau, flags), seeds, out_tokens);
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, pick_typical(temp, tau, flags), out_tokens});
 }
 
 int rwkv_sample_nucleus(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_nucleus_params *p, double u, uint64_t *token)
 {
     if (const int rc = guard(c, NEED_HEAD | LAUNCHES, p && token)) return rc;
-    if (row >= c->maxT || slot >= c->maxT)
-        return fail(RWKV_E_ARG, "logits row %llu or slot %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (const int rc = check_row_slot(c, row, slot)) return rc;
     const rwkv_pick pk = pick_nucleus(*p);
     if (const int rc = check_pick(pk)) return rc;
     if (!(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need 0 <= u < 1");
@@ -2221,18 +2260,14 @@ int rwkv_sample_nucleus(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_nuc
 int rwkv_decode_nucleus(rwkv_ctx *c, uint64_t first_token, uint64_t n, const rwkv_nucleus_params *p, uint64_t seed, uint64_t *out_tokens)
 {
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, p && out_tokens)) return rc;
-    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
-    if (n == 0 || n > c->gen_cap) return fail(RWKV_E_ARG, "n_tokens must be in 1..%u", c->gen_cap);
-    const rwkv_pick pk = pick_nucleus(*p);
-    if (const int rc = check_pick(pk)) return rc;
-    return finish(c, enqueue_decode(c, first_token, n, pk, seed, out_tokens));
+    return decode_one(c, first_token, n, pick_nucleus(*p), seed, out_tokens);
 }
 
 int rwkv_decode_batch_nucleus(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_nucleus_params *p,
                               const uint64_t *seeds, uint64_t *out_tokens)
 {
     if (const int rc = guard(c, 0, p)) return rc;
-    return decode_batch(c, first_tokens, n_streams, n_steps, pick_nucleus(*p), seeds, out_tokens);
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, pick_nucleus(*p), out_tokens});
 }
 
 int rwkv_decode_batch_until(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
@@ -2240,9 +2275,8 @@ int rwkv_decode_batch_until(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t 
                             uint64_t *steps_run)
 {
     if (const int rc = guard(c, NEED_WHOLE, pick && stop && out_len)) return rc;
-    const Until until{stop, out_len, out_reason, steps_run};
-    if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);      // an unknown kind: in front of decode_batch's checks
-    return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until);
+    if (const int rc = check_pick_kind(*pick)) return rc;
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, *pick, out_tokens, stop, out_len, out_reason, steps_run});
 }
 
 static_assert(TOPN_MAX == RWKV_MAX_TOPN, "topn.hip.h holds the header's limit");
@@ -2252,15 +2286,9 @@ int rwkv_decode_batch_logprobs(rwkv_ctx *c, const uint64_t *first_tokens, uint64
                                uint32_t *out_len, uint32_t *out_reason, uint64_t *steps_run)
 {
     if (const int rc = guard(c, NEED_WHOLE, pick && lp && lp->logprob && (!stop || out_len))) return rc;
-    if (lp->top_n > RWKV_MAX_TOPN) return fail(RWKV_E_ARG, "top_n must be in 0..%u", RWKV_MAX_TOPN);
-    if ((lp->top_n > 0) != (lp->top_ids != nullptr) || (lp->top_n > 0) != (lp->top_logprob != nullptr))
-        return fail(RWKV_E_ARG, "top_ids and top_logprob go with top_n > 0, and only with it");
-    if (lp->reserved) return fail(RWKV_E_ARG, "reserved != 0");
-    if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);
-    const rwkv_stop_params none{};                      // no stop: the plain loop, every stream runs n_steps
-    std::vector<uint32_t> len(out_len ? 0 : std::min<uint64_t>(n_streams, c->maxT));
-    const Until until{stop ? stop : &none, out_len ? out_len : len.data(), out_reason, steps_run};
-    return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until, lp);
+    if (const int rc = check_logprob_out(*lp)) return rc;
+    if (const int rc = check_pick_kind(*pick)) return rc;
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, *pick, out_tokens, stop, out_len, out_reason, steps_run, lp});
 }
 
 int rwkv_constraint_set(rwkv_ctx *c, const rwkv_automaton *a)
@@ -2311,7 +2339,7 @@ int rwkv_constraint_clear(rwkv_ctx *c)
 int rwkv_constraint_state_set(rwkv_ctx *c, uint64_t slot0, uint64_t n, const uint32_t *states)
 {
     if (const int rc = guard(c, NEED_LOADED, states)) return rc;
-    if (n == 0 || slot0 >= c->maxT || n > c->maxT - slot0) return fail(RWKV_E_ARG, "slots %llu .. + %llu out of range (max context %llu)", (unsigned long long)slot0, (unsigned long long)n, (unsigned long long)c->maxT);
+    if (const int rc = check_slot_span(c, slot0, n)) return rc;
     for (uint64_t i = 0; i < n; i++)
         if (states[i] >= std::max(c->cn_S, 1u)) return fail(RWKV_E_ARG, "automaton state %u is not below %u", states[i], std::max(c->cn_S, 1u));
     std::vector<unsigned> &q = cn_states(c);
@@ -2330,7 +2358,7 @@ int rwkv_constraint_state_set(rwkv_ctx *c, uint64_t slot0, uint64_t n, const uin
 int rwkv_constraint_state_get(rwkv_ctx *c, uint64_t slot0, uint64_t n, uint32_t *states)
 {
     if (const int rc = guard(c, NEED_LOADED, states)) return rc;
-    if (n == 0 || slot0 >= c->maxT || n > c->maxT - slot0) return fail(RWKV_E_ARG, "slots %llu .. + %llu out of range (max context %llu)", (unsigned long long)slot0, (unsigned long long)n, (unsigned long long)c->maxT);
+    if (const int rc = check_slot_span(c, slot0, n)) return rc;
     const std::vector<unsigned> &q = cn_states(c);
     std::copy(q.begin() + slot0, q.begin() + slot0 + n, states);
     return 0;
@@ -2340,8 +2368,7 @@ int rwkv_pick_constrained(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_p
                           uint32_t *state_out)
 {
     if (const int rc = guard(c, NEED_HEAD | LAUNCHES, pick && token)) return rc;
-    if (row >= c->maxT || slot >= c->maxT)
-        return fail(RWKV_E_ARG, "logits row %llu or slot %llu out of range (max context %llu)", (unsigned long long)row, (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (const int rc = check_row_slot(c, row, slot)) return rc;
     if (pick->kind == RWKV_PICK_TYPICAL) return fail(RWKV_E_ARG, "typical sampling under a constraint is out of scope: pick greedy or nucleus");
     if (const int rc = check_pick(*pick)) return rc;
     const bool sampled = pick->kind == RWKV_PICK_NUCLEUS;
@@ -2357,12 +2384,12 @@ int rwkv_pick_constrained(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_p
         if (sampled) {
             if (const int rc = pick_counts(c, *pick, slot, 1, false)) return rc;
             Sampler s = make_sampler(c, *pick, false);
-            s.n.logits = cn.r.out; s.n.ban0 = 0; s.n.row = (int)row; s.n.slot = (unsigned)slot; s.n.u = u;
+            cn.feed(s);
+            s.n.row = (int)row; s.n.slot = (unsigned)slot; s.n.u = u;
             if (const int rc = enqueue_pick(c, s, 1)) return rc;
         } else {
-            if (const int rc = grow_buffer(c, BD_VAL, sizeof(float) * AM_SLICES)) return rc;
-            if (const int rc = grow_buffer(c, BD_IDX, sizeof(unsigned) * AM_SLICES)) return rc;
-            if (const int rc = cn.argmax(c, cn.r.out + row * RWKV_VOCAB, 1, c->pick)) return rc;
+            if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, 1)) return rc;
+            if (const int rc = enqueue_argmax_rows(c, cn.r.out + row * RWKV_VOCAB, 1, c->pick)) return rc;
         }
         if (advance && c->cn_S) {
             if (const int rc = cn.advance(c, c->pick)) return rc;
@@ -2391,14 +2418,9 @@ int rwkv_decode_batch_constrained(rwkv_ctx *c, const uint64_t *first_tokens, uin
                                   uint64_t *out_tokens, uint32_t *out_len, uint32_t *out_reason, uint64_t *steps_run)
 {
     if (const int rc = guard(c, NEED_WHOLE, pick && cp && out_len && (!lp || lp->logprob))) return rc;
-    if (lp && lp->top_n > RWKV_MAX_TOPN) return fail(RWKV_E_ARG, "top_n must be in 0..%u", RWKV_MAX_TOPN);
-    if (lp && ((lp->top_n > 0) != (lp->top_ids != nullptr) || (lp->top_n > 0) != (lp->top_logprob != nullptr)))
-        return fail(RWKV_E_ARG, "top_ids and top_logprob go with top_n > 0, and only with it");
-    if (lp && lp->reserved) return fail(RWKV_E_ARG, "reserved != 0");
-    if (pick->kind < RWKV_PICK_GREEDY || pick->kind > RWKV_PICK_NUCLEUS) return check_pick(*pick);
-    const rwkv_stop_params none{};                      // no stop: every stream runs until its automaton ends it, or n_steps
-    const Until until{stop ? stop : &none, out_len, out_reason, steps_run};
-    return decode_batch(c, first_tokens, n_streams, n_steps, *pick, seeds, out_tokens, &until, lp, cp);
+    if (const int rc = lp ? check_logprob_out(*lp) : 0) return rc;
+    if (const int rc = check_pick_kind(*pick)) return rc;
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, *pick, out_tokens, stop, out_len, out_reason, steps_run, lp, cp});
 }
 
 int rwkv_topn_rows(rwkv_ctx *c, const uint64_t *rows, uint64_t n, uint32_t top_n, uint64_t *ids, double *logprob)
@@ -2435,7 +2457,7 @@ int rwkv_debug_stop_scan(rwkv_ctx *c, const uint64_t *ids, const uint64_t *first
 {
     if (const int rc = guard(c, NEED_LOADED | LAUNCHES, ids && first_tokens && stop && out_len && out_reason)) return rc;
     if (n == 0 || n > c->maxT) return fail(RWKV_E_ARG, "n must be in 1..%llu (max context)", (unsigned long long)c->maxT);
-    if (steps == 0 || steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
+    if (const int rc = check_steps(steps, "steps")) return rc;
     if (const int rc = check_ids(first_tokens, n, "token")) return rc;
     if (const int rc = check_ids(ids, n * steps, "planted")) return rc;
     StopTable table{};
@@ -2443,9 +2465,9 @@ int rwkv_debug_stop_scan(rwkv_ctx *c, const uint64_t *ids, const uint64_t *first
     Stopper st;
     const int rc = finish(c, [&]() -> int {
         if (const int rc = grow_buffer(c, BD_IDS, sizeof(unsigned long long) * n * steps)) return rc;
-        if (const int rc = stopper_setup(c, st, table, *stop, first_tokens, n, steps, false, false)) return rc;
+        if (const int rc = stopper_setup(c, st, table, stop, first_tokens, n, steps, false, false)) return rc;
         c->bd_host.resize(n * steps);
-        for (uint64_t k = 0; k < steps; k++)            // [stream][step] -> [step][stream], as the batched loop leaves its picks
+        for (uint64_t k = 0; k < steps; k++)            // [stream][step] -> [step][stream], as a generation call of many streams leaves its picks
             for (uint64_t s = 0; s < n; s++) c->bd_host[k * n + s] = ids[s * steps + k];
         unsigned long long *picks = c->buf<unsigned long long>(BD_IDS);
         HIPCHK(hipMemcpyAsync(picks, c->bd_host.data(), sizeof(unsigned long long) * n * steps, hipMemcpyHostToDevice, c->stream));
@@ -2607,7 +2629,7 @@ int rwkv_decode_beam(rwkv_ctx *c, uint64_t first_token, uint64_t n_steps, const 
 {
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, bp && out && out->tokens && out->len && out->score)) return rc;
     if (const int rc = check_beam(c, bp)) return rc;
-    if (n_steps == 0 || n_steps > RWKV_MAX_DECODE_STEPS) return fail(RWKV_E_ARG, "n_steps must be in 1..%u", RWKV_MAX_DECODE_STEPS);
+    if (const int rc = check_steps(n_steps, "n_steps")) return rc;
     if (const int rc = check_ids(&first_token, 1, "token")) return rc;
     if (!c->seq_ok) return fail(RWKV_E_STATE, "beam search needs the chunk path (off: RWKV_SEQ=0, max context 1 or n_embed not a multiple of 64)");
     const uint64_t W = bp->width;

@@ -264,30 +264,43 @@ def test_the_loop_is_the_callers_loop_it_replaces(eng, model, start, n, kind):
     m.constraint_clear()
 
 
+@pytest.mark.parametrize("logprobs", [False, True])
+@pytest.mark.parametrize("n", [1, 5])
 @pytest.mark.parametrize("kind", ["greedy", "nucleus"])
-def test_an_allow_everything_automaton_is_the_until_call(eng, model, start, kind):
-    m, n = model, 5
-    first, seeds, budgets = firsts_of(n), seeds_of(n), [3, 12, 7, 1, 12]
+def test_an_allow_everything_automaton_is_the_until_call(eng, model, start, kind, n, logprobs):
+    """stops, budgets, the constraint and (logprobs) the record in one call, in the one-stream form and the batched one: the only place
+    where every hook of the decode loops is on at once"""
+    m = model
+    first, seeds, budgets = firsts_of(n), seeds_of(n), [3, 12, 7, 1, 12] if n == 5 else [7]
     restore(m, start)
     full = m.decode_batch_until(first, STEPS, seeds=seeds, **KW[kind])
-    stop = [int(v) for v in full[0][1][5:7]]
+    stop = [int(v) for v in (full[0][1][5:7] if n == 5 else full[0][0][3:5])]               # n = 1: the stream's own ids, complete at step 5 of 12
+    rec = dict(logprobs=True, top_n=3) if logprobs else {}
     restore(m, start)
-    u = m.decode_batch_until(first, STEPS, seeds=seeds, stops=[stop], max_new=budgets, **KW[kind])
+    if logprobs:
+        u = m.decode_batch_logprobs(first, STEPS, top_n=3, seeds=seeds, stops=[stop], max_new=budgets, **KW[kind])
+    else:
+        u = m.decode_batch_until(first, STEPS, seeds=seeds, stops=[stop], max_new=budgets, **KW[kind])
     ref = slots(m, n, kind == "nucleus")
+    if n == 1:
+        assert u[1][0] <= 5 and u[2][0] == 2                                          # the stop fired in mid-run, in front of the budget
     m.constraint_set(*cc.everything_automaton())
     restore(m, start)
-    r = m.decode_batch_constrained(first, STEPS, seeds=seeds, stops=[stop], max_new=budgets, **KW[kind])
+    r = m.decode_batch_constrained(first, STEPS, seeds=seeds, stops=[stop], max_new=budgets, **rec, **KW[kind])
     got = slots(m, n, kind == "nucleus")
     m.constraint_clear()
     restore(m, start)
-    b = m.decode_batch_constrained(first, STEPS, seeds=seeds, stops=[stop], max_new=budgets, **KW[kind])     # no automaton: the implicit state
+    b = m.decode_batch_constrained(first, STEPS, seeds=seeds, stops=[stop], max_new=budgets, **rec, **KW[kind])     # no automaton: the implicit state
     if not np.array_equal(r[0], u[0]):
+        print(f"{kind} n={n} logprobs={logprobs}: len {u[1].tolist()} reason {u[2].tolist()} steps_run {u[3]}")
         print("row maxima of the last step:", ref[5].max(axis=1))                           # (-inf instead of -99 at id 0 can only show at a tiny logit scale)
     assert np.array_equal(r[0], u[0]) and np.array_equal(b[0], u[0])
     assert np.array_equal(r[1], u[1]) and np.array_equal(r[2], u[2]) and r[3] == u[3] and r[4].tolist() == [0] * n
     assert np.array_equal(b[1], u[1]) and np.array_equal(b[2], u[2])
     for g, w in zip(got, ref):
         assert same_bits(g, w)
+    for i in range(4, len(u)):                                                              # logprob, entropy, top_ids, top_logprob: the MODEL's, bit for bit
+        assert same_bits(r[i + 1], u[i]) and same_bits(b[i + 1], u[i])
 
 
 def test_a_trie_of_four_choices(eng, model, start):
