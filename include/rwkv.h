@@ -433,6 +433,34 @@ public:
         }
         rwkv_detail::check(rwkv_state_permute(ctx_, p.data(), p.size()));
     }
+    // speculative greedy decoding (rwkv_mi355x.h "speculative greedy decoding").  specVerify feeds [token, draft ...] to slot 0 in ONE pass of the
+    // chunk path and keeps the longest prefix of the draft that the greedy picks confirm: slot 0 is left behind token, draft[0 .. accepted), and
+    // `next` is emitted, not fed.  decodeSpeculative is the loop around it with a draft MODEL (loaded with maxGPT >= k + 2, its slot 0 holding the
+    // same prefix): n ids that do not depend on the draft model, both models left behind first, ids[0 .. n - 1).  The verifier is the chunk path:
+    // the ids equal decodeGreedy's wherever the top two logits lie further apart than the two paths differ.  In the host-authoritative mode slot 0
+    // is pushed before and pulled after, of both models.
+    struct SpecStep { unsigned long long accepted, next; };
+    struct SpecResult { std::vector<unsigned long long> tokens; unsigned long long rounds, drafted, accepted; };
+    SpecStep specVerify(unsigned long long token, const std::vector<unsigned long long> &draft)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        const std::vector<uint64_t> d(draft.begin(), draft.end());
+        uint64_t a = 0, nx = 0;
+        push_slot0();
+        rwkv_detail::check(rwkv_spec_verify(ctx_, token, d.empty() ? nullptr : d.data(), d.size(), &a, &nx));
+        pull_slot0();
+        return SpecStep{a, nx};
+    }
+    SpecResult decodeSpeculative(RWKV &draft_model, unsigned long long first, unsigned long long n, unsigned k = 4)
+    {
+        if (!ready || !draft_model.ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> ids(n);
+        rwkv_spec_stats st{0, 0, 0};
+        push_slot0(); draft_model.push_slot0();
+        rwkv_detail::check(rwkv_decode_speculative(ctx_, draft_model.ctx_, first, n, k, ids.data(), &st));
+        pull_slot0(); draft_model.pull_slot0();
+        return SpecResult{std::vector<unsigned long long>(ids.begin(), ids.end()), st.rounds, st.drafted, st.accepted};
+    }
     // constrained decoding on the device (rwkv_mi355x.h "constrained decoding"): a token-level automaton in CSR form -- compiled from a regex,
     // a grammar or a choice list by a library of the caller's; include/rwkv_sampler.h constraint_trie builds the choice-list case -- and a sparse
     // logit bias per stream decide what may be generated at all.  setConstraint validates, uploads and puts every slot's automaton state to 0.
@@ -592,6 +620,9 @@ private:
         s.argmax.assign(am.begin(), am.end());
         return s;
     }
+    // slot 0 of the host-authoritative state to the device and back (nothing in the resident mode)
+    void push_slot0() { if (!residentState) rwkv_detail::check(rwkv_set_state(ctx_, state->statexy, state->stateaa, state->statebb, state->statepp, state->statedd, 1)); }
+    void pull_slot0() { if (!residentState) rwkv_detail::check(rwkv_get_output(ctx_, nullptr, state->statexy, state->stateaa, state->statebb, state->statepp, state->statedd, 1)); }
     void ensure_ctx()
     {
         if (!ctx_) rwkv_detail::check(rwkv_create(&ctx_, device_));

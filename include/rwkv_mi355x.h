@@ -506,6 +506,54 @@ int rwkv_decode_batch_constrained(rwkv_ctx *ctx, const uint64_t *first_tokens, u
                                   const rwkv_logprob_out *lp /* may be NULL */, uint64_t *out_tokens, uint32_t *out_len, uint32_t *out_reason,
                                   uint64_t *steps_run);
 
+/* ---- speculative greedy decoding: a draft verified in one pass of the chunk path (no reference counterpart: the reference decodes token by token) ----
+ * One stream, greedy.  rwkv_spec_verify feeds the rows [token, draft[0], .., draft[n_draft - 1]] to slot 0 in ONE GPT-mode pass of the chunk path
+ * (n_draft + 1 <= 32 rows, one half: every weight byte is read once for all of them), picks every row as rwkv_decode_greedy picks -- logit 0 is
+ * banned, ties go to the lowest id, no winner gives 0 -- and keeps the longest prefix of the draft that the picks confirm:
+ *     a = the number of leading i with draft[i] == pick[i]                (row i's pick is the id that follows token, draft[0 .. i - 1])
+ * On return slot 0 holds the state after rows 0 .. a, i.e. after the a + 1 ids token, draft[0 .. a - 1] were fed; *n_accepted = a; *next_token =
+ * pick[a], which has been emitted but not fed, as with rwkv_decode_greedy: feed it as the next call's `token`.  Logits rows 0 .. n_draft are what
+ * rwkv_forward of the same rows leaves.  The pass commits nothing itself: it leaves every row's state in a checkpoint buffer
+ * (4 L (n_draft + 1) n_embed f64, the context's, allocated at the first call for the largest n_draft seen: 134 MB at 7B for 31), a one-wave kernel
+ * finds a, and a copy kernel writes xy, aa, bb, dd of slot 0 from checkpoint row a (pp is not touched: the chunk path does not use it).  There is
+ * no host synchronisation between the pass and the commit; the call waits once, for 16 bytes.  n_draft == 0 is a plain one-token step on the
+ * chunk path (draft may then be NULL).  Slots >= 1, the penalty counts and the constraint states are not touched.
+ * THE VERIFIER IS THE CHUNK PATH, not the decode kernels rwkv_decode_greedy runs.  The two paths compute the same logits to within the project's
+ * parity bound (held to 3e-5 of the row's largest |logit|; about 3e-6 measured), so the ids equal rwkv_decode_greedy's wherever the top two logits
+ * of a row lie further apart than the two paths differ; in an exact near-tie the ids may differ, and both results are within the parity contract.
+ * What is exact: the result does not depend on the draft -- the state, the logits rows 0 .. a and the ids are bit for bit those of
+ * rwkv_forward(rows 0 .. a) for a >= 1, and of rwkv_spec_verify(n_draft = 0) for a = 0.
+ * Status: RWKV_E_ARG for a NULL output pointer (or NULL draft with n_draft > 0), n_draft > RWKV_SPEC_MAX_DRAFT or n_draft + 1 > max_ctx, any id >=
+ * 50277; RWKV_E_STATE when not loaded, on a pipeline-stage context, or without the chunk path (the rule of rwkv_decode_batch_greedy with n_streams
+ * >= 2).  Every check runs before any launch: a rejected call leaves the state and the logits as they were.
+ *
+ * rwkv_decode_speculative is the loop around it with a draft MODEL: draft_ctx is a second whole-model context on the same device, usually a smaller
+ * model.  On entry both contexts hold the same prefix in slot 0; on return both have consumed first_token, out_tokens[0 .. n_tokens - 2], so calls
+ * chain: feed out_tokens[n_tokens - 1] as the next first_token.  Per round, with k' = min(k, remaining - 1):
+ *     1. the draft model runs k' + 1 greedy steps on its slot 0 with its decode kernels and copies slot 0 into slot i + 1 behind step i
+ *        (so draft_ctx needs max_ctx >= k + 2; its slots 1 .. k + 1 are scratch of the call);
+ *     2. the target verifies the k' drafts (rwkv_spec_verify without its wait in front of the download);
+ *     3. the draft's slot 0 is restored from its slot a + 1;
+ *     4. a + 1 ids are emitted: draft[0 .. a - 1], next.
+ * A call never emits or consumes more than n_tokens.  At most two host synchronisations per round, each with a download of a few bytes (the drafts;
+ * {a, next}); no logits leave the device.  At the end the logits row the last id was picked from is copied to row 0.  out_tokens does not depend on
+ * the draft model at all: it is the continuation that repeated rwkv_spec_verify(n_draft = 0) gives, whatever the draft guesses -- the draft only
+ * decides how many rounds that takes.  The comparison with rwkv_decode_greedy is the one above: THE VERIFIER IS THE CHUNK PATH; ids equal wherever
+ * the top two logits lie further apart than the two paths differ (held to 3e-5, about 3e-6 measured), and may differ in an exact near-tie, both
+ * within the parity contract.  stats (may be NULL): rounds, ids drafted (sum of k'), ids accepted (sum of a).
+ * Status: as rwkv_spec_verify for ctx; RWKV_E_ARG also for k == 0, k > RWKV_SPEC_MAX_DRAFT, draft_ctx == ctx or NULL, a draft context on another
+ * device or with max_ctx < k + 2, ctx with max_ctx < k + 1, n_tokens == 0 or above RWKV_MAX_DECODE_STEPS; RWKV_E_STATE for a draft context that is
+ * not loaded or is a pipeline stage.
+ * Out of scope: sampled acceptance (rejection sampling needs the draft's probabilities), draft trees, more than one stream, pipeline contexts,
+ * drafts longer than one half. */
+#define RWKV_SPEC_MAX_DRAFT 31u
+int rwkv_spec_verify(rwkv_ctx *ctx, uint64_t token, const uint64_t *draft, uint64_t n_draft, uint64_t *n_accepted, uint64_t *next_token);
+typedef struct rwkv_spec_stats {
+    uint64_t rounds, drafted, accepted;
+} rwkv_spec_stats;
+int rwkv_decode_speculative(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_token, uint64_t n_tokens, uint32_t k, uint64_t *out_tokens,
+                            rwkv_spec_stats *stats /* may be NULL */);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

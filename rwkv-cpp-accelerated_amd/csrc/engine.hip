@@ -14,6 +14,7 @@
 #include "stop.hip.h"
 #include "beam.hip.h"
 #include "constrain.hip.h"
+#include "spec.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -240,6 +241,8 @@ enum GrownBuf {
     CN_ROWS,                          // f32 [max_ctx][V]: the constrained rows, packed like the logits buffer; allocated ONCE by the first call that needs it
     CN_Q,                             // u32 [max_ctx]: the slots' automaton states (cn_q is the host copy); allocated ONCE, zeroed
     CN_CALL,                          // u32, one call's upload: bias_ptr [n + 1] | bias tok [nb] | bias val f32 [nb]; behind it done [n]
+    SPEC_CKPT,                        // rwkv_spec_verify (spec.hip.h): f64 [4][L][rows][D], the verify pass's checkpoints (xy | aa | bb | dd) for the largest n_draft seen
+    SPEC_REC,                         // u64: {a, next} | picks [SEQ_T]
     N_GROWN
 };
 
@@ -1083,8 +1086,10 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
 // own output in it.  The layers run on `st` with scratch set `S` (the software pipeline of rwkv_forward: a stream and a set per stage).
 // dtok: the pass's n token ids on the device, read where the pass holds the embedding -- token_slot(c, buf) behind upload_chunk_tokens, or wherever
 // they already are (the batched decode's picks of the previous step)
+// ckpt: the verify pass of rwkv_spec_verify (GPT mode, one half, whole model) -- [4][L][n][D], see spec.hip.h: every row's state is left there and
+// NOTHING is committed to slot 0
 struct SeqPass {
-    uint64_t la, lb; hipStream_t st; const SeqScratch *S; int buf, n; uint64_t row0; bool par; const unsigned long long *dtok;
+    uint64_t la, lb; hipStream_t st; const SeqScratch *S; int buf, n; uint64_t row0; bool par; const unsigned long long *dtok; double *ckpt = nullptr;
     bool embeds(const rwkv_ctx *c) const { return c->l0 == 0 && la == c->l0; }
     bool heads(const rwkv_ctx *c) const { return c->l1 == c->L && lb == c->l1; }
 };
@@ -1102,6 +1107,10 @@ int upload_chunk_tokens(rwkv_ctx *c, const uint64_t *tokens, int n, int buf, hip
     c->sq_n++;
     return 0;
 }
+// the CKPT instances of the verify pass, named where rwkv_spec_verify stands (hipcc emits a template instance where the host code first names it:
+// these stay behind every kernel the parent of this feature had, beam.hip.h k_beam_select)
+struct SeqCkptFns { void (*site3)(SeqSiteArgs) = nullptr; void (*site2)(SeqSiteArgs) = nullptr; void (*wkv)(SeqWkvArgs) = nullptr; };
+SeqCkptFns seq_ckpt_fns();
 int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 {
     if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
@@ -1121,6 +1130,10 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     // at these element offsets behind half 0's
     const bool two = n > SEQ_T;
     const SeqHalf h((size_t)D);
+    double *const ck = pass.ckpt;
+    if (ck && (par || two)) return fail(RWKV_E_ARG, "a checkpointing pass is one half in GPT mode");
+    const SeqCkptFns ckf = ck ? seq_ckpt_fns() : SeqCkptFns{};
+    const size_t ck_arr = (size_t)L * n * D;      // one of the four checkpoint arrays; layer l's rows start l * n * D into it
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
     // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
     const SeqPart *const parts[4] = {S.qpart, S.qparta, S.qpart, S.qparth};
@@ -1135,7 +1148,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         for (int v = 0; v < 3; v++) g.img[v] = reinterpret_cast<const u32x4 *>(kind == 3 ? S.imgh : S.img[v]);
         g.part = parts[kind]; g.pk = pks[kind]; g.out = nullptr; g.T = n;
         g.tl = (c->tl_on && c->tl_cls == 10 + kind && tl_layer) ? c->tl : nullptr;
-        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par) ? D : 0;
+        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par && !ck) ? D : 0;
         if (p.fn_b) p.fn_b<<<dim3(p.grid), dim3(SEQ_NT), seq_lds_image(1, 2, 1, p.nkb_max).bytes, st>>>(b);
         else p.fn_p<<<dim3(p.grid), dim3(SEQ_NT), p.smem, st>>>(g);
     };
@@ -1148,16 +1161,17 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         else if (mode == 1) k_seq_resid<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
         else k_seq_resid<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
     };
-    auto site = [&](int nv, const double *lnw, const double *lnb, const double *const *mix, const float *const *r, const float *const *o, double *state) {
+    auto site = [&](int nv, const double *lnw, const double *lnb, const double *const *mix, const float *const *r, const float *const *o, double *state, double *ckpt) {
         SeqSiteArgs s{};
         s.x = x; s.stat = S.stat; s.lnw = lnw; s.lnb = lnb;
         for (int q = 0; q < nv; q++) { s.mix[q] = mix ? mix[q] : nullptr; s.r[q] = r[q]; s.o[q] = o[q]; }
-        s.state = state; s.state_new = (state && !par) ? S.state : nullptr;
+        s.state = state; s.state_new = (state && !par && !ckpt) ? S.state : nullptr; s.ckpt = ckpt;
         s.par = par && state; s.state_par = state; s.slot_stride = LD; s.slot0 = (int)row0;
         for (int q = 0; q < 3; q++) s.img[q] = S.img[q];
         s.part = S.qpart; s.D = D; s.T = n;
         s.img_h = h.img; s.part_h = h.part3;
-        if (nv == 3) k_seq_site<3><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
+        if (ckpt) (nv == 3 ? ckf.site3 : ckf.site2)<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
+        else if (nv == 3) k_seq_site<3><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else if (nv == 2) k_seq_site<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else k_seq_site<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
     };
@@ -1170,10 +1184,13 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         {   // time mix
             const double *mix[3] = {c->mixk + lo, c->mixv + lo, c->mixr + lo};
             const float *r[3] = {c->kr + lo, c->vr + lo, c->rr + lo}, *o[3] = {c->o1 + lo, c->o2 + lo, c->o3 + lo};
-            site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo);
+            site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo, ck ? ck + lo * n : nullptr);
             gemm(0, c->wc[0].b_at(wl, D), c->wc[0].r8_at(wl, D), c->state[0] + lo);
             SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, par ? 1 : 0, LD, (int)row0, h.pk3, h.part3};
-            if (two) k_seq_wkv<SEQ_TM><<<dim3(n_wkv), dim3(SEQ_TM * WKV_CH), 0, st>>>(wa);
+            if (ck) {
+                wa.ckpt_aa = ck + ck_arr + lo * n; wa.ckpt_bb = ck + 2 * ck_arr + lo * n;
+                ckf.wkv<<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
+            } else if (two) k_seq_wkv<SEQ_TM><<<dim3(n_wkv), dim3(SEQ_TM * WKV_CH), 0, st>>>(wa);
             else k_seq_wkv<SEQ_T><<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
             SeqStageArgs sa{S.y, nullptr, nullptr, c->attr + lo, c->atto + lo, S.img[0], S.qparta, D, n, 0, 0, h.img, h.part1};
             k_seq_stage<0><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sa);
@@ -1186,7 +1203,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         {   // channel mix
             const double *mix[3] = {c->fmixk + lo, c->fmixr + lo, nullptr};
             const float *r[3] = {c->fkr + lo, c->frr + lo, nullptr}, *o[3] = {c->fko + lo, c->fro + lo, nullptr};
-            site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo);
+            site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo, ck ? ck + 3 * ck_arr + lo * n : nullptr);
             gemm(2, c->wc[2].b_at(wl, D), c->wc[2].r8_at(wl, D), c->state[4] + lo);
             SeqStageArgs sh{nullptr, S.pk5, S.qpart, c->fvr + 4 * lo, c->fvo + 4 * lo, S.imgh, S.qparth, 4 * D, n, h.pk5, h.part3, h.imgh, h.part1};
             k_seq_stage<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sh);
@@ -1196,7 +1213,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     }
     if (pass.heads(c)) {   // ln_out and the head
         const float *r[3] = {c->headr, nullptr, nullptr}, *o[3] = {c->heado, nullptr, nullptr};
-        site(1, c->ln + (4 * L + 2) * D, c->ln + (4 * L + 3) * D, nullptr, r, o, nullptr);
+        site(1, c->ln + (4 * L + 2) * D, c->ln + (4 * L + 3) * D, nullptr, r, o, nullptr, nullptr);
         SeqGemmArgs g{};
         g.bimg = reinterpret_cast<const u32x4 *>(c->wc[4].b); g.rs8 = c->wc[4].r8; g.N = (int)V; g.K = D; g.Q = 1;
         for (int hf = 0; hf < (two ? 2 : 1); hf++) {      // the head once per half (its weights are 3 % of a pass's bytes; 240 accumulator registers would not fit one wave)
@@ -2803,6 +2820,118 @@ int rwkv_score(rwkv_ctx *c, const uint64_t *tokens, const uint64_t *targets, uin
         }
         return 0;
     }(), logprob, entropy, argmax);
+}
+
+namespace {
+// ---- speculative greedy decoding (spec.hip.h): rwkv_spec_verify, rwkv_decode_speculative ----
+static_assert(SPEC_MAX_DRAFT == RWKV_SPEC_MAX_DRAFT, "spec.hip.h holds the header's limit");
+SeqCkptFns seq_ckpt_fns() { return SeqCkptFns{k_seq_site<3, true>, k_seq_site<2, true>, k_seq_wkv<SEQ_T, true>}; }
+
+// the buffers a verify of n rows needs: checkpoints, record and picks, the row argmax's partials
+int spec_buffers(rwkv_ctx *c, uint64_t n)
+{
+    if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * n * c->D)) return rc;
+    if (const int rc = grow_buffer(c, SPEC_REC, sizeof(unsigned long long) * (2 + SEQ_T))) return rc;
+    return grow_pick_buffers(c, RWKV_PICK_GREEDY, n);
+}
+
+// Everything of one verify but the wait: ids up, the checkpointing pass over rows [token, draft ..] on slot 0, the pick of every row, what stands,
+// the commit of that row, and the record's download into rec[2].  No host synchronisation in between: k_spec_commit reads a where k_spec_accept
+// left it.  The pass is LAUNCHED DIRECTLY, not replayed as a captured graph under a key of its own.  Measured at 7B both ways
+// (profiles/spec/graph_vs_direct.txt), the replay was never the faster one: 0.01 - 0.02 ms slower up to 16 rows, which is what the runs differ by
+// among themselves, and 0.06 ms slower at 32 rows, which is not.  With nothing to gain the simpler form is kept: one pass per call, with the
+// call's wait behind it, leaves the host nothing to fall behind with.
+int enqueue_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft, unsigned long long *rec)
+{
+    const int n = (int)n_draft + 1;
+    if (const int rc = spec_buffers(c, (uint64_t)n)) return rc;
+    uint64_t rows[SEQ_T];
+    rows[0] = token;
+    for (uint64_t i = 0; i < n_draft; i++) rows[i + 1] = draft[i];
+    if (const int rc = upload_chunk_tokens(c, rows, n, 0, c->stream)) return rc;
+    double *ck = c->buf<double>(SPEC_CKPT);
+    unsigned long long *drec = c->buf<unsigned long long>(SPEC_REC), *picks = drec + 2;
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, n, 0, false, token_slot(c, 0), ck};
+    if (const int rc = enqueue_chunk(c, pass)) return rc;
+    if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)n, picks)) return rc;
+    k_spec_accept<64><<<dim3(1), dim3(64), 0, c->stream>>>(SpecAcceptArgs{token_slot(c, 0), picks, drec, (unsigned)n_draft});
+    const SpecCommitArgs ca{drec, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)n};
+    k_spec_commit<SPEC_COMMIT_NT><<<dim3((unsigned)((c->L * c->D + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT)), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(rec, drec, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+// the checks of a verify behind the guard, all of them before anything is launched
+int check_verify(const rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft)
+{
+    if (n_draft > RWKV_SPEC_MAX_DRAFT || n_draft + 1 > c->maxT)
+        return fail(RWKV_E_ARG, "n_draft must be in 0..%llu (one half of a pass, and max context - 1)", (unsigned long long)std::min<uint64_t>(RWKV_SPEC_MAX_DRAFT, c->maxT - 1));
+    if (n_draft && !draft) return fail(RWKV_E_ARG, "NULL argument");
+    if (const int rc = check_ids(&token, 1, "token")) return rc;
+    return check_ids(draft, n_draft, "draft");
+}
+} // namespace
+
+int rwkv_spec_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft, uint64_t *n_accepted, uint64_t *next_token)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, n_accepted && next_token)) return rc;
+    if (const int rc = check_verify(c, token, draft, n_draft)) return rc;
+    unsigned long long rec[2] = {0ull, 0ull};
+    const int rc = finish(c, enqueue_verify(c, token, draft, n_draft, rec));
+    if (!rc) { *n_accepted = rec[0]; *next_token = rec[1]; }
+    return rc;
+}
+
+int rwkv_decode_speculative(rwkv_ctx *c, rwkv_ctx *dc, uint64_t first_token, uint64_t n_tokens, uint32_t k, uint64_t *out_tokens, rwkv_spec_stats *stats)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, dc && out_tokens)) return rc;
+    if (dc == c) return fail(RWKV_E_ARG, "the draft context must be another context than the target");
+    if (const int rc = guard(dc, NEED_WHOLE | LAUNCHES)) return rc;
+    if (dc->device != c->device) return fail(RWKV_E_ARG, "the draft context is on device %d, the target on device %d", dc->device, c->device);
+    if (k == 0 || k > RWKV_SPEC_MAX_DRAFT) return fail(RWKV_E_ARG, "k must be in 1..%u", RWKV_SPEC_MAX_DRAFT);
+    if (dc->maxT < (uint64_t)k + 2) return fail(RWKV_E_ARG, "the draft context needs max context >= k + 2 = %u (a state slot per draft step)", k + 2);
+    if ((uint64_t)k + 1 > c->maxT) return fail(RWKV_E_ARG, "the target context needs max context >= k + 1 = %u", k + 1);
+    if (const int rc = check_steps(n_tokens, "n_tokens")) return rc;
+    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
+    const size_t LD = (size_t)dc->L * dc->D;
+    // the draft's slot `dst` <- its slot `src`, on its stream
+    auto draft_copy = [&](uint64_t dst, uint64_t src) -> int {
+        for (int s = 0; s < 5; s++)
+            HIPCHK(hipMemcpyAsync(dc->state[s] + dst * LD, dc->state[s] + src * LD, LD * sizeof(double), hipMemcpyDeviceToDevice, dc->stream));
+        return 0;
+    };
+    rwkv_spec_stats sts{0, 0, 0};
+    uint64_t done = 0, token = first_token, last_row = 0;
+    unsigned long long draft[SEQ_T], rec[2];
+    // One round: the draft model's kd + 1 greedy steps on its slot 0 with a copy of slot 0 into slot i + 1 behind step i (the last step only
+    // consumes draft[kd - 1]: slot kd + 1 is what the draft holds when all of it stands), the drafts' download; the verify with its 16-byte
+    // download; the draft's slot 0 back from slot a + 1.  Two waits, and the restore runs under the next round's first step.
+    int rc = 0;
+    while (!rc && done < n_tokens) {
+        const uint64_t kd = std::min<uint64_t>(k, n_tokens - done - 1);
+        rc = set_ctl(dc, token, 0, 0);
+        for (uint64_t i = 0; !rc && i <= kd; i++) {
+            rc = run_token(dc, true);
+            if (!rc) rc = draft_copy(i + 1, 0);
+        }
+        if (!rc && kd) rc = [&]() -> int { HIPCHK(hipMemcpyAsync(draft, dc->gen, kd * sizeof(unsigned long long), hipMemcpyDeviceToHost, dc->stream)); return 0; }();
+        if (kd || rc) rc = finish(dc, rc);
+        if (rc) break;
+        rc = finish(c, enqueue_verify(c, token, reinterpret_cast<const uint64_t *>(draft), kd, rec));
+        if (rc) break;
+        const uint64_t a = rec[0];
+        rc = draft_copy(0, a + 1);
+        for (uint64_t i = 0; i < a; i++) out_tokens[done + i] = draft[i];
+        out_tokens[done + a] = rec[1];
+        done += a + 1; token = rec[1]; last_row = a;
+        sts.rounds++; sts.drafted += kd; sts.accepted += a;
+    }
+    // the row the last id was picked from -> row 0, where a one-stream call leaves it
+    if (!rc && last_row) rc = [&]() -> int { HIPCHK(hipMemcpyAsync(c->logits, c->logits + last_row * RWKV_VOCAB, RWKV_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, c->stream)); return 0; }();
+    rc = finish(dc, rc);
+    rc = finish(c, rc);
+    if (!rc && stats) *stats = sts;
+    return rc;
 }
 
 void rwkv_free(rwkv_ctx *c)

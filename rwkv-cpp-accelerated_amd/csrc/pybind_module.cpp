@@ -139,6 +139,20 @@ PYBIND11_MODULE(rwkv, m)
     }, "beam search ON THE DEVICE from the state slot 0 holds (load with maxGPT >= width): (tokens [width][n], len [width], score [width], "
        "token log-probs [width][n]); hypothesis 0 is the best, entries behind a hypothesis's end are 0 (engine extension)",
           py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("width") = 4u, py::arg("stops") = std::vector<int64_t>{});
+    m.def("specVerify", [](std::uintptr_t h, int64_t token, const std::vector<int64_t> &draft) {
+        const RWKV::SpecStep s = M(h)->specVerify((unsigned long long)token, std::vector<unsigned long long>(draft.begin(), draft.end()));
+        return py::make_tuple((int64_t)s.accepted, (int64_t)s.next);
+    }, "feed [token, *draft] to slot 0 in one pass of the chunk path and keep the longest prefix of the draft the greedy picks confirm: "
+       "(n_accepted, next); next is emitted, not fed (engine extension)", py::arg("rwkvp"), py::arg("token"), py::arg("draft") = std::vector<int64_t>{});
+    m.def("decodeSpeculative", [](std::uintptr_t h, std::uintptr_t draft, int64_t first, int64_t n, unsigned k) {
+        if (n < 1) throw std::runtime_error("n must be at least 1");
+        const RWKV::SpecResult r = M(h)->decodeSpeculative(*M(draft), (unsigned long long)first, (unsigned long long)n, k);
+        py::array_t<int64_t> ids((size_t)n);
+        std::copy(r.tokens.begin(), r.tokens.end(), ids.mutable_data());
+        return py::make_tuple(ids, py::make_tuple((int64_t)r.rounds, (int64_t)r.drafted, (int64_t)r.accepted));
+    }, "speculative greedy decoding: the model of handle `draft` (loaded with maxGPT >= k + 2, same prefix in slot 0) guesses k ids per round, this "
+       "one verifies them in one pass: (ids [n], (rounds, drafted, accepted)); the ids do not depend on the draft model (engine extension)",
+          py::arg("rwkvp"), py::arg("draft"), py::arg("first"), py::arg("n"), py::arg("k") = 4u);
     // ---- constrained decoding: the engine calls, and the host twins of include/rwkv_sampler.h for the suite ----
     using u32arr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
     using f32arr = py::array_t<float, py::array::c_style | py::array::forcecast>;

@@ -294,6 +294,7 @@ struct SeqSiteArgs {
     SeqPart *part;               // [NV][T][SEQ_O]
     int D, T;
     size_t img_h, part_h;        // second half of a pass: offsets of its images (in 32-bit words) and records
+    double *ckpt;                // CKPT instances (the verify pass of speculative decoding, spec.hip.h): [T][D] the LayerNorm output of EVERY row
 };
 // mean, rstd of rows t and tp from their octant partials (every thread computes them: 16 tiny loads)
 __device__ __forceinline__ void seq_row_stats2(const SeqStat *stat, int t, int tp, int D, double &mean, double &rstd, double &meanp, double &rstdp)
@@ -311,11 +312,14 @@ __device__ __forceinline__ void seq_row_stats2(const SeqStat *stat, int t, int t
 }
 // (row, octant) workgroups, one quad (4 channels) per thread: LayerNorm + shift mix of the octant, its exact max|.| per
 // vector (one workgroup reduction), quantisation into the A image.  D / 32 <= SEQ_ENT quads per octant.
-template <int NV>
+// CKPT (GPT mode only): the pass commits nothing -- every row's LayerNorm output goes to a.ckpt, what a state holds once that row is the last one
+// fed, and neither a.state_new nor a slot is written (spec.hip.h k_spec_commit copies the row that stands).
+template <int NV, bool CKPT = false>
 __global__ __launch_bounds__(SEQ_ENT) void k_seq_site(SeqSiteArgs a)
 {
     __shared__ double red[SEQ_ENW * 4];
     RWKV_ARGS_NOW(a.x, a.stat, a.lnw, a.lnb, a.state, a.state_par, a.state_new, a.part);      // (see k_seq_resid)
+    if (CKPT) RWKV_ARGS_NOW(a.ckpt);
     RWKV_ARGS_NOW(a.mix[0], a.r[0], a.o[0], a.img[0]);
     if (NV > 1) RWKV_ARGS_NOW(a.mix[NV - 1], a.r[NV - 1], a.o[NV - 1], a.img[NV - 1], a.mix[NV > 2 ? 1 : 0], a.r[NV > 2 ? 1 : 0], a.o[NV > 2 ? 1 : 0], a.img[NV > 2 ? 1 : 0]);
     const int D = a.D, t = blockIdx.x / SEQ_O, o = blockIdx.x % SEQ_O;      // t: row of the pass (0 .. 63)
@@ -348,7 +352,8 @@ __global__ __launch_bounds__(SEQ_ENT) void k_seq_site(SeqSiteArgs a)
             xx[e] = lw[e] * ((xt[e] - mean) * rstd) + lb[e];
             xprev[e] = lnprev ? lw[e] * ((xp[e] - meanp) * rstdp) + lb[e] : xp[e];
             const int j = qd * 4 + e;
-            if (a.par) a.state_par[(size_t)(a.slot0 + t) * a.slot_stride + j] = xx[e];   // own slot: read above by this thread only
+            if (CKPT) a.ckpt[(size_t)t * D + j] = xx[e];
+            else if (a.par) a.state_par[(size_t)(a.slot0 + t) * a.slot_stride + j] = xx[e];   // own slot: read above by this thread only
             else if (a.state_new && t == a.T - 1) a.state_new[j] = xx[e];                // mixatt / mixffn state write (:344,:385)
         }
 #pragma unroll
@@ -454,16 +459,22 @@ struct SeqWkvArgs {
     size_t slot_stride;
     int slot0;
     size_t pk_h, part_h;         // second half of a pass: offsets of its pk / records
+    double *ckpt_aa, *ckpt_bb;   // CKPT instance: [T][D] each, the state AFTER every row
 };
 constexpr int WKV_CH = 16;       // channels per workgroup (TCAP x 16 threads: 16 channels x the rows of the pass)
 // rwkv.cu:242-255 with the GPT-mode state slot 0.  The exponentials do not depend on the state, so
 // one thread per (row, channel) evaluates them; then one thread per channel runs the (linear) state
 // recurrence along the chunk and the outputs are finished in parallel.  TCAP = 32 (one half) or 64 rows.
-template <int TCAP>
+// CKPT (GPT mode only): saa / sbb are read and NOT written; the state after every row goes to ckpt_aa / ckpt_bb.  The walk already leaves the
+// state before row t in LDS, which is the state after row t - 1: one more LDS row takes the walk's final value, and the (row, channel) threads
+// store row t + 1 of that table as the state after their row.
+template <int TCAP, bool CKPT = false>
 __global__ __launch_bounds__(TCAP * WKV_CH) void k_seq_wkv(SeqWkvArgs a)
 {
-    __shared__ double e1s[TCAP][WKV_CH], eks[TCAP][WKV_CH], vs[TCAP][WKV_CH], sgs[TCAP][WKV_CH], aas[TCAP][WKV_CH];
+    constexpr int TS = TCAP + (CKPT ? 1 : 0);      // rows of the two state tables
+    __shared__ double e1s[TCAP][WKV_CH], eks[TS][WKV_CH], vs[TCAP][WKV_CH], sgs[TCAP][WKV_CH], aas[TS][WKV_CH];
     RWKV_ARGS_NOW(a.pk, a.qpart, a.uw, a.ew, a.saa, a.sbb, a.y);      // (see k_seq_resid)
+    if (CKPT) RWKV_ARGS_NOW(a.ckpt_aa, a.ckpt_bb);
     const int ch = threadIdx.x & (WKV_CH - 1), t = threadIdx.x / WKV_CH;     // t: row of the pass
     const int i = blockIdx.x * WKV_CH + ch;
     const bool live = i < a.D && t < a.T;
@@ -497,19 +508,27 @@ __global__ __launch_bounds__(TCAP * WKV_CH) void k_seq_wkv(SeqWkvArgs a)
     if (threadIdx.x < WKV_CH && i < a.D) {
         double aa = a.saa[i], bb = a.sbb[i];
         const double ew = a.ew[i];
+        // The steps' roundings are pinned: one fma and one product for aa, one sum and one product for bb.  Left to the compiler's contraction,
+        // the loop -- unrolled by eight -- fused a step's product with the NEXT step's sum, bb' + e^k' = fma(bb + e^k, e^w, e^k'), inside the
+        // unrolled body and not in its remainder loop: bb after row t then depended, in the last bit, on how many rows the pass had, and a
+        // prompt fed as 5 + 5 rows differed from the same prompt fed as 10.  The header's promise (and rwkv_spec_verify's rollback) needs the
+        // state after a row to be the same whatever follows the row in its pass (speculative decoding).
         for (int tt = 0; tt < a.T; tt++) {
+#pragma clang fp contract(off)
             const double ek = eks[tt][ch], vv = vs[tt][ch];
             eks[tt][ch] = aa;                 // state before row tt (the slot of e^k is free once read)
             aas[tt][ch] = bb;
-            aa = (aa + ek * vv) * ew;
+            aa = __builtin_fma(ek, vv, aa) * ew;
             bb = (bb + ek) * ew;
         }
-        a.saa[i] = aa; a.sbb[i] = bb;
+        if (CKPT) { eks[a.T][ch] = aa; aas[a.T][ch] = bb; }      // (a.T <= TCAP: the tables' extra row at most)
+        else { a.saa[i] = aa; a.sbb[i] = bb; }
     }
     __syncthreads();
     if (live) {
         const double e1 = e1s[t][ch];
         a.y[(size_t)t * a.D + i] = (float)(sgs[t][ch] * ((eks[t][ch] + e1 * vs[t][ch]) / (aas[t][ch] + e1)));
+        if (CKPT) { a.ckpt_aa[(size_t)t * a.D + i] = eks[t + 1][ch]; a.ckpt_bb[(size_t)t * a.D + i] = aas[t + 1][ch]; }
     }
 }
 

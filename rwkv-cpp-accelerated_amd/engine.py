@@ -41,9 +41,11 @@ ABI_SYMBOLS = [
     "rwkv_decode_beam", "rwkv_state_permute", "rwkv_debug_beam_step",
     "rwkv_constraint_set", "rwkv_constraint_clear", "rwkv_constraint_state_set", "rwkv_constraint_state_get", "rwkv_pick_constrained",
     "rwkv_debug_constrained_row", "rwkv_decode_batch_constrained",
+    "rwkv_spec_verify", "rwkv_decode_speculative",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
+SPEC_MAX_DRAFT = 31               # RWKV_SPEC_MAX_DRAFT
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 TOPN_MAX = 32                     # RWKV_MAX_TOPN
 LOGPROB_ENTRIES_MAX = 1 << 22     # RWKV_MAX_LOGPROB_ENTRIES: n_streams * n_steps * (1 + top_n) of one call
@@ -105,6 +107,25 @@ def beam_params(width, stops=()):
     st = [int(t) for t in stops]
     ids = (C.c_uint64 * max(1, len(st)))(*st)
     return BeamParams(int(width), len(st), ids if st else None, 0), ids
+
+
+class SpecStats(C.Structure):
+    """rwkv_spec_stats of include/rwkv_mi355x.h (24 bytes)"""
+    _fields_ = [("rounds", C.c_uint64), ("drafted", C.c_uint64), ("accepted", C.c_uint64)]
+
+
+def ngram_draft(history, k: int, n: int = 3):
+    """the host-side lookup drafter (no model): the up to k ids that followed the MOST RECENT earlier occurrence of the last n ids of `history`;
+    [] where the history is shorter than n + 1 ids or its tail has not occurred before.  An occurrence may overlap the tail itself."""
+    h = [int(t) for t in history]
+    n, k = int(n), int(k)
+    if n < 1 or k < 1 or len(h) <= n:
+        return []
+    tail = h[-n:]
+    for s in range(len(h) - n - 1, -1, -1):           # the occurrence starts at s and ends in front of the last id: something follows it
+        if h[s:s + n] == tail:
+            return h[s + n:s + n + k]
+    return []
 
 
 class Automaton(C.Structure):
@@ -254,6 +275,8 @@ def lib():
     L.rwkv_decode_batch_constrained.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(ConstrainParams),
                                                 C.POINTER(StopParams), C.POINTER(LogprobOut), C.POINTER(u64), u32p, u32p, C.POINTER(u64)]
     L.rwkv_decode_batch_constrained.restype = i32
+    L.rwkv_spec_verify.argtypes = [vp, u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_spec_verify.restype = i32
+    L.rwkv_decode_speculative.argtypes = [vp, vp, u64, u64, C.c_uint32, C.POINTER(u64), C.POINTER(SpecStats)]; L.rwkv_decode_speculative.restype = i32
     _lib = L
     return L
 
@@ -775,6 +798,60 @@ class RWKV:
                                         eo.ctypes.data_as(C.POINTER(C.c_uint8))))
         del alive
         return par[:W].astype(np.int64), tok[:W].astype(np.int64), sc[:W].copy(), lp[:W].copy(), eo[:W].astype(np.int64)
+
+    # -- speculative greedy decoding (include/rwkv_mi355x.h rwkv_spec_verify) ---------------------------------------------------
+    def spec_verify(self, token: int, draft=()):
+        """feed [token, *draft] to slot 0 in ONE pass of the chunk path and keep the longest prefix of the draft that the greedy picks confirm:
+        (n_accepted, next).  Slot 0 is left after token, draft[:n_accepted]; `next` is emitted and not fed.  len(draft) <= 31; an empty draft is a
+        plain one-token step on the chunk path."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        d = [int(t) for t in draft]
+        arr = (C.c_uint64 * max(1, len(d)))(*d)
+        a, nx = C.c_uint64(0), C.c_uint64(0)
+        if not self.resident:
+            self.push_state(1)
+        _chk(lib().rwkv_spec_verify(self._h, int(token), arr if d else None, len(d), C.byref(a), C.byref(nx)))
+        if not self.resident:
+            self.pull_state(1)
+        return int(a.value), int(nx.value)
+
+    def decode_speculative(self, draft_model: "RWKV", first_token: int, n_tokens: int, k: int = 4):
+        """greedy continuation of n_tokens ids with `draft_model` (a second loaded model on the same device whose slot 0 holds the same prefix,
+        loaded with maxGPT >= k + 2) guessing k ids per round and this model verifying them in one pass: (ids, stats) with stats = dict(rounds,
+        drafted, accepted).  The ids do not depend on the draft model.  Both models are left behind first_token, ids[:-1]."""
+        if not self.ready or not draft_model.ready:
+            raise RuntimeError("RWKV not loaded")
+        n = int(n_tokens)
+        out = (C.c_uint64 * max(1, n))()
+        st = SpecStats()
+        for m in (self, draft_model):
+            if not m.resident:
+                m.push_state(1)
+        _chk(lib().rwkv_decode_speculative(self._h, draft_model._h, int(first_token), n, int(k), out, C.byref(st)))
+        for m in (self, draft_model):
+            if not m.resident:
+                m.pull_state(1)
+        return np.frombuffer(out, dtype=np.uint64)[:n].astype(np.int64), dict(rounds=int(st.rounds), drafted=int(st.drafted), accepted=int(st.accepted))
+
+    def decode_lookup(self, history, n_tokens: int, k: int = 8, n: int = 3):
+        """greedy continuation of n_tokens ids with the host-side lookup drafter (ngram_draft) in place of a draft model: history = the ids so
+        far, of which all but the last have been fed (the last one is fed first).  Returns (ids, stats) like decode_speculative; the ids are
+        those of repeated spec_verify(token, ())."""
+        h = [int(t) for t in history]
+        if not h:
+            raise ValueError("history holds at least the id to feed first")
+        n_tokens = int(n_tokens)
+        out = []
+        stats = dict(rounds=0, drafted=0, accepted=0)
+        while len(out) < n_tokens:
+            kd = min(int(k), SPEC_MAX_DRAFT, self.maxContext - 1, n_tokens - len(out) - 1)
+            d = ngram_draft(h, kd, n) if kd > 0 else []
+            a, nx = self.spec_verify(h[-1], d)
+            new = d[:a] + [nx]
+            out += new; h += new
+            stats["rounds"] += 1; stats["drafted"] += len(d); stats["accepted"] += a
+        return np.asarray(out, dtype=np.int64), stats
 
     def debug_stop_scan(self, ids, first_tokens, stops=(), max_new=None, keep: bool = False):
         """the stop test alone over PLANTED picks ids [n][steps] (rwkv_debug_stop_scan): (len [n], reason [n]); stream s uses slot s's history"""
