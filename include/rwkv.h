@@ -461,6 +461,27 @@ public:
         pull_slot0(); draft_model.pull_slot0();
         return SpecResult{std::vector<unsigned long long>(ids.begin(), ids.end()), st.rounds, st.drafted, st.accepted};
     }
+    // segmented forward (rwkv_mi355x.h "segmented forward"): each segment is a run of consecutive tokens of the sequence on state slot `slot`
+    // (the slots of one call pairwise distinct); every sequence continues from its slot and leaves it after its tokens, all behind one read of the
+    // weights per pass -- decoding streams and pieces of new prompts in one call.  Row j of the logits buffer belongs to token j of the segments'
+    // tokens back to back; the result holds, per segment, the row of its last token (scoreRows / topnRows / sampleNucleus read rows).  In the
+    // host-authoritative mode every slot is pushed before and pulled after.
+    struct Segment { unsigned slot; std::vector<unsigned long long> tokens; };
+    std::vector<unsigned long long> forwardSegments(const std::vector<Segment> &segments)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<rwkv_segment> segs;
+        std::vector<uint64_t> ids;
+        for (const Segment &s : segments) {
+            segs.push_back(rwkv_segment{s.slot, (uint32_t)s.tokens.size()});
+            ids.insert(ids.end(), s.tokens.begin(), s.tokens.end());
+        }
+        std::vector<uint64_t> last(segs.size());
+        if (!residentState) pushState();
+        rwkv_detail::check(rwkv_forward_segments(ctx_, ids.data(), segs.data(), segs.size(), 0, last.data()));
+        if (!residentState) pullState();
+        return std::vector<unsigned long long>(last.begin(), last.end());
+    }
     // constrained decoding on the device (rwkv_mi355x.h "constrained decoding"): a token-level automaton in CSR form -- compiled from a regex,
     // a grammar or a choice list by a library of the caller's; include/rwkv_sampler.h constraint_trie builds the choice-list case -- and a sparse
     // logit bias per stream decide what may be generated at all.  setConstraint validates, uploads and puts every slot's automaton state to 0.

@@ -554,6 +554,48 @@ typedef struct rwkv_spec_stats {
 int rwkv_decode_speculative(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_token, uint64_t n_tokens, uint32_t k, uint64_t *out_tokens,
                             rwkv_spec_stats *stats /* may be NULL */);
 
+/* ---- segmented forward: many sequences of any length behind one read of the weights (no reference counterpart: the reference has the two ends) ----
+ * The rows of a call are SEGMENTS: segment i is n consecutive tokens of the sequence on state slot `slot`, and the segments' tokens stand back to
+ * back in `tokens`.  One segment {0, n} is rwkv_forward's GPT mode, n segments of length 1 are its PARRALEL mode, and a mix is the step of a
+ * continuous-batching server: the decoding streams' last picks and a piece of every waiting prompt, admitted on their own slots, in one call.
+ * Row numbering and logits: T = sum n; row j of the call is token j of the packed array and its logits land in row j of the device logits buffer,
+ * where rwkv_score_rows, rwkv_topn_rows and rwkv_sample_nucleus(row, slot) read them.  last_row[i] (may be NULL) is the row of segment i's last
+ * token, the one a server picks from.
+ * Arguments: 1 <= T <= max_ctx, n_segs >= 1, every n >= 1, every slot < max_ctx, THE SLOTS OF ONE CALL ARE PAIRWISE DISTINCT, every id < 50277,
+ * flags == 0.
+ * State: segment i starts from what slot segs[i].slot holds and leaves that slot after its n tokens (xy, aa, bb, dd; pp is untouched, as
+ * everywhere on the chunk path).  Slots not named, the penalty counts, the stop histories and the constraint states are untouched.
+ * Every call runs the CHUNK PATH, T == 1 included (the one-row pass that rwkv_spec_verify(n_draft = 0) is).  The rows are cut into passes exactly
+ * as rwkv_forward cuts them -- 32 rows for T <= 32 or RWKV_SEQ_ROWS=32, else 64 in two halves -- and more than one pass runs the RWKV_SEQ_STAGES
+ * pipeline.  A segment may straddle a half or a pass boundary: the piece behind a pass boundary continues from the slot, which the piece in front
+ * of it has just written on the same stage's stream.  Synchronous on return, like rwkv_forward; inside the call the row plan is uploaded once and
+ * the ids once per pass through the pinned ring, and there is no host synchronisation between passes.  At the first call the context allocates the
+ * plan (8 max_ctx bytes) and 64 n_embed f64 of staging per pipeline stage in use; rwkv_resident_bytes counts them.
+ * EXACT: the result for a segment does not depend on what else is in the call or where its rows sit -- its slot's state and its logits rows are
+ * bit for bit those of the same segment alone in a call.  A single segment {0, n}, n >= 2, leaves state and logits rows 0 .. n - 1 bit for bit as
+ * rwkv_forward(tokens, n, RWKV_MODE_GPT) does, and {0, 1} as rwkv_spec_verify(token, NULL, 0, ..) does.  Against rwkv_forward(RWKV_MODE_PARRALEL)
+ * for segments of length 1 the results lie within the chunk path's parity bounds; bit equality there is not promised (DESIGN.md has what was
+ * measured): the PARRALEL kernels leave roundings to the compiler that the GPT walk pins.
+ * Status: RWKV_E_ARG for each rule above and for a NULL ctx, tokens or segs; RWKV_E_STATE when not loaded, on a pipeline-stage context, or without
+ * the chunk path (the rule of rwkv_decode_batch_greedy with n_streams >= 2).  Every check runs before anything is launched or allocated: a rejected
+ * call leaves state, logits and buffers as they were.
+ *
+ * rwkv_segment_plan is the ONE validator (rwkv_forward_segments calls it) and needs neither a context nor a device: it checks a segment list
+ * against max_ctx by the rules above (the ids aside) and writes the per-row plan the device reads: row_slot[j], the slot of row j; row_flags[j],
+ * bit 0 set when the row is the first of its piece (its shift input and WKV state come from the slot), bit 1 when it is the last of its piece (its
+ * LayerNorm outputs and WKV state go to the slot).  A piece ends where its segment ends or where the pass ends, so the plan depends on the pass
+ * size: the exported function assumes passes of 64 rows (rwkv_forward_segments plans for the pass size it runs).  row_slot, row_flags and n_rows
+ * may each be NULL (validate only); nothing is written when the list is rejected.
+ * Out of scope: a device-side decode loop with admission, a batched sampler over arbitrary (row, slot) pairs (rwkv_sample_nucleus is one call per
+ * stream), logits for the last rows only, segments on pipeline-stage contexts, the same slot twice in one call, checkpointing (speculative)
+ * segments. */
+typedef struct rwkv_segment { uint32_t slot; uint32_t n; } rwkv_segment;   /* n >= 1 consecutive tokens of the sequence on state slot `slot` */
+int rwkv_forward_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' tokens back to back */,
+                          const rwkv_segment *segs, uint64_t n_segs, uint32_t flags /* must be 0 */,
+                          uint64_t *last_row /* host [n_segs], may be NULL: logits row of each segment's last token */);
+int rwkv_segment_plan(const rwkv_segment *segs, uint64_t n_segs, uint64_t max_ctx,
+                      uint32_t *row_slot /* [T] */, uint8_t *row_flags /* [T], may both be NULL: validate only */, uint64_t *n_rows);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

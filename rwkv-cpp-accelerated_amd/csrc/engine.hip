@@ -15,6 +15,7 @@
 #include "beam.hip.h"
 #include "constrain.hip.h"
 #include "spec.hip.h"
+#include "segments.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -169,6 +170,7 @@ struct SeqScratch {
     SeqPart *qpart = nullptr, *qparta = nullptr, *qparth = nullptr;    // quantisation records: site vectors [3][SEQ_T][SEQ_O], att_out input [SEQ_T][SEQ_O], ffn_v input [SEQ_T][SEQ_O]
     SeqStat *stat = nullptr;            // [SEQ_TM][SEQ_O] LayerNorm partial statistics
     float *pk3 = nullptr, *pk5 = nullptr, *pk1 = nullptr;   // per-slice partial values of the K/V/R, ffn k/r, att_out | ffn_v GEMMs (accumulator images, seq.hip.h pk_index)
+    double *seg = nullptr;              // segmented passes only (allocated at the first one that uses the set): [SEQ_TM][D] LayerNorm outputs of the pieces' last rows
 };
 // Elements of ONE half of a scratch set at width D: the allocation holds two of each, and a pass of two halves finds half 1 at these offsets
 struct SeqHalf {
@@ -243,6 +245,7 @@ enum GrownBuf {
     CN_CALL,                          // u32, one call's upload: bias_ptr [n + 1] | bias tok [nb] | bias val f32 [nb]; behind it done [n]
     SPEC_CKPT,                        // rwkv_spec_verify (spec.hip.h): f64 [4][L][rows][D], the verify pass's checkpoints (xy | aa | bb | dd) for the largest n_draft seen
     SPEC_REC,                         // u64: {a, next} | picks [SEQ_T]
+    SEG_PLAN,                         // rwkv_forward_segments (segments.hip.h): SegRow [max_ctx], the call's row plan; allocated ONCE at the first segmented call
     N_GROWN
 };
 
@@ -293,6 +296,7 @@ struct rwkv_ctx {
     unsigned *blk_idx = nullptr;
     Ctl *ctl = nullptr;
     Ctl *h_ctl = nullptr;    // pinned staging, maxT entries
+    SegRow *h_seg_plan = nullptr;   // pinned [maxT]: what rwkv_forward_segments uploads into SEG_PLAN (allocated with it)
     unsigned long long *gen = nullptr;
     unsigned long long *pick = nullptr;      // device: id drawn by the sampler
     double *ts_part = nullptr;               // sampler scratch (sampler.hip.h)
@@ -1088,8 +1092,11 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
 // they already are (the batched decode's picks of the previous step)
 // ckpt: the verify pass of rwkv_spec_verify (GPT mode, one half, whole model) -- [4][L][n][D], see spec.hip.h: every row's state is left there and
 // NOTHING is committed to slot 0
+// plan: a SEGMENTED pass (segments.hip.h; par == false, no ckpt) -- the pass's slice of the row plan on the device, [n]{slot, flags}: the rows are
+// pieces of sequences on slots of their own.  Null: one of the two layouts above
 struct SeqPass {
     uint64_t la, lb; hipStream_t st; const SeqScratch *S; int buf, n; uint64_t row0; bool par; const unsigned long long *dtok; double *ckpt = nullptr;
+    const SegRow *plan = nullptr;
     bool embeds(const rwkv_ctx *c) const { return c->l0 == 0 && la == c->l0; }
     bool heads(const rwkv_ctx *c) const { return c->l1 == c->L && lb == c->l1; }
 };
@@ -1111,6 +1118,12 @@ int upload_chunk_tokens(rwkv_ctx *c, const uint64_t *tokens, int n, int buf, hip
 // these stay behind every kernel the parent of this feature had, beam.hip.h k_beam_select)
 struct SeqCkptFns { void (*site3)(SeqSiteArgs) = nullptr; void (*site2)(SeqSiteArgs) = nullptr; void (*wkv)(SeqWkvArgs) = nullptr; };
 SeqCkptFns seq_ckpt_fns();
+// the instances of a segmented pass, named where rwkv_forward_segments stands for the same reason
+struct SegFns {
+    void (*site3)(SegSiteArgs) = nullptr; void (*site2)(SegSiteArgs) = nullptr; void (*wkv32)(SegWkvArgs) = nullptr; void (*wkv64)(SegWkvArgs) = nullptr;
+    void (*stage)(SegStageArgs) = nullptr;
+};
+SegFns seg_fns();
 int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 {
     if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
@@ -1133,6 +1146,9 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     double *const ck = pass.ckpt;
     if (ck && (par || two)) return fail(RWKV_E_ARG, "a checkpointing pass is one half in GPT mode");
     const SeqCkptFns ckf = ck ? seq_ckpt_fns() : SeqCkptFns{};
+    const SegRow *const plan = pass.plan;
+    if (plan && (par || ck || !S.seg)) return fail(RWKV_E_ARG, "a segmented pass is neither PARRALEL nor checkpointing, and its scratch set holds the staging rows");
+    const SegFns sgf = plan ? seg_fns() : SegFns{};
     const size_t ck_arr = (size_t)L * n * D;      // one of the four checkpoint arrays; layer l's rows start l * n * D into it
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
     // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
@@ -1148,7 +1164,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         for (int v = 0; v < 3; v++) g.img[v] = reinterpret_cast<const u32x4 *>(kind == 3 ? S.imgh : S.img[v]);
         g.part = parts[kind]; g.pk = pks[kind]; g.out = nullptr; g.T = n;
         g.tl = (c->tl_on && c->tl_cls == 10 + kind && tl_layer) ? c->tl : nullptr;
-        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par && !ck) ? D : 0;
+        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par && !ck && !plan) ? D : 0;
         if (p.fn_b) p.fn_b<<<dim3(p.grid), dim3(SEQ_NT), seq_lds_image(1, 2, 1, p.nkb_max).bytes, st>>>(b);
         else p.fn_p<<<dim3(p.grid), dim3(SEQ_NT), p.smem, st>>>(g);
     };
@@ -1170,7 +1186,8 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         for (int q = 0; q < 3; q++) s.img[q] = S.img[q];
         s.part = S.qpart; s.D = D; s.T = n;
         s.img_h = h.img; s.part_h = h.part3;
-        if (ckpt) (nv == 3 ? ckf.site3 : ckf.site2)<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
+        if (plan && state) (nv == 3 ? sgf.site3 : sgf.site2)<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(SegSiteArgs{s, plan, S.seg});
+        else if (ckpt) (nv == 3 ? ckf.site3 : ckf.site2)<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else if (nv == 3) k_seq_site<3><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else if (nv == 2) k_seq_site<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
         else k_seq_site<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
@@ -1187,7 +1204,8 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
             site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo, ck ? ck + lo * n : nullptr);
             gemm(0, c->wc[0].b_at(wl, D), c->wc[0].r8_at(wl, D), c->state[0] + lo);
             SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, par ? 1 : 0, LD, (int)row0, h.pk3, h.part3};
-            if (ck) {
+            if (plan) (two ? sgf.wkv64 : sgf.wkv32)<<<dim3(n_wkv), dim3((two ? SEQ_TM : SEQ_T) * WKV_CH), 0, st>>>(SegWkvArgs{wa, plan, S.seg, c->state[0] + lo});
+            else if (ck) {
                 wa.ckpt_aa = ck + ck_arr + lo * n; wa.ckpt_bb = ck + 2 * ck_arr + lo * n;
                 ckf.wkv<<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
             } else if (two) k_seq_wkv<SEQ_TM><<<dim3(n_wkv), dim3(SEQ_TM * WKV_CH), 0, st>>>(wa);
@@ -1206,7 +1224,8 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
             site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo, ck ? ck + 3 * ck_arr + lo * n : nullptr);
             gemm(2, c->wc[2].b_at(wl, D), c->wc[2].r8_at(wl, D), c->state[4] + lo);
             SeqStageArgs sh{nullptr, S.pk5, S.qpart, c->fvr + 4 * lo, c->fvo + 4 * lo, S.imgh, S.qparth, 4 * D, n, h.pk5, h.part3, h.imgh, h.part1};
-            k_seq_stage<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sh);
+            if (plan) sgf.stage<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(SegStageArgs{sh, plan, S.seg, c->state[4] + lo, LD, D});
+            else k_seq_stage<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sh);
             gemm(3, c->wc[3].b_at(wl, D), c->wc[3].r8_at(wl, D), nullptr);
             resid(2, S.qparth);     // x += ffn_v * sigmoid(r); statistics for the next site
         }
@@ -1311,15 +1330,20 @@ int enqueue_pass(rwkv_ctx *c, const SeqPass &pass)
     return 0;
 }
 
+// rows per weight pass: 64 (two halves sharing every weight fragment) for calls of more than 32 rows, else 32
+uint64_t seq_pass_rows(const rwkv_ctx *c, uint64_t T) { return (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T; }
+
 // The chunk path's schedule of T >= 2 rows (rwkv_forward's; every step of rwkv_decode_batch_* runs it too): passes of <= 64 rows and,
 // for more than one pass, the software pipeline over the RWKV_SEQ_STAGES streams.  The token ids come from the host
 // (`tokens`) or, PARRALEL mode only, from the device array `dtok` ([T], e.g. the picks of the previous decode step).  Only enqueues:
 // the context's stream holds the result when it returns.
-int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *dtok, uint64_t T, int mode)
+// plan: the SEGMENTED layout (GPT mode, T >= 1, ids from the host) -- the call's row plan on the device, [T], cut for passes of seq_pass_rows(c, T);
+// pass t0 reads plan + t0 and is launched directly, like a PARRALEL pass (its shape changes from call to call: nothing to replay).
+int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *dtok, uint64_t T, int mode, const SegRow *plan = nullptr)
 {
     if (dtok && mode != RWKV_MODE_PARRALEL) return fail(RWKV_E_ARG, "device token ids need PARRALEL mode");
-    // rows per weight pass: 64 (two halves sharing every weight fragment) for calls of more than 32 rows, else 32
-    const uint64_t CH = (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T;
+    if (plan && (dtok || mode != RWKV_MODE_GPT)) return fail(RWKV_E_ARG, "a row plan needs GPT mode and ids from the host");
+    const uint64_t CH = seq_pass_rows(c, T);
     const uint64_t nchunks = (T + CH - 1) / CH;
     int rc = 0;
     // Software pipeline over the chunks: stage k = an equal share of the layers (the last one with the head) on its
@@ -1331,6 +1355,8 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
     // scratch, every pass in buffer 0, nothing to hand over and so no event (and no split_setup for a single pass: nothing is allocated).
     if (nchunks >= 2 && (rc = split_setup(c))) return rc;
     const int ns = nchunks >= 2 ? c->n_split : 1;
+    for (int k = 0; plan && k < ns; k++)      // the staging rows of the scratch sets this call uses
+        if (!c->sp_scratch[k].seg && (rc = dalloc(c, &c->sp_scratch[k].seg, (size_t)SEQ_TM * c->D))) return rc;
     if (ns >= 2) HIPCHK(hipEventRecord(c->sp_end, c->stream));        // the other stages start behind whatever the context's stream holds
     for (int k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(c->sp_stream[k], c->sp_end, 0));
     uint64_t i = 0;
@@ -1342,9 +1368,10 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
             if (k > 0) HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                    // the stage before has handed chunk i over
             else if (ns >= 2 && i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0));   // the last stage is done with this buffer (chunk i - ns)
             // (stage 0: the context's own stream and scratch)
-            const SeqPass pass{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k], b, n, t0, mode == RWKV_MODE_PARRALEL, dtok ? dtok + t0 : token_slot(c, b)};
+            const SeqPass pass{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k], b, n, t0, mode == RWKV_MODE_PARRALEL, dtok ? dtok + t0 : token_slot(c, b),
+                               nullptr, plan ? plan + t0 : nullptr};
             if (pass.embeds(c) && !dtok) rc = upload_chunk_tokens(c, tokens + t0, n, b, st);
-            if (!rc) rc = pass.par ? enqueue_chunk(c, pass) : enqueue_pass(c, pass);
+            if (!rc) rc = (pass.par || pass.plan) ? enqueue_chunk(c, pass) : enqueue_pass(c, pass);
             if (ns >= 2) HIPCHK(hipEventRecord(c->sp_done[k][b], st));
         }
     }
@@ -2934,6 +2961,68 @@ int rwkv_decode_speculative(rwkv_ctx *c, rwkv_ctx *dc, uint64_t first_token, uin
     return rc;
 }
 
+// ---- segmented forward (segments.hip.h): rwkv_segment_plan, rwkv_forward_segments ----
+static_assert(sizeof(rwkv_segment) == 8 && sizeof(SegRow) == 8, "rwkv_segment and a row of the plan are two 32-bit words");
+namespace {
+SegFns seg_fns() { return SegFns{k_seg_site<3>, k_seg_site<2>, k_seg_wkv<SEQ_T>, k_seg_wkv<SEQ_TM>, k_seg_stage<1>}; }
+
+// The one validator and planner: the rules of a segment list, then -- into whichever outputs are there -- the plan for passes of `pass_rows` rows.
+// A piece ends where its segment ends or where the pass ends.  Nothing is written when the list is rejected.
+int segment_plan(const rwkv_segment *segs, uint64_t n_segs, uint64_t max_ctx, uint64_t pass_rows, uint32_t *row_slot, uint8_t *row_flags, SegRow *rows,
+                 uint64_t *last_row, uint64_t *n_rows)
+{
+    if (!segs) return fail(RWKV_E_ARG, "NULL argument");
+    if (n_segs == 0 || n_segs > max_ctx) return fail(RWKV_E_ARG, "n_segs must be in 1..%llu (max context)", (unsigned long long)max_ctx);
+    uint64_t T = 0;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        if (segs[i].n == 0) return fail(RWKV_E_ARG, "segment %llu is empty", (unsigned long long)i);
+        if (segs[i].slot >= max_ctx) return fail(RWKV_E_ARG, "segment %llu: slot %u out of range, max context is %llu", (unsigned long long)i, segs[i].slot, (unsigned long long)max_ctx);
+        T += segs[i].n;
+        if (T > max_ctx) return fail(RWKV_E_ARG, "Context too large, max context is %llu", (unsigned long long)max_ctx);
+    }
+    std::vector<uint32_t> slots(n_segs);
+    for (uint64_t i = 0; i < n_segs; i++) slots[i] = segs[i].slot;
+    std::sort(slots.begin(), slots.end());
+    for (uint64_t i = 1; i < n_segs; i++)
+        if (slots[i] == slots[i - 1]) return fail(RWKV_E_ARG, "slot %u is named twice: the slots of one call are pairwise distinct", slots[i]);
+    uint64_t j = 0;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        for (uint32_t k = 0; k < segs[i].n; k++, j++) {
+            const unsigned f = ((k == 0 || j % pass_rows == 0) ? SEG_FIRST : 0u) | ((k + 1 == segs[i].n || (j + 1) % pass_rows == 0) ? SEG_LAST : 0u);
+            if (row_slot) row_slot[j] = segs[i].slot;
+            if (row_flags) row_flags[j] = (uint8_t)f;
+            if (rows) rows[j] = SegRow{segs[i].slot, f};
+        }
+        if (last_row) last_row[i] = j - 1;
+    }
+    if (n_rows) *n_rows = T;
+    return 0;
+}
+} // namespace
+
+int rwkv_segment_plan(const rwkv_segment *segs, uint64_t n_segs, uint64_t max_ctx, uint32_t *row_slot, uint8_t *row_flags, uint64_t *n_rows)
+{
+    return segment_plan(segs, n_segs, max_ctx, (uint64_t)SEQ_TM, row_slot, row_flags, nullptr, nullptr, n_rows);
+}
+
+int rwkv_forward_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_segment *segs, uint64_t n_segs, uint32_t flags, uint64_t *last_row)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    uint64_t T = 0;
+    if (const int rc = segment_plan(segs, n_segs, c->maxT, 1, nullptr, nullptr, nullptr, nullptr, &T)) return rc;      // the rules alone
+    if (const int rc = check_ids(tokens, T, "token")) return rc;
+    if (!c->h_seg_plan) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_seg_plan), sizeof(SegRow) * c->maxT, hipHostMallocDefault));
+    if (const int rc = grow_buffer(c, SEG_PLAN, sizeof(SegRow) * c->maxT)) return rc;
+    // (the pinned plan is free: every call that read it has returned behind its wait)
+    (void)segment_plan(segs, n_segs, c->maxT, seq_pass_rows(c, T), nullptr, nullptr, c->h_seg_plan, last_row, nullptr);
+    return finish(c, [&]() -> int {
+        SegRow *plan = c->buf<SegRow>(SEG_PLAN);
+        HIPCHK(hipMemcpyAsync(plan, c->h_seg_plan, sizeof(SegRow) * T, hipMemcpyHostToDevice, c->stream));
+        return enqueue_rows(c, tokens, nullptr, T, RWKV_MODE_GPT, plan);
+    }());
+}
+
 void rwkv_free(rwkv_ctx *c)
 {
     if (!c) return;
@@ -2945,6 +3034,7 @@ void rwkv_free(rwkv_ctx *c)
     for (void *p : c->allocs) (void)hipFree(p);
     for (const rwkv_ctx::Grown &g : c->grown) if (g.p) (void)hipFree(g.p);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
+    if (c->h_seg_plan) (void)hipHostFree(c->h_seg_plan);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);

@@ -153,6 +153,13 @@ PYBIND11_MODULE(rwkv, m)
     }, "speculative greedy decoding: the model of handle `draft` (loaded with maxGPT >= k + 2, same prefix in slot 0) guesses k ids per round, this "
        "one verifies them in one pass: (ids [n], (rounds, drafted, accepted)); the ids do not depend on the draft model (engine extension)",
           py::arg("rwkvp"), py::arg("draft"), py::arg("first"), py::arg("n"), py::arg("k") = 4u);
+    m.def("modelForwardSegments", [](std::uintptr_t h, const std::vector<std::pair<unsigned, std::vector<int64_t>>> &segments) {
+        std::vector<RWKV::Segment> segs;
+        for (const auto &s : segments) segs.push_back(RWKV::Segment{s.first, std::vector<unsigned long long>(s.second.begin(), s.second.end())});
+        const std::vector<unsigned long long> last = M(h)->forwardSegments(segs);
+        return std::vector<int64_t>(last.begin(), last.end());
+    }, "one call of the chunk path over segments [(slot, ids)] with pairwise distinct slots: every sequence continues from its slot, logits row j "
+       "belongs to token j of the ids back to back; returns the row of each segment's last token (engine extension)", py::arg("rwkvp"), py::arg("segments"));
     // ---- constrained decoding: the engine calls, and the host twins of include/rwkv_sampler.h for the suite ----
     using u32arr = py::array_t<uint32_t, py::array::c_style | py::array::forcecast>;
     using f32arr = py::array_t<float, py::array::c_style | py::array::forcecast>;

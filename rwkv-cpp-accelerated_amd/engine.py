@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "rwkv_constraint_set", "rwkv_constraint_clear", "rwkv_constraint_state_set", "rwkv_constraint_state_get", "rwkv_pick_constrained",
     "rwkv_debug_constrained_row", "rwkv_decode_batch_constrained",
     "rwkv_spec_verify", "rwkv_decode_speculative",
+    "rwkv_forward_segments", "rwkv_segment_plan",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
@@ -112,6 +113,31 @@ def beam_params(width, stops=()):
 class SpecStats(C.Structure):
     """rwkv_spec_stats of include/rwkv_mi355x.h (24 bytes)"""
     _fields_ = [("rounds", C.c_uint64), ("drafted", C.c_uint64), ("accepted", C.c_uint64)]
+
+
+class Segment(C.Structure):
+    """rwkv_segment of include/rwkv_mi355x.h (8 bytes)"""
+    _fields_ = [("slot", C.c_uint32), ("n", C.c_uint32)]
+
+
+def _segments(segments):
+    """(Segment array, count, the packed ids) of a list of (slot, token_ids)"""
+    segs = [(int(s), [int(t) for t in ids]) for s, ids in segments]
+    arr = (Segment * max(1, len(segs)))(*[Segment(s, len(ids)) for s, ids in segs])
+    return arr, len(segs), [t for _, ids in segs for t in ids]
+
+
+def segment_plan(segments, max_ctx: int):
+    """rwkv_segment_plan, host only (no model, no device): validates `segments`, a list of (slot, token_ids) or of (slot, n), against max_ctx and
+    returns (row_slot, row_flags) for passes of 64 rows: per row of the call its slot, and bit 0 = first of its piece, bit 1 = last of its piece.
+    A list that breaks a rule raises RWKVError."""
+    segs = [(int(s), int(n) if np.isscalar(n) else len(n)) for s, n in segments]
+    arr = (Segment * max(1, len(segs)))(*[Segment(s, n) for s, n in segs])
+    T = C.c_uint64(0)
+    _chk(lib().rwkv_segment_plan(arr, len(segs), int(max_ctx), None, None, C.byref(T)))
+    slot, flags = np.zeros(T.value, np.uint32), np.zeros(T.value, np.uint8)
+    _chk(lib().rwkv_segment_plan(arr, len(segs), int(max_ctx), slot.ctypes.data_as(C.POINTER(C.c_uint32)), flags.ctypes.data_as(C.POINTER(C.c_uint8)), None))
+    return slot, flags
 
 
 def ngram_draft(history, k: int, n: int = 3):
@@ -277,6 +303,8 @@ def lib():
     L.rwkv_decode_batch_constrained.restype = i32
     L.rwkv_spec_verify.argtypes = [vp, u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_spec_verify.restype = i32
     L.rwkv_decode_speculative.argtypes = [vp, vp, u64, u64, C.c_uint32, C.POINTER(u64), C.POINTER(SpecStats)]; L.rwkv_decode_speculative.restype = i32
+    L.rwkv_forward_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(Segment), u64, C.c_uint32, C.POINTER(u64)]; L.rwkv_forward_segments.restype = i32
+    L.rwkv_segment_plan.argtypes = [C.POINTER(Segment), u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(u64)]; L.rwkv_segment_plan.restype = i32
     _lib = L
     return L
 
@@ -815,6 +843,24 @@ class RWKV:
         if not self.resident:
             self.pull_state(1)
         return int(a.value), int(nx.value)
+
+    # -- segmented forward (include/rwkv_mi355x.h rwkv_forward_segments) --------------------------------------------------------
+    def forward_segments(self, segments):
+        """one call of the chunk path over `segments`, a list of (slot, token_ids) with pairwise distinct slots: each sequence continues from its
+        slot and leaves it after its ids, all behind one read of the weights per pass.  Row j of the logits buffer belongs to token j of the
+        ids back to back; returns last_row, the row of each segment's last token (read it with logits / score_rows / topn_rows)."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        arr, n, ids = _segments(segments)
+        toks = (C.c_uint64 * max(1, len(ids)))(*ids)
+        last = (C.c_uint64 * max(1, n))()
+        slots = min(self.maxContext, 1 + max([int(s.slot) for s in arr[:n]], default=0))
+        if not self.resident:
+            self.push_state(slots)
+        _chk(lib().rwkv_forward_segments(self._h, toks, arr, n, 0, last))
+        if not self.resident:
+            self.pull_state(slots)
+        return [int(r) for r in last[:n]]
 
     def decode_speculative(self, draft_model: "RWKV", first_token: int, n_tokens: int, k: int = 4):
         """greedy continuation of n_tokens ids with `draft_model` (a second loaded model on the same device whose slot 0 holds the same prefix,
