@@ -1080,23 +1080,32 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     return 0;
 }
 
+// The ROW LAYOUT of a pass: what its rows are to each other -- one of four, with the one thing that layout needs besides the pass's rows.
+//   GPT        rwkv.cu:493-593: n tokens of one sequence on state slot 0, the token shift runs along the rows
+//   PARRALEL   rwkv.cu:236-240: n independent sequences, one token each, row t on state slot row0 + t -- the batched decode step
+//   CKPT       the verify pass of rwkv_spec_verify (spec.hip.h): GPT rows, one half, whole model, that commit NOTHING to slot 0 -- every row's state
+//              is left in `ckpt`, [4][L][n][D]
+//   SEGMENTED  segments.hip.h: the rows are pieces of sequences on slots of their own, as `plan` says ([rows]{slot, flags} on the device)
+// Only GPT passes are replayed as captured graphs (enqueue_pass: its key holds a shape, no layout); the rest change from call to call and are
+// launched directly.
+struct RowLayout {
+    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED } kind = GPT;
+    union { double *ckpt = nullptr; const SegRow *plan; };
+    static RowLayout of_mode(int mode) { RowLayout r; r.kind = mode == RWKV_MODE_PARRALEL ? PARRALEL : GPT; return r; }
+    static RowLayout checkpoints(double *ck) { RowLayout r; r.kind = CKPT; r.ckpt = ck; return r; }
+    static RowLayout segments(const SegRow *plan) { RowLayout r; r.kind = SEGMENTED; r.plan = plan; return r; }
+    bool replayed() const { return kind == GPT; }
+    RowLayout from_row(uint64_t t0) const { RowLayout r = *this; if (kind == SEGMENTED) r.plan += t0; return r; }      // the layout of the pass that starts at row t0 of a call
+};
 // One pass (n <= SEQ_TM = 64 rows: one or two halves of <= 32) through the MFMA path (seq.hip.h) for layers [la, lb) of THIS context's [l0, l1);
 // logits rows [row0, row0 + n) where the pass holds the head.
-// par == false: GPT-mode semantics of rwkv.cu:493-593 -- n tokens of one sequence, state slot 0, token
-// shift along the chunk.  par == true: PARRALEL mode (rwkv.cu:236-240) -- n independent sequences, one
-// token each, row t uses state slot row0 + t: the batched decode step, weights read once for all.
 // The residual stream of the chunk lives in sq_x[buf]: the pass that holds the embedding fills it from the table, a later
 // pipeline stage finds the previous stage's output there (placed by an RCCL recv or a copy) and every stage leaves its
 // own output in it.  The layers run on `st` with scratch set `S` (the software pipeline of rwkv_forward: a stream and a set per stage).
 // dtok: the pass's n token ids on the device, read where the pass holds the embedding -- token_slot(c, buf) behind upload_chunk_tokens, or wherever
 // they already are (the batched decode's picks of the previous step)
-// ckpt: the verify pass of rwkv_spec_verify (GPT mode, one half, whole model) -- [4][L][n][D], see spec.hip.h: every row's state is left there and
-// NOTHING is committed to slot 0
-// plan: a SEGMENTED pass (segments.hip.h; par == false, no ckpt) -- the pass's slice of the row plan on the device, [n]{slot, flags}: the rows are
-// pieces of sequences on slots of their own.  Null: one of the two layouts above
 struct SeqPass {
-    uint64_t la, lb; hipStream_t st; const SeqScratch *S; int buf, n; uint64_t row0; bool par; const unsigned long long *dtok; double *ckpt = nullptr;
-    const SegRow *plan = nullptr;
+    uint64_t la, lb; hipStream_t st; const SeqScratch *S; int buf, n; uint64_t row0; const unsigned long long *dtok; RowLayout rows;
     bool embeds(const rwkv_ctx *c) const { return c->l0 == 0 && la == c->l0; }
     bool heads(const rwkv_ctx *c) const { return c->l1 == c->L && lb == c->l1; }
 };
@@ -1114,11 +1123,10 @@ int upload_chunk_tokens(rwkv_ctx *c, const uint64_t *tokens, int n, int buf, hip
     c->sq_n++;
     return 0;
 }
-// the CKPT instances of the verify pass, named where rwkv_spec_verify stands (hipcc emits a template instance where the host code first names it:
-// these stay behind every kernel the parent of this feature had, beam.hip.h k_beam_select)
+// The instances of the CKPT and SEGMENTED layouts are declared here and NAMED beside their features, behind every other kernel: hipcc emits a template
+// instance where host code first names it, and a kernel that moves in the code object costs time elsewhere (beam.hip.h k_beam_select).
 struct SeqCkptFns { void (*site3)(SeqSiteArgs) = nullptr; void (*site2)(SeqSiteArgs) = nullptr; void (*wkv)(SeqWkvArgs) = nullptr; };
 SeqCkptFns seq_ckpt_fns();
-// the instances of a segmented pass, named where rwkv_forward_segments stands for the same reason
 struct SegFns {
     void (*site3)(SegSiteArgs) = nullptr; void (*site2)(SegSiteArgs) = nullptr; void (*wkv32)(SegWkvArgs) = nullptr; void (*wkv64)(SegWkvArgs) = nullptr;
     void (*stage)(SegStageArgs) = nullptr;
@@ -1129,7 +1137,6 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
     const int D = (int)c->D, n = pass.n;
     const uint64_t L = c->L, V = RWKV_VOCAB, row0 = pass.row0;
-    const bool par = pass.par;
     hipStream_t st = pass.st;
     const SeqScratch &S = *pass.S;
     double *x = c->sq_x[pass.buf];
@@ -1143,19 +1150,22 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     // at these element offsets behind half 0's
     const bool two = n > SEQ_T;
     const SeqHalf h((size_t)D);
-    double *const ck = pass.ckpt;
-    if (ck && (par || two)) return fail(RWKV_E_ARG, "a checkpointing pass is one half in GPT mode");
-    const SeqCkptFns ckf = ck ? seq_ckpt_fns() : SeqCkptFns{};
-    const SegRow *const plan = pass.plan;
-    if (plan && (par || ck || !S.seg)) return fail(RWKV_E_ARG, "a segmented pass is neither PARRALEL nor checkpointing, and its scratch set holds the staging rows");
-    const SegFns sgf = plan ? seg_fns() : SegFns{};
+    // What the layout means, said once.  A site with a token shift keeps its LayerNorm output for the sequence's next row: GPT in S.state (the last
+    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT in the checkpoint rows; SEGMENTED in
+    // the staging rows, which the WKV and stage-1 kernels behind the GEMMs commit.  The three launch helpers below (site, wkv, stage) pick their instance.
+    const RowLayout &rows = pass.rows;
+    const bool commits = rows.kind == RowLayout::GPT;
+    if (rows.kind == RowLayout::CKPT && two) return fail(RWKV_E_ARG, "a checkpointing pass is one half");
+    if (rows.kind == RowLayout::SEGMENTED && !S.seg) return fail(RWKV_E_ARG, "the scratch set of a segmented pass holds the staging rows");
+    const SeqCkptFns ckf = rows.kind == RowLayout::CKPT ? seq_ckpt_fns() : SeqCkptFns{};
+    const SegFns sgf = rows.kind == RowLayout::SEGMENTED ? seg_fns() : SegFns{};
     const size_t ck_arr = (size_t)L * n * D;      // one of the four checkpoint arrays; layer l's rows start l * n * D into it
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
     // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
     const SeqPart *const parts[4] = {S.qpart, S.qparta, S.qpart, S.qparth};
     float *const pks[4] = {S.pk3, S.pk1, S.pk5, S.pk1};
     // tile-per-wave GEMM of layer matrix `bimg` (row sums `rs8`) over the 8 K-slices, partial values into the kind's pk, launched as the context's
-    // plan says (seq_gemm_plan); state_dst: GPT mode commits the state of the site in front of it behind it
+    // plan says (seq_gemm_plan); state_dst: where a layout that `commits` has it copy the state of the site in front of it
     auto gemm = [&](int kind, const uint8_t *bimg, const unsigned *rs8, double *state_dst) {
         const SeqGemmPlan &p = c->seq_plan[4 * two + kind];
         SeqGemmBArgs b = p.args;
@@ -1164,7 +1174,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         for (int v = 0; v < 3; v++) g.img[v] = reinterpret_cast<const u32x4 *>(kind == 3 ? S.imgh : S.img[v]);
         g.part = parts[kind]; g.pk = pks[kind]; g.out = nullptr; g.T = n;
         g.tl = (c->tl_on && c->tl_cls == 10 + kind && tl_layer) ? c->tl : nullptr;
-        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && !par && !ck && !plan) ? D : 0;
+        g.cp_src = S.state; g.cp_dst = state_dst; g.cp_n = (state_dst && commits) ? D : 0;
         if (p.fn_b) p.fn_b<<<dim3(p.grid), dim3(SEQ_NT), seq_lds_image(1, 2, 1, p.nkb_max).bytes, st>>>(b);
         else p.fn_p<<<dim3(p.grid), dim3(SEQ_NT), p.smem, st>>>(g);
     };
@@ -1177,22 +1187,48 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         else if (mode == 1) k_seq_resid<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
         else k_seq_resid<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(r);
     };
-    auto site = [&](int nv, const double *lnw, const double *lnb, const double *const *mix, const float *const *r, const float *const *o, double *state, double *ckpt) {
+    // state: this layer's xy / dd of slot 0 for a site with a token shift, null for ln_out, which shifts and keeps nothing and so is the plain instance
+    // in every layout; ck_at: where this site's rows start in the checkpoint arrays
+    auto site = [&](int nv, const double *lnw, const double *lnb, const double *const *mix, const float *const *r, const float *const *o, double *state, size_t ck_at) {
         SeqSiteArgs s{};
         s.x = x; s.stat = S.stat; s.lnw = lnw; s.lnb = lnb;
         for (int q = 0; q < nv; q++) { s.mix[q] = mix ? mix[q] : nullptr; s.r[q] = r[q]; s.o[q] = o[q]; }
-        s.state = state; s.state_new = (state && !par && !ckpt) ? S.state : nullptr; s.ckpt = ckpt;
-        s.par = par && state; s.state_par = state; s.slot_stride = LD; s.slot0 = (int)row0;
+        s.state = s.state_par = state; s.slot_stride = LD; s.slot0 = (int)row0;
         for (int q = 0; q < 3; q++) s.img[q] = S.img[q];
         s.part = S.qpart; s.D = D; s.T = n;
         s.img_h = h.img; s.part_h = h.part3;
-        if (plan && state) (nv == 3 ? sgf.site3 : sgf.site2)<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(SegSiteArgs{s, plan, S.seg});
-        else if (ckpt) (nv == 3 ? ckf.site3 : ckf.site2)<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
-        else if (nv == 3) k_seq_site<3><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
-        else if (nv == 2) k_seq_site<2><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
-        else k_seq_site<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(s);
+        const dim3 grid(egrid), block(SEQ_ENT);
+        switch (state ? rows.kind : RowLayout::GPT) {
+        case RowLayout::SEGMENTED: (nv == 3 ? sgf.site3 : sgf.site2)<<<grid, block, 0, st>>>(SegSiteArgs{s, rows.plan, S.seg}); return;
+        case RowLayout::CKPT: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ckf.site3 : ckf.site2)<<<grid, block, 0, st>>>(s); return;
+        case RowLayout::PARRALEL: s.par = 1; break;
+        case RowLayout::GPT: s.state_new = state ? S.state : nullptr; break;      // (and ln_out of every layout: nothing to keep)
+        }
+        if (nv == 3) k_seq_site<3><<<grid, block, 0, st>>>(s);
+        else if (nv == 2) k_seq_site<2><<<grid, block, 0, st>>>(s);
+        else k_seq_site<1><<<grid, block, 0, st>>>(s);
     };
-    const int n_wkv = (D + WKV_CH - 1) / WKV_CH;
+    auto wkv = [&](size_t lo) {
+        SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, rows.kind == RowLayout::PARRALEL, LD, (int)row0, h.pk3, h.part3};
+        const dim3 grid((D + WKV_CH - 1) / WKV_CH), block((two ? SEQ_TM : SEQ_T) * WKV_CH);
+        switch (rows.kind) {
+        case RowLayout::SEGMENTED: (two ? sgf.wkv64 : sgf.wkv32)<<<grid, block, 0, st>>>(SegWkvArgs{wa, rows.plan, S.seg, c->state[0] + lo}); return;
+        case RowLayout::CKPT:      // (one half: refused above otherwise)
+            wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
+            ckf.wkv<<<grid, block, 0, st>>>(wa);
+            return;
+        default: break;
+        }
+        if (two) k_seq_wkv<SEQ_TM><<<grid, block, 0, st>>>(wa);
+        else k_seq_wkv<SEQ_T><<<grid, block, 0, st>>>(wa);
+    };
+    // kind 0: the att_out input, the same in every layout; kind 1: the ffn_v input -- in a segmented pass with the commit of the ln2 site's rows
+    auto stage = [&](int kind, const SeqStageArgs &sa, size_t lo) {
+        const dim3 grid(egrid), block(SEQ_ENT);
+        if (kind == 0) k_seq_stage<0><<<grid, block, 0, st>>>(sa);
+        else if (rows.kind == RowLayout::SEGMENTED) sgf.stage<<<grid, block, 0, st>>>(SegStageArgs{sa, rows.plan, S.seg, c->state[4] + lo, LD, D});
+        else k_seq_stage<1><<<grid, block, 0, st>>>(sa);
+    };
     resid(0, nullptr);     // LayerNorm statistics of the incoming residual stream (embedding rows, or the previous stage's output)
     for (uint64_t l = pass.la; l < pass.lb; l++) {
         tl_layer = l == (c->l0 + c->l1) / 2;
@@ -1201,17 +1237,11 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         {   // time mix
             const double *mix[3] = {c->mixk + lo, c->mixv + lo, c->mixr + lo};
             const float *r[3] = {c->kr + lo, c->vr + lo, c->rr + lo}, *o[3] = {c->o1 + lo, c->o2 + lo, c->o3 + lo};
-            site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo, ck ? ck + lo * n : nullptr);
+            site(3, c->ln + (4 * l + 2) * D, c->ln + (4 * l + 3) * D, mix, r, o, c->state[0] + lo, lo * n);
             gemm(0, c->wc[0].b_at(wl, D), c->wc[0].r8_at(wl, D), c->state[0] + lo);
-            SeqWkvArgs wa{S.pk3, S.qpart, c->uw + lo, c->ew + lo, c->state[1] + lo, c->state[2] + lo, S.y, D, n, par ? 1 : 0, LD, (int)row0, h.pk3, h.part3};
-            if (plan) (two ? sgf.wkv64 : sgf.wkv32)<<<dim3(n_wkv), dim3((two ? SEQ_TM : SEQ_T) * WKV_CH), 0, st>>>(SegWkvArgs{wa, plan, S.seg, c->state[0] + lo});
-            else if (ck) {
-                wa.ckpt_aa = ck + ck_arr + lo * n; wa.ckpt_bb = ck + 2 * ck_arr + lo * n;
-                ckf.wkv<<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
-            } else if (two) k_seq_wkv<SEQ_TM><<<dim3(n_wkv), dim3(SEQ_TM * WKV_CH), 0, st>>>(wa);
-            else k_seq_wkv<SEQ_T><<<dim3(n_wkv), dim3(SEQ_T * WKV_CH), 0, st>>>(wa);
+            wkv(lo);
             SeqStageArgs sa{S.y, nullptr, nullptr, c->attr + lo, c->atto + lo, S.img[0], S.qparta, D, n, 0, 0, h.img, h.part1};
-            k_seq_stage<0><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sa);
+            stage(0, sa, lo);
             gemm(1, c->wc[1].b_at(wl, D), c->wc[1].r8_at(wl, D), nullptr);
             // x = f32(x) + att_out; statistics for ln2.  (Round 3 tried this launch and the site behind it as ONE launch whose (row, octant)
             // workgroups meet on a per-row arrival counter: +3.6 us per fused launch, profiles/r03/prefill_fuse.txt -- the in-launch
@@ -1221,18 +1251,17 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         {   // channel mix
             const double *mix[3] = {c->fmixk + lo, c->fmixr + lo, nullptr};
             const float *r[3] = {c->fkr + lo, c->frr + lo, nullptr}, *o[3] = {c->fko + lo, c->fro + lo, nullptr};
-            site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo, ck ? ck + 3 * ck_arr + lo * n : nullptr);
+            site(2, c->ln + (4 * l + 4) * D, c->ln + (4 * l + 5) * D, mix, r, o, c->state[4] + lo, 3 * ck_arr + lo * n);
             gemm(2, c->wc[2].b_at(wl, D), c->wc[2].r8_at(wl, D), c->state[4] + lo);
             SeqStageArgs sh{nullptr, S.pk5, S.qpart, c->fvr + 4 * lo, c->fvo + 4 * lo, S.imgh, S.qparth, 4 * D, n, h.pk5, h.part3, h.imgh, h.part1};
-            if (plan) sgf.stage<<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(SegStageArgs{sh, plan, S.seg, c->state[4] + lo, LD, D});
-            else k_seq_stage<1><<<dim3(egrid), dim3(SEQ_ENT), 0, st>>>(sh);
+            stage(1, sh, lo);
             gemm(3, c->wc[3].b_at(wl, D), c->wc[3].r8_at(wl, D), nullptr);
             resid(2, S.qparth);     // x += ffn_v * sigmoid(r); statistics for the next site
         }
     }
     if (pass.heads(c)) {   // ln_out and the head
         const float *r[3] = {c->headr, nullptr, nullptr}, *o[3] = {c->heado, nullptr, nullptr};
-        site(1, c->ln + (4 * L + 2) * D, c->ln + (4 * L + 3) * D, nullptr, r, o, nullptr, nullptr);
+        site(1, c->ln + (4 * L + 2) * D, c->ln + (4 * L + 3) * D, nullptr, r, o, nullptr, 0);
         SeqGemmArgs g{};
         g.bimg = reinterpret_cast<const u32x4 *>(c->wc[4].b); g.rs8 = c->wc[4].r8; g.N = (int)V; g.K = D; g.Q = 1;
         for (int hf = 0; hf < (two ? 2 : 1); hf++) {      // the head once per half (its weights are 3 % of a pass's bytes; 240 accumulator registers would not fit one wave)
@@ -1247,7 +1276,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 // a GPT-mode pass over the context's whole layer range on its own stream with its own scratch, the ids (where it holds the embedding) from the host
 int enqueue_whole(rwkv_ctx *c, const uint64_t *tokens, int n, uint64_t row0, int buf)
 {
-    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], buf, n, row0, false, token_slot(c, buf)};
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], buf, n, row0, token_slot(c, buf)};
     if (pass.embeds(c)) { const int rcu = upload_chunk_tokens(c, tokens, n, buf, c->stream); if (rcu) return rcu; }
     return enqueue_chunk(c, pass);
 }
@@ -1300,11 +1329,12 @@ void trim_pass_graphs(rwkv_ctx *c)
     c->sq_graphs.clear();
 }
 
-// one pass of the chunk path (GPT mode): replay of the captured graph of exactly this pass shape, captured at first use.  The token
+// one pass of the chunk path (GPT layout only: the key below cannot tell layouts apart): replay of the captured graph of exactly this pass shape, captured at first use.  The token
 // upload stays outside (the caller's: host memory changes per pass; the pass reads the ids from its buffer's device slot); everything
 // else a pass launches depends only on the key.  A capture that fails turns the graphs off for the context and the pass is launched directly.
 int enqueue_pass(rwkv_ctx *c, const SeqPass &pass)
 {
+    if (!pass.rows.replayed()) return fail(RWKV_E_ARG, "only a GPT pass is replayed");
     if (!c->seq_graph || c->tl_on) return enqueue_chunk(c, pass);
     const rwkv_ctx::SeqGraphKey key{pass.la, pass.lb, pass.heads(c) ? pass.row0 : 0, pass.buf, pass.n};
     auto it = c->sq_graphs.find(key);
@@ -1334,15 +1364,15 @@ int enqueue_pass(rwkv_ctx *c, const SeqPass &pass)
 uint64_t seq_pass_rows(const rwkv_ctx *c, uint64_t T) { return (T > (uint64_t)SEQ_T && c->seq_rows > SEQ_T) ? (uint64_t)SEQ_TM : (uint64_t)SEQ_T; }
 
 // The chunk path's schedule of T >= 2 rows (rwkv_forward's; every step of rwkv_decode_batch_* runs it too): passes of <= 64 rows and,
-// for more than one pass, the software pipeline over the RWKV_SEQ_STAGES streams.  The token ids come from the host
-// (`tokens`) or, PARRALEL mode only, from the device array `dtok` ([T], e.g. the picks of the previous decode step).  Only enqueues:
-// the context's stream holds the result when it returns.
-// plan: the SEGMENTED layout (GPT mode, T >= 1, ids from the host) -- the call's row plan on the device, [T], cut for passes of seq_pass_rows(c, T);
-// pass t0 reads plan + t0 and is launched directly, like a PARRALEL pass (its shape changes from call to call: nothing to replay).
-int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *dtok, uint64_t T, int mode, const SegRow *plan = nullptr)
+// for more than one pass, the software pipeline over the RWKV_SEQ_STAGES streams, in the row layout `rows` of the whole call (a
+// segmented call's plan is cut for passes of seq_pass_rows(c, T): pass t0 reads plan + t0).  The token ids come from the host (`tokens`) or from
+// the device array `dtok` ([T], e.g. the picks of the previous decode step) -- not for a layout that is replayed: a captured pass reads its ids
+// from its buffer's slot.  Only enqueues: the context's stream holds the result when it returns.
+int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *dtok, uint64_t T, const RowLayout &rows)
 {
-    if (dtok && mode != RWKV_MODE_PARRALEL) return fail(RWKV_E_ARG, "device token ids need PARRALEL mode");
-    if (plan && (dtok || mode != RWKV_MODE_GPT)) return fail(RWKV_E_ARG, "a row plan needs GPT mode and ids from the host");
+    if (dtok && rows.replayed()) return fail(RWKV_E_ARG, "a replayed pass takes its token ids from the host");
+    // (the checkpoint arrays are laid out for ONE pass: enqueue_verify builds its pass itself)
+    if (rows.kind == RowLayout::CKPT) return fail(RWKV_E_ARG, "a checkpointing pass is not cut into passes");
     const uint64_t CH = seq_pass_rows(c, T);
     const uint64_t nchunks = (T + CH - 1) / CH;
     int rc = 0;
@@ -1355,7 +1385,7 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
     // scratch, every pass in buffer 0, nothing to hand over and so no event (and no split_setup for a single pass: nothing is allocated).
     if (nchunks >= 2 && (rc = split_setup(c))) return rc;
     const int ns = nchunks >= 2 ? c->n_split : 1;
-    for (int k = 0; plan && k < ns; k++)      // the staging rows of the scratch sets this call uses
+    for (int k = 0; rows.kind == RowLayout::SEGMENTED && k < ns; k++)      // the staging rows of the scratch sets this call uses
         if (!c->sp_scratch[k].seg && (rc = dalloc(c, &c->sp_scratch[k].seg, (size_t)SEQ_TM * c->D))) return rc;
     if (ns >= 2) HIPCHK(hipEventRecord(c->sp_end, c->stream));        // the other stages start behind whatever the context's stream holds
     for (int k = 1; k < ns; k++) HIPCHK(hipStreamWaitEvent(c->sp_stream[k], c->sp_end, 0));
@@ -1368,10 +1398,9 @@ int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *
             if (k > 0) HIPCHK(hipStreamWaitEvent(st, c->sp_done[k - 1][b], 0));                    // the stage before has handed chunk i over
             else if (ns >= 2 && i >= (uint64_t)ns) HIPCHK(hipStreamWaitEvent(st, c->sp_done[ns - 1][b], 0));   // the last stage is done with this buffer (chunk i - ns)
             // (stage 0: the context's own stream and scratch)
-            const SeqPass pass{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k], b, n, t0, mode == RWKV_MODE_PARRALEL, dtok ? dtok + t0 : token_slot(c, b),
-                               nullptr, plan ? plan + t0 : nullptr};
+            const SeqPass pass{split_point(c, k, ns), split_point(c, k + 1, ns), st, &c->sp_scratch[k], b, n, t0, dtok ? dtok + t0 : token_slot(c, b), rows.from_row(t0)};
             if (pass.embeds(c) && !dtok) rc = upload_chunk_tokens(c, tokens + t0, n, b, st);
-            if (!rc) rc = (pass.par || pass.plan) ? enqueue_chunk(c, pass) : enqueue_pass(c, pass);
+            if (!rc) rc = pass.rows.replayed() ? enqueue_pass(c, pass) : enqueue_chunk(c, pass);
             if (ns >= 2) HIPCHK(hipEventRecord(c->sp_done[k][b], st));
         }
     }
@@ -1537,7 +1566,7 @@ int rwkv_forward(rwkv_ctx *c, const uint64_t *tokens, uint64_t T, int mode)
     if (const int rc = check_ids(tokens, T, "token")) return rc;
     trim_pass_graphs(c);
     if (T >= 2 && c->seq_ok && c->l0 == 0 && c->l1 == c->L)   // prompt chunks (GPT) / batched decode step of T streams (PARRALEL): weights read once per <= 64 rows
-        return finish(c, enqueue_rows(c, tokens, nullptr, T, mode));
+        return finish(c, enqueue_rows(c, tokens, nullptr, T, RowLayout::of_mode(mode)));
     return finish(c, [&]() -> int {
         for (uint64_t t = 0; t < T; t++) {
             c->h_ctl[t].token = tokens[t];
@@ -2192,7 +2221,7 @@ struct DecodeRun {
         const unsigned n = (unsigned)d.N;
         unsigned long long *to = one ? c->pick : ids + (k + 1) * n;       // where the pick writes,
         const unsigned long long *picks = one ? c->gen + k : to;          // and where what follows it reads step k's picks
-        if (const int rc = one ? run_token(c, !sampled && !cn) : enqueue_rows(c, nullptr, ids + k * n, n, RWKV_MODE_PARRALEL)) return rc;      // logits rows and state slots 0 .. N - 1
+        if (const int rc = one ? run_token(c, !sampled && !cn) : enqueue_rows(c, nullptr, ids + k * n, n, RowLayout::of_mode(RWKV_MODE_PARRALEL))) return rc;      // logits rows and state slots 0 .. N - 1
         if (const int rc = cn ? cn->rows(c, n) : 0) return rc;
         if (sampled) {
             smp.draw().step = one ? -1 : (int)k; smp.draw().pick = to;
@@ -2685,7 +2714,7 @@ int rwkv_decode_beam(rwkv_ctx *c, uint64_t first_token, uint64_t n_steps, const 
         if (const int rc = b.setup(c, *bp, n_steps, fed, cum, nullptr, 0u)) return rc;
         if (const int rc = enqueue_gather(c, b.g)) return rc;                                  // the fork: slots 1 .. W - 1 <- slot 0
         for (uint64_t k = 0; k < n_steps; k++) {
-            if (const int rc = enqueue_rows(c, nullptr, b.ids + (k & 1) * W, W, RWKV_MODE_PARRALEL)) return rc;     // logits rows 0 .. W - 1, state slots 0 .. W - 1
+            if (const int rc = enqueue_rows(c, nullptr, b.ids + (k & 1) * W, W, RowLayout::of_mode(RWKV_MODE_PARRALEL))) return rc;     // logits rows 0 .. W - 1, state slots 0 .. W - 1
             if (const int rc = b.step(c, k)) return rc;
         }
         return b.download(c, n_steps);
@@ -2837,7 +2866,7 @@ int rwkv_score(rwkv_ctx *c, const uint64_t *tokens, const uint64_t *targets, uin
         HIPCHK(hipMemcpyAsync(c->buf<void>(SC_IN), c->sc_host.data(), sizeof(unsigned long long) * up, hipMemcpyHostToDevice, c->stream));
         for (uint64_t t0 = 0, k = 0; t0 < n; t0 += P) {
             const uint64_t np = std::min(P, n - t0);
-            if (chunked(np)) { if (const int rc = enqueue_rows(c, tokens + t0, nullptr, np, RWKV_MODE_GPT)) return rc; }
+            if (chunked(np)) { if (const int rc = enqueue_rows(c, tokens + t0, nullptr, np, RowLayout::of_mode(RWKV_MODE_GPT))) return rc; }
             else
                 for (uint64_t t = 0; t < np; t++) {
                     HIPCHK(hipMemcpyAsync(c->ctl, d_ctl + k++, sizeof(Ctl), hipMemcpyDeviceToDevice, c->stream));
@@ -2878,7 +2907,7 @@ int enqueue_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t 
     if (const int rc = upload_chunk_tokens(c, rows, n, 0, c->stream)) return rc;
     double *ck = c->buf<double>(SPEC_CKPT);
     unsigned long long *drec = c->buf<unsigned long long>(SPEC_REC), *picks = drec + 2;
-    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, n, 0, false, token_slot(c, 0), ck};
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, n, 0, token_slot(c, 0), RowLayout::checkpoints(ck)};
     if (const int rc = enqueue_chunk(c, pass)) return rc;
     if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)n, picks)) return rc;
     k_spec_accept<64><<<dim3(1), dim3(64), 0, c->stream>>>(SpecAcceptArgs{token_slot(c, 0), picks, drec, (unsigned)n_draft});
@@ -3019,7 +3048,7 @@ int rwkv_forward_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_segmen
     return finish(c, [&]() -> int {
         SegRow *plan = c->buf<SegRow>(SEG_PLAN);
         HIPCHK(hipMemcpyAsync(plan, c->h_seg_plan, sizeof(SegRow) * T, hipMemcpyHostToDevice, c->stream));
-        return enqueue_rows(c, tokens, nullptr, T, RWKV_MODE_GPT, plan);
+        return enqueue_rows(c, tokens, nullptr, T, RowLayout::segments(plan));
     }());
 }
 

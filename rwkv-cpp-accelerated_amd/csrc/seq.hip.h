@@ -312,23 +312,17 @@ __device__ __forceinline__ void seq_row_stats2(const SeqStat *stat, int t, int t
 }
 // (row, octant) workgroups, one quad (4 channels) per thread: LayerNorm + shift mix of the octant, its exact max|.| per
 // vector (one workgroup reduction), quantisation into the A image.  D / 32 <= SEQ_ENT quads per octant.
-// CKPT (GPT mode only): the pass commits nothing -- every row's LayerNorm output goes to a.ckpt, what a state holds once that row is the last one
-// fed, and neither a.state_new nor a slot is written (spec.hip.h k_spec_commit copies the row that stands).
-template <int NV, bool CKPT = false>
-__global__ __launch_bounds__(SEQ_ENT) void k_seq_site(SeqSiteArgs a)
+// seq_site_row is the ONE body of every site kernel (k_seq_site here, k_seg_site in segments.hip.h), for octant o of row t of the pass.  What a row
+// layout decides comes from the kernel: whether the vectors take a token shift at all (`shift`), the shift input (`xprow`; `lnprev`: it is the
+// residual stream of the previous row and wants this site's LayerNorm, not a LayerNorm output already stored), and `keep(j, xx)`, which puts the
+// LayerNorm output of channel j where the layout keeps it.  `keep` is a functor, resolved where the kernel is compiled: no instance carries
+// another layout's branches.
+template <int NV, class Keep>
+__device__ __forceinline__ void seq_site_row(const SeqSiteArgs &a, int t, int o, bool shift, bool lnprev, const double *xprow, Keep keep, double *red)
 {
-    __shared__ double red[SEQ_ENW * 4];
-    RWKV_ARGS_NOW(a.x, a.stat, a.lnw, a.lnb, a.state, a.state_par, a.state_new, a.part);      // (see k_seq_resid)
-    if (CKPT) RWKV_ARGS_NOW(a.ckpt);
-    RWKV_ARGS_NOW(a.mix[0], a.r[0], a.o[0], a.img[0]);
-    if (NV > 1) RWKV_ARGS_NOW(a.mix[NV - 1], a.r[NV - 1], a.o[NV - 1], a.img[NV - 1], a.mix[NV > 2 ? 1 : 0], a.r[NV > 2 ? 1 : 0], a.o[NV > 2 ? 1 : 0], a.img[NV > 2 ? 1 : 0]);
-    const int D = a.D, t = blockIdx.x / SEQ_O, o = blockIdx.x % SEQ_O;      // t: row of the pass (0 .. 63)
-    const int hh = t / SEQ_T, th = t % SEQ_T;                                 // its half and the row inside the half (images, records)
+    const int D = a.D, hh = t / SEQ_T, th = t % SEQ_T;      // the row's half and the row inside the half (images, records)
     int c0, c1;
     octant_range(D, o, c0, c1);
-    const bool shift = a.mix[0] != nullptr;
-    const bool lnprev = shift && t > 0 && !a.par;   // the shift input is a LayerNorm output: of the previous row (GPT) or already stored (state)
-    const double *xprow = !shift ? a.x : a.par ? a.state_par + (size_t)(a.slot0 + t) * a.slot_stride : (t > 0 ? a.x + (size_t)(t - 1) * D : a.state);
     // both rows' statistics in ONE round trip (unconditionally: a branch around the second read is a second trip where it is taken)
     double mean, rstd, meanp, rstdp;
     seq_row_stats2(a.stat, t, lnprev ? t - 1 : t, D, mean, rstd, meanp, rstdp);
@@ -351,11 +345,8 @@ __global__ __launch_bounds__(SEQ_ENT) void k_seq_site(SeqSiteArgs a)
         for (int e = 0; e < 4; e++) {
             xx[e] = lw[e] * ((xt[e] - mean) * rstd) + lb[e];
             xprev[e] = lnprev ? lw[e] * ((xp[e] - meanp) * rstdp) + lb[e] : xp[e];
-            const int j = qd * 4 + e;
-            if (CKPT) a.ckpt[(size_t)t * D + j] = xx[e];
-            else if (a.par) a.state_par[(size_t)(a.slot0 + t) * a.slot_stride + j] = xx[e];   // own slot: read above by this thread only
-            else if (a.state_new && t == a.T - 1) a.state_new[j] = xx[e];                // mixatt / mixffn state write (:344,:385)
         }
+        keep(qd * 4, xx);
 #pragma unroll
         for (int m = 0; m < NV; m++) {
             const f32x4 rr = reinterpret_cast<const f32x4 *>(a.r[m])[qd], oo = reinterpret_cast<const f32x4 *>(a.o[m])[qd];
@@ -379,6 +370,29 @@ __global__ __launch_bounds__(SEQ_ENT) void k_seq_site(SeqSiteArgs a)
         seq_finish(ls, So[m], c1 - c0, amax[m], a.part + hh * a.part_h + ((size_t)m * SEQ_T + th) * SEQ_O + o, red);
     }
 }
+// GPT and PARRALEL rows (a.par).  CKPT (GPT mode only): the pass commits nothing -- every row's LayerNorm output goes to a.ckpt, what a state holds
+// once that row is the last one fed, and neither a.state_new nor a slot is written (spec.hip.h k_spec_commit copies the row that stands).
+template <int NV, bool CKPT = false>
+__global__ __launch_bounds__(SEQ_ENT) void k_seq_site(SeqSiteArgs a)
+{
+    __shared__ double red[SEQ_ENW * 4];
+    RWKV_ARGS_NOW(a.x, a.stat, a.lnw, a.lnb, a.state, a.state_par, a.state_new, a.part);      // (see k_seq_resid)
+    if (CKPT) RWKV_ARGS_NOW(a.ckpt);
+    RWKV_ARGS_NOW(a.mix[0], a.r[0], a.o[0], a.img[0]);
+    if (NV > 1) RWKV_ARGS_NOW(a.mix[NV - 1], a.r[NV - 1], a.o[NV - 1], a.img[NV - 1], a.mix[NV > 2 ? 1 : 0], a.r[NV > 2 ? 1 : 0], a.o[NV > 2 ? 1 : 0], a.img[NV > 2 ? 1 : 0]);
+    const int D = a.D, t = blockIdx.x / SEQ_O, o = blockIdx.x % SEQ_O;      // t: row of the pass (0 .. 63)
+    const bool shift = a.mix[0] != nullptr;
+    const bool lnprev = shift && t > 0 && !a.par;   // the shift input is a LayerNorm output: of the previous row (GPT) or already stored (state)
+    const double *xprow = !shift ? a.x : a.par ? a.state_par + (size_t)(a.slot0 + t) * a.slot_stride : (t > 0 ? a.x + (size_t)(t - 1) * D : a.state);
+    seq_site_row<NV>(a, t, o, shift, lnprev, xprow, [&](int j, const double (&xx)[4]) {
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            if (CKPT) a.ckpt[(size_t)t * D + j + e] = xx[e];
+            else if (a.par) a.state_par[(size_t)(a.slot0 + t) * a.slot_stride + j + e] = xx[e];   // own slot: read above by this thread only
+            else if (a.state_new && t == a.T - 1) a.state_new[j + e] = xx[e];                // mixatt / mixffn state write (:344,:385)
+        }
+    }, red);
+}
 
 // ------------------------------------------------------------------------------------------
 struct SeqStageArgs {
@@ -394,13 +408,11 @@ struct SeqStageArgs {
 constexpr int SEQ_SQ = 3;        // quads per thread of a stage workgroup: K / 32 <= 3 * SEQ_ENT
 // (row, octant) workgroups.  KIND 0: f = src (att_out input).  KIND 1: f = relu(k)^2 with k = ffn_k GEMM output
 // (rwkv.cu:189-190), K = 4D.  Exact max|f * r| of the octant by one workgroup reduction, then quantisation.
+// seq_stage_row is the one body, for octant o of row tg of the pass (k_seg_stage of segments.hip.h runs it behind its commit).
 template <int KIND>
-__global__ __launch_bounds__(SEQ_ENT) void k_seq_stage(SeqStageArgs a)
+__device__ __forceinline__ void seq_stage_row(const SeqStageArgs &a, int tg, int o, double *red)
 {
-    __shared__ double red[SEQ_ENW * 4];
-    RWKV_ARGS_NOW(a.src, a.pk, a.qpart_k, a.r, a.o, a.img, a.part);      // (see k_seq_resid)
-    const int K = a.K, tg = blockIdx.x / SEQ_O, o = blockIdx.x % SEQ_O;
-    const int hh = tg / SEQ_T, t = tg % SEQ_T;
+    const int K = a.K, hh = tg / SEQ_T, t = tg % SEQ_T;
     const float *pk = a.pk + hh * a.pk_h;
     int c0, c1;
     octant_range(K, o, c0, c1);
@@ -446,6 +458,13 @@ __global__ __launch_bounds__(SEQ_ENT) void k_seq_stage(SeqStageArgs a)
     }
     seq_finish(ls, So, c1 - c0, am[0], a.part + hh * a.part_h + (size_t)t * SEQ_O + o, red);
 }
+template <int KIND>
+__global__ __launch_bounds__(SEQ_ENT) void k_seq_stage(SeqStageArgs a)
+{
+    __shared__ double red[SEQ_ENW * 4];
+    RWKV_ARGS_NOW(a.src, a.pk, a.qpart_k, a.r, a.o, a.img, a.part);      // (see k_seq_resid)
+    seq_stage_row<KIND>(a, blockIdx.x / SEQ_O, blockIdx.x % SEQ_O, red);
+}
 
 // ------------------------------------------------------------------------------------------
 struct SeqWkvArgs {
@@ -462,9 +481,42 @@ struct SeqWkvArgs {
     double *ckpt_aa, *ckpt_bb;   // CKPT instance: [T][D] each, the state AFTER every row
 };
 constexpr int WKV_CH = 16;       // channels per workgroup (TCAP x 16 threads: 16 channels x the rows of the pass)
-// rwkv.cu:242-255 with the GPT-mode state slot 0.  The exponentials do not depend on the state, so
-// one thread per (row, channel) evaluates them; then one thread per channel runs the (linear) state
-// recurrence along the chunk and the outputs are finished in parallel.  TCAP = 32 (one half) or 64 rows.
+// The three pieces every WKV kernel is made of (k_seq_wkv here, k_seg_wkv in segments.hip.h), each written once.
+// (row t, channel i) of the pass: the exponentials and the gate of rwkv.cu:242-255 from the K/V/R partial values.  They do not depend on the state.
+__device__ __forceinline__ void seq_wkv_terms(const SeqWkvArgs &a, int t, int i, double &e1, double &ek, double &vv, double &sg)
+{
+    const int CB = (a.D + 15) >> 4, hh = t / SEQ_T, th = t % SEQ_T;
+    const float *pk = a.pk + hh * a.pk_h;
+    const SeqPart *qp = a.qpart + hh * a.part_h;
+    const float k = seq_val(pk, 3 * CB, 0 * CB + (i >> 4), th, i & 15, seq_so(qp, 0, th));
+    const float v = seq_val(pk, 3 * CB, 1 * CB + (i >> 4), th, i & 15, seq_so(qp, 1, th));
+    const float r = seq_val(pk, 3 * CB, 2 * CB + (i >> 4), th, i & 15, seq_so(qp, 2, th));
+    e1 = exp(a.uw[i] + (double)k);
+    ek = exp((double)k);
+    vv = (double)v;
+    sg = 1.0 / (1.0 + (double)expf(-r));       // rwkv.cu:250: exp of a float argument
+}
+// One step of the serial walk along the rows of a sequence: aa' = (aa + e^k v) e^w, bb' = (bb + e^k) e^w.  `ek_aa` holds the row's e^k and takes aa,
+// `s_bb` takes bb: the state BEFORE the row, which its output needs (the slot of e^k is free once read).
+// The step's roundings are pinned: one fma and one product for aa, one sum and one product for bb.  Left to the compiler's contraction, the
+// loop -- unrolled by eight -- fused a step's product with the NEXT step's sum, bb' + e^k' = fma(bb + e^k, e^w, e^k'), inside the unrolled body and
+// not in its remainder loop: bb after row t then depended, in the last bit, on how many rows the pass had, and a prompt fed as 5 + 5 rows differed
+// from the same prompt fed as 10.  The header's promise, rwkv_spec_verify's rollback and the bit equality of the row layouts need the state after a
+// row to be the same whatever else the pass holds (speculative decoding) -- which is why every walk calls THIS step.
+__device__ __forceinline__ void seq_wkv_step(double &aa, double &bb, double &ek_aa, const double &v, double &s_bb, double ew)
+{
+#pragma clang fp contract(off)
+    const double ek = ek_aa, vv = v;
+    ek_aa = aa;
+    s_bb = bb;
+    aa = __builtin_fma(ek, vv, aa) * ew;
+    bb = (bb + ek) * ew;
+}
+// the gated output of a row from the state before it (rwkv.cu:242-255 evaluates the same expressions in the same order per row)
+__device__ __forceinline__ float seq_wkv_out(double e1, double sg, double aa, double vv, double bb) { return (float)(sg * ((aa + e1 * vv) / (bb + e1))); }
+
+// rwkv.cu:242-255 with the GPT-mode state slot 0.  One thread per (row, channel) evaluates the terms; then one thread per channel runs the
+// (linear) state recurrence along the chunk and the outputs are finished in parallel.  TCAP = 32 (one half) or 64 rows.
 // CKPT (GPT mode only): saa / sbb are read and NOT written; the state after every row goes to ckpt_aa / ckpt_bb.  The walk already leaves the
 // state before row t in LDS, which is the state after row t - 1: one more LDS row takes the walk's final value, and the (row, channel) threads
 // store row t + 1 of that table as the state after their row.
@@ -478,20 +530,9 @@ __global__ __launch_bounds__(TCAP * WKV_CH) void k_seq_wkv(SeqWkvArgs a)
     const int ch = threadIdx.x & (WKV_CH - 1), t = threadIdx.x / WKV_CH;     // t: row of the pass
     const int i = blockIdx.x * WKV_CH + ch;
     const bool live = i < a.D && t < a.T;
-    if (live) {
-        const int CB = (a.D + 15) >> 4, hh = t / SEQ_T, th = t % SEQ_T;
-        const float *pk = a.pk + hh * a.pk_h;
-        const SeqPart *qp = a.qpart + hh * a.part_h;
-        const float k = seq_val(pk, 3 * CB, 0 * CB + (i >> 4), th, i & 15, seq_so(qp, 0, th));
-        const float v = seq_val(pk, 3 * CB, 1 * CB + (i >> 4), th, i & 15, seq_so(qp, 1, th));
-        const float r = seq_val(pk, 3 * CB, 2 * CB + (i >> 4), th, i & 15, seq_so(qp, 2, th));
-        e1s[t][ch] = exp(a.uw[i] + (double)k);
-        eks[t][ch] = exp((double)k);
-        vs[t][ch] = (double)v;
-        sgs[t][ch] = 1.0 / (1.0 + (double)expf(-r));       // rwkv.cu:250: exp of a float argument
-    }
+    if (live) seq_wkv_terms(a, t, i, e1s[t][ch], eks[t][ch], vs[t][ch], sgs[t][ch]);
     __syncthreads();
-    if (a.par) {
+    if (a.par) {      // row t is slot slot0 + t: no walk.  Its own expressions, not the pinned step (not promised bit-equal to a walk)
         if (live) {
             const size_t so = (size_t)(a.slot0 + t) * a.slot_stride + i;
             const double aa = a.saa[so], bb = a.sbb[so], ew = a.ew[i];
@@ -502,32 +543,18 @@ __global__ __launch_bounds__(TCAP * WKV_CH) void k_seq_wkv(SeqWkvArgs a)
         }
         return;
     }
-    // GPT mode: the state recurrences aa' = (aa + e^k v) e^w, bb' = (bb + e^k) e^w are LINEAR -- one thread per channel walks
-    // them along the chunk (two fma per step) and leaves the state every row sees; the divisions of all (row, channel) pairs
-    // then run in parallel (rwkv.cu:242-255 evaluates the same expressions in the same order per row)
+    // GPT mode: one thread per channel walks the state along the chunk and leaves the state every row sees; the divisions of all (row, channel)
+    // pairs then run in parallel
     if (threadIdx.x < WKV_CH && i < a.D) {
         double aa = a.saa[i], bb = a.sbb[i];
         const double ew = a.ew[i];
-        // The steps' roundings are pinned: one fma and one product for aa, one sum and one product for bb.  Left to the compiler's contraction,
-        // the loop -- unrolled by eight -- fused a step's product with the NEXT step's sum, bb' + e^k' = fma(bb + e^k, e^w, e^k'), inside the
-        // unrolled body and not in its remainder loop: bb after row t then depended, in the last bit, on how many rows the pass had, and a
-        // prompt fed as 5 + 5 rows differed from the same prompt fed as 10.  The header's promise (and rwkv_spec_verify's rollback) needs the
-        // state after a row to be the same whatever follows the row in its pass (speculative decoding).
-        for (int tt = 0; tt < a.T; tt++) {
-#pragma clang fp contract(off)
-            const double ek = eks[tt][ch], vv = vs[tt][ch];
-            eks[tt][ch] = aa;                 // state before row tt (the slot of e^k is free once read)
-            aas[tt][ch] = bb;
-            aa = __builtin_fma(ek, vv, aa) * ew;
-            bb = (bb + ek) * ew;
-        }
+        for (int tt = 0; tt < a.T; tt++) seq_wkv_step(aa, bb, eks[tt][ch], vs[tt][ch], aas[tt][ch], ew);
         if (CKPT) { eks[a.T][ch] = aa; aas[a.T][ch] = bb; }      // (a.T <= TCAP: the tables' extra row at most)
         else { a.saa[i] = aa; a.sbb[i] = bb; }
     }
     __syncthreads();
     if (live) {
-        const double e1 = e1s[t][ch];
-        a.y[(size_t)t * a.D + i] = (float)(sgs[t][ch] * ((eks[t][ch] + e1 * vs[t][ch]) / (aas[t][ch] + e1)));
+        a.y[(size_t)t * a.D + i] = seq_wkv_out(e1s[t][ch], sgs[t][ch], eks[t][ch], vs[t][ch], aas[t][ch]);
         if (CKPT) { a.ckpt_aa[(size_t)t * a.D + i] = eks[t + 1][ch]; a.ckpt_bb[(size_t)t * a.D + i] = aas[t + 1][ch]; }
     }
 }
