@@ -8,7 +8,7 @@
 The seeded synthetic model at the narrowest width that has a chunk path (L = 2, D = 64, max_ctx 8); every case starts from one fixed prompt
 state (three PARRALEL steps of 8 streams), zero counts and the automaton states it names.  One line per case: the first 16 hex digits of
 SHA-256 of ids / len / reason / steps_run, of the record arrays and the out states, of the five state arrays, the logits rows and the count
-vectors.  The grid: N in {1, 3} x pick in {greedy, typical, nucleus with penalties} x hooks in {none, stop + budget that fires, record with
+vectors.  The grid: N in {1, 3} x pick in {greedy, typical, typical recipe, nucleus with penalties} x hooks in {none, stop + budget that fires, record with
 top_n 3, constraint with a bias, all three}, the all-three case also as a KEEP continuation, and the three one-stream entry points.  Then a
 block of refused calls, each with its status and rwkv_last_error() text; most of them carry two faults at once, so the order of an entry
 point's checks shows."""
@@ -21,8 +21,9 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 L, D, CTX, STEPS, TOPN = 2, 64, 8, 12, 3
-PICKS = dict(greedy=dict(pick="greedy"), typical=dict(pick="typical", temp=0.9, tau=0.8),
-             nucleus=dict(pick="nucleus", temp=1.0, top_p=0.9, presence=0.4, frequency=0.4, decay=0.996))
+PICKS = {"greedy": dict(pick="greedy"), "typical": dict(pick="typical", temp=0.9, tau=0.8),
+         "typical recipe": dict(pick="typical", temp=0.9, tau=0.8, recipe=True),      # default mode has no select: this one runs it
+         "nucleus": dict(pick="nucleus", temp=1.0, top_p=0.9, presence=0.4, frequency=0.4, decay=0.996)}
 EDGES = 48
 
 
@@ -99,12 +100,8 @@ def run_cases():
             kw = dict(kw, seeds=seeds)
             m.constraint_clear()
             restore()
-            if pick == "greedy":
-                line(f"{tag} none", (m.decode_batch_greedy(first, STEPS),))
-            elif pick == "typical":
-                line(f"{tag} none", (m.decode_batch_typical(first, STEPS, temp=kw["temp"], tau=kw["tau"], seeds=seeds),))
-            else:
-                line(f"{tag} none", (m.decode_batch_nucleus(first, STEPS, seeds=seeds, **{k: v for k, v in PICKS[pick].items() if k != "pick"}),))
+            plain = {"greedy": m.decode_batch_greedy, "typical": m.decode_batch_typical, "nucleus": m.decode_batch_nucleus}[kw["pick"]]
+            line(f"{tag} none", (plain(first, STEPS, **({} if pick == "greedy" else {k: v for k, v in kw.items() if k != "pick"})),))
             restore()
             full = m.decode_batch_until(first, STEPS, **kw)
             line(f"{tag} until without a stop", full)
@@ -114,7 +111,7 @@ def run_cases():
             line(f"{tag} record", m.decode_batch_logprobs(first, STEPS, top_n=TOPN, **kw))
             restore()
             line(f"{tag} stop + record", m.decode_batch_logprobs(first, STEPS, top_n=TOPN, **stop_of(full), **kw))
-            if pick == "typical":
+            if kw["pick"] == "typical":
                 continue                            # typical under a constraint is a refusal: in the block below
             restore()
             line(f"{tag} constraint (implicit state) + bias", m.decode_batch_constrained(first, STEPS, bias=bias, **kw))
