@@ -20,8 +20,6 @@ exactly 0 by construction (bitwise-equal rows under equal cum, equal logits insi
 from __future__ import annotations
 
 import functools
-import os
-import subprocess
 
 import numpy as np
 
@@ -163,13 +161,3 @@ def check(label, got, want):
     if not np.all(dl <= sc.LP_TOL):
         bad.append(f"{label}: |d token logprob| {float(dl.max()):.3e} > {sc.LP_TOL}")
     return worst, bad
-
-
-def build_beam_app(outdir):
-    """tests/cpp/beam_app.cpp against include/rwkv.h and the engine library (no GPU needed to compile and link); returns the executable"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "rwkv-cpp-accelerated_amd", "csrc")
-    exe = os.path.join(outdir, "beam_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "beam_app.cpp"),
-                           "-I" + os.path.join(root, "include"), "-L" + csrc, "-lrwkv_mi355x", "-Wl,-rpath," + csrc, "-o", exe])
-    return exe

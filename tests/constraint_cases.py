@@ -6,13 +6,12 @@ Everything compared against it is compared bit for bit -- there is no tolerance 
 pick on the same numbers."""
 import os
 import re
-import subprocess
 
 import numpy as np
 
+from support import CSRC
+
 V = 50277
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
 WORDS = 1572                      # mask words per state
 
 
@@ -155,14 +154,6 @@ def trie_accepts(a, seq):
             return False
         q = int(nxt[e[0]])
     return row_ptr[q] == row_ptr[q + 1]
-
-
-def build_constrain_app(outdir):
-    """tests/cpp/constrain_app.cpp against include/rwkv.h and the engine library (no GPU needed to compile and link); returns the executable"""
-    exe = os.path.join(outdir, "constrain_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "constrain_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-L" + CSRC, "-lrwkv_mi355x", "-Wl,-rpath," + CSRC, "-o", exe])
-    return exe
 
 
 # ---- malformed inputs, by the name constraint_check gives the rule (include/rwkv_sampler.h) ----

@@ -16,8 +16,6 @@ boundary of its own, so no further rows are needed; `one_wave` below adds the wa
 from __future__ import annotations
 
 import functools
-import os
-import subprocess
 
 import numpy as np
 
@@ -98,13 +96,3 @@ def check(label, got_ids, got_lp, want_ids, want_lp):
     if not np.all(d <= sc.LP_TOL):
         bad.append(f"{label}: |d logprob| {worst:.3e} > {sc.LP_TOL}")
     return worst, bad
-
-
-def build_logprobs_app(outdir):
-    """tests/cpp/logprobs_app.cpp against include/rwkv.h and the engine library (no GPU needed to compile and link); returns the executable"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "rwkv-cpp-accelerated_amd", "csrc")
-    exe = os.path.join(outdir, "logprobs_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "logprobs_app.cpp"),
-                           "-I" + os.path.join(root, "include"), "-L" + csrc, "-lrwkv_mi355x", "-Wl,-rpath," + csrc, "-o", exe])
-    return exe

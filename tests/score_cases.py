@@ -15,8 +15,6 @@ sum e d being of one sign.  An implementation that accumulates in f32 misses by 
 from __future__ import annotations
 
 import functools
-import os
-import subprocess
 
 import numpy as np
 
@@ -109,13 +107,3 @@ def check(label, got_lp, got_ent, got_am, want_lp, want_ent, want_am):
     if not np.array_equal(np.asarray(got_am, np.int64), np.asarray(want_am, np.int64)):
         bad.append(f"{label}: argmax {np.asarray(got_am).tolist()} reference {np.asarray(want_am).tolist()}")
     return wl, we, bad
-
-
-def build_score_app(outdir):
-    """tests/cpp/score_app.cpp against include/rwkv.h and the engine library (no GPU needed to compile and link); returns the executable"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "rwkv-cpp-accelerated_amd", "csrc")
-    exe = os.path.join(outdir, "score_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "score_app.cpp"),
-                           "-I" + os.path.join(root, "include"), "-L" + csrc, "-lrwkv_mi355x", "-Wl,-rpath," + csrc, "-o", exe])
-    return exe

@@ -5,7 +5,6 @@ suite, compared with the device by the GPU suite -- and the Python statement of 
 The models are modelfile.synthetic_tensors, every context loaded with max_ctx = 80.  Widths: those of spec_cases.WIDTHS -- 64 (the smallest chunk
 width: WKV workgroups partly filled), 320 (uneven octants), 1024, and one 4096-wide two-layer case."""
 import os
-import subprocess
 
 import numpy as np
 
@@ -106,16 +105,6 @@ def mix77_digests(eng):
         out[D] = digest(m, ROWS["MIX77"])
         m.close()
     return out
-
-
-def build_segments_app(outdir):
-    """tests/cpp/segments_app.cpp against include/rwkv.h and the engine library (no GPU needed to compile and link); returns the executable"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "rwkv-cpp-accelerated_amd", "csrc")
-    exe = os.path.join(outdir, "segments_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "segments_app.cpp"),
-                           "-I" + os.path.join(root, "include"), "-L" + csrc, "-lrwkv_mi355x", "-Wl,-rpath," + csrc, "-o", exe])
-    return exe
 
 
 if __name__ == "__main__":      # the child process of tests/test_segments_gpu.py: "D digest" per width, under the environment it was given

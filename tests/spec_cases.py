@@ -4,8 +4,6 @@ the CPU oracle by the CPU suite, compared with the device by the GPU suite.
 
 The models are modelfile.synthetic_tensors, three layers deep, every context loaded with max_ctx = 34.  Widths: 64 (the smallest chunk width:
 octants of 8 channels, WKV workgroups partly filled), 320 (no power of two, uneven octants), 1024, and one 4096-wide two-layer case."""
-import os
-import subprocess
 
 import numpy as np
 
@@ -118,13 +116,3 @@ def edge_tensors(L, D, seed):
     h[0, : V - 1] = np.minimum(h[0, : V - 1], 254)
     t[mf.HEAD] = h.reshape(-1)
     return t
-
-
-def build_spec_app(outdir):
-    """tests/cpp/spec_app.cpp against include/rwkv.h and the engine library (no GPU needed to compile and link); returns the executable"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    csrc = os.path.join(root, "rwkv-cpp-accelerated_amd", "csrc")
-    exe = os.path.join(outdir, "spec_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(root, "tests", "cpp", "spec_app.cpp"),
-                           "-I" + os.path.join(root, "include"), "-L" + csrc, "-lrwkv_mi355x", "-Wl,-rpath," + csrc, "-o", exe])
-    return exe

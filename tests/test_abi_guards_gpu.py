@@ -8,14 +8,13 @@ One table: entry point, arguments, status, a piece of rwkv_last_error().  The co
 feeds a bad value to a kernel: where an entry point has no check for a value, the table has no case for it."""
 import ctypes as C
 
-import numpy as np
 import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
+from support import E_ARG, E_IO, E_STATE, GuardContexts, V, check_refused, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E_ARG, E_IO, E_STATE = -1, -2, -4
-L, D, MAXT, V = 2, 64, 8, mf.VOCAB
+L, D, MAXT = 2, 64, 8
 u64 = C.c_uint64
 
 
@@ -270,52 +269,9 @@ def _case_id(i):
     return f"{i:03d}-{entry[5:]}-{args[0] if isinstance(args[0], str) else 'null'}"
 
 
-class Ctx:
-    FIRST, N = 11, 4
-
-    def __init__(self, eng):
-        self.lib = eng.lib()
-        t = mf.synthetic_tensors(L, D, seed=4100)
-        self.models = dict(M=eng.RWKV(resident=True), U=eng.RWKV(resident=True), S=eng.RWKV(resident=True), P=eng.RWKV(resident=True))
-        self.models["M"].loadTensors(L, D, t, maxGPT=MAXT)
-        self.models["S"].set_layer_range(0, 1)
-        self.models["S"].loadTensors(L, D, t, maxGPT=MAXT)
-        self.models["P"].loadTensors(L, D, t, maxGPT=32)
-        self.models["P"].pipe_init(eng.RWKV.pipe_unique_id(), 0, 1)
-        self.h = {k: m._h for k, m in self.models.items()}
-        m = self.models["M"]
-        m.forward([5, 40000, 77, 9, 1234], eng.MODE_PARRALEL)         # a history on slots 0 .. 4
-        m.forward([7, 50000, 11], eng.MODE_GPT)                       # and three logits rows
-        self.state0, _ = self.snapshot()
-        self.ids0 = self.decode()
-        self.restore()
-
-    def snapshot(self):
-        st = [np.zeros(MAXT * L * D) for _ in range(5)]
-        lg = np.zeros(MAXT * V, np.float32)
-        ptr = lambda x: C.c_void_p(x.ctypes.data)
-        assert self.lib.rwkv_get_output(self.h["M"], ptr(lg), *[ptr(s) for s in st], MAXT) == 0
-        return [s.view(np.uint64) for s in st], lg.view(np.uint32)
-
-    def decode(self):
-        out = (u64 * self.N)()
-        assert self.lib.rwkv_decode_greedy(self.h["M"], self.FIRST, self.N, out) == 0, self.lib.rwkv_last_error()
-        return list(out)
-
-    def restore(self):
-        assert self.lib.rwkv_set_state(self.h["M"], *[C.c_void_p(s.ctypes.data) for s in self.state0], MAXT) == 0
-
-    def close(self):
-        for m in self.models.values():
-            m.close()
-
-
 @pytest.fixture(scope="module")
-def ctx(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    x = Ctx(engine)
+def ctx(eng):
+    x = GuardContexts(eng, L, D, MAXT, extra=("P",))
     yield x
     x.close()
 
@@ -323,15 +279,4 @@ def ctx(built):
 @pytest.mark.parametrize("i", range(len(CASES)), ids=_case_id)
 def test_a_refused_call_answers_its_status_and_launches_nothing(ctx, i):
     entry, args, status, text = CASES[i]
-    state, logits = ctx.snapshot()
-    rc = int(getattr(ctx.lib, entry)(*[ctx.h[v] if isinstance(v, str) else v for v in args]))
-    err = ctx.lib.rwkv_last_error().decode()
-    print(f"{entry}: status {rc}, {err!r}")
-    assert rc == status, err
-    assert text in err, err
-    state1, logits1 = ctx.snapshot()
-    for name, x, y in zip("xy aa bb pp dd".split(), state, state1):
-        assert np.array_equal(x, y), name
-    assert np.array_equal(logits, logits1)
-    assert ctx.decode() == ctx.ids0
-    ctx.restore()
+    check_refused(ctx, entry, [ctx.h[v] if isinstance(v, str) else v for v in args], status, text)

@@ -1,23 +1,18 @@
 """The batched decode through the C++ drop-in header include/rwkv.h (decodeBatchGreedy / decodeBatchTypical / copyState):
 tests/cpp/batch_app.cpp compiles and links on a box without a GPU; on the GPU box its ids equal the Python engine's."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
+from support import build_app, run_app
 
 
 @pytest.fixture(scope="module")
 def batch_app(built, tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("cpp") / "batch_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "batch_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-L" + CSRC, "-lrwkv_mi355x", "-Wl,-rpath," + CSRC, "-o", exe])
-    return exe
+    return build_app("batch_app", tmp_path_factory.mktemp("cpp"))
 
 
 def test_batch_app_compiles_and_links(batch_app):
@@ -40,9 +35,8 @@ def test_batch_app_matches_python_engine(batch_app, tmp_path):
     t = mf.synthetic_tensors(L, D, seed=31, head_scale=30.0)
     p = str(tmp_path / "model.bin")
     mf.write_bin(p, L, D, t)
-    out = subprocess.run([batch_app, p, str(n), str(steps)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(batch_app, [p, n, steps])
+    assert rc == 0, raw
     assert lines[-1] == "batch_ok"
     rows = np.array([[int(x) for x in l.split()] for l in lines[-1 - 2 * n:-1]], np.int64)
     m = engine.RWKV(resident=True)

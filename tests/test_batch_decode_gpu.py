@@ -10,20 +10,12 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
+from sampler_cases import splitmix_u
+from support import E_ARG, E_STATE, eng, load, restore, snapshot, start_state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 L, D, MAXN = 3, 256, 96          # three layers: a call of more than 64 rows runs the three-stage pipeline
-E_ARG, E_STATE = -1, -4
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
 
 
 @pytest.fixture(scope="module")
@@ -33,39 +25,9 @@ def tensors():
 
 @pytest.fixture(scope="module")
 def model(eng, tensors):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, tensors, maxGPT=MAXN)
+    m = load(eng, L, D, 21, MAXN, tensors)
     yield m
     m.close()
-
-
-def splitmix_u(seed, step):
-    m = (1 << 64) - 1
-    x = (seed + step + 0x9E3779B97F4A7C15) & m
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
-    x ^= x >> 31
-    return (x >> 11) / 9007199254740992.0
-
-
-def snapshot(m, n=MAXN):
-    m.pull_state(n)
-    return [a[: n * L * D].copy() for a in m.state.arrays()]
-
-
-def restore(m, snap, n=MAXN):
-    for a, s in zip(m.state.arrays(), snap):
-        a[: n * L * D] = s
-    m.push_state(n)
-
-
-def histories(eng, m, n=MAXN):
-    """distinct state in every slot: a few PARRALEL steps of different tokens"""
-    m.reset_state()
-    rng = np.random.default_rng(5)
-    for _ in range(3):
-        m.forward([int(v) for v in rng.integers(1, mf.VOCAB, n)], eng.MODE_PARRALEL)
-    return snapshot(m, n)
 
 
 def host_greedy(eng, m, first, n_steps):
@@ -93,7 +55,7 @@ def first_tokens(n, seed=3):
 @pytest.mark.parametrize("n", [2, 32, 64, 96])
 def test_greedy_equals_host_loop_bit_for_bit(eng, model, n):
     m, steps = model, 6
-    snap = histories(eng, m)
+    snap = start_state(eng, m, MAXN)
     first = first_tokens(n)
     got = m.decode_batch_greedy(first, steps).astype(np.int64)
     dev_state = snapshot(m, n)
@@ -110,7 +72,7 @@ def test_greedy_equals_host_loop_bit_for_bit(eng, model, n):
 @pytest.mark.parametrize("recipe", [False, True])
 def test_typical_equals_host_loop(eng, model, recipe):
     m, n, steps, temp, tau = model, 40, 5, 0.45, 0.8
-    snap = histories(eng, m)
+    snap = start_state(eng, m, MAXN)
     first, seeds = first_tokens(n, 4), [1000 + 7 * s for s in range(n)]
     got = m.decode_batch_typical(first, steps, temp=temp, tau=tau, seeds=seeds, recipe=recipe).astype(np.int64)
     dev_state = snapshot(m, n)
@@ -123,7 +85,7 @@ def test_typical_equals_host_loop(eng, model, recipe):
 
 def test_streams_are_isolated(eng, model):
     m, steps = model, 5
-    snap = histories(eng, m)
+    snap = start_state(eng, m, MAXN)
     first, seeds = first_tokens(8, 6), list(range(50, 58))
     g8 = m.decode_batch_greedy(first, steps); restore(m, snap)
     g4 = m.decode_batch_greedy(first[:4], steps); restore(m, snap)
@@ -169,12 +131,12 @@ def test_one_stream_is_the_decode_loop(eng, model):
     m.reset_state(); m.forward([5, 6, 7], eng.MODE_GPT)
     snap = snapshot(m, 1)
     got = m.decode_batch_greedy([42], steps)[0]
-    restore(m, snap, 1)
+    restore(m, snap)
     assert np.array_equal(got, m.decode_greedy(42, steps))
     for recipe in (False, True):
-        restore(m, snap, 1)
+        restore(m, snap)
         got = m.decode_batch_typical([42], steps, temp=0.45, seeds=[77], recipe=recipe)[0]
-        restore(m, snap, 1)
+        restore(m, snap)
         assert np.array_equal(got, m.decode_typical(42, steps, temp=0.45, seed=77, recipe=recipe))
 
 
@@ -185,16 +147,15 @@ def test_fork_a_prompt_into_slots(eng, model):
     for s in range(1, n):
         m.copy_state(s, 0)
     snap = snapshot(m, n)
-    per = L * D
     for a in snap:
         for s in range(1, n):
-            assert np.array_equal(a[s * per:(s + 1) * per], a[:per])
+            assert np.array_equal(a[s], a[0])
     g = m.decode_batch_greedy([500] * n, steps)
     assert all(np.array_equal(g[s], g[0]) for s in range(n))
-    restore(m, snap, n)
+    restore(m, snap)
     t = m.decode_batch_typical([500] * n, steps, temp=1.0, tau=0.9, seeds=list(range(n)))
     assert not all(np.array_equal(t[s], t[0]) for s in range(n))
-    restore(m, snap, n)
+    restore(m, snap)
     assert np.array_equal(t, m.decode_batch_typical([500] * n, steps, temp=1.0, tau=0.9, seeds=list(range(n))))
 
 
@@ -205,8 +166,8 @@ def _status(fn, *args):
 def test_rejected_calls_leave_the_state_alone(eng, model, tensors):
     lib, m = eng.lib(), model
     u64 = C.c_uint64
-    histories(eng, m, 4)
-    before = snapshot(m)
+    start_state(eng, m, 4)
+    before = snapshot(m, MAXN)
     out = (u64 * 4096)()
     ft = lambda *v: (u64 * len(v))(*v)
     seeds = ft(1, 2, 3, 4)
@@ -224,7 +185,7 @@ def test_rejected_calls_leave_the_state_alone(eng, model, tensors):
         assert T(ft(1, 2), 2, 4, temp=bad) == E_ARG
     assert _status(lib.rwkv_state_copy, m._h, MAXN, 0) == E_ARG
     assert _status(lib.rwkv_state_copy, m._h, 0, MAXN) == E_ARG
-    for a, b in zip(before, snapshot(m)):
+    for a, b in zip(before, snapshot(m, MAXN)):
         assert np.array_equal(a, b)
     # not loaded
     e = eng.RWKV(resident=True)

@@ -6,25 +6,14 @@ reference alone.  (rwkv_create needs a device, so the status codes of a context 
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import beam_cases as bc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
-E_ARG = -1
+from support import E_ARG, ROOT, build_app, rwkv_mod  # noqa: F401
 V = bc.V
-
-
-@pytest.fixture(scope="module")
-def rwkv_mod(built):
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
-    return rwkv
 
 
 def twin(rwkv_mod, name, r):
@@ -73,7 +62,7 @@ def test_pybind_module_has_the_beam_functions(rwkv_mod):
 
 
 def test_beam_app_compiles_and_links(built, tmp_path):
-    app = bc.build_beam_app(str(tmp_path))
+    app = build_app("beam_app", tmp_path)
     syms = subprocess.run(["nm", "-D", "--undefined-only", app], capture_output=True, text=True).stdout
     assert "rwkv_decode_beam" in syms and "rwkv_state_permute" in syms
 

@@ -6,56 +6,23 @@ copy_state forks, then per step forward(PARRALEL), topn_rows(W + 1), the host tw
 a stop id; rejected calls; buffer accounting; the C++ and pybind bindings.  Every context is a synthetic 2-layer model.
 Each planted case prints its worst figure before anything is asserted."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import beam_cases as bc
 import logprob_cases as lc
-import sampler_cases
+import support
+from support import E_ARG, E_STATE, V, build_app, eng, load, restore, run_app, rwkv_mod, same_bits, start_state  # noqa: F401
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
 L = 2
 ROWS = 16                        # maxGPT of the planted context: W = 16 needs 16 rows (rows 0 .. 3 start at the four offsets from a 16-byte boundary)
 D_LOOP, MAXN, STEPS = 128, 8, 12
-E_ARG, E_STATE = -1, -4
-V = mf.VOCAB
 NINF = -np.inf
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-@pytest.fixture(scope="module")
-def rwkv_mod(built):
-    sys.path.insert(0, CSRC)
-    import rwkv
-    return rwkv
-
-
-def load(eng, D, max_ctx, seed, **kw):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=seed, **kw), maxGPT=max_ctx)
-    return m
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def plant_state(m, seed):
@@ -86,18 +53,15 @@ def check_gather(m, old, parents, logits=None):
 # ---- planted select -----------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def planted(eng):
-    m = load(eng, 64, ROWS, 3)
+    m = load(eng, L, 64, 3, ROWS)
     m.forward(5)
     yield m
     m.close()
 
 
 def plant(m, rows):
-    import torch
-    view = sampler_cases.logits_view(m, ROWS)
-    for r, name in enumerate(rows):
-        view[r].copy_(torch.from_numpy(np.array(lc.logits_of(name), np.float32)).cuda())      # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
+    """rows: the case names of rows 0 .. W - 1"""
+    support.plant_rows(m, {r: lc.logits_of(name) for r, name in enumerate(rows)}, ROWS)
 
 
 @pytest.mark.parametrize("name,r", bc.case_shifts())
@@ -138,7 +102,7 @@ MAPS = dict(identity=list(range(8)), swap=[1, 0, 2, 3, 4, 5, 6, 7], cycle3=[0, 1
 
 @pytest.mark.parametrize("D", [64, 80, 128])
 def test_state_permute_moves_every_slot_at_once(eng, D):
-    m = load(eng, D, 8, 21)
+    m = load(eng, L, D, 21, 8)
     m.forward([5, 6, 7] if D != 80 else 5, eng.MODE_GPT)
     logits = m.logits(8).copy()
     for k, (name, parents) in enumerate(MAPS.items()):
@@ -158,7 +122,7 @@ def test_state_permute_moves_every_slot_at_once(eng, D):
 # ---- the loop against the caller's loop it stands for --------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model(eng):
-    m = load(eng, D_LOOP, MAXN, 41, head_scale=30.0)
+    m = load(eng, L, D_LOOP, 41, MAXN, head_scale=30.0)
     yield m
     m.close()
 
@@ -166,18 +130,7 @@ def model(eng):
 @pytest.fixture(scope="module")
 def start(eng, model):
     """distinct state in every slot: where every run of the loop tests starts"""
-    model.reset_state()
-    rng = np.random.default_rng(5)
-    for _ in range(3):
-        model.forward([int(v) for v in rng.integers(1, V, MAXN)], eng.MODE_PARRALEL)
-    model.pull_state(MAXN)
-    return [a.copy() for a in model.state.arrays()]
-
-
-def restore(m, snap):
-    for a, s in zip(m.state.arrays(), snap):
-        a[:] = s
-    m.push_state(MAXN)
+    return start_state(eng, model, MAXN)
 
 
 def callers_loop(eng, rwkv_mod, m, first, steps, W, stops):
@@ -224,7 +177,7 @@ def run_both(eng, rwkv_mod, m, start, W, stops=()):
     live = [h for h in range(W) if not want[4][h]]
     for a, b, s in zip(got_state, want_state, start):
         assert same_bits(a[live], b[live])                                               # a live hypothesis's slot: every token but the last fed
-        assert same_bits(a[W:], s.reshape(MAXN, -1)[W:])                                 # a call of width W leaves slots >= W alone
+        assert same_bits(a[W:], s.view(np.float64)[W:])                                 # a call of width W leaves slots >= W alone
     for h in range(W):
         assert not tokens[h, ln[h]:].any() and not tlp[h, ln[h]:].any() and (tokens[h, : ln[h]] > 0).all()
         run = 0.0
@@ -319,7 +272,7 @@ def test_rejected_calls_leave_everything_alone(eng, model, start):
         check_gather(e, old, [2, 0, 1])
         e.close()
     # a context without the chunk path does not search
-    e = load(eng, 48, 4, 42)
+    e = load(eng, L, 48, 42, 4)
     assert beam(h=e._h) == E_STATE
     e.close()
 
@@ -334,7 +287,7 @@ def beam_bytes(W, steps, D):
 
 def test_the_buffers_are_counted(eng):
     D = 64
-    m = load(eng, D, 8, 9)
+    m = load(eng, L, D, 9, 8)
     m.forward([5, 6, 7, 8, 9, 10, 11, 12], eng.MODE_PARRALEL)
     base = m.resident_bytes()
     m.decode_beam(5, 6, 4)
@@ -350,7 +303,7 @@ def test_the_buffers_are_counted(eng):
     m.decode_beam(5, 9, 4)
     assert m.resident_bytes() - r2 == beam_bytes(4, 9, D)[0] - beam_bytes(4, 6, D)[0]
     m.close()
-    m = load(eng, D, 8, 9)                                                   # the gather alone: the map and the staging buffer
+    m = load(eng, L, D, 9, 8)                                                # the gather alone: the map and the staging buffer
     base = m.resident_bytes()
     m.state_permute([2, 0, 1])
     assert m.resident_bytes() - base == 8 * 2 + 40 * 3 * L * D
@@ -360,9 +313,7 @@ def test_the_buffers_are_counted(eng):
 # ---- bindings -----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model_file(tmp_path_factory):
-    p = str(tmp_path_factory.mktemp("beam") / "model.bin")
-    mf.write_bin(p, L, D_LOOP, mf.synthetic_tensors(L, D_LOOP, seed=43, head_scale=30.0))
-    return p
+    return support.model_file(tmp_path_factory, "beam", L, D_LOOP, 43, head_scale=30.0)
 
 
 def test_beam_app_matches_the_python_engine(eng, built, model_file, tmp_path):
@@ -376,10 +327,9 @@ def test_beam_app_matches_the_python_engine(eng, built, model_file, tmp_path):
     m.forward([5, 6, 7], eng.MODE_GPT)
     tokens, ln, score, tlp = m.decode_beam(100, steps, W, [stop])
     m.close()
-    app = bc.build_beam_app(str(tmp_path))
-    out = subprocess.run([app, model_file, str(W), str(steps), str(stop)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l.split() for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(build_app("beam_app", tmp_path), [model_file, W, steps, stop])
+    assert rc == 0, raw
+    lines = [l.split() for l in lines]
     assert lines[-1] == ["beam_ok"] and len(lines) == W + 1
     hx = float.fromhex
     for f in lines[:W]:

@@ -2,12 +2,12 @@
 that turns a parity failure anywhere in the line into a non-zero exit, and the source digests that key the committed counter
 figures (a figure measured on other sources must read as "none on record", never as this tree's)."""
 import json
-import os
 import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT
+
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 

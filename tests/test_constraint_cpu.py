@@ -6,30 +6,15 @@ preloaded).  (rwkv_create needs a device, so the status codes of a context are c
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import constraint_cases as cc
 
-ROOT = cc.ROOT
-CSRC = cc.CSRC
-E_ARG = -1
+from support import CSRC, E_ARG, ROOT, build_app, rwkv_mod, same_bits  # noqa: F401
+
 V = cc.V
-
-
-@pytest.fixture(scope="module")
-def rwkv_mod(built):
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
-    return rwkv
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
 
 
 def test_entry_points_are_declared_exported_and_bound(built):
@@ -83,7 +68,7 @@ def test_pybind_module_has_the_constraint_functions(rwkv_mod):
 
 
 def test_constrain_app_compiles_and_links(built, tmp_path):
-    app = cc.build_constrain_app(str(tmp_path))
+    app = build_app("constrain_app", tmp_path)
     syms = subprocess.run(["nm", "-D", "--undefined-only", app], capture_output=True, text=True).stdout
     assert "rwkv_constraint_set" in syms and "rwkv_decode_batch_constrained" in syms and "rwkv_pick_constrained" in syms
 

@@ -6,48 +6,27 @@ host advance), against rwkv_decode_batch_until under an allow-everything automat
 a KEEP continuation, the log-prob hook, rejected calls, accounting and the C++ / pybind bindings.  Every context is a synthetic 2-layer model.
 No tolerance anywhere: the constrained pick is the existing pick on the same numbers."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import constraint_cases as cc
 import sampler_cases
-
-from rwkv_cpp_accelerated_amd import modelfile as mf
+import support
+from support import E_ARG, E_STATE, V, build_app, eng, firsts_of, load, plant_rows, restore, run_app, rwkv_mod, same_bits, seeds_of, slots, start_state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-CSRC = cc.CSRC
 L = 2
 ROWS = 4                         # maxGPT of the planted context: rows 0 .. 3 start at the four offsets from a 16-byte boundary
 D_LOOP, MAXN, STEPS = 128, 5, 12
-E_ARG, E_STATE = -1, -4
 NUC = dict(temp=1.0, top_p=0.9, presence=0.4, frequency=0.4, decay=0.996)      # nucleus with penalties: the counts are part of a slot
 KW = dict(greedy=dict(pick="greedy"), nucleus=dict(pick="nucleus", **NUC))
-V = cc.V
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-def load(eng, D, max_ctx, seed, **kw):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=seed, **kw), maxGPT=max_ctx)
-    return m
 
 
 @pytest.fixture(scope="module")
 def planted(eng):
-    m = load(eng, 64, ROWS, 3)
+    m = load(eng, L, 64, 3, ROWS)
     m.forward(5)
     m.constraint_set(*cc.planted_automaton())
     yield m
@@ -56,7 +35,7 @@ def planted(eng):
 
 @pytest.fixture(scope="module")
 def model(eng):
-    m = load(eng, D_LOOP, MAXN, 41, head_scale=30.0)
+    m = load(eng, L, D_LOOP, 41, MAXN, head_scale=30.0)
     yield m
     m.close()
 
@@ -64,50 +43,7 @@ def model(eng):
 @pytest.fixture(scope="module")
 def start(eng, model):
     """distinct state in every slot: where every run of the loop tests starts"""
-    model.reset_state()
-    rng = np.random.default_rng(5)
-    for _ in range(3):
-        model.forward([int(v) for v in rng.integers(1, V, MAXN)], eng.MODE_PARRALEL)
-    model.pull_state(MAXN)
-    return [a.copy() for a in model.state.arrays()]
-
-
-def restore(m, snap):
-    for a, s in zip(m.state.arrays(), snap):
-        a[:] = s
-    m.push_state(MAXN)
-
-
-def slots(m, n, counts):
-    """per slot: the five state arrays [n][L D], the logits rows [n][V] and (counts) the count vectors [n][V]"""
-    m.pull_state(n)
-    out = [a[: n * L * D_LOOP].reshape(n, L * D_LOOP).copy() for a in m.state.arrays()]
-    out.append(m.logits(n).reshape(n, V).copy())
-    if counts:
-        out.append(np.stack([m.penalty_get(s) for s in range(n)]))
-    return out
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def firsts_of(n):
-    return [int(v) for v in np.random.default_rng(3).integers(1, V, n)]
-
-
-def seeds_of(n):
-    return [1000 + 7 * s for s in range(n)]
-
-
-def plant(m, rows, n=ROWS):
-    """rows: {logits row: f32 [V]}"""
-    import torch
-    view = sampler_cases.logits_view(m, n)
-    for r, l in rows.items():
-        view[r].copy_(torch.from_numpy(np.array(l, np.float32)).cuda())
-    torch.cuda.synchronize()
+    return start_state(eng, model, MAXN)
 
 
 # ---- planted rows through rwkv_pick_constrained -----------------------------------------------------------------------------------
@@ -116,7 +52,7 @@ def test_greedy_pick_on_each_of_the_four_row_alignments(planted, name):
     m, a, q = planted, cc.planted_automaton(), cc.PLANTED_STATES[name]
     mask = cc.allowed_mask(a, q)
     rows = {r: cc.planted_row(mask, 10 * q + r) for r in range(ROWS)}
-    plant(m, rows)
+    plant_rows(m, rows, ROWS)
     m.constraint_state_set([q] * ROWS)
     before = m.logits(ROWS).copy()
     for r in range(ROWS):
@@ -133,7 +69,7 @@ def test_bias_cases(planted):
     m, a = planted, cc.planted_automaton()
     every, triple = cc.allowed_mask(a, cc.P_ALL), cc.allowed_mask(a, cc.P_TRIPLE)
     rows = {r: cc.planted_row(triple, 77 + r) for r in range(ROWS)}                         # the best of 31, 32, 33 lies 50 below every other id
-    plant(m, rows)
+    plant_rows(m, rows, ROWS)
     before = m.logits(ROWS).copy()
     for r in range(ROWS):
         l = rows[r]
@@ -173,9 +109,9 @@ def test_nucleus_pick_is_sample_nucleus_on_the_planted_constrained_row(planted, 
         m.penalty_set(r, counts if penalty else None)
     for r in range(ROWS):
         c = cc.constrained(rows[r], mask, bias)
-        plant(m, {r: c})                                                                    # the existing kernel on the same numbers ...
+        plant_rows(m, {r: c}, ROWS)                                                         # the existing kernel on the same numbers ...
         ref = [m.sample_nucleus(u=u, row=r, slot=r, ban0=False, **kw) for u in (0.0, 0.25, 0.5, 0.999999)]
-        plant(m, {r: rows[r]})                                                              # ... and the model's row back
+        plant_rows(m, {r: rows[r]}, ROWS)                                                   # ... and the model's row back
         got = [m.pick_constrained("nucleus", bias=bias, u=u, row=r, slot=r, advance=False, **kw)[0] for u in (0.0, 0.25, 0.5, 0.999999)]
         print(f"{name:>11} row {r} penalty {penalty}: {got}")
         assert got == ref and all(mask[g] for g in got), (name, r, got, ref)
@@ -192,7 +128,7 @@ def test_advance(planted):
         l = np.zeros(V, np.float32)
         l[g] = 9.0                                                                          # the winner among whatever q allows
         for r in (0, 3):
-            plant(m, {r: l})
+            plant_rows(m, {r: l}, ROWS)
             m.constraint_state_set([q] * ROWS)
             assert m.pick_constrained("greedy", row=r, slot=r, advance=False) == (g, q)
             assert m.constraint_state_get().tolist() == [q] * ROWS                          # advance = 0 leaves q alone
@@ -222,11 +158,11 @@ def callers_loop(eng, m, a, first, seeds, kind, steps, start_q, bias=None):
         rows = m.logits(n).reshape(n, V).copy()
         c = [cc.constrained(rows[s], cc.allowed_mask(a, q[s]), bias[s] if bias else None) for s in range(n)]
         if kind == "nucleus":
-            plant(m, {s: c[s] for s in range(n)}, MAXN)
+            plant_rows(m, {s: c[s] for s in range(n)}, MAXN)
             for s in range(n):
                 u = sampler_cases.splitmix_u(seeds[s], k)
                 ids[s, k] = m.sample_nucleus(u=u, row=s, slot=s, ban0=False, update=True, **NUC)
-            plant(m, {s: rows[s] for s in range(n)}, MAXN)
+            plant_rows(m, {s: rows[s] for s in range(n)}, MAXN)
         else:
             ids[:, k] = [cc.argmax_low(c[s]) for s in range(n)]
         lp[:, k], _, _ = m.score_rows(list(range(n)), ids[:, k].tolist())
@@ -428,7 +364,7 @@ def test_rejected_calls_leave_everything_alone(eng, model, start):
     e = eng.RWKV(resident=True)
     assert lib_rc(eng, e, first, 4) == E_STATE
     e.close()
-    e = load(eng, 48, 3, 42)
+    e = load(eng, L, 48, 42, 3)
     assert lib_rc(eng, e, first, 4) == E_STATE and lib_rc(eng, e, [5], 4) == 0
     e.close()
     m.constraint_clear()
@@ -438,7 +374,7 @@ def test_rejected_calls_leave_everything_alone(eng, model, start):
 # ---- accounting -------------------------------------------------------------------------------------------------------------------
 def test_the_buffers_are_counted_and_a_plain_until_call_allocates_nothing_new(eng):
     D, n, maxn = 64, 4, 8
-    m = load(eng, D, maxn, 9)
+    m = load(eng, L, D, 9, maxn)
     a = cc.loop_automaton()
     S, nnz = len(a[0]) - 1, len(a[1])
     r0 = m.resident_bytes()
@@ -459,17 +395,14 @@ def test_the_buffers_are_counted_and_a_plain_until_call_allocates_nothing_new(en
 # ---- bindings -----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model_file(tmp_path_factory):
-    p = str(tmp_path_factory.mktemp("constrain") / "model.bin")
-    mf.write_bin(p, L, D_LOOP, mf.synthetic_tensors(L, D_LOOP, seed=43, head_scale=30.0))
-    return p
+    return support.model_file(tmp_path_factory, "constrain", L, D_LOOP, 43, head_scale=30.0)
 
 
 def test_constrain_app_matches_the_python_engine(eng, built, model_file, tmp_path):
     n, steps = 3, 6
-    app = cc.build_constrain_app(str(tmp_path))
-    out = subprocess.run([app, model_file, str(n), str(steps)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l.split() for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(build_app("constrain_app", tmp_path), [model_file, n, steps])
+    assert rc == 0, raw
+    lines = [l.split() for l in lines]
     assert lines[-1] == ["constrain_ok"] and len(lines) == 2 * n + 2
     m = eng.RWKV(resident=True)
     m.loadFile(model_file, n)
@@ -492,9 +425,8 @@ def test_constrain_app_matches_the_python_engine(eng, built, model_file, tmp_pat
     assert lines[-2] == ["pick", str(pick[0]), str(pick[1])]
 
 
-def test_pybind_decode_constrained_matches_the_python_engine(eng, built, model_file):
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_decode_constrained_matches_the_python_engine(eng, rwkv_mod, model_file):
+    rwkv = rwkv_mod
     a = eng.constraint_trie(cc.CHOICES)
     h = rwkv.initRwkv()
     rwkv.loadModel(h, model_file)

@@ -1,7 +1,5 @@
 """The C++ drop-in header include/rwkv.h (class RWKV / RWKVState over the C-ABI) and the pybind module `rwkv`."""
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -9,28 +7,22 @@ import pytest
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
+from support import build_app, run_app, rwkv_mod  # noqa: F401
 
 
 @pytest.fixture(scope="module")
 def app(built, tmp_path_factory):
     """compiles on a box without a GPU: proves the header is self-contained and links against the C-ABI"""
-    exe = str(tmp_path_factory.mktemp("cpp") / "greedy_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "greedy_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-L" + CSRC, "-lrwkv_mi355x", "-Wl,-rpath," + CSRC, "-o", exe])
-    return exe
+    return build_app("greedy_app", tmp_path_factory.mktemp("cpp"))
 
 
 def test_cpp_header_compiles_and_links(app):
     assert os.path.exists(app)
 
 
-def test_pybind_module_surface(built):
+def test_pybind_module_surface(rwkv_mod):
     """all 11 names of bindings/pybind/c_binding.cpp:158-175: the 8 model functions and the 3 tokenizer forwards"""
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
+    rwkv = rwkv_mod
     for f in ("initRwkv", "loadModel", "modelForward", "initState", "getState", "initOutput", "getOutput", "typicalSample"):
         assert hasattr(rwkv, f), f
 
@@ -42,9 +34,8 @@ def test_cpp_app_matches_python_engine(app, tmp_path):
     t = mf.synthetic_tensors(L, D, seed=77)
     p = str(tmp_path / "model.bin")
     mf.write_bin(p, L, D, t)
-    out = subprocess.run([app, p, "42", "12"], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(app, [p, 42, 12])
+    assert rc == 0, raw
     ids = [int(x) for x in lines[-2].split()]
     assert lines[-1].startswith("state_ok")
     m = engine.RWKV(resident=True); m.loadFile(p, 2)
@@ -57,9 +48,8 @@ def test_cpp_app_matches_python_engine(app, tmp_path):
 
 
 @pytest.mark.gpu
-def test_pybind_module_forward(built, tmp_path):
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_module_forward(rwkv_mod, tmp_path):
+    rwkv = rwkv_mod
     from rwkv_cpp_accelerated_amd import engine
     L, D = 2, 768
     t = mf.synthetic_tensors(L, D, seed=78)
@@ -86,11 +76,10 @@ def test_pybind_module_forward(built, tmp_path):
 
 
 @pytest.mark.gpu
-def test_pybind_module_two_models_side_by_side(built, tmp_path):
+def test_pybind_module_two_models_side_by_side(rwkv_mod, tmp_path):
     """reference bindings/pybind/c_binding.cpp:28-33: every initRwkv() hands out its own RWKV -- two different models alive in
     one Python process through the module, forwards interleaved, one freed while the other goes on"""
-    sys.path.insert(0, CSRC)
-    import rwkv
+    rwkv = rwkv_mod
     from rwkv_cpp_accelerated_amd import engine
     hs, ms = [], []
     for (L, D, seed) in ((2, 768, 81), (3, 1024, 82)):

@@ -16,8 +16,7 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
+from support import CSRC, INCLUDE, LINK, ROOT
 REF = build.reference_root()
 needs_ref = pytest.mark.skipif(REF is None, reason="/root/reference not present (authoring container only)")
 
@@ -63,8 +62,7 @@ def test_backend_tu_defines_every_prototype_of_the_reference_header(built, tmp_p
                      "  return (a && b && c && d && e && f) ? 0 : 1;\n}\n")
     exe = str(tmp_path / "probe")
     subprocess.check_call(["g++", "-std=c++17", "-w", str(probe), os.path.join(ROOT, "integration", "rwkv_backend_mi355x.cpp"),
-                           "-I" + os.path.join(REF, "include"), "-I" + os.path.join(ROOT, "include"),
-                           "-L" + CSRC, "-lrwkv_mi355x", "-Wl,-rpath," + CSRC, "-o", exe])
+                           "-I" + os.path.join(REF, "include"), "-I" + INCLUDE, *LINK, "-o", exe])
 
 
 @needs_ref

@@ -25,7 +25,8 @@ import parity
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, run_app
+
 INIT_PROMPT = "### Instruction: Write a story/book using the themes and details provided\n\n### Input:"   # storygen.cpp:5-7
 USER_LINE = "a knight"
 
@@ -242,9 +243,8 @@ def test_two_models_in_one_process(built, tmp_path, exe):
         mf.write_bin(p, L, D, mf.synthetic_tensors(L, D, seed=seed))
         paths.append(p)
     n = 10
-    out = subprocess.run([binp, paths[0], paths[1], str(n)], capture_output=True, text=True, timeout=240)
-    assert out.returncode == 0, out.stdout[-400:] + out.stderr[-400:]
-    lines = [l for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(binp, [paths[0], paths[1], n], timeout=240)
+    assert rc == 0, raw[-800:]
     ia, ib, ic = ([int(x) for x in l.split()] for l in lines[-4:-1])
     assert lines[-1].split() == ["layers", "3", "1024"]
     want = []

@@ -9,31 +9,22 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
+from support import ROOT, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()   # raises if the HIP extension is missing: no fallback
-    return engine
-
-
-def _model(eng_mod, L, D, seed, maxGPT=1, resident=True):
+def _model(eng, L, D, seed, maxGPT=1, resident=True):
     t = mf.synthetic_tensors(L, D, seed=seed)
-    m = eng_mod.RWKV(resident=resident)
+    m = eng.RWKV(resident=resident)
     m.loadTensors(L, D, t, maxGPT=maxGPT)
     return m, t
 
 
 @pytest.mark.parametrize("L,D", [(2, 64), (3, 768), (2, 1024), (2, 2048), (1, 2560), (1, 4096), (1, 5120)])
-def test_token_logits_vs_oracle(eng_mod, oracle, L, D):
+def test_token_logits_vs_oracle(eng, oracle, L, D):
     """teacher-forced single-token decode: per-step logits and state vs the CPU restatement"""
-    m, t = _model(eng_mod, L, D, seed=100 + D)
+    m, t = _model(eng, L, D, seed=100 + D)
     om = oracle.from_tensors(L, D, t)
     st = om.new_state()
     toks = [11, 50276, 1, 4097, 11, 333]
@@ -49,14 +40,14 @@ def test_token_logits_vs_oracle(eng_mod, oracle, L, D):
     om.close(); m.close()
 
 
-def test_gpt_mode_chunk_equals_token_by_token(eng_mod, oracle):
+def test_gpt_mode_chunk_equals_token_by_token(eng, oracle):
     """GPT mode: T consecutive tokens of one sequence (rwkv.cu:227-240); logits for every position"""
     L, D, T = 2, 768, 5
-    m, t = _model(eng_mod, L, D, seed=5, maxGPT=8)
+    m, t = _model(eng, L, D, seed=5, maxGPT=8)
     om = oracle.from_tensors(L, D, t)
     toks = [9, 8, 7, 50000, 6]
     ref = om.forward(toks, om.new_state())
-    got = m.forward(toks, eng_mod.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
+    got = m.forward(toks, eng.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
     for i in range(T):
         parity.check_logits(got[i], ref[i], f"pos {i}")
     m.reset_state()
@@ -68,24 +59,24 @@ def test_gpt_mode_chunk_equals_token_by_token(eng_mod, oracle):
     # with the chunked path switched off a GPT-mode call is the same kernels token by token: bit for bit
     os.environ["RWKV_SEQ"] = "0"
     try:
-        m2 = eng_mod.RWKV(resident=True)
+        m2 = eng.RWKV(resident=True)
         m2.loadTensors(L, D, t, maxGPT=8)
     finally:
         del os.environ["RWKV_SEQ"]
-    got2 = m2.forward(toks, eng_mod.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
+    got2 = m2.forward(toks, eng.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
     assert np.array_equal(one, got2)
     om.close(); m2.close()
 
 
-def test_parralel_mode_independent_slots(eng_mod, oracle):
+def test_parralel_mode_independent_slots(eng, oracle):
     """PARRALEL mode: one step of T independent sequences, state slot t (rwkv.cu:238-240)"""
     L, D, T = 2, 768, 3
-    m, t = _model(eng_mod, L, D, seed=6, maxGPT=4, resident=False)
+    m, t = _model(eng, L, D, seed=6, maxGPT=4, resident=False)
     om = oracle.from_tensors(L, D, t)
     sp = om.new_state(slots=T)
     for rnd, toks in enumerate([[3, 4, 5], [6, 7, 3]]):
         ref = om.forward(toks, sp, mode=0)
-        got = m.forward(toks, eng_mod.MODE_PARRALEL)[: T * mf.VOCAB].reshape(T, mf.VOCAB)
+        got = m.forward(toks, eng.MODE_PARRALEL)[: T * mf.VOCAB].reshape(T, mf.VOCAB)
         for i in range(T):
             parity.check_logits(got[i], ref[i], f"round {rnd} slot {i}")
     for g, r in zip(m.state.arrays(), sp):      # host-authoritative (drop-in) mode: state came back
@@ -93,34 +84,34 @@ def test_parralel_mode_independent_slots(eng_mod, oracle):
     om.close(); m.close()
 
 
-def test_load_file_equals_load_tensors(eng_mod, tmp_path):
+def test_load_file_equals_load_tensors(eng, tmp_path):
     L, D = 2, 768
     t = mf.synthetic_tensors(L, D, seed=8)
     p = str(tmp_path / "model.bin")
     mf.write_bin(p, L, D, t)
-    a = eng_mod.RWKV(resident=True); a.loadFile(p)
-    b = eng_mod.RWKV(resident=True); b.loadTensors(L, D, t)
+    a = eng.RWKV(resident=True); a.loadFile(p)
+    b = eng.RWKV(resident=True); b.loadTensors(L, D, t)
     import torch
     tt = [None if (x is None or i in mf.BUFFER_SLOTS) else torch.from_numpy(np.ascontiguousarray(x)).cuda() for i, x in enumerate(t)]
-    c = eng_mod.RWKV(resident=True); c.loadTensors(L, D, tt)
+    c = eng.RWKV(resident=True); c.loadTensors(L, D, tt)
     assert (a.num_layers, a.num_embed) == (L, D)
     for tk in (5, 6):
         la = a.forward(tk).copy(); lb = b.forward(tk).copy(); lc = c.forward(tk).copy()
         assert np.array_equal(la, lb) and np.array_equal(la, lc)
     with pytest.raises(RuntimeError, match="already loaded"):
         a.loadFile(p)
-    with pytest.raises(eng_mod.RWKVError, match="Error opening file"):
-        eng_mod.RWKV().loadFile(str(tmp_path / "nope.bin"))
+    with pytest.raises(eng.RWKVError, match="Error opening file"):
+        eng.RWKV().loadFile(str(tmp_path / "nope.bin"))
     with pytest.raises(RuntimeError, match="Context too large"):
-        a.forward([1, 2], eng_mod.MODE_GPT)
+        a.forward([1, 2], eng.MODE_GPT)
     for x in (a, b, c):
         x.close()
 
 
-def test_state_roundtrip_and_snapshot(eng_mod):
+def test_state_roundtrip_and_snapshot(eng):
     """RWKVState value semantics (rwkv.h:140-242): snapshot, diverge, restore => identical logits"""
     L, D = 2, 768
-    m, _ = _model(eng_mod, L, D, seed=9, resident=False)
+    m, _ = _model(eng, L, D, seed=9, resident=False)
     for tk in (1, 2, 3):
         m.forward(tk)
     snap = m.state.getSubState(0)
@@ -132,10 +123,10 @@ def test_state_roundtrip_and_snapshot(eng_mod):
     m.close()
 
 
-def test_decode_greedy_matches_host_loop(eng_mod):
+def test_decode_greedy_matches_host_loop(eng):
     """device-side argmax feedback == host loop of forward + argmax(out[0] banned)"""
     L, D, n = 2, 1024, 24
-    m, _ = _model(eng_mod, L, D, seed=10)
+    m, _ = _model(eng, L, D, seed=10)
     ids = m.decode_greedy(42, n)
     last = m.logits(1).copy()
     m.reset_state()
@@ -148,32 +139,32 @@ def test_decode_greedy_matches_host_loop(eng_mod):
     m.close()
 
 
-def test_full_size_properties_7b_layer(eng_mod):
+def test_full_size_properties_7b_layer(eng):
     """BASELINE.json full width (D=4096) through size-independent properties: determinism (no float
     atomics => bit-identical reruns) and state-slot independence.  (The GEMV kernels themselves are checked one launch at a time in
     tests/test_kernels_gpu.py.)"""
     import torch
     L, D = 2, 4096
     t = mf.synthetic_tensors_torch(L, D, seed=3)
-    m = eng_mod.RWKV(resident=True); m.loadTensors(L, D, t, maxGPT=2)
-    a = m.forward([7, 9], eng_mod.MODE_PARRALEL)[: 2 * mf.VOCAB].copy()
+    m = eng.RWKV(resident=True); m.loadTensors(L, D, t, maxGPT=2)
+    a = m.forward([7, 9], eng.MODE_PARRALEL)[: 2 * mf.VOCAB].copy()
     m.reset_state()
-    b = m.forward([9, 7], eng_mod.MODE_PARRALEL)[: 2 * mf.VOCAB].copy()
+    b = m.forward([9, 7], eng.MODE_PARRALEL)[: 2 * mf.VOCAB].copy()
     assert np.array_equal(a[: mf.VOCAB], b[mf.VOCAB:]) and np.array_equal(a[mf.VOCAB:], b[: mf.VOCAB])
     m.reset_state()
-    c = m.forward([7, 9], eng_mod.MODE_PARRALEL)[: 2 * mf.VOCAB].copy()
+    c = m.forward([7, 9], eng.MODE_PARRALEL)[: 2 * mf.VOCAB].copy()
     assert np.array_equal(a, c)
     m.close()
 
 
-def test_pipeline_virtual_stages_equal_full_model(eng_mod):
+def test_pipeline_virtual_stages_equal_full_model(eng):
     """layer pipeline with all stages co-located on one GPU (same code path as the multi-GPU run minus
     the RCCL hop): chaining the stage contexts reproduces the full model's greedy ids and logits"""
     import torch
     from rwkv_cpp_accelerated_amd import pipeline
     L, D, n = 6, 768, 6
     t = mf.synthetic_tensors(L, D, seed=55)
-    full = eng_mod.RWKV(resident=True); full.loadTensors(L, D, t, maxGPT=2)
+    full = eng.RWKV(resident=True); full.loadTensors(L, D, t, maxGPT=2)
     parts = pipeline.partition_layers(L, 3, D)
     stages = [pipeline.EngineStage(t, L, D, l0, l1, n_slots=2) for l0, l1 in parts]
     assert stages[0].first and stages[-1].last and not stages[1].first and not stages[1].last
@@ -197,11 +188,11 @@ def test_pipeline_virtual_stages_equal_full_model(eng_mod):
     full.close()
 
 
-def test_long_decode_is_stable_and_deterministic(eng_mod):
+def test_long_decode_is_stable_and_deterministic(eng):
     """thousands of device-side steps: ids reproducible run to run, state and logits stay finite"""
     L, D, n = 4, 2048, 3000
     t = mf.synthetic_tensors(L, D, seed=21)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t)
     a = m.decode_greedy(17, n)
     la = m.logits(1).copy()
@@ -212,20 +203,20 @@ def test_long_decode_is_stable_and_deterministic(eng_mod):
     m.pull_state(1)
     for arr in m.state.arrays():
         assert np.isfinite(arr[: L * D]).all()
-    with pytest.raises(eng_mod.RWKVError):
+    with pytest.raises(eng.RWKVError):
         m.decode_greedy(17, (1 << 16) + 1)                                      # beyond the generated-id buffer
     m.close()
 
 
-def test_graph_replay_equals_eager_launches(eng_mod):
+def test_graph_replay_equals_eager_launches(eng):
     """the captured hipGraph and plain stream launches run the same kernels: bit-identical logits"""
     L, D = 2, 1024
     t = mf.synthetic_tensors(L, D, seed=22)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t)
     os.environ["RWKV_GRAPH"] = "2"          # bit 0 clear: the token's kernels are launched one by one
     try:
-        e = eng_mod.RWKV(resident=True)
+        e = eng.RWKV(resident=True)
         e.loadTensors(L, D, t)
     finally:
         del os.environ["RWKV_GRAPH"]
@@ -251,7 +242,7 @@ def _pipe_worker(rank, world, port, first_tokens, L, D, seed, steps, q):
 
 
 @pytest.mark.parametrize("world", [2, 3])
-def test_pipeline_processes_with_engine_stages(eng_mod, world):
+def test_pipeline_processes_with_engine_stages(eng, world):
     """bench.py's N > 1 path end to end, minus RCCL: `world` processes, each an EngineStage on its layer range
     (all on this box's one GPU), the residual hop through gloo.  Must equal single-context greedy decoding of
     every stream."""
@@ -260,7 +251,7 @@ def test_pipeline_processes_with_engine_stages(eng_mod, world):
     L, D, seed, steps = 6, 768, 77, 6
     first = [11, 222, 3333][:world]
     t = mf.synthetic_tensors(L, D, seed=seed)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t)
     want = np.zeros((world, steps), np.int64)
     for k, tk in enumerate(first):
@@ -283,7 +274,7 @@ def test_pipeline_processes_with_engine_stages(eng_mod, world):
     assert np.array_equal(got, want)
 
 
-def test_config1_169m_reference_converter_file_greedy_decode(eng_mod, oracle, tmp_path):
+def test_config1_169m_reference_converter_file_greedy_decode(eng, oracle, tmp_path):
     """BASELINE config 1: RWKV-4 169M (L=12, D=768), a model.bin equal to what the REFERENCE CONVERTER writes for the
     checkpoint (tests/golden/converter_169M.npz holds the sha256 of every tensor of the reference converter's own file;
     the offset vectors may differ by 4e-7, torch's vs numpy's reduction order), storygen-style greedy decode (out[0]
@@ -299,13 +290,13 @@ def test_config1_169m_reference_converter_file_greedy_decode(eng_mod, oracle, tm
     p = str(tmp_path / "model.bin")
     mf.write_bin(p, L, D, t)
     assert os.path.getsize(p) == int(g["file_bytes"])
-    m = eng_mod.RWKV(resident=True); m.loadFile(p, 32)
+    m = eng.RWKV(resident=True); m.loadFile(p, 32)
     om = oracle.open_file(p)
     st = om.new_state()
     prompt = [int(x) for x in np.random.default_rng(169).integers(2, mf.VOCAB, 40)]
     ref = om.forward(prompt, st)                                   # the reference's loadContext semantics, token by token
-    got = m.forward(prompt[:32], eng_mod.MODE_GPT)                 # the engine: a 32-token chunk, then the rest
-    got = m.forward(prompt[32:], eng_mod.MODE_GPT)[: 8 * mf.VOCAB].reshape(8, mf.VOCAB)[-1]
+    got = m.forward(prompt[:32], eng.MODE_GPT)                 # the engine: a 32-token chunk, then the rest
+    got = m.forward(prompt[32:], eng.MODE_GPT)[: 8 * mf.VOCAB].reshape(8, mf.VOCAB)[-1]
     parity.check_logits(got, ref[-1], "169M prompt")
     tk = parity.argmax_ban0(ref[-1])
     ids_ref, ids_eng = [], []
@@ -320,26 +311,26 @@ def test_config1_169m_reference_converter_file_greedy_decode(eng_mod, oracle, tm
     om.close(); m.close()
 
 
-def test_abi_version_and_small_grid_is_rejected(eng_mod, monkeypatch):
+def test_abi_version_and_small_grid_is_rejected(eng, monkeypatch):
     """the library reports the C-ABI version of include/rwkv_mi355x.h; RWKV_GRID below ceil(D / 512) is refused at load"""
-    assert eng_mod.lib().rwkv_abi_version() == eng_mod.ABI_VERSION
+    assert eng.lib().rwkv_abi_version() == eng.ABI_VERSION
     monkeypatch.setenv("RWKV_GRID", "3")
-    m = eng_mod.RWKV(resident=True)
-    with pytest.raises(eng_mod.RWKVError, match="RWKV_GRID"):
+    m = eng.RWKV(resident=True)
+    with pytest.raises(eng.RWKVError, match="RWKV_GRID"):
         m.loadTensors(1, 2048, mf.synthetic_tensors(1, 2048, seed=3))
     m.close()
     monkeypatch.setenv("RWKV_GRID", "8")           # a small but sufficient grid still computes the same thing
     t = mf.synthetic_tensors(1, 1024, seed=4)
-    a = eng_mod.RWKV(resident=True); a.loadTensors(1, 1024, t)
+    a = eng.RWKV(resident=True); a.loadTensors(1, 1024, t)
     monkeypatch.delenv("RWKV_GRID")
-    b = eng_mod.RWKV(resident=True); b.loadTensors(1, 1024, t)
+    b = eng.RWKV(resident=True); b.loadTensors(1, 1024, t)
     la = np.array(a.forward(9)[: mf.VOCAB]); lb = np.array(b.forward(9)[: mf.VOCAB])
     assert np.abs(la.astype(np.float64) - lb).max() <= 1e-5 * np.abs(lb).max()
     assert a.resident_bytes() > 0
     a.close(); b.close()
 
 
-def _decodes_like_the_oracle(eng_mod, oracle, m, what):
+def _decodes_like_the_oracle(eng, oracle, m, what):
     """a valid load on handle m, then two tokens against the oracle"""
     L, D = 1, 80
     t = mf.synthetic_tensors(L, D, seed=81)
@@ -352,32 +343,32 @@ def _decodes_like_the_oracle(eng_mod, oracle, m, what):
 
 
 @pytest.mark.parametrize("L,D", [(1, 8), (1, 24), (1, 1032), (1, 5136), (0, 64)])
-def test_a_model_shape_outside_the_accepted_set_is_refused_before_anything_is_read(eng_mod, oracle, L, D):
+def test_a_model_shape_outside_the_accepted_set_is_refused_before_anything_is_read(eng, oracle, L, D):
     """n_embed must be a multiple of 16 up to 5120 and n_layers at least 1: anything else is RWKV_E_ARG with a message, and the handle
     takes a valid model afterwards.  The tensors have the size the call states (for n_layers 0: a one-layer model's, which is more),
     so a shape check that moved behind an upload would upload garbage and fail here instead of reading out of bounds."""
     t = mf.synthetic_tensors(max(L, 1), D, seed=5)
-    m = eng_mod.RWKV(resident=True)
-    with pytest.raises(eng_mod.RWKVError, match=r"unsupported model shape.*status -1"):
+    m = eng.RWKV(resident=True)
+    with pytest.raises(eng.RWKVError, match=r"unsupported model shape.*status -1"):
         m.loadTensors(L, D, t)
     assert not m.ready
     del t
-    _decodes_like_the_oracle(eng_mod, oracle, m, f"after the refusal of L{L} D{D}")
+    _decodes_like_the_oracle(eng, oracle, m, f"after the refusal of L{L} D{D}")
     m.close()
 
 
-def test_the_smallest_grid_is_exact_at_the_widest_model(eng_mod, oracle, monkeypatch):
+def test_the_smallest_grid_is_exact_at_the_widest_model(eng, oracle, monkeypatch):
     """RWKV_GRID = 9 at D = 5120 is one workgroup short of 512 channels each (10 is accepted: test_kernels_gpu.py)"""
     monkeypatch.setenv("RWKV_GRID", "9")
-    m = eng_mod.RWKV(resident=True)
-    with pytest.raises(eng_mod.RWKVError, match=r"RWKV_GRID=9 is too small.*need >= 10.*status -1"):
+    m = eng.RWKV(resident=True)
+    with pytest.raises(eng.RWKVError, match=r"RWKV_GRID=9 is too small.*need >= 10.*status -1"):
         m.loadTensors(1, 5120, mf.synthetic_tensors(1, 5120, seed=6))
     assert m.debug_grid() == 9
-    _decodes_like_the_oracle(eng_mod, oracle, m, "after the refusal of RWKV_GRID=9")       # (9 workgroups are enough for D = 80)
+    _decodes_like_the_oracle(eng, oracle, m, "after the refusal of RWKV_GRID=9")       # (9 workgroups are enough for D = 80)
     m.close()
 
 
-def test_load_file_streams_through_pinned_staging(eng_mod, tmp_path):
+def test_load_file_streams_through_pinned_staging(eng, tmp_path):
     """rwkv_load_file (rwkv.cu:638-717): a model.bin read through two pinned staging buffers in 32 MiB pieces, no device wait
     per tensor -- the context must compute exactly what a context loaded from the same tensors in memory computes.  D = 2048,
     L = 3: the 4D x D matrices (16 MiB) and the embedding table (412 MB) span several pieces."""
@@ -385,8 +376,8 @@ def test_load_file_streams_through_pinned_staging(eng_mod, tmp_path):
     t = mf.synthetic_tensors(L, D, seed=77)
     path = str(tmp_path / "model.bin")
     mf.write_bin(path, L, D, [np.zeros(n, dtype=dt) if x is None else x for x, n, dt in zip(t, mf.sizes(L, D), mf.DTYPES)])
-    a = eng_mod.RWKV(resident=True); a.loadTensors(L, D, t)
-    b = eng_mod.RWKV(resident=True); b.loadFile(path)
+    a = eng.RWKV(resident=True); a.loadTensors(L, D, t)
+    b = eng.RWKV(resident=True); b.loadFile(path)
     for tk in (3, 50000, 17, 17):
         la = np.array(a.forward(tk)[: mf.VOCAB]); lb = np.array(b.forward(tk)[: mf.VOCAB])
         assert np.array_equal(la, lb)

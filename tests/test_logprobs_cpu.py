@@ -6,7 +6,6 @@ checked by the GPU suite; a NULL context is checked here.)"""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,9 +13,7 @@ import pytest
 import logprob_cases as lc
 import score_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
-E_ARG = -1
+from support import E_ARG, ROOT, build_app, rwkv_mod  # noqa: F401
 
 
 def test_entry_points_are_declared_exported_and_bound(built):
@@ -45,17 +42,15 @@ def test_a_null_context_is_a_bad_argument(built):
     assert lib.rwkv_decode_batch_logprobs(None, one, 1, 1, C.byref(pk), None, None, C.byref(rec), ids, ln, None, None) == E_ARG
 
 
-def test_pybind_module_has_top_logprobs(built):
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_module_has_top_logprobs(rwkv_mod):
+    rwkv = rwkv_mod
     assert callable(getattr(rwkv, "topLogprobs", None))
     for f in ("initRwkv", "loadModel", "modelForward", "initState", "getState", "initOutput", "getOutput", "typicalSample", "scoreTokens"):
         assert hasattr(rwkv, f), f                      # the reference's names stay
 
 
 def test_logprobs_app_compiles_and_links(built, tmp_path):
-    app = lc.build_logprobs_app(str(tmp_path))
+    app = build_app("logprobs_app", tmp_path)
     syms = subprocess.run(["nm", "-D", "--undefined-only", app], capture_output=True, text=True).stdout
     assert "rwkv_decode_batch_logprobs" in syms and "rwkv_topn_rows" in syms
 

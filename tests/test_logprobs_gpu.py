@@ -5,49 +5,28 @@ topn_rows per step -- bitwise, and against rwkv_decode_batch_until for ids, leng
 continuation; rejected calls; scratch accounting; the C++ and pybind bindings.  Every context is a synthetic 2-layer model.
 Each planted case prints its worst figure before anything is asserted."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import logprob_cases as lc
-import sampler_cases
+import support
+from support import E_ARG, E_STATE, V, build_app, eng, firsts_of, load, restore, run_app, rwkv_mod, same_bits, seeds_of, slots, start_state  # noqa: F401
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
 L = 2
 ROWS = 4                         # maxGPT of the planted context: rows 0 .. 3 start at the four offsets from a 16-byte boundary
 D_LOOP, MAXN, STEPS = 128, 5, 12
-E_ARG, E_STATE = -1, -4
 NUC = dict(temp=1.0, top_p=0.9, presence=0.4, frequency=0.4, decay=0.996)      # nucleus with penalties: the counts are part of a slot
 KW = dict(greedy=dict(pick="greedy"), nucleus=dict(pick="nucleus", **NUC))
-V = mf.VOCAB
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-def load(eng, D, max_ctx, seed, **kw):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=seed, **kw), maxGPT=max_ctx)
-    return m
 
 
 @pytest.fixture(scope="module")
 def planted(eng):
-    m = load(eng, 64, ROWS, 3)
+    m = load(eng, L, 64, 3, ROWS)
     m.forward(5)
     yield m
     m.close()
@@ -55,7 +34,7 @@ def planted(eng):
 
 @pytest.fixture(scope="module")
 def model(eng):
-    m = load(eng, D_LOOP, MAXN, 41, head_scale=30.0)
+    m = load(eng, L, D_LOOP, 41, MAXN, head_scale=30.0)
     yield m
     m.close()
 
@@ -63,50 +42,12 @@ def model(eng):
 @pytest.fixture(scope="module")
 def start(eng, model):
     """distinct state in every slot: where every run of the loop tests starts"""
-    model.reset_state()
-    rng = np.random.default_rng(5)
-    for _ in range(3):
-        model.forward([int(v) for v in rng.integers(1, V, MAXN)], eng.MODE_PARRALEL)
-    model.pull_state(MAXN)
-    return [a.copy() for a in model.state.arrays()]
-
-
-def restore(m, snap):
-    for a, s in zip(m.state.arrays(), snap):
-        a[:] = s
-    m.push_state(MAXN)
-
-
-def slots(m, n, counts):
-    """per slot: the five state arrays [n][L D], the logits rows [n][V] and (counts) the count vectors [n][V]"""
-    m.pull_state(n)
-    out = [a[: n * L * D_LOOP].reshape(n, L * D_LOOP).copy() for a in m.state.arrays()]
-    out.append(m.logits(n).reshape(n, V).copy())
-    if counts:
-        out.append(np.stack([m.penalty_get(s) for s in range(n)]))
-    return out
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
-
-
-def firsts_of(n):
-    return [int(v) for v in np.random.default_rng(3).integers(1, V, n)]
-
-
-def seeds_of(n):
-    return [1000 + 7 * s for s in range(n)]
+    return start_state(eng, model, MAXN)
 
 
 def plant(m, rows):
     """rows: {logits row: case name}"""
-    import torch
-    view = sampler_cases.logits_view(m, ROWS)
-    for r, name in rows.items():
-        view[r].copy_(torch.from_numpy(np.array(lc.logits_of(name), np.float32)).cuda())      # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
+    support.plant_rows(m, {r: lc.logits_of(name) for r, name in rows.items()}, ROWS)
 
 
 # ---- planted rows -------------------------------------------------------------------------------------------------------------
@@ -333,7 +274,7 @@ def test_rejected_calls_leave_everything_alone(eng, model, start):
         assert call(h=e._h) == E_STATE
         e.close()
     # a context without the chunk path runs one stream only
-    e = load(eng, 48, 3, 42)
+    e = load(eng, L, 48, 42, 3)
     assert call(h=e._h, stop=None) == E_STATE and call(h=e._h, first=a(5), n=1, stop=None) == 0
     e.close()
 
@@ -347,7 +288,7 @@ def record_bytes(n, steps, top_n):
 def test_the_record_is_counted_and_a_plain_until_call_allocates_what_it_did(eng):
     D, n = 64, 4
     park = 4 * n * (10 * L * D + 50280) + 4 * (5 * n + 2) + 4 * 8 * 8        # park buffer, run record, histories (tests/test_stop_gpu.py)
-    m = load(eng, D, 8, 9)
+    m = load(eng, L, D, 9, 8)
     m.decode_batch_until(firsts_of(n), 9)                                    # cannot stop a stream: the plain loop (9 steps: the ids of the longest call below)
     base = m.resident_bytes()
     m.decode_batch_until(firsts_of(n), 8, max_new=[8] * n)
@@ -362,7 +303,7 @@ def test_the_record_is_counted_and_a_plain_until_call_allocates_what_it_did(eng)
     m.decode_batch_logprobs(firsts_of(n), 9, top_n=5)
     assert m.resident_bytes() - r0 == record_bytes(n, 9, 5)
     m.close()
-    m = load(eng, D, 8, 9)                                                   # the other order: the record first
+    m = load(eng, L, D, 9, 8)                                                # the other order: the record first
     m.decode_batch_greedy(firsts_of(n), 8)
     base = m.resident_bytes()
     m.decode_batch_logprobs(firsts_of(n), 8, top_n=0)
@@ -376,17 +317,14 @@ def test_the_record_is_counted_and_a_plain_until_call_allocates_what_it_did(eng)
 # ---- bindings -----------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def model_file(tmp_path_factory):
-    p = str(tmp_path_factory.mktemp("logprobs") / "model.bin")
-    mf.write_bin(p, L, D_LOOP, mf.synthetic_tensors(L, D_LOOP, seed=43, head_scale=30.0))
-    return p
+    return support.model_file(tmp_path_factory, "logprobs", L, D_LOOP, 43, head_scale=30.0)
 
 
 def test_logprobs_app_matches_the_python_engine(eng, built, model_file, tmp_path):
     n, steps, top_n = 3, 6, 4
-    app = lc.build_logprobs_app(str(tmp_path))
-    out = subprocess.run([app, model_file, str(n), str(steps), str(top_n)], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l.split() for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(build_app("logprobs_app", tmp_path), [model_file, n, steps, top_n])
+    assert rc == 0, raw
+    lines = [l.split() for l in lines]
     assert lines[-1] == ["logprobs_ok"] and len(lines) == n * steps + n + 1
     m = eng.RWKV(resident=True)
     m.loadFile(model_file, n)
@@ -406,9 +344,8 @@ def test_logprobs_app_matches_the_python_engine(eng, built, model_file, tmp_path
         assert f[0] == "row" and [int(v) for v in f[2::2]] == r_ids[s].tolist() and [hx(v).hex() for v in f[3::2]] == [float(v).hex() for v in r_lp[s]]
 
 
-def test_pybind_top_logprobs_matches_the_python_engine(eng, built, model_file):
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_top_logprobs_matches_the_python_engine(eng, rwkv_mod, model_file):
+    rwkv = rwkv_mod
     h = rwkv.initRwkv()
     rwkv.loadModel(h, model_file)
     rwkv.initOutput(h); rwkv.initState(h)

@@ -14,7 +14,8 @@ import pytest
 
 import nucleus_cases as nc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, build_app, syntax_only
+
 RUNS = nc.all_runs()
 IDS = [f"{label}-t{r.temp}-p{r.top_p}-k{r.top_k}-{'ban0' if r.ban0 else 'noban'}-pen{r.presence}/{r.frequency}" for (label, _, r, _, _) in RUNS]
 NEW = ["rwkv_sample_nucleus", "rwkv_decode_nucleus", "rwkv_decode_batch_nucleus", "rwkv_penalty_set", "rwkv_penalty_get"]
@@ -23,15 +24,16 @@ NEW = ["rwkv_sample_nucleus", "rwkv_decode_nucleus", "rwkv_decode_batch_nucleus"
 @pytest.fixture(scope="module")
 def app(tmp_path_factory):
     """(path, sanitized): with -fsanitize=address,undefined where that links (the sanitizer runtime is installed), plain otherwise"""
-    exe = str(tmp_path_factory.mktemp("nucc") / "nucleus_app")
-    cmd = ["g++", "-std=c++17", "-O2", "-g", os.path.join(ROOT, "tests", "cpp", "nucleus_app.cpp"), "-I" + os.path.join(ROOT, "include"), "-o", exe]
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
-    if subprocess.run(cmd + san, capture_output=True).returncode == 0:
+    outdir = tmp_path_factory.mktemp("nucc")
+    san = ("-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer")
+    try:
+        exe = build_app("nucleus_app", outdir, link=False, opt="-O2", extra=("-g",) + san)
         print("nucleus_app: built with -fsanitize=address,undefined")
         return exe, True
-    subprocess.check_call(cmd)
-    print("nucleus_app: the sanitizer runtime is not installed; built without")
-    return exe, False
+    except subprocess.CalledProcessError:
+        exe = build_app("nucleus_app", outdir, link=False, opt="-O2", extra=("-g",))
+        print("nucleus_app: the sanitizer runtime is not installed; built without")
+        return exe, False
 
 
 def test_the_uniforms_are_the_66_of_the_typical_cases():
@@ -161,8 +163,7 @@ def test_cpp_header_offers_the_wrappers(tmp_path):
                    "    nucleus_count(c.data(), nucleus_u(m.out, c.data(), 1.0f, 0.9f, 40, 0.5, 0.4f, 0.4f, true), 0.996f);\n"
                    "    return (int)(a.size() + b.size());\n"
                    "}\n")
-    out = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-I" + os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-3000:]
+    syntax_only(src, extra=())
 
 
 def test_library_exports_the_new_entry_points(built):

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import nucleus_cases as nc
+from support import E_ARG, E_STATE, GuardContexts, check_refused, eng, load, plant_rows, rwkv_mod  # noqa: F401
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
@@ -21,36 +22,17 @@ ROWS = 4                      # maxGPT of the planted context and of the loop mo
 V = nc.V
 
 
-@pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
 def planted_context(eng):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(2, 64, mf.synthetic_tensors(2, 64, seed=3), maxGPT=ROWS)
+    m = load(eng, 2, 64, 3, ROWS)
     m.forward(5)
     return m
 
 
 @pytest.fixture(scope="module")
-def ctx(eng_mod):
-    m = planted_context(eng_mod)
+def ctx(eng):
+    m = planted_context(eng)
     yield m
     m.close()
-
-
-def plant(m, rows):
-    """rows: {logits row: float32 vector}"""
-    import torch
-    view = nc.logits_view(m, ROWS)
-    for r, vec in rows.items():
-        view[r].copy_(torch.from_numpy(np.array(vec, np.float32)).cuda())          # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
 
 
 def run_draws(m, label, ref, run, row=0, slot=0):
@@ -84,7 +66,7 @@ def test_planted_case_matches_the_log_space_reference(ctx, name):
     planted = None
     for run in case.runs:
         if planted != run.ban0:                      # (the tie set of d1025 has one more id under the ban)
-            plant(ctx, {0: nc.logits_of(case.logits, run.ban0)})
+            plant_rows(ctx, {0: nc.logits_of(case.logits, run.ban0)}, ROWS)
             planted = run.ban0
         bad += run_draws(ctx, name, nc.ref_of(case.logits, run, case.counted), run)
     if case.counted:
@@ -94,7 +76,7 @@ def test_planted_case_matches_the_log_space_reference(ctx, name):
 
 def test_rows_and_slots_are_addressed_independently_case_r(ctx):
     """three rows of different content, each sampled with the counts of a different slot"""
-    plant(ctx, {row: nc.logits_of(n, False) for (n, row, _) in nc.ROW_CASE})
+    plant_rows(ctx, {row: nc.logits_of(n, False) for (n, row, _) in nc.ROW_CASE}, ROWS)
     for (n, _, slot) in nc.ROW_CASE:
         ctx.penalty_set(slot, nc.counts_of(n, slot))
     bad = []
@@ -104,11 +86,11 @@ def test_rows_and_slots_are_addressed_independently_case_r(ctx):
     assert not bad, f"{len(bad)} draws, first (case, run, u, device, reference, why): {bad[:4]}"
 
 
-def test_count_update_is_the_f32_restatement(eng_mod):
-    m = planted_context(eng_mod)                    # a context of its own: no count buffer yet
+def test_count_update_is_the_f32_restatement(eng):
+    m = planted_context(eng)                    # a context of its own: no count buffer yet
     try:
         lg = nc.logits_of("a")
-        plant(m, {0: lg})
+        plant_rows(m, {0: lg}, ROWS)
         rb0 = m.resident_bytes()
         for u in (0.1, 0.5, 0.9):                   # both penalties 0: nothing is read, updated or allocated, UPDATE or not
             got = m.sample_nucleus(1.0, 0.9, 0, 0.0, 0.0, 0.996, u, update=True)
@@ -147,9 +129,8 @@ LOOP_IDS = ["temp1", "temp0.01"]
 
 
 @pytest.fixture(scope="module")
-def model(eng_mod):
-    m = eng_mod.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=12, head_scale=30.0), maxGPT=ROWS)
+def model(eng):
+    m = load(eng, L, D, 12, ROWS, head_scale=30.0)
     yield m
     m.close()
 
@@ -181,7 +162,7 @@ def test_decode_nucleus_equals_the_reference_loop(model, kw):
 
 
 @pytest.mark.parametrize("kw", LOOPS, ids=LOOP_IDS)
-def test_decode_batch_nucleus_equals_the_reference_loop(eng_mod, model, kw):
+def test_decode_batch_nucleus_equals_the_reference_loop(eng, model, kw):
     m, first, seeds = model, [9, 4242, 30000], [11, 22, 33]
     m.reset_state()
     got = m.decode_batch_nucleus(first, N_GEN, seeds=seeds, **kw).astype(np.int64)
@@ -190,7 +171,7 @@ def test_decode_batch_nucleus_equals_the_reference_loop(eng_mod, model, kw):
     m.reset_state()
     ids, cs = list(first), [np.zeros(V, np.float32) for _ in range(3)]
     for step in range(N_GEN):
-        lg = m.forward(ids, eng_mod.MODE_PARRALEL)[: 3 * V].reshape(3, V).copy()
+        lg = m.forward(ids, eng.MODE_PARRALEL)[: 3 * V].reshape(3, V).copy()
         for s in range(3):
             ids[s], cs[s] = follow(lg[s], cs[s], kw, nc.splitmix_u(seeds[s], step), int(got[s, step]), f"stream {s} step {step}")
     for s in range(3):
@@ -240,15 +221,12 @@ def test_keep_continues_a_batched_call(model):
 
 
 # ---- the pybind module: RWKV::sampleNucleus / decodeNucleus of include/rwkv.h at run time, host-authoritative state (push / pull) ------
-def test_pybind_nucleus_matches_the_python_engine(eng_mod, tmp_path):
-    import os
-    import sys
-    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rwkv-cpp-accelerated_amd", "csrc"))
-    import rwkv
+def test_pybind_nucleus_matches_the_python_engine(eng, rwkv_mod, tmp_path):
+    rwkv = rwkv_mod
     path = str(tmp_path / "model.bin")
     mf.write_bin(path, L, 128, mf.synthetic_tensors(L, 128, seed=43, head_scale=30.0))
     kw = LOOPS[0]
-    m = eng_mod.RWKV()                                  # host state authoritative, as the module's RWKV object
+    m = eng.RWKV()                                  # host state authoritative, as the module's RWKV object
     m.loadFile(path)
     want_a = m.decode_nucleus(30000, 8, seed=7, **kw).tolist()
     want_b = m.decode_nucleus(want_a[-1], 8, seed=15, keep=True, **kw).tolist()
@@ -273,7 +251,6 @@ def test_pybind_nucleus_matches_the_python_engine(eng_mod, tmp_path):
 
 
 # ---- refused calls: one table in the style of tests/test_abi_guards_gpu.py ---------------------------------------------------------
-E_ARG, E_STATE = -1, -4
 GL, GD, MAXT = 2, 64, 8
 u64 = C.c_uint64
 
@@ -382,51 +359,9 @@ def _guard_id(i):
     return f"{i:02d}-{entry[5:]}-{args[0] if isinstance(args[0], str) else 'null'}"
 
 
-class GuardCtx:
-    FIRST, N = 11, 4
-
-    def __init__(self, eng):
-        self.lib = eng.lib()
-        t = mf.synthetic_tensors(GL, GD, seed=4100)
-        self.models = dict(M=eng.RWKV(resident=True), U=eng.RWKV(resident=True), S=eng.RWKV(resident=True), W=eng.RWKV(resident=True))
-        self.models["M"].loadTensors(GL, GD, t, maxGPT=MAXT)
-        self.models["S"].set_layer_range(0, 1)
-        self.models["S"].loadTensors(GL, GD, t, maxGPT=MAXT)
-        self.models["W"].loadTensors(GL, 80, mf.synthetic_tensors(GL, 80, seed=4100), maxGPT=MAXT)      # a width without a chunk path
-        self.h = {k: m._h for k, m in self.models.items()}
-        m = self.models["M"]
-        m.forward([5, 40000, 77, 9, 1234], eng.MODE_PARRALEL)         # a history on slots 0 .. 4
-        m.forward([7, 50000, 11], eng.MODE_GPT)                       # and three logits rows
-        for s in range(MAXT):                                         # and counts on every slot
-            m.penalty_set(s, np.roll(nc.counts_of("a"), 1000 * s))
-        self.state0, _, _ = self.snapshot()
-        self.ids0 = self.decode()
-        self.restore()
-
-    def snapshot(self):
-        st = [np.zeros(MAXT * GL * GD) for _ in range(5)]
-        lg = np.zeros(MAXT * V, np.float32)
-        ptr = lambda x: C.c_void_p(x.ctypes.data)
-        assert self.lib.rwkv_get_output(self.h["M"], ptr(lg), *[ptr(s) for s in st], MAXT) == 0
-        counts = np.stack([self.models["M"].penalty_get(s) for s in range(MAXT)])
-        return [s.view(np.uint64) for s in st], lg.view(np.uint32), counts.view(np.uint32)
-
-    def decode(self):
-        out = (u64 * self.N)()
-        assert self.lib.rwkv_decode_greedy(self.h["M"], self.FIRST, self.N, out) == 0, self.lib.rwkv_last_error()
-        return list(out)
-
-    def restore(self):
-        assert self.lib.rwkv_set_state(self.h["M"], *[C.c_void_p(s.ctypes.data) for s in self.state0], MAXT) == 0
-
-    def close(self):
-        for m in self.models.values():
-            m.close()
-
-
 @pytest.fixture(scope="module")
-def gctx(eng_mod):
-    x = GuardCtx(eng_mod)
+def gctx(eng):
+    x = GuardContexts(eng, GL, GD, MAXT, extra=("W",), counts=[np.roll(nc.counts_of("a"), 1000 * s) for s in range(MAXT)])
     yield x
     x.close()
 
@@ -434,19 +369,6 @@ def gctx(eng_mod):
 @pytest.mark.parametrize("i", range(len(GUARDS)), ids=_guard_id)
 def test_a_refused_call_answers_its_status_and_launches_nothing(gctx, i):
     entry, args, status, text = GUARDS[i]
-    state, logits, counts = gctx.snapshot()
-    rb = gctx.models["M"].resident_bytes()
     keep = [P(**v) if isinstance(v, dict) else None for v in args]
     call = [gctx.h[v] if isinstance(v, str) else C.byref(k) if isinstance(v, dict) else v for v, k in zip(args, keep)]
-    rc = int(getattr(gctx.lib, entry)(*call))
-    err = gctx.lib.rwkv_last_error().decode()
-    print(f"{entry}: status {rc}, {err!r}")
-    assert rc == status, err
-    assert text in err, err
-    state1, logits1, counts1 = gctx.snapshot()
-    for name, x, y in zip("xy aa bb pp dd".split(), state, state1):
-        assert np.array_equal(x, y), name
-    assert np.array_equal(logits, logits1) and np.array_equal(counts, counts1)
-    assert gctx.models["M"].resident_bytes() == rb
-    assert gctx.decode() == gctx.ids0
-    gctx.restore()
+    check_refused(gctx, entry, call, status, text)

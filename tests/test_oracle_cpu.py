@@ -8,8 +8,7 @@ import numpy as np
 import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT
 
 
 def test_mm8_one_matches_float64(oracle):

@@ -9,21 +9,13 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
+from support import eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
 @pytest.mark.parametrize("S,n_tokens", [(2, 256), (3, 77), (4, 130)])
-def test_pipelined_prefill_over_virtual_stages(eng_mod, S, n_tokens):
+def test_pipelined_prefill_over_virtual_stages(eng, S, n_tokens):
     """RWKV::loadContext (rwkv.h:395-413) with the prompt's 32-token chunks as micro-batches over S stages co-located on one
     GPU (same code path as rwkv_pipe_prefill minus the RCCL hop: stage s works on chunk t - s at tick t, the chunk's residual
     stream handed from stage to stage): logits of the last position, every stage's share of the recurrent state and the
@@ -33,9 +25,9 @@ def test_pipelined_prefill_over_virtual_stages(eng_mod, S, n_tokens):
     t = mf.synthetic_tensors(L, D, seed=91)
     rng = np.random.default_rng(S)
     prompt = [int(x) for x in rng.integers(2, mf.VOCAB, n_tokens)]
-    full = eng_mod.RWKV(resident=True); full.loadTensors(L, D, t, maxGPT=32)
+    full = eng.RWKV(resident=True); full.loadTensors(L, D, t, maxGPT=32)
     for i in range(0, n_tokens, 32):
-        last_logits = full.forward(prompt[i:i + 32], eng_mod.MODE_GPT)[: len(prompt[i:i + 32]) * mf.VOCAB].reshape(-1, mf.VOCAB)[-1].copy()
+        last_logits = full.forward(prompt[i:i + 32], eng.MODE_GPT)[: len(prompt[i:i + 32]) * mf.VOCAB].reshape(-1, mf.VOCAB)[-1].copy()
     full.pull_state(1)
     parts = pipeline.partition_layers(L, S, D)
     stages = [pipeline.EngineStage(t, L, D, l0, l1, n_slots=1, prefill=True) for l0, l1 in parts]
@@ -73,7 +65,7 @@ def test_pipelined_prefill_over_virtual_stages(eng_mod, S, n_tokens):
 
 
 @pytest.mark.parametrize("S", [2, 4, 8])
-def test_14b_shape_virtual_stages(eng_mod, S):
+def test_14b_shape_virtual_stages(eng, S):
     """BASELINE config 4's split (RWKV-4-14B: L=40, D=5120 over 2/4/8 stages) with all stages on this box's one GPU: the
     chained stage contexts reproduce the whole-model greedy ids and logits bit for bit"""
     import torch
@@ -81,7 +73,7 @@ def test_14b_shape_virtual_stages(eng_mod, S):
     L, D = mf.SHAPES["14B"]
     t = mf.synthetic_tensors_torch(L, D, seed=14, device="cuda")
     torch.cuda.synchronize()
-    full = eng_mod.RWKV(resident=True); full.loadTensors(L, D, t, maxGPT=1)
+    full = eng.RWKV(resident=True); full.loadTensors(L, D, t, maxGPT=1)
     parts = pipeline.partition_layers(L, S, D)
     assert parts[0][0] == 0 and parts[-1][1] == L and all(a[1] == b[0] for a, b in zip(parts, parts[1:]))
     stages = [pipeline.EngineStage(t, L, D, l0, l1, n_slots=1) for l0, l1 in parts]
@@ -102,7 +94,7 @@ def test_14b_shape_virtual_stages(eng_mod, S):
     torch.cuda.empty_cache()
 
 
-def test_native_transport_single_rank(eng_mod):
+def test_native_transport_single_rank(eng):
     """rwkv_pipe_init / rwkv_pipe_decode / rwkv_pipe_prefill with world = 1 on the REAL library: librccl.so is resolved, a
     communicator is made, and rwkv_pipe_init's agreement round makes its one hop to the rank itself -- a grouped ncclSend + ncclRecv of
     8 x uint64 on the engine's stream, checked byte for byte: the entry points, datatype codes, group and stream order the multi-GPU
@@ -110,14 +102,14 @@ def test_native_transport_single_rank(eng_mod):
     device-side id feedback run (no further hop to make): must equal decode_greedy and the chunked forward"""
     L, D, n = 3, 768, 24
     t = mf.synthetic_tensors(L, D, seed=92)
-    a = eng_mod.RWKV(resident=True); a.loadTensors(L, D, t, maxGPT=32)
-    b = eng_mod.RWKV(resident=True); b.loadTensors(L, D, t, maxGPT=32)
-    b.pipe_init(eng_mod.RWKV.pipe_unique_id(), 0, 1)
+    a = eng.RWKV(resident=True); a.loadTensors(L, D, t, maxGPT=32)
+    b = eng.RWKV(resident=True); b.loadTensors(L, D, t, maxGPT=32)
+    b.pipe_init(eng.RWKV.pipe_unique_id(), 0, 1)
     info = b.pipe_info()
     assert info["world"] == 1 and info["rccl_version"] > 20000 and "fake" not in info["rccl_path"], info      # (2.x.y as 2xxyy: not the test stand-in)
     prompt = [int(x) for x in np.random.default_rng(2).integers(2, mf.VOCAB, 70)]
     for i in range(0, 70, 32):
-        a.forward(prompt[i:i + 32], eng_mod.MODE_GPT)
+        a.forward(prompt[i:i + 32], eng.MODE_GPT)
     b.pipe_prefill(prompt, len(prompt))
     assert np.array_equal(a.logits(32)[: 6 * mf.VOCAB], b.logits(32)[: 6 * mf.VOCAB])
     want = a.decode_greedy(77, n)
@@ -183,7 +175,7 @@ def _native_worker(rank, world, port, first_tokens, L, D, seed, steps, prompt, q
 
 
 @pytest.mark.parametrize("world", [2, 4])
-def test_native_transport_with_several_ranks_on_one_gpu(eng_mod, world):
+def test_native_transport_with_several_ranks_on_one_gpu(eng, world):
     """rwkv_pipe_init / rwkv_pipe_prefill / rwkv_pipe_decode EXECUTED with world = 2 and 4: one process per rank, all on cuda:0,
     the engine's ncclSend / ncclRecv groups served by tests/fake_rccl.cpp (shared-memory channels, stream ordered; real RCCL
     refuses two ranks on one device and a gpurun box has one GPU).  Exercises what world = 1 cannot: the composition of the
@@ -222,9 +214,9 @@ def test_native_transport_with_several_ranks_on_one_gpu(eng_mod, world):
     assert info["rank"] == world - 1 and info["world"] == world and info["prefill_rows"] == 64 and info["rccl_version"] == 1, info
     assert info["rccl_path"].endswith("libfake_rccl.so") and info["device"] == 0 and info["arch"].startswith("gfx"), info
     t = mf.synthetic_tensors(L, D, seed=seed)
-    m = eng_mod.RWKV(resident=True); m.loadTensors(L, D, t, maxGPT=32)
+    m = eng.RWKV(resident=True); m.loadTensors(L, D, t, maxGPT=32)
     for i in range(0, len(prompt), 32):
-        ref = m.forward(prompt[i:i + 32], eng_mod.MODE_GPT)[: len(prompt[i:i + 32]) * mf.VOCAB].reshape(-1, mf.VOCAB)[-1].copy()
+        ref = m.forward(prompt[i:i + 32], eng.MODE_GPT)[: len(prompt[i:i + 32]) * mf.VOCAB].reshape(-1, mf.VOCAB)[-1].copy()
     assert np.array_equal(lg, ref)
     # the streams of the native decode started from slot k's state: slot 0 holds the prompt, the others are fresh
     for k, tk in enumerate(first):
@@ -279,7 +271,7 @@ def _mismatch_worker(rank, world, port, L, D, q, rccl_lib):
         q.put(("error", rank, repr(e)))
 
 
-def test_pipe_init_refuses_ranks_that_disagree_on_the_micro_batch(eng_mod):
+def test_pipe_init_refuses_ranks_that_disagree_on_the_micro_batch(eng):
     """rwkv_pipe_prefill's micro-batch (64 or 32 rows) comes from per-rank values (RWKV_SEQ_ROWS, max_ctx): ranks that differ would
     exchange differently sized messages and hang or corrupt the residual stream.  rwkv_pipe_init agrees on it over the communicator
     (ADVICE r04): with RWKV_SEQ_ROWS=32 on rank 1 only, EVERY rank must fail the init with the same diagnosis."""

@@ -6,32 +6,24 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
+from support import eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
 
 
 def _toks(n, seed):
     return [int(v) for v in np.random.default_rng(seed).integers(2, mf.VOCAB, n)]
 
 
-def _chunk_vs_oracle(eng_mod, oracle, L, D, T):
+def _chunk_vs_oracle(eng, oracle, L, D, T):
     t = mf.synthetic_tensors(L, D, seed=300 + D + T)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t, maxGPT=max(T, 2))
     om = oracle.from_tensors(L, D, t)
     st = om.new_state()
     toks = _toks(T, D + T)
     ref = om.forward(toks, st)
-    got = m.forward(toks, eng_mod.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
+    got = m.forward(toks, eng.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
     for i in range(T):
         parity.check_logits(got[i], ref[i], f"L{L} D{D} pos {i}")
         parity.check_argmax(got[i], ref[i], f"L{L} D{D} pos {i}")
@@ -52,43 +44,43 @@ def _chunk_vs_oracle(eng_mod, oracle, L, D, T):
 # 9/10 k-blocks per octant
 @pytest.mark.parametrize("L,D,T", [(2, 768, 5), (2, 768, 16), (2, 1024, 32), (1, 2048, 33), (1, 2560, 2), (1, 4096, 32), (1, 5120, 17), (2, 64, 40),
                                    (2, 128, 40), (2, 448, 33), (2, 576, 17), (1, 1088, 64), (1, 3008, 32), (1, 4032, 33), (1, 4160, 64), (1, 5056, 47)])
-def test_chunk_logits_and_state_vs_oracle(eng_mod, oracle, L, D, T):
-    _chunk_vs_oracle(eng_mod, oracle, L, D, T)
+def test_chunk_logits_and_state_vs_oracle(eng, oracle, L, D, T):
+    _chunk_vs_oracle(eng, oracle, L, D, T)
 
 
-def test_chunk_under_a_small_grid_vs_oracle(eng_mod, oracle, monkeypatch):
+def test_chunk_under_a_small_grid_vs_oracle(eng, oracle, monkeypatch):
     """RWKV_GRID=96: the chunk path's head GEMM (k_seq_gemm_ks) and the continuation's decode kernels run on the context's grid"""
     monkeypatch.setenv("RWKV_GRID", "96")
-    _chunk_vs_oracle(eng_mod, oracle, 1, 1088, 40)
+    _chunk_vs_oracle(eng, oracle, 1, 1088, 40)
 
 
-def test_chunk_is_deterministic(eng_mod):
+def test_chunk_is_deterministic(eng):
     L, D, T = 2, 1024, 32
     t = mf.synthetic_tensors(L, D, seed=77)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t, maxGPT=T)
     toks = _toks(T, 5)
-    a = m.forward(toks, eng_mod.MODE_GPT)[: T * mf.VOCAB].copy()
+    a = m.forward(toks, eng.MODE_GPT)[: T * mf.VOCAB].copy()
     m.reset_state()
-    b = m.forward(toks, eng_mod.MODE_GPT)[: T * mf.VOCAB].copy()
+    b = m.forward(toks, eng.MODE_GPT)[: T * mf.VOCAB].copy()
     assert np.array_equal(a, b)      # integer contraction + exact LDS sums: no order dependence
     m.close()
 
 
 @pytest.mark.parametrize("L,D,T", [(2, 768, 3), (2, 1024, 32), (1, 4096, 17), (2, 256, 40), (2, 768, 70), (1, 1024, 96),
                                    (2, 448, 70), (1, 1088, 96), (1, 4160, 40)])
-def test_parralel_batch_vs_oracle(eng_mod, oracle, L, D, T):
+def test_parralel_batch_vs_oracle(eng, oracle, L, D, T):
     """PARRALEL mode (rwkv.cu:236-240): T independent sequences advance one token per call, state slot t;
     the engine runs the batch through the MFMA path (weights read once for all streams)."""
     t = mf.synthetic_tensors(L, D, seed=500 + D + T)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t, maxGPT=T)
     om = oracle.from_tensors(L, D, t)
     sp = om.new_state(slots=T)
     for rnd in range(3):                     # the state of every slot carries over between rounds
         toks = _toks(T, 1000 * rnd + T)
         ref = om.forward(toks, sp, mode=0)
-        got = m.forward(toks, eng_mod.MODE_PARRALEL)[: T * mf.VOCAB].reshape(T, mf.VOCAB)
+        got = m.forward(toks, eng.MODE_PARRALEL)[: T * mf.VOCAB].reshape(T, mf.VOCAB)
         for i in range(T):
             parity.check_logits(got[i], ref[i], f"L{L} D{D} round {rnd} slot {i}")
             parity.check_argmax(got[i], ref[i], f"L{L} D{D} round {rnd} slot {i}")
@@ -123,9 +115,9 @@ def _adversarial(L, D, seed):
 
 
 @pytest.mark.parametrize("L,D", [(2, 1024), (1, 4096)])
-def test_adversarial_statistics_decode_and_chunk(eng_mod, oracle, L, D):
+def test_adversarial_statistics_decode_and_chunk(eng, oracle, L, D):
     t = _adversarial(L, D, seed=900 + D)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t, maxGPT=16)
     om = oracle.from_tensors(L, D, t)
     st = om.new_state()
@@ -134,7 +126,7 @@ def test_adversarial_statistics_decode_and_chunk(eng_mod, oracle, L, D):
         parity.check_logits(m.forward(tk)[: mf.VOCAB], ref, f"adversarial D{D} decode {step}")
     toks = _toks(16, D + 1)                                 # then a chunk from that state (per-token exact scales)
     ref = om.forward(toks, st)
-    got = m.forward(toks, eng_mod.MODE_GPT)[: 16 * mf.VOCAB].reshape(16, mf.VOCAB)
+    got = m.forward(toks, eng.MODE_GPT)[: 16 * mf.VOCAB].reshape(16, mf.VOCAB)
     for i in range(16):
         parity.check_logits(got[i], ref[i], f"adversarial D{D} chunk pos {i}")
     m.pull_state(1)
@@ -144,17 +136,17 @@ def test_adversarial_statistics_decode_and_chunk(eng_mod, oracle, L, D):
 
 
 @pytest.mark.parametrize("L,D,T,mode", [(4, 768, 200, "gpt"), (3, 1024, 97, "gpt"), (2, 768, 70, "par")])
-def test_long_prompt_two_stage_pipeline_is_bit_identical(eng_mod, oracle, L, D, T, mode, monkeypatch):
+def test_long_prompt_two_stage_pipeline_is_bit_identical(eng, oracle, L, D, T, mode, monkeypatch):
     """A forward call of several chunks runs as a two-stage software pipeline on two streams (engine.hip rwkv_forward: layers
     [0, mid) of chunk i + 1 under layers [mid, L) + head of chunk i).  Same kernels on the same data: every logits row and the
     whole recurrent state must equal the one-stream schedule (RWKV_SEQ_STAGES=1) bit for bit -- and the oracle within tolerance."""
     t = mf.synthetic_tensors(L, D, seed=700 + D + T)
     toks = _toks(T, 5 * D + T)
-    md = eng_mod.MODE_GPT if mode == "gpt" else eng_mod.MODE_PARRALEL
+    md = eng.MODE_GPT if mode == "gpt" else eng.MODE_PARRALEL
     outs = {}
     for split in ("0", "1"):
         monkeypatch.setenv("RWKV_SEQ_STAGES", "1" if split == "0" else "3")
-        m = eng_mod.RWKV(resident=True)
+        m = eng.RWKV(resident=True)
         m.loadTensors(L, D, t, maxGPT=T)
         lg = m.forward(toks, md)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
         lg2 = m.forward(toks, md)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()      # a second call: the pipeline's buffers and events are reused
@@ -175,18 +167,18 @@ def test_long_prompt_two_stage_pipeline_is_bit_identical(eng_mod, oracle, L, D, 
 
 
 @pytest.mark.parametrize("mode,T", [("gpt", 150), ("par", 96)])
-def test_seq_stages_1_to_4_are_bit_identical_and_match_the_oracle(eng_mod, oracle, mode, T, monkeypatch):
+def test_seq_stages_1_to_4_are_bit_identical_and_match_the_oracle(eng, oracle, mode, T, monkeypatch):
     """RWKV_SEQ_STAGES = 1, 2, 3 (default), 4: the software pipeline over the chunks of one forward call only re-schedules the same
     kernels on the same data -- every logits row and the whole recurrent state are bit-identical across the four settings; the
     result is the ORACLE's within tolerance in both modes (PARRALEL with more than 32 slots = several passes)."""
     L, D = 4, 768
     t = mf.synthetic_tensors(L, D, seed=811 + T)
     toks = _toks(T, 3 * T)
-    md = eng_mod.MODE_GPT if mode == "gpt" else eng_mod.MODE_PARRALEL
+    md = eng.MODE_GPT if mode == "gpt" else eng.MODE_PARRALEL
     outs = {}
     for stages in ("1", "2", "3", "4"):
         monkeypatch.setenv("RWKV_SEQ_STAGES", stages)
-        m = eng_mod.RWKV(resident=True)
+        m = eng.RWKV(resident=True)
         m.loadTensors(L, D, t, maxGPT=T)
         lg = m.forward(toks, md)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
         lg2 = m.forward(toks, md)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()      # second call: buffers and events reused
@@ -215,7 +207,7 @@ def test_seq_stages_1_to_4_are_bit_identical_and_match_the_oracle(eng_mod, oracl
 
 @pytest.mark.parametrize("mode,T,L,D", [("gpt", 150, 3, 768), ("gpt", 64, 2, 2048), ("gpt", 47, 2, 1024), ("par", 96, 3, 768), ("par", 70, 2, 2560), ("gpt", 70, 1, 5120), ("gpt", 96, 1, 4096),
                                         ("gpt", 70, 1, 1088), ("gpt", 64, 1, 4160), ("par", 96, 1, 5056), ("gpt", 47, 2, 448)])
-def test_64_row_passes_are_bit_identical_to_32_row_chunks(eng_mod, oracle, mode, T, L, D, monkeypatch):
+def test_64_row_passes_are_bit_identical_to_32_row_chunks(eng, oracle, mode, T, L, D, monkeypatch):
     """Round 4: a forward call of more than 32 rows runs in passes of up to 64 rows = TWO halves that share every weight fragment
     (seq.hip.h SEQ_TM; k_seq_gemm_p with NH = 2, the element-wise kernels on a global row index, k_seq_wkv over 64 rows) -- weights
     read once per 64 rows.  It is a re-scheduling of the same arithmetic: every logits row and the whole recurrent state must be
@@ -223,11 +215,11 @@ def test_64_row_passes_are_bit_identical_to_32_row_chunks(eng_mod, oracle, mode,
     modes, at 1 KiB-multiple and other row sizes; and they must be the ORACLE's within tolerance."""
     t = mf.synthetic_tensors(L, D, seed=640 + T)
     toks = _toks(T, 5 * T)
-    md = eng_mod.MODE_GPT if mode == "gpt" else eng_mod.MODE_PARRALEL
+    md = eng.MODE_GPT if mode == "gpt" else eng.MODE_PARRALEL
     outs = {}
     for rows in ("32", "64"):
         monkeypatch.setenv("RWKV_SEQ_ROWS", rows)
-        m = eng_mod.RWKV(resident=True)
+        m = eng.RWKV(resident=True)
         m.loadTensors(L, D, t, maxGPT=T)
         lg = m.forward(toks, md)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
         lg2 = m.forward(toks, md)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
@@ -249,7 +241,7 @@ def test_64_row_passes_are_bit_identical_to_32_row_chunks(eng_mod, oracle, mode,
 # k_seq_gemm_b needs octants of at least RWKV_SEQ_BDEPTH = 3 k-blocks: D = 1536 (KB = 24) is the narrowest width that has them, 4160 and 5056
 # have 8/9 and 9/10.  At 1088 (2/3 k-blocks per octant) and 128 (0/1) forcing it must fall back to k_seq_gemm_p<.., 2> and still agree.
 @pytest.mark.parametrize("T,L,D", [(70, 2, 2560), (96, 1, 4096), (64, 1, 1536), (64, 1, 4160), (96, 1, 5056), (70, 1, 1088), (40, 2, 128)])
-def test_64_row_gemm_forms_agree(eng_mod, T, L, D, monkeypatch):
+def test_64_row_gemm_forms_agree(eng, T, L, D, monkeypatch):
     """The 64-row pass has two forms of its K/V/R and ffn k/r GEMMs: k_seq_gemm_p<.., true, 2> (image re-staged per two k-blocks, plain
     workgroup ranges; RWKV_SEQ_B=0) and k_seq_gemm_b (one vector's image resident, workgroup ranges aligned to the vector groups, a wave's
     tiles in batches; RWKV_SEQ_B=5 forces both kinds, the default picks by width).  Same arithmetic per output: identical logits and state."""
@@ -261,9 +253,9 @@ def test_64_row_gemm_forms_agree(eng_mod, T, L, D, monkeypatch):
             monkeypatch.delenv("RWKV_SEQ_B", raising=False)
         else:
             monkeypatch.setenv("RWKV_SEQ_B", b)
-        m = eng_mod.RWKV(resident=True)
+        m = eng.RWKV(resident=True)
         m.loadTensors(L, D, t, maxGPT=T)
-        lg = m.forward(toks, eng_mod.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
+        lg = m.forward(toks, eng.MODE_GPT)[: T * mf.VOCAB].reshape(T, mf.VOCAB).copy()
         m.pull_state(1)
         outs[b] = (lg, [a.copy() for a in m.state.arrays()])
         m.close()
@@ -274,7 +266,7 @@ def test_64_row_gemm_forms_agree(eng_mod, T, L, D, monkeypatch):
 
 
 @pytest.mark.parametrize("T,L,D", [(150, 3, 768), (64, 2, 2048), (20, 2, 1024)])
-def test_captured_passes_replay_bit_identically(eng_mod, T, L, D, monkeypatch):
+def test_captured_passes_replay_bit_identically(eng, T, L, D, monkeypatch):
     """GPT-mode passes are captured as hipGraphs at first use (one per layer range, residual buffer, row count and logits row) and
     replayed afterwards (engine.hip enqueue_pass; RWKV_GRAPH bit 1 clear: direct launches).  First call (capture + launch), second call
     (replay) and the direct launches must agree bit for bit, logits and state, also when a different prompt goes through the same graphs."""
@@ -283,12 +275,12 @@ def test_captured_passes_replay_bit_identically(eng_mod, T, L, D, monkeypatch):
     outs = {}
     for gr in ("0", "1"):
         monkeypatch.setenv("RWKV_GRAPH", "1" if gr == "0" else "3")
-        m = eng_mod.RWKV(resident=True)
+        m = eng.RWKV(resident=True)
         m.loadTensors(L, D, t, maxGPT=T)
         res = []
         for tk in (toks, toks, toks2, toks[: T // 2 + 1]):      # the last: a shorter call through the SAME context's graphs (other ragged pass)
             m.reset_state()
-            lg = m.forward(tk, eng_mod.MODE_GPT)[: len(tk) * mf.VOCAB].reshape(len(tk), mf.VOCAB).copy()
+            lg = m.forward(tk, eng.MODE_GPT)[: len(tk) * mf.VOCAB].reshape(len(tk), mf.VOCAB).copy()
             m.pull_state(1)
             res.append((lg, [a.copy() for a in m.state.arrays()]))
         outs[gr] = res

@@ -8,8 +8,8 @@ import subprocess
 import sys
 
 import pytest
+from support import ROOT
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PROBE = "import sys; sys.path.insert(0, %r)\n%s\nfrom rwkv_cpp_accelerated_amd import engine\nprint('RCCL=' + engine.RWKV.pipe_rccl_path())"
 
 

@@ -12,7 +12,8 @@ import pytest
 import sampler_cases as sc
 from sampler_recipe import sampler_u, sampler_weights
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import build_app
+
 DBL_MIN = 2.2250738585072014e-308
 
 RUNS = sc.all_runs()
@@ -21,10 +22,7 @@ IDS = [f"{c.name}-t{temp}-tau{tau}-{'ban0' if ban0 else 'noban'}-{'recipe' if re
 
 @pytest.fixture(scope="module")
 def app(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("sampc") / "sampler_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "sampler_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe])
-    return exe
+    return build_app("sampler_app", tmp_path_factory.mktemp("sampc"), link=False, opt="-O2")
 
 
 def banned(name, ban0):

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import sampler_cases as sc
+from support import eng, load, plant_rows  # noqa: F401
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
@@ -22,30 +23,11 @@ ROWS = 4                      # maxGPT of the planted context: rows 0, 1 and 3 (
 
 
 @pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-@pytest.fixture(scope="module")
-def ctx(eng_mod):
-    m = eng_mod.RWKV(resident=True)
-    m.loadTensors(2, 64, mf.synthetic_tensors(2, 64, seed=3), maxGPT=ROWS)
+def ctx(eng):
+    m = load(eng, 2, 64, 3, ROWS)
     m.forward(5)
     yield m
     m.close()
-
-
-def plant(m, rows):
-    """rows: {logits row: float32 vector}"""
-    import torch
-    view = sc.logits_view(m, ROWS)
-    for r, vec in rows.items():
-        view[r].copy_(torch.from_numpy(np.array(vec, np.float32)).cuda())          # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
 
 
 def run_case(m, name, row, label):
@@ -53,7 +35,7 @@ def run_case(m, name, row, label):
     case, bad = sc.CASES[name], []
     for (temp, tau, ban0) in case.runs:
         if name == "d1025" and ban0:
-            plant(m, {row: sc.logits_of(name, True)})         # (its tie set has one more id under ban0: sampler_cases' docstring)
+            plant_rows(m, {row: sc.logits_of(name, True)}, ROWS)         # (its tie set has one more id under ban0: sampler_cases' docstring)
         for recipe in case.modes:
             r = sc.ref_of(name, temp, tau, ban0, recipe)
             excused = mismatched = 0
@@ -80,7 +62,7 @@ def run_case(m, name, row, label):
 
 @pytest.mark.parametrize("name", list(sc.CASES))
 def test_planted_case_matches_the_log_space_reference(ctx, name):
-    plant(ctx, {0: sc.logits_of(name, False)})
+    plant_rows(ctx, {0: sc.logits_of(name, False)}, ROWS)
     bad = run_case(ctx, name, 0, name)
     assert not bad, f"{len(bad)} draws, first (case, temp, tau, ban0, recipe, u, device, reference, why): {bad[:4]}"
 
@@ -91,7 +73,7 @@ def test_rows_are_addressed_one_by_one_case_r(ctx):
     bad = []
     for shift in (0, 1):
         names = [sc.ROW_CASES[(k - shift) % 3] for k in range(3)]
-        plant(ctx, {r: sc.logits_of(n, False) for r, n in zip(where, names)})
+        plant_rows(ctx, {r: sc.logits_of(n, False) for r, n in zip(where, names)}, ROWS)
         for r, n in zip(where, names):
             bad += run_case(ctx, n, r, f"r{shift}/{n}@{r}")
     assert not bad, f"{len(bad)} draws, first (case, temp, tau, ban0, recipe, u, device, reference, why): {bad[:4]}"
@@ -102,9 +84,8 @@ L, D, N_GEN, TEMP, TAU = 2, 256, 16, 0.01, 0.8
 
 
 @pytest.fixture(scope="module")
-def model(eng_mod):
-    m = eng_mod.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=12, head_scale=30.0), maxGPT=ROWS)
+def model(eng):
+    m = load(eng, L, D, 12, ROWS, head_scale=30.0)
     yield m
     m.close()
 
@@ -134,7 +115,7 @@ def test_decode_typical_near_greedy_equals_the_reference_loop(model, recipe):
 
 
 @pytest.mark.parametrize("recipe", [False, True])
-def test_decode_batch_typical_near_greedy_equals_the_reference_loop(eng_mod, model, recipe):
+def test_decode_batch_typical_near_greedy_equals_the_reference_loop(eng, model, recipe):
     m, first, seeds = model, [9, 4242, 30000], [11, 22, 33]
     m.reset_state()
     got = m.decode_batch_typical(first, N_GEN, temp=TEMP, tau=TAU, seeds=seeds, recipe=recipe).astype(np.int64)
@@ -142,6 +123,6 @@ def test_decode_batch_typical_near_greedy_equals_the_reference_loop(eng_mod, mod
     m.reset_state()
     ids = list(first)
     for step in range(N_GEN):
-        lg = m.forward(ids, eng_mod.MODE_PARRALEL)[: 3 * mf.VOCAB].reshape(3, mf.VOCAB).copy()
+        lg = m.forward(ids, eng.MODE_PARRALEL)[: 3 * mf.VOCAB].reshape(3, mf.VOCAB).copy()
         ids = [follow(lg[s], sc.splitmix_u(seeds[s], step), int(got[s, step]), recipe, f"stream {s} step {step}") for s in range(3)]
     assert ((got > 0) & (got < mf.VOCAB)).all()

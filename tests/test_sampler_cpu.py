@@ -10,16 +10,14 @@ import pytest
 
 from sampler_recipe import sampler_u
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import build_app
+
 V = 50277
 
 
 @pytest.fixture(scope="module")
 def app(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("samp") / "sampler_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "sampler_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe])
-    return exe
+    return build_app("sampler_app", tmp_path_factory.mktemp("samp"), link=False, opt="-O2")
 
 
 @pytest.mark.parametrize("truncate", [False, True])     # False: the reference as compiled; True: the documented recipe

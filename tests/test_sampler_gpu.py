@@ -8,29 +8,12 @@ import numpy as np
 import pytest
 
 from sampler_recipe import sampler_weights, sampler_u
-from sampler_cases import logits_view
+from sampler_cases import logits_view, splitmix_u
+from support import eng  # noqa: F401
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-def splitmix_u(seed, step):
-    m = (1 << 64) - 1
-    x = (seed + step + 0x9E3779B97F4A7C15) & m
-    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & m
-    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & m
-    x ^= x >> 31
-    return (x >> 11) / 9007199254740992.0
 
 
 def _near_boundary(logits, temp, tau, u, ban0, recipe, eps=1e-6):
@@ -45,9 +28,9 @@ def _near_boundary(logits, temp, tau, u, ban0, recipe, eps=1e-6):
 
 @pytest.mark.parametrize("recipe", [False, True])
 @pytest.mark.parametrize("temp,tau", [(0.9, 0.8), (1.0, 0.95), (0.5, 0.2), (2.0, 0.999), (1.0, 1.5), (0.3, 0.5)])
-def test_sample_matches_host_recipe(eng_mod, temp, tau, recipe):
+def test_sample_matches_host_recipe(eng, temp, tau, recipe):
     L, D = 2, 256
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=11, head_scale=30.0))
     rng = np.random.default_rng(int(temp * 100 + tau * 1000))
     mismatches = 0
@@ -64,10 +47,10 @@ def test_sample_matches_host_recipe(eng_mod, temp, tau, recipe):
 
 
 @pytest.mark.parametrize("recipe", [False, True])
-def test_decode_typical_equals_host_loop_and_is_reproducible(eng_mod, recipe):
+def test_decode_typical_equals_host_loop_and_is_reproducible(eng, recipe):
     L, D, n = 2, 256, 24
     t = mf.synthetic_tensors(L, D, seed=12, head_scale=30.0)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t)
     ids = m.decode_typical(9, n, temp=0.45, tau=0.8, seed=1234, recipe=recipe)
     m.reset_state()
@@ -92,13 +75,13 @@ def test_decode_typical_equals_host_loop_and_is_reproducible(eng_mod, recipe):
 
 
 @pytest.mark.parametrize("k,j", [(0, 0), (1, 4), (2, 2), (0, 3)])
-def test_device_sampler_fits_the_reference_histograms(eng_mod, k, j):
+def test_device_sampler_fits_the_reference_histograms(eng, k, j):
     """PIN to the reference's own typical(): the device sampler (default mode), driven with a stratified grid of uniforms on
     the golden logits vector, against the histogram of 20 000 draws of the reference (two-sample chi-square, pooled bins)"""
     import torch
     gold = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "typical_ref.npz"))
     temp, tau = (float(x) for x in gold["pairs"][j])
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(2, 64, mf.synthetic_tensors(2, 64, seed=3))
     m.forward(5)
     logits_view(m)[0].copy_(torch.from_numpy(np.ascontiguousarray(gold["logits"][k])).cuda())

@@ -21,7 +21,8 @@ import pytest
 
 from sampler_recipe import sampler_weights
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from support import ROOT, build_app
+
 GOLD = os.path.join(ROOT, "tests", "golden", "typical_ref.npz")
 V = 50277
 
@@ -46,10 +47,7 @@ def gold():
 
 @pytest.fixture(scope="module")
 def app(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("samp") / "sampler_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O2", os.path.join(ROOT, "tests", "cpp", "sampler_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe])
-    return exe
+    return build_app("sampler_app", tmp_path_factory.mktemp("samp"), link=False, opt="-O2")
 
 
 def cases(gold):

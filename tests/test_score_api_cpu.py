@@ -4,20 +4,15 @@ needs a device, so the status codes of an unloaded context are checked by tests/
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import pytest
 
-import score_cases as sc
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
-E_ARG = -1
+from support import E_ARG, ROOT, build_app, rwkv_mod  # noqa: F401
 
 
 @pytest.fixture(scope="module")
 def score_app(built, tmp_path_factory):
-    return sc.build_score_app(str(tmp_path_factory.mktemp("cpp")))
+    return build_app("score_app", tmp_path_factory.mktemp("cpp"))
 
 
 def test_score_app_compiles_and_links(score_app):
@@ -47,10 +42,8 @@ def test_a_null_context_is_a_bad_argument(built):
     assert lib.rwkv_score(None, one, one, 1, lp, None, None) == E_ARG
 
 
-def test_pybind_module_has_score_tokens(built):
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_module_has_score_tokens(rwkv_mod):
+    rwkv = rwkv_mod
     assert callable(getattr(rwkv, "scoreTokens", None))
     for f in ("initRwkv", "loadModel", "modelForward", "initState", "getState", "initOutput", "getOutput", "typicalSample"):
         assert hasattr(rwkv, f), f                      # the reference's names stay

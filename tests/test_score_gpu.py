@@ -4,47 +4,27 @@ from: score_cases' docstring).  Planted rows at all four row alignments; rwkv_sc
 PARRALEL step; rejected calls; scratch accounting; the C++ and pybind bindings.  Every context is a synthetic 2-layer model.
 Each planted case prints its worst figures before anything is asserted (the table is in profiles/NOTES.md, "scoring on the device")."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-import sampler_cases
 import score_cases as sc
+import support
+from support import E_ARG, E_STATE, build_app, eng, load, restore, run_app, rwkv_mod, same_state, snapshot  # noqa: F401
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
 L = 2
 ROWS = 4                         # maxGPT of the planted context: rows 0 .. 3 start at the four offsets from a 16-byte boundary
 D_SEQ, MAX_SEQ = 128, 40         # the sequence context: a chunk path, pieces of 40 tokens
 D_TOK, MAX_TOK = 48, 3           # a width without a chunk path: every piece runs token by token
-E_ARG, E_STATE = -1, -4
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-def load(eng, D, max_ctx, seed, **kw):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=seed, **kw), maxGPT=max_ctx)
-    return m
 
 
 @pytest.fixture(scope="module")
 def planted(eng):
-    m = load(eng, 64, ROWS, 3)
+    m = load(eng, L, 64, 3, ROWS)
     m.forward(5)
     yield m
     m.close()
@@ -52,25 +32,21 @@ def planted(eng):
 
 @pytest.fixture(scope="module")
 def seq(eng):
-    m = load(eng, D_SEQ, MAX_SEQ, 41, head_scale=30.0)
+    m = load(eng, L, D_SEQ, 41, MAX_SEQ, head_scale=30.0)
     yield m
     m.close()
 
 
 @pytest.fixture(scope="module")
 def tok(eng):
-    m = load(eng, D_TOK, MAX_TOK, 42, head_scale=30.0)
+    m = load(eng, L, D_TOK, 42, MAX_TOK, head_scale=30.0)
     yield m
     m.close()
 
 
 def plant(m, rows):
     """rows: {logits row: case name}"""
-    import torch
-    view = sampler_cases.logits_view(m, ROWS)
-    for r, name in rows.items():
-        view[r].copy_(torch.from_numpy(np.array(sc.logits_of(name), np.float32)).cuda())      # (a copy: the cases are read-only)
-    torch.cuda.synchronize()
+    support.plant_rows(m, {r: sc.logits_of(name) for r, name in rows.items()}, ROWS)
 
 
 def want_of(queries):
@@ -108,26 +84,15 @@ def test_one_call_repeats_rows_out_of_order_across_different_cases(planted):
 
 
 # ---- a sequence, bit-tied to rwkv_forward -------------------------------------------------------------------------------------------
-def snapshot(m):
-    m.pull_state(1)
-    return [a[: L * m.num_embed].copy() for a in m.state.arrays()]
-
-
-def restore(m, snap):
-    for a, s in zip(m.state.arrays(), snap):
-        a[: L * m.num_embed] = s
-    m.push_state(1)
-
-
 def sequence_case(eng, m, n, seed):
     rng = np.random.default_rng(seed)
     tokens = [int(v) for v in rng.integers(0, mf.VOCAB, n)]
     targets = [int(v) for v in rng.integers(0, mf.VOCAB, n)]
     m.reset_state()
     m.forward([11, 4242, 30000][: min(3, m.maxContext)], eng.MODE_GPT)                   # "from the current state": not the zero state
-    start = snapshot(m)
+    start = snapshot(m, 1)
     lp, ent, am = m.score(tokens, targets)
-    dev_state = snapshot(m)
+    dev_state = snapshot(m, 1)
     last = n % m.maxContext or m.maxContext
     dev_logits = m.logits(last).copy()
     restore(m, start)
@@ -141,8 +106,7 @@ def sequence_case(eng, m, n, seed):
     wl, we, bad = sc.check(f"n={n}", lp, ent, am, w_lp, w_ent, w_am)
     print(f"D {m.num_embed} n {n}: worst |d logprob| {wl:.2e}  worst |d entropy| {we:.2e}")
     assert not bad, bad
-    for a, b in zip(dev_state, snapshot(m)):
-        assert np.array_equal(a.view(np.uint64), b.view(np.uint64))                     # the final state, bit for bit
+    same_state(dev_state, snapshot(m, 1), f"n={n}")                                      # the final state, bit for bit
     assert np.array_equal(dev_logits.view(np.uint32), m.logits(last).view(np.uint32))   # the logits buffer holds the last piece's rows
 
 
@@ -184,7 +148,7 @@ def test_rejected_calls_leave_state_and_logits_alone(eng, seq):
     u64 = C.c_uint64
     m.reset_state()
     m.forward([5, 6, 7, 8], eng.MODE_GPT)
-    state, logits = snapshot(m), m.logits(MAX_SEQ).copy()
+    state, logits = snapshot(m, 1), m.logits(MAX_SEQ).copy()
     a = lambda *v: (u64 * len(v))(*v)
     lp, ent, am = (C.c_double * 4)(), (C.c_double * 4)(), (u64 * 4)()
     R = lambda rows, targets, n, out=lp: int(lib.rwkv_score_rows(m._h, rows, targets, n, out, ent, am))
@@ -198,8 +162,7 @@ def test_rejected_calls_leave_state_and_logits_alone(eng, seq):
     assert S(a(1, mf.VOCAB), a(1, 2), 2) == E_ARG                 # a token = 50277, behind a good one
     assert S(a(1, 2), a(1, 2), 0) == E_ARG and S(a(1, 2), a(1, 2), 65537) == E_ARG
     assert S(None, a(1, 2), 2) == E_ARG and S(a(1, 2), None, 2) == E_ARG and S(a(1, 2), a(1, 2), 2, None) == E_ARG
-    for x, y in zip(state, snapshot(m)):
-        assert np.array_equal(x.view(np.uint64), y.view(np.uint64))
+    same_state(state, snapshot(m, 1), "rejected calls")
     assert np.array_equal(logits.view(np.uint32), m.logits(MAX_SEQ).view(np.uint32))
     assert R(a(0, 1), a(1, 2), 2) == 0 and S(a(1, 2), a(1, 2), 2) == 0        # entropy and argmax may be NULL
     assert int(lib.rwkv_score_rows(m._h, a(0), a(1), 1, lp, None, None)) == 0
@@ -225,7 +188,7 @@ def test_rejected_calls_leave_state_and_logits_alone(eng, seq):
 
 # ---- scratch accounting -------------------------------------------------------------------------------------------------------------
 def test_scratch_is_counted_once_per_size(eng):
-    m = load(eng, 64, 2, 9)
+    m = load(eng, L, 64, 9, 2)
     m.forward([5, 6], eng.MODE_GPT)
     r0 = m.resident_bytes()
     m.score_rows([0, 1, 0], [1, 2, 3])
@@ -247,16 +210,13 @@ PROMPT = [3, 1000, 2000, 15, 9, 77, 40000, 5, 50276, 0, 31337]
 
 @pytest.fixture(scope="module")
 def model_file(tmp_path_factory):
-    p = str(tmp_path_factory.mktemp("score") / "model.bin")
-    mf.write_bin(p, L, D_SEQ, mf.synthetic_tensors(L, D_SEQ, seed=43, head_scale=30.0))
-    return p
+    return support.model_file(tmp_path_factory, "score", L, D_SEQ, 43, head_scale=30.0)
 
 
 def test_score_app_matches_the_python_engine(eng, built, model_file, tmp_path_factory):
-    app, max_ctx = sc.build_score_app(str(tmp_path_factory.mktemp('cpp'))), 4
-    out = subprocess.run([app, model_file, str(max_ctx)] + [str(t) for t in PROMPT], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    app, max_ctx = build_app("score_app", tmp_path_factory.mktemp('cpp')), 4
+    rc, lines, raw = run_app(app, [model_file, max_ctx] + PROMPT)
+    assert rc == 0, raw
     assert lines[-1] == "score_ok"
     n, last = len(PROMPT) - 1, (len(PROMPT) - 1) % max_ctx or max_ctx
     got = np.array([float(l) for l in lines[-1 - last - n:-1 - last]])
@@ -271,9 +231,8 @@ def test_score_app_matches_the_python_engine(eng, built, model_file, tmp_path_fa
     m.close()
 
 
-def test_pybind_score_tokens_matches_the_python_engine(eng, built, model_file):
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_score_tokens_matches_the_python_engine(eng, rwkv_mod, model_file):
+    rwkv = rwkv_mod
     h = rwkv.initRwkv()
     rwkv.loadModel(h, model_file)
     rwkv.initOutput(h); rwkv.initState(h)

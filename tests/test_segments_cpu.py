@@ -6,7 +6,6 @@ context are checked by the GPU suite; a NULL context is checked here.)"""
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -14,9 +13,7 @@ import pytest
 import oracle_lib
 import segment_cases as sg
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
-E_ARG = -1
+from support import E_ARG, ROOT, build_app, headers_compile, rwkv_mod  # noqa: F401
 
 
 def test_entry_points_are_declared_exported_and_bound(built):
@@ -45,21 +42,16 @@ def test_a_null_context_is_a_bad_argument(built):
 
 
 def test_headers_compile(built, tmp_path):
-    for hdr, std, cc in (("rwkv_mi355x.h", "-std=c11", "gcc"), ("rwkv_mi355x.h", "-std=c++17", "g++"), ("rwkv.h", "-std=c++17", "g++")):
-        src = tmp_path / ("t.c" if cc == "gcc" else "t.cpp")
-        src.write_text(f'#include "{hdr}"\nint main(void) {{ return 0; }}\n')
-        subprocess.check_call([cc, std, "-fsyntax-only", "-Wall", "-I" + os.path.join(ROOT, "include"), str(src)])
+    headers_compile(tmp_path)
 
 
-def test_pybind_module_has_the_function(built):
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_module_has_the_function(rwkv_mod):
+    rwkv = rwkv_mod
     assert callable(getattr(rwkv, "modelForwardSegments", None))
 
 
 def test_segments_app_compiles_and_links(built, tmp_path):
-    app = sg.build_segments_app(str(tmp_path))
+    app = build_app("segments_app", tmp_path)
     syms = subprocess.run(["nm", "-D", "--undefined-only", app], capture_output=True, text=True).stdout
     assert "rwkv_forward_segments" in syms and "rwkv_score_rows" in syms
 

@@ -14,41 +14,10 @@ import pytest
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
 import segment_cases as sg
+from support import E_ARG, E_STATE, NAMES, build_app, eng, load, restore, rows, same_state, snapshot  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 V, MAXT = sg.V, sg.MAXT
-E_ARG, E_STATE = -1, -4
-NAMES = "xy aa bb pp dd".split()
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-def snapshot(m):
-    """the five state arrays over all 80 slots, as bit patterns [80][L D]"""
-    m.pull_state(MAXT)
-    return [a.copy().view(np.uint64).reshape(MAXT, -1) for a in m.state.arrays()]
-
-
-def restore(m, st):
-    for a, b in zip(m.state.arrays(), st):
-        a.reshape(-1)[:] = b.view(np.float64).reshape(-1)
-    m.push_state(MAXT)
-
-
-def rows(m, n):
-    return m.logits(n).copy().view(np.uint32).reshape(n, V)
-
-
-def same_state(got, want, what, slots=slice(None)):
-    for name, g, w in zip(NAMES, got, want):
-        assert np.array_equal(g[slots], w[slots]), f"{what}: {name}"
 
 
 class Width:
@@ -57,10 +26,9 @@ class Width:
     def __init__(self, eng, L, D):
         self.L, self.D = L, D
         self.t = mf.synthetic_tensors(L, D, seed=sg.SEED + D)
-        self.m = eng.RWKV(resident=True)
-        self.m.loadTensors(L, D, self.t, maxGPT=MAXT)
+        self.m = load(eng, L, D, 0, MAXT, self.t)
         sg.start_state(eng, self.m, D)
-        self.start = snapshot(self.m)
+        self.start = snapshot(self.m, MAXT)
         for x in self.start:
             x.setflags(write=False)
 
@@ -68,7 +36,7 @@ class Width:
         """(state, logits rows, last_row) of one call from the start state"""
         restore(self.m, self.start)
         last = self.m.forward_segments(segments)
-        return snapshot(self.m), rows(self.m, sum(len(ids) for _, ids in segments)), last
+        return snapshot(self.m, MAXT), rows(self.m, sum(len(ids) for _, ids in segments)), last
 
     def close(self):
         self.m.close()
@@ -96,7 +64,7 @@ def test_one_segment_is_gpt_mode_bit_for_bit(eng, widths, L, D):
         n = len(ids)
         restore(m, w.start)
         m.forward(ids, eng.MODE_GPT)
-        want, want_rows = snapshot(m), rows(m, n)
+        want, want_rows = snapshot(m, MAXT), rows(m, n)
         got, got_rows, last = w.run([(0, ids)])
         what = f"D{D} {name}"
         assert last == [n - 1], what
@@ -105,9 +73,9 @@ def test_one_segment_is_gpt_mode_bit_for_bit(eng, widths, L, D):
         # the same segment on slot 41, which holds a copy of slot 0: slot 41 gets the bits slot 0 got, every other slot stays
         restore(m, w.start)
         m.copy_state(41, 0)
-        base = snapshot(m)
+        base = snapshot(m, MAXT)
         assert m.forward_segments([(41, ids)]) == [n - 1]
-        got = snapshot(m)
+        got = snapshot(m, MAXT)
         others = [s for s in range(MAXT) if s != 41]
         same_state(got, base, what + " on slot 41, the other slots", others)
         for k, name_k in enumerate(NAMES):
@@ -116,7 +84,7 @@ def test_one_segment_is_gpt_mode_bit_for_bit(eng, widths, L, D):
     # one row on slot 0 is the one-row pass of the chunk path
     restore(m, w.start)
     m.spec_verify(4242, [])
-    want, want_row = snapshot(m), rows(m, 1)
+    want, want_row = snapshot(m, MAXT), rows(m, 1)
     got, got_row, last = w.run([(0, [4242])])
     assert last == [0]
     same_state(got, want, f"D{D} (0, 1) against spec_verify")
@@ -168,7 +136,7 @@ def test_two_calls_chain_like_one(eng, widths, L, D):
     restore(w.m, w.start)
     w.m.forward_segments(segs)
     last2 = w.m.forward_segments(more)
-    got, got_rows = snapshot(w.m), rows(w.m, 12)
+    got, got_rows = snapshot(w.m, MAXT), rows(w.m, 12)
     longer = [(s, a + b) for (s, a), (_, b) in zip(segs, more)]
     want, want_rows, last = w.run(longer)
     same_state(got, want, f"D{D} MIX64 then 3 more per slot")
@@ -198,7 +166,7 @@ def test_against_the_statement_over_the_oracle(eng, oracle, widths, L, D, name):
     if name == "PAR40":                                              # against rwkv_forward(PARRALEL): the bound is asserted, bit equality is reported
         restore(w.m, w.start)
         w.m.forward([ids[0] for _, ids in segs], eng.MODE_PARRALEL)
-        par, par_rows = snapshot(w.m), rows(w.m, 40)
+        par, par_rows = snapshot(w.m, MAXT), rows(w.m, 40)
         parity.check_logits(got_rows.view(np.float32), par_rows.view(np.float32), what + " against forward(PARRALEL)")
         eq = {n_: bool(np.array_equal(g, p)) for n_, g, p in zip(NAMES, got, par)}
         print(f"{what} against rwkv_forward(PARRALEL): state bitwise equal {eq}, logits bitwise equal {bool(np.array_equal(got_rows, par_rows))}")
@@ -235,13 +203,13 @@ def test_refused_calls_leave_state_and_logits_as_they_were(eng, widths):
     ]
     restore(m, w.start)
     m.forward_segments([(3, [5, 6, 7]), (0, [8])])                    # four logits rows and a state to keep
-    state, logits = snapshot(m), rows(m, MAXT)
+    state, logits = snapshot(m, MAXT), rows(m, MAXT)
     for args, status, text in cases:
         rc = int(lib.rwkv_forward_segments(*[h[v] if isinstance(v, str) else v for v in args]))
         err = lib.rwkv_last_error().decode()
         print(f"{args[0]}: status {rc}, {err!r}")
         assert rc == status and text in err, (args, err)
-        same_state(snapshot(m), state, text)
+        same_state(snapshot(m, MAXT), state, text)
         assert np.array_equal(rows(m, MAXT), logits), text
     assert lib.rwkv_forward_segments(h["M"], ids(5, 6), sl((0, 2)), 1, 0, None) == 0       # last_row may be NULL
     for k, v in ctx.items():
@@ -273,7 +241,7 @@ def test_segments_app_prints_the_engine_rows(eng, tmp_path):
     t = mf.synthetic_tensors(L, D, seed=sg.SEED + 5)
     path = str(tmp_path / "model.bin")
     mf.write_bin(path, L, D, t)
-    app = sg.build_segments_app(str(tmp_path))
+    app = build_app("segments_app", tmp_path)
     r = subprocess.run([app, path], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("segments_ok"), (r.returncode, r.stdout, r.stderr)
     lines = [l.split() for l in r.stdout.splitlines() if l.startswith(("last", "argmax"))]

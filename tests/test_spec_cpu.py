@@ -6,16 +6,13 @@ status codes of a context are checked by the GPU suite; a NULL context is checke
 import ctypes as C
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import spec_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
-E_ARG = -1
+from support import E_ARG, ROOT, build_app, headers_compile, rwkv_mod  # noqa: F401
 
 
 @pytest.fixture(scope="module")
@@ -76,22 +73,17 @@ def test_a_null_context_is_a_bad_argument(built):
 
 
 def test_headers_compile(built, tmp_path):
-    for hdr, std, cc in (("rwkv_mi355x.h", "-std=c11", "gcc"), ("rwkv_mi355x.h", "-std=c++17", "g++"), ("rwkv.h", "-std=c++17", "g++")):
-        src = tmp_path / ("t.c" if cc == "gcc" else "t.cpp")
-        src.write_text(f'#include "{hdr}"\nint main(void) {{ return 0; }}\n')
-        subprocess.check_call([cc, std, "-fsyntax-only", "-Wall", "-I" + os.path.join(ROOT, "include"), str(src)])
+    headers_compile(tmp_path)
 
 
-def test_pybind_module_has_the_spec_functions(built):
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
+def test_pybind_module_has_the_spec_functions(rwkv_mod):
+    rwkv = rwkv_mod
     for f in ("specVerify", "decodeSpeculative"):
         assert callable(getattr(rwkv, f, None)), f
 
 
 def test_spec_app_compiles_and_links(built, tmp_path):
-    app = sc.build_spec_app(str(tmp_path))
+    app = build_app("spec_app", tmp_path)
     syms = subprocess.run(["nm", "-D", "--undefined-only", app], capture_output=True, text=True).stdout
     assert "rwkv_spec_verify" in syms and "rwkv_decode_speculative" in syms
 

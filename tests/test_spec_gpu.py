@@ -12,49 +12,11 @@ import pytest
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
 import spec_cases as sc
+from support import E_ARG, E_STATE, NAMES, build_app, eng, load, restore, rows, same_state, snapshot  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 V, MAXT = sc.V, sc.MAXT
-E_ARG, E_STATE = -1, -4
-NAMES = "xy aa bb pp dd".split()
 TOKEN = 4242                                 # the id fed first in the width cases
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
-
-
-def load(eng, L, D, seed, tensors=None):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, mf.synthetic_tensors(L, D, seed=seed) if tensors is None else tensors, maxGPT=MAXT)
-    return m
-
-
-def snapshot(m):
-    """the five state arrays over all 34 slots, as bit patterns"""
-    m.pull_state(MAXT)
-    return [a.copy().view(np.uint64) for a in m.state.arrays()]
-
-
-def restore(m, st):
-    for a, b in zip(m.state.arrays(), st):
-        a[:] = b.view(np.float64)
-    m.push_state(MAXT)
-
-
-def rows(m, n):
-    return m.logits(n).copy().view(np.uint32).reshape(n, V)
-
-
-def same_state(got, want, what, slots=slice(None)):
-    for name, g, w in zip(NAMES, got, want):
-        n = g.size // MAXT
-        assert np.array_equal(g.reshape(MAXT, n)[slots], w.reshape(MAXT, n)[slots]), f"{what}: {name}"
 
 
 class Width:
@@ -63,12 +25,12 @@ class Width:
     def __init__(self, eng, L, D):
         self.L, self.D = L, D
         self.t = mf.synthetic_tensors(L, D, seed=sc.SEED + D)
-        self.m = load(eng, L, D, 0, self.t)
+        self.m = load(eng, L, D, 0, MAXT, self.t)
         m = self.m
         rng = np.random.default_rng(D)
         m.forward([int(v) for v in rng.integers(1, V, MAXT)], eng.MODE_PARRALEL)     # a history on every slot
         m.forward([7, 50000, 11, 9], eng.MODE_GPT)                                    # and a prompt on slot 0
-        self.start = snapshot(m)
+        self.start = snapshot(m, MAXT)
         # g[i] = the pick of row i of forward([TOKEN, g[0 .. i - 1]]); the state and the rows that forward of a + 1 >= 2 rows leaves
         self.g, self.state, self.rows = [], {}, {}
         restore(m, self.start)
@@ -77,7 +39,7 @@ class Width:
         for a in range(1, sc.MAX_DRAFT + 1):
             restore(m, self.start)
             m.forward([TOKEN] + self.g[:a], eng.MODE_GPT)
-            self.state[a] = snapshot(m)
+            self.state[a] = snapshot(m, MAXT)
             self.rows[a] = rows(m, a + 1)
             self.g.append(sc.pick(m.logits(a + 1)[a * V:]))
         for a in self.state:
@@ -108,13 +70,13 @@ def test_rollback_is_exact(eng, widths, L, D, n_draft):
     m = w.m
     restore(m, w.start)
     assert m.spec_verify(TOKEN, []) == (0, w.g[0])                   # n_draft = 0: a plain step on the chunk path
-    zero, zero_row = snapshot(m), rows(m, 1)
+    zero, zero_row = snapshot(m, MAXT), rows(m, 1)
     for label, d, a_want in sc.planted(w.g, n_draft):
         restore(m, w.start)
         a, nx = m.spec_verify(TOKEN, d)
         what = f"D{D} n_draft {n_draft} wrong id {label}"
         assert (a, nx) == (a_want, w.g[a_want]), what
-        got = snapshot(m)
+        got = snapshot(m, MAXT)
         same_state(got, w.start, what + ", slots 1 .. 33", slice(1, None))
         if a >= 1:
             same_state(got, w.state[a], what)
@@ -132,16 +94,15 @@ def test_one_row_pass_is_within_the_chunk_bounds_of_the_oracle(eng, oracle, widt
     m = w.m
     restore(m, w.start)
     assert m.spec_verify(TOKEN, []) == (0, w.g[0])
-    zero, zero_row = snapshot(m), rows(m, 1)
+    zero, zero_row = snapshot(m, MAXT), rows(m, 1)
     om = oracle.from_tensors(L, D, w.t)
-    st = [s.view(np.float64)[: L * D].copy() for s in w.start]
+    st = [s.view(np.float64)[0].copy() for s in w.start]
     ref = om.forward([TOKEN], st)
     om.close()
-    n = L * D
     for l in range(L):
         lo = slice(l * D, (l + 1) * D)
         for k, tol in ((0, parity.TOL), (1, 1e-4), (2, 1e-4), (4, parity.TOL)):
-            e = parity._close(zero[k].view(np.float64)[:n][lo], st[k][lo], f"D{D} a = 0, layer {l} state {NAMES[k]}", tol)
+            e = parity._close(zero[k].view(np.float64)[0][lo], st[k][lo], f"D{D} a = 0, layer {l} state {NAMES[k]}", tol)
             print(f"D{D} a = 0 layer {l} {NAMES[k]}: {e:.2e}")
     assert np.array_equal(zero[3], w.start[3])                       # pp: the chunk path does not use it
     parity.check_logits(zero_row[0].view(np.float32), ref[0], f"D{D} a = 0 logits")
@@ -157,7 +118,7 @@ def test_three_verifies_chain_like_one_forward(eng, widths, L, D):
     assert m.spec_verify(TOKEN, d) == (2, g[2])                      # consumed TOKEN, g[0], g[1]
     assert m.spec_verify(g[2], g[3:7]) == (4, g[7])                  # g[2] .. g[6], all of the draft stands
     assert m.spec_verify(g[7], [sc.wrong(g[8])]) == (0, g[8])      # g[7]
-    same_state(snapshot(m), w.state[8], f"D{D} after three verifies")     # = forward([TOKEN] + g[:8]) from the start state
+    same_state(snapshot(m, MAXT), w.state[8], f"D{D} after three verifies")     # = forward([TOKEN] + g[:8]) from the start state
 
 
 def test_draft_ids_at_the_edges(eng, widths):
@@ -172,9 +133,9 @@ def test_draft_ids_at_the_edges(eng, widths):
             restore(m, w.start)
             assert m.spec_verify(TOKEN, d) == (p, g[p]), (planted_id, p)
     # a model whose every row picks 50276 (the last id of the vocabulary): a draft of that id is accepted exactly as far as it says so
-    e = load(eng, L, D, 0, sc.edge_tensors(L, D, sc.SEED))
+    e = load(eng, L, D, 0, MAXT, sc.edge_tensors(L, D, sc.SEED))
     e.forward([5, 6], eng.MODE_GPT)
-    st = snapshot(e)
+    st = snapshot(e, MAXT)
     for d, a_want in (([V - 1] * 5, 5), ([V - 1, V - 1, 7, V - 1], 2), ([V - 2, V - 1], 0), ([V - 1] * 31, 31)):
         restore(e, st)
         assert e.spec_verify(9, d) == (a_want, V - 1), d
@@ -186,11 +147,11 @@ def trio(eng):
     """the loop's target (3 x 320), a second context with the same weights, a narrower draft of another seed, and the reference ids"""
     L, D = 3, 320
     t = mf.synthetic_tensors(L, D, seed=sc.SEED + 1)
-    target, same, other = load(eng, L, D, 0, t), load(eng, L, D, 0, t), load(eng, 3, 64, sc.SEED + 2)
+    target, same, other = load(eng, L, D, 0, MAXT, t), load(eng, L, D, 0, MAXT, t), load(eng, 3, 64, sc.SEED + 2, MAXT)
     prompt = [5, 6, 7, 800, 9]
     for m in (target, same, other):
         m.forward(prompt, eng.MODE_GPT)
-    start = {m: snapshot(m) for m in (target, same, other)}
+    start = {m: snapshot(m, MAXT) for m in (target, same, other)}
     ids, t_ = [], 100
     for _ in range(60):                                              # repeated spec_verify(n_draft = 0): the continuation every loop must give
         t_ = target.spec_verify(t_, [])[1]
@@ -202,9 +163,9 @@ def trio(eng):
     h = tp[mf.HEAD].reshape(D, V).copy()
     h[:, banned] = 0
     tp[mf.HEAD] = h.reshape(-1)
-    part = load(eng, L, D, 0, tp)
+    part = load(eng, L, D, 0, MAXT, tp)
     part.forward(prompt, eng.MODE_GPT)
-    start[part] = snapshot(part)
+    start[part] = snapshot(part, MAXT)
     yield dict(target=target, same=same, other=other, part=part, banned=banned, start=start, ids=ids, first=100)
     for m in (target, same, other, part):
         m.close()
@@ -242,7 +203,7 @@ def after_forward(eng, m, start, toks):
         n = len(toks) if len(toks) <= 32 else (32 if len(toks) != 33 else 31)
         m.forward(toks[:n], eng.MODE_GPT)
         toks = toks[n:]
-    return snapshot(m)
+    return snapshot(m, MAXT)
 
 
 @pytest.mark.parametrize("k", [1, 4, 31])
@@ -271,11 +232,11 @@ def test_loop_does_not_depend_on_the_draft(eng, trio, draft, k):
         assert 0 < stats["accepted"] < stats["drafted"] and (k == 1 or stats["rounds"] * (k + 1) > N + k)
     assert sc.pick(target.logits(1)) == ids[N - 1]                   # the row the last id was picked from is row 0
     fed = [first] + ids[:N - 1]
-    t_state = snapshot(target)
+    t_state = snapshot(target, MAXT)
     same_state(t_state, after_forward(eng, target, trio["start"][target], fed), f"{draft} k {k}: target", slice(0, 1))
     same_state(t_state, trio["start"][target], f"{draft} k {k}: target slots 1 .. 33", slice(1, None))
     if dm is not None:
-        d_state = snapshot(dm)
+        d_state = snapshot(dm, MAXT)
         want = after_forward(eng, dm, trio["start"][dm], fed)
         draft_close(d_state, want, f"{draft} k {k}: draft state")
     # a second call continues
@@ -289,7 +250,7 @@ def test_loop_does_not_depend_on_the_draft(eng, trio, draft, k):
         reset()
         got, stats = run(first, n, [])
         assert got.tolist() == ids[:n]
-        t_got, d_got = snapshot(target), snapshot(dm) if dm is not None else None
+        t_got, d_got = snapshot(target, MAXT), snapshot(dm, MAXT) if dm is not None else None
         same_state(t_got, after_forward(eng, target, trio["start"][target], [first] + ids[:n - 1]) if n >= 2 else t1_state(target, trio, first),
                    f"{draft} k {k} n_tokens {n}", slice(0, 1))
         if dm is not None:                                           # the draft context has consumed the same ids and no more
@@ -298,15 +259,14 @@ def test_loop_does_not_depend_on_the_draft(eng, trio, draft, k):
                 dm.forward([first] + ids[:n - 1], eng.MODE_GPT)
             else:
                 dm.forward(first)
-            draft_close(d_got, snapshot(dm), f"{draft} k {k} n_tokens {n}: draft state")
+            draft_close(d_got, snapshot(dm, MAXT), f"{draft} k {k} n_tokens {n}: draft state")
 
 
 def draft_close(got, want, what):
     """slot 0 of the draft context within 1e-4, as tests/test_widths_gpu.py holds the decode kernels to the chunk path (pp: where the chunk path,
     which does not use it, was the reference, only the other four)"""
     for name, g_, r_ in zip(NAMES, got, want):
-        n = g_.size // MAXT
-        g0, r0 = g_.view(np.float64)[:n], r_.view(np.float64)[:n]
+        g0, r0 = g_.view(np.float64)[0], r_.view(np.float64)[0]
         if name != "pp":
             assert np.abs(g0 - r0).max() <= 1e-4 * max(1.0, np.abs(r0).max()), f"{what} {name}"
 
@@ -324,28 +284,28 @@ def test_lookup_drafts_are_verified_like_any_other(eng, trio):
     print(f"lookup on a repeating history: rounds {stats['rounds']} drafted {stats['drafted']} accepted {stats['accepted']}")
     assert got.tolist() == ids[:N]
     assert stats == dict(rounds=N - 6, drafted=8, accepted=6), stats      # [r, r, w, 7] -> 2 stand; [r, r, r, r] -> 4 stand
-    same_state(snapshot(target), after_forward(eng, target, trio["start"][target], [first] + ids[:N - 1]), "lookup, repeating history", slice(0, 1))
+    same_state(snapshot(target, MAXT), after_forward(eng, target, trio["start"][target], [first] + ids[:N - 1]), "lookup, repeating history", slice(0, 1))
     # the clamp of the draft to what n_tokens leaves room for: two ids asked, one drafted, it stands, nothing beyond is consumed
     restore(target, trio["start"][target])
     got, stats = target.decode_lookup(fake + [first], 2, k=4, n=2)
     assert got.tolist() == ids[:2] and stats == dict(rounds=1, drafted=1, accepted=1), stats
-    same_state(snapshot(target), after_forward(eng, target, trio["start"][target], [first, ids[0]]), "lookup, n_tokens 2", slice(0, 1))
+    same_state(snapshot(target, MAXT), after_forward(eng, target, trio["start"][target], [first, ids[0]]), "lookup, n_tokens 2", slice(0, 1))
 
 
 def t1_state(target, trio, first):
     restore(target, trio["start"][target])
     target.spec_verify(first, [])
-    return snapshot(target)
+    return snapshot(target, MAXT)
 
 
 def test_ids_equal_plain_greedy_decode_where_the_margin_is_proved(eng):
     """the model, prompt and first token of spec_cases.PLAIN: tests/test_spec_cpu.py proves on the oracle that every step's top-two gap is at
     least 1e-3 of the row's largest |logit|, 30 times what the decode kernels and the chunk path are allowed to differ by"""
     p = sc.PLAIN
-    target, dm = load(eng, p["L"], p["D"], p["seed"]), load(eng, p["L"], p["D"], p["seed"])
+    target, dm = load(eng, p["L"], p["D"], p["seed"], MAXT), load(eng, p["L"], p["D"], p["seed"], MAXT)
     for m in (target, dm):
         m.forward(list(p["prompt"]), eng.MODE_GPT)
-    st = snapshot(target)
+    st = snapshot(target, MAXT)
     want = target.decode_greedy(p["first"], p["n"]).tolist()
     restore(target, st)
     got, stats = target.decode_speculative(dm, p["first"], p["n"], 4)
@@ -363,7 +323,7 @@ def test_refused_calls_leave_state_and_logits_as_they_were(eng, widths):
     u64 = C.c_uint64
     arr = lambda *v: (u64 * len(v))(*v)
     t = mf.synthetic_tensors(2, 64, seed=1)
-    ctx = dict(M=m, U=eng.RWKV(resident=True), S=eng.RWKV(resident=True), N=eng.RWKV(resident=True), D=load(eng, 2, 64, 1, t), D4=eng.RWKV(resident=True))
+    ctx = dict(M=m, U=eng.RWKV(resident=True), S=eng.RWKV(resident=True), N=eng.RWKV(resident=True), D=load(eng, 2, 64, 1, MAXT, t), D4=eng.RWKV(resident=True))
     ctx["S"].set_layer_range(0, 1)
     ctx["S"].loadTensors(2, 64, t, maxGPT=MAXT)
     ctx["N"].loadTensors(2, 64, t, maxGPT=1)                          # no chunk path: max context 1
@@ -397,16 +357,16 @@ def test_refused_calls_leave_state_and_logits_as_they_were(eng, widths):
     ]
     restore(m, w.start)
     m.forward([TOKEN] + w.g[:3], eng.MODE_GPT)                       # four logits rows and a state to keep
-    state, logits = snapshot(m), rows(m, MAXT)
-    dstate = snapshot(ctx["D"])
+    state, logits = snapshot(m, MAXT), rows(m, MAXT)
+    dstate = snapshot(ctx["D"], MAXT)
     for entry, args, status, text in cases:
         rc = int(getattr(lib, entry)(*[h[v] if isinstance(v, str) else v for v in args]))
         err = lib.rwkv_last_error().decode()
         print(f"{entry}{args[:1]}: status {rc}, {err!r}")
         assert rc == status and text in err, (entry, args, err)
-        same_state(snapshot(m), state, entry)
+        same_state(snapshot(m, MAXT), state, entry)
         assert np.array_equal(rows(m, MAXT), logits), entry
-        same_state(snapshot(ctx["D"]), dstate, entry + " (draft)")
+        same_state(snapshot(ctx["D"], MAXT), dstate, entry + " (draft)")
     for k, v in ctx.items():
         if k != "M":
             v.close()
@@ -419,7 +379,7 @@ def test_spec_app_prints_the_engine_ids(eng, tmp_path):
     mf.write_bin(pt, L, D, tt); mf.write_bin(pd, 2, 64, td)
     target, dm = eng.RWKV(resident=True), eng.RWKV(resident=True)
     target.loadTensors(L, D, tt, maxGPT=k + 2); dm.loadTensors(2, 64, td, maxGPT=k + 2)
-    app = sc.build_spec_app(str(tmp_path))
+    app = build_app("spec_app", tmp_path)
     r = subprocess.run([app, pt, pd, str(n), str(k)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.strip().endswith("spec_ok"), (r.returncode, r.stdout, r.stderr)
     lines = [l for l in r.stdout.splitlines() if l.startswith(("ids", "stats", "verify", "spec_ok"))]

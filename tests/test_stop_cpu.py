@@ -6,25 +6,20 @@ import ctypes as C
 import os
 import re
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import stop_cases as sc
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
-E_ARG = -1
+from support import E_ARG, ROOT, build_app, rwkv_mod, syntax_only  # noqa: F401
+
 NEW = ("rwkv_decode_batch_until", "rwkv_debug_stop_scan")
 
 
 @pytest.fixture(scope="module")
 def scan_app(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("cpp") / "stop_scan_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", os.path.join(ROOT, "tests", "cpp", "stop_scan_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-o", exe])
-    return exe
+    return build_app("stop_scan_app", tmp_path_factory.mktemp("cpp"), link=False, extra=("-Wall",))
 
 
 def run_twin(exe, path, cases):
@@ -121,7 +116,7 @@ def test_null_arguments_are_bad_arguments(built):
     assert lib.rwkv_debug_stop_scan(None, one, one, 1, 1, C.byref(sp), ln, ln) == E_ARG
 
 
-def test_cpp_header_and_pybind_offer_the_wrappers(built, tmp_path):
+def test_cpp_header_and_pybind_offer_the_wrappers(rwkv_mod, tmp_path):
     src = tmp_path / "use_until.cpp"
     src.write_text('#include "rwkv.h"\n'
                    "unsigned use(RWKV &m) {\n"
@@ -132,9 +127,5 @@ def test_cpp_header_and_pybind_offer_the_wrappers(built, tmp_path):
                    "    std::vector<unsigned long long> h;\n"
                    "    return r.len[0] + r.reason[1] + (unsigned)r.steps_run + stop_scan({1, 2}, 3, stop.sequences, 0, h).len;\n"
                    "}\n")
-    out = subprocess.run(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-I" + os.path.join(ROOT, "include"), str(src)], capture_output=True, text=True)
-    assert out.returncode == 0, out.stderr[-3000:]
-    assert built["pybind"], "pybind module not built"
-    sys.path.insert(0, CSRC)
-    import rwkv
-    assert callable(getattr(rwkv, "decodeUntil", None))
+    syntax_only(src)
+    assert callable(getattr(rwkv_mod, "decodeUntil", None))

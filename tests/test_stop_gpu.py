@@ -4,31 +4,19 @@ the plain rwkv_decode_batch_* calls: the picks, and for every length the state, 
 steps leaves.  Every comparison is exact."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import stop_cases as sc
+from support import E_ARG, E_STATE, build_app, eng, firsts_of, load, restore, run_app, seeds_of, slots, start_state  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 L, D, MAXN, STEPS = 3, 256, 96, sc.STEPS
-E_ARG, E_STATE = -1, -4
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "rwkv-cpp-accelerated_amd", "csrc")
 NUC = dict(temp=1.0, top_p=0.9, presence=0.4, frequency=0.4, decay=0.996)      # nucleus with penalties: the counts are part of a slot
 KINDS = ["greedy", "typical", "nucleus"]
-
-
-@pytest.fixture(scope="module")
-def eng(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
 
 
 @pytest.fixture(scope="module")
@@ -38,45 +26,15 @@ def tensors():
 
 @pytest.fixture(scope="module")
 def model(eng, tensors):
-    m = eng.RWKV(resident=True)
-    m.loadTensors(L, D, tensors, maxGPT=MAXN)
+    m = load(eng, L, D, 21, MAXN, tensors)
     yield m
     m.close()
 
 
 @pytest.fixture(scope="module")
 def start(eng, model):
-    """distinct state in every slot (a few PARRALEL steps of different tokens): where every run of this module starts"""
-    model.reset_state()
-    rng = np.random.default_rng(5)
-    for _ in range(3):
-        model.forward([int(v) for v in rng.integers(1, mf.VOCAB, MAXN)], eng.MODE_PARRALEL)
-    model.pull_state(MAXN)
-    return [a.copy() for a in model.state.arrays()]
-
-
-def restore(m, snap):
-    for a, s in zip(m.state.arrays(), snap):
-        a[:] = s
-    m.push_state(MAXN)
-
-
-def slots(m, n, counts):
-    """what the invariant covers, per slot: the five state arrays [n][L D], the logits rows [n][V] and (counts) the count vectors [n][V]"""
-    m.pull_state(n)
-    out = [a[: n * L * D].reshape(n, L * D).copy() for a in m.state.arrays()]
-    out.append(m.logits(n).reshape(n, mf.VOCAB).copy())
-    if counts:
-        out.append(np.stack([m.penalty_get(s) for s in range(n)]))
-    return out
-
-
-def firsts_of(n):
-    return [int(v) for v in np.random.default_rng(3).integers(1, mf.VOCAB, n)]
-
-
-def seeds_of(n):
-    return [1000 + 7 * s for s in range(n)]
+    """distinct state in every slot: where every run of this module starts"""
+    return start_state(eng, model, MAXN)
 
 
 def plain(m, kind, first, steps, seeds, keep=False):
@@ -363,7 +321,7 @@ def test_host_authoritative_mode(eng, tensors, start):
     m.loadTensors(L, D, tensors, maxGPT=8)
     n = 6
     for a, s in zip(m.state.arrays(), start):
-        a[:] = s.reshape(MAXN, L * D)[:8].ravel()
+        a[:] = s.view(np.float64)[:8].ravel()
     first = firsts_of(n)
     ids, ln, rs, _ = m.decode_batch_until(first, 8, max_new=[1 + s for s in range(n)])
     dev = [np.zeros(8 * L * D) for _ in range(5)]
@@ -378,9 +336,7 @@ def test_host_authoritative_mode(eng, tensors, start):
 
 def test_stop_app_matches_python_engine(built, tmp_path):
     from rwkv_cpp_accelerated_amd import engine
-    exe = str(tmp_path / "stop_app")
-    subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "cpp", "stop_app.cpp"),
-                           "-I" + os.path.join(ROOT, "include"), "-L" + CSRC, "-lrwkv_mi355x", "-Wl,-rpath," + CSRC, "-o", exe])
+    exe = build_app("stop_app", tmp_path)
     Lm, Dm, n, steps = 2, 256, 5, 16
     t = mf.synthetic_tensors(Lm, Dm, seed=31, head_scale=30.0)
     p = str(tmp_path / "model.bin")
@@ -399,9 +355,8 @@ def test_stop_app_matches_python_engine(built, tmp_path):
     U = m.decode_batch_nucleus(first, steps, seeds=list(range(n)), **NUC).astype(np.int64)
     stop = [int(U[1][3]), int(U[1][4])]
     budgets = [steps, steps, 3, steps, 7]
-    out = subprocess.run([exe, p, str(n), str(steps), *[str(v) for v in budgets], "--", *[str(v) for v in stop]], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0, out.stdout + out.stderr
-    lines = [l for l in out.stdout.splitlines() if l.strip() and not l.startswith(("n_layers", "n_embed"))]
+    rc, lines, raw = run_app(exe, [p, n, steps, *budgets, "--", *stop])
+    assert rc == 0, raw
     assert lines[-1] == "stop_ok"
     rows = np.array([[int(x) for x in l.split()] for l in lines[-1 - n:-1]], np.int64)          # per stream: len reason ids...
     prefill()

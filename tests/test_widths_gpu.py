@@ -10,29 +10,20 @@ import pytest
 
 from rwkv_cpp_accelerated_amd import modelfile as mf
 import parity
+from support import E_STATE, eng  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-E_STATE = -4
 L, MAXT, T = 2, 8, 5
 WIDTHS = [80, 1040]
-
-
-@pytest.fixture(scope="module")
-def eng_mod(built):
-    import torch
-    assert torch.cuda.is_available(), "these tests need the GPU box"
-    from rwkv_cpp_accelerated_amd import engine
-    engine.lib()
-    return engine
 
 
 def _toks(n, seed):
     return [int(v) for v in np.random.default_rng(seed).integers(2, mf.VOCAB, n)]
 
 
-def _load(eng_mod, D, seed):
+def _load(eng, D, seed):
     t = mf.synthetic_tensors(L, D, seed=seed)
-    m = eng_mod.RWKV(resident=True)
+    m = eng.RWKV(resident=True)
     m.loadTensors(L, D, t, maxGPT=MAXT)
     return t, m
 
@@ -44,13 +35,13 @@ def _snapshot(m):
 
 @pytest.mark.parametrize("mode", ["gpt", "par"])
 @pytest.mark.parametrize("D", WIDTHS)
-def test_forward_of_several_tokens_falls_back_to_token_by_token_and_matches_the_oracle(eng_mod, oracle, D, mode):
+def test_forward_of_several_tokens_falls_back_to_token_by_token_and_matches_the_oracle(eng, oracle, D, mode):
     """forward(5 tokens) in GPT mode (one sequence on slot 0) and in PARRALEL mode (five sequences on slots 0 .. 4), three rounds that
     continue from each other's state: every logits row, its argmax and the five state arrays over all eight slots are the oracle's"""
-    t, m = _load(eng_mod, D, 1300 + D)
+    t, m = _load(eng, D, 1300 + D)
     om = oracle.from_tensors(L, D, t)
     st = om.new_state(slots=MAXT)
-    md, omode = (eng_mod.MODE_GPT, 1) if mode == "gpt" else (eng_mod.MODE_PARRALEL, 0)
+    md, omode = (eng.MODE_GPT, 1) if mode == "gpt" else (eng.MODE_PARRALEL, 0)
     for rnd in range(3):
         toks = _toks(T, 100 * rnd + D)
         ref = om.forward(toks, st, mode=omode)
@@ -64,11 +55,11 @@ def test_forward_of_several_tokens_falls_back_to_token_by_token_and_matches_the_
 
 
 @pytest.mark.parametrize("D", WIDTHS)
-def test_batched_decode_of_two_streams_is_refused_and_one_stream_is_the_decode_loop(eng_mod, D):
-    t, m = _load(eng_mod, D, 1400 + D)
-    lib = eng_mod.lib()
+def test_batched_decode_of_two_streams_is_refused_and_one_stream_is_the_decode_loop(eng, D):
+    t, m = _load(eng, D, 1400 + D)
+    lib = eng.lib()
     u64 = C.c_uint64
-    m.forward(_toks(T, D), eng_mod.MODE_PARRALEL)                   # a history on slots 0 .. 4
+    m.forward(_toks(T, D), eng.MODE_PARRALEL)                   # a history on slots 0 .. 4
     before = _snapshot(m)
     out = (u64 * 64)()
     ft, seeds = (u64 * 2)(11, 12), (u64 * 2)(3, 4)
@@ -98,12 +89,12 @@ def test_batched_decode_of_two_streams_is_refused_and_one_stream_is_the_decode_l
 
 
 @pytest.mark.parametrize("D", WIDTHS)
-def test_stage_chunk_is_refused_and_launches_nothing(eng_mod, D):
-    t, m = _load(eng_mod, D, 1500 + D)
-    m.forward(_toks(T, D), eng_mod.MODE_GPT)
+def test_stage_chunk_is_refused_and_launches_nothing(eng, D):
+    t, m = _load(eng, D, 1500 + D)
+    m.forward(_toks(T, D), eng.MODE_GPT)
     before = _snapshot(m)
     logits = m.logits(MAXT).copy()
-    with pytest.raises(eng_mod.RWKVError, match=r"multiple of 64.*status -4"):
+    with pytest.raises(eng.RWKVError, match=r"multiple of 64.*status -4"):
         m.stage_chunk(_toks(T, 1), T)
     m.sync()
     for a, b in zip(before, _snapshot(m)):
@@ -112,12 +103,12 @@ def test_stage_chunk_is_refused_and_launches_nothing(eng_mod, D):
     m.close()
 
 
-def test_pipe_prefill_is_refused_on_a_width_without_the_chunk_path(eng_mod):
+def test_pipe_prefill_is_refused_on_a_width_without_the_chunk_path(eng):
     """rwkv_pipe_prefill has the same check behind rwkv_pipe_init: a one-rank transport, as in test_pipeline_gpu.py"""
-    t, m = _load(eng_mod, 1040, 1600)
-    m.pipe_init(eng_mod.RWKV.pipe_unique_id(), 0, 1)
+    t, m = _load(eng, 1040, 1600)
+    m.pipe_init(eng.RWKV.pipe_unique_id(), 0, 1)
     before = _snapshot(m)
-    with pytest.raises(eng_mod.RWKVError, match=r"multiple of 64.*status -4"):
+    with pytest.raises(eng.RWKVError, match=r"multiple of 64.*status -4"):
         m.pipe_prefill(_toks(40, 2), 40)
     for a, b in zip(before, _snapshot(m)):
         assert np.array_equal(a, b)
