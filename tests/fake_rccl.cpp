@@ -9,10 +9,14 @@
 // Transport: one POSIX shared-memory segment per communicator (its name travels in the 128-byte unique id), one channel per
 // (source, destination) pair: a ring of SLOTS staging slots with a produced / consumed sequence pair.  All of it STREAM
 // ORDERED like the real calls, and -- like the real calls -- every wait is made ON THE DEVICE, in the stream:
-//   send  = a one-lane kernel that waits for room in the ring, hipMemcpyAsync device -> slot (the segment is hipHostRegister'ed),
-//           then a host function that publishes the slot
-//   recv  = a one-lane kernel that waits for the slot's sequence number, hipMemcpyAsync slot -> device, then a host function that
-//           frees it
+//   send  = a one-lane kernel that waits for room in the ring, hipMemcpyAsync device -> pinned staging, then a host function that
+//           copies the staging into the slot and publishes it
+//   recv  = a one-lane kernel that waits for the slot's sequence number, a host function that copies the slot into pinned staging,
+//           hipMemcpyAsync staging -> device, then a host function that frees the slot
+// The segment itself is plain host memory that the device never addresses (registering an existing mapping with hipHostRegister is
+// not possible on every machine, a virtual one for instance): what the device touches is allocated pinned with hipHostMalloc -- the
+// staging, the failure word, and a per-process MIRROR of the sequence numbers the wait kernels poll, which one host thread per
+// communicator keeps equal to the counters in the segment.
 // No host function ever blocks: HIP runs the host functions of all of a process's streams on one thread, so a blocking wait in one
 // stream's callback held back the publishing callbacks of the process's OTHER streams -- with two communicators on two streams per
 // rank (rwkv_pipe_decode_dual) two ranks could wait for each other that way until the time-out (seen once in a full GPU-suite run).
@@ -58,16 +62,34 @@ struct Segment {
 };
 size_t seg_bytes(int n) { return sizeof(Segment) + (size_t)n * n * SLOTS * SLOT_BYTES; }
 
+struct Pinned {
+    int failed;
+    char pad[60];
+    uint64_t produced[MAX_RANKS];              // of channel [peer][this rank]: what the peer has published
+    uint64_t consumed[MAX_RANKS];              // of channel [this rank][peer]: what the peer has freed
+};
+
 struct Comm {
     Segment *seg = nullptr;
     size_t bytes = 0;
     int rank = 0, nranks = 1;
     std::string name;
     uint64_t sent[MAX_RANKS] = {}, recvd[MAX_RANKS] = {};     // messages enqueued so far per peer
-    Segment *seg_dev = nullptr;                                // the segment as the device addresses it
-    int *failed = nullptr;                                     // pinned host word, written by a wait kernel that gave up (or a size mismatch)
+    Pinned *pin = nullptr;                                     // what the wait kernels read and write (hipHostMalloc)
+    int *failed = nullptr;                                     // &pin->failed: written by a wait kernel that gave up (or a size mismatch)
+    char *stage[2][MAX_RANKS] = {};                            // pinned staging rings, [0] sends / [1] receives, per peer, made at first use
+    std::thread mirror;                                        // keeps pin->produced / pin->consumed equal to the segment's counters
+    std::atomic<bool> stop{false};
     uint64_t wait_ticks = 0;                                   // WAIT_MS in ticks of the device's wall clock
     bool has_failed() const { return __atomic_load_n(failed, __ATOMIC_ACQUIRE) != 0; }
+    char *staging(int dir, int peer, uint64_t seq)
+    {
+        if (!stage[dir][peer] && hipHostMalloc(reinterpret_cast<void **>(&stage[dir][peer]), SLOTS * SLOT_BYTES, hipHostMallocDefault) != hipSuccess) {
+            stage[dir][peer] = nullptr;
+            return nullptr;
+        }
+        return stage[dir][peer] + (seq % SLOTS) * SLOT_BYTES;
+    }
     char *slot(int src, int dst, uint64_t seq) const
     {
         return reinterpret_cast<char *>(seg) + sizeof(Segment) + ((((size_t)src * nranks + dst) * SLOTS) + seq % SLOTS) * SLOT_BYTES;
@@ -78,9 +100,10 @@ struct Op { bool send; void *buf; size_t bytes; int peer; Comm *c; hipStream_t s
 thread_local int g_depth = 0;
 thread_local std::vector<Op> g_queue;
 
-struct Note { Comm *c; int src, dst; uint64_t seq; size_t bytes; int what; };   // what: 0 publish, 1 check the size of what arrived, 2 free
+struct Note { Comm *c; int src, dst; uint64_t seq; size_t bytes; char *stage; int what; };   // what: 0 publish, 1 check the size of what arrived and take it, 2 free
 
-// stream-ordered wait for *flag >= least (a sequence number another PROCESS advances in the shared segment): one lane polling host memory
+// stream-ordered wait for *flag >= least (the mirror of a sequence number another PROCESS advances in the shared segment): one lane
+// polling pinned host memory
 __global__ void k_wait(const uint64_t *flag, uint64_t least, int *failed, uint64_t ticks)
 {
     const uint64_t t0 = wall_clock64();
@@ -95,7 +118,10 @@ void host_note(void *p)
     Note *n = static_cast<Note *>(p);
     Channel &ch = n->c->seg->ch[n->src][n->dst];
     switch (n->what) {
-    case 0: ch.bytes[n->seq % SLOTS] = n->bytes; ch.produced.store(n->seq + 1, std::memory_order_release); break;
+    case 0:
+        memcpy(n->c->slot(n->src, n->dst, n->seq), n->stage, n->bytes);
+        ch.bytes[n->seq % SLOTS] = n->bytes; ch.produced.store(n->seq + 1, std::memory_order_release);
+        break;
     case 1:
         if (ch.produced.load(std::memory_order_acquire) < n->seq + 1) {
             if (__atomic_load_n(n->c->failed, __ATOMIC_ACQUIRE) == 2)
@@ -104,28 +130,44 @@ void host_note(void *p)
             fprintf(stderr, "[fake_rccl] rank %d: message %llu from %d has %llu bytes, receiver asked for %zu\n", n->c->rank,
                     (unsigned long long)n->seq, n->src, (unsigned long long)ch.bytes[n->seq % SLOTS], n->bytes);
             __atomic_store_n(n->c->failed, 1, __ATOMIC_RELEASE);
+        } else {
+            memcpy(n->stage, n->c->slot(n->src, n->dst, n->seq), n->bytes);
         }
         break;
     case 2: ch.consumed.store(n->seq + 1, std::memory_order_release); break;
     }
     delete n;
 }
+void mirror_loop(Comm *c)
+{
+    while (!c->stop.load(std::memory_order_acquire)) {
+        for (int p = 0; p < c->nranks; p++) {
+            __atomic_store_n(&c->pin->produced[p], c->seg->ch[p][c->rank].produced.load(std::memory_order_acquire), __ATOMIC_RELEASE);
+            __atomic_store_n(&c->pin->consumed[p], c->seg->ch[c->rank][p].consumed.load(std::memory_order_acquire), __ATOMIC_RELEASE);
+        }
+        std::this_thread::sleep_for(std::chrono::microseconds(20));
+    }
+}
 int enqueue(const Op &o)
 {
     Comm *c = o.c;
     if (o.bytes > SLOT_BYTES || o.peer < 0 || o.peer >= c->nranks) return 4;   // ncclInvalidArgument (a hop to the rank itself is allowed, as in NCCL >= 2.7 inside a group: the send is enqueued first)
     if (o.send) {
+        char *stage = c->staging(0, o.peer, c->sent[o.peer]);
+        if (!stage) return 1;
         const uint64_t seq = c->sent[o.peer]++;
         if (seq >= (uint64_t)SLOTS)
-            k_wait<<<dim3(1), dim3(1), 0, o.st>>>(reinterpret_cast<const uint64_t *>(&c->seg_dev->ch[c->rank][o.peer].consumed), seq - SLOTS + 1, c->failed, c->wait_ticks);
-        if (hipMemcpyAsync(c->slot(c->rank, o.peer, seq), o.buf, o.bytes, hipMemcpyDeviceToHost, o.st) != hipSuccess) return 1;
-        if (hipLaunchHostFunc(o.st, host_note, new Note{c, c->rank, o.peer, seq, o.bytes, 0}) != hipSuccess) return 1;
+            k_wait<<<dim3(1), dim3(1), 0, o.st>>>(&c->pin->consumed[o.peer], seq - SLOTS + 1, c->failed, c->wait_ticks);
+        if (hipMemcpyAsync(stage, o.buf, o.bytes, hipMemcpyDeviceToHost, o.st) != hipSuccess) return 1;
+        if (hipLaunchHostFunc(o.st, host_note, new Note{c, c->rank, o.peer, seq, o.bytes, stage, 0}) != hipSuccess) return 1;
     } else {
+        char *stage = c->staging(1, o.peer, c->recvd[o.peer]);
+        if (!stage) return 1;
         const uint64_t seq = c->recvd[o.peer]++;
-        k_wait<<<dim3(1), dim3(1), 0, o.st>>>(reinterpret_cast<const uint64_t *>(&c->seg_dev->ch[o.peer][c->rank].produced), seq + 1, c->failed, c->wait_ticks);
-        if (hipLaunchHostFunc(o.st, host_note, new Note{c, o.peer, c->rank, seq, o.bytes, 1}) != hipSuccess) return 1;
-        if (hipMemcpyAsync(o.buf, c->slot(o.peer, c->rank, seq), o.bytes, hipMemcpyHostToDevice, o.st) != hipSuccess) return 1;
-        if (hipLaunchHostFunc(o.st, host_note, new Note{c, o.peer, c->rank, seq, o.bytes, 2}) != hipSuccess) return 1;
+        k_wait<<<dim3(1), dim3(1), 0, o.st>>>(&c->pin->produced[o.peer], seq + 1, c->failed, c->wait_ticks);
+        if (hipLaunchHostFunc(o.st, host_note, new Note{c, o.peer, c->rank, seq, o.bytes, stage, 1}) != hipSuccess) return 1;
+        if (hipMemcpyAsync(o.buf, stage, o.bytes, hipMemcpyHostToDevice, o.st) != hipSuccess) return 1;
+        if (hipLaunchHostFunc(o.st, host_note, new Note{c, o.peer, c->rank, seq, o.bytes, nullptr, 2}) != hipSuccess) return 1;
     }
     if (hipGetLastError() != hipSuccess) return 1;
     return c->has_failed() ? 2 : 0;
@@ -170,26 +212,25 @@ int ncclCommInitRank(void **comm, int nranks, ncclUniqueId id, int rank)
     close(fd);
     if (p == MAP_FAILED) { delete c; return 2; }
     c->seg = static_cast<Segment *>(p);
-    if (hipHostRegister(p, c->bytes, hipHostRegisterPortable | hipHostRegisterMapped) != hipSuccess) { munmap(p, c->bytes); delete c; return 1; }
-    void *dp = nullptr;
     int dev = 0, khz = 0;
-    if (hipHostGetDevicePointer(&dp, p, 0) != hipSuccess || hipHostMalloc(reinterpret_cast<void **>(&c->failed), 64, hipHostMallocMapped) != hipSuccess ||
-        hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) {
-        (void)hipHostUnregister(p); munmap(p, c->bytes); delete c; return 1;
+    if (hipHostMalloc(reinterpret_cast<void **>(&c->pin), sizeof(Pinned), hipHostMallocMapped) != hipSuccess) { munmap(p, c->bytes); delete c; return 1; }
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, dev) != hipSuccess || khz <= 0) {
+        (void)hipHostFree(c->pin); munmap(p, c->bytes); delete c; return 1;
     }
-    c->seg_dev = static_cast<Segment *>(dp);
-    *c->failed = 0;
+    memset(c->pin, 0, sizeof(Pinned));
+    c->failed = &c->pin->failed;
     c->wait_ticks = (uint64_t)khz * (uint64_t)WAIT_MS;
     c->seg->nranks = (uint32_t)nranks;
     c->seg->joined.fetch_add(1);
     const auto t0 = std::chrono::steady_clock::now();
     while (c->seg->joined.load() < (uint32_t)nranks) {       // like the real call: returns once every rank has joined
         if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(JOIN_MS)) {
-            (void)hipHostUnregister(p); (void)hipHostFree(c->failed); munmap(p, c->bytes); shm_unlink(c->name.c_str()); delete c;
+            (void)hipHostFree(c->pin); munmap(p, c->bytes); shm_unlink(c->name.c_str()); delete c;
             return 2;
         }
         std::this_thread::sleep_for(std::chrono::microseconds(100));
     }
+    c->mirror = std::thread(mirror_loop, c);
     *comm = c;
     return 0;
 }
@@ -199,9 +240,13 @@ int ncclCommDestroy(void *comm)
     Comm *c = static_cast<Comm *>(comm);
     if (!c) return 4;
     (void)hipDeviceSynchronize();
+    c->stop.store(true, std::memory_order_release);
+    c->mirror.join();
     const bool last = c->seg->left.fetch_add(1) + 1 == (uint32_t)c->nranks;
-    (void)hipHostUnregister(c->seg);
-    (void)hipHostFree(c->failed);
+    for (auto &dir : c->stage)
+        for (char *s : dir)
+            if (s) (void)hipHostFree(s);
+    (void)hipHostFree(c->pin);
     munmap(c->seg, c->bytes);
     if (last) shm_unlink(c->name.c_str());
     delete c;
