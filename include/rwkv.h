@@ -461,6 +461,27 @@ public:
         pull_slot0(); draft_model.pull_slot0();
         return SpecResult{std::vector<unsigned long long>(ids.begin(), ids.end()), st.rounds, st.drafted, st.accepted};
     }
+    // speculative greedy decoding for many streams (rwkv_mi355x.h "speculative greedy decoding for many streams"): the last n_draft ids of a segment
+    // are guesses; ONE pass of the chunk path verifies all segments and each slot is left after the ids that stand.  Per segment: the number of
+    // draft ids kept, the id that follows them (emitted, not fed) and the logits row it was picked from.  All rows fit one pass (64).
+    struct SpecSegment { unsigned slot; std::vector<unsigned long long> tokens; unsigned n_draft; };
+    struct SpecSegStep { unsigned accepted; unsigned long long next, row; };
+    std::vector<SpecSegStep> specVerifySegments(const std::vector<SpecSegment> &segments)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<rwkv_spec_segment> segs;
+        std::vector<uint64_t> ids;
+        for (const SpecSegment &s : segments) {
+            segs.push_back(rwkv_spec_segment{s.slot, (uint32_t)s.tokens.size(), s.n_draft, 0u});
+            ids.insert(ids.end(), s.tokens.begin(), s.tokens.end());
+        }
+        std::vector<uint32_t> a(segs.size() + 1);
+        std::vector<uint64_t> nx(segs.size() + 1), row(segs.size() + 1);
+        rwkv_detail::check(rwkv_spec_verify_segments(ctx_, ids.data(), segs.data(), segs.size(), 0, a.data(), nx.data(), row.data()));
+        std::vector<SpecSegStep> out;
+        for (size_t i = 0; i < segs.size(); i++) out.push_back(SpecSegStep{a[i], nx[i], row[i]});
+        return out;
+    }
     // segmented forward (rwkv_mi355x.h "segmented forward"): each segment is a run of consecutive tokens of the sequence on state slot `slot`
     // (the slots of one call pairwise distinct); every sequence continues from its slot and leaves it after its tokens, all behind one read of the
     // weights per pass -- decoding streams and pieces of new prompts in one call.  Row j of the logits buffer belongs to token j of the segments'

@@ -544,8 +544,9 @@ int rwkv_decode_batch_constrained(rwkv_ctx *ctx, const uint64_t *first_tokens, u
  * Status: as rwkv_spec_verify for ctx; RWKV_E_ARG also for k == 0, k > RWKV_SPEC_MAX_DRAFT, draft_ctx == ctx or NULL, a draft context on another
  * device or with max_ctx < k + 2, ctx with max_ctx < k + 1, n_tokens == 0 or above RWKV_MAX_DECODE_STEPS; RWKV_E_STATE for a draft context that is
  * not loaded or is a pipeline stage.
- * Out of scope: sampled acceptance (rejection sampling needs the draft's probabilities), draft trees, more than one stream, pipeline contexts,
- * drafts longer than one half. */
+ * More than one stream: rwkv_spec_verify_segments below verifies the drafts of many streams in one pass.
+ * Out of scope: sampled acceptance (rejection sampling needs the draft's probabilities), draft trees, pipeline contexts, drafts longer than one
+ * half. */
 #define RWKV_SPEC_MAX_DRAFT 31u
 int rwkv_spec_verify(rwkv_ctx *ctx, uint64_t token, const uint64_t *draft, uint64_t n_draft, uint64_t *n_accepted, uint64_t *next_token);
 typedef struct rwkv_spec_stats {
@@ -587,14 +588,49 @@ int rwkv_decode_speculative(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_t
  * size: the exported function assumes passes of 64 rows (rwkv_forward_segments plans for the pass size it runs).  row_slot, row_flags and n_rows
  * may each be NULL (validate only); nothing is written when the list is rejected.
  * Out of scope: a device-side decode loop with admission, a batched sampler over arbitrary (row, slot) pairs (rwkv_sample_nucleus is one call per
- * stream), logits for the last rows only, segments on pipeline-stage contexts, the same slot twice in one call, checkpointing (speculative)
- * segments. */
+ * stream), logits for the last rows only, segments on pipeline-stage contexts, the same slot twice in one call.  Checkpointing (speculative)
+ * segments are rwkv_spec_verify_segments below. */
 typedef struct rwkv_segment { uint32_t slot; uint32_t n; } rwkv_segment;   /* n >= 1 consecutive tokens of the sequence on state slot `slot` */
 int rwkv_forward_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' tokens back to back */,
                           const rwkv_segment *segs, uint64_t n_segs, uint32_t flags /* must be 0 */,
                           uint64_t *last_row /* host [n_segs], may be NULL: logits row of each segment's last token */);
 int rwkv_segment_plan(const rwkv_segment *segs, uint64_t n_segs, uint64_t max_ctx,
                       uint32_t *row_slot /* [T] */, uint8_t *row_flags /* [T], may both be NULL: validate only */, uint64_t *n_rows);
+
+/* ---- speculative greedy decoding for many streams: every stream's draft verified in ONE segmented pass (no reference counterpart) ----
+ * The rows of a call are segments as in rwkv_forward_segments; segment i is n consecutive rows on state slot `slot`, of which the first n - n_draft
+ * are CERTAIN (a decoding stream's last pick, or a piece of a prompt) and the last n_draft are GUESSES.  Three kinds of segment so share a call:
+ * n_draft == 0, a plain segment committed whole; n == n_draft + 1, the shape of rwkv_spec_verify; anything between, a prompt's tail followed by a
+ * draft.  Together they are a continuous-batching server's whole step, speculation included.
+ * With r0 the segment's first row and c = n - n_draft - 1 its last certain row, every row is picked as rwkv_spec_verify picks (logit 0 banned, ties
+ * to the lowest id) and
+ *     a_i = the number of leading j < n_draft with tokens[r0 + c + 1 + j] == pick[r0 + c + j];
+ * the slot is left after rows r0 .. r0 + c + a_i (xy, aa, bb, dd; pp is not touched); n_accepted[i] = a_i; next_token[i] = pick[r0 + c + a_i], emitted
+ * and not fed; row[i] (may be NULL) = r0 + c + a_i, the logits row it was picked from, where rwkv_topn_rows, rwkv_score_rows and rwkv_sample_nucleus
+ * read.  Logits rows 0 .. T - 1 are written, T = sum n.
+ * Arguments: n_segs >= 1; every n >= 1; n_draft <= min(n - 1, RWKV_SPEC_MAX_DRAFT); the slots pairwise distinct and below max_ctx; reserved == 0 and
+ * flags == 0; every id < 50277; T <= max_ctx; and T FITS ONE PASS as the context runs it: 64 rows, or 32 under RWKV_SEQ_ROWS=32.
+ * ONE PASS IS THE LIMIT: a verify commits nothing until it knows a, which it learns behind the head, so the piece behind a pass boundary would have
+ * no state to continue from.  A call does not chain across passes; a server cuts its step to 64 rows (longer prompt pieces go through
+ * rwkv_forward_segments first).
+ * The pass is a segmented pass that commits nothing: the state after every row goes to the checkpoint buffer rwkv_spec_verify uses, 4 L T n_embed
+ * f64, grown to the largest T seen (268 MB at 7B for 64 rows).  Behind the head one wave per segment finds a_i and a copy kernel writes the slots
+ * from the rows that stand.  Ids, row plan and segment table go up in one copy, n_segs records of 24 bytes come down in one, and the call waits
+ * once; there is no host synchronisation between the pass and the commit.  rwkv_resident_bytes counts the buffers.
+ * EXACT: the result for a segment does not depend on the other segments, on where its rows sit, or on the rejected draft ids.  Slot state and logits
+ * rows r0 .. r0 + c + a_i are bit for bit those of rwkv_forward_segments of {slot, c + a_i + 1} alone.  A single segment {0, n, n - 1} leaves slot
+ * 0, the ids and those logits rows bit for bit as rwkv_spec_verify does.  Slots not named are untouched; so are pp, the penalty counts, the stop
+ * histories and the constraint states.
+ * Status: as rwkv_forward_segments -- RWKV_E_ARG for each rule above and for a NULL ctx, tokens, segs, n_accepted or next_token; RWKV_E_STATE when
+ * not loaded, on a pipeline-stage context, or without the chunk path.  Every check runs before anything is launched or allocated: a rejected call
+ * leaves state, logits and buffers as they were.
+ * Out of scope: a draft MODEL loop for many streams (its rollback needs a snapshot slot per stream and step in the draft context), sampled
+ * acceptance, draft trees, pipeline-stage contexts. */
+typedef struct rwkv_spec_segment { uint32_t slot, n, n_draft, reserved; } rwkv_spec_segment;
+int rwkv_spec_verify_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' rows back to back */,
+                              const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags /* must be 0 */,
+                              uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,
+                              uint64_t *row /* [n_segs], may be NULL */);
 
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()

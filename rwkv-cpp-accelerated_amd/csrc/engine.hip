@@ -16,6 +16,7 @@
 #include "constrain.hip.h"
 #include "spec.hip.h"
 #include "segments.hip.h"
+#include "specseg.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -26,6 +27,7 @@
 #include <chrono>
 #include <unistd.h>
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -246,6 +248,8 @@ enum GrownBuf {
     SPEC_CKPT,                        // rwkv_spec_verify (spec.hip.h): f64 [4][L][rows][D], the verify pass's checkpoints (xy | aa | bb | dd) for the largest n_draft seen
     SPEC_REC,                         // u64: {a, next} | picks [SEQ_T]
     SEG_PLAN,                         // rwkv_forward_segments (segments.hip.h): SegRow [max_ctx], the call's row plan; allocated ONCE at the first segmented call
+    SPECSEG_IO,                       // rwkv_spec_verify_segments (specseg.hip.h), SpecSegIo: the call's ONE upload (ids | plan | per-segment table), behind it the records
+                                      // and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT, grown to 4 L T D for the largest T seen
     N_GROWN
 };
 
@@ -297,6 +301,7 @@ struct rwkv_ctx {
     Ctl *ctl = nullptr;
     Ctl *h_ctl = nullptr;    // pinned staging, maxT entries
     SegRow *h_seg_plan = nullptr;   // pinned [maxT]: what rwkv_forward_segments uploads into SEG_PLAN (allocated with it)
+    struct SpecSegIo *h_specseg = nullptr;   // pinned: what rwkv_spec_verify_segments uploads into SPECSEG_IO and downloads from it (allocated with it)
     unsigned long long *gen = nullptr;
     unsigned long long *pick = nullptr;      // device: id drawn by the sampler
     double *ts_part = nullptr;               // sampler scratch (sampler.hip.h)
@@ -1080,20 +1085,25 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     return 0;
 }
 
-// The ROW LAYOUT of a pass: what its rows are to each other -- one of four, with the one thing that layout needs besides the pass's rows.
+// The ROW LAYOUT of a pass: what its rows are to each other -- one of five, with what that layout needs besides the pass's rows.
 //   GPT        rwkv.cu:493-593: n tokens of one sequence on state slot 0, the token shift runs along the rows
 //   PARRALEL   rwkv.cu:236-240: n independent sequences, one token each, row t on state slot row0 + t -- the batched decode step
 //   CKPT       the verify pass of rwkv_spec_verify (spec.hip.h): GPT rows, one half, whole model, that commit NOTHING to slot 0 -- every row's state
 //              is left in `ckpt`, [4][L][n][D]
 //   SEGMENTED  segments.hip.h: the rows are pieces of sequences on slots of their own, as `plan` says ([rows]{slot, flags} on the device)
+//   SPECSEG    the verify pass of rwkv_spec_verify_segments (specseg.hip.h): SEGMENTED rows, one or two halves, whole model, that commit NOTHING to
+//              their slots -- every row's state is left in `ckpt`, [4][L][n][D]
 // Only GPT passes are replayed as captured graphs (enqueue_pass: its key holds a shape, no layout); the rest change from call to call and are
 // launched directly.
 struct RowLayout {
-    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED } kind = GPT;
-    union { double *ckpt = nullptr; const SegRow *plan; };
+    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED, SPECSEG } kind = GPT;
+    double *ckpt = nullptr;
+    const SegRow *plan = nullptr;
     static RowLayout of_mode(int mode) { RowLayout r; r.kind = mode == RWKV_MODE_PARRALEL ? PARRALEL : GPT; return r; }
     static RowLayout checkpoints(double *ck) { RowLayout r; r.kind = CKPT; r.ckpt = ck; return r; }
     static RowLayout segments(const SegRow *plan) { RowLayout r; r.kind = SEGMENTED; r.plan = plan; return r; }
+    static RowLayout spec_segments(const SegRow *plan, double *ck) { RowLayout r; r.kind = SPECSEG; r.plan = plan; r.ckpt = ck; return r; }
+    bool one_pass() const { return kind == CKPT || kind == SPECSEG; }      // the checkpoint arrays are laid out for ONE pass
     bool replayed() const { return kind == GPT; }
     RowLayout from_row(uint64_t t0) const { RowLayout r = *this; if (kind == SEGMENTED) r.plan += t0; return r; }      // the layout of the pass that starts at row t0 of a call
 };
@@ -1132,6 +1142,10 @@ struct SegFns {
     void (*stage)(SegStageArgs) = nullptr;
 };
 SegFns seg_fns();
+struct SpecSegFns {
+    void (*site3)(SpecSegSiteArgs) = nullptr; void (*site2)(SpecSegSiteArgs) = nullptr; void (*wkv32)(SpecSegWkvArgs) = nullptr; void (*wkv64)(SpecSegWkvArgs) = nullptr;
+};
+SpecSegFns specseg_fns();
 int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 {
     if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
@@ -1151,7 +1165,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     const bool two = n > SEQ_T;
     const SeqHalf h((size_t)D);
     // What the layout means, said once.  A site with a token shift keeps its LayerNorm output for the sequence's next row: GPT in S.state (the last
-    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT in the checkpoint rows; SEGMENTED in
+    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT and SPECSEG in the checkpoint rows; SEGMENTED in
     // the staging rows, which the WKV and stage-1 kernels behind the GEMMs commit.  The three launch helpers below (site, wkv, stage) pick their instance.
     const RowLayout &rows = pass.rows;
     const bool commits = rows.kind == RowLayout::GPT;
@@ -1159,6 +1173,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     if (rows.kind == RowLayout::SEGMENTED && !S.seg) return fail(RWKV_E_ARG, "the scratch set of a segmented pass holds the staging rows");
     const SeqCkptFns ckf = rows.kind == RowLayout::CKPT ? seq_ckpt_fns() : SeqCkptFns{};
     const SegFns sgf = rows.kind == RowLayout::SEGMENTED ? seg_fns() : SegFns{};
+    const SpecSegFns ssf = rows.kind == RowLayout::SPECSEG ? specseg_fns() : SpecSegFns{};
     const size_t ck_arr = (size_t)L * n * D;      // one of the four checkpoint arrays; layer l's rows start l * n * D into it
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
     // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
@@ -1201,6 +1216,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         switch (state ? rows.kind : RowLayout::GPT) {
         case RowLayout::SEGMENTED: (nv == 3 ? sgf.site3 : sgf.site2)<<<grid, block, 0, st>>>(SegSiteArgs{s, rows.plan, S.seg}); return;
         case RowLayout::CKPT: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ckf.site3 : ckf.site2)<<<grid, block, 0, st>>>(s); return;
+        case RowLayout::SPECSEG: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ssf.site3 : ssf.site2)<<<grid, block, 0, st>>>(SpecSegSiteArgs{s, rows.plan}); return;
         case RowLayout::PARRALEL: s.par = 1; break;
         case RowLayout::GPT: s.state_new = state ? S.state : nullptr; break;      // (and ln_out of every layout: nothing to keep)
         }
@@ -1216,6 +1232,10 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         case RowLayout::CKPT:      // (one half: refused above otherwise)
             wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
             ckf.wkv<<<grid, block, 0, st>>>(wa);
+            return;
+        case RowLayout::SPECSEG:
+            wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
+            (two ? ssf.wkv64 : ssf.wkv32)<<<grid, block, 0, st>>>(SpecSegWkvArgs{wa, rows.plan});
             return;
         default: break;
         }
@@ -1371,8 +1391,8 @@ uint64_t seq_pass_rows(const rwkv_ctx *c, uint64_t T) { return (T > (uint64_t)SE
 int enqueue_rows(rwkv_ctx *c, const uint64_t *tokens, const unsigned long long *dtok, uint64_t T, const RowLayout &rows)
 {
     if (dtok && rows.replayed()) return fail(RWKV_E_ARG, "a replayed pass takes its token ids from the host");
-    // (the checkpoint arrays are laid out for ONE pass: enqueue_verify builds its pass itself)
-    if (rows.kind == RowLayout::CKPT) return fail(RWKV_E_ARG, "a checkpointing pass is not cut into passes");
+    // (the checkpoint arrays are laid out for ONE pass: enqueue_verify and enqueue_verify_segments build their pass themselves)
+    if (rows.one_pass()) return fail(RWKV_E_ARG, "a checkpointing pass is not cut into passes");
     const uint64_t CH = seq_pass_rows(c, T);
     const uint64_t nchunks = (T + CH - 1) / CH;
     int rc = 0;
@@ -3052,6 +3072,95 @@ int rwkv_forward_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_segmen
     }());
 }
 
+// ---- speculative greedy decoding for many streams (specseg.hip.h): rwkv_spec_verify_segments ----
+static_assert(sizeof(rwkv_spec_segment) == 16 && sizeof(SpecSegEntry) == 16 && sizeof(SpecSegRec) == 24, "the records the header and the kernels share");
+namespace {
+SpecSegFns specseg_fns() { return SpecSegFns{k_specseg_site<3>, k_specseg_site<2>, k_specseg_wkv<SEQ_T>, k_specseg_wkv<SEQ_TM>}; }
+}
+// the device image of one call (SPECSEG_IO) and its pinned twin: `up` bytes go up in ONE copy, the records come down in one
+struct SpecSegIo {
+    unsigned long long ids[SEQ_TM];
+    SegRow plan[SEQ_TM];
+    SpecSegEntry tab[SEQ_TM];
+    SpecSegRec rec[SEQ_TM];           // <- not uploaded
+    unsigned long long picks[SEQ_TM];
+};
+constexpr size_t SPECSEG_UP = offsetof(SpecSegIo, rec);
+namespace {
+// the rules of a call behind the guard, all of them before anything is launched or allocated; *T_out: the rows of the call
+int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t *T_out)
+{
+    const uint64_t pass_rows = (uint64_t)(c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T);
+    if (n_segs == 0 || n_segs > pass_rows) return fail(RWKV_E_ARG, "n_segs must be in 1..%llu (the rows of one pass)", (unsigned long long)pass_rows);
+    uint64_t T = 0;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        const rwkv_spec_segment &s = segs[i];
+        if (s.n == 0) return fail(RWKV_E_ARG, "segment %llu is empty", (unsigned long long)i);
+        if (s.reserved) return fail(RWKV_E_ARG, "segment %llu: reserved must be 0", (unsigned long long)i);
+        if (s.n_draft >= s.n || s.n_draft > RWKV_SPEC_MAX_DRAFT)
+            return fail(RWKV_E_ARG, "segment %llu: n_draft %u must be in 0..%u (n - 1 = %u, and one half less a row)", (unsigned long long)i, s.n_draft,
+                        std::min<uint32_t>(s.n - 1, RWKV_SPEC_MAX_DRAFT), s.n - 1);
+        if (s.slot >= c->maxT) return fail(RWKV_E_ARG, "segment %llu: slot %u out of range, max context is %llu", (unsigned long long)i, s.slot, (unsigned long long)c->maxT);
+        T += s.n;
+        if (T > c->maxT) return fail(RWKV_E_ARG, "Context too large, max context is %llu", (unsigned long long)c->maxT);
+        if (T > pass_rows) return fail(RWKV_E_ARG, "%llu rows and more: a verify is ONE pass of at most %llu rows", (unsigned long long)T, (unsigned long long)pass_rows);
+    }
+    std::vector<uint32_t> slots(n_segs);
+    for (uint64_t i = 0; i < n_segs; i++) slots[i] = segs[i].slot;
+    std::sort(slots.begin(), slots.end());
+    for (uint64_t i = 1; i < n_segs; i++)
+        if (slots[i] == slots[i - 1]) return fail(RWKV_E_ARG, "slot %u is named twice: the slots of one call are pairwise distinct", slots[i]);
+    if (const int rc = check_ids(tokens, T, "token")) return rc;
+    *T_out = T;
+    return 0;
+}
+// Everything of one call but the wait: ids, plan and table up in one copy, the checkpointing segmented pass, the pick of every row, what stands per
+// segment, the commit of exactly those rows, and the records' download.  No host synchronisation in between.  Launched directly, as enqueue_verify is.
+int enqueue_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T)
+{
+    if (!c->h_specseg) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specseg), sizeof(SpecSegIo), hipHostMallocDefault));
+    if (const int rc = grow_buffer(c, SPECSEG_IO, sizeof(SpecSegIo))) return rc;
+    if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * T * c->D)) return rc;
+    if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, T)) return rc;
+    // (the pinned block is free: every call that used it has returned behind its wait)
+    SpecSegIo *h = c->h_specseg, *d = c->buf<SpecSegIo>(SPECSEG_IO);
+    uint64_t j = 0;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        for (uint32_t k = 0; k < segs[i].n; k++, j++) { h->ids[j] = tokens[j]; h->plan[j] = SegRow{segs[i].slot, k == 0 ? SEG_FIRST : 0u}; }
+        h->tab[i] = SpecSegEntry{(unsigned)j - segs[i].n_draft - 1u, segs[i].n_draft, segs[i].slot, 0u};
+    }
+    for (; j < (uint64_t)SEQ_TM; j++) { h->ids[j] = 0; h->plan[j] = SegRow{0u, SEG_FIRST}; }
+    HIPCHK(hipMemcpyAsync(d, h, SPECSEG_UP, hipMemcpyHostToDevice, c->stream));
+    double *ck = c->buf<double>(SPEC_CKPT);
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, d->ids, RowLayout::spec_segments(d->plan, ck)};
+    if (const int rc = enqueue_chunk(c, pass)) return rc;
+    if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)T, d->picks)) return rc;
+    k_specseg_accept<64><<<dim3((unsigned)n_segs), dim3(64), 0, c->stream>>>(SpecSegAcceptArgs{d->ids, d->picks, d->tab, d->rec});
+    const SpecSegCommitArgs ca{d->rec, d->tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
+    const unsigned pairs = (unsigned)(c->L * c->D / 2);
+    k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)n_segs), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->rec, d->rec, sizeof(SpecSegRec) * n_segs, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+} // namespace
+
+int rwkv_spec_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags, uint32_t *n_accepted,
+                              uint64_t *next_token, uint64_t *row)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs && n_accepted && next_token)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    uint64_t T = 0;
+    if (const int rc = check_verify_segments(c, tokens, segs, n_segs, &T)) return rc;
+    const int rc = finish(c, enqueue_verify_segments(c, tokens, segs, n_segs, T));
+    for (uint64_t i = 0; !rc && i < n_segs; i++) {
+        const SpecSegRec &r = c->h_specseg->rec[i];
+        n_accepted[i] = (uint32_t)r.a; next_token[i] = r.next;
+        if (row) row[i] = r.row;
+    }
+    return rc;
+}
+
 void rwkv_free(rwkv_ctx *c)
 {
     if (!c) return;
@@ -3064,6 +3173,7 @@ void rwkv_free(rwkv_ctx *c)
     for (const rwkv_ctx::Grown &g : c->grown) if (g.p) (void)hipFree(g.p);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->h_seg_plan) (void)hipHostFree(c->h_seg_plan);
+    if (c->h_specseg) (void)hipHostFree(c->h_specseg);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);

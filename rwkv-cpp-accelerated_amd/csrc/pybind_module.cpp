@@ -153,6 +153,15 @@ PYBIND11_MODULE(rwkv, m)
     }, "speculative greedy decoding: the model of handle `draft` (loaded with maxGPT >= k + 2, same prefix in slot 0) guesses k ids per round, this "
        "one verifies them in one pass: (ids [n], (rounds, drafted, accepted)); the ids do not depend on the draft model (engine extension)",
           py::arg("rwkvp"), py::arg("draft"), py::arg("first"), py::arg("n"), py::arg("k") = 4u);
+    m.def("specVerifySegments", [](std::uintptr_t h, const std::vector<std::tuple<unsigned, std::vector<int64_t>, unsigned>> &segments) {
+        std::vector<RWKV::SpecSegment> segs;
+        for (const auto &s : segments)
+            segs.push_back(RWKV::SpecSegment{std::get<0>(s), std::vector<unsigned long long>(std::get<1>(s).begin(), std::get<1>(s).end()), std::get<2>(s)});
+        std::vector<std::tuple<unsigned, unsigned long long, unsigned long long>> out;
+        for (const RWKV::SpecSegStep &r : M(h)->specVerifySegments(segs)) out.emplace_back(r.accepted, r.next, r.row);
+        return out;
+    }, "speculative greedy decoding for many streams: segments [(slot, ids, n_draft)] with pairwise distinct slots, the last n_draft ids of each are "
+       "guesses; one pass verifies them all and returns [(n_accepted, next, row)] per segment (engine extension)", py::arg("rwkvp"), py::arg("segments"));
     m.def("modelForwardSegments", [](std::uintptr_t h, const std::vector<std::pair<unsigned, std::vector<int64_t>>> &segments) {
         std::vector<RWKV::Segment> segs;
         for (const auto &s : segments) segs.push_back(RWKV::Segment{s.first, std::vector<unsigned long long>(s.second.begin(), s.second.end())});

@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "rwkv_debug_constrained_row", "rwkv_decode_batch_constrained",
     "rwkv_spec_verify", "rwkv_decode_speculative",
     "rwkv_forward_segments", "rwkv_segment_plan",
+    "rwkv_spec_verify_segments",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
@@ -120,6 +121,11 @@ class Segment(C.Structure):
     _fields_ = [("slot", C.c_uint32), ("n", C.c_uint32)]
 
 
+class SpecSegment(C.Structure):
+    """rwkv_spec_segment of include/rwkv_mi355x.h (16 bytes)"""
+    _fields_ = [("slot", C.c_uint32), ("n", C.c_uint32), ("n_draft", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def _segments(segments):
     """(Segment array, count, the packed ids) of a list of (slot, token_ids)"""
     segs = [(int(s), [int(t) for t in ids]) for s, ids in segments]
@@ -152,6 +158,35 @@ def ngram_draft(history, k: int, n: int = 3):
         if h[s:s + n] == tail:
             return h[s + n:s + n + k]
     return []
+
+
+def lookup_streams(verify, histories, n_tokens: int, k: int = 8, n: int = 3, pass_rows: int = 64):
+    """the round loop of RWKV.decode_lookup_streams over verify(segments) -> [(n_accepted, next, row)] (RWKV.spec_verify_segments): every round
+    drafts at most k ids per stream with ngram_draft and verifies all streams, stream s on slot s, in ONE pass of pass_rows rows; a stream that
+    has its n_tokens ids leaves the rounds.  Never emits or consumes more than n_tokens per stream."""
+    hist = [[int(t) for t in h] for h in histories]
+    if not hist or any(not h for h in hist):
+        raise ValueError("every history holds at least the id to feed first")
+    n_tokens, N = int(n_tokens), len(hist)
+    if N > pass_rows:
+        raise ValueError(f"{N} streams do not fit one pass of {pass_rows} rows")
+    out = [[] for _ in range(N)]
+    stats = [dict(rounds=0, drafted=0, accepted=0) for _ in range(N)]
+    while True:
+        live = [s for s in range(N) if len(out[s]) < n_tokens]
+        if not live:
+            break
+        room = pass_rows // len(live) - 1                           # draft rows a stream may bring: the round is one pass
+        segs = []
+        for s in live:
+            kd = min(int(k), SPEC_MAX_DRAFT, room, n_tokens - len(out[s]) - 1)
+            d = ngram_draft(hist[s], kd, n) if kd > 0 else []
+            segs.append((s, [hist[s][-1]] + d, len(d)))
+        for (s, ids, nd), (a, nx, _) in zip(segs, verify(segs)):
+            new = ids[1:1 + a] + [int(nx)]
+            out[s] += new; hist[s] += new
+            stats[s]["rounds"] += 1; stats[s]["drafted"] += nd; stats[s]["accepted"] += a
+    return np.asarray(out, dtype=np.int64).reshape(N, n_tokens), stats
 
 
 class Automaton(C.Structure):
@@ -304,6 +339,8 @@ def lib():
     L.rwkv_spec_verify.argtypes = [vp, u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_spec_verify.restype = i32
     L.rwkv_decode_speculative.argtypes = [vp, vp, u64, u64, C.c_uint32, C.POINTER(u64), C.POINTER(SpecStats)]; L.rwkv_decode_speculative.restype = i32
     L.rwkv_forward_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(Segment), u64, C.c_uint32, C.POINTER(u64)]; L.rwkv_forward_segments.restype = i32
+    L.rwkv_spec_verify_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(SpecSegment), u64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64)]
+    L.rwkv_spec_verify_segments.restype = i32
     L.rwkv_segment_plan.argtypes = [C.POINTER(Segment), u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(u64)]; L.rwkv_segment_plan.restype = i32
     _lib = L
     return L
@@ -861,6 +898,34 @@ class RWKV:
         if not self.resident:
             self.pull_state(slots)
         return [int(r) for r in last[:n]]
+
+    # -- speculative greedy decoding for many streams (include/rwkv_mi355x.h rwkv_spec_verify_segments) -------------------------
+    def spec_verify_segments(self, segments):
+        """one pass of the chunk path over `segments`, a list of (slot, token_ids, n_draft) with pairwise distinct slots: the last n_draft ids of
+        a segment are guesses, of which the longest prefix the greedy picks confirm is kept.  Returns [(n_accepted, next, row)] per segment: the
+        slot is left after the ids that stand, `next` is emitted and not fed, `row` is the logits row it was picked from.  All rows fit one pass."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        segs = [(int(s), [int(t) for t in ids], int(nd)) for s, ids, nd in segments]
+        n = len(segs)
+        arr = (SpecSegment * max(1, n))(*[SpecSegment(s, len(ids), nd, 0) for s, ids, nd in segs])
+        ids = [t for _, i, _ in segs for t in i]
+        toks = (C.c_uint64 * max(1, len(ids)))(*ids)
+        acc, nx, row = (C.c_uint32 * max(1, n))(), (C.c_uint64 * max(1, n))(), (C.c_uint64 * max(1, n))()
+        slots = min(self.maxContext, 1 + max([s for s, _, _ in segs], default=0))
+        if not self.resident:
+            self.push_state(slots)
+        _chk(lib().rwkv_spec_verify_segments(self._h, toks, arr, n, 0, acc, nx, row))
+        if not self.resident:
+            self.pull_state(slots)
+        return [(int(acc[i]), int(nx[i]), int(row[i])) for i in range(n)]
+
+    def decode_lookup_streams(self, histories, n_tokens: int, k: int = 8, n: int = 3):
+        """decode_lookup for N streams over spec_verify_segments (lookup_streams): stream s runs on slot s, histories[s] = its ids so far, of
+        which all but the last have been fed.  Returns (ids [N][n_tokens], [dict(rounds, drafted, accepted)] per stream); the ids of a stream
+        are those of repeated spec_verify_segments([(s, [token], 0)])."""
+        rows = 32 if int(os.environ.get("RWKV_SEQ_ROWS", "64")) <= 32 else 64
+        return lookup_streams(self.spec_verify_segments, histories, n_tokens, k, n, min(self.maxContext, rows))
 
     def decode_speculative(self, draft_model: "RWKV", first_token: int, n_tokens: int, k: int = 4):
         """greedy continuation of n_tokens ids with `draft_model` (a second loaded model on the same device whose slot 0 holds the same prefix,
