@@ -482,6 +482,54 @@ public:
         for (size_t i = 0; i < segs.size(); i++) out.push_back(SpecSegStep{a[i], nx[i], row[i]});
         return out;
     }
+    // a sampler over any (row, slot) pairs (rwkv_mi355x.h "a sampler over any (row, slot) pairs"): queries.size() independent picks in one call,
+    // each from its own logits row of the last forward with the counts of its own slot, its own parameters and its own uniform -- or, with
+    // use_seed, the draw the decode loops make at step `step` under `seed`.  A nucleus query picks what sampleNucleus picks (update: and counts
+    // it), a greedy one what decodeBatchGreedy picks.  The sampling server step: forwardSegments, then sampleRows over the last rows.
+    struct PickQuery { unsigned row = 0, slot = 0; Pick pick{}; bool ban0 = false, update = false, use_seed = false; unsigned long long seed = 0, step = 0; double u = 0.0; };
+    static rwkv_pick pickOf(const Pick &pick, unsigned flags)
+    {
+        rwkv_pick p{};
+        p.kind = pick.kind; p.temp = pick.temp; p.tau = pick.tau;
+        p.nucleus = nucleusParams(pick.s, flags);
+        return p;
+    }
+    std::vector<unsigned long long> sampleRows(const std::vector<PickQuery> &queries)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<rwkv_pick_query> qs;
+        for (const PickQuery &q : queries)
+            qs.push_back(rwkv_pick_query{q.row, q.slot, pickOf(q.pick, (q.ban0 ? RWKV_NUCLEUS_BAN0 : 0u) | (q.update ? RWKV_NUCLEUS_UPDATE : 0u)), q.seed, q.step, q.u,
+                                         q.use_seed ? RWKV_PICKQ_SEED : 0u, 0u});
+        std::vector<uint64_t> ids(qs.size() + 1);
+        rwkv_detail::check(rwkv_sample_rows(ctx_, qs.data(), qs.size(), ids.data()));
+        return std::vector<unsigned long long>(ids.begin(), ids.begin() + qs.size());
+    }
+    // specVerifySegments with SAMPLED acceptance (rwkv_mi355x.h "the segmented verify with SAMPLED acceptance"): segment i's uncertain rows are
+    // picked by picks[i] (greedy or nucleus, no penalties) with the draws of steps step0[i], step0[i] + 1, ... under seeds[i], logit 0 banned; a
+    // draft id stands where the draw confirms it.  A segment emits accepted + 1 ids: its next step0 is step0 + accepted + 1.
+    std::vector<SpecSegStep> specSampleSegments(const std::vector<SpecSegment> &segments, const std::vector<Pick> &picks,
+                                                const std::vector<unsigned long long> &seeds, const std::vector<unsigned long long> &step0)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        if (picks.size() != segments.size() || seeds.size() != segments.size() || step0.size() != segments.size())
+            throw std::runtime_error("need one pick, seed and step0 per segment");
+        std::vector<rwkv_spec_segment> segs;
+        std::vector<uint64_t> ids;
+        std::vector<rwkv_pick> pk;
+        for (const SpecSegment &s : segments) {
+            segs.push_back(rwkv_spec_segment{s.slot, (uint32_t)s.tokens.size(), s.n_draft, 0u});
+            ids.insert(ids.end(), s.tokens.begin(), s.tokens.end());
+        }
+        for (const Pick &p : picks) pk.push_back(pickOf(p, 0u));
+        const std::vector<uint64_t> sd(seeds.begin(), seeds.end()), st(step0.begin(), step0.end());
+        std::vector<uint32_t> a(segs.size() + 1);
+        std::vector<uint64_t> nx(segs.size() + 1), row(segs.size() + 1);
+        rwkv_detail::check(rwkv_spec_sample_segments(ctx_, ids.data(), segs.data(), segs.size(), pk.data(), sd.data(), st.data(), 0, a.data(), nx.data(), row.data()));
+        std::vector<SpecSegStep> out;
+        for (size_t i = 0; i < segs.size(); i++) out.push_back(SpecSegStep{a[i], nx[i], row[i]});
+        return out;
+    }
     // segmented forward (rwkv_mi355x.h "segmented forward"): each segment is a run of consecutive tokens of the sequence on state slot `slot`
     // (the slots of one call pairwise distinct); every sequence continues from its slot and leaves it after its tokens, all behind one read of the
     // weights per pass -- decoding streams and pieces of new prompts in one call.  Row j of the logits buffer belongs to token j of the segments'

@@ -545,7 +545,8 @@ int rwkv_decode_batch_constrained(rwkv_ctx *ctx, const uint64_t *first_tokens, u
  * device or with max_ctx < k + 2, ctx with max_ctx < k + 1, n_tokens == 0 or above RWKV_MAX_DECODE_STEPS; RWKV_E_STATE for a draft context that is
  * not loaded or is a pipeline stage.
  * More than one stream: rwkv_spec_verify_segments below verifies the drafts of many streams in one pass.
- * Out of scope: sampled acceptance (rejection sampling needs the draft's probabilities), draft trees, pipeline contexts, drafts longer than one
+ * Out of scope: a draft model that samples (rejection sampling then needs the draft's probabilities; sampled acceptance of a deterministic
+ * draft is rwkv_spec_sample_segments), draft trees, pipeline contexts, drafts longer than one
  * half. */
 #define RWKV_SPEC_MAX_DRAFT 31u
 int rwkv_spec_verify(rwkv_ctx *ctx, uint64_t token, const uint64_t *draft, uint64_t n_draft, uint64_t *n_accepted, uint64_t *next_token);
@@ -561,7 +562,7 @@ int rwkv_decode_speculative(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_t
  * continuous-batching server: the decoding streams' last picks and a piece of every waiting prompt, admitted on their own slots, in one call.
  * Row numbering and logits: T = sum n; row j of the call is token j of the packed array and its logits land in row j of the device logits buffer,
  * where rwkv_score_rows, rwkv_topn_rows and rwkv_sample_nucleus(row, slot) read them.  last_row[i] (may be NULL) is the row of segment i's last
- * token, the one a server picks from.
+ * token, the one a server picks from: rwkv_sample_rows below samples all of them in one call.
  * Arguments: 1 <= T <= max_ctx, n_segs >= 1, every n >= 1, every slot < max_ctx, THE SLOTS OF ONE CALL ARE PAIRWISE DISTINCT, every id < 50277,
  * flags == 0.
  * State: segment i starts from what slot segs[i].slot holds and leaves that slot after its n tokens (xy, aa, bb, dd; pp is untouched, as
@@ -587,8 +588,7 @@ int rwkv_decode_speculative(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_t
  * LayerNorm outputs and WKV state go to the slot).  A piece ends where its segment ends or where the pass ends, so the plan depends on the pass
  * size: the exported function assumes passes of 64 rows (rwkv_forward_segments plans for the pass size it runs).  row_slot, row_flags and n_rows
  * may each be NULL (validate only); nothing is written when the list is rejected.
- * Out of scope: a device-side decode loop with admission, a batched sampler over arbitrary (row, slot) pairs (rwkv_sample_nucleus is one call per
- * stream), logits for the last rows only, segments on pipeline-stage contexts, the same slot twice in one call.  Checkpointing (speculative)
+ * Out of scope: a device-side decode loop with admission, logits for the last rows only, segments on pipeline-stage contexts, the same slot twice in one call.  Checkpointing (speculative)
  * segments are rwkv_spec_verify_segments below. */
 typedef struct rwkv_segment { uint32_t slot; uint32_t n; } rwkv_segment;   /* n >= 1 consecutive tokens of the sequence on state slot `slot` */
 int rwkv_forward_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' tokens back to back */,
@@ -624,12 +624,70 @@ int rwkv_segment_plan(const rwkv_segment *segs, uint64_t n_segs, uint64_t max_ct
  * Status: as rwkv_forward_segments -- RWKV_E_ARG for each rule above and for a NULL ctx, tokens, segs, n_accepted or next_token; RWKV_E_STATE when
  * not loaded, on a pipeline-stage context, or without the chunk path.  Every check runs before anything is launched or allocated: a rejected call
  * leaves state, logits and buffers as they were.
- * Out of scope: a draft MODEL loop for many streams (its rollback needs a snapshot slot per stream and step in the draft context), sampled
- * acceptance, draft trees, pipeline-stage contexts. */
+ * Out of scope: a draft MODEL loop for many streams (its rollback needs a snapshot slot per stream and step in the draft context), draft trees,
+ * pipeline-stage contexts.  Sampled acceptance is rwkv_spec_sample_segments below. */
 typedef struct rwkv_spec_segment { uint32_t slot, n, n_draft, reserved; } rwkv_spec_segment;
 int rwkv_spec_verify_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' rows back to back */,
                               const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags /* must be 0 */,
                               uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,
+                              uint64_t *row /* [n_segs], may be NULL */);
+
+/* ---- a sampler over any (row, slot) pairs: n independent picks, one record each, in one call (no reference counterpart) ----
+ * What a continuous-batching server's step samples with: after rwkv_forward_segments the rows to pick from are last_row[i], the count vectors are
+ * whatever slots the server assigned, and every stream has its own parameters and stands at its own step.  Query j names logits row `row` of the
+ * LAST forward and the count vector of state slot `slot` (independent of each other; the vector is read only with a penalty), and picks by `pick`:
+ *   RWKV_PICK_NUCLEUS  the pick is bit for bit that of rwkv_sample_nucleus(row, slot, &pick.nucleus, u), and with RWKV_NUCLEUS_UPDATE the count
+ *                      vector of `slot` afterwards is bit for bit that call's as well (the kernels run that sampler's own bodies, csrc/pickrows.hip.h).
+ *                      nucleus.flags: RWKV_NUCLEUS_BAN0 and RWKV_NUCLEUS_UPDATE as there.  With RWKV_PICKQ_SEED the uniform is not `u` but
+ *                      uniform(splitmix64(seed + step)), the draw the decode loops make at step `step` under seed `seed`: a server stream sampled
+ *                      through this call with (seed, step = k) draws what rwkv_decode_batch_nucleus draws at its step k.
+ *   RWKV_PICK_GREEDY   the pick of rwkv_decode_batch_greedy on that row: logit 0 banned, ties to the lowest id, no winner gives 0.  No counts are
+ *                      read or touched; seed, step and u are not read.
+ * The queries are independent: rows need not be consecutive, ascending or distinct (one row under eight seeds is best-of-n from one prompt), slots
+ * need not relate to rows, and a slot that is only read may repeat.  A slot that a query UPDATES (a penalty and RWKV_NUCLEUS_UPDATE) is named by no
+ * other query with a penalty: two updates of one vector in one launch would race, and a reader next to the update would see either side of it.
+ * The call leaves logits, state, stop histories and constraint states alone; counts change only for updating queries.
+ * Traffic: one upload of the records (72 bytes each), one launch sequence of three launches per batch of 64 queries, one download of n ids;
+ * synchronous on return; works on any context with a head.  64 is one pass of the segmented forward and one round of 1024-thread workgroups on
+ * the device's compute units; the sampler's scratch (1.84 MB per row: the batched-decode scratch, grown to min(n, 64) rows -- 118 MB) stays inside
+ * the Infinity Cache.  A call of greedy queries alone allocates only the partials.  rwkv_resident_bytes counts the buffers, rwkv_free frees them.
+ * Status: RWKV_E_ARG for a NULL pointer, n == 0 or n > RWKV_MAX_PICK_ROWS, a row or slot >= max_ctx, a kind other than GREEDY or NUCLEUS, whatever
+ * rwkv_sample_nucleus rejects in the parameters, u outside [0, 1) without RWKV_PICKQ_SEED, unknown flag bits or reserved != 0, an updating slot
+ * named again; RWKV_E_STATE when the context is not loaded or has no head.  Every check runs before anything is launched or allocated: a rejected
+ * call leaves state, logits, counts and buffers as they were.
+ * Out of scope: typical sampling per query, constrained picks per query (rwkv_pick_constrained is one call per stream). */
+#define RWKV_MAX_PICK_ROWS 1024u
+#define RWKV_PICKQ_SEED 1u /* u = uniform(splitmix64(seed + step)); else the query's u */
+typedef struct rwkv_pick_query {
+    uint32_t row, slot;      /* logits row of the LAST forward; count vector of this state slot (read only with a penalty) */
+    rwkv_pick pick;          /* kind RWKV_PICK_GREEDY or RWKV_PICK_NUCLEUS; nucleus.flags: BAN0, UPDATE as in rwkv_sample_nucleus */
+    uint64_t seed, step;
+    double u;
+    uint32_t flags, reserved; /* RWKV_PICKQ_SEED; reserved must be 0 */
+} rwkv_pick_query;
+int rwkv_sample_rows(rwkv_ctx *ctx, const rwkv_pick_query *q, uint64_t n, uint64_t *tokens /* host [n] */);
+
+/* ---- the segmented verify with SAMPLED acceptance (no reference counterpart) ----
+ * With a deterministic draft -- a lookup drafter, a greedy draft model -- the proposal distribution is a point mass on the draft id x, and
+ * speculative sampling's rule (accept x with probability p(x); on rejection draw from p conditioned on != x) is exactly: draw t from p, accept if
+ * t == x, else emit t.  So this is rwkv_spec_verify_segments with each row's pick taken by the segment's sampler, and the result is a function of
+ * the seeds alone as the greedy verify's is of the logits alone.
+ * Segments, rows, the one-pass limit, checkpoints, acceptance and commit are those of rwkv_spec_verify_segments (the same kernels).  With r0 and c
+ * as there, row r0 + c + j of segment i, j = 0 .. n_draft, is picked by picks[i] with u = uniform(splitmix64(seeds[i] + step0[i] + j)); logit 0 is
+ * always banned, as in every device loop; the rows in front of c are not picked at all.  A segment emits a_i + 1 ids, drawn at steps step0[i] ..
+ * step0[i] + a_i: the caller's next step0 is step0 + a_i + 1.  A RWKV_PICK_GREEDY segment behaves as in rwkv_spec_verify_segments.
+ * The query table goes up with ids, plan and segment table in the ONE upload; there is no host synchronisation between the pass, the pick, the
+ * accept and the commit, and the call waits once.
+ * EXACT: write A for rwkv_forward_segments({slot, c + a_i + 1}) of the segment alone.  n_accepted, next_token and row do not depend on the other
+ * segments or on the rejected draft ids; the slot and logits rows r0 .. r0 + c + a_i are bit for bit those of A; next_token is bit for bit what
+ * rwkv_sample_rows picks from that row with (seed, step0 + a_i) and RWKV_NUCLEUS_BAN0 after A.
+ * Status: as rwkv_spec_verify_segments, and RWKV_E_ARG for a NULL picks, seeds or step0, RWKV_PICK_TYPICAL, whatever rwkv_sample_nucleus rejects in
+ * a pick's parameters, and a pick with a penalty.
+ * Out of scope: penalties (the counts behind row j would depend on how much of the draft stands), typical sampling, a draft model that samples (it
+ * needs the draft's probabilities), draft trees, pipeline-stage contexts. */
+int rwkv_spec_sample_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T] */, const rwkv_spec_segment *segs, uint64_t n_segs,
+                              const rwkv_pick *picks /* [n_segs] */, const uint64_t *seeds /* [n_segs] */, const uint64_t *step0 /* [n_segs] */,
+                              uint32_t flags /* must be 0 */, uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,
                               uint64_t *row /* [n_segs], may be NULL */);
 
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----

@@ -17,6 +17,7 @@
 #include "spec.hip.h"
 #include "segments.hip.h"
 #include "specseg.hip.h"
+#include "pickrows.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -250,6 +251,9 @@ enum GrownBuf {
     SEG_PLAN,                         // rwkv_forward_segments (segments.hip.h): SegRow [max_ctx], the call's row plan; allocated ONCE at the first segmented call
     SPECSEG_IO,                       // rwkv_spec_verify_segments (specseg.hip.h), SpecSegIo: the call's ONE upload (ids | plan | per-segment table), behind it the records
                                       // and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT, grown to 4 L T D for the largest T seen
+    PICKQ_IO,                         // rwkv_sample_rows (pickrows.hip.h), PickIo: the call's upload (the query table) and the ids it downloads; allocated ONCE at the
+                                      // first call.  The sampler scratch is BD_PART / BD_P / BD_PW / BD_KEY, grown to min(n, PQ_BATCH) rows
+    SPECSAMPLE_IO,                    // rwkv_spec_sample_segments, SpecSampleIo: the query table in front of a SpecSegIo, so that ONE copy still carries the upload
     N_GROWN
 };
 
@@ -302,6 +306,8 @@ struct rwkv_ctx {
     Ctl *h_ctl = nullptr;    // pinned staging, maxT entries
     SegRow *h_seg_plan = nullptr;   // pinned [maxT]: what rwkv_forward_segments uploads into SEG_PLAN (allocated with it)
     struct SpecSegIo *h_specseg = nullptr;   // pinned: what rwkv_spec_verify_segments uploads into SPECSEG_IO and downloads from it (allocated with it)
+    struct PickIo *h_pickq = nullptr;        // pinned twin of PICKQ_IO (allocated with it)
+    struct SpecSampleIo *h_specsample = nullptr;   // pinned twin of SPECSAMPLE_IO (allocated with it)
     unsigned long long *gen = nullptr;
     unsigned long long *pick = nullptr;      // device: id drawn by the sampler
     double *ts_part = nullptr;               // sampler scratch (sampler.hip.h)
@@ -1779,6 +1785,21 @@ int pick_counts(rwkv_ctx *c, const rwkv_pick &pk, uint64_t slot0, uint64_t n, bo
     return 0;
 }
 
+// What the kernels take of a nucleus pick that is not the caller's number as it stands -- derived HERE, once, for NucleusArgs (make_sampler) and
+// for the query record of pickrows.hip.h (make_pickq).  `loop`: logit 0 always banned, the counts always updated (make_sampler)
+struct NucleusDerived { double inv_temp; unsigned top_k; int penalty, update, ban0; };
+NucleusDerived derive_nucleus(const rwkv_pick &pk, bool loop)
+{
+    const rwkv_nucleus_params &p = pk.nucleus;
+    NucleusDerived d;
+    d.inv_temp = p.temp == 1.0f ? 1.0 : 1.0 / (double)p.temp;
+    d.top_k = p.top_k >= RWKV_VOCAB ? 0u : p.top_k;
+    d.penalty = pick_penalty(pk) ? 1 : 0;
+    d.update = (loop || (p.flags & RWKV_NUCLEUS_UPDATE)) ? 1 : 0;
+    d.ban0 = (loop || (p.flags & RWKV_NUCLEUS_BAN0)) ? 1 : 0;
+    return d;
+}
+
 // One call's sampler: the kind (RWKV_PICK_TYPICAL or _NUCLEUS) and that kind's kernel arguments
 struct Sampler {
     int kind = RWKV_PICK_GREEDY;
@@ -1808,12 +1829,13 @@ Sampler make_sampler(rwkv_ctx *c, const rwkv_pick &pk, bool loop)
         d.ban0 = (loop || (pk.typical_flags & RWKV_SAMPLE_BAN0)) ? 1 : 0;
     } else {
         const rwkv_nucleus_params &p = pk.nucleus;
-        s.n.inv_temp = p.temp == 1.0f ? 1.0 : 1.0 / (double)p.temp;
-        s.n.top_p = p.top_p; s.n.top_k = p.top_k >= RWKV_VOCAB ? 0u : p.top_k;
+        const NucleusDerived nd = derive_nucleus(pk, loop);
+        s.n.inv_temp = nd.inv_temp;
+        s.n.top_p = p.top_p; s.n.top_k = nd.top_k;
         s.n.presence = p.presence; s.n.frequency = p.frequency; s.n.decay = p.decay;
-        s.n.penalty = pick_penalty(pk) ? 1 : 0;
-        s.n.update = (loop || (p.flags & RWKV_NUCLEUS_UPDATE)) ? 1 : 0;
-        d.ban0 = (loop || (p.flags & RWKV_NUCLEUS_BAN0)) ? 1 : 0;
+        s.n.penalty = nd.penalty;
+        s.n.update = nd.update;
+        d.ban0 = nd.ban0;
         s.n.counts = s.n.penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
     }
     return s;
@@ -3072,7 +3094,101 @@ int rwkv_forward_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_segmen
     }());
 }
 
-// ---- speculative greedy decoding for many streams (specseg.hip.h): rwkv_spec_verify_segments ----
+// ---- a sampler over any (row, slot) pairs (pickrows.hip.h): rwkv_sample_rows, and the pick of rwkv_spec_sample_segments ----
+// Queries per launch sequence.  64: the rows of one segmented pass, so a verify's picks are one batch; one round of 1024-thread workgroups on 256
+// compute units with room left; and 64 rows of scratch (118 MB) lie inside the 256 MB Infinity Cache, where the three launches hand them on.
+constexpr unsigned PQ_BATCH = 64;
+static_assert(PQ_BATCH >= (unsigned)SEQ_TM, "the picks of one verify pass are one batch");
+static_assert(sizeof(rwkv_pick) == 48 && sizeof(rwkv_pick_query) == 88, "rwkv_pick_query is 88 bytes in the C ABI");
+// the device image of one rwkv_sample_rows call and its pinned twin: n records go up, n ids come down
+struct PickIo {
+    PickQ q[RWKV_MAX_PICK_ROWS];
+    unsigned long long out[RWKV_MAX_PICK_ROWS];
+};
+namespace {
+// the record of one query: greedy, or nucleus by pk.nucleus.  `ban`: logit 0 banned whatever the pick's flags say (the verify, as every device loop)
+PickQ make_pickq(const rwkv_pick &pk, bool ban, unsigned row, unsigned slot, unsigned out, bool use_seed, uint64_t seed, uint64_t step, double u)
+{
+    PickQ q{};
+    q.row = row; q.slot = slot; q.out = out;
+    if (pk.kind != RWKV_PICK_NUCLEUS) return q;
+    const NucleusDerived nd = derive_nucleus(pk, false);
+    q.flags = PQ_NUCLEUS | (nd.penalty ? PQ_PENALTY : 0u) | (nd.penalty && nd.update ? PQ_UPDATE : 0u) | (ban || nd.ban0 ? PQ_BAN0 : 0u) | (use_seed ? PQ_SEED : 0u);
+    q.inv_temp = nd.inv_temp; q.top_p = pk.nucleus.top_p; q.top_k = nd.top_k;
+    q.presence = pk.nucleus.presence; q.frequency = pk.nucleus.frequency; q.decay = pk.nucleus.decay;
+    q.u = u; q.seed = seed; q.step = step;
+    return q;
+}
+// the sampler scratch of `rows` queries of one batch; greedy queries alone need the partials only
+int grow_pickq_scratch(rwkv_ctx *c, uint64_t rows, bool nucleus)
+{
+    return nucleus ? grow_pick_buffers(c, RWKV_PICK_NUCLEUS, rows) : grow_buffer(c, BD_PART, sizeof(double) * rows * TS_PART_ROW);
+}
+// three launches per batch of PQ_BATCH queries of the device table dq[n], the ids into out[q.out]
+int enqueue_pickq(rwkv_ctx *c, const PickQ *dq, unsigned n, unsigned long long *out)
+{
+    PickQArgs g{dq, c->logits, c->buf<float>(PEN_COUNTS), out, c->buf<double>(BD_PART), c->buf<float>(BD_P), c->buf<unsigned>(BD_KEY), c->buf<float>(BD_PW)};
+    for (unsigned b = 0; b < n; b += PQ_BATCH) {
+        const unsigned rows = std::min(n - b, PQ_BATCH);
+        g.q = dq + b;
+        k_pickq_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(g);
+        k_pickq_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(g);
+        k_pickq<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(g);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the rules of rwkv_sample_rows behind the guard; *penalty / *nucleus: some query has one / is one
+int check_pick_queries(const rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, bool *penalty, bool *nucleus)
+{
+    if (n == 0 || n > RWKV_MAX_PICK_ROWS) return fail(RWKV_E_ARG, "n must be in 1..%u", RWKV_MAX_PICK_ROWS);
+    std::vector<uint32_t> upd, rd;       // the slots that penalty queries update / only read
+    *penalty = *nucleus = false;
+    for (uint64_t i = 0; i < n; i++) {
+        if (const int rc = check_row_slot(c, q[i].row, q[i].slot)) return rc;
+        if (q[i].pick.kind != RWKV_PICK_GREEDY && q[i].pick.kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "query %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, q[i].pick.kind);
+        if ((q[i].flags & ~RWKV_PICKQ_SEED) || q[i].reserved) return fail(RWKV_E_ARG, "query %llu: unknown flag bits (0x%x) or reserved != 0", (unsigned long long)i, q[i].flags);
+        if (q[i].pick.kind == RWKV_PICK_GREEDY) continue;
+        if (const int rc = check_nucleus(&q[i].pick.nucleus)) return rc;
+        if (!(q[i].flags & RWKV_PICKQ_SEED) && !(q[i].u >= 0.0 && q[i].u < 1.0)) return fail(RWKV_E_ARG, "query %llu: need 0 <= u < 1", (unsigned long long)i);
+        *nucleus = true;
+        if (!pick_penalty(q[i].pick)) continue;
+        *penalty = true;
+        ((q[i].pick.nucleus.flags & RWKV_NUCLEUS_UPDATE) ? upd : rd).push_back(q[i].slot);
+    }
+    std::sort(upd.begin(), upd.end());
+    for (size_t i = 1; i < upd.size(); i++)
+        if (upd[i] == upd[i - 1]) return fail(RWKV_E_ARG, "slot %u is updated twice: the slots that one call updates are pairwise distinct", upd[i]);
+    for (const uint32_t s : rd)
+        if (std::binary_search(upd.begin(), upd.end(), s)) return fail(RWKV_E_ARG, "slot %u is updated by one query and read by another", s);
+    return 0;
+}
+} // namespace
+
+int rwkv_sample_rows(rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, uint64_t *tokens)
+{
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, q && tokens)) return rc;
+    bool penalty = false, nucleus = false;
+    if (const int rc = check_pick_queries(c, q, n, &penalty, &nucleus)) return rc;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = penalty ? counts_alloc(c) : 0) return rc;
+        if (!c->h_pickq) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_pickq), sizeof(PickIo), hipHostMallocDefault));
+        if (const int rc = grow_buffer(c, PICKQ_IO, sizeof(PickIo))) return rc;
+        if (const int rc = grow_pickq_scratch(c, std::min<uint64_t>(n, PQ_BATCH), nucleus)) return rc;
+        // (the pinned block is free: every call that used it has returned behind its wait)
+        PickIo *h = c->h_pickq, *d = c->buf<PickIo>(PICKQ_IO);
+        for (uint64_t i = 0; i < n; i++)
+            h->q[i] = make_pickq(q[i].pick, false, q[i].row, q[i].slot, (unsigned)i, (q[i].flags & RWKV_PICKQ_SEED) != 0, q[i].seed, q[i].step, q[i].u);
+        HIPCHK(hipMemcpyAsync(d->q, h->q, sizeof(PickQ) * n, hipMemcpyHostToDevice, c->stream));
+        if (const int rc = enqueue_pickq(c, d->q, (unsigned)n, d->out)) return rc;
+        HIPCHK(hipMemcpyAsync(h->out, d->out, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+    if (!rc) std::copy(c->h_pickq->out, c->h_pickq->out + n, tokens);
+    return rc;
+}
+
+// ---- speculative decoding for many streams (specseg.hip.h): rwkv_spec_verify_segments, rwkv_spec_sample_segments ----
 static_assert(sizeof(rwkv_spec_segment) == 16 && sizeof(SpecSegEntry) == 16 && sizeof(SpecSegRec) == 24, "the records the header and the kernels share");
 namespace {
 SpecSegFns specseg_fns() { return SpecSegFns{k_specseg_site<3>, k_specseg_site<2>, k_specseg_wkv<SEQ_T>, k_specseg_wkv<SEQ_TM>}; }
@@ -3086,6 +3202,13 @@ struct SpecSegIo {
     unsigned long long picks[SEQ_TM];
 };
 constexpr size_t SPECSEG_UP = offsetof(SpecSegIo, rec);
+// the sampled verify's image: the query table IN FRONT, so that q | ids | plan | table is still one contiguous upload
+struct SpecSampleIo {
+    PickQ q[SEQ_TM];
+    SpecSegIo s;
+};
+// what rwkv_spec_sample_segments adds to a verify: how segment i picks, and its draws' seed and first step
+struct SpecSampleCall { const rwkv_pick *picks; const uint64_t *seeds, *step0; };
 namespace {
 // the rules of a call behind the guard, all of them before anything is launched or allocated; *T_out: the rows of the call
 int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t *T_out)
@@ -3116,32 +3239,66 @@ int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_
 }
 // Everything of one call but the wait: ids, plan and table up in one copy, the checkpointing segmented pass, the pick of every row, what stands per
 // segment, the commit of exactly those rows, and the records' download.  No host synchronisation in between.  Launched directly, as enqueue_verify is.
-int enqueue_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T)
+// `sm` (nullptr: the greedy verify, every row picked by k_argmax_rows): the rows from each segment's last certain one on are picked by the segment's
+// query -- row rc + j at step step0 + j -- and the query table travels in front of the ids.  *rec: the pinned records the download fills.
+int enqueue_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T, const SpecSampleCall *sm,
+                            const SpecSegRec **rec)
 {
-    if (!c->h_specseg) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specseg), sizeof(SpecSegIo), hipHostMallocDefault));
-    if (const int rc = grow_buffer(c, SPECSEG_IO, sizeof(SpecSegIo))) return rc;
+    SpecSegIo *h, *d;
+    PickQ *hq = nullptr, *dq = nullptr;
+    unsigned nq = 0;
+    if (sm) {
+        if (!c->h_specsample) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specsample), sizeof(SpecSampleIo), hipHostMallocDefault));
+        if (const int rc = grow_buffer(c, SPECSAMPLE_IO, sizeof(SpecSampleIo))) return rc;
+        h = &c->h_specsample->s; d = &c->buf<SpecSampleIo>(SPECSAMPLE_IO)->s;
+        hq = c->h_specsample->q; dq = c->buf<SpecSampleIo>(SPECSAMPLE_IO)->q;
+        bool nucleus = false;
+        for (uint64_t i = 0; i < n_segs; i++) { nq += segs[i].n_draft + 1u; nucleus = nucleus || sm->picks[i].kind == RWKV_PICK_NUCLEUS; }
+        if (const int rc = grow_pickq_scratch(c, nq, nucleus)) return rc;
+    } else {
+        if (!c->h_specseg) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specseg), sizeof(SpecSegIo), hipHostMallocDefault));
+        if (const int rc = grow_buffer(c, SPECSEG_IO, sizeof(SpecSegIo))) return rc;
+        if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, T)) return rc;
+        h = c->h_specseg; d = c->buf<SpecSegIo>(SPECSEG_IO);
+    }
     if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * T * c->D)) return rc;
-    if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, T)) return rc;
     // (the pinned block is free: every call that used it has returned behind its wait)
-    SpecSegIo *h = c->h_specseg, *d = c->buf<SpecSegIo>(SPECSEG_IO);
     uint64_t j = 0;
+    unsigned iq = 0;
     for (uint64_t i = 0; i < n_segs; i++) {
         for (uint32_t k = 0; k < segs[i].n; k++, j++) { h->ids[j] = tokens[j]; h->plan[j] = SegRow{segs[i].slot, k == 0 ? SEG_FIRST : 0u}; }
-        h->tab[i] = SpecSegEntry{(unsigned)j - segs[i].n_draft - 1u, segs[i].n_draft, segs[i].slot, 0u};
+        const unsigned rc = (unsigned)j - segs[i].n_draft - 1u;
+        h->tab[i] = SpecSegEntry{rc, segs[i].n_draft, segs[i].slot, 0u};
+        for (uint32_t k = 0; sm && k <= segs[i].n_draft; k++) hq[iq++] = make_pickq(sm->picks[i], true, rc + k, segs[i].slot, rc + k, true, sm->seeds[i], sm->step0[i] + k, 0.0);
     }
     for (; j < (uint64_t)SEQ_TM; j++) { h->ids[j] = 0; h->plan[j] = SegRow{0u, SEG_FIRST}; }
-    HIPCHK(hipMemcpyAsync(d, h, SPECSEG_UP, hipMemcpyHostToDevice, c->stream));
+    for (; sm && iq < (unsigned)SEQ_TM; iq++) hq[iq] = PickQ{};
+    if (sm) HIPCHK(hipMemcpyAsync(dq, hq, offsetof(SpecSampleIo, s) + SPECSEG_UP, hipMemcpyHostToDevice, c->stream));
+    else HIPCHK(hipMemcpyAsync(d, h, SPECSEG_UP, hipMemcpyHostToDevice, c->stream));
     double *ck = c->buf<double>(SPEC_CKPT);
     const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, d->ids, RowLayout::spec_segments(d->plan, ck)};
     if (const int rc = enqueue_chunk(c, pass)) return rc;
-    if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)T, d->picks)) return rc;
+    if (const int rc = sm ? enqueue_pickq(c, dq, nq, d->picks) : enqueue_argmax_rows(c, c->logits, (unsigned)T, d->picks)) return rc;
     k_specseg_accept<64><<<dim3((unsigned)n_segs), dim3(64), 0, c->stream>>>(SpecSegAcceptArgs{d->ids, d->picks, d->tab, d->rec});
     const SpecSegCommitArgs ca{d->rec, d->tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
     const unsigned pairs = (unsigned)(c->L * c->D / 2);
     k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)n_segs), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(h->rec, d->rec, sizeof(SpecSegRec) * n_segs, hipMemcpyDeviceToHost, c->stream));
+    *rec = h->rec;
     return 0;
+}
+// a verify behind its checks: everything enqueued, the one wait, the records into the caller's arrays
+int run_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T, const SpecSampleCall *sm,
+                        uint32_t *n_accepted, uint64_t *next_token, uint64_t *row)
+{
+    const SpecSegRec *rec = nullptr;
+    const int rc = finish(c, enqueue_verify_segments(c, tokens, segs, n_segs, T, sm, &rec));
+    for (uint64_t i = 0; !rc && i < n_segs; i++) {
+        n_accepted[i] = (uint32_t)rec[i].a; next_token[i] = rec[i].next;
+        if (row) row[i] = rec[i].row;
+    }
+    return rc;
 }
 } // namespace
 
@@ -3152,13 +3309,23 @@ int rwkv_spec_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_sp
     if (flags) return fail(RWKV_E_ARG, "flags must be 0");
     uint64_t T = 0;
     if (const int rc = check_verify_segments(c, tokens, segs, n_segs, &T)) return rc;
-    const int rc = finish(c, enqueue_verify_segments(c, tokens, segs, n_segs, T));
-    for (uint64_t i = 0; !rc && i < n_segs; i++) {
-        const SpecSegRec &r = c->h_specseg->rec[i];
-        n_accepted[i] = (uint32_t)r.a; next_token[i] = r.next;
-        if (row) row[i] = r.row;
+    return run_verify_segments(c, tokens, segs, n_segs, T, nullptr, n_accepted, next_token, row);
+}
+
+int rwkv_spec_sample_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, const rwkv_pick *picks,
+                              const uint64_t *seeds, const uint64_t *step0, uint32_t flags, uint32_t *n_accepted, uint64_t *next_token, uint64_t *row)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs && picks && seeds && step0 && n_accepted && next_token)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    uint64_t T = 0;
+    if (const int rc = check_verify_segments(c, tokens, segs, n_segs, &T)) return rc;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        if (picks[i].kind != RWKV_PICK_GREEDY && picks[i].kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "segment %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, picks[i].kind);
+        if (const int rc = check_pick(picks[i])) return rc;
+        if (pick_penalty(picks[i])) return fail(RWKV_E_ARG, "segment %llu: penalties are not verified (the counts behind a row depend on how much of the draft stands)", (unsigned long long)i);
     }
-    return rc;
+    const SpecSampleCall sm{picks, seeds, step0};
+    return run_verify_segments(c, tokens, segs, n_segs, T, &sm, n_accepted, next_token, row);
 }
 
 void rwkv_free(rwkv_ctx *c)
@@ -3174,6 +3341,8 @@ void rwkv_free(rwkv_ctx *c)
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->h_seg_plan) (void)hipHostFree(c->h_seg_plan);
     if (c->h_specseg) (void)hipHostFree(c->h_specseg);
+    if (c->h_pickq) (void)hipHostFree(c->h_pickq);
+    if (c->h_specsample) (void)hipHostFree(c->h_specsample);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);

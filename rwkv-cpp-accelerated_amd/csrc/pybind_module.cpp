@@ -162,6 +162,44 @@ PYBIND11_MODULE(rwkv, m)
         return out;
     }, "speculative greedy decoding for many streams: segments [(slot, ids, n_draft)] with pairwise distinct slots, the last n_draft ids of each are "
        "guesses; one pass verifies them all and returns [(n_accepted, next, row)] per segment (engine extension)", py::arg("rwkvp"), py::arg("segments"));
+    // a pick as a tuple: ("greedy",) or ("nucleus", temp, top_p, top_k, presence, frequency, decay)
+    static const auto pick_of = [](const py::tuple &t) {
+        const std::string kind = t[0].cast<std::string>();
+        if (kind == "greedy") return RWKV::Pick::greedy();
+        if (kind != "nucleus" || t.size() != 7) throw std::runtime_error("a pick is (\"greedy\",) or (\"nucleus\", temp, top_p, top_k, presence, frequency, decay)");
+        RWKV::Pick p;
+        p.kind = RWKV_PICK_NUCLEUS;
+        p.s = RWKV::Nucleus{t[1].cast<float>(), t[2].cast<float>(), t[3].cast<unsigned>(), t[4].cast<float>(), t[5].cast<float>(), t[6].cast<float>()};
+        return p;
+    };
+    m.def("sampleRows", [](std::uintptr_t h, const std::vector<py::dict> &queries) {
+        std::vector<RWKV::PickQuery> qs;
+        for (const py::dict &d : queries) {
+            RWKV::PickQuery q;
+            q.row = d["row"].cast<unsigned>(); q.slot = d.contains("slot") ? d["slot"].cast<unsigned>() : 0u;
+            q.pick = pick_of(d["pick"].cast<py::tuple>());
+            q.ban0 = d.contains("ban0") && d["ban0"].cast<bool>(); q.update = d.contains("update") && d["update"].cast<bool>();
+            q.use_seed = !d.contains("u");
+            if (q.use_seed) { q.seed = d.contains("seed") ? d["seed"].cast<unsigned long long>() : 0ull; q.step = d.contains("step") ? d["step"].cast<unsigned long long>() : 0ull; }
+            else q.u = d["u"].cast<double>();
+            qs.push_back(q);
+        }
+        const std::vector<unsigned long long> ids = M(h)->sampleRows(qs);
+        return std::vector<int64_t>(ids.begin(), ids.end());
+    }, "len(queries) independent picks ON THE DEVICE in one call: each query a dict(row, slot, pick, ban0, update, and u or seed / step) with pick = "
+       "(\"greedy\",) or (\"nucleus\", temp, top_p, top_k, presence, frequency, decay); returns the ids (engine extension)", py::arg("rwkvp"), py::arg("queries"));
+    m.def("specSampleSegments", [](std::uintptr_t h, const std::vector<std::tuple<unsigned, std::vector<int64_t>, unsigned>> &segments,
+                                   const std::vector<py::tuple> &picks, const std::vector<unsigned long long> &seeds, const std::vector<unsigned long long> &step0) {
+        std::vector<RWKV::SpecSegment> segs;
+        for (const auto &s : segments)
+            segs.push_back(RWKV::SpecSegment{std::get<0>(s), std::vector<unsigned long long>(std::get<1>(s).begin(), std::get<1>(s).end()), std::get<2>(s)});
+        std::vector<RWKV::Pick> pk;
+        for (const py::tuple &t : picks) pk.push_back(pick_of(t));
+        std::vector<std::tuple<unsigned, unsigned long long, unsigned long long>> out;
+        for (const RWKV::SpecSegStep &r : M(h)->specSampleSegments(segs, pk, seeds, step0)) out.emplace_back(r.accepted, r.next, r.row);
+        return out;
+    }, "specVerifySegments with sampled acceptance: segment i's uncertain rows are picked by picks[i] at steps step0[i], step0[i] + 1, ... under "
+       "seeds[i]; returns [(n_accepted, next, row)] per segment (engine extension)", py::arg("rwkvp"), py::arg("segments"), py::arg("picks"), py::arg("seeds"), py::arg("step0"));
     m.def("modelForwardSegments", [](std::uintptr_t h, const std::vector<std::pair<unsigned, std::vector<int64_t>>> &segments) {
         std::vector<RWKV::Segment> segs;
         for (const auto &s : segments) segs.push_back(RWKV::Segment{s.first, std::vector<unsigned long long>(s.second.begin(), s.second.end())});

@@ -44,11 +44,13 @@ ABI_SYMBOLS = [
     "rwkv_spec_verify", "rwkv_decode_speculative",
     "rwkv_forward_segments", "rwkv_segment_plan",
     "rwkv_spec_verify_segments",
+    "rwkv_sample_rows", "rwkv_spec_sample_segments",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 SPEC_MAX_DRAFT = 31               # RWKV_SPEC_MAX_DRAFT
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
+MAX_PICK_ROWS, PICKQ_SEED, PICK_BATCH = 1024, 1, 64   # RWKV_MAX_PICK_ROWS, RWKV_PICKQ_SEED; the queries of one launch sequence (csrc/engine.hip PQ_BATCH)
 TOPN_MAX = 32                     # RWKV_MAX_TOPN
 LOGPROB_ENTRIES_MAX = 1 << 22     # RWKV_MAX_LOGPROB_ENTRIES: n_streams * n_steps * (1 + top_n) of one call
 
@@ -68,6 +70,24 @@ def nucleus_params(temp=1.0, top_p=0.9, top_k=0, presence=0.0, frequency=0.0, de
 class Pick(C.Structure):
     """rwkv_pick of include/rwkv_mi355x.h (48 bytes)"""
     _fields_ = [("kind", C.c_int), ("temp", C.c_float), ("tau", C.c_float), ("typical_flags", C.c_int), ("nucleus", NucleusParams)]
+
+
+class PickQuery(C.Structure):
+    """rwkv_pick_query of include/rwkv_mi355x.h (88 bytes)"""
+    _fields_ = [("row", C.c_uint32), ("slot", C.c_uint32), ("pick", Pick), ("seed", C.c_uint64), ("step", C.c_uint64), ("u", C.c_double),
+                ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def pick_of(kind="nucleus", ban0=False, update=False, **nucleus) -> Pick:
+    """the rwkv_pick of kind "greedy" or "nucleus" (nucleus: the keywords of nucleus_params)"""
+    flags = (NUCLEUS_BAN0 if ban0 else 0) | (NUCLEUS_UPDATE if update else 0)
+    return Pick({"greedy": PICK_GREEDY, "nucleus": PICK_NUCLEUS}[kind], 1.0, 0.8, 0, nucleus_params(flags=flags, **nucleus))
+
+
+def pick_query(row, slot=0, kind="nucleus", u=None, seed=0, step=0, **pick) -> PickQuery:
+    """one query of RWKV.sample_rows: logits row, count vector, pick_of(kind, **pick); u in [0, 1) is the caller's uniform, u=None draws
+    uniform(splitmix64(seed + step)) as the decode loops do at that step"""
+    return PickQuery(int(row), int(slot), pick_of(kind, **pick), int(seed), int(step), 0.0 if u is None else float(u), PICKQ_SEED if u is None else 0, 0)
 
 
 class StopParams(C.Structure):
@@ -341,6 +361,10 @@ def lib():
     L.rwkv_forward_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(Segment), u64, C.c_uint32, C.POINTER(u64)]; L.rwkv_forward_segments.restype = i32
     L.rwkv_spec_verify_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(SpecSegment), u64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64)]
     L.rwkv_spec_verify_segments.restype = i32
+    L.rwkv_sample_rows.argtypes = [vp, C.POINTER(PickQuery), u64, C.POINTER(u64)]; L.rwkv_sample_rows.restype = i32
+    L.rwkv_spec_sample_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(SpecSegment), u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(u64), C.c_uint32,
+                                            C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64)]
+    L.rwkv_spec_sample_segments.restype = i32
     L.rwkv_segment_plan.argtypes = [C.POINTER(Segment), u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(u64)]; L.rwkv_segment_plan.restype = i32
     _lib = L
     return L
@@ -900,10 +924,41 @@ class RWKV:
         return [int(r) for r in last[:n]]
 
     # -- speculative greedy decoding for many streams (include/rwkv_mi355x.h rwkv_spec_verify_segments) -------------------------
+    def sample_rows(self, queries) -> list:
+        """len(queries) independent picks ON THE DEVICE in one call: `queries` is a list of pick_query(row, slot, ...), each with its own logits
+        row of the last forward, count vector, parameters and uniform (or seed and step).  A nucleus query picks what sample_nucleus picks (and
+        with update=True counts it), a greedy one what decode_batch_greedy picks.  The sampling server step: forward_segments, then
+        sample_rows over last_row.  Returns the ids."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        n = len(queries)
+        arr = (PickQuery * max(1, n))(*queries)
+        out = (C.c_uint64 * max(1, n))()
+        _chk(lib().rwkv_sample_rows(self._h, arr, n, out))
+        return [int(t) for t in out[:n]]
+
+    def spec_sample_segments(self, segments, picks, seeds, step0):
+        """spec_verify_segments with SAMPLED acceptance: segment i's uncertain rows are picked by picks[i] (pick_of(...), no penalties) with
+        u = uniform(splitmix64(seeds[i] + step0[i] + j)) for the j-th of them, logit 0 banned; a draft id stands where the draw confirms it.
+        Returns [(n_accepted, next, row)]; a segment emits n_accepted + 1 ids, so its next step0 is step0 + n_accepted + 1."""
+        if len(picks) != len(segments) or len(seeds) != len(segments) or len(step0) != len(segments):
+            raise ValueError("need one pick, seed and step0 per segment")
+        n = len(segments)
+        pk = (Pick * max(1, n))(*picks)
+        sd = (C.c_uint64 * max(1, n))(*[int(x) for x in seeds])
+        st = (C.c_uint64 * max(1, n))(*[int(x) for x in step0])
+        return self._verify_segments(segments, lambda toks, arr, acc, nx, row: lib().rwkv_spec_sample_segments(
+            self._h, toks, arr, n, pk, sd, st, 0, acc, nx, row))
+
     def spec_verify_segments(self, segments):
         """one pass of the chunk path over `segments`, a list of (slot, token_ids, n_draft) with pairwise distinct slots: the last n_draft ids of
         a segment are guesses, of which the longest prefix the greedy picks confirm is kept.  Returns [(n_accepted, next, row)] per segment: the
         slot is left after the ids that stand, `next` is emitted and not fed, `row` is the logits row it was picked from.  All rows fit one pass."""
+        return self._verify_segments(segments, lambda toks, arr, acc, nx, row: lib().rwkv_spec_verify_segments(
+            self._h, toks, arr, len(segments), 0, acc, nx, row))
+
+    def _verify_segments(self, segments, call):
+        """the marshalling of spec_verify_segments / spec_sample_segments around call(ids, segment array, n_accepted, next, row)"""
         if not self.ready:
             raise RuntimeError("RWKV not loaded")
         segs = [(int(s), [int(t) for t in ids], int(nd)) for s, ids, nd in segments]
@@ -915,7 +970,7 @@ class RWKV:
         slots = min(self.maxContext, 1 + max([s for s, _, _ in segs], default=0))
         if not self.resident:
             self.push_state(slots)
-        _chk(lib().rwkv_spec_verify_segments(self._h, toks, arr, n, 0, acc, nx, row))
+        _chk(call(toks, arr, acc, nx, row))
         if not self.resident:
             self.pull_state(slots)
         return [(int(acc[i]), int(nx[i]), int(row[i])) for i in range(n)]
