@@ -482,6 +482,31 @@ public:
         for (size_t i = 0; i < segs.size(); i++) out.push_back(SpecSegStep{a[i], nx[i], row[i]});
         return out;
     }
+    // draft TREES for many streams (rwkv_mi355x.h "draft TREES for many streams"): specVerifySegments where the last n_draft ids of a segment are a
+    // tree -- parent[r], one entry per id of the segment, counted from its first id and read for the guesses, names the last certain id or an earlier
+    // guess.  Of the guesses the one path the greedy picks confirm is kept; `ids` are its ids in order.
+    struct SpecTree { unsigned slot; std::vector<unsigned long long> tokens; unsigned n_draft; std::vector<unsigned char> parent; };
+    struct SpecTreeStep { unsigned accepted; unsigned long long next, row; std::vector<unsigned long long> ids; };
+    std::vector<SpecTreeStep> specVerifyTrees(const std::vector<SpecTree> &trees)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<rwkv_spec_segment> segs;
+        std::vector<uint64_t> ids;
+        std::vector<uint8_t> par;
+        for (const SpecTree &s : trees) {
+            if (s.parent.size() != s.tokens.size()) throw std::runtime_error("need one parent entry per id of a segment");
+            segs.push_back(rwkv_spec_segment{s.slot, (uint32_t)s.tokens.size(), s.n_draft, 0u});
+            ids.insert(ids.end(), s.tokens.begin(), s.tokens.end());
+            par.insert(par.end(), s.parent.begin(), s.parent.end());
+        }
+        std::vector<uint32_t> a(segs.size() + 1);
+        std::vector<uint64_t> nx(segs.size() + 1), row(segs.size() + 1), em((segs.size() + 1) * RWKV_SPEC_MAX_DRAFT);
+        rwkv_detail::check(rwkv_spec_verify_trees(ctx_, ids.data(), par.data(), segs.data(), segs.size(), 0, a.data(), nx.data(), row.data(), em.data()));
+        std::vector<SpecTreeStep> out;
+        for (size_t i = 0; i < segs.size(); i++)
+            out.push_back(SpecTreeStep{a[i], nx[i], row[i], std::vector<unsigned long long>(em.begin() + i * RWKV_SPEC_MAX_DRAFT, em.begin() + i * RWKV_SPEC_MAX_DRAFT + a[i])});
+        return out;
+    }
     // a sampler over any (row, slot) pairs (rwkv_mi355x.h "a sampler over any (row, slot) pairs"): queries.size() independent picks in one call,
     // each from its own logits row of the last forward with the counts of its own slot, its own parameters and its own uniform -- or, with
     // use_seed, the draw the decode loops make at step `step` under `seed`.  A nucleus query picks what sampleNucleus picks (update: and counts

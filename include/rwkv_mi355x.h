@@ -624,8 +624,8 @@ int rwkv_segment_plan(const rwkv_segment *segs, uint64_t n_segs, uint64_t max_ct
  * Status: as rwkv_forward_segments -- RWKV_E_ARG for each rule above and for a NULL ctx, tokens, segs, n_accepted or next_token; RWKV_E_STATE when
  * not loaded, on a pipeline-stage context, or without the chunk path.  Every check runs before anything is launched or allocated: a rejected call
  * leaves state, logits and buffers as they were.
- * Out of scope: a draft MODEL loop for many streams (its rollback needs a snapshot slot per stream and step in the draft context), draft trees,
- * pipeline-stage contexts.  Sampled acceptance is rwkv_spec_sample_segments below. */
+ * Out of scope: a draft MODEL loop for many streams (its rollback needs a snapshot slot per stream and step in the draft context),
+ * pipeline-stage contexts.  Sampled acceptance is rwkv_spec_sample_segments below, draft trees are rwkv_spec_verify_trees. */
 typedef struct rwkv_spec_segment { uint32_t slot, n, n_draft, reserved; } rwkv_spec_segment;
 int rwkv_spec_verify_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' rows back to back */,
                               const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags /* must be 0 */,
@@ -684,11 +684,61 @@ int rwkv_sample_rows(rwkv_ctx *ctx, const rwkv_pick_query *q, uint64_t n, uint64
  * Status: as rwkv_spec_verify_segments, and RWKV_E_ARG for a NULL picks, seeds or step0, RWKV_PICK_TYPICAL, whatever rwkv_sample_nucleus rejects in
  * a pick's parameters, and a pick with a penalty.
  * Out of scope: penalties (the counts behind row j would depend on how much of the draft stands), typical sampling, a draft model that samples (it
- * needs the draft's probabilities), draft trees, pipeline-stage contexts. */
+ * needs the draft's probabilities), pipeline-stage contexts.  Draft trees are rwkv_spec_sample_trees below. */
 int rwkv_spec_sample_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T] */, const rwkv_spec_segment *segs, uint64_t n_segs,
                               const rwkv_pick *picks /* [n_segs] */, const uint64_t *seeds /* [n_segs] */, const uint64_t *step0 /* [n_segs] */,
                               uint32_t flags /* must be 0 */, uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,
                               uint64_t *row /* [n_segs], may be NULL */);
+
+/* ---- draft TREES for many streams: branching guesses per stream verified in ONE segmented pass (no reference counterpart) ----
+ * rwkv_spec_verify_segments verifies a chain: row j of a draft counts only if rows 0 .. j - 1 were all guessed right, so a chain spends its rows
+ * where acceptance is least likely, and a lookup drafter that finds several continuations must discard all but one.  A verify costs the same for 2
+ * or 16 rows; a tree places the alternatives side by side, as siblings, in the same pass.  RWKV has no cache to fork: the state behind every row is
+ * already checkpointed per row, so a branch is one more parent index.
+ * Segments are those of rwkv_spec_verify_segments ({slot, n, n_draft}: n - n_draft certain rows, a chain, then n_draft guesses).  With r0 the
+ * segment's first row and c = n - n_draft - 1 its last certain row, the draft rows form a tree ROOTED at row r0 + c, given by parent[T] (one entry
+ * per row of the call, beside tokens): for a draft row r, counted from the segment's first row, c <= parent[r] < r -- the last certain row or an
+ * earlier draft row, so the rows are in topological order -- and two children of one parent do not carry the same id.  The entries of certain rows
+ * are not read.  A chain is parent[r] = r - 1.
+ * Every row is picked as in rwkv_spec_verify_segments.  A draft row is CONFIRMED when its id is the pick of its parent's row, and STANDS when it and
+ * all its ancestors are confirmed; siblings differ, so the rows that stand are one path from the root.  a_i = their number; the slot is left after
+ * the certain rows and that path (xy, aa, bb, dd; pp is not touched); row[i] (may be NULL) = the last row of the path, r0 + c when nothing stands;
+ * next_token[i] = its pick, emitted and not fed; emitted (may be NULL) receives the path's ids in order, a_i of them at emitted + i *
+ * RWKV_SPEC_MAX_DRAFT: the caller appends them and next_token and walks no parents.  Logits rows 0 .. T - 1 are written.
+ * Limits as in rwkv_spec_verify_segments: n_draft <= min(n - 1, RWKV_SPEC_MAX_DRAFT), pairwise distinct slots, T fits ONE pass as the context runs
+ * it (64 rows, or 32 under RWKV_SEQ_ROWS=32); a tree does not cross a pass boundary.
+ * The pass: the checkpointing segmented pass with one more table, the row each row starts from.  The token shift reads that row (in either half of
+ * the pass) instead of the row in front; the serial WKV walk, which already leaves the state after every row in two LDS tables, starts each row from
+ * its parent's entry there, loaded one step ahead so that it costs the walk no round trip, and keeps the registers where the parent is the row in
+ * front; one wave per segment finds the path with ballots; the commit is rwkv_spec_verify_segments' own.  ONE upload (ids, plan, segment table,
+ * parents; the query table in front for the sampled call), ONE download (records and accepted ids), one wait, no host synchronisation between pass,
+ * pick, accept and commit.  rwkv_resident_bytes counts the buffers, rwkv_free frees them.
+ * EXACT: the result for a segment does not depend on the other segments, on where its rows sit, or on any row off the accepted path.  Write A for
+ * rwkv_forward_segments({slot, c + a_i + 1}) of the segment alone, fed the certain ids followed by the accepted ids: the slot is bit for bit that of
+ * A, and the logits rows of the certain rows and of the path are bit for bit those of A.  A chain gives, bit for bit, what rwkv_spec_verify_segments
+ * gives: ids, records, slot and logits rows.  Slots not named are untouched; so are pp, the penalty counts, the stop histories and the constraint
+ * states.
+ * rwkv_spec_sample_trees is the same call with SAMPLED acceptance, as rwkv_spec_sample_segments is of the chain: with a point-mass proposal per
+ * child, "draw t from p at the node, descend into the child whose id is t, else emit t" preserves the target distribution exactly.  A row is drawn
+ * at step step0[i] + its depth below row r0 + c -- the step at which a decode of the path draws there -- with logit 0 banned; next_token is what
+ * rwkv_sample_rows picks from row[i] with (seeds[i], step0[i] + a_i) and RWKV_NUCLEUS_BAN0 after A.  A RWKV_PICK_GREEDY segment behaves as in
+ * rwkv_spec_verify_trees.  Penalties and typical sampling are refused.
+ * rwkv_tree_plan is the ONE validator, on the host alone (no context, no device), and both calls run it before anything is launched or allocated:
+ * RWKV_E_ARG for each rule above -- a rejected call leaves state, logits and buffers as they were.  Into whichever outputs are not NULL it writes,
+ * per row of the call, the row of the call it starts from (a segment's first row: itself) and its depth below the last certain row (certain rows: 0).
+ * pass_rows is 32 or 64.  Status otherwise as rwkv_spec_verify_segments / rwkv_spec_sample_segments.
+ * Out of scope: a device-side drafter, a sampling draft model with probabilities of its own, trees across a pass boundary, pipeline-stage contexts. */
+int rwkv_tree_plan(const uint64_t *tokens /* [T] */, const uint8_t *parent /* [T] */, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t max_ctx,
+                   uint32_t pass_rows, uint8_t *row_from /* [T] */, uint8_t *row_depth /* [T], may both be NULL: validate only */, uint64_t *n_rows /* may be NULL */);
+int rwkv_spec_verify_trees(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the segments' rows back to back */,
+                           const uint8_t *parent /* [T], per row: its parent, counted from its segment's first row */,
+                           const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags /* must be 0 */,
+                           uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */, uint64_t *row /* [n_segs], may be NULL */,
+                           uint64_t *emitted /* [n_segs][RWKV_SPEC_MAX_DRAFT], may be NULL */);
+int rwkv_spec_sample_trees(rwkv_ctx *ctx, const uint64_t *tokens /* [T] */, const uint8_t *parent /* [T] */, const rwkv_spec_segment *segs, uint64_t n_segs,
+                           const rwkv_pick *picks /* [n_segs] */, const uint64_t *seeds /* [n_segs] */, const uint64_t *step0 /* [n_segs] */,
+                           uint32_t flags /* must be 0 */, uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,
+                           uint64_t *row /* [n_segs], may be NULL */, uint64_t *emitted /* [n_segs][RWKV_SPEC_MAX_DRAFT], may be NULL */);
 
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()

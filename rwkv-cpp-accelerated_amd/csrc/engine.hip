@@ -17,6 +17,7 @@
 #include "spec.hip.h"
 #include "segments.hip.h"
 #include "specseg.hip.h"
+#include "spectree.hip.h"
 #include "pickrows.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
@@ -254,6 +255,8 @@ enum GrownBuf {
     PICKQ_IO,                         // rwkv_sample_rows (pickrows.hip.h), PickIo: the call's upload (the query table) and the ids it downloads; allocated ONCE at the
                                       // first call.  The sampler scratch is BD_PART / BD_P / BD_PW / BD_KEY, grown to min(n, PQ_BATCH) rows
     SPECSAMPLE_IO,                    // rwkv_spec_sample_segments, SpecSampleIo: the query table in front of a SpecSegIo, so that ONE copy still carries the upload
+    SPECTREE_IO,                      // rwkv_spec_verify_trees / rwkv_spec_sample_trees (spectree.hip.h), SpecTreeIo: query table | ids | plan | segment table | from table,
+                                      // behind them the records, the accepted ids and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT
     N_GROWN
 };
 
@@ -308,6 +311,7 @@ struct rwkv_ctx {
     struct SpecSegIo *h_specseg = nullptr;   // pinned: what rwkv_spec_verify_segments uploads into SPECSEG_IO and downloads from it (allocated with it)
     struct PickIo *h_pickq = nullptr;        // pinned twin of PICKQ_IO (allocated with it)
     struct SpecSampleIo *h_specsample = nullptr;   // pinned twin of SPECSAMPLE_IO (allocated with it)
+    struct SpecTreeIo *h_spectree = nullptr;       // pinned twin of SPECTREE_IO (allocated with it)
     unsigned long long *gen = nullptr;
     unsigned long long *pick = nullptr;      // device: id drawn by the sampler
     double *ts_part = nullptr;               // sampler scratch (sampler.hip.h)
@@ -1091,7 +1095,7 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     return 0;
 }
 
-// The ROW LAYOUT of a pass: what its rows are to each other -- one of five, with what that layout needs besides the pass's rows.
+// The ROW LAYOUT of a pass: what its rows are to each other -- one of six, with what that layout needs besides the pass's rows.
 //   GPT        rwkv.cu:493-593: n tokens of one sequence on state slot 0, the token shift runs along the rows
 //   PARRALEL   rwkv.cu:236-240: n independent sequences, one token each, row t on state slot row0 + t -- the batched decode step
 //   CKPT       the verify pass of rwkv_spec_verify (spec.hip.h): GPT rows, one half, whole model, that commit NOTHING to slot 0 -- every row's state
@@ -1099,17 +1103,21 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
 //   SEGMENTED  segments.hip.h: the rows are pieces of sequences on slots of their own, as `plan` says ([rows]{slot, flags} on the device)
 //   SPECSEG    the verify pass of rwkv_spec_verify_segments (specseg.hip.h): SEGMENTED rows, one or two halves, whole model, that commit NOTHING to
 //              their slots -- every row's state is left in `ckpt`, [4][L][n][D]
+//   SPECTREE   the verify pass of rwkv_spec_verify_trees (spectree.hip.h): SPECSEG rows of which each starts from the row `from` names ([rows] on the
+//              device) instead of the row in front -- a segment's draft rows are a tree
 // Only GPT passes are replayed as captured graphs (enqueue_pass: its key holds a shape, no layout); the rest change from call to call and are
 // launched directly.
 struct RowLayout {
-    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED, SPECSEG } kind = GPT;
+    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED, SPECSEG, SPECTREE } kind = GPT;
     double *ckpt = nullptr;
     const SegRow *plan = nullptr;
+    const unsigned char *from = nullptr;
     static RowLayout of_mode(int mode) { RowLayout r; r.kind = mode == RWKV_MODE_PARRALEL ? PARRALEL : GPT; return r; }
     static RowLayout checkpoints(double *ck) { RowLayout r; r.kind = CKPT; r.ckpt = ck; return r; }
     static RowLayout segments(const SegRow *plan) { RowLayout r; r.kind = SEGMENTED; r.plan = plan; return r; }
     static RowLayout spec_segments(const SegRow *plan, double *ck) { RowLayout r; r.kind = SPECSEG; r.plan = plan; r.ckpt = ck; return r; }
-    bool one_pass() const { return kind == CKPT || kind == SPECSEG; }      // the checkpoint arrays are laid out for ONE pass
+    static RowLayout spec_trees(const SegRow *plan, const unsigned char *from, double *ck) { RowLayout r = spec_segments(plan, ck); r.kind = SPECTREE; r.from = from; return r; }
+    bool one_pass() const { return kind == CKPT || kind == SPECSEG || kind == SPECTREE; }      // the checkpoint arrays are laid out for ONE pass
     bool replayed() const { return kind == GPT; }
     RowLayout from_row(uint64_t t0) const { RowLayout r = *this; if (kind == SEGMENTED) r.plan += t0; return r; }      // the layout of the pass that starts at row t0 of a call
 };
@@ -1152,6 +1160,10 @@ struct SpecSegFns {
     void (*site3)(SpecSegSiteArgs) = nullptr; void (*site2)(SpecSegSiteArgs) = nullptr; void (*wkv32)(SpecSegWkvArgs) = nullptr; void (*wkv64)(SpecSegWkvArgs) = nullptr;
 };
 SpecSegFns specseg_fns();
+struct SpecTreeFns {
+    void (*site3)(SpecTreeSiteArgs) = nullptr; void (*site2)(SpecTreeSiteArgs) = nullptr; void (*wkv32)(SpecTreeWkvArgs) = nullptr; void (*wkv64)(SpecTreeWkvArgs) = nullptr;
+};
+SpecTreeFns spectree_fns();
 int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 {
     if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
@@ -1171,7 +1183,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     const bool two = n > SEQ_T;
     const SeqHalf h((size_t)D);
     // What the layout means, said once.  A site with a token shift keeps its LayerNorm output for the sequence's next row: GPT in S.state (the last
-    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT and SPECSEG in the checkpoint rows; SEGMENTED in
+    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT, SPECSEG and SPECTREE in the checkpoint rows; SEGMENTED in
     // the staging rows, which the WKV and stage-1 kernels behind the GEMMs commit.  The three launch helpers below (site, wkv, stage) pick their instance.
     const RowLayout &rows = pass.rows;
     const bool commits = rows.kind == RowLayout::GPT;
@@ -1180,6 +1192,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     const SeqCkptFns ckf = rows.kind == RowLayout::CKPT ? seq_ckpt_fns() : SeqCkptFns{};
     const SegFns sgf = rows.kind == RowLayout::SEGMENTED ? seg_fns() : SegFns{};
     const SpecSegFns ssf = rows.kind == RowLayout::SPECSEG ? specseg_fns() : SpecSegFns{};
+    const SpecTreeFns stf = rows.kind == RowLayout::SPECTREE ? spectree_fns() : SpecTreeFns{};
     const size_t ck_arr = (size_t)L * n * D;      // one of the four checkpoint arrays; layer l's rows start l * n * D into it
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
     // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
@@ -1223,6 +1236,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         case RowLayout::SEGMENTED: (nv == 3 ? sgf.site3 : sgf.site2)<<<grid, block, 0, st>>>(SegSiteArgs{s, rows.plan, S.seg}); return;
         case RowLayout::CKPT: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ckf.site3 : ckf.site2)<<<grid, block, 0, st>>>(s); return;
         case RowLayout::SPECSEG: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ssf.site3 : ssf.site2)<<<grid, block, 0, st>>>(SpecSegSiteArgs{s, rows.plan}); return;
+        case RowLayout::SPECTREE: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? stf.site3 : stf.site2)<<<grid, block, 0, st>>>(SpecTreeSiteArgs{s, rows.plan, rows.from}); return;
         case RowLayout::PARRALEL: s.par = 1; break;
         case RowLayout::GPT: s.state_new = state ? S.state : nullptr; break;      // (and ln_out of every layout: nothing to keep)
         }
@@ -1242,6 +1256,10 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         case RowLayout::SPECSEG:
             wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
             (two ? ssf.wkv64 : ssf.wkv32)<<<grid, block, 0, st>>>(SpecSegWkvArgs{wa, rows.plan});
+            return;
+        case RowLayout::SPECTREE:
+            wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
+            (two ? stf.wkv64 : stf.wkv32)<<<grid, block, 0, st>>>(SpecTreeWkvArgs{wa, rows.plan, rows.from});
             return;
         default: break;
         }
@@ -3211,9 +3229,9 @@ struct SpecSampleIo {
 struct SpecSampleCall { const rwkv_pick *picks; const uint64_t *seeds, *step0; };
 namespace {
 // the rules of a call behind the guard, all of them before anything is launched or allocated; *T_out: the rows of the call
-int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t *T_out)
+// (the rules need no context: rwkv_tree_plan runs them on max_ctx and the rows of a pass alone)
+int check_spec_segments(const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t maxT, uint64_t pass_rows, uint64_t *T_out)
 {
-    const uint64_t pass_rows = (uint64_t)(c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T);
     if (n_segs == 0 || n_segs > pass_rows) return fail(RWKV_E_ARG, "n_segs must be in 1..%llu (the rows of one pass)", (unsigned long long)pass_rows);
     uint64_t T = 0;
     for (uint64_t i = 0; i < n_segs; i++) {
@@ -3223,9 +3241,9 @@ int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_
         if (s.n_draft >= s.n || s.n_draft > RWKV_SPEC_MAX_DRAFT)
             return fail(RWKV_E_ARG, "segment %llu: n_draft %u must be in 0..%u (n - 1 = %u, and one half less a row)", (unsigned long long)i, s.n_draft,
                         std::min<uint32_t>(s.n - 1, RWKV_SPEC_MAX_DRAFT), s.n - 1);
-        if (s.slot >= c->maxT) return fail(RWKV_E_ARG, "segment %llu: slot %u out of range, max context is %llu", (unsigned long long)i, s.slot, (unsigned long long)c->maxT);
+        if (s.slot >= maxT) return fail(RWKV_E_ARG, "segment %llu: slot %u out of range, max context is %llu", (unsigned long long)i, s.slot, (unsigned long long)maxT);
         T += s.n;
-        if (T > c->maxT) return fail(RWKV_E_ARG, "Context too large, max context is %llu", (unsigned long long)c->maxT);
+        if (T > maxT) return fail(RWKV_E_ARG, "Context too large, max context is %llu", (unsigned long long)maxT);
         if (T > pass_rows) return fail(RWKV_E_ARG, "%llu rows and more: a verify is ONE pass of at most %llu rows", (unsigned long long)T, (unsigned long long)pass_rows);
     }
     std::vector<uint32_t> slots(n_segs);
@@ -3236,6 +3254,10 @@ int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_
     if (const int rc = check_ids(tokens, T, "token")) return rc;
     *T_out = T;
     return 0;
+}
+int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t *T_out)
+{
+    return check_spec_segments(tokens, segs, n_segs, c->maxT, (uint64_t)(c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T), T_out);
 }
 // Everything of one call but the wait: ids, plan and table up in one copy, the checkpointing segmented pass, the pick of every row, what stands per
 // segment, the commit of exactly those rows, and the records' download.  No host synchronisation in between.  Launched directly, as enqueue_verify is.
@@ -3328,6 +3350,144 @@ int rwkv_spec_sample_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_sp
     return run_verify_segments(c, tokens, segs, n_segs, T, &sm, n_accepted, next_token, row);
 }
 
+// ---- draft trees for many streams (spectree.hip.h): rwkv_tree_plan, rwkv_spec_verify_trees, rwkv_spec_sample_trees ----
+namespace {
+SpecTreeFns spectree_fns() { return SpecTreeFns{k_spectree_site<3>, k_spectree_site<2>, k_spectree_wkv<SEQ_T>, k_spectree_wkv<SEQ_TM>}; }
+}
+// the device image of one call (SPECTREE_IO) and its pinned twin.  The query table in front as in SpecSampleIo: a sampled call uploads from q, a greedy
+// one from ids, either way ONE copy up to `rec`; rec and the first n_segs rows of `emitted` come down in one
+struct SpecTreeIo {
+    PickQ q[SEQ_TM];
+    unsigned long long ids[SEQ_TM];
+    SegRow plan[SEQ_TM];
+    SpecSegEntry tab[SEQ_TM];
+    unsigned char from[SEQ_TM];       // the row of the pass each row starts from (spectree.hip.h)
+    SpecSegRec rec[SEQ_TM];           // <- not uploaded
+    unsigned long long emitted[SEQ_TM][SPEC_MAX_DRAFT];
+    unsigned long long picks[SEQ_TM];
+};
+static_assert(offsetof(SpecTreeIo, emitted) == offsetof(SpecTreeIo, rec) + sizeof(SpecSegRec) * SEQ_TM, "records and accepted ids are one download");
+namespace {
+// The one validator of a tree call: the rules of rwkv_spec_verify_segments (check_spec_segments), then per segment the rules of `parent` -- and, into
+// whichever outputs are there, the row each row starts from (a first row: itself) and its depth below the segment's last certain row.  Nothing is
+// written when the call is rejected.
+int tree_plan(const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t maxT, uint64_t pass_rows,
+              uint8_t *row_from, uint8_t *row_depth, uint64_t *n_rows)
+{
+    uint64_t T = 0;
+    if (const int rc = check_spec_segments(tokens, segs, n_segs, maxT, pass_rows, &T)) return rc;
+    uint8_t from[SEQ_TM], depth[SEQ_TM];
+    uint64_t r0 = 0;
+    for (uint64_t i = 0; i < n_segs; r0 += segs[i].n, i++) {
+        const uint32_t n = segs[i].n, cr = n - segs[i].n_draft - 1u;      // cr: the last certain row, the tree's root
+        for (uint32_t k = 0; k < n; k++) {
+            const uint64_t j = r0 + k;
+            if (k <= cr) { from[j] = (uint8_t)(k == 0 ? j : j - 1); depth[j] = 0; continue; }
+            const uint32_t p = parent[j];
+            if (p < cr || p >= k)
+                return fail(RWKV_E_ARG, "segment %llu: parent %u of row %u must be in %u..%u (the last certain row or an earlier draft row)", (unsigned long long)i, p, k, cr, k - 1);
+            for (uint32_t q = cr + 1; q < k; q++)
+                if (parent[r0 + q] == p && tokens[r0 + q] == tokens[j])
+                    return fail(RWKV_E_ARG, "segment %llu: rows %u and %u are children of row %u with the same id %llu", (unsigned long long)i, q, k, p, (unsigned long long)tokens[j]);
+            from[j] = (uint8_t)(r0 + p); depth[j] = (uint8_t)(depth[r0 + p] + 1u);
+        }
+    }
+    if (row_from) std::copy(from, from + T, row_from);
+    if (row_depth) std::copy(depth, depth + T, row_depth);
+    if (n_rows) *n_rows = T;
+    return 0;
+}
+// Everything of one tree call but the wait, as enqueue_verify_segments: ONE upload (query table | ids | plan | segment table | from table), the
+// checkpointing pass in the SPECTREE layout, the pick of every row, the path that stands per segment, the commit of its last row (k_specseg_commit as
+// it is), ONE download (records | accepted ids).  `sm`: row r0 + c + k of segment i is picked by the segment's query at step step0 + depth, the depth
+// below the last certain row -- the step at which a decode of the path would draw there.
+int enqueue_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *from, const uint8_t *depth, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T,
+                         const SpecSampleCall *sm)
+{
+    bool nucleus = false;
+    unsigned nq = 0;
+    for (uint64_t i = 0; sm && i < n_segs; i++) { nq += segs[i].n_draft + 1u; nucleus = nucleus || sm->picks[i].kind == RWKV_PICK_NUCLEUS; }
+    if (!c->h_spectree) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_spectree), sizeof(SpecTreeIo), hipHostMallocDefault));
+    if (const int rc = grow_buffer(c, SPECTREE_IO, sizeof(SpecTreeIo))) return rc;
+    if (const int rc = sm ? grow_pickq_scratch(c, nq, nucleus) : grow_pick_buffers(c, RWKV_PICK_GREEDY, T)) return rc;
+    if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * T * c->D)) return rc;
+    // (the pinned block is free: every call that used it has returned behind its wait)
+    SpecTreeIo *h = c->h_spectree, *d = c->buf<SpecTreeIo>(SPECTREE_IO);
+    uint64_t j = 0;
+    unsigned iq = 0;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        for (uint32_t k = 0; k < segs[i].n; k++, j++) { h->ids[j] = tokens[j]; h->plan[j] = SegRow{segs[i].slot, k == 0 ? SEG_FIRST : 0u}; h->from[j] = from[j]; }
+        const unsigned rc = (unsigned)j - segs[i].n_draft - 1u;
+        h->tab[i] = SpecSegEntry{rc, segs[i].n_draft, segs[i].slot, 0u};
+        for (uint32_t k = 0; sm && k <= segs[i].n_draft; k++)
+            h->q[iq++] = make_pickq(sm->picks[i], true, rc + k, segs[i].slot, rc + k, true, sm->seeds[i], sm->step0[i] + depth[rc + k], 0.0);
+    }
+    for (; j < (uint64_t)SEQ_TM; j++) { h->ids[j] = 0; h->plan[j] = SegRow{0u, SEG_FIRST}; h->from[j] = (unsigned char)j; }
+    for (; sm && iq < (unsigned)SEQ_TM; iq++) h->q[iq] = PickQ{};
+    const size_t up0 = sm ? 0 : offsetof(SpecTreeIo, ids);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(d) + up0, reinterpret_cast<const char *>(h) + up0, offsetof(SpecTreeIo, rec) - up0, hipMemcpyHostToDevice, c->stream));
+    double *ck = c->buf<double>(SPEC_CKPT);
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, d->ids, RowLayout::spec_trees(d->plan, d->from, ck)};
+    if (const int rc = enqueue_chunk(c, pass)) return rc;
+    if (const int rc = sm ? enqueue_pickq(c, d->q, nq, d->picks) : enqueue_argmax_rows(c, c->logits, (unsigned)T, d->picks)) return rc;
+    k_spectree_accept<64><<<dim3((unsigned)n_segs), dim3(64), 0, c->stream>>>(SpecTreeAcceptArgs{d->ids, d->picks, d->from, d->tab, d->rec, &d->emitted[0][0]});
+    const SpecSegCommitArgs ca{d->rec, d->tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
+    const unsigned pairs = (unsigned)(c->L * c->D / 2);
+    k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)n_segs), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h->rec, d->rec, sizeof(h->rec) + sizeof(h->emitted[0]) * n_segs, hipMemcpyDeviceToHost, c->stream));
+    return 0;
+}
+// a tree call behind its guard: the plan (every rule, before anything is launched or allocated), everything enqueued, the one wait, the outputs
+int run_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, const SpecSampleCall *sm,
+                     uint32_t *n_accepted, uint64_t *next_token, uint64_t *row, uint64_t *emitted)
+{
+    uint8_t from[SEQ_TM], depth[SEQ_TM];
+    uint64_t T = 0;
+    if (const int rc = tree_plan(tokens, parent, segs, n_segs, c->maxT, (uint64_t)(c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T), from, depth, &T)) return rc;
+    for (uint64_t i = 0; sm && i < n_segs; i++) {
+        const rwkv_pick &pk = sm->picks[i];
+        if (pk.kind != RWKV_PICK_GREEDY && pk.kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "segment %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, pk.kind);
+        if (const int rc = check_pick(pk)) return rc;
+        if (pick_penalty(pk)) return fail(RWKV_E_ARG, "segment %llu: penalties are not verified (the counts behind a row depend on how much of the draft stands)", (unsigned long long)i);
+    }
+    const int rc = finish(c, enqueue_verify_trees(c, tokens, from, depth, segs, n_segs, T, sm));
+    const SpecTreeIo *h = c->h_spectree;
+    for (uint64_t i = 0; !rc && i < n_segs; i++) {
+        n_accepted[i] = (uint32_t)h->rec[i].a; next_token[i] = h->rec[i].next;
+        if (row) row[i] = h->rec[i].row;
+        if (emitted) std::copy(h->emitted[i], h->emitted[i] + h->rec[i].a, emitted + i * RWKV_SPEC_MAX_DRAFT);
+    }
+    return rc;
+}
+} // namespace
+
+int rwkv_tree_plan(const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t max_ctx, uint32_t pass_rows,
+                   uint8_t *row_from, uint8_t *row_depth, uint64_t *n_rows)
+{
+    if (!tokens || !parent || !segs) return fail(RWKV_E_ARG, "NULL argument");
+    if (pass_rows != (uint32_t)SEQ_T && pass_rows != (uint32_t)SEQ_TM) return fail(RWKV_E_ARG, "pass_rows must be %d or %d", SEQ_T, SEQ_TM);
+    return tree_plan(tokens, parent, segs, n_segs, max_ctx, pass_rows, row_from, row_depth, n_rows);
+}
+
+int rwkv_spec_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags,
+                           uint32_t *n_accepted, uint64_t *next_token, uint64_t *row, uint64_t *emitted)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && parent && segs && n_accepted && next_token)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    return run_verify_trees(c, tokens, parent, segs, n_segs, nullptr, n_accepted, next_token, row, emitted);
+}
+
+int rwkv_spec_sample_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, const rwkv_pick *picks,
+                           const uint64_t *seeds, const uint64_t *step0, uint32_t flags, uint32_t *n_accepted, uint64_t *next_token, uint64_t *row,
+                           uint64_t *emitted)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && parent && segs && picks && seeds && step0 && n_accepted && next_token)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    const SpecSampleCall sm{picks, seeds, step0};
+    return run_verify_trees(c, tokens, parent, segs, n_segs, &sm, n_accepted, next_token, row, emitted);
+}
+
 void rwkv_free(rwkv_ctx *c)
 {
     if (!c) return;
@@ -3343,6 +3503,7 @@ void rwkv_free(rwkv_ctx *c)
     if (c->h_specseg) (void)hipHostFree(c->h_specseg);
     if (c->h_pickq) (void)hipHostFree(c->h_pickq);
     if (c->h_specsample) (void)hipHostFree(c->h_specsample);
+    if (c->h_spectree) (void)hipHostFree(c->h_spectree);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);

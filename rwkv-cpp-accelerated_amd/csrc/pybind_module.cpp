@@ -162,6 +162,16 @@ PYBIND11_MODULE(rwkv, m)
         return out;
     }, "speculative greedy decoding for many streams: segments [(slot, ids, n_draft)] with pairwise distinct slots, the last n_draft ids of each are "
        "guesses; one pass verifies them all and returns [(n_accepted, next, row)] per segment (engine extension)", py::arg("rwkvp"), py::arg("segments"));
+    m.def("specVerifyTrees", [](std::uintptr_t h, const std::vector<std::tuple<unsigned, std::vector<int64_t>, unsigned, std::vector<unsigned>>> &trees) {
+        std::vector<RWKV::SpecTree> segs;
+        for (const auto &s : trees)
+            segs.push_back(RWKV::SpecTree{std::get<0>(s), std::vector<unsigned long long>(std::get<1>(s).begin(), std::get<1>(s).end()), std::get<2>(s),
+                                          std::vector<unsigned char>(std::get<3>(s).begin(), std::get<3>(s).end())});
+        std::vector<std::tuple<unsigned, unsigned long long, unsigned long long, std::vector<int64_t>>> out;
+        for (const RWKV::SpecTreeStep &r : M(h)->specVerifyTrees(segs)) out.emplace_back(r.accepted, r.next, r.row, std::vector<int64_t>(r.ids.begin(), r.ids.end()));
+        return out;
+    }, "draft trees for many streams: segments [(slot, ids, n_draft, parent)], parent[r] per id counted from the segment's first id; one pass verifies "
+       "them all and returns [(n_accepted, next, row, accepted ids)] per segment (engine extension)", py::arg("rwkvp"), py::arg("trees"));
     // a pick as a tuple: ("greedy",) or ("nucleus", temp, top_p, top_k, presence, frequency, decay)
     static const auto pick_of = [](const py::tuple &t) {
         const std::string kind = t[0].cast<std::string>();

@@ -317,15 +317,17 @@ __device__ __forceinline__ void seq_row_stats2(const SeqStat *stat, int t, int t
 // residual stream of the previous row and wants this site's LayerNorm, not a LayerNorm output already stored), and `keep(j, xx)`, which puts the
 // LayerNorm output of channel j where the layout keeps it.  `keep` is a functor, resolved where the kernel is compiled: no instance carries
 // another layout's branches.
+// seq_site_row_from: the same with the shift input's row named -- `tp`, the row of the pass whose residual stream `xprow` is (read where lnprev).
+// In every layout but a draft tree's (spectree.hip.h) that is the row in front, which is what seq_site_row says.
 template <int NV, class Keep>
-__device__ __forceinline__ void seq_site_row(const SeqSiteArgs &a, int t, int o, bool shift, bool lnprev, const double *xprow, Keep keep, double *red)
+__device__ __forceinline__ void seq_site_row_from(const SeqSiteArgs &a, int t, int tp, int o, bool shift, bool lnprev, const double *xprow, Keep keep, double *red)
 {
     const int D = a.D, hh = t / SEQ_T, th = t % SEQ_T;      // the row's half and the row inside the half (images, records)
     int c0, c1;
     octant_range(D, o, c0, c1);
     // both rows' statistics in ONE round trip (unconditionally: a branch around the second read is a second trip where it is taken)
     double mean, rstd, meanp, rstdp;
-    seq_row_stats2(a.stat, t, lnprev ? t - 1 : t, D, mean, rstd, meanp, rstdp);
+    seq_row_stats2(a.stat, t, lnprev ? tp : t, D, mean, rstd, meanp, rstdp);
     if (!lnprev) { meanp = 0.0; rstdp = 1.0; }
     const int qd = (c0 >> 2) + threadIdx.x;
     const bool live = qd < (c1 >> 2);
@@ -369,6 +371,11 @@ __device__ __forceinline__ void seq_site_row(const SeqSiteArgs &a, int t, int o,
         if (live) seq_store_quad(a.img[m] + hh * a.img_h, qd, th, v[m], inv_scale(amax[m]), ls);
         seq_finish(ls, So[m], c1 - c0, amax[m], a.part + hh * a.part_h + ((size_t)m * SEQ_T + th) * SEQ_O + o, red);
     }
+}
+template <int NV, class Keep>
+__device__ __forceinline__ void seq_site_row(const SeqSiteArgs &a, int t, int o, bool shift, bool lnprev, const double *xprow, Keep keep, double *red)
+{
+    seq_site_row_from<NV>(a, t, t - 1, o, shift, lnprev, xprow, keep, red);
 }
 // GPT and PARRALEL rows (a.par).  CKPT (GPT mode only): the pass commits nothing -- every row's LayerNorm output goes to a.ckpt, what a state holds
 // once that row is the last one fed, and neither a.state_new nor a slot is written (spec.hip.h k_spec_commit copies the row that stands).

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "rwkv_forward_segments", "rwkv_segment_plan",
     "rwkv_spec_verify_segments",
     "rwkv_sample_rows", "rwkv_spec_sample_segments",
+    "rwkv_tree_plan", "rwkv_spec_verify_trees", "rwkv_spec_sample_trees",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
@@ -209,6 +210,89 @@ def lookup_streams(verify, histories, n_tokens: int, k: int = 8, n: int = 3, pas
     return np.asarray(out, dtype=np.int64).reshape(N, n_tokens), stats
 
 
+def tree_plan(segments, max_ctx: int, pass_rows: int = 64):
+    """rwkv_tree_plan, host only (no model, no device): validates `segments`, a list of (slot, token_ids, n_draft, parent) -- parent[r] per row
+    of the segment, counted from its first row, read for the draft rows -- and returns (row_from, row_depth): per row of the call the row it
+    starts from (a segment's first row: itself) and its depth below the segment's last certain row.  A list that breaks a rule raises RWKVError."""
+    arr, n, toks, par, T = _tree_segments(segments)
+    frm, dep = np.zeros(max(1, T), np.uint8), np.zeros(max(1, T), np.uint8)
+    u8p = C.POINTER(C.c_uint8)
+    _chk(lib().rwkv_tree_plan(toks, par, arr, n, int(max_ctx), int(pass_rows), frm.ctypes.data_as(u8p), dep.ctypes.data_as(u8p), None))
+    return frm[:T], dep[:T]
+
+
+def _tree_segments(segments):
+    """(SpecSegment array, count, ids, parents, rows) of a list of (slot, token_ids, n_draft, parent); parent None is a chain"""
+    segs = [(int(s), [int(t) for t in ids], int(nd), [max(0, r - 1) for r in range(len(ids))] if par is None else [int(p) for p in par]) for s, ids, nd, par in segments]
+    if any(len(ids) != len(par) for _, ids, _, par in segs):
+        raise ValueError("need one parent entry per id of a segment")
+    n = len(segs)
+    arr = (SpecSegment * max(1, n))(*[SpecSegment(s, len(ids), nd, 0) for s, ids, nd, _ in segs])
+    ids = [t for _, i, _, _ in segs for t in i]
+    par = [p for _, _, _, pp in segs for p in pp]
+    if any(not 0 <= p <= 255 for p in par):
+        raise ValueError("a parent is a row of its segment, 0 .. 255")
+    return arr, n, (C.c_uint64 * max(1, len(ids)))(*ids), (C.c_uint8 * max(1, len(par)))(*par), len(ids)
+
+
+def ngram_draft_tree(history, k: int, n: int = 3, branches: int = 3):
+    """the host-side lookup drafter for draft TREES (no model): the continuations behind the most recent `branches` earlier occurrences of the
+    last n ids of `history`, most recent first, merged into a trie of at most k nodes.  Returns (ids, parent): node j carries ids[j] and hangs
+    below node parent[j] < j, or below the history's last id where parent[j] == -1; siblings differ.  ([], []) where ngram_draft gives []."""
+    h = [int(t) for t in history]
+    n, k, branches = int(n), int(k), int(branches)
+    ids, parent = [], []
+    if n < 1 or k < 1 or branches < 1 or len(h) <= n:
+        return ids, parent
+    tail = h[-n:]
+    conts = [h[s + n:s + n + k] for s in range(len(h) - n - 1, -1, -1) if h[s:s + n] == tail][:branches]
+    at = [-1] * len(conts)                                  # per continuation: the node it has reached, None once it could not go on
+    for d in range(k):                                      # level by level: the ids nearest the root are the likeliest to stand
+        for b, cont in enumerate(conts):
+            if at[b] is None or d >= len(cont):
+                continue
+            child = next((j for j in range(len(ids)) if parent[j] == at[b] and ids[j] == cont[d]), None)
+            if child is None and len(ids) < k:
+                ids.append(cont[d]); parent.append(at[b])
+                child = len(ids) - 1
+            at[b] = child
+    return ids, parent
+
+
+def lookup_tree_streams(verify, histories, n_tokens: int, k: int = 8, n: int = 3, branches: int = 3, pass_rows: int = 64):
+    """lookup_streams with ngram_draft_tree over verify(segments) -> [(n_accepted, next, row, accepted ids)] (RWKV.spec_verify_trees): a stream's
+    round brings a trie of at most k nodes, of which no path is longer than the ids the stream still wants."""
+    hist = [[int(t) for t in h] for h in histories]
+    if not hist or any(not h for h in hist):
+        raise ValueError("every history holds at least the id to feed first")
+    n_tokens, N = int(n_tokens), len(hist)
+    if N > pass_rows:
+        raise ValueError(f"{N} streams do not fit one pass of {pass_rows} rows")
+    out = [[] for _ in range(N)]
+    stats = [dict(rounds=0, drafted=0, accepted=0) for _ in range(N)]
+    while True:
+        live = [s for s in range(N) if len(out[s]) < n_tokens]
+        if not live:
+            break
+        room = pass_rows // len(live) - 1
+        segs = []
+        for s in live:
+            kd, deep = min(int(k), SPEC_MAX_DRAFT, room), n_tokens - len(out[s]) - 1
+            ids, par = ngram_draft_tree(hist[s], kd, n, branches) if kd > 0 and deep > 0 else ([], [])
+            depth, keep = [], []                            # cut the trie at the depth the stream still wants: a parent goes before its children
+            for j, p in enumerate(par):
+                depth.append(1 if p < 0 else depth[p] + 1)
+                if depth[j] <= deep:
+                    keep.append(j)
+            new = {j: i for i, j in enumerate(keep)}
+            segs.append((s, [hist[s][-1]] + [ids[j] for j in keep], len(keep), [0] + [1 + new[par[j]] if par[j] >= 0 else 0 for j in keep]))
+        for (s, _, nd, _), (a, nx, _, acc) in zip(segs, verify(segs)):
+            new = list(acc) + [int(nx)]
+            out[s] += new; hist[s] += new
+            stats[s]["rounds"] += 1; stats[s]["drafted"] += nd; stats[s]["accepted"] += a
+    return np.asarray(out, dtype=np.int64).reshape(N, n_tokens), stats
+
+
 class Automaton(C.Structure):
     """rwkv_automaton of include/rwkv_mi355x.h (40 bytes)"""
     _fields_ = [("n_states", C.c_uint32), ("reserved", C.c_uint32), ("nnz", C.c_uint64), ("row_ptr", C.POINTER(C.c_uint32)),
@@ -365,6 +449,14 @@ def lib():
     L.rwkv_spec_sample_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(SpecSegment), u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(u64), C.c_uint32,
                                             C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64)]
     L.rwkv_spec_sample_segments.restype = i32
+    u8p = C.POINTER(C.c_uint8)
+    L.rwkv_tree_plan.argtypes = [C.POINTER(u64), u8p, C.POINTER(SpecSegment), u64, u64, C.c_uint32, u8p, u8p, C.POINTER(u64)]; L.rwkv_tree_plan.restype = i32
+    L.rwkv_spec_verify_trees.argtypes = [vp, C.POINTER(u64), u8p, C.POINTER(SpecSegment), u64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64),
+                                         C.POINTER(u64)]
+    L.rwkv_spec_verify_trees.restype = i32
+    L.rwkv_spec_sample_trees.argtypes = [vp, C.POINTER(u64), u8p, C.POINTER(SpecSegment), u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(u64), C.c_uint32,
+                                         C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
+    L.rwkv_spec_sample_trees.restype = i32
     L.rwkv_segment_plan.argtypes = [C.POINTER(Segment), u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(u64)]; L.rwkv_segment_plan.restype = i32
     _lib = L
     return L
@@ -981,6 +1073,52 @@ class RWKV:
         are those of repeated spec_verify_segments([(s, [token], 0)])."""
         rows = 32 if int(os.environ.get("RWKV_SEQ_ROWS", "64")) <= 32 else 64
         return lookup_streams(self.spec_verify_segments, histories, n_tokens, k, n, min(self.maxContext, rows))
+
+    # -- draft trees for many streams (include/rwkv_mi355x.h rwkv_spec_verify_trees) ---------------------------------------------
+    def spec_verify_trees(self, segments):
+        """spec_verify_segments over draft TREES: `segments` is a list of (slot, token_ids, n_draft, parent), parent[r] per id of the segment
+        (counted from its first id; read for the last n_draft; None: a chain) naming the last certain id or an earlier guess.  Of the guesses the
+        one path from the root that the greedy picks confirm is kept.  Returns [(n_accepted, next, row, accepted ids)] per segment."""
+        return self._verify_trees(segments, lambda toks, par, arr, n, acc, nx, row, em: lib().rwkv_spec_verify_trees(
+            self._h, toks, par, arr, n, 0, acc, nx, row, em))
+
+    def spec_sample_trees(self, segments, picks, seeds, step0):
+        """spec_verify_trees with SAMPLED acceptance (spec_sample_segments for trees): a row is drawn by picks[i] at step step0[i] + its depth
+        below the last certain id; a segment emits n_accepted + 1 ids, so its next step0 is step0 + n_accepted + 1."""
+        if len(picks) != len(segments) or len(seeds) != len(segments) or len(step0) != len(segments):
+            raise ValueError("need one pick, seed and step0 per segment")
+        m = max(1, len(segments))
+        pk = (Pick * m)(*picks)
+        sd = (C.c_uint64 * m)(*[int(x) for x in seeds])
+        st = (C.c_uint64 * m)(*[int(x) for x in step0])
+        return self._verify_trees(segments, lambda toks, par, arr, n, acc, nx, row, em: lib().rwkv_spec_sample_trees(
+            self._h, toks, par, arr, n, pk, sd, st, 0, acc, nx, row, em))
+
+    def _verify_trees(self, segments, call):
+        """the marshalling of spec_verify_trees / spec_sample_trees around call(ids, parents, segment array, count, n_accepted, next, row, emitted)"""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        arr, n, toks, par, _ = _tree_segments(segments)
+        m = max(1, n)
+        acc, nx, row, em = (C.c_uint32 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * m)(), (C.c_uint64 * (m * SPEC_MAX_DRAFT))()
+        slots = min(self.maxContext, 1 + max([int(s.slot) for s in arr[:n]], default=0))
+        if not self.resident:
+            self.push_state(slots)
+        _chk(call(toks, par, arr, n, acc, nx, row, em))
+        if not self.resident:
+            self.pull_state(slots)
+        return [(int(acc[i]), int(nx[i]), int(row[i]), [int(t) for t in em[i * SPEC_MAX_DRAFT:i * SPEC_MAX_DRAFT + acc[i]]]) for i in range(n)]
+
+    def decode_lookup_tree_streams(self, histories, n_tokens: int, k: int = 8, n: int = 3, branches: int = 3):
+        """decode_lookup_streams with draft trees (lookup_tree_streams over spec_verify_trees): the ids are those of decode_lookup_streams, the
+        rounds are fewer where a history continues in more than one way."""
+        rows = 32 if int(os.environ.get("RWKV_SEQ_ROWS", "64")) <= 32 else 64
+        return lookup_tree_streams(self.spec_verify_trees, histories, n_tokens, k, n, branches, min(self.maxContext, rows))
+
+    def decode_lookup_tree(self, history, n_tokens: int, k: int = 8, n: int = 3, branches: int = 3):
+        """decode_lookup with draft trees: one stream on slot 0.  Returns (ids, stats)."""
+        out, stats = self.decode_lookup_tree_streams([history], n_tokens, k, n, branches)
+        return out[0], stats[0]
 
     def decode_speculative(self, draft_model: "RWKV", first_token: int, n_tokens: int, k: int = 4):
         """greedy continuation of n_tokens ids with `draft_model` (a second loaded model on the same device whose slot 0 holds the same prefix,
