@@ -352,6 +352,9 @@ public:
         static Pick greedy() { return Pick{}; }
         static Pick typical(float temp = 0.9f, float tau = 0.8f, bool recipe = RWKV_TYPICAL_RECIPE != 0) { Pick p; p.kind = RWKV_PICK_TYPICAL; p.temp = temp; p.tau = tau; p.recipe = recipe; return p; }
         static Pick nucleus(const Nucleus &s) { Pick p; p.kind = RWKV_PICK_NUCLEUS; p.s = s; return p; }
+        // the floor cuts (rwkv_mi355x.h "min-p and Mirostat v2"): s gives temperature and penalties, its top_p and top_k are switched off
+        static Pick minp(float min_p, const Nucleus &s) { Pick p; p.kind = RWKV_PICK_MINP; p.tau = min_p; p.temp = 1.0f; p.s = s; p.s.top_p = 1.0f; p.s.top_k = 0; return p; }
+        static Pick mirostat(float tau, float eta, const Nucleus &s) { Pick p; p.kind = RWKV_PICK_MIROSTAT; p.tau = tau; p.temp = eta; p.s = s; p.s.top_p = 1.0f; p.s.top_k = 0; return p; }
     };
     // ids[s * n + k] (0 behind a stream's end), len[s] tokens of stream s count, reason[s]: 0 ran all n, 1 budget, 2 + j sequence j;
     // steps_run: the steps the device was given (rwkv_mi355x.h "bounded run-ahead")
@@ -664,6 +667,24 @@ private:
         return r;
     }
 public:
+    // one min-p or Mirostat draw (Pick::minp / Pick::mirostat) from logits row `row` of the last forward with the counts and the mu of slot `slot`;
+    // update: counts and mu move behind the pick
+    int sampleFloor(const Pick &pick, double u, bool ban0 = false, bool update = false, unsigned long long row = 0, unsigned long long slot = 0)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        uint64_t tok = 0;
+        const rwkv_pick p = pickOf(pick, (ban0 ? RWKV_NUCLEUS_BAN0 : 0u) | (update ? RWKV_NUCLEUS_UPDATE : 0u));
+        rwkv_detail::check(rwkv_sample_floor(ctx_, row, slot, &p, u, &tok));
+        return (int)tok;
+    }
+    // Mirostat's running threshold of slots slot0 .. slot0 + n - 1
+    void setMirostat(unsigned long long slot0, const std::vector<double> &mu) { rwkv_detail::check(rwkv_mirostat_set(ctx_, slot0, mu.size(), mu.data())); }
+    std::vector<double> getMirostat(unsigned long long slot0, unsigned long long n)
+    {
+        std::vector<double> mu(n);
+        rwkv_detail::check(rwkv_mirostat_get(ctx_, slot0, n, mu.data()));
+        return mu;
+    }
     // the occurrence counts of one slot (50277 floats): save / restore a session, or upload a prompt's counts; empty = zero them
     void setPenaltyCounts(unsigned long long slot, const std::vector<float> &counts)
     {

@@ -253,12 +253,14 @@ int rwkv_penalty_get(rwkv_ctx *ctx, uint64_t slot, float *counts /* host [50277]
 #define RWKV_STOP_MAX_LEN 8u
 #define RWKV_STOP_POLL 8u /* steps per block of the bounded run-ahead */
 #define RWKV_STOP_KEEP 1u /* continue the slots' match history from the previous call */
-enum rwkv_pick_kind { RWKV_PICK_GREEDY = 0, RWKV_PICK_TYPICAL = 1, RWKV_PICK_NUCLEUS = 2 };
+enum rwkv_pick_kind { RWKV_PICK_GREEDY = 0, RWKV_PICK_TYPICAL = 1, RWKV_PICK_NUCLEUS = 2, RWKV_PICK_MINP = 3, RWKV_PICK_MIROSTAT = 4 };
 typedef struct rwkv_pick {
     int kind;
-    float temp, tau;
+    float temp, tau;             /* TYPICAL: temp and tau.  MINP: tau = min_p in (0, 1], temp not read.  MIROSTAT: tau = the target surprise in bits
+                                  * (> 0, finite), temp = eta, the learning rate (> 0, finite).  The sampling temperature of MINP and MIROSTAT is nucleus.temp */
     int typical_flags;           /* TYPICAL: as rwkv_decode_batch_typical */
-    rwkv_nucleus_params nucleus; /* NUCLEUS: as rwkv_decode_batch_nucleus */
+    rwkv_nucleus_params nucleus; /* NUCLEUS: as rwkv_decode_batch_nucleus.  MINP, MIROSTAT: temp, presence, frequency, decay and flags as there;
+                                  * top_p >= 1, top_k == 0 and reserved == 0 are required (rwkv_sample_floor below) */
 } rwkv_pick;
 typedef struct rwkv_stop_params {
     const uint64_t *seq_ids; /* host: the stop sequences, concatenated */
@@ -274,6 +276,37 @@ int rwkv_decode_batch_until(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_
                             uint32_t *out_reason /* [n_streams], may be NULL */, uint64_t *steps_run /* may be NULL */);
 int rwkv_debug_stop_scan(rwkv_ctx *ctx, const uint64_t *ids /* host [n][steps] */, const uint64_t *first_tokens, uint64_t n, uint64_t steps,
                          const rwkv_stop_params *stop, uint32_t *out_len, uint32_t *out_reason);
+
+/* ---- min-p and Mirostat v2 sampling, on the device: the two probability-floor cuts (no reference counterpart) ----
+ * Both keep { i : p_i >= floor } with a floor that is known as soon as the row's maximum (min-p) or its log-sum-exp (Mirostat) is, so they need no
+ * order statistic: two launches and no per-token scratch (csrc/floor.hip.h), where nucleus sampling takes three and 1.84 MB per row.  For one
+ * logits row l (f32 widened to f64), one count vector c and, for Mirostat, one mu (f64, one per state slot):
+ *   1. penalty  l'_i exactly as step 1 of nucleus sampling above (the device calls the same function); mx = max l'
+ *   2. kept     evaluated in f64 exactly as written:
+ *      MINP      i is kept iff l'_i - mx >= lnf, lnf = log((double)min_p) computed once on the host.  The cut is on the UNTEMPERED distribution, like
+ *                this project's top-p.  min_p = 1 keeps the top token and its exact ties.  One subtraction and one comparison: a numpy restatement
+ *                gives the same kept set bit for bit
+ *      MIROSTAT  d_i = (l'_i - mx) / temp, Z = sum over l'_i > -inf of exp(d_i), S_i = (log Z - d_i) / ln 2: the surprise in bits on the TEMPERED
+ *                distribution.  i is kept iff S_i <= mu; if nothing is, the top token and its exact ties are
+ *   3. weights  exp((l'_i - mx) / temp) on the kept set (the largest is exactly 1); inverse CDF in token order for u in [0, 1); in the loops u of
+ *               step k = uniform(splitmix64(seed + k)), the generator of the other loops
+ *   4. update   counts as step 8 of nucleus sampling; MIROSTAT then mu <- mu - eta (S_g - tau) for the pick g.  S_g is the surprise under the
+ *               UNTRUNCATED tempered distribution: the rule of the Mirostat paper and of its authors' implementation.  llama.cpp takes the
+ *               probability renormalised over the kept set instead; the two differ whenever something is cut.
+ * Parameters ride in rwkv_pick without a change of layout (documented at the struct).  mu is one [max_ctx] f64 buffer of the context, allocated
+ * zeroed at the first call that needs it, counted by rwkv_resident_bytes, moved by rwkv_mirostat_set / _get.  The generation loops
+ * (rwkv_decode_batch_until, _logprobs, _constrained; n_streams == 1 on the decode kernels) accept both kinds; a Mirostat loop starts its slots at
+ * mu = 2 tau unless RWKV_NUCLEUS_KEEP is set: with it a 16-step call equals an 8-step call followed by an 8-step KEEP call with seed + 8, ids and mu.
+ * A stream parked by a stop keeps the mu of its stop (the invariant of rwkv_decode_batch_until extends to mu).  rwkv_sample_floor is the single
+ * draw, the twin of rwkv_sample_nucleus: counts and mu move only with RWKV_NUCLEUS_UPDATE.  rwkv_pick_constrained and rwkv_sample_rows accept
+ * the kinds as well; in rwkv_sample_rows a Mirostat query names its slot's mu under the rule of the counts, held separately for mu (one updater of a slot's mu, no reader beside
+ * it).  rwkv_spec_sample_* and rwkv_decode_beam do not take them.
+ * Status: RWKV_E_ARG for what rwkv_sample_nucleus rejects, a kind other than MINP or MIROSTAT (rwkv_sample_floor), min_p outside (0, 1], a tau or
+ * eta that is not finite and > 0, top_p < 1 or top_k != 0.  Every check runs before anything is launched or allocated.
+ * Held draw by draw to an f64 numpy evaluation on planted logits by tests/test_floor_gpu.py; include/rwkv_sampler.h minp_u / mirostat_u are the host twins. */
+int rwkv_sample_floor(rwkv_ctx *ctx, uint64_t row, uint64_t slot, const rwkv_pick *pick, double u, uint64_t *token);
+int rwkv_mirostat_set(rwkv_ctx *ctx, uint64_t slot0, uint64_t n, const double *mu /* host [n] */);
+int rwkv_mirostat_get(rwkv_ctx *ctx, uint64_t slot0, uint64_t n, double *mu /* host [n] */);
 
 /* ---- scoring: how probable is a given token, on the device (no reference counterpart: the reference only generates) ----
  * What they replace is a download: rwkv_forward, rwkv_get_output of [n][50277] f32 logits (201 KB per position) and a log-softmax on
@@ -651,16 +684,17 @@ int rwkv_spec_verify_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T], the 
  * synchronous on return; works on any context with a head.  64 is one pass of the segmented forward and one round of 1024-thread workgroups on
  * the device's compute units; the sampler's scratch (1.84 MB per row: the batched-decode scratch, grown to min(n, 64) rows -- 118 MB) stays inside
  * the Infinity Cache.  A call of greedy queries alone allocates only the partials.  rwkv_resident_bytes counts the buffers, rwkv_free frees them.
- * Status: RWKV_E_ARG for a NULL pointer, n == 0 or n > RWKV_MAX_PICK_ROWS, a row or slot >= max_ctx, a kind other than GREEDY or NUCLEUS, whatever
+ * Status: RWKV_E_ARG for a NULL pointer, n == 0 or n > RWKV_MAX_PICK_ROWS, a row or slot >= max_ctx, a kind other than GREEDY, NUCLEUS, MINP or MIROSTAT, whatever
  * rwkv_sample_nucleus rejects in the parameters, u outside [0, 1) without RWKV_PICKQ_SEED, unknown flag bits or reserved != 0, an updating slot
  * named again; RWKV_E_STATE when the context is not loaded or has no head.  Every check runs before anything is launched or allocated: a rejected
  * call leaves state, logits, counts and buffers as they were.
+ * RWKV_PICK_MINP / RWKV_PICK_MIROSTAT queries pick what rwkv_sample_floor picks (two launches per batch, csrc/floor.hip.h); RWKV_NUCLEUS_UPDATE moves counts and mu.
  * Out of scope: typical sampling per query, constrained picks per query (rwkv_pick_constrained is one call per stream). */
 #define RWKV_MAX_PICK_ROWS 1024u
 #define RWKV_PICKQ_SEED 1u /* u = uniform(splitmix64(seed + step)); else the query's u */
 typedef struct rwkv_pick_query {
     uint32_t row, slot;      /* logits row of the LAST forward; count vector of this state slot (read only with a penalty) */
-    rwkv_pick pick;          /* kind RWKV_PICK_GREEDY or RWKV_PICK_NUCLEUS; nucleus.flags: BAN0, UPDATE as in rwkv_sample_nucleus */
+    rwkv_pick pick;          /* kind RWKV_PICK_GREEDY, _NUCLEUS, _MINP or _MIROSTAT (the last two as rwkv_sample_floor); nucleus.flags: BAN0, UPDATE as in rwkv_sample_nucleus */
     uint64_t seed, step;
     double u;
     uint32_t flags, reserved; /* RWKV_PICKQ_SEED; reserved must be 0 */

@@ -168,6 +168,57 @@ inline void nucleus_count(float *counts, int pick, float decay)
     counts[pick] += 1.0f;
 }
 
+// ---- min-p and Mirostat v2: the host twins of the device's floor sampler (csrc/floor.hip.h; the semantics are those of
+// include/rwkv_mi355x.h rwkv_sample_floor).  Penalty and ban as nucleus_weights; the kept set in f64 exactly as the header writes it.
+inline std::vector<double> floor_logits(const float *_logits, const float *counts, float presence, float frequency, bool ban0)
+{
+    std::vector<double> l(50277);
+    for (int i = 0; i < 50277; i++) {
+        l[i] = _logits[i];
+        if (counts && (presence != 0.f || frequency != 0.f) && counts[i] > 0.f) l[i] -= (double)presence + (double)counts[i] * (double)frequency;
+    }
+    if (ban0) l[0] = -99.0;
+    return l;
+}
+// the inverse CDF in token order over weights exp((l - mx) inv_temp) on kept(l); *lpick (may be nullptr): l of the pick
+template <class Kept>
+inline int floor_draw(const std::vector<double> &l, double mx, double inv_temp, double u, Kept kept, double *lpick = nullptr)
+{
+    double total = 0;
+    for (double v : l) if (kept(v)) total += std::exp((v - mx) * inv_temp);
+    const double target = u * total;
+    double c = 0;
+    int last = 0, sel = -1;
+    for (int i = 0; i < (int)l.size() && sel < 0; i++)
+        if (kept(l[i])) { const double w = std::exp((l[i] - mx) * inv_temp); if (w > 0) { c += w; last = i; if (target < c) sel = i; } }
+    if (sel < 0) sel = last;
+    if (lpick) *lpick = l[sel];
+    return sel;
+}
+// min-p: keep p_i >= min_p p_max on the untempered distribution, draw at _temp
+inline int minp_u(const float *_logits, const float *counts, float _temp, float min_p, double u, float presence = 0.f, float frequency = 0.f, bool ban0 = false)
+{
+    const std::vector<double> l = floor_logits(_logits, counts, presence, frequency, ban0);
+    const double mx = *std::max_element(l.begin(), l.end()), lnf = std::log((double)min_p);
+    return floor_draw(l, mx, _temp == 1.0f ? 1.0 : 1.0 / (double)_temp, u, [&](double v) { return v - mx >= lnf; });
+}
+// Mirostat v2: keep the tokens whose surprise (bits, tempered distribution) is at most *mu, draw, then *mu <- *mu - eta (S_pick - tau) when `update`
+inline int mirostat_u(const float *_logits, const float *counts, float _temp, float tau, float eta, double *mu, double u, float presence = 0.f,
+                      float frequency = 0.f, bool ban0 = false, bool update = true)
+{
+    const std::vector<double> l = floor_logits(_logits, counts, presence, frequency, ban0);
+    const double mx = *std::max_element(l.begin(), l.end()), it = _temp == 1.0f ? 1.0 : 1.0 / (double)_temp, ln2 = 0.693147180559945309417232121458;
+    double z = 0;
+    for (double v : l) if (v > -INFINITY) z += std::exp((v - mx) * it);
+    const double logZ = std::log(z), m = *mu;
+    auto S = [&](double v) { return (logZ - (v - mx) * it) / ln2; };
+    const bool any = S(mx) <= m;
+    double lg = mx;
+    const int g = floor_draw(l, mx, it, u, [&](double v) { return any ? S(v) <= m : v == mx; }, &lg);
+    if (update) *mu = m - (double)eta * (S(lg) - (double)tau);
+    return g;
+}
+
 // ---- stop sequences and budgets: the host twin of the scan the device decode loops make behind every pick (csrc/stop.hip.h; the semantics
 // are those of include/rwkv_mi355x.h rwkv_decode_batch_until) for ONE stream.  ids: the picks g_0 .. g_{n-1} of an n-step call fed `first`;
 // stops: the stop sequences (each 1 .. 8 ids); max_new: the budget (0: none; n is none too).  history: the stream's newest ids, oldest first,

@@ -19,6 +19,7 @@
 #include "specseg.hip.h"
 #include "spectree.hip.h"
 #include "pickrows.hip.h"
+#include "floor.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -257,6 +258,7 @@ enum GrownBuf {
     SPECSAMPLE_IO,                    // rwkv_spec_sample_segments, SpecSampleIo: the query table in front of a SpecSegIo, so that ONE copy still carries the upload
     SPECTREE_IO,                      // rwkv_spec_verify_trees / rwkv_spec_sample_trees (spectree.hip.h), SpecTreeIo: query table | ids | plan | segment table | from table,
                                       // behind them the records, the accepted ids and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT
+    MIRO_MU,                          // f64 [max_ctx]: Mirostat's running threshold per state slot (floor.hip.h); allocated ONCE, zeroed, at the first call that needs it
     N_GROWN
 };
 
@@ -1757,6 +1759,15 @@ int check_nucleus(const rwkv_nucleus_params *p)
     if ((p->flags & ~NUCLEUS_FLAGS) || p->reserved) return fail(RWKV_E_ARG, "unknown flag bits (0x%x) or reserved != 0", p->flags);
     return 0;
 }
+bool pick_floor(const rwkv_pick &pk) { return pk.kind == RWKV_PICK_MINP || pk.kind == RWKV_PICK_MIROSTAT; }
+// a floor pick (floor.hip.h): pick.nucleus for temperature, penalties and flags, without its cuts; the floor in the two outer floats
+int check_floor(const rwkv_pick &pk)
+{
+    if (const int rc = check_nucleus(&pk.nucleus)) return rc;
+    if (!(pk.nucleus.top_p >= 1.f) || pk.nucleus.top_k != 0u) return fail(RWKV_E_ARG, "a floor cut does not combine with top-p or top-k: need top_p >= 1 and top_k == 0");
+    if (pk.kind == RWKV_PICK_MINP) return pk.tau > 0.f && pk.tau <= 1.f ? 0 : fail(RWKV_E_ARG, "min_p (tau) must be in (0, 1]");
+    return pk.tau > 0.f && std::isfinite(pk.tau) && pk.temp > 0.f && std::isfinite(pk.temp) ? 0 : fail(RWKV_E_ARG, "Mirostat needs a finite tau > 0 and a finite eta (temp) > 0");
+}
 // the pick's own parameters are acceptable
 int check_pick(const rwkv_pick &pk)
 {
@@ -1764,11 +1775,12 @@ int check_pick(const rwkv_pick &pk)
     case RWKV_PICK_GREEDY: return 0;
     case RWKV_PICK_TYPICAL: return pk.temp > 0.f ? 0 : fail(RWKV_E_ARG, "need temp > 0");
     case RWKV_PICK_NUCLEUS: return check_nucleus(&pk.nucleus);
+    case RWKV_PICK_MINP: case RWKV_PICK_MIROSTAT: return check_floor(pk);
     default: return fail(RWKV_E_ARG, "unknown pick kind %d", pk.kind);
     }
 }
 // an unknown kind answers in front of decode_batch's checks
-int check_pick_kind(const rwkv_pick &pk) { return pk.kind < RWKV_PICK_GREEDY || pk.kind > RWKV_PICK_NUCLEUS ? check_pick(pk) : 0; }
+int check_pick_kind(const rwkv_pick &pk) { return pk.kind < RWKV_PICK_GREEDY || pk.kind > RWKV_PICK_MIROSTAT ? check_pick(pk) : 0; }
 // the ranges that several entry points share, each in the caller's words
 int check_steps(uint64_t n, const char *name) { return n == 0 || n > RWKV_MAX_DECODE_STEPS ? fail(RWKV_E_ARG, "%s must be in 1..%u", name, RWKV_MAX_DECODE_STEPS) : 0; }
 int check_row_slot(const rwkv_ctx *c, uint64_t row, uint64_t slot)
@@ -1779,7 +1791,7 @@ int check_slot_span(const rwkv_ctx *c, uint64_t slot0, uint64_t n)
 {
     return n != 0 && slot0 < c->maxT && n <= c->maxT - slot0 ? 0 : fail(RWKV_E_ARG, "slots %llu .. + %llu out of range (max context %llu)", (unsigned long long)slot0, (unsigned long long)n, (unsigned long long)c->maxT);
 }
-bool pick_penalty(const rwkv_pick &pk) { return pk.kind == RWKV_PICK_NUCLEUS && (pk.nucleus.presence != 0.f || pk.nucleus.frequency != 0.f); }
+bool pick_penalty(const rwkv_pick &pk) { return (pk.kind == RWKV_PICK_NUCLEUS || pk.kind == RWKV_PICK_MINP || pk.kind == RWKV_PICK_MIROSTAT) && (pk.nucleus.presence != 0.f || pk.nucleus.frequency != 0.f); }
 // the count vectors (device [max_ctx][V] f32): allocated and zeroed once
 int counts_alloc(rwkv_ctx *c)
 {
@@ -1803,6 +1815,30 @@ int pick_counts(rwkv_ctx *c, const rwkv_pick &pk, uint64_t slot0, uint64_t n, bo
     return 0;
 }
 
+// Mirostat's mu (device [max_ctx] f64, one per state slot): allocated and zeroed once
+int mu_alloc(rwkv_ctx *c)
+{
+    if (c->grown[MIRO_MU].p) return 0;
+    const size_t bytes = sizeof(double) * c->maxT;
+    void *q = nullptr;
+    HIPCHK(hipMalloc(&q, bytes));
+    c->grown[MIRO_MU].p = q; c->grown[MIRO_MU].bytes = bytes; c->alloc_bytes += bytes;
+    HIPCHK(hipMemsetAsync(q, 0, bytes, c->stream));
+    return 0;
+}
+// what a call with this pick needs of the mu of slots [slot0, slot0 + n): nothing unless Mirostat; else the buffer, and (`start`: the loops) those
+// slots at 2 tau unless the caller keeps them
+int pick_mu(rwkv_ctx *c, const rwkv_pick &pk, uint64_t slot0, uint64_t n, bool start)
+{
+    if (pk.kind != RWKV_PICK_MIROSTAT) return 0;
+    if (const int rc = mu_alloc(c)) return rc;
+    if (start && !(pk.nucleus.flags & RWKV_NUCLEUS_KEEP)) {
+        k_floor_mu_fill<<<dim3((unsigned)(n + 63) / 64), dim3(64), 0, c->stream>>>(c->buf<double>(MIRO_MU) + slot0, (unsigned)n, 2.0 * (double)pk.tau);
+        HIPCHK(hipGetLastError());
+    }
+    return 0;
+}
+
 // What the kernels take of a nucleus pick that is not the caller's number as it stands -- derived HERE, once, for NucleusArgs (make_sampler) and
 // for the query record of pickrows.hip.h (make_pickq).  `loop`: logit 0 always banned, the counts always updated (make_sampler)
 struct NucleusDerived { double inv_temp; unsigned top_k; int penalty, update, ban0; };
@@ -1823,7 +1859,10 @@ struct Sampler {
     int kind = RWKV_PICK_GREEDY;
     TypicalArgs t{};
     NucleusArgs n{};
-    DrawArgs &draw() { return kind == RWKV_PICK_NUCLEUS ? static_cast<DrawArgs &>(n) : t; }
+    FloorArgs f{};
+    bool floor() const { return kind == RWKV_PICK_MINP || kind == RWKV_PICK_MIROSTAT; }
+    NucleusArgs &counted() { return floor() ? static_cast<NucleusArgs &>(f) : n; }      // the record of a kind with count vectors
+    DrawArgs &draw() { return kind == RWKV_PICK_TYPICAL ? static_cast<DrawArgs &>(t) : counted(); }
 };
 // The sampler of a call that picks by `pk` (not greedy), on the context's single-row scratch.  `loop`: as a generation call of one stream runs it
 // (logit 0 always banned, the counts always updated, row and step from the control block, u from seed + step, the pick fed back); else the
@@ -1848,13 +1887,20 @@ Sampler make_sampler(rwkv_ctx *c, const rwkv_pick &pk, bool loop)
     } else {
         const rwkv_nucleus_params &p = pk.nucleus;
         const NucleusDerived nd = derive_nucleus(pk, loop);
-        s.n.inv_temp = nd.inv_temp;
-        s.n.top_p = p.top_p; s.n.top_k = nd.top_k;
-        s.n.presence = p.presence; s.n.frequency = p.frequency; s.n.decay = p.decay;
-        s.n.penalty = nd.penalty;
-        s.n.update = nd.update;
+        NucleusArgs &n = s.counted();
+        n.inv_temp = nd.inv_temp;
+        n.top_p = p.top_p; n.top_k = nd.top_k;
+        n.presence = p.presence; n.frequency = p.frequency; n.decay = p.decay;
+        n.penalty = nd.penalty;
+        n.update = nd.update;
         d.ban0 = nd.ban0;
-        s.n.counts = s.n.penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
+        n.counts = n.penalty ? c->buf<float>(PEN_COUNTS) : nullptr;
+    }
+    if (s.floor()) {      // the floor rides in the two outer floats (behind pick_mu)
+        s.f.miro = pk.kind == RWKV_PICK_MIROSTAT ? 1 : 0;
+        s.f.mu_update = s.f.update;
+        if (s.f.miro) { s.f.tau = (double)pk.tau; s.f.eta = (double)pk.temp; s.f.mu = c->buf<double>(MIRO_MU); }
+        else s.f.lnf = log((double)pk.tau);
     }
     return s;
 }
@@ -1869,7 +1915,10 @@ void sampler_to_batch(rwkv_ctx *c, Sampler &s, const unsigned long long *dseeds)
 // the sampler's three launches over `rows` logits rows (row onwards), each row with its own scratch slice and pick
 int enqueue_pick(rwkv_ctx *c, const Sampler &s, unsigned rows)
 {
-    if (s.kind == RWKV_PICK_NUCLEUS) {
+    if (s.floor()) {      // two launches, no scratch but the partials
+        k_floor_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.f);
+        k_floor<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(s.f);
+    } else if (s.kind == RWKV_PICK_NUCLEUS) {
         k_nucleus_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.n);
         k_nucleus_keys<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(s.n);
         k_nucleus<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(s.n);
@@ -2217,6 +2266,7 @@ int grow_pick_buffers(rwkv_ctx *c, int kind, uint64_t rows)
         return grow_buffer(c, BD_IDX, sizeof(unsigned) * rows * AM_SLICES);
     }
     if (const int rc = grow_buffer(c, BD_PART, sizeof(double) * rows * TS_PART_ROW)) return rc;
+    if (kind == RWKV_PICK_MINP || kind == RWKV_PICK_MIROSTAT) return 0;      // a floor cut has no per-token scratch
     if (const int rc = grow_buffer(c, BD_P, sizeof(float) * rows * TS_ROW)) return rc;
     if (const int rc = grow_buffer(c, BD_PW, sizeof(float) * rows * TS_ROW)) return rc;
     return grow_buffer(c, BD_KEY, sizeof(unsigned) * rows * TS_ROW);
@@ -2256,6 +2306,7 @@ struct DecodeRun {
         if (const int rc = cn ? constrainer_setup(c, *cn, 0, 0, N, d.cp->bias_ptr, d.cp->bias_tok, d.cp->bias_val, st, d.cp->start) : 0) return rc;
         if (const int rc = lp ? lp_setup(c, *lp, N, d.n_steps, d.lp->top_n) : 0) return rc;
         if (const int rc = pick_counts(c, d.pick, 0, N, true)) return rc;
+        if (const int rc = pick_mu(c, d.pick, 0, N, true)) return rc;
         c->bd_host.assign(N * (d.n_steps + 1), 0ull);       // many: the upload; both: the download of the picks, [step][stream]
         if (one) {
             if (const int rc = set_ctl(c, d.first[0], 0, 0)) return rc;
@@ -2270,6 +2321,7 @@ struct DecodeRun {
             if (one) smp.draw().seed = d.seeds[0];
             else sampler_to_batch(c, smp, ids - N);
             if (cn) cn->feed(smp);
+            if (smp.floor()) smp.f.stopped = st ? st->a.len : nullptr;       // a stopped stream keeps its mu (floor.hip.h FloorArgs)
         }
         if (cn) cn->v.feedback = one && !sampled ? 1 : 0;      // one stream, greedy: k_constraint_advance feeds the pick back
         return 0;
@@ -2390,6 +2442,46 @@ int rwkv_sample_nucleus(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_nuc
     }());
 }
 
+int rwkv_sample_floor(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_pick *pick, double u, uint64_t *token)
+{
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, pick && token)) return rc;
+    if (const int rc = check_row_slot(c, row, slot)) return rc;
+    if (!pick_floor(*pick)) return fail(RWKV_E_ARG, "kind %d is neither min-p nor Mirostat", pick->kind);
+    if (const int rc = check_pick(*pick)) return rc;
+    if (!(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need 0 <= u < 1");
+    return finish(c, [&]() -> int {
+        if (const int rc = pick_counts(c, *pick, slot, 1, false)) return rc;
+        if (const int rc = pick_mu(c, *pick, slot, 1, false)) return rc;
+        Sampler s = make_sampler(c, *pick, false);
+        s.f.row = (int)row; s.f.slot = (unsigned)slot; s.f.u = u;
+        if (const int rc = enqueue_pick(c, s, 1)) return rc;
+        HIPCHK(hipMemcpyAsync(token, c->pick, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+}
+
+int rwkv_mirostat_set(rwkv_ctx *c, uint64_t slot0, uint64_t n, const double *mu)
+{
+    if (const int rc = guard(c, NEED_LOADED, mu)) return rc;
+    if (const int rc = check_slot_span(c, slot0, n)) return rc;
+    return finish(c, [&]() -> int {
+        if (const int rc = mu_alloc(c)) return rc;
+        HIPCHK(hipMemcpyAsync(c->buf<double>(MIRO_MU) + slot0, mu, sizeof(double) * n, hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }());
+}
+
+int rwkv_mirostat_get(rwkv_ctx *c, uint64_t slot0, uint64_t n, double *mu)
+{
+    if (const int rc = guard(c, NEED_LOADED, mu)) return rc;
+    if (const int rc = check_slot_span(c, slot0, n)) return rc;
+    if (!c->grown[MIRO_MU].p) { std::fill(mu, mu + n, 0.0); return 0; }      // zero is what an unallocated buffer holds
+    return finish(c, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(mu, c->buf<double>(MIRO_MU) + slot0, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+}
+
 int rwkv_decode_nucleus(rwkv_ctx *c, uint64_t first_token, uint64_t n, const rwkv_nucleus_params *p, uint64_t seed, uint64_t *out_tokens)
 {
     if (const int rc = guard(c, NEED_WHOLE | LAUNCHES, p && out_tokens)) return rc;
@@ -2504,7 +2596,7 @@ int rwkv_pick_constrained(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_p
     if (const int rc = check_row_slot(c, row, slot)) return rc;
     if (pick->kind == RWKV_PICK_TYPICAL) return fail(RWKV_E_ARG, "typical sampling under a constraint is out of scope: pick greedy or nucleus");
     if (const int rc = check_pick(*pick)) return rc;
-    const bool sampled = pick->kind == RWKV_PICK_NUCLEUS;
+    const bool sampled = pick->kind != RWKV_PICK_GREEDY;
     if (sampled && !(u >= 0.0 && u < 1.0)) return fail(RWKV_E_ARG, "need 0 <= u < 1");
     if (bias && bias->reserved) return fail(RWKV_E_ARG, "reserved != 0");
     if (const int rc = bias ? check_bias(bias->n, bias->tok, bias->val) : 0) return rc;
@@ -2516,9 +2608,10 @@ int rwkv_pick_constrained(rwkv_ctx *c, uint64_t row, uint64_t slot, const rwkv_p
         if (const int rc = cn.rows(c, 1)) return rc;
         if (sampled) {
             if (const int rc = pick_counts(c, *pick, slot, 1, false)) return rc;
+            if (const int rc = pick_mu(c, *pick, slot, 1, false)) return rc;
             Sampler s = make_sampler(c, *pick, false);
             cn.feed(s);
-            s.n.row = (int)row; s.n.slot = (unsigned)slot; s.n.u = u;
+            s.counted().row = (int)row; s.counted().slot = (unsigned)slot; s.counted().u = u;
             if (const int rc = enqueue_pick(c, s, 1)) return rc;
         } else {
             if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, 1)) return rc;
@@ -3137,6 +3230,20 @@ PickQ make_pickq(const rwkv_pick &pk, bool ban, unsigned row, unsigned slot, uns
     q.u = u; q.seed = seed; q.step = step;
     return q;
 }
+// the record of a min-p or Mirostat query (floor.hip.h FloorQ: a PickQ's place in the table); PQ_UPDATE covers counts and mu
+FloorQ make_floorq(const rwkv_pick &pk, unsigned row, unsigned slot, unsigned out, bool use_seed, uint64_t seed, uint64_t step, double u)
+{
+    FloorQ q{};
+    const NucleusDerived nd = derive_nucleus(pk, false);
+    q.row = row; q.slot = slot; q.out = out;
+    q.flags = (pk.kind == RWKV_PICK_MINP ? PQ_MINP : PQ_MIROSTAT) | (nd.penalty ? PQ_PENALTY : 0u) | (nd.update ? PQ_UPDATE : 0u) | (nd.ban0 ? PQ_BAN0 : 0u) | (use_seed ? PQ_SEED : 0u);
+    q.inv_temp = nd.inv_temp;
+    if (pk.kind == RWKV_PICK_MINP) q.lnf = log((double)pk.tau);
+    else { q.m.tau = pk.tau; q.m.eta = pk.temp; }
+    q.presence = pk.nucleus.presence; q.frequency = pk.nucleus.frequency; q.decay = pk.nucleus.decay;
+    q.u = u; q.seed = seed; q.step = step;
+    return q;
+}
 // the sampler scratch of `rows` queries of one batch; greedy queries alone need the partials only
 int grow_pickq_scratch(rwkv_ctx *c, uint64_t rows, bool nucleus)
 {
@@ -3156,29 +3263,49 @@ int enqueue_pickq(rwkv_ctx *c, const PickQ *dq, unsigned n, unsigned long long *
     HIPCHK(hipGetLastError());
     return 0;
 }
-// the rules of rwkv_sample_rows behind the guard; *penalty / *nucleus: some query has one / is one
-int check_pick_queries(const rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, bool *penalty, bool *nucleus)
+// two launches per batch of PQ_BATCH floor queries of the device table dq[n], the ids into out[q.out]
+int enqueue_floorq(rwkv_ctx *c, const FloorQ *dq, unsigned n, unsigned long long *out)
+{
+    FloorQArgs g{dq, c->logits, c->buf<float>(PEN_COUNTS), c->buf<double>(MIRO_MU), out, c->buf<double>(BD_PART)};
+    for (unsigned b = 0; b < n; b += PQ_BATCH) {
+        const unsigned rows = std::min(n - b, PQ_BATCH);
+        g.q = dq + b;
+        k_floorq_stats<<<dim3(TS_G, rows), dim3(TS_GT), 0, c->stream>>>(g);
+        k_floorq<<<dim3(1, rows), dim3(TS_NT), 0, c->stream>>>(g);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the rules of rwkv_sample_rows behind the guard; *penalty / *nucleus / *miro: some query has one / is one; *n_floor: the floor queries
+int check_pick_queries(const rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, bool *penalty, bool *nucleus, bool *miro, uint64_t *n_floor)
 {
     if (n == 0 || n > RWKV_MAX_PICK_ROWS) return fail(RWKV_E_ARG, "n must be in 1..%u", RWKV_MAX_PICK_ROWS);
-    std::vector<uint32_t> upd, rd;       // the slots that penalty queries update / only read
-    *penalty = *nucleus = false;
+    // the slots whose count vector penalty queries update / only read, and the same for the mu of Mirostat queries: two buffers, two rules
+    std::vector<uint32_t> upd, rd, mu_upd, mu_rd;
+    *penalty = *nucleus = *miro = false;
+    *n_floor = 0;
     for (uint64_t i = 0; i < n; i++) {
         if (const int rc = check_row_slot(c, q[i].row, q[i].slot)) return rc;
-        if (q[i].pick.kind != RWKV_PICK_GREEDY && q[i].pick.kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "query %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, q[i].pick.kind);
+        if (q[i].pick.kind != RWKV_PICK_GREEDY && q[i].pick.kind != RWKV_PICK_NUCLEUS && !pick_floor(q[i].pick)) return fail(RWKV_E_ARG, "query %llu: kind %d is neither greedy nor nucleus, min-p or Mirostat", (unsigned long long)i, q[i].pick.kind);
         if ((q[i].flags & ~RWKV_PICKQ_SEED) || q[i].reserved) return fail(RWKV_E_ARG, "query %llu: unknown flag bits (0x%x) or reserved != 0", (unsigned long long)i, q[i].flags);
         if (q[i].pick.kind == RWKV_PICK_GREEDY) continue;
-        if (const int rc = check_nucleus(&q[i].pick.nucleus)) return rc;
+        if (const int rc = check_pick(q[i].pick)) return rc;
         if (!(q[i].flags & RWKV_PICKQ_SEED) && !(q[i].u >= 0.0 && q[i].u < 1.0)) return fail(RWKV_E_ARG, "query %llu: need 0 <= u < 1", (unsigned long long)i);
-        *nucleus = true;
+        if (pick_floor(q[i].pick)) ++*n_floor; else *nucleus = true;
+        const bool updating = (q[i].pick.nucleus.flags & RWKV_NUCLEUS_UPDATE) != 0;
+        if (q[i].pick.kind == RWKV_PICK_MIROSTAT) { *miro = true; (updating ? mu_upd : mu_rd).push_back(q[i].slot); }
         if (!pick_penalty(q[i].pick)) continue;
         *penalty = true;
-        ((q[i].pick.nucleus.flags & RWKV_NUCLEUS_UPDATE) ? upd : rd).push_back(q[i].slot);
+        (updating ? upd : rd).push_back(q[i].slot);
     }
-    std::sort(upd.begin(), upd.end());
-    for (size_t i = 1; i < upd.size(); i++)
-        if (upd[i] == upd[i - 1]) return fail(RWKV_E_ARG, "slot %u is updated twice: the slots that one call updates are pairwise distinct", upd[i]);
-    for (const uint32_t s : rd)
-        if (std::binary_search(upd.begin(), upd.end(), s)) return fail(RWKV_E_ARG, "slot %u is updated by one query and read by another", s);
+    // one updater of a slot's vector (of its mu), and no reader beside it
+    for (auto *l : {&upd, &mu_upd}) {
+        std::sort(l->begin(), l->end());
+        for (size_t i = 1; i < l->size(); i++)
+            if ((*l)[i] == (*l)[i - 1]) return fail(RWKV_E_ARG, "slot %u is updated twice: the slots that one call updates are pairwise distinct", (*l)[i]);
+        for (const uint32_t s : l == &upd ? rd : mu_rd)
+            if (std::binary_search(l->begin(), l->end(), s)) return fail(RWKV_E_ARG, "slot %u is updated by one query and read by another", s);
+    }
     return 0;
 }
 } // namespace
@@ -3186,19 +3313,27 @@ int check_pick_queries(const rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, 
 int rwkv_sample_rows(rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, uint64_t *tokens)
 {
     if (const int rc = guard(c, NEED_HEAD | LAUNCHES, q && tokens)) return rc;
-    bool penalty = false, nucleus = false;
-    if (const int rc = check_pick_queries(c, q, n, &penalty, &nucleus)) return rc;
+    bool penalty = false, nucleus = false, miro = false;
+    uint64_t n_floor = 0;
+    if (const int rc = check_pick_queries(c, q, n, &penalty, &nucleus, &miro, &n_floor)) return rc;
     const int rc = finish(c, [&]() -> int {
         if (const int rc = penalty ? counts_alloc(c) : 0) return rc;
+        if (const int rc = miro ? mu_alloc(c) : 0) return rc;
         if (!c->h_pickq) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_pickq), sizeof(PickIo), hipHostMallocDefault));
         if (const int rc = grow_buffer(c, PICKQ_IO, sizeof(PickIo))) return rc;
         if (const int rc = grow_pickq_scratch(c, std::min<uint64_t>(n, PQ_BATCH), nucleus)) return rc;
         // (the pinned block is free: every call that used it has returned behind its wait)
         PickIo *h = c->h_pickq, *d = c->buf<PickIo>(PICKQ_IO);
-        for (uint64_t i = 0; i < n; i++)
-            h->q[i] = make_pickq(q[i].pick, false, q[i].row, q[i].slot, (unsigned)i, (q[i].flags & RWKV_PICKQ_SEED) != 0, q[i].seed, q[i].step, q[i].u);
+        // the table in two parts, greedy and nucleus queries in front of the floor queries: each part has its kernels; out[q.out] keeps the caller's order
+        uint64_t at[2] = {0, n - n_floor};
+        for (uint64_t i = 0; i < n; i++) {
+            const bool fl = pick_floor(q[i].pick), seeded = (q[i].flags & RWKV_PICKQ_SEED) != 0;
+            if (fl) { const FloorQ f = make_floorq(q[i].pick, q[i].row, q[i].slot, (unsigned)i, seeded, q[i].seed, q[i].step, q[i].u); memcpy(&h->q[at[1]++], &f, sizeof f); }
+            else h->q[at[0]++] = make_pickq(q[i].pick, false, q[i].row, q[i].slot, (unsigned)i, seeded, q[i].seed, q[i].step, q[i].u);
+        }
         HIPCHK(hipMemcpyAsync(d->q, h->q, sizeof(PickQ) * n, hipMemcpyHostToDevice, c->stream));
-        if (const int rc = enqueue_pickq(c, d->q, (unsigned)n, d->out)) return rc;
+        if (const int rc = n > n_floor ? enqueue_pickq(c, d->q, (unsigned)(n - n_floor), d->out) : 0) return rc;
+        if (const int rc = n_floor ? enqueue_floorq(c, reinterpret_cast<const FloorQ *>(d->q + (n - n_floor)), (unsigned)n_floor, d->out) : 0) return rc;
         HIPCHK(hipMemcpyAsync(h->out, d->out, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
         return 0;
     }());

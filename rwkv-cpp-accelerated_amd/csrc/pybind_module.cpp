@@ -90,6 +90,18 @@ PYBIND11_MODULE(rwkv, m)
        "context's decaying occurrence counts, which the pick updates (engine extension)",
           py::arg("rwkvp"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u, py::arg("presence") = 0.f,
           py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("ban0") = false);
+    m.def("minpSample", [](std::uintptr_t h, float temp, float min_p, float presence, float frequency, float decay, bool ban0) {
+        const double u = std::generate_canonical<double, 53>(rwkv_sampler_rng());
+        return M(h)->sampleFloor(RWKV::Pick::minp(min_p, RWKV::Nucleus{temp, 1.0f, 0u, presence, frequency, decay}), u < 1.0 ? u : 0.0, ban0, true);
+    }, "one min-p draw on the device from the last logits row, counting the pick (engine extension)", py::arg("rwkvp"), py::arg("temp") = 1.0f,
+       py::arg("min_p") = 0.05f, py::arg("presence") = 0.0f, py::arg("frequency") = 0.0f, py::arg("decay") = 1.0f, py::arg("ban0") = true);
+    m.def("mirostatSample", [](std::uintptr_t h, float temp, float tau, float eta, float presence, float frequency, float decay, bool ban0) {
+        const double u = std::generate_canonical<double, 53>(rwkv_sampler_rng());
+        return M(h)->sampleFloor(RWKV::Pick::mirostat(tau, eta, RWKV::Nucleus{temp, 1.0f, 0u, presence, frequency, decay}), u < 1.0 ? u : 0.0, ban0, true);
+    }, "one Mirostat v2 draw on the device from the last logits row; slot 0's mu and counts move (engine extension)", py::arg("rwkvp"), py::arg("temp") = 1.0f,
+       py::arg("tau") = 5.0f, py::arg("eta") = 0.1f, py::arg("presence") = 0.0f, py::arg("frequency") = 0.0f, py::arg("decay") = 1.0f, py::arg("ban0") = true);
+    m.def("setMirostat", [](std::uintptr_t h, int64_t slot0, const std::vector<double> &mu) { M(h)->setMirostat(slot0, mu); }, py::arg("rwkvp"), py::arg("slot0"), py::arg("mu"));
+    m.def("getMirostat", [](std::uintptr_t h, int64_t slot0, int64_t n) { return M(h)->getMirostat(slot0, n); }, py::arg("rwkvp"), py::arg("slot0"), py::arg("n"));
     m.def("decodeNucleus", [](std::uintptr_t h, int64_t first, int64_t n, float temp, float top_p, unsigned top_k, float presence, float frequency,
                               float decay, uint64_t seed, bool keep) {
         return M(h)->decodeNucleus(first, n, RWKV::Nucleus{temp, top_p, top_k, presence, frequency, decay}, seed, keep);

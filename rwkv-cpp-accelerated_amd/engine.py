@@ -20,7 +20,8 @@ MODE_PARRALEL, MODE_GPT = 0, 1   # reference enums/enum.h:2-5
 SAMPLE_BAN0, SAMPLE_RECIPE = 1, 2   # include/rwkv_mi355x.h
 NUCLEUS_BAN0, NUCLEUS_KEEP, NUCLEUS_UPDATE = 1, 2, 4
 STOP_MAX_SEQS, STOP_MAX_LEN, STOP_POLL, STOP_KEEP = 16, 8, 8, 1
-PICK_GREEDY, PICK_TYPICAL, PICK_NUCLEUS = 0, 1, 2
+PICK_GREEDY, PICK_TYPICAL, PICK_NUCLEUS, PICK_MINP, PICK_MIROSTAT = 0, 1, 2, 3, 4
+PICK_KINDS = {"greedy": PICK_GREEDY, "typical": PICK_TYPICAL, "nucleus": PICK_NUCLEUS, "minp": PICK_MINP, "mirostat": PICK_MIROSTAT}
 N_KCLASS = 7
 ABI_VERSION = 6                   # RWKV_MI355X_ABI_VERSION of include/rwkv_mi355x.h
 KCLASS_NAMES = ["first", "att_kvr_wkv", "att_out", "ffn_rk", "ffn_v", "head", "argmax"]
@@ -46,6 +47,7 @@ ABI_SYMBOLS = [
     "rwkv_spec_verify_segments",
     "rwkv_sample_rows", "rwkv_spec_sample_segments",
     "rwkv_tree_plan", "rwkv_spec_verify_trees", "rwkv_spec_sample_trees",
+    "rwkv_sample_floor", "rwkv_mirostat_set", "rwkv_mirostat_get",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
@@ -79,10 +81,19 @@ class PickQuery(C.Structure):
                 ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
-def pick_of(kind="nucleus", ban0=False, update=False, **nucleus) -> Pick:
-    """the rwkv_pick of kind "greedy" or "nucleus" (nucleus: the keywords of nucleus_params)"""
+def floor_pick(kind, temp=1.0, min_p=0.05, tau=5.0, eta=0.1, presence=0.0, frequency=0.0, decay=1.0, flags=0) -> Pick:
+    """the rwkv_pick of kind "minp" (min_p) or "mirostat" (tau, eta): the floor rides in the two outer floats, temperature, penalties and flags in
+    `nucleus` with its cuts off (top_p 1, top_k 0)"""
+    outer = (1.0, float(min_p)) if kind == "minp" else (float(eta), float(tau))
+    return Pick({"minp": PICK_MINP, "mirostat": PICK_MIROSTAT}[kind], outer[0], outer[1], 0, nucleus_params(temp, 1.0, 0, presence, frequency, decay, flags))
+
+
+def pick_of(kind="nucleus", ban0=False, update=False, **params) -> Pick:
+    """the rwkv_pick of kind "greedy" or "nucleus" (the keywords of nucleus_params), "minp" or "mirostat" (the keywords of floor_pick)"""
     flags = (NUCLEUS_BAN0 if ban0 else 0) | (NUCLEUS_UPDATE if update else 0)
-    return Pick({"greedy": PICK_GREEDY, "nucleus": PICK_NUCLEUS}[kind], 1.0, 0.8, 0, nucleus_params(flags=flags, **nucleus))
+    if kind in ("minp", "mirostat"):
+        return floor_pick(kind, flags=flags, **params)
+    return Pick({"greedy": PICK_GREEDY, "nucleus": PICK_NUCLEUS}[kind], 1.0, 0.8, 0, nucleus_params(flags=flags, **params))
 
 
 def pick_query(row, slot=0, kind="nucleus", u=None, seed=0, step=0, **pick) -> PickQuery:
@@ -415,6 +426,9 @@ def lib():
     L.rwkv_decode_batch_nucleus.argtypes = [vp, C.POINTER(u64), u64, u64, npp, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_decode_batch_nucleus.restype = i32
     L.rwkv_penalty_set.argtypes = [vp, u64, vp]; L.rwkv_penalty_set.restype = i32
     L.rwkv_penalty_get.argtypes = [vp, u64, vp]; L.rwkv_penalty_get.restype = i32
+    L.rwkv_sample_floor.argtypes = [vp, u64, u64, C.POINTER(Pick), C.c_double, C.POINTER(u64)]; L.rwkv_sample_floor.restype = i32
+    L.rwkv_mirostat_set.argtypes = [vp, u64, u64, vp]; L.rwkv_mirostat_set.restype = i32
+    L.rwkv_mirostat_get.argtypes = [vp, u64, u64, vp]; L.rwkv_mirostat_get.restype = i32
     L.rwkv_decode_batch_until.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(StopParams), C.POINTER(u64),
                                           C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(u64)]
     L.rwkv_decode_batch_until.restype = i32
@@ -783,14 +797,16 @@ class RWKV:
 
     # -- stop sequences and per-stream budgets in the device loops (include/rwkv_mi355x.h rwkv_decode_batch_until) --------
     def decode_batch_until(self, first_tokens, n_steps: int, stops=(), max_new=None, keep: bool = False, pick: str = "greedy", seeds=None,
-                           temp: float = 1.0, tau: float = 0.8, recipe: bool = False, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
-                           frequency: float = 0.0, decay: float = 1.0, _logprobs=None, _constrain=None):
+                           temp: float = 1.0, tau: float | None = None, recipe: bool = False, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
+                           frequency: float = 0.0, decay: float = 1.0, min_p: float = 0.05, eta: float = 0.1, _logprobs=None, _constrain=None):
         """decode_batch_greedy / _typical / _nucleus (pick = "greedy", "typical", "nucleus", with that call's parameters) in which stream s ends
         at the first of the stop sequences `stops` (lists of token ids, each 1 .. 8 long) that its newest ids spell, or after max_new[s] tokens.
         keep: the match history (and the nucleus counts) continue from the previous call.  Returns (ids [N][n_steps], 0 behind a stream's end;
         len [N]; reason [N]: 0 ran all n_steps, 1 budget, 2 + j matched stops[j]; steps_run).  Slot s is left as it was when stream s stopped:
-        feed ids[s][len[s] - 1] to continue it."""
-        kind = {"greedy": PICK_GREEDY, "typical": PICK_TYPICAL, "nucleus": PICK_NUCLEUS}[pick]
+        feed ids[s][len[s] - 1] to continue it.  pick = "minp" (temp, min_p) or "mirostat" (temp, tau = target surprise, eta) are the floor cuts of
+        sample_floor, with the penalties of the nucleus pick; keep also continues Mirostat's mu."""
+        kind = PICK_KINDS[pick]
+        tau = (5.0 if kind == PICK_MIROSTAT else 0.8) if tau is None else tau      # (the defaults of floor_pick and of the typical calls)
         n = len(first_tokens)
         sd = list(range(n)) if seeds is None else [int(x) for x in seeds]
         if len(sd) != n:
@@ -800,6 +816,8 @@ class RWKV:
         arr = (C.c_uint64 * max(1, n))(*sd)
         pk = Pick(kind, float(temp), float(tau), SAMPLE_RECIPE if recipe else 0,
                   nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_KEEP if keep else 0))
+        if kind in (PICK_MINP, PICK_MIROSTAT):
+            pk = floor_pick(pick, temp, min_p, tau, eta, presence, frequency, decay, NUCLEUS_KEEP if keep else 0)
         sp, alive = stop_params(stops, max_new, keep)
         ln, rs, ran = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))(), C.c_uint64(0)
         sdp = None if kind == PICK_GREEDY else arr
@@ -860,12 +878,15 @@ class RWKV:
         _chk(lib().rwkv_constraint_state_set(self._h, int(slot0), a.size, a.ctypes.data_as(C.POINTER(C.c_uint32))))
 
     def pick_constrained(self, pick: str = "greedy", bias=None, u: float = 0.5, advance: bool = True, row: int = 0, slot: int = 0, temp: float = 1.0,
-                         top_p: float = 0.9, top_k: int = 0, presence: float = 0.0, frequency: float = 0.0, decay: float = 1.0, update: bool = False):
+                         top_p: float = 0.9, top_k: int = 0, presence: float = 0.0, frequency: float = 0.0, decay: float = 1.0, update: bool = False,
+                         min_p: float = 0.05, tau: float = 5.0, eta: float = 0.1):
         """ONE constrained draw from logits row `row` of the last forward under the automaton state of slot `slot` and the bias list `bias`
-        ({id: value}; -inf bans), greedy or nucleus with that call's parameters; advance: the slot's state moves along the pick.  Returns
+        ({id: value}; -inf bans), greedy, nucleus, minp or mirostat with that kind's parameters; advance: the slot's state moves along the pick.  Returns
         (token, the slot's automaton state on return).  Logits and state stay as they are."""
-        kind = {"greedy": PICK_GREEDY, "typical": PICK_TYPICAL, "nucleus": PICK_NUCLEUS}[pick]
+        kind = PICK_KINDS[pick]
         pk = Pick(kind, float(temp), 0.8, 0, nucleus_params(temp, top_p, top_k, presence, frequency, decay, NUCLEUS_UPDATE if update else 0))
+        if kind in (PICK_MINP, PICK_MIROSTAT):
+            pk = floor_pick(pick, temp, min_p, tau, eta, presence, frequency, decay, NUCLEUS_UPDATE if update else 0)
         b, alive = None, None
         if bias is not None:
             alive = _bias_arrays(bias)
@@ -1167,6 +1188,25 @@ class RWKV:
         _chk(lib().rwkv_debug_stop_scan(self._h, a.ctypes.data_as(C.POINTER(C.c_uint64)), ft, n, steps, C.byref(sp), ln, rs))
         del alive
         return np.frombuffer(ln, dtype=np.uint32)[:n].astype(np.int64), np.frombuffer(rs, dtype=np.uint32)[:n].astype(np.int64)
+
+    # -- min-p and Mirostat v2 (include/rwkv_mi355x.h rwkv_sample_floor) --------
+    def sample_floor(self, kind: str = "minp", u: float = 0.5, row: int = 0, slot: int = 0, ban0: bool = False, update: bool = False, **params) -> int:
+        """ONE min-p ("minp": temp, min_p) or Mirostat v2 ("mirostat": temp, tau, eta) draw ON THE DEVICE from logits row `row` of the last forward
+        with the counts (presence, frequency, decay) and, Mirostat, the mu of state slot `slot`; update: counts and mu move behind the pick"""
+        tok = C.c_uint64(0)
+        pk = pick_of(kind, ban0, update, **params)
+        _chk(lib().rwkv_sample_floor(self._h, int(row), int(slot), C.byref(pk), float(u), C.byref(tok)))
+        return int(tok.value)
+
+    def mirostat_set(self, mu, slot0: int = 0):
+        """Mirostat's running threshold of slots slot0 .. slot0 + len(mu) - 1"""
+        a = np.ascontiguousarray(mu, dtype=np.float64).reshape(-1)
+        _chk(lib().rwkv_mirostat_set(self._h, int(slot0), a.size, _ptr(a)))
+
+    def mirostat_get(self, slot0: int = 0, n: int = 1) -> np.ndarray:
+        out = np.zeros(max(1, int(n)), dtype=np.float64)
+        _chk(lib().rwkv_mirostat_get(self._h, int(slot0), int(n), _ptr(out)))
+        return out[: int(n)]
 
     def penalty_set(self, slot: int, counts=None):
         """upload the occurrence counts of state slot `slot` (float32 [50277]; None: zero them)"""
