@@ -485,6 +485,27 @@ public:
         for (size_t i = 0; i < segs.size(); i++) out.push_back(SpecSegStep{a[i], nx[i], row[i]});
         return out;
     }
+    // lookup decoding as one device loop (rwkv_mi355x.h "lookup decoding as ONE device loop"): stream s runs on slot s from histories[s], of which
+    // all but the last id have been fed; every round the device drafts up to k ids per stream behind the most recent earlier occurrence of its last
+    // n ids, verifies all streams in one pass, commits what stands and appends it.  n ids per stream and, per stream, its rounds, drafted and
+    // accepted ids (SpecResult).  The state lives on the device, as for specVerifySegments.
+    std::vector<SpecResult> decodeLookupStreams(const std::vector<std::vector<unsigned long long>> &histories, unsigned long long n, unsigned k = 8,
+                                                unsigned ngram = 3)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> ids, len;
+        for (const auto &h : histories) { ids.insert(ids.end(), h.begin(), h.end()); len.push_back(h.size()); }
+        const size_t N = histories.size();
+        std::vector<uint64_t> out(N * n + 1);
+        std::vector<rwkv_spec_stats> st(N + 1);
+        const rwkv_lookup_params p{k, ngram, 0u, 0u};
+        ids.push_back(0); len.push_back(0);      // (never read: non-NULL pointers for an empty list, which the call then refuses by its own rule)
+        rwkv_detail::check(rwkv_decode_lookup_streams(ctx_, ids.data(), len.data(), N, n, &p, out.data(), st.data()));
+        std::vector<SpecResult> res;
+        for (size_t s = 0; s < N; s++)
+            res.push_back(SpecResult{std::vector<unsigned long long>(out.begin() + s * n, out.begin() + (s + 1) * n), st[s].rounds, st[s].drafted, st[s].accepted});
+        return res;
+    }
     // draft TREES for many streams (rwkv_mi355x.h "draft TREES for many streams"): specVerifySegments where the last n_draft ids of a segment are a
     // tree -- parent[r], one entry per id of the segment, counted from its first id and read for the guesses, names the last certain id or an earlier
     // guess.  Of the guesses the one path the greedy picks confirm is kept; `ids` are its ids in order.

@@ -774,6 +774,52 @@ int rwkv_spec_sample_trees(rwkv_ctx *ctx, const uint64_t *tokens /* [T] */, cons
                            uint32_t flags /* must be 0 */, uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,
                            uint64_t *row /* [n_segs], may be NULL */, uint64_t *emitted /* [n_segs][RWKV_SPEC_MAX_DRAFT], may be NULL */);
 
+/* ---- lookup decoding as ONE device loop: drafter, verify, accept, commit and append without the host (no reference counterpart) ----
+ * Prompt-lookup speculative greedy decoding for n_streams streams in one call, the loop every other generation mode already has on the device.
+ * `history` holds the streams' ids back to back, hist_len[s] of them for stream s, which runs on state slot s.  On entry slot s holds the state
+ * behind all but the LAST id of history s; that id is fed first.  On return out_tokens[s][0 .. n_tokens - 1] are the stream's next ids and slot s
+ * has consumed the last id of its history and out_tokens[s][0 .. n_tokens - 2], so calls chain.  No stream ever emits or consumes more than
+ * n_tokens.
+ * A round, per live stream, with kd = min(k, remaining - 1):
+ *     1. DRAFT: the up to kd ids that followed the MOST RECENT earlier occurrence of the history's last n ids.  The occurrence starts at
+ *        s <= len - n - 1 (something follows it), may overlap the tail, and the draft is cut where the history ends; it is empty when len <= n or
+ *        nothing matches;
+ *     2. VERIFY the drafts of all streams in one checkpointing segmented pass and pick every row greedily (rwkv_spec_verify_segments' pass and pick);
+ *     3. ACCEPT the longest prefix the picks confirm and COMMIT the slot from the row that stands (its kernels);
+ *     4. APPEND the a accepted ids and the next pick to the stream's history and output, lower its budget; a stream that has its ids RETIRES.
+ * The launch shape is fixed for the call: n_streams segments of 1 + k rows (the id to feed, the draft, padding).  A retired stream's rows still run
+ * through the pass; its slot, history, output and counters do not move -- its slot is left bit for bit as it stood when the stream retired.
+ * Traffic: ONE upload (the histories as 32-bit ids, the constant row plan), per round five launches besides the pass's own and nothing uploaded or
+ * downloaded -- the round kernel writes the pass's ids and segment table where the pass reads them and reads the accept's records where they are --
+ * and ONE download (ids and counters) at the end.  Run-ahead is bounded: the first ceil(n_tokens / (k + 1)) rounds, which every call needs, are
+ * enqueued blind; behind them the count of live streams travels to a pinned word after every round kernel and the round's pass is enqueued only
+ * when that word arrived non-zero, so no pass runs behind the last retirement (blocks of rounds with a lag, as in rwkv_decode_batch_until, ran up
+ * to eight 3 ms passes for nobody: profiles/lookup_loop).  At most n_tokens rounds are enqueued, and a round kernel launched for retired streams
+ * changes no state, history or output.
+ * EXACT: ids, stats and the slots' xy / aa / bb / dd are bit for bit those of the host loop over rwkv_spec_verify_segments that drafts by the same
+ * rule with the same kd (one segment {s, 1 + n_draft, n_draft} per live stream and round): a segment's result does not depend on the rows behind
+ * its draft or on the other segments.  The ids are those of repeated rwkv_spec_verify_segments({s, 1, 0}); the draft decides the rounds alone.
+ * THE VERIFIER IS THE CHUNK PATH (see rwkv_spec_verify).  Slots >= n_streams, pp, penalty counts, stop histories and constraint states are
+ * untouched; the logits rows are left as the last round wrote them.
+ * stats (may be NULL), per stream: rounds it took part in, ids drafted (the true draft lengths), ids accepted.
+ * Status: RWKV_E_ARG for a NULL ctx, history, hist_len, params or out_tokens, n_streams == 0, k outside 1..RWKV_SPEC_MAX_DRAFT, n outside
+ * 1..RWKV_LOOKUP_MAX_NGRAM, n_streams (k + 1) above ONE pass as the context runs it (min(max_ctx, 64) rows, 32 under RWKV_SEQ_ROWS=32), a
+ * hist_len outside 1..RWKV_LOOKUP_MAX_HISTORY, n_tokens outside 1..RWKV_MAX_DECODE_STEPS, any id >= 50277, flags or reserved != 0; RWKV_E_STATE
+ * when not loaded, on a pipeline-stage context, or without the chunk path.  Every check runs before anything is launched or allocated: a rejected
+ * call leaves state, logits and buffers as they were.  The buffers (the histories with room for n_tokens more ids each, the checkpoints of
+ * rwkv_spec_verify_segments) are counted by rwkv_resident_bytes and freed by rwkv_free.
+ * rwkv_debug_lookup_draft runs the drafter ALONE with kd = k on uploaded histories and downloads what it drafted: draft[s][0 .. n_draft[s] - 1]
+ * (the rest of the row is 0).  It makes no pass and touches no state or logits; any created context will do; n_streams <= 64, the other limits as above.
+ * Out of scope: sampled acceptance in the loop, draft trees, a draft model, stop sequences, admission of new streams mid-call. */
+#define RWKV_LOOKUP_MAX_NGRAM 8u
+#define RWKV_LOOKUP_MAX_HISTORY (1u << 20)
+typedef struct rwkv_lookup_params { uint32_t k, n, flags, reserved; } rwkv_lookup_params;   /* draft ids per round, tail length; flags and reserved must be 0 */
+int rwkv_decode_lookup_streams(rwkv_ctx *ctx, const uint64_t *history /* the streams' ids back to back */, const uint64_t *hist_len /* [n_streams] */,
+                               uint64_t n_streams, uint64_t n_tokens, const rwkv_lookup_params *params, uint64_t *out_tokens /* [n_streams][n_tokens] */,
+                               rwkv_spec_stats *stats /* [n_streams], may be NULL */);
+int rwkv_debug_lookup_draft(rwkv_ctx *ctx, const uint64_t *history, const uint64_t *hist_len /* [n_streams] */, uint64_t n_streams, uint32_t k, uint32_t n,
+                            uint64_t *draft /* [n_streams][k] */, uint32_t *n_draft /* [n_streams] */);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

@@ -20,6 +20,7 @@
 #include "spectree.hip.h"
 #include "pickrows.hip.h"
 #include "floor.hip.h"
+#include "lookup.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -259,6 +260,8 @@ enum GrownBuf {
     SPECTREE_IO,                      // rwkv_spec_verify_trees / rwkv_spec_sample_trees (spectree.hip.h), SpecTreeIo: query table | ids | plan | segment table | from table,
                                       // behind them the records, the accepted ids and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT
     MIRO_MU,                          // f64 [max_ctx]: Mirostat's running threshold per state slot (floor.hip.h); allocated ONCE, zeroed, at the first call that needs it
+    LOOKUP_RUN,                       // rwkv_decode_lookup_streams / rwkv_debug_lookup_draft (lookup.hip.h), LookupLayout: ids | picks | records | plan | segment table | live |
+                                      // histories u32 | streams | output u32; everything in front of the output goes up in ONE copy, streams and output come down in one
     N_GROWN
 };
 
@@ -365,7 +368,7 @@ struct rwkv_ctx {
     int tile_th = 0, tile_s = 0, tile_tpc = 0;     // rows per tile, KiB per ring unit, tiles per row class and workgroup (0: no tile form at this width)
     struct Grown { void *p = nullptr; size_t bytes = 0; } grown[N_GROWN];      // (enum GrownBuf)
     template <class T> T *buf(GrownBuf which) const { return static_cast<T *>(grown[which].p); }
-    std::vector<unsigned long long> bd_host, sc_host, lp_host, beam_host;   // staging of a call's one upload and one download
+    std::vector<unsigned long long> bd_host, sc_host, lp_host, beam_host, lk_host;   // staging of a call's one upload and one download
     static constexpr int STOP_RING = 4;           // rwkv_decode_batch_until: block b's count of active streams lands in word b % 4, read when block b + 2 is due
     unsigned long long *stop_ring = nullptr;      // pinned
     hipEvent_t stop_ev[STOP_RING] = {};
@@ -2065,16 +2068,21 @@ int check_stop(const rwkv_stop_params *sp, uint64_t N, uint64_t n_steps, StopTab
 // max_new [N].  Where len starts (reason and max_new follow it at N and 2 N) and the record's size
 constexpr size_t stop_run_len(uint64_t N) { return 2 + 2 * N; }
 constexpr size_t stop_run_words(uint64_t N) { return stop_run_len(N) + 3 * N; }
+// the pinned poll ring of a bounded run-ahead and its events (Stopper::after_step, rwkv_decode_lookup_streams): allocated ONCE
+int poll_ring_setup(rwkv_ctx *c)
+{
+    if (c->stop_ring) return 0;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->stop_ring), sizeof(unsigned long long) * rwkv_ctx::STOP_RING, hipHostMallocDefault));
+    for (auto &e : c->stop_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    return 0;
+}
 // the buffers and the upload of one call's stopping (sp == nullptr: no sequence, no budget, no flag -- only its automaton ends a stream): the run
 // record (STOP_RUN), the histories (once), and -- `park`: a generation call, not the planted scan -- the park buffer, the poll ring and, with
 // `penalty`, the count vectors that are parked with the state
 int stopper_setup(rwkv_ctx *c, Stopper &st, const StopTable &t, const rwkv_stop_params *sp, const uint64_t *first, uint64_t N, uint64_t n_steps,
                   bool park, bool penalty)
 {
-    if (park && !c->stop_ring) {
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->stop_ring), sizeof(unsigned long long) * rwkv_ctx::STOP_RING, hipHostMallocDefault));
-        for (auto &e : c->stop_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    if (const int rc = park ? poll_ring_setup(c) : 0) return rc;
     if (!c->grown[STOP_HISTORY].p) {
         if (const int rc = grow_buffer(c, STOP_HISTORY, sizeof(unsigned) * c->maxT * STOP_HIST)) return rc;
         HIPCHK(hipMemsetAsync(c->grown[STOP_HISTORY].p, 0xFF, sizeof(unsigned) * c->maxT * STOP_HIST, c->stream));      // STOP_NONE everywhere
@@ -3621,6 +3629,180 @@ int rwkv_spec_sample_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *p
     if (flags) return fail(RWKV_E_ARG, "flags must be 0");
     const SpecSampleCall sm{picks, seeds, step0};
     return run_verify_trees(c, tokens, parent, segs, n_segs, &sm, n_accepted, next_token, row, emitted);
+}
+
+// ---- lookup decoding as one device loop (lookup.hip.h): rwkv_decode_lookup_streams, rwkv_debug_lookup_draft ----
+static_assert(sizeof(rwkv_lookup_params) == 16 && LK_MAX_N == RWKV_LOOKUP_MAX_NGRAM, "the params of the C ABI; lookup.hip.h holds the header's limit");
+namespace {
+// LOOKUP_RUN in bytes for N streams, T rows, `hist` history words (the streams' capacities, each a multiple of 4) and `out` output words.  [0, out)
+// is the call's ONE upload, [st, bytes) its one download
+struct LookupLayout {
+    size_t ids, picks, rec, plan, tab, live, hist, st, out, bytes;
+    LookupLayout(uint64_t N, uint64_t T, uint64_t hist_words, uint64_t out_words)
+    {
+        const size_t rows = std::max<size_t>(T, SEQ_TM);
+        ids = 0; picks = ids + 8 * rows; rec = picks + 8 * rows; plan = rec + sizeof(SpecSegRec) * N; tab = plan + sizeof(SegRow) * rows;
+        live = tab + sizeof(SpecSegEntry) * N; hist = (live + 8 + 15) / 16 * 16; st = hist + 4 * hist_words; out = st + sizeof(LookupStream) * N;
+        bytes = out + 4 * ((out_words + 3) / 4 * 4);
+    }
+};
+// one call's streams behind their checks: where each history sits and how much it may grow (`grow` ids), the device image, the kernels' arguments
+struct LookupRun {
+    LookupLayout lay{1, 1, 0, 0};
+    LookupArgs a{};
+    SpecSegAcceptArgs acc{};
+    const SegRow *plan = nullptr;
+    uint64_t N = 0, T = 0;
+    // the rules the two entry points share, all of them before anything is launched or allocated
+    static int check(const uint64_t *history, const uint64_t *hist_len, uint64_t N, uint64_t max_streams, uint32_t k, uint32_t n)
+    {
+        if (N == 0 || N > max_streams) return fail(RWKV_E_ARG, "n_streams must be in 1..%llu", (unsigned long long)max_streams);
+        if (k == 0 || k > RWKV_SPEC_MAX_DRAFT) return fail(RWKV_E_ARG, "k = %u is not in 1..%u", k, RWKV_SPEC_MAX_DRAFT);
+        if (n == 0 || n > RWKV_LOOKUP_MAX_NGRAM) return fail(RWKV_E_ARG, "n = %u is not in 1..%u", n, RWKV_LOOKUP_MAX_NGRAM);
+        uint64_t total = 0;
+        for (uint64_t s = 0; s < N; total += hist_len[s++])
+            if (hist_len[s] == 0 || hist_len[s] > RWKV_LOOKUP_MAX_HISTORY)
+                return fail(RWKV_E_ARG, "hist_len[%llu] = %llu is not in 1..%u (a history holds at least the id to feed first)", (unsigned long long)s,
+                            (unsigned long long)hist_len[s], RWKV_LOOKUP_MAX_HISTORY);
+        return check_ids(history, total, "token");
+    }
+    // buffers, the host image and its ONE upload: rows of valid ids, the constant row plan (stream s on slot s, 1 + k rows), a table of retired
+    // entries (the first round applies nothing), the histories as u32 and the streams
+    int setup(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t grow, uint32_t k, uint32_t n)
+    {
+        N = n_streams; T = N * (k + 1u);
+        std::vector<uint64_t> off(N + 1, 0);
+        for (uint64_t s = 0; s < N; s++) off[s + 1] = off[s] + (hist_len[s] + grow + 3) / 4 * 4;
+        lay = LookupLayout(N, T, off[N], N * grow);
+        if (const int rc = grow_buffer(c, LOOKUP_RUN, lay.bytes)) return rc;
+        c->lk_host.assign((lay.bytes + 7) / 8, 0ull);
+        unsigned char *hb = reinterpret_cast<unsigned char *>(c->lk_host.data()), *db = c->buf<unsigned char>(LOOKUP_RUN);
+        SegRow *hp = reinterpret_cast<SegRow *>(hb + lay.plan);
+        for (uint64_t j = 0; j < std::max<uint64_t>(T, SEQ_TM); j++) hp[j] = j < T ? SegRow{(unsigned)(j / (k + 1u)), j % (k + 1u) == 0 ? SEG_FIRST : 0u} : SegRow{0u, SEG_FIRST};
+        *reinterpret_cast<unsigned long long *>(hb + lay.live) = N;
+        unsigned *hh = reinterpret_cast<unsigned *>(hb + lay.hist);
+        LookupStream *hs = reinterpret_cast<LookupStream *>(hb + lay.st);
+        for (uint64_t s = 0, j = 0; s < N; s++) {
+            for (uint64_t i = 0; i < hist_len[s]; i++, j++) hh[off[s] + i] = (unsigned)history[j];
+            hs[s] = LookupStream{off[s], (unsigned)(off[s + 1] - off[s]), (unsigned)hist_len[s], (unsigned)grow, 0u, 0u, 0u};
+        }
+        HIPCHK(hipMemcpyAsync(db, hb, lay.out, hipMemcpyHostToDevice, c->stream));
+        a.hist = reinterpret_cast<unsigned *>(db + lay.hist); a.st = reinterpret_cast<LookupStream *>(db + lay.st);
+        a.out = reinterpret_cast<unsigned *>(db + lay.out); a.live = reinterpret_cast<unsigned long long *>(db + lay.live);
+        a.ids = reinterpret_cast<unsigned long long *>(db + lay.ids); a.tab = reinterpret_cast<SpecSegEntry *>(db + lay.tab);
+        a.rec = reinterpret_cast<const SpecSegRec *>(db + lay.rec);
+        a.n_tokens = (unsigned)grow; a.k = k; a.n = n;
+        acc = SpecSegAcceptArgs{a.ids, reinterpret_cast<const unsigned long long *>(db + lay.picks), a.tab, reinterpret_cast<SpecSegRec *>(db + lay.rec)};
+        plan = reinterpret_cast<const SegRow *>(db + lay.plan);
+        return 0;
+    }
+    // apply the records of the round in front (none: nothing), draft the next round's rows
+    int round(rwkv_ctx *c) const
+    {
+        k_lookup_round<LK_NT, LK_W><<<dim3((unsigned)N), dim3(LK_NT), 0, c->stream>>>(a);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    // the rows the round kernel wrote, verified: the checkpointing segmented pass, every row's greedy pick, what stands, the commit of exactly that.
+    // Launched directly, nothing uploaded; a retired stream's rows run through the pass and commit nothing
+    int verify(rwkv_ctx *c) const
+    {
+        double *ck = c->buf<double>(SPEC_CKPT);
+        const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, a.ids, RowLayout::spec_segments(plan, ck)};
+        if (const int rc = enqueue_chunk(c, pass)) return rc;
+        if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)T, const_cast<unsigned long long *>(acc.pick))) return rc;
+        k_lookup_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(acc);
+        const SpecSegCommitArgs ca{acc.rec, a.tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
+        const unsigned pairs = (unsigned)(c->L * c->D / 2);
+        k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)N), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
+    // All rounds of a call.  A round emits at most k + 1 ids per stream, so the first ceil(n_tokens / (k + 1)) rounds are needed whatever the
+    // drafts are worth and are enqueued blind.  From then on the live count travels into the pinned poll word behind every round kernel and the
+    // host enqueues the round's pass only once that word has arrived non-zero: no round runs behind the last retirement.  (Stopper::after_step's
+    // blocks of steps with a lag of two were measured here first: a pass is 3 ms, and up to eight of them ran for nobody -- profiles/lookup_loop.
+    // The wait costs the device the wake-up of the host, about 1 % of a pass, and the host enqueues a pass in less than half the time it runs.)
+    // The last launch applies the last round's records and drafts for nobody
+    int rounds(rwkv_ctx *c, uint64_t n_tokens) const
+    {
+        const uint64_t blind = (n_tokens + a.k) / (a.k + 1u);
+        for (uint64_t r = 0; r < n_tokens; r++) {
+            if (const int rc = round(c)) return rc;
+            if (r >= blind) {
+                HIPCHK(hipMemcpyAsync(&c->stop_ring[0], a.live, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+                HIPCHK(hipEventRecord(c->stop_ev[0], c->stream));
+                HIPCHK(hipEventSynchronize(c->stop_ev[0]));
+                if (c->stop_ring[0] == 0ull) return 0;      // every stream has its ids, and the launch above has applied the last of them
+            }
+            if (const int rc = verify(c)) return rc;
+        }
+        return round(c);
+    }
+    // the streams and (decode) the output rows come down in one copy
+    int download(rwkv_ctx *c, bool with_out)
+    {
+        unsigned char *hb = reinterpret_cast<unsigned char *>(c->lk_host.data());
+        HIPCHK(hipMemcpyAsync(hb + lay.st, c->buf<unsigned char>(LOOKUP_RUN) + lay.st, (with_out ? lay.bytes : lay.out) - lay.st, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }
+};
+} // namespace
+
+int rwkv_decode_lookup_streams(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t n_tokens,
+                               const rwkv_lookup_params *p, uint64_t *out_tokens, rwkv_spec_stats *stats)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, history && hist_len && p && out_tokens)) return rc;
+    if (p->flags || p->reserved) return fail(RWKV_E_ARG, "flags and reserved must be 0");
+    if (const int rc = check_steps(n_tokens, "n_tokens")) return rc;
+    const uint64_t pass_rows = std::min<uint64_t>(c->maxT, c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T);
+    if (const int rc = LookupRun::check(history, hist_len, n_streams, pass_rows, p->k, p->n)) return rc;
+    if (n_streams * (p->k + 1u) > pass_rows)
+        return fail(RWKV_E_ARG, "%llu streams of 1 + %u rows: a round is ONE pass of at most %llu rows", (unsigned long long)n_streams, p->k, (unsigned long long)pass_rows);
+    LookupRun run;
+    auto enqueue = [&]() -> int {
+        if (const int rc = poll_ring_setup(c)) return rc;
+        if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, n_streams * (p->k + 1u))) return rc;
+        if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * n_streams * (p->k + 1u) * c->D)) return rc;
+        if (const int rc = run.setup(c, history, hist_len, n_streams, n_tokens, p->k, p->n)) return rc;
+        if (const int rc = run.rounds(c, n_tokens)) return rc;
+        return run.download(c, true);
+    };
+    const int rc = finish(c, enqueue());
+    if (rc) return rc;
+    const unsigned char *hb = reinterpret_cast<const unsigned char *>(c->lk_host.data());
+    const LookupStream *hs = reinterpret_cast<const LookupStream *>(hb + run.lay.st);
+    const unsigned *ho = reinterpret_cast<const unsigned *>(hb + run.lay.out);
+    for (uint64_t i = 0; i < n_streams * n_tokens; i++) out_tokens[i] = ho[i];
+    for (uint64_t s = 0; stats && s < n_streams; s++) stats[s] = rwkv_spec_stats{hs[s].rounds, hs[s].drafted, hs[s].accepted};
+    return 0;
+}
+
+int rwkv_debug_lookup_draft(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint32_t k, uint32_t n,
+                            uint64_t *draft, uint32_t *n_draft)
+{
+    if (const int rc = guard(c, LAUNCHES, history && hist_len && draft && n_draft)) return rc;
+    if (const int rc = LookupRun::check(history, hist_len, n_streams, SEQ_TM, k, n)) return rc;
+    LookupRun run;
+    auto enqueue = [&]() -> int {
+        if (const int rc = run.setup(c, history, hist_len, n_streams, (uint64_t)k + 1u, k, n)) return rc;      // a budget of k + 1 ids: kd = k
+        if (const int rc = run.round(c)) return rc;
+        const LookupLayout &l = run.lay;
+        unsigned char *hb = reinterpret_cast<unsigned char *>(c->lk_host.data()), *db = c->buf<unsigned char>(LOOKUP_RUN);
+        HIPCHK(hipMemcpyAsync(hb + l.ids, db + l.ids, 8 * run.T, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(hb + l.tab, db + l.tab, sizeof(SpecSegEntry) * n_streams, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    const int rc = finish(c, enqueue());
+    if (rc) return rc;
+    const unsigned char *hb = reinterpret_cast<const unsigned char *>(c->lk_host.data());
+    const unsigned long long *ids = reinterpret_cast<const unsigned long long *>(hb + run.lay.ids);
+    const SpecSegEntry *tab = reinterpret_cast<const SpecSegEntry *>(hb + run.lay.tab);
+    for (uint64_t s = 0; s < n_streams; s++) {
+        n_draft[s] = tab[s].n_draft;
+        for (uint32_t j = 0; j < k; j++) draft[s * k + j] = j < tab[s].n_draft ? ids[s * (k + 1u) + 1u + j] : 0;
+    }
+    return 0;
 }
 
 void rwkv_free(rwkv_ctx *c)

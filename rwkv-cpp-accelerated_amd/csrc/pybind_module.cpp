@@ -174,6 +174,21 @@ PYBIND11_MODULE(rwkv, m)
         return out;
     }, "speculative greedy decoding for many streams: segments [(slot, ids, n_draft)] with pairwise distinct slots, the last n_draft ids of each are "
        "guesses; one pass verifies them all and returns [(n_accepted, next, row)] per segment (engine extension)", py::arg("rwkvp"), py::arg("segments"));
+    m.def("decodeLookupStreams", [](std::uintptr_t h, const std::vector<std::vector<int64_t>> &histories, int64_t n, unsigned k, unsigned ngram) {
+        if (n < 1) throw std::runtime_error("n must be at least 1");
+        std::vector<std::vector<unsigned long long>> hist;
+        for (const auto &q : histories) hist.emplace_back(q.begin(), q.end());
+        std::vector<std::vector<int64_t>> ids;
+        std::vector<std::tuple<int64_t, int64_t, int64_t>> stats;
+        for (const RWKV::SpecResult &r : M(h)->decodeLookupStreams(hist, (unsigned long long)n, k, ngram)) {
+            ids.emplace_back(r.tokens.begin(), r.tokens.end());
+            stats.emplace_back((int64_t)r.rounds, (int64_t)r.drafted, (int64_t)r.accepted);
+        }
+        return py::make_tuple(ids, stats);
+    }, "lookup decoding as one device loop: stream s on slot s continues histories[s] (all but its last id fed) by n ids; the device drafts up to k ids "
+       "behind the most recent earlier occurrence of the last `ngram` ids, verifies, commits and appends, round after round: "
+       "(ids [streams][n], [(rounds, drafted, accepted)]) (engine extension)",
+          py::arg("rwkvp"), py::arg("histories"), py::arg("n"), py::arg("k") = 8u, py::arg("ngram") = 3u);
     m.def("specVerifyTrees", [](std::uintptr_t h, const std::vector<std::tuple<unsigned, std::vector<int64_t>, unsigned, std::vector<unsigned>>> &trees) {
         std::vector<RWKV::SpecTree> segs;
         for (const auto &s : trees)

@@ -48,10 +48,12 @@ ABI_SYMBOLS = [
     "rwkv_sample_rows", "rwkv_spec_sample_segments",
     "rwkv_tree_plan", "rwkv_spec_verify_trees", "rwkv_spec_sample_trees",
     "rwkv_sample_floor", "rwkv_mirostat_set", "rwkv_mirostat_get",
+    "rwkv_decode_lookup_streams", "rwkv_debug_lookup_draft",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 SPEC_MAX_DRAFT = 31               # RWKV_SPEC_MAX_DRAFT
+LOOKUP_MAX_NGRAM, LOOKUP_MAX_HISTORY = 8, 1 << 20   # RWKV_LOOKUP_MAX_NGRAM, RWKV_LOOKUP_MAX_HISTORY
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 MAX_PICK_ROWS, PICKQ_SEED, PICK_BATCH = 1024, 1, 64   # RWKV_MAX_PICK_ROWS, RWKV_PICKQ_SEED; the queries of one launch sequence (csrc/engine.hip PQ_BATCH)
 TOPN_MAX = 32                     # RWKV_MAX_TOPN
@@ -146,6 +148,11 @@ def beam_params(width, stops=()):
 class SpecStats(C.Structure):
     """rwkv_spec_stats of include/rwkv_mi355x.h (24 bytes)"""
     _fields_ = [("rounds", C.c_uint64), ("drafted", C.c_uint64), ("accepted", C.c_uint64)]
+
+
+class LookupParams(C.Structure):
+    """rwkv_lookup_params of include/rwkv_mi355x.h (16 bytes)"""
+    _fields_ = [("k", C.c_uint32), ("n", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class Segment(C.Structure):
@@ -471,6 +478,10 @@ def lib():
     L.rwkv_spec_sample_trees.argtypes = [vp, C.POINTER(u64), u8p, C.POINTER(SpecSegment), u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(u64), C.c_uint32,
                                          C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]
     L.rwkv_spec_sample_trees.restype = i32
+    L.rwkv_decode_lookup_streams.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, u64, C.POINTER(LookupParams), C.POINTER(u64), C.POINTER(SpecStats)]
+    L.rwkv_decode_lookup_streams.restype = i32
+    L.rwkv_debug_lookup_draft.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(C.c_uint32)]
+    L.rwkv_debug_lookup_draft.restype = i32
     L.rwkv_segment_plan.argtypes = [C.POINTER(Segment), u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(u64)]; L.rwkv_segment_plan.restype = i32
     _lib = L
     return L
@@ -1094,6 +1105,40 @@ class RWKV:
         are those of repeated spec_verify_segments([(s, [token], 0)])."""
         rows = 32 if int(os.environ.get("RWKV_SEQ_ROWS", "64")) <= 32 else 64
         return lookup_streams(self.spec_verify_segments, histories, n_tokens, k, n, min(self.maxContext, rows))
+
+    # -- lookup decoding as one device loop (include/rwkv_mi355x.h rwkv_decode_lookup_streams) -------------------------------------
+    @staticmethod
+    def _histories(histories):
+        """(packed ids, lengths, count) of a list of id lists"""
+        hist = [[int(t) for t in h] for h in histories]
+        flat = [t for h in hist for t in h]
+        return (C.c_uint64 * max(1, len(flat)))(*flat), (C.c_uint64 * max(1, len(hist)))(*[len(h) for h in hist]), len(hist)
+
+    def decode_lookup_device(self, histories, n_tokens: int, k: int = 8, n: int = 3):
+        """decode_lookup_streams as ONE call: the device drafts (ngram_draft's rule), verifies, accepts, commits and appends, round after round,
+        and the host only enqueues.  Stream s runs on slot s.  Returns (ids [N][n_tokens], [dict(rounds, drafted, accepted)] per stream): what
+        decode_lookup_streams returns wherever its per-round `room` does not bind, i.e. N * (k + 1) rows fit one pass."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        ids, lens, N = self._histories(histories)
+        n_tokens = int(n_tokens)
+        out = (C.c_uint64 * max(1, N * n_tokens))()
+        st = (SpecStats * max(1, N))()
+        slots = min(self.maxContext, max(1, N))
+        if not self.resident:
+            self.push_state(slots)
+        _chk(lib().rwkv_decode_lookup_streams(self._h, ids, lens, N, n_tokens, C.byref(LookupParams(int(k), int(n), 0, 0)), out, st))
+        if not self.resident:
+            self.pull_state(slots)
+        got = np.frombuffer(out, dtype=np.uint64)[:N * n_tokens].astype(np.int64).reshape(N, n_tokens)
+        return got, [dict(rounds=int(s.rounds), drafted=int(s.drafted), accepted=int(s.accepted)) for s in st[:N]]
+
+    def debug_lookup_draft(self, histories, k: int, n: int = 3):
+        """the device drafter alone (rwkv_debug_lookup_draft): per history the list ngram_draft(history, k, n) gives.  No pass, no state."""
+        ids, lens, N = self._histories(histories)
+        draft, nd = (C.c_uint64 * max(1, N * int(k)))(), (C.c_uint32 * max(1, N))()
+        _chk(lib().rwkv_debug_lookup_draft(self._h, ids, lens, N, int(k), int(n), draft, nd))
+        return [[int(t) for t in draft[s * int(k):s * int(k) + nd[s]]] for s in range(N)]
 
     # -- draft trees for many streams (include/rwkv_mi355x.h rwkv_spec_verify_trees) ---------------------------------------------
     def spec_verify_trees(self, segments):
