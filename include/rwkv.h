@@ -659,11 +659,42 @@ public:
         r.until = until_call(first, n, pick, seeds, stop, nullptr, &cp);
         return r;
     }
+    // DRY and no-repeat-n-gram penalties in the device loops (rwkv_mi355x.h "DRY and no-repeat-n-gram penalties"): decodeBatchUntil -- under the
+    // installed automaton, if there is one, from the slots' current states -- in which the id that would extend a repeat of >= allowed_length ids
+    // of the stream's own tail loses multiplier * base^(repeat - allowed_length) on its logit; multiplier = INFINITY bans every
+    // (allowed_length + 1)-gram that the newest `window` ids hold; breakers: ids no repeat reaches across.  Step k appends the id it feeds to the
+    // history of slot s (setDryHistory plants a prompt's ids but the last; getDryHistory reads the ring, oldest first).
+    struct Dry { float multiplier = 0.8f, base = 1.75f; unsigned allowed_length = 2, window = RWKV_DRY_MAX_WINDOW; std::vector<unsigned> breakers; };
+    Until decodeBatchDry(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                         const std::vector<unsigned long long> &seeds, const Dry &dry)
+    {
+        return decodeBatchDry(first, n, pick, seeds, dry, Stop());
+    }
+    Until decodeBatchDry(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
+                         const std::vector<unsigned long long> &seeds, const Dry &dry, const Stop &stop)
+    {
+        const rwkv_dry_params dp{dry.multiplier, dry.base, dry.allowed_length, dry.window, (uint32_t)dry.breakers.size(), 0u,
+                                 dry.breakers.empty() ? nullptr : dry.breakers.data(), 0};
+        return until_call(first, n, pick, seeds, stop, nullptr, nullptr, &dp);
+    }
+    void setDryHistory(unsigned long long slot, const std::vector<unsigned long long> &ids)
+    {
+        const std::vector<uint64_t> h(ids.begin(), ids.end());
+        rwkv_detail::check(rwkv_dry_history_set(ctx_, slot, h.data(), h.size()));
+    }
+    std::vector<unsigned long long> getDryHistory(unsigned long long slot)
+    {
+        std::vector<uint64_t> h(RWKV_DRY_MAX_WINDOW);
+        uint64_t kept = 0, total = 0;
+        rwkv_detail::check(rwkv_dry_history_get(ctx_, slot, h.data(), &kept, &total));
+        return std::vector<unsigned long long>(h.begin(), h.begin() + kept);
+    }
 private:
     // decodeBatchUntil, with `lp` decodeBatchLogprobs and with `cp` decodeConstrained: one preparation of the C ABI's records, one push / pull of
     // host-authoritative state
     Until until_call(const std::vector<unsigned long long> &first, unsigned long long n, const Pick &pick,
-                     const std::vector<unsigned long long> &seeds, const Stop &stop, const rwkv_logprob_out *lp, const rwkv_constrain_params *cp = nullptr)
+                     const std::vector<unsigned long long> &seeds, const Stop &stop, const rwkv_logprob_out *lp, const rwkv_constrain_params *cp = nullptr,
+                     const rwkv_dry_params *dry = nullptr)
     {
         if (!ready) throw std::runtime_error("RWKV not loaded");
         if (pick.kind != RWKV_PICK_GREEDY && seeds.size() != first.size()) throw std::runtime_error("need one seed per stream");
@@ -680,7 +711,8 @@ private:
         uint64_t ran = 0;
         if (!residentState) pushState();      // host state is authoritative: continue from it ...
         const uint64_t *sdp = pick.kind == RWKV_PICK_GREEDY ? nullptr : sd.data();
-        rwkv_detail::check(cp ? rwkv_decode_batch_constrained(ctx_, ft.data(), ft.size(), n, &p, sdp, cp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
+        rwkv_detail::check(dry ? rwkv_decode_batch_dry(ctx_, ft.data(), ft.size(), n, &p, sdp, cp, dry, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
+                           : cp ? rwkv_decode_batch_constrained(ctx_, ft.data(), ft.size(), n, &p, sdp, cp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
                            : lp ? rwkv_decode_batch_logprobs(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, lp, ids.data(), len.data(), reason.data(), &ran)
                               : rwkv_decode_batch_until(ctx_, ft.data(), ft.size(), n, &p, sdp, &sp, ids.data(), len.data(), reason.data(), &ran));
         if (!residentState) pullState();      // ... and leave every slot where its stream stopped

@@ -820,6 +820,64 @@ int rwkv_decode_lookup_streams(rwkv_ctx *ctx, const uint64_t *history /* the str
 int rwkv_debug_lookup_draft(rwkv_ctx *ctx, const uint64_t *history, const uint64_t *hist_len /* [n_streams] */, uint64_t n_streams, uint32_t k, uint32_t n,
                             uint64_t *draft /* [n_streams][k] */, uint32_t *n_draft /* [n_streams] */);
 
+/* ---- DRY and no-repeat-n-gram penalties in the device decode loops (no reference counterpart: the reference only samples) ----
+ * The count penalties of rwkv_nucleus_params see single tokens.  DRY ("don't repeat yourself") sees SEQUENCES: it penalises the id that would
+ * extend a repeat of the stream's own tail, the longer the repeat the harder; with an infinite penalty it is a no-repeat-n-gram ban.  Both need a
+ * search over the stream's history at every step.  csrc/dry.hip.h makes it on the device, one workgroup per stream, one launch per step.
+ * History.  Per state slot the device keeps a ring of the newest RWKV_DRY_MAX_WINDOW ids and the total number of ids the slot was given.  It is
+ * allocated by the first call that needs it (16 KB + 8 bytes per slot of the context), counted by rwkv_resident_bytes, freed with the context and
+ * persistent across calls like the penalty counts.  It changes only through rwkv_dry_history_set and through a DRY loop: step k of stream s appends
+ * the id that step FEEDS -- first_tokens[s] at k = 0, then the pick of step k - 1 -- and nothing once the stream has stopped.  So after the call
+ * history s = history before + first_tokens[s] + out_tokens[s][0 .. out_len[s] - 2]: feed out_tokens[s][out_len[s] - 1] to continue the stream, as
+ * for its state.  A prompt's ids go in through rwkv_dry_history_set (all but the last one, which the loop feeds).
+ * Scan, per stream and step, after the append.  h[0 .. n - 1] = the newest min(total, window) ids of the slot, last = h[n - 1].  If n < 2 or `last`
+ * is a breaker nothing is penalised.  Otherwise every j in 0 .. n - 2 with h[j] == last has a match length m_j: the largest m such that for all
+ * 0 <= k < m: j - k >= 0, h[j - k] == h[n - 1 - k] and h[j - k] is no breaker; m_j is capped at RWKV_DRY_MAX_MATCH.  The match may overlap the
+ * tail.  Its follower is t = h[j + 1], and L_t = the maximum of m_j over all j with that follower.  t is penalised when L_t >= allowed_length.
+ * Penalty.  One table per call, built on the host in f64: p_0 = multiplier, p_(i+1) = p_i * base, pen[i] = (float)p_i (include/rwkv_sampler.h
+ * dry_table; a numpy restatement is bit exact).  multiplier is >= 0 and finite, or +inf: 0 means off, +inf bans every (allowed_length + 1)-gram
+ * that the window already holds.  base is >= 1 and finite.  On the CONSTRAINED row c of the stream (see constrained decoding, above: behind the
+ * automaton's mask and the bias list, in front of the pick) c_t <- c_t - pen[L_t - allowed_length], one f32 subtraction.  The model's logits are
+ * never written: the log-prob hook, the park buffer and a later call see the model's rows.  NaN or +inf logits, or a row left without a finite
+ * entry, behave as under a constraint: the pick is unspecified but below 50277, q stays, nothing faults.
+ * rwkv_decode_batch_dry is rwkv_decode_batch_constrained with the penalty: the same arguments, results, stops, budgets, record and invariant, and
+ * `dry` behind `constrain`.  constrain may be NULL: no automaton state to start from, no bias, no out_state.  A DRY call always runs under a
+ * constraint -- the installed automaton, or the implicit state that allows every id but 0 -- so it parks and unparks like a constrained call, and
+ * RWKV_PICK_TYPICAL is RWKV_E_ARG as there; the one-stream greedy loop uses the row pick.  Per step it adds ONE launch of one workgroup per stream
+ * between k_constrain_rows and the pick: no host synchronisation, no copy, nothing cleared in device memory, no scratch of vocabulary size.
+ * dry == NULL or multiplier == 0 runs exactly the launches of rwkv_decode_batch_constrained, and the histories stay as they are.  With the KEEP flags
+ * a 16-step call equals an 8-step call followed by an 8-step call fed the first call's last ids.
+ * rwkv_dry_history_set replaces the history of `slot` by ids[0 .. n) (each < 50277): the newest RWKV_DRY_MAX_WINDOW of them are kept, the total
+ * becomes n; n = 0 empties it (ids may then be NULL).  rwkv_dry_history_get returns the ids the ring holds, oldest first, their number and the total.
+ * rwkv_debug_dry_scan is the scan alone over the history of `slot` as it stands -- no append, no row, no forward: any loaded context will do -- and
+ * returns the penalised (id, L) pairs sorted by id, at most RWKV_DRY_MAX_WINDOW - 1 of them (tests).
+ * Status: RWKV_E_ARG for whatever the constrained call rejects, a multiplier that is negative or NaN, a base below 1 or not finite, allowed_length
+ * outside 1 .. RWKV_DRY_MAX_MATCH, window outside 1 .. RWKV_DRY_MAX_WINDOW, more than RWKV_DRY_MAX_BREAKERS breakers, a breaker or history id
+ * >= 50277, flags or reserved != 0.  Every check runs before anything is launched or allocated.
+ * Out of scope: DRY in rwkv_pick_constrained, rwkv_sample_rows, beam search and the speculative calls; breaker STRINGS of several tokens (a breaker
+ * is one id: pass the ids of newline, quote and the like); windows above RWKV_DRY_MAX_WINDOW. */
+#define RWKV_DRY_MAX_WINDOW 4096u
+#define RWKV_DRY_MAX_MATCH 64u
+#define RWKV_DRY_MAX_BREAKERS 32u
+typedef struct rwkv_dry_params {
+    float multiplier;         /* >= 0 and finite, or +inf; 0: off */
+    float base;               /* >= 1, finite */
+    uint32_t allowed_length;  /* 1 .. RWKV_DRY_MAX_MATCH: repeats shorter than this cost nothing */
+    uint32_t window;          /* 1 .. RWKV_DRY_MAX_WINDOW: the newest ids that are searched */
+    uint32_t n_breakers;      /* 0 .. RWKV_DRY_MAX_BREAKERS */
+    uint32_t flags;           /* must be 0 */
+    const uint32_t *breakers; /* host [n_breakers], ids < 50277; may be NULL when n_breakers == 0 */
+    uint64_t reserved;        /* must be 0 */
+} rwkv_dry_params;
+int rwkv_dry_history_set(rwkv_ctx *ctx, uint64_t slot, const uint64_t *ids, uint64_t n);
+int rwkv_dry_history_get(rwkv_ctx *ctx, uint64_t slot, uint64_t *ids /* host [RWKV_DRY_MAX_WINDOW] */, uint64_t *n, uint64_t *total);
+int rwkv_debug_dry_scan(rwkv_ctx *ctx, uint64_t slot, const rwkv_dry_params *dry, uint32_t *tok /* host [RWKV_DRY_MAX_WINDOW] */,
+                        uint32_t *len /* likewise */, uint32_t *n_out);
+int rwkv_decode_batch_dry(rwkv_ctx *ctx, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                          const uint64_t *seeds, const rwkv_constrain_params *constrain /* may be NULL */, const rwkv_dry_params *dry /* may be NULL */,
+                          const rwkv_stop_params *stop /* may be NULL */, const rwkv_logprob_out *lp /* may be NULL */, uint64_t *out_tokens,
+                          uint32_t *out_len, uint32_t *out_reason, uint64_t *steps_run);
+
 /* ---- layer pipeline (no reference counterpart: the reference is single-device) ----
  * A context may own a contiguous layer range [l0, l1) of the model: call rwkv_set_layer_range()
  * before loading.  The first stage (l0 == 0) also owns the embedding table + ln0, the last stage

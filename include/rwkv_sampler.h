@@ -384,6 +384,40 @@ inline constraint_automaton constraint_trie(const std::vector<std::vector<unsign
     return A;
 }
 
+// ---- DRY and no-repeat-n-gram penalties: the host twins of csrc/dry.hip.h (the semantics are those of include/rwkv_mi355x.h
+// rwkv_decode_batch_dry).  dry_table: the 64 penalties of a call, pen[i] = what a repeat of allowed_length + i ids costs -- p_0 = multiplier,
+// p_(i+1) = p_i * base in f64, each rounded once to f32; it is the table the engine uploads.
+inline std::vector<float> dry_table(float multiplier, float base)
+{
+    std::vector<float> pen(64);
+    double p = multiplier;
+    for (float &v : pen) { v = (float)p; p *= (double)base; }
+    return pen;
+}
+// the scan over ONE stream's history (oldest first; the newest `window` ids of it count, the last one being the id just fed): the (id, L) pairs
+// with L >= allowed, ascending by id -- id t follows a start j whose ids match the tail backwards over L_t ids (the longest such start wins;
+// no breaker inside, capped at 64, the match may overlap the tail).  c[id] -= dry_table(..)[L - allowed] is the penalty.
+struct dry_hit { unsigned id, len; };
+inline std::vector<dry_hit> dry_scan(const std::vector<unsigned long long> &history, unsigned allowed, unsigned window,
+                                     const std::vector<unsigned> &breakers = {})
+{
+    const size_t n = std::min<size_t>(history.size(), window);
+    const unsigned long long *h = history.data() + (history.size() - n);
+    const auto brk = [&](unsigned long long t) { return std::find(breakers.begin(), breakers.end(), (unsigned)t) != breakers.end(); };
+    std::vector<dry_hit> out;
+    if (n < 2 || brk(h[n - 1])) return out;
+    std::vector<unsigned> best(50277, 0u);
+    for (size_t j = 0; j + 1 < n; j++) {
+        if (h[j] != h[n - 1] || h[j + 1] >= 50277ull) continue;
+        unsigned m = 0;
+        while (m < 64u && m <= j && h[j - m] == h[n - 1 - m] && !brk(h[j - m])) m++;
+        best[h[j + 1]] = std::max(best[h[j + 1]], m);
+    }
+    for (unsigned t = 0; t < 50277u; t++)
+        if (best[t] && best[t] >= allowed) out.push_back(dry_hit{t, best[t]});
+    return out;
+}
+
 inline int typical(float *_logits, float _temp = 0.9, float _tau = 0.8)
 {
     const std::vector<double> probs = typical_weights(_logits, _temp, _tau);

@@ -12,6 +12,10 @@ ROOT = os.path.dirname(HERE)
 HIPCC = os.environ.get("HIPCC") or shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 ARCH = "gfx950"
 ENGINE_LIBS = []   # extra link flags of librwkv_mi355x.so
+# The device link puts the code object's instructions on a page of their own.  Without it they start wherever the descriptors, symbols and
+# metadata in front of them end, so every added kernel moves every existing one inside its 4 KB page -- and the single-stream decode measured
+# 0.6 % slower after such a move with not one instruction changed (profiles/dry/bench_ab.txt).
+DEVICE_LINK = ["-Xoffload-linker", "-z", "-Xoffload-linker", "separate-code"]
 
 
 def _digest(sources, extra="") -> str:
@@ -70,10 +74,11 @@ def build_engine(force: bool = False) -> str:
     """csrc/engine.hip (+ every header it includes) -> csrc/librwkv_mi355x.so"""
     out = os.path.join(CSRC, "librwkv_mi355x.so")
     srcs = engine_sources()
-    if force or _stale(out, srcs):
+    flags = " ".join(DEVICE_LINK)
+    if force or _stale(out, srcs, flags):
         _run([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared",
-              "-Wno-unused-result", os.path.join(CSRC, "engine.hip"), "-o", out] + ENGINE_LIBS)
-        _stamp(out, srcs)
+              "-Wno-unused-result", os.path.join(CSRC, "engine.hip"), "-o", out] + DEVICE_LINK + ENGINE_LIBS)
+        _stamp(out, srcs, flags)
     return out
 
 

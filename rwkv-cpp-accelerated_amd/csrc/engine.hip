@@ -21,6 +21,7 @@
 #include "pickrows.hip.h"
 #include "floor.hip.h"
 #include "lookup.hip.h"
+#include "dry.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -262,6 +263,9 @@ enum GrownBuf {
     MIRO_MU,                          // f64 [max_ctx]: Mirostat's running threshold per state slot (floor.hip.h); allocated ONCE, zeroed, at the first call that needs it
     LOOKUP_RUN,                       // rwkv_decode_lookup_streams / rwkv_debug_lookup_draft (lookup.hip.h), LookupLayout: ids | picks | records | plan | segment table | live |
                                       // histories u32 | streams | output u32; everything in front of the output goes up in ONE copy, streams and output come down in one
+    DRY_HIST,                         // DRY penalties (dry.hip.h): u32 [max_ctx][DRY_MAX_WINDOW] the slots' id rings | u64 [max_ctx] the ids each slot was given; allocated ONCE,
+                                      // emptied, at the first call that needs it
+    DRY_DBG,                          // rwkv_debug_dry_scan, u32: count | id [DRY_MAX_WINDOW] | L [DRY_MAX_WINDOW]
     N_GROWN
 };
 
@@ -1967,8 +1971,19 @@ struct Constrainer {
     }
 };
 
+// ---- DRY penalties (dry.hip.h): one call's penalty, set up by dryer_setup.  scan() is the part of a step between the constrained rows and the pick:
+// one workgroup per stream appends the id the step feeds (`fed`, set per step) to the slot's history, searches it and subtracts from the stream's row.
+// Both launches are DEFINED at the end of this file: hipcc emits a template kernel where the host code first names it, so the two kernels come
+// out behind every other kernel of the code object and none of those moves against its neighbours.  (That alone did not keep the single-stream
+// decode where it was -- where the instructions start inside their page did: build.py DEVICE_LINK, profiles/dry/bench_ab.txt.)
+struct Dryer {
+    DryArgs a{};
+    int scan(rwkv_ctx *c, unsigned n) const;
+};
+int dry_debug_scan(rwkv_ctx *c, const DryArgs &a);      // k_dry_scan<true>, one workgroup
+
 // ---- a generation call: what it is (here), and how it runs (DecodeRun, below the setup functions of its parts) ----
-// rwkv_decode_greedy / _typical / _nucleus and rwkv_decode_batch_greedy / _typical / _nucleus / _until / _logprobs / _constrained fill this and hand
+// rwkv_decode_greedy / _typical / _nucleus and rwkv_decode_batch_greedy / _typical / _nucleus / _until / _logprobs / _constrained / _dry fill this and hand
 // it on.  A null member means that the part is absent (trailing members left out of the initialiser are null).
 struct DecodeCall {
     uint64_t N, n_steps;                            // streams (on slots 0 .. N - 1) and steps
@@ -1980,6 +1995,7 @@ struct DecodeCall {
     uint64_t *steps_run;
     const rwkv_logprob_out *lp;                     // the record, with the caller's arrays for it
     const rwkv_constrain_params *cp;                // the constraint, with the caller's out_state
+    const rwkv_dry_params *dry;                     // the DRY penalty (only with a constraint, and only when it is on: multiplier != 0)
 };
 int run_call(rwkv_ctx *c, const DecodeCall &d, const StopTable *table = nullptr);
 // the checks of rwkv_decode_greedy / _typical / _nucleus behind the guard: one stream on slot 0
@@ -2266,6 +2282,52 @@ int constrainer_download(rwkv_ctx *c, uint64_t slot0, uint64_t n)
     return 0;
 }
 
+// ---- the host side of the DRY penalties (rwkv_dry_history_*, rwkv_debug_dry_scan, rwkv_decode_batch_dry) ----
+static_assert(sizeof(rwkv_dry_params) == 40, "rwkv_dry_params is 40 bytes in the C ABI");
+static_assert(DRY_MAX_WINDOW == RWKV_DRY_MAX_WINDOW && DRY_MAX_MATCH == RWKV_DRY_MAX_MATCH && DRY_MAX_BREAKERS == RWKV_DRY_MAX_BREAKERS,
+              "dry.hip.h holds the header's limits");
+static_assert(offsetof(Ctl, token) == 0, "the one-stream loop hands k_dry_scan the control block as the array of fed ids");
+// the penalty's parameters are acceptable
+int check_dry(const rwkv_dry_params &p)
+{
+    if (!(p.multiplier >= 0.f)) return fail(RWKV_E_ARG, "dry: multiplier must be >= 0 (finite or +inf)");
+    if (!(p.base >= 1.f) || !std::isfinite(p.base)) return fail(RWKV_E_ARG, "dry: base must be >= 1 and finite");
+    if (p.allowed_length == 0 || p.allowed_length > RWKV_DRY_MAX_MATCH) return fail(RWKV_E_ARG, "dry: allowed_length must be in 1..%u", RWKV_DRY_MAX_MATCH);
+    if (p.window == 0 || p.window > RWKV_DRY_MAX_WINDOW) return fail(RWKV_E_ARG, "dry: window must be in 1..%u", RWKV_DRY_MAX_WINDOW);
+    if (p.n_breakers > RWKV_DRY_MAX_BREAKERS) return fail(RWKV_E_ARG, "dry: at most %u breakers", RWKV_DRY_MAX_BREAKERS);
+    if (p.flags || p.reserved) return fail(RWKV_E_ARG, "dry: unknown flag bits (0x%x) or reserved != 0", p.flags);
+    if (p.n_breakers && !p.breakers) return fail(RWKV_E_ARG, "NULL argument");
+    for (uint32_t i = 0; i < p.n_breakers; i++)
+        if (p.breakers[i] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "dry: breaker id %u out of range", p.breakers[i]);
+    return 0;
+}
+// the histories: the rings of all slots, behind them the totals; allocated ONCE, every slot empty
+unsigned long long *dry_totals(rwkv_ctx *c) { return reinterpret_cast<unsigned long long *>(c->buf<unsigned>(DRY_HIST) + c->maxT * DRY_MAX_WINDOW); }
+int dry_buffers(rwkv_ctx *c)
+{
+    if (c->grown[DRY_HIST].p) return 0;
+    if (const int rc = grow_buffer(c, DRY_HIST, (sizeof(unsigned) * DRY_MAX_WINDOW + sizeof(unsigned long long)) * c->maxT)) return rc;
+    HIPCHK(hipMemsetAsync(dry_totals(c), 0, sizeof(unsigned long long) * c->maxT, c->stream));      // (the rings' words are read only below a total)
+    return 0;
+}
+// the kernel's arguments from the parameters: the window, the breakers and the penalty table (include/rwkv_sampler.h dry_table); no device work
+void dry_args(rwkv_ctx *c, DryArgs &a, const rwkv_dry_params &p, unsigned slot0)
+{
+    a.ring = c->buf<unsigned>(DRY_HIST); a.total = dry_totals(c); a.slot = slot0;
+    a.allowed = p.allowed_length; a.window = p.window; a.n_breakers = p.n_breakers;
+    for (uint32_t i = 0; i < p.n_breakers; i++) a.breakers[i] = p.breakers[i];
+    const std::vector<float> pen = dry_table(p.multiplier, p.base);
+    std::copy(pen.begin(), pen.begin() + DRY_MAX_MATCH, a.pen);
+}
+// the penalty of a generation call over slots 0 .. N - 1: the histories, and the arguments that do not change from step to step
+int dryer_setup(rwkv_ctx *c, Dryer &dr, const rwkv_dry_params &p, const Constrainer &cn, const Stopper &st)
+{
+    if (const int rc = dry_buffers(c)) return rc;
+    dry_args(c, dr.a, p, 0u);
+    dr.a.rows = cn.r.out; dr.a.stopped = st.a.len;
+    return 0;
+}
+
 // what a pick of kind `kind` over `rows` rows needs besides the rows: the row argmax's partials, or a scratch slice per row for a sampler
 int grow_pick_buffers(rwkv_ctx *c, int kind, uint64_t rows)
 {
@@ -2281,7 +2343,7 @@ int grow_pick_buffers(rwkv_ctx *c, int kind, uint64_t rows)
 }
 
 // ---- the run of a generation call (DecodeCall) ----
-// setup; per step k: forward -> constrained rows -> pick -> automaton advance -> record -> stop test (step); end; the wait; results on the host.
+// setup; per step k: forward -> constrained rows -> DRY scan -> pick -> automaton advance -> record -> stop test (step); end; the wait; results on the host.
 // The parts a call does not ask for are absent from every one of these.  A call has one of two forms, one stream (the decode path's kernels on
 // slot 0) or many (the chunk path over rows and slots 0 .. N - 1), and they differ in three things only:
 //   the forward             one: the token graph, with its argmax node only where that node is the pick (greedy, no constraint);
@@ -2300,6 +2362,7 @@ struct DecodeRun {
     Stopper stopper, *st = d.cp || (d.stop && (d.stop->n_seqs || d.stop->max_new)) ? &stopper : nullptr;
     LpRecorder recorder, *lp = d.lp ? &recorder : nullptr;
     Constrainer constrainer, *cn = d.cp ? &constrainer : nullptr;
+    Dryer dryer, *dr = d.dry ? &dryer : nullptr;
     Sampler smp{};                                  // greedy: no arguments are built
     unsigned long long *ids = nullptr;              // many: ids row k, the ids fed at step k (BD_IDS behind the seeds)
     uint64_t ran() const { return st ? st->steps_run : d.n_steps; }      // steps enqueued
@@ -2312,6 +2375,7 @@ struct DecodeRun {
         if (const int rc = !one || (cn && !sampled) ? grow_pick_buffers(c, d.pick.kind, N) : 0) return rc;      // (one stream: only the row argmax needs any)
         if (const int rc = st ? stopper_setup(c, *st, *table, d.stop, d.first, N, d.n_steps, true, pick_penalty(d.pick)) : 0) return rc;
         if (const int rc = cn ? constrainer_setup(c, *cn, 0, 0, N, d.cp->bias_ptr, d.cp->bias_tok, d.cp->bias_val, st, d.cp->start) : 0) return rc;
+        if (const int rc = dr ? dryer_setup(c, *dr, *d.dry, *cn, *st) : 0) return rc;
         if (const int rc = lp ? lp_setup(c, *lp, N, d.n_steps, d.lp->top_n) : 0) return rc;
         if (const int rc = pick_counts(c, d.pick, 0, N, true)) return rc;
         if (const int rc = pick_mu(c, d.pick, 0, N, true)) return rc;
@@ -2343,6 +2407,8 @@ struct DecodeRun {
         const unsigned long long *picks = one ? c->gen + k : to;          // and where what follows it reads step k's picks
         if (const int rc = one ? run_token(c, !sampled && !cn) : enqueue_rows(c, nullptr, ids + k * n, n, RowLayout::of_mode(RWKV_MODE_PARRALEL))) return rc;      // logits rows and state slots 0 .. N - 1
         if (const int rc = cn ? cn->rows(c, n) : 0) return rc;
+        if (dr) dr->a.fed = one ? reinterpret_cast<const unsigned long long *>(c->ctl) : ids + k * n;      // the id step k feeds (one: still in the control block)
+        if (const int rc = dr ? dr->scan(c, n) : 0) return rc;
         if (sampled) {
             smp.draw().step = one ? -1 : (int)k; smp.draw().pick = to;
             if (const int rc = enqueue_pick(c, smp, n)) return rc;
@@ -2655,6 +2721,82 @@ int rwkv_decode_batch_constrained(rwkv_ctx *c, const uint64_t *first_tokens, uin
     if (const int rc = lp ? check_logprob_out(*lp) : 0) return rc;
     if (const int rc = check_pick_kind(*pick)) return rc;
     return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, *pick, out_tokens, stop, out_len, out_reason, steps_run, lp, cp});
+}
+
+int rwkv_decode_batch_dry(rwkv_ctx *c, const uint64_t *first_tokens, uint64_t n_streams, uint64_t n_steps, const rwkv_pick *pick,
+                          const uint64_t *seeds, const rwkv_constrain_params *cp, const rwkv_dry_params *dry, const rwkv_stop_params *stop,
+                          const rwkv_logprob_out *lp, uint64_t *out_tokens, uint32_t *out_len, uint32_t *out_reason, uint64_t *steps_run)
+{
+    if (const int rc = guard(c, NEED_WHOLE, pick && out_len && (!lp || lp->logprob))) return rc;
+    if (const int rc = lp ? check_logprob_out(*lp) : 0) return rc;
+    if (const int rc = check_pick_kind(*pick)) return rc;
+    if (const int rc = dry ? check_dry(*dry) : 0) return rc;
+    const rwkv_constrain_params none{};            // no start states, no bias, no out_state: the constraint a DRY call runs under when the caller brings none
+    return decode_batch(c, DecodeCall{n_streams, n_steps, first_tokens, seeds, *pick, out_tokens, stop, out_len, out_reason, steps_run, lp, cp ? cp : &none,
+                                      dry && dry->multiplier != 0.f ? dry : nullptr});
+}
+
+int rwkv_dry_history_set(rwkv_ctx *c, uint64_t slot, const uint64_t *ids, uint64_t n)
+{
+    if (const int rc = guard(c, NEED_LOADED, ids || n == 0)) return rc;
+    if (slot >= c->maxT) return fail(RWKV_E_ARG, "slot %llu out of range (max context %llu)", (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (const int rc = check_ids(ids, n, "history")) return rc;
+    if (n == 0 && !c->grown[DRY_HIST].p) return 0;           // empty is what an unallocated history is
+    std::vector<unsigned> ring(DRY_MAX_WINDOW, 0u);          // id number i at word i mod DRY_MAX_WINDOW, as k_dry_scan appends
+    for (uint64_t i = n > DRY_MAX_WINDOW ? n - DRY_MAX_WINDOW : 0; i < n; i++) ring[i & (DRY_MAX_WINDOW - 1u)] = (unsigned)ids[i];
+    const unsigned long long total = n;
+    return finish(c, [&]() -> int {
+        if (const int rc = dry_buffers(c)) return rc;
+        HIPCHK(hipMemcpyAsync(c->buf<unsigned>(DRY_HIST) + slot * DRY_MAX_WINDOW, ring.data(), sizeof(unsigned) * DRY_MAX_WINDOW, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(dry_totals(c) + slot, &total, sizeof(total), hipMemcpyHostToDevice, c->stream));
+        return 0;
+    }());
+}
+
+int rwkv_dry_history_get(rwkv_ctx *c, uint64_t slot, uint64_t *ids, uint64_t *n, uint64_t *total)
+{
+    if (const int rc = guard(c, NEED_LOADED, ids && n && total)) return rc;
+    if (slot >= c->maxT) return fail(RWKV_E_ARG, "slot %llu out of range (max context %llu)", (unsigned long long)slot, (unsigned long long)c->maxT);
+    *n = 0; *total = 0;
+    if (!c->grown[DRY_HIST].p) return 0;
+    std::vector<unsigned> ring(DRY_MAX_WINDOW, 0u);
+    unsigned long long tot = 0;
+    const int rc = finish(c, [&]() -> int {
+        HIPCHK(hipMemcpyAsync(ring.data(), c->buf<unsigned>(DRY_HIST) + slot * DRY_MAX_WINDOW, sizeof(unsigned) * DRY_MAX_WINDOW, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(&tot, dry_totals(c) + slot, sizeof(tot), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+    if (rc) return rc;
+    const uint64_t keep = std::min<uint64_t>(tot, DRY_MAX_WINDOW);
+    for (uint64_t i = 0; i < keep; i++) ids[i] = ring[(tot - keep + i) & (DRY_MAX_WINDOW - 1u)];
+    *n = keep; *total = tot;
+    return 0;
+}
+
+int rwkv_debug_dry_scan(rwkv_ctx *c, uint64_t slot, const rwkv_dry_params *dry, uint32_t *tok, uint32_t *len, uint32_t *n_out)
+{
+    if (const int rc = guard(c, NEED_LOADED | LAUNCHES, dry && tok && len && n_out)) return rc;
+    if (slot >= c->maxT) return fail(RWKV_E_ARG, "slot %llu out of range (max context %llu)", (unsigned long long)slot, (unsigned long long)c->maxT);
+    if (const int rc = check_dry(*dry)) return rc;
+    std::vector<unsigned> out(1 + 2 * DRY_MAX_WINDOW, 0u);
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = dry_buffers(c)) return rc;
+        if (const int rc = grow_buffer(c, DRY_DBG, sizeof(unsigned) * out.size())) return rc;
+        DryArgs a{};
+        dry_args(c, a, *dry, (unsigned)slot);
+        a.dbg = c->buf<unsigned>(DRY_DBG);
+        if (const int rc = dry_debug_scan(c, a)) return rc;
+        HIPCHK(hipMemcpyAsync(out.data(), a.dbg, sizeof(unsigned) * out.size(), hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    }());
+    if (rc) return rc;
+    const unsigned cnt = std::min(out[0], DRY_MAX_WINDOW);
+    std::vector<std::pair<unsigned, unsigned>> pairs;       // the table's sweep order is the buckets': by id for the caller
+    for (unsigned i = 0; i < cnt; i++) pairs.emplace_back(out[1 + i], out[1 + DRY_MAX_WINDOW + i]);
+    std::sort(pairs.begin(), pairs.end());
+    for (unsigned i = 0; i < cnt; i++) { tok[i] = pairs[i].first; len[i] = pairs[i].second; }
+    *n_out = cnt;
+    return 0;
 }
 
 int rwkv_topn_rows(rwkv_ctx *c, const uint64_t *rows, uint64_t n, uint32_t top_n, uint64_t *ids, double *logprob)
@@ -4666,5 +4808,21 @@ void *rwkv_tensor_device(rwkv_ctx *c, int slot)
     default: return nullptr;
     }
 }
+
+namespace {
+// the launches of dry.hip.h (see Dryer): the LAST kernels this file names
+int Dryer::scan(rwkv_ctx *c, unsigned n) const
+{
+    k_dry_scan<false><<<dim3(n), dim3(DRY_NT), 0, c->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+int dry_debug_scan(rwkv_ctx *c, const DryArgs &a)
+{
+    k_dry_scan<true><<<dim3(1), dim3(DRY_NT), 0, c->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+} // namespace
 
 } // extern "C"

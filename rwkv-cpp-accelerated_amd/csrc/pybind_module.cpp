@@ -268,6 +268,21 @@ PYBIND11_MODULE(rwkv, m)
           py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("temp") = 1.0f, py::arg("top_p") = 0.9f, py::arg("top_k") = 0u,
           py::arg("presence") = 0.f, py::arg("frequency") = 0.f, py::arg("decay") = 1.0f, py::arg("seed") = 0ull, py::arg("greedy") = false,
           py::arg("bias_tok") = std::vector<uint32_t>{}, py::arg("bias_val") = std::vector<float>{});
+    m.def("decodeBatchDry", [](std::uintptr_t h, const std::vector<int64_t> &first, int64_t n, float multiplier, float base, unsigned allowed_length,
+                               unsigned window, const std::vector<uint32_t> &breakers, const std::vector<int64_t> &history, float temp, float top_p,
+                               unsigned top_k, float presence, float frequency, float decay, const std::vector<uint64_t> &seeds, bool greedy) {
+        const RWKV::Pick pick = greedy ? RWKV::Pick::greedy() : RWKV::Pick::nucleus(RWKV::Nucleus{temp, top_p, top_k, presence, frequency, decay});
+        if (!history.empty()) M(h)->setDryHistory(0, std::vector<unsigned long long>(history.begin(), history.end()));
+        const RWKV::Until r = M(h)->decodeBatchDry(std::vector<unsigned long long>(first.begin(), first.end()), n, pick,
+                                                   std::vector<unsigned long long>(seeds.begin(), seeds.end()),
+                                                   RWKV::Dry{multiplier, base, allowed_length, window, breakers});
+        return std::vector<int64_t>(r.ids.begin(), r.ids.end());
+    }, "device-side continuation of len(first) streams with the DRY penalty (multiplier = inf: a no-repeat-n-gram ban with n = allowed_length + 1); "
+       "history: ids planted as the DRY history of slot 0 in front of the call; returns the ids [stream][n] flattened (engine extension)",
+          py::arg("rwkvp"), py::arg("first"), py::arg("n"), py::arg("multiplier") = 0.8f, py::arg("base") = 1.75f, py::arg("allowed_length") = 2u,
+          py::arg("window") = 4096u, py::arg("breakers") = std::vector<uint32_t>{}, py::arg("history") = std::vector<int64_t>{}, py::arg("temp") = 1.0f,
+          py::arg("top_p") = 0.9f, py::arg("top_k") = 0u, py::arg("presence") = 0.f, py::arg("frequency") = 0.f, py::arg("decay") = 1.0f,
+          py::arg("seeds") = std::vector<uint64_t>{}, py::arg("greedy") = false);
     m.def("constraintCheck", [](py::object S, py::object row_ptr, py::object tok, py::object next, py::object bias_tok, py::object bias_val) -> py::object {
         // the arrays as given: S and the lengths are NOT derived from each other, so that every malformed input reaches the validator
         u32arr rp, tk, nx, bt;

@@ -49,11 +49,13 @@ ABI_SYMBOLS = [
     "rwkv_tree_plan", "rwkv_spec_verify_trees", "rwkv_spec_sample_trees",
     "rwkv_sample_floor", "rwkv_mirostat_set", "rwkv_mirostat_get",
     "rwkv_decode_lookup_streams", "rwkv_debug_lookup_draft",
+    "rwkv_dry_history_set", "rwkv_dry_history_get", "rwkv_debug_dry_scan", "rwkv_decode_batch_dry",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 SPEC_MAX_DRAFT = 31               # RWKV_SPEC_MAX_DRAFT
 LOOKUP_MAX_NGRAM, LOOKUP_MAX_HISTORY = 8, 1 << 20   # RWKV_LOOKUP_MAX_NGRAM, RWKV_LOOKUP_MAX_HISTORY
+DRY_MAX_WINDOW, DRY_MAX_MATCH, DRY_MAX_BREAKERS = 4096, 64, 32   # RWKV_DRY_MAX_*
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 MAX_PICK_ROWS, PICKQ_SEED, PICK_BATCH = 1024, 1, 64   # RWKV_MAX_PICK_ROWS, RWKV_PICKQ_SEED; the queries of one launch sequence (csrc/engine.hip PQ_BATCH)
 TOPN_MAX = 32                     # RWKV_MAX_TOPN
@@ -328,6 +330,20 @@ class ConstrainParams(C.Structure):
                 ("bias_val", C.POINTER(C.c_float)), ("out_state", C.POINTER(C.c_uint32)), ("reserved", C.c_uint64)]
 
 
+class DryParams(C.Structure):
+    """rwkv_dry_params of include/rwkv_mi355x.h (40 bytes)"""
+    _fields_ = [("multiplier", C.c_float), ("base", C.c_float), ("allowed_length", C.c_uint32), ("window", C.c_uint32), ("n_breakers", C.c_uint32),
+                ("flags", C.c_uint32), ("breakers", C.POINTER(C.c_uint32)), ("reserved", C.c_uint64)]
+
+
+def dry_params(multiplier=0.8, base=1.75, allowed_length=2, window=DRY_MAX_WINDOW, breakers=()):
+    """(DryParams, the array it points into -- keep it alive for the call); multiplier=float("inf") bans every (allowed_length + 1)-gram the
+    window already holds"""
+    br = [int(t) for t in breakers]
+    arr = (C.c_uint32 * max(1, len(br)))(*br)
+    return DryParams(float(multiplier), float(base), int(allowed_length), int(window), len(br), 0, arr if br else None, 0), arr
+
+
 def _bias_arrays(bias):
     """one bias list -- a dict {id: value} or a sequence of (id, value) pairs, given in any order -- as (ids u32, values f32), ids ascending"""
     pairs = sorted((int(t), float(v)) for t, v in (bias.items() if hasattr(bias, "items") else bias))
@@ -482,6 +498,12 @@ def lib():
     L.rwkv_decode_lookup_streams.restype = i32
     L.rwkv_debug_lookup_draft.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.rwkv_debug_lookup_draft.restype = i32
+    L.rwkv_dry_history_set.argtypes = [vp, u64, C.POINTER(u64), u64]; L.rwkv_dry_history_set.restype = i32
+    L.rwkv_dry_history_get.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]; L.rwkv_dry_history_get.restype = i32
+    L.rwkv_debug_dry_scan.argtypes = [vp, u64, C.POINTER(DryParams), u32p, u32p, u32p]; L.rwkv_debug_dry_scan.restype = i32
+    L.rwkv_decode_batch_dry.argtypes = [vp, C.POINTER(u64), u64, u64, C.POINTER(Pick), C.POINTER(u64), C.POINTER(ConstrainParams), C.POINTER(DryParams),
+                                        C.POINTER(StopParams), C.POINTER(LogprobOut), C.POINTER(u64), u32p, u32p, C.POINTER(u64)]
+    L.rwkv_decode_batch_dry.restype = i32
     L.rwkv_segment_plan.argtypes = [C.POINTER(Segment), u64, u64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.POINTER(u64)]; L.rwkv_segment_plan.restype = i32
     _lib = L
     return L
@@ -809,7 +831,7 @@ class RWKV:
     # -- stop sequences and per-stream budgets in the device loops (include/rwkv_mi355x.h rwkv_decode_batch_until) --------
     def decode_batch_until(self, first_tokens, n_steps: int, stops=(), max_new=None, keep: bool = False, pick: str = "greedy", seeds=None,
                            temp: float = 1.0, tau: float | None = None, recipe: bool = False, top_p: float = 0.9, top_k: int = 0, presence: float = 0.0,
-                           frequency: float = 0.0, decay: float = 1.0, min_p: float = 0.05, eta: float = 0.1, _logprobs=None, _constrain=None):
+                           frequency: float = 0.0, decay: float = 1.0, min_p: float = 0.05, eta: float = 0.1, _logprobs=None, _constrain=None, _dry=None):
         """decode_batch_greedy / _typical / _nucleus (pick = "greedy", "typical", "nucleus", with that call's parameters) in which stream s ends
         at the first of the stop sequences `stops` (lists of token ids, each 1 .. 8 long) that its newest ids spell, or after max_new[s] tokens.
         keep: the match history (and the nucleus counts) continue from the previous call.  Returns (ids [N][n_steps], 0 behind a stream's end;
@@ -832,7 +854,10 @@ class RWKV:
         sp, alive = stop_params(stops, max_new, keep)
         ln, rs, ran = (C.c_uint32 * max(1, n))(), (C.c_uint32 * max(1, n))(), C.c_uint64(0)
         sdp = None if kind == PICK_GREEDY else arr
-        if _constrain is not None:      # decode_batch_constrained: the same call with the constraint hook (and the record, or none)
+        if _dry is not None:            # decode_batch_dry: the constrained call with the DRY penalty
+            call = lambda ft, n_, out: lib().rwkv_decode_batch_dry(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(_constrain), C.byref(_dry), C.byref(sp),
+                                                                   None if _logprobs is None else C.byref(_logprobs), out, ln, rs, C.byref(ran))
+        elif _constrain is not None:    # decode_batch_constrained: the same call with the constraint hook (and the record, or none)
             call = lambda ft, n_, out: lib().rwkv_decode_batch_constrained(self._h, ft, n_, n_steps, C.byref(pk), sdp, C.byref(_constrain), C.byref(sp),
                                                                            None if _logprobs is None else C.byref(_logprobs), out, ln, rs, C.byref(ran))
         elif _logprobs is None:
@@ -942,6 +967,39 @@ class RWKV:
         else:
             r = self.decode_batch_until(first_tokens, n_steps, _constrain=cp, **kw)
         return r[:4] + (out_state[:n].astype(np.int64),) + r[4:]
+
+    # -- DRY and no-repeat-n-gram penalties (include/rwkv_mi355x.h rwkv_decode_batch_dry) --------
+    def dry_history_set(self, ids, slot: int = 0):
+        """replace the DRY history of slot `slot` by `ids` (the newest 4096 are kept; an empty list empties it): a prompt's ids but the last,
+        which the loop feeds"""
+        a = [int(t) for t in ids]
+        _chk(lib().rwkv_dry_history_set(self._h, int(slot), (C.c_uint64 * max(1, len(a)))(*a), len(a)))
+
+    def dry_history_get(self, slot: int = 0):
+        """(the ids the slot's ring holds, oldest first, int64; the total number of ids the slot was given)"""
+        out, n, total = (C.c_uint64 * DRY_MAX_WINDOW)(), C.c_uint64(0), C.c_uint64(0)
+        _chk(lib().rwkv_dry_history_get(self._h, int(slot), out, C.byref(n), C.byref(total)))
+        return np.frombuffer(out, dtype=np.uint64)[: n.value].astype(np.int64), int(total.value)
+
+    def debug_dry_scan(self, slot: int = 0, **dry):
+        """the device scan alone over the history of slot `slot` as it stands (the keywords of dry_params): [(id, L)] ascending by id, the ids a
+        DRY step would penalise and the length of the repeat each would extend.  No append, no row, no forward."""
+        p, alive = dry_params(**dry)
+        tok, ln, n = (C.c_uint32 * DRY_MAX_WINDOW)(), (C.c_uint32 * DRY_MAX_WINDOW)(), C.c_uint32(0)
+        _chk(lib().rwkv_debug_dry_scan(self._h, int(slot), C.byref(p), tok, ln, C.byref(n)))
+        del alive
+        return [(int(tok[i]), int(ln[i])) for i in range(n.value)]
+
+    def decode_batch_dry(self, first_tokens, n_steps: int, multiplier: float = 0.8, base: float = 1.75, allowed_length: int = 2,
+                         window: int = DRY_MAX_WINDOW, breakers=(), **kw):
+        """decode_batch_constrained (its arguments and results: start, bias, logprobs, top_n, stops, max_new, keep, pick, seeds, ...) with the DRY
+        penalty: at every step the id that would extend a repeat of >= allowed_length ids of the stream's own tail loses multiplier *
+        base ** (repeat - allowed_length) on its constrained logit; multiplier = inf bans every (allowed_length + 1)-gram seen in the newest `window`
+        ids; breakers: ids no repeat reaches across.  Step k appends the id it feeds to slot s's history (dry_history_set plants a prompt)."""
+        p, alive = dry_params(multiplier, base, allowed_length, window, breakers)
+        r = self.decode_batch_constrained(first_tokens, n_steps, _dry=p, **kw)
+        del alive
+        return r
 
     def topn_rows(self, rows, top_n: int):
         """(ids [n][top_n], logprob [n][top_n]): the top_n most probable tokens of logits row rows[i] of the LAST forward (rwkv_topn_rows), in
