@@ -506,6 +506,25 @@ public:
             res.push_back(SpecResult{std::vector<unsigned long long>(out.begin() + s * n, out.begin() + (s + 1) * n), st[s].rounds, st[s].drafted, st[s].accepted});
         return res;
     }
+    // decodeLookupStreams with draft TREES (rwkv_mi355x.h "lookup decoding with DRAFT TREES as one device loop"): every round the device merges what
+    // followed the `branches` most recent occurrences of the stream's last n ids into a trie of at most k nodes and keeps the path that stands.
+    std::vector<SpecResult> decodeLookupTrees(const std::vector<std::vector<unsigned long long>> &histories, unsigned long long n, unsigned k = 8,
+                                              unsigned ngram = 3, unsigned branches = 3)
+    {
+        if (!ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> ids, len;
+        for (const auto &h : histories) { ids.insert(ids.end(), h.begin(), h.end()); len.push_back(h.size()); }
+        const size_t N = histories.size();
+        std::vector<uint64_t> out(N * n + 1);
+        std::vector<rwkv_spec_stats> st(N + 1);
+        const rwkv_lookup_tree_params p{k, ngram, branches, 0u};
+        ids.push_back(0); len.push_back(0);      // (never read: see decodeLookupStreams)
+        rwkv_detail::check(rwkv_decode_lookup_trees(ctx_, ids.data(), len.data(), N, n, &p, out.data(), st.data()));
+        std::vector<SpecResult> res;
+        for (size_t s = 0; s < N; s++)
+            res.push_back(SpecResult{std::vector<unsigned long long>(out.begin() + s * n, out.begin() + (s + 1) * n), st[s].rounds, st[s].drafted, st[s].accepted});
+        return res;
+    }
     // draft TREES for many streams (rwkv_mi355x.h "draft TREES for many streams"): specVerifySegments where the last n_draft ids of a segment are a
     // tree -- parent[r], one entry per id of the segment, counted from its first id and read for the guesses, names the last certain id or an earlier
     // guess.  Of the guesses the one path the greedy picks confirm is kept; `ids` are its ids in order.

@@ -810,7 +810,8 @@ int rwkv_spec_sample_trees(rwkv_ctx *ctx, const uint64_t *tokens /* [T] */, cons
  * rwkv_spec_verify_segments) are counted by rwkv_resident_bytes and freed by rwkv_free.
  * rwkv_debug_lookup_draft runs the drafter ALONE with kd = k on uploaded histories and downloads what it drafted: draft[s][0 .. n_draft[s] - 1]
  * (the rest of the row is 0).  It makes no pass and touches no state or logits; any created context will do; n_streams <= 64, the other limits as above.
- * Out of scope: sampled acceptance in the loop, draft trees, a draft model, stop sequences, admission of new streams mid-call. */
+ * Out of scope: sampled acceptance in the loop, a draft model, stop sequences, admission of new streams mid-call.  Draft trees have their own
+ * loop, below. */
 #define RWKV_LOOKUP_MAX_NGRAM 8u
 #define RWKV_LOOKUP_MAX_HISTORY (1u << 20)
 typedef struct rwkv_lookup_params { uint32_t k, n, flags, reserved; } rwkv_lookup_params;   /* draft ids per round, tail length; flags and reserved must be 0 */
@@ -819,6 +820,33 @@ int rwkv_decode_lookup_streams(rwkv_ctx *ctx, const uint64_t *history /* the str
                                rwkv_spec_stats *stats /* [n_streams], may be NULL */);
 int rwkv_debug_lookup_draft(rwkv_ctx *ctx, const uint64_t *history, const uint64_t *hist_len /* [n_streams] */, uint64_t n_streams, uint32_t k, uint32_t n,
                             uint64_t *draft /* [n_streams][k] */, uint32_t *n_draft /* [n_streams] */);
+
+/* ---- lookup decoding with DRAFT TREES as one device loop (csrc/lookuptree.hip.h; no reference counterpart) ----
+ * rwkv_decode_lookup_trees is rwkv_decode_lookup_streams, word for word -- stream s on slot s, which holds the state behind all but the last id of
+ * its history; the fixed launch shape of n_streams segments of 1 + k rows in one pass; the blind rounds, the polled rounds, the refusal rules, one
+ * upload and one download -- with a drafter that keeps more than one occurrence and a verify that knows a tree:
+ *     1. DRAFT: the continuations behind the `branches` MOST RECENT earlier occurrences of the history's last n ids, most recent first, each up to
+ *        k ids and cut where the history ends, merged LEVEL BY LEVEL into a trie of at most k nodes: at level d, continuation after continuation,
+ *        the id either follows an existing child of the node the continuation has reached or, while fewer than k nodes exist, becomes a new one; a
+ *        continuation that gets no node stops.  Node j hangs below node parent[j] < j or, with parent[j] == -1, below the history's last id;
+ *        siblings differ.  The trie is then cut at the depth the stream still wants (remaining - 1), which keeps a prefix of the nodes;
+ *     2. VERIFY in the layout of rwkv_spec_verify_trees: a node's row starts from its parent's row; rows behind the kept nodes are padding;
+ *     3. ACCEPT the one path from the root the greedy picks confirm, COMMIT the slot from its last row;
+ *     4. APPEND the path's ids and the next pick.
+ * stats.drafted counts the nodes kept after the cut.
+ * EXACT: ids, stats and the slots' xy / aa / bb / dd are bit for bit those of the host loop over rwkv_spec_verify_trees that drafts by the same rule
+ * with the same k (one segment per live stream and round), whenever n_streams (k + 1) fits one pass -- which this call requires.  With branches == 1
+ * they are bit for bit those of rwkv_decode_lookup_streams.
+ * Status: as rwkv_decode_lookup_streams, and RWKV_E_ARG for branches outside 1..RWKV_LOOKUP_MAX_BRANCHES or flags != 0.
+ * rwkv_debug_lookup_tree runs the drafter ALONE, with a budget that does not cut, on uploaded histories: ids[s][j] and parent[s][j] for
+ * j < n_nodes[s] (the rest of a row is 0 / -1).  It makes no pass and touches no state or logits; any created context will do; n_streams <= 64.
+ * Out of scope: sampled acceptance in the loop, a draft model, stop sequences, admission of new streams mid-call, cutting the launch shape per round. */
+#define RWKV_LOOKUP_MAX_BRANCHES 8u
+typedef struct rwkv_lookup_tree_params { uint32_t k, n, branches, flags; } rwkv_lookup_tree_params;   /* nodes per round, tail length, occurrences merged; flags must be 0 */
+int rwkv_decode_lookup_trees(rwkv_ctx *ctx, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t n_tokens,
+                             const rwkv_lookup_tree_params *params, uint64_t *out_tokens, rwkv_spec_stats *stats /* may be NULL */);
+int rwkv_debug_lookup_tree(rwkv_ctx *ctx, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint32_t k, uint32_t n, uint32_t branches,
+                           uint64_t *ids /* [n_streams][k] */, int32_t *parent /* [n_streams][k], -1 = below the history's last id */, uint32_t *n_nodes /* [n_streams] */);
 
 /* ---- DRY and no-repeat-n-gram penalties in the device decode loops (no reference counterpart: the reference only samples) ----
  * The count penalties of rwkv_nucleus_params see single tokens.  DRY ("don't repeat yourself") sees SEQUENCES: it penalises the id that would

@@ -21,6 +21,7 @@
 #include "pickrows.hip.h"
 #include "floor.hip.h"
 #include "lookup.hip.h"
+#include "lookuptree.hip.h"
 #include "dry.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
@@ -262,7 +263,8 @@ enum GrownBuf {
                                       // behind them the records, the accepted ids and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT
     MIRO_MU,                          // f64 [max_ctx]: Mirostat's running threshold per state slot (floor.hip.h); allocated ONCE, zeroed, at the first call that needs it
     LOOKUP_RUN,                       // rwkv_decode_lookup_streams / rwkv_debug_lookup_draft (lookup.hip.h), LookupLayout: ids | picks | records | plan | segment table | live |
-                                      // histories u32 | streams | output u32; everything in front of the output goes up in ONE copy, streams and output come down in one
+                                      // histories u32 | streams | output u32; everything in front of the output goes up in ONE copy, streams and output come down in one.
+                                      // rwkv_decode_lookup_trees / rwkv_debug_lookup_tree (lookuptree.hip.h): the from table and the accepted ids behind `live`
     DRY_HIST,                         // DRY penalties (dry.hip.h): u32 [max_ctx][DRY_MAX_WINDOW] the slots' id rings | u64 [max_ctx] the ids each slot was given; allocated ONCE,
                                       // emptied, at the first call that needs it
     DRY_DBG,                          // rwkv_debug_dry_scan, u32: count | id [DRY_MAX_WINDOW] | L [DRY_MAX_WINDOW]
@@ -3775,16 +3777,19 @@ int rwkv_spec_sample_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *p
 
 // ---- lookup decoding as one device loop (lookup.hip.h): rwkv_decode_lookup_streams, rwkv_debug_lookup_draft ----
 static_assert(sizeof(rwkv_lookup_params) == 16 && LK_MAX_N == RWKV_LOOKUP_MAX_NGRAM, "the params of the C ABI; lookup.hip.h holds the header's limit");
+static_assert(sizeof(rwkv_lookup_tree_params) == 16 && LKT_MAX_B == RWKV_LOOKUP_MAX_BRANCHES, "the params of the C ABI; lookuptree.hip.h holds the header's limit");
 namespace {
 // LOOKUP_RUN in bytes for N streams, T rows, `hist` history words (the streams' capacities, each a multiple of 4) and `out` output words.  [0, out)
-// is the call's ONE upload, [st, bytes) its one download
+// is the call's ONE upload, [st, bytes) its one download.  `tree`: behind `live` the from table (a byte per row) and the accepted ids
+// [N][SPEC_MAX_DRAFT] of lookuptree.hip.h; without it both are empty and the layout is the chain's
 struct LookupLayout {
-    size_t ids, picks, rec, plan, tab, live, hist, st, out, bytes;
-    LookupLayout(uint64_t N, uint64_t T, uint64_t hist_words, uint64_t out_words)
+    size_t ids, picks, rec, plan, tab, live, from, emitted, hist, st, out, bytes;
+    LookupLayout(uint64_t N, uint64_t T, uint64_t hist_words, uint64_t out_words, bool tree = false)
     {
         const size_t rows = std::max<size_t>(T, SEQ_TM);
         ids = 0; picks = ids + 8 * rows; rec = picks + 8 * rows; plan = rec + sizeof(SpecSegRec) * N; tab = plan + sizeof(SegRow) * rows;
-        live = tab + sizeof(SpecSegEntry) * N; hist = (live + 8 + 15) / 16 * 16; st = hist + 4 * hist_words; out = st + sizeof(LookupStream) * N;
+        live = tab + sizeof(SpecSegEntry) * N; from = live + 8; emitted = (from + (tree ? rows : 0) + 7) / 8 * 8;
+        hist = (emitted + (tree ? 8 * SPEC_MAX_DRAFT * N : 0) + 15) / 16 * 16; st = hist + 4 * hist_words; out = st + sizeof(LookupStream) * N;
         bytes = out + 4 * ((out_words + 3) / 4 * 4);
     }
 };
@@ -3793,6 +3798,7 @@ struct LookupRun {
     LookupLayout lay{1, 1, 0, 0};
     LookupArgs a{};
     SpecSegAcceptArgs acc{};
+    LookupTreeArgs ta{};               // branches > 0: the tree form (lookuptree.hip.h) of the same run
     const SegRow *plan = nullptr;
     uint64_t N = 0, T = 0;
     // the rules the two entry points share, all of them before anything is launched or allocated
@@ -3809,19 +3815,21 @@ struct LookupRun {
         return check_ids(history, total, "token");
     }
     // buffers, the host image and its ONE upload: rows of valid ids, the constant row plan (stream s on slot s, 1 + k rows), a table of retired
-    // entries (the first round applies nothing), the histories as u32 and the streams
-    int setup(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t grow, uint32_t k, uint32_t n)
+    // entries (the first round applies nothing), the histories as u32 and the streams.  branches > 0: the tree form, whose from table starts as
+    // enqueue_verify_trees leaves the rows behind T -- every row its own
+    int setup(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t grow, uint32_t k, uint32_t n, uint32_t branches = 0)
     {
         N = n_streams; T = N * (k + 1u);
         std::vector<uint64_t> off(N + 1, 0);
         for (uint64_t s = 0; s < N; s++) off[s + 1] = off[s] + (hist_len[s] + grow + 3) / 4 * 4;
-        lay = LookupLayout(N, T, off[N], N * grow);
+        lay = LookupLayout(N, T, off[N], N * grow, branches > 0);
         if (const int rc = grow_buffer(c, LOOKUP_RUN, lay.bytes)) return rc;
         c->lk_host.assign((lay.bytes + 7) / 8, 0ull);
         unsigned char *hb = reinterpret_cast<unsigned char *>(c->lk_host.data()), *db = c->buf<unsigned char>(LOOKUP_RUN);
         SegRow *hp = reinterpret_cast<SegRow *>(hb + lay.plan);
         for (uint64_t j = 0; j < std::max<uint64_t>(T, SEQ_TM); j++) hp[j] = j < T ? SegRow{(unsigned)(j / (k + 1u)), j % (k + 1u) == 0 ? SEG_FIRST : 0u} : SegRow{0u, SEG_FIRST};
         *reinterpret_cast<unsigned long long *>(hb + lay.live) = N;
+        for (size_t j = lay.from; branches > 0 && j < lay.emitted; j++) hb[j] = (unsigned char)(j - lay.from);
         unsigned *hh = reinterpret_cast<unsigned *>(hb + lay.hist);
         LookupStream *hs = reinterpret_cast<LookupStream *>(hb + lay.st);
         for (uint64_t s = 0, j = 0; s < N; s++) {
@@ -3836,12 +3844,14 @@ struct LookupRun {
         a.n_tokens = (unsigned)grow; a.k = k; a.n = n;
         acc = SpecSegAcceptArgs{a.ids, reinterpret_cast<const unsigned long long *>(db + lay.picks), a.tab, reinterpret_cast<SpecSegRec *>(db + lay.rec)};
         plan = reinterpret_cast<const SegRow *>(db + lay.plan);
+        ta = LookupTreeArgs{a, db + lay.from, reinterpret_cast<const unsigned long long *>(db + lay.emitted), nullptr, branches};
         return 0;
     }
     // apply the records of the round in front (none: nothing), draft the next round's rows
     int round(rwkv_ctx *c) const
     {
-        k_lookup_round<LK_NT, LK_W><<<dim3((unsigned)N), dim3(LK_NT), 0, c->stream>>>(a);
+        if (ta.branches) k_lookup_tree_round<LK_NT, LK_W><<<dim3((unsigned)N), dim3(LK_NT), 0, c->stream>>>(ta);
+        else k_lookup_round<LK_NT, LK_W><<<dim3((unsigned)N), dim3(LK_NT), 0, c->stream>>>(a);
         HIPCHK(hipGetLastError());
         return 0;
     }
@@ -3850,10 +3860,11 @@ struct LookupRun {
     int verify(rwkv_ctx *c) const
     {
         double *ck = c->buf<double>(SPEC_CKPT);
-        const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, a.ids, RowLayout::spec_segments(plan, ck)};
+        const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, a.ids, ta.branches ? RowLayout::spec_trees(plan, ta.from, ck) : RowLayout::spec_segments(plan, ck)};
         if (const int rc = enqueue_chunk(c, pass)) return rc;
         if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)T, const_cast<unsigned long long *>(acc.pick))) return rc;
-        k_lookup_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(acc);
+        if (ta.branches) k_lookup_tree_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(SpecTreeAcceptArgs{a.ids, acc.pick, ta.from, a.tab, acc.rec, const_cast<unsigned long long *>(ta.emitted)});
+        else k_lookup_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(acc);
         const SpecSegCommitArgs ca{acc.rec, a.tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
         const unsigned pairs = (unsigned)(c->L * c->D / 2);
         k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)N), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
@@ -3891,22 +3902,23 @@ struct LookupRun {
 };
 } // namespace
 
-int rwkv_decode_lookup_streams(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t n_tokens,
-                               const rwkv_lookup_params *p, uint64_t *out_tokens, rwkv_spec_stats *stats)
+namespace {
+// a decode call of either form behind its guard and its params' own rules: the shared checks, everything enqueued, the one wait, ids and stats out.
+// branches == 0: chains (lookup.hip.h)
+int run_lookup_decode(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t n_tokens, uint32_t k, uint32_t n,
+                      uint32_t branches, uint64_t *out_tokens, rwkv_spec_stats *stats)
 {
-    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, history && hist_len && p && out_tokens)) return rc;
-    if (p->flags || p->reserved) return fail(RWKV_E_ARG, "flags and reserved must be 0");
     if (const int rc = check_steps(n_tokens, "n_tokens")) return rc;
     const uint64_t pass_rows = std::min<uint64_t>(c->maxT, c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T);
-    if (const int rc = LookupRun::check(history, hist_len, n_streams, pass_rows, p->k, p->n)) return rc;
-    if (n_streams * (p->k + 1u) > pass_rows)
-        return fail(RWKV_E_ARG, "%llu streams of 1 + %u rows: a round is ONE pass of at most %llu rows", (unsigned long long)n_streams, p->k, (unsigned long long)pass_rows);
+    if (const int rc = LookupRun::check(history, hist_len, n_streams, pass_rows, k, n)) return rc;
+    if (n_streams * (k + 1u) > pass_rows)
+        return fail(RWKV_E_ARG, "%llu streams of 1 + %u rows: a round is ONE pass of at most %llu rows", (unsigned long long)n_streams, k, (unsigned long long)pass_rows);
     LookupRun run;
     auto enqueue = [&]() -> int {
         if (const int rc = poll_ring_setup(c)) return rc;
-        if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, n_streams * (p->k + 1u))) return rc;
-        if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * n_streams * (p->k + 1u) * c->D)) return rc;
-        if (const int rc = run.setup(c, history, hist_len, n_streams, n_tokens, p->k, p->n)) return rc;
+        if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, n_streams * (k + 1u))) return rc;
+        if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * n_streams * (k + 1u) * c->D)) return rc;
+        if (const int rc = run.setup(c, history, hist_len, n_streams, n_tokens, k, n, branches)) return rc;
         if (const int rc = run.rounds(c, n_tokens)) return rc;
         return run.download(c, true);
     };
@@ -3918,6 +3930,28 @@ int rwkv_decode_lookup_streams(rwkv_ctx *c, const uint64_t *history, const uint6
     for (uint64_t i = 0; i < n_streams * n_tokens; i++) out_tokens[i] = ho[i];
     for (uint64_t s = 0; stats && s < n_streams; s++) stats[s] = rwkv_spec_stats{hs[s].rounds, hs[s].drafted, hs[s].accepted};
     return 0;
+}
+int check_branches(uint32_t branches)
+{
+    return branches == 0 || branches > RWKV_LOOKUP_MAX_BRANCHES ? fail(RWKV_E_ARG, "branches = %u is not in 1..%u", branches, RWKV_LOOKUP_MAX_BRANCHES) : 0;
+}
+} // namespace
+
+int rwkv_decode_lookup_streams(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t n_tokens,
+                               const rwkv_lookup_params *p, uint64_t *out_tokens, rwkv_spec_stats *stats)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, history && hist_len && p && out_tokens)) return rc;
+    if (p->flags || p->reserved) return fail(RWKV_E_ARG, "flags and reserved must be 0");
+    return run_lookup_decode(c, history, hist_len, n_streams, n_tokens, p->k, p->n, 0u, out_tokens, stats);
+}
+
+int rwkv_decode_lookup_trees(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t n_tokens,
+                             const rwkv_lookup_tree_params *p, uint64_t *out_tokens, rwkv_spec_stats *stats)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, history && hist_len && p && out_tokens)) return rc;
+    if (p->flags) return fail(RWKV_E_ARG, "flags must be 0");
+    if (const int rc = check_branches(p->branches)) return rc;
+    return run_lookup_decode(c, history, hist_len, n_streams, n_tokens, p->k, p->n, p->branches, out_tokens, stats);
 }
 
 int rwkv_debug_lookup_draft(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint32_t k, uint32_t n,
@@ -3943,6 +3977,40 @@ int rwkv_debug_lookup_draft(rwkv_ctx *c, const uint64_t *history, const uint64_t
     for (uint64_t s = 0; s < n_streams; s++) {
         n_draft[s] = tab[s].n_draft;
         for (uint32_t j = 0; j < k; j++) draft[s * k + j] = j < tab[s].n_draft ? ids[s * (k + 1u) + 1u + j] : 0;
+    }
+    return 0;
+}
+
+int rwkv_debug_lookup_tree(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint32_t k, uint32_t n, uint32_t branches,
+                           uint64_t *ids, int32_t *parent, uint32_t *n_nodes)
+{
+    if (const int rc = guard(c, LAUNCHES, history && hist_len && ids && parent && n_nodes)) return rc;
+    if (const int rc = LookupRun::check(history, hist_len, n_streams, SEQ_TM, k, n)) return rc;
+    if (const int rc = check_branches(branches)) return rc;
+    LookupRun run;
+    auto enqueue = [&]() -> int {
+        if (const int rc = run.setup(c, history, hist_len, n_streams, (uint64_t)k + 1u, k, n, branches)) return rc;      // a budget of k + 1 ids: no cut
+        const LookupLayout &l = run.lay;
+        unsigned char *hb = reinterpret_cast<unsigned char *>(c->lk_host.data()), *db = c->buf<unsigned char>(LOOKUP_RUN);
+        run.ta.parent = reinterpret_cast<int *>(db + l.emitted);      // (the accepted ids' place: no round follows that would read them)
+        if (const int rc = run.round(c)) return rc;
+        HIPCHK(hipMemcpyAsync(hb + l.ids, db + l.ids, 8 * run.T, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(hb + l.tab, db + l.tab, sizeof(SpecSegEntry) * n_streams, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(hb + l.emitted, db + l.emitted, sizeof(int) * n_streams * k, hipMemcpyDeviceToHost, c->stream));
+        return 0;
+    };
+    const int rc = finish(c, enqueue());
+    if (rc) return rc;
+    const unsigned char *hb = reinterpret_cast<const unsigned char *>(c->lk_host.data());
+    const unsigned long long *di = reinterpret_cast<const unsigned long long *>(hb + run.lay.ids);
+    const SpecSegEntry *tab = reinterpret_cast<const SpecSegEntry *>(hb + run.lay.tab);
+    const int *dp = reinterpret_cast<const int *>(hb + run.lay.emitted);
+    for (uint64_t s = 0; s < n_streams; s++) {
+        n_nodes[s] = tab[s].n_draft;
+        for (uint32_t j = 0; j < k; j++) {
+            ids[s * k + j] = j < tab[s].n_draft ? di[s * (k + 1u) + 1u + j] : 0;
+            parent[s * k + j] = j < tab[s].n_draft ? dp[s * k + j] : -1;
+        }
     }
     return 0;
 }

@@ -189,6 +189,20 @@ PYBIND11_MODULE(rwkv, m)
        "behind the most recent earlier occurrence of the last `ngram` ids, verifies, commits and appends, round after round: "
        "(ids [streams][n], [(rounds, drafted, accepted)]) (engine extension)",
           py::arg("rwkvp"), py::arg("histories"), py::arg("n"), py::arg("k") = 8u, py::arg("ngram") = 3u);
+    m.def("decodeLookupTrees", [](std::uintptr_t h, const std::vector<std::vector<int64_t>> &histories, int64_t n, unsigned k, unsigned ngram, unsigned branches) {
+        if (n < 1) throw std::runtime_error("n must be at least 1");
+        std::vector<std::vector<unsigned long long>> hist;
+        for (const auto &q : histories) hist.emplace_back(q.begin(), q.end());
+        std::vector<std::vector<int64_t>> ids;
+        std::vector<std::tuple<int64_t, int64_t, int64_t>> stats;
+        for (const RWKV::SpecResult &r : M(h)->decodeLookupTrees(hist, (unsigned long long)n, k, ngram, branches)) {
+            ids.emplace_back(r.tokens.begin(), r.tokens.end());
+            stats.emplace_back((int64_t)r.rounds, (int64_t)r.drafted, (int64_t)r.accepted);
+        }
+        return py::make_tuple(ids, stats);
+    }, "decodeLookupStreams with draft trees: every round the device merges what followed the `branches` most recent occurrences of the last `ngram` "
+       "ids into a trie of at most k nodes, verifies it and keeps the path that stands: (ids [streams][n], [(rounds, drafted, accepted)]) (engine extension)",
+          py::arg("rwkvp"), py::arg("histories"), py::arg("n"), py::arg("k") = 8u, py::arg("ngram") = 3u, py::arg("branches") = 3u);
     m.def("specVerifyTrees", [](std::uintptr_t h, const std::vector<std::tuple<unsigned, std::vector<int64_t>, unsigned, std::vector<unsigned>>> &trees) {
         std::vector<RWKV::SpecTree> segs;
         for (const auto &s : trees)

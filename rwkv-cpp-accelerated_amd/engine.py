@@ -49,12 +49,14 @@ ABI_SYMBOLS = [
     "rwkv_tree_plan", "rwkv_spec_verify_trees", "rwkv_spec_sample_trees",
     "rwkv_sample_floor", "rwkv_mirostat_set", "rwkv_mirostat_get",
     "rwkv_decode_lookup_streams", "rwkv_debug_lookup_draft",
+    "rwkv_decode_lookup_trees", "rwkv_debug_lookup_tree",
     "rwkv_dry_history_set", "rwkv_dry_history_get", "rwkv_debug_dry_scan", "rwkv_decode_batch_dry",
 ]
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 SPEC_MAX_DRAFT = 31               # RWKV_SPEC_MAX_DRAFT
 LOOKUP_MAX_NGRAM, LOOKUP_MAX_HISTORY = 8, 1 << 20   # RWKV_LOOKUP_MAX_NGRAM, RWKV_LOOKUP_MAX_HISTORY
+LOOKUP_MAX_BRANCHES = 8           # RWKV_LOOKUP_MAX_BRANCHES
 DRY_MAX_WINDOW, DRY_MAX_MATCH, DRY_MAX_BREAKERS = 4096, 64, 32   # RWKV_DRY_MAX_*
 MAX_SCORE = 65536                 # RWKV_MAX_SCORE
 MAX_PICK_ROWS, PICKQ_SEED, PICK_BATCH = 1024, 1, 64   # RWKV_MAX_PICK_ROWS, RWKV_PICKQ_SEED; the queries of one launch sequence (csrc/engine.hip PQ_BATCH)
@@ -155,6 +157,11 @@ class SpecStats(C.Structure):
 class LookupParams(C.Structure):
     """rwkv_lookup_params of include/rwkv_mi355x.h (16 bytes)"""
     _fields_ = [("k", C.c_uint32), ("n", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LookupTreeParams(C.Structure):
+    """rwkv_lookup_tree_params of include/rwkv_mi355x.h (16 bytes)"""
+    _fields_ = [("k", C.c_uint32), ("n", C.c_uint32), ("branches", C.c_uint32), ("flags", C.c_uint32)]
 
 
 class Segment(C.Structure):
@@ -498,6 +505,11 @@ def lib():
     L.rwkv_decode_lookup_streams.restype = i32
     L.rwkv_debug_lookup_draft.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(C.c_uint32)]
     L.rwkv_debug_lookup_draft.restype = i32
+    L.rwkv_decode_lookup_trees.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, u64, C.POINTER(LookupTreeParams), C.POINTER(u64), C.POINTER(SpecStats)]
+    L.rwkv_decode_lookup_trees.restype = i32
+    L.rwkv_debug_lookup_tree.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), u64, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(u64), C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_uint32)]
+    L.rwkv_debug_lookup_tree.restype = i32
     L.rwkv_dry_history_set.argtypes = [vp, u64, C.POINTER(u64), u64]; L.rwkv_dry_history_set.restype = i32
     L.rwkv_dry_history_get.argtypes = [vp, u64, C.POINTER(u64), C.POINTER(u64), C.POINTER(u64)]; L.rwkv_dry_history_get.restype = i32
     L.rwkv_debug_dry_scan.argtypes = [vp, u64, C.POINTER(DryParams), u32p, u32p, u32p]; L.rwkv_debug_dry_scan.restype = i32
@@ -1176,6 +1188,16 @@ class RWKV:
         """decode_lookup_streams as ONE call: the device drafts (ngram_draft's rule), verifies, accepts, commits and appends, round after round,
         and the host only enqueues.  Stream s runs on slot s.  Returns (ids [N][n_tokens], [dict(rounds, drafted, accepted)] per stream): what
         decode_lookup_streams returns wherever its per-round `room` does not bind, i.e. N * (k + 1) rows fit one pass."""
+        return self._lookup_device(histories, n_tokens, lambda *a: lib().rwkv_decode_lookup_streams(*a), LookupParams(int(k), int(n), 0, 0))
+
+    def decode_lookup_tree_device(self, histories, n_tokens: int, k: int = 8, n: int = 3, branches: int = 3):
+        """decode_lookup_tree_streams as ONE call (rwkv_decode_lookup_trees): the device drafts the trie (ngram_draft_tree's rule), verifies,
+        accepts the path that stands, commits and appends, round after round.  Returns what decode_lookup_tree_streams returns wherever
+        N * (k + 1) rows fit one pass; with branches=1 what decode_lookup_device returns."""
+        return self._lookup_device(histories, n_tokens, lambda *a: lib().rwkv_decode_lookup_trees(*a), LookupTreeParams(int(k), int(n), int(branches), 0))
+
+    def _lookup_device(self, histories, n_tokens, call, params):
+        """the marshalling of decode_lookup_device / decode_lookup_tree_device around call(ctx, ids, lengths, N, n_tokens, params, out, stats)"""
         if not self.ready:
             raise RuntimeError("RWKV not loaded")
         ids, lens, N = self._histories(histories)
@@ -1185,7 +1207,7 @@ class RWKV:
         slots = min(self.maxContext, max(1, N))
         if not self.resident:
             self.push_state(slots)
-        _chk(lib().rwkv_decode_lookup_streams(self._h, ids, lens, N, n_tokens, C.byref(LookupParams(int(k), int(n), 0, 0)), out, st))
+        _chk(call(self._h, ids, lens, N, n_tokens, C.byref(params), out, st))
         if not self.resident:
             self.pull_state(slots)
         got = np.frombuffer(out, dtype=np.uint64)[:N * n_tokens].astype(np.int64).reshape(N, n_tokens)
@@ -1197,6 +1219,15 @@ class RWKV:
         draft, nd = (C.c_uint64 * max(1, N * int(k)))(), (C.c_uint32 * max(1, N))()
         _chk(lib().rwkv_debug_lookup_draft(self._h, ids, lens, N, int(k), int(n), draft, nd))
         return [[int(t) for t in draft[s * int(k):s * int(k) + nd[s]]] for s in range(N)]
+
+    def debug_lookup_tree(self, histories, k: int, n: int = 3, branches: int = 3):
+        """the device tree drafter alone (rwkv_debug_lookup_tree): per history the (ids, parent) ngram_draft_tree(history, k, n, branches) gives.
+        No pass, no state."""
+        hist, lens, N = self._histories(histories)
+        k = int(k)
+        ids, par, nn = (C.c_uint64 * max(1, N * k))(), (C.c_int32 * max(1, N * k))(), (C.c_uint32 * max(1, N))()
+        _chk(lib().rwkv_debug_lookup_tree(self._h, hist, lens, N, k, int(n), int(branches), ids, par, nn))
+        return [([int(t) for t in ids[s * k:s * k + nn[s]]], [int(p) for p in par[s * k:s * k + nn[s]]]) for s in range(N)]
 
     # -- draft trees for many streams (include/rwkv_mi355x.h rwkv_spec_verify_trees) ---------------------------------------------
     def spec_verify_trees(self, segments):
