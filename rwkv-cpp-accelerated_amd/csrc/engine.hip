@@ -17,7 +17,6 @@
 #include "spec.hip.h"
 #include "segments.hip.h"
 #include "specseg.hip.h"
-#include "spectree.hip.h"
 #include "pickrows.hip.h"
 #include "floor.hip.h"
 #include "lookup.hip.h"
@@ -254,17 +253,15 @@ enum GrownBuf {
     SPEC_CKPT,                        // rwkv_spec_verify (spec.hip.h): f64 [4][L][rows][D], the verify pass's checkpoints (xy | aa | bb | dd) for the largest n_draft seen
     SPEC_REC,                         // u64: {a, next} | picks [SEQ_T]
     SEG_PLAN,                         // rwkv_forward_segments (segments.hip.h): SegRow [max_ctx], the call's row plan; allocated ONCE at the first segmented call
-    SPECSEG_IO,                       // rwkv_spec_verify_segments (specseg.hip.h), SpecSegIo: the call's ONE upload (ids | plan | per-segment table), behind it the records
-                                      // and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT, grown to 4 L T D for the largest T seen
+    SPECSEG_IO,                       // rwkv_spec_verify_segments / _trees, rwkv_spec_sample_segments / _trees (specseg.hip.h), SpecSegIo: the call's ONE upload (query table |
+                                      // ids | plan | segment table | from table), behind it the records, the accepted ids and the picks; allocated ONCE at the first call.
+                                      // The checkpoints are SPEC_CKPT, grown to 4 L T D for the largest T seen
     PICKQ_IO,                         // rwkv_sample_rows (pickrows.hip.h), PickIo: the call's upload (the query table) and the ids it downloads; allocated ONCE at the
                                       // first call.  The sampler scratch is BD_PART / BD_P / BD_PW / BD_KEY, grown to min(n, PQ_BATCH) rows
-    SPECSAMPLE_IO,                    // rwkv_spec_sample_segments, SpecSampleIo: the query table in front of a SpecSegIo, so that ONE copy still carries the upload
-    SPECTREE_IO,                      // rwkv_spec_verify_trees / rwkv_spec_sample_trees (spectree.hip.h), SpecTreeIo: query table | ids | plan | segment table | from table,
-                                      // behind them the records, the accepted ids and the picks; allocated ONCE at the first call.  The checkpoints are SPEC_CKPT
     MIRO_MU,                          // f64 [max_ctx]: Mirostat's running threshold per state slot (floor.hip.h); allocated ONCE, zeroed, at the first call that needs it
-    LOOKUP_RUN,                       // rwkv_decode_lookup_streams / rwkv_debug_lookup_draft (lookup.hip.h), LookupLayout: ids | picks | records | plan | segment table | live |
-                                      // histories u32 | streams | output u32; everything in front of the output goes up in ONE copy, streams and output come down in one.
-                                      // rwkv_decode_lookup_trees / rwkv_debug_lookup_tree (lookuptree.hip.h): the from table and the accepted ids behind `live`
+    LOOKUP_RUN,                       // rwkv_decode_lookup_streams / _trees, rwkv_debug_lookup_draft / _tree (lookup.hip.h, lookuptree.hip.h), LookupLayout: ids | picks | records |
+                                      // plan | segment table | live | from table | accepted ids | histories u32 | streams | output u32; everything in front of the output goes up
+                                      // in ONE copy, streams and output come down in one
     DRY_HIST,                         // DRY penalties (dry.hip.h): u32 [max_ctx][DRY_MAX_WINDOW] the slots' id rings | u64 [max_ctx] the ids each slot was given; allocated ONCE,
                                       // emptied, at the first call that needs it
     DRY_DBG,                          // rwkv_debug_dry_scan, u32: count | id [DRY_MAX_WINDOW] | L [DRY_MAX_WINDOW]
@@ -319,10 +316,8 @@ struct rwkv_ctx {
     Ctl *ctl = nullptr;
     Ctl *h_ctl = nullptr;    // pinned staging, maxT entries
     SegRow *h_seg_plan = nullptr;   // pinned [maxT]: what rwkv_forward_segments uploads into SEG_PLAN (allocated with it)
-    struct SpecSegIo *h_specseg = nullptr;   // pinned: what rwkv_spec_verify_segments uploads into SPECSEG_IO and downloads from it (allocated with it)
+    struct SpecSegIo *h_specseg = nullptr;   // pinned twin of SPECSEG_IO: what a many-stream verify uploads into it and downloads from it (allocated with it)
     struct PickIo *h_pickq = nullptr;        // pinned twin of PICKQ_IO (allocated with it)
-    struct SpecSampleIo *h_specsample = nullptr;   // pinned twin of SPECSAMPLE_IO (allocated with it)
-    struct SpecTreeIo *h_spectree = nullptr;       // pinned twin of SPECTREE_IO (allocated with it)
     unsigned long long *gen = nullptr;
     unsigned long long *pick = nullptr;      // device: id drawn by the sampler
     double *ts_part = nullptr;               // sampler scratch (sampler.hip.h)
@@ -1106,29 +1101,27 @@ int load_common(rwkv_ctx *c, Source &src, uint64_t L, uint64_t D, uint64_t max_c
     return 0;
 }
 
-// The ROW LAYOUT of a pass: what its rows are to each other -- one of six, with what that layout needs besides the pass's rows.
+// The ROW LAYOUT of a pass: what its rows are to each other -- one of five, with what that layout needs besides the pass's rows.
 //   GPT        rwkv.cu:493-593: n tokens of one sequence on state slot 0, the token shift runs along the rows
 //   PARRALEL   rwkv.cu:236-240: n independent sequences, one token each, row t on state slot row0 + t -- the batched decode step
 //   CKPT       the verify pass of rwkv_spec_verify (spec.hip.h): GPT rows, one half, whole model, that commit NOTHING to slot 0 -- every row's state
 //              is left in `ckpt`, [4][L][n][D]
 //   SEGMENTED  segments.hip.h: the rows are pieces of sequences on slots of their own, as `plan` says ([rows]{slot, flags} on the device)
-//   SPECSEG    the verify pass of rwkv_spec_verify_segments (specseg.hip.h): SEGMENTED rows, one or two halves, whole model, that commit NOTHING to
-//              their slots -- every row's state is left in `ckpt`, [4][L][n][D]
-//   SPECTREE   the verify pass of rwkv_spec_verify_trees (spectree.hip.h): SPECSEG rows of which each starts from the row `from` names ([rows] on the
-//              device) instead of the row in front -- a segment's draft rows are a tree
+//   SPECSEG    the verify pass of rwkv_spec_verify_segments / rwkv_spec_verify_trees and of the lookup loops (specseg.hip.h): SEGMENTED rows, one or
+//              two halves, whole model, that commit NOTHING to their slots -- every row's state is left in `ckpt`, [4][L][n][D] -- and of which each
+//              starts from the row `from` names ([rows] on the device): a segment's draft rows are a tree, a chain where `from` names the row in front
 // Only GPT passes are replayed as captured graphs (enqueue_pass: its key holds a shape, no layout); the rest change from call to call and are
 // launched directly.
 struct RowLayout {
-    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED, SPECSEG, SPECTREE } kind = GPT;
+    enum Kind { GPT, PARRALEL, CKPT, SEGMENTED, SPECSEG } kind = GPT;
     double *ckpt = nullptr;
     const SegRow *plan = nullptr;
     const unsigned char *from = nullptr;
     static RowLayout of_mode(int mode) { RowLayout r; r.kind = mode == RWKV_MODE_PARRALEL ? PARRALEL : GPT; return r; }
     static RowLayout checkpoints(double *ck) { RowLayout r; r.kind = CKPT; r.ckpt = ck; return r; }
     static RowLayout segments(const SegRow *plan) { RowLayout r; r.kind = SEGMENTED; r.plan = plan; return r; }
-    static RowLayout spec_segments(const SegRow *plan, double *ck) { RowLayout r; r.kind = SPECSEG; r.plan = plan; r.ckpt = ck; return r; }
-    static RowLayout spec_trees(const SegRow *plan, const unsigned char *from, double *ck) { RowLayout r = spec_segments(plan, ck); r.kind = SPECTREE; r.from = from; return r; }
-    bool one_pass() const { return kind == CKPT || kind == SPECSEG || kind == SPECTREE; }      // the checkpoint arrays are laid out for ONE pass
+    static RowLayout spec_segments(const SegRow *plan, const unsigned char *from, double *ck) { RowLayout r; r.kind = SPECSEG; r.plan = plan; r.from = from; r.ckpt = ck; return r; }
+    bool one_pass() const { return kind == CKPT || kind == SPECSEG; }      // the checkpoint arrays are laid out for ONE pass
     bool replayed() const { return kind == GPT; }
     RowLayout from_row(uint64_t t0) const { RowLayout r = *this; if (kind == SEGMENTED) r.plan += t0; return r; }      // the layout of the pass that starts at row t0 of a call
 };
@@ -1171,10 +1164,6 @@ struct SpecSegFns {
     void (*site3)(SpecSegSiteArgs) = nullptr; void (*site2)(SpecSegSiteArgs) = nullptr; void (*wkv32)(SpecSegWkvArgs) = nullptr; void (*wkv64)(SpecSegWkvArgs) = nullptr;
 };
 SpecSegFns specseg_fns();
-struct SpecTreeFns {
-    void (*site3)(SpecTreeSiteArgs) = nullptr; void (*site2)(SpecTreeSiteArgs) = nullptr; void (*wkv32)(SpecTreeWkvArgs) = nullptr; void (*wkv64)(SpecTreeWkvArgs) = nullptr;
-};
-SpecTreeFns spectree_fns();
 int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
 {
     if (pass.buf < 0 || pass.buf >= rwkv_ctx::SPLIT_MAX) return fail(RWKV_E_ARG, "residual buffer %d out of range", pass.buf);
@@ -1194,7 +1183,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     const bool two = n > SEQ_T;
     const SeqHalf h((size_t)D);
     // What the layout means, said once.  A site with a token shift keeps its LayerNorm output for the sequence's next row: GPT in S.state (the last
-    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT, SPECSEG and SPECTREE in the checkpoint rows; SEGMENTED in
+    // row's), which the GEMM behind the site copies to slot 0 (`commits`); PARRALEL in the row's own slot; CKPT and SPECSEG in the checkpoint rows; SEGMENTED in
     // the staging rows, which the WKV and stage-1 kernels behind the GEMMs commit.  The three launch helpers below (site, wkv, stage) pick their instance.
     const RowLayout &rows = pass.rows;
     const bool commits = rows.kind == RowLayout::GPT;
@@ -1203,7 +1192,6 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
     const SeqCkptFns ckf = rows.kind == RowLayout::CKPT ? seq_ckpt_fns() : SeqCkptFns{};
     const SegFns sgf = rows.kind == RowLayout::SEGMENTED ? seg_fns() : SegFns{};
     const SpecSegFns ssf = rows.kind == RowLayout::SPECSEG ? specseg_fns() : SpecSegFns{};
-    const SpecTreeFns stf = rows.kind == RowLayout::SPECTREE ? spectree_fns() : SpecTreeFns{};
     const size_t ck_arr = (size_t)L * n * D;      // one of the four checkpoint arrays; layer l's rows start l * n * D into it
     bool tl_layer = false;     // debug timeline (rwkv_debug_timeline with RWKV_TL_CLASS = 10 + GEMM kind): the middle layer's GEMM stamps its phases
     // the records a GEMM of each kind (0 K/V/R, 1 att_out, 2 ffn k/r, 3 ffn_v) reads and the partial values it writes, in the pass's scratch set
@@ -1246,8 +1234,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
         switch (state ? rows.kind : RowLayout::GPT) {
         case RowLayout::SEGMENTED: (nv == 3 ? sgf.site3 : sgf.site2)<<<grid, block, 0, st>>>(SegSiteArgs{s, rows.plan, S.seg}); return;
         case RowLayout::CKPT: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ckf.site3 : ckf.site2)<<<grid, block, 0, st>>>(s); return;
-        case RowLayout::SPECSEG: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ssf.site3 : ssf.site2)<<<grid, block, 0, st>>>(SpecSegSiteArgs{s, rows.plan}); return;
-        case RowLayout::SPECTREE: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? stf.site3 : stf.site2)<<<grid, block, 0, st>>>(SpecTreeSiteArgs{s, rows.plan, rows.from}); return;
+        case RowLayout::SPECSEG: s.ckpt = rows.ckpt + ck_at; (nv == 3 ? ssf.site3 : ssf.site2)<<<grid, block, 0, st>>>(SpecSegSiteArgs{s, rows.plan, rows.from}); return;
         case RowLayout::PARRALEL: s.par = 1; break;
         case RowLayout::GPT: s.state_new = state ? S.state : nullptr; break;      // (and ln_out of every layout: nothing to keep)
         }
@@ -1266,11 +1253,7 @@ int enqueue_chunk(rwkv_ctx *c, const SeqPass &pass)
             return;
         case RowLayout::SPECSEG:
             wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
-            (two ? ssf.wkv64 : ssf.wkv32)<<<grid, block, 0, st>>>(SpecSegWkvArgs{wa, rows.plan});
-            return;
-        case RowLayout::SPECTREE:
-            wa.ckpt_aa = rows.ckpt + ck_arr + lo * n; wa.ckpt_bb = rows.ckpt + 2 * ck_arr + lo * n;
-            (two ? stf.wkv64 : stf.wkv32)<<<grid, block, 0, st>>>(SpecTreeWkvArgs{wa, rows.plan, rows.from});
+            (two ? ssf.wkv64 : ssf.wkv32)<<<grid, block, 0, st>>>(SpecSegWkvArgs{wa, rows.plan, rows.from});
             return;
         default: break;
         }
@@ -3493,26 +3476,26 @@ int rwkv_sample_rows(rwkv_ctx *c, const rwkv_pick_query *q, uint64_t n, uint64_t
     return rc;
 }
 
-// ---- speculative decoding for many streams (specseg.hip.h): rwkv_spec_verify_segments, rwkv_spec_sample_segments ----
+// ---- speculative decoding for many streams (specseg.hip.h): rwkv_spec_verify_segments, rwkv_spec_sample_segments, rwkv_tree_plan,
+// rwkv_spec_verify_trees, rwkv_spec_sample_trees ----
 static_assert(sizeof(rwkv_spec_segment) == 16 && sizeof(SpecSegEntry) == 16 && sizeof(SpecSegRec) == 24, "the records the header and the kernels share");
 namespace {
 SpecSegFns specseg_fns() { return SpecSegFns{k_specseg_site<3>, k_specseg_site<2>, k_specseg_wkv<SEQ_T>, k_specseg_wkv<SEQ_TM>}; }
 }
-// the device image of one call (SPECSEG_IO) and its pinned twin: `up` bytes go up in ONE copy, the records come down in one
+// the device image of one call (SPECSEG_IO) and its pinned twin.  The query table IN FRONT: a sampled call uploads from q, a greedy one from ids, either
+// way ONE contiguous copy up to `rec`; rec and the first n_segs rows of `emitted` come down in one
 struct SpecSegIo {
+    PickQ q[SEQ_TM];
     unsigned long long ids[SEQ_TM];
     SegRow plan[SEQ_TM];
     SpecSegEntry tab[SEQ_TM];
+    unsigned char from[SEQ_TM];       // the row of the pass each row starts from (specseg.hip.h)
     SpecSegRec rec[SEQ_TM];           // <- not uploaded
+    unsigned long long emitted[SEQ_TM][SPEC_MAX_DRAFT];
     unsigned long long picks[SEQ_TM];
 };
-constexpr size_t SPECSEG_UP = offsetof(SpecSegIo, rec);
-// the sampled verify's image: the query table IN FRONT, so that q | ids | plan | table is still one contiguous upload
-struct SpecSampleIo {
-    PickQ q[SEQ_TM];
-    SpecSegIo s;
-};
-// what rwkv_spec_sample_segments adds to a verify: how segment i picks, and its draws' seed and first step
+static_assert(offsetof(SpecSegIo, emitted) == offsetof(SpecSegIo, rec) + sizeof(SpecSegRec) * SEQ_TM, "records and accepted ids are one download");
+// what a sampled verify adds to a greedy one: how segment i picks, and its draws' seed and first step
 struct SpecSampleCall { const rwkv_pick *picks; const uint64_t *seeds, *step0; };
 namespace {
 // the rules of a call behind the guard, all of them before anything is launched or allocated; *T_out: the rows of the call
@@ -3542,122 +3525,9 @@ int check_spec_segments(const uint64_t *tokens, const rwkv_spec_segment *segs, u
     *T_out = T;
     return 0;
 }
-int check_verify_segments(const rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t *T_out)
-{
-    return check_spec_segments(tokens, segs, n_segs, c->maxT, (uint64_t)(c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T), T_out);
-}
-// Everything of one call but the wait: ids, plan and table up in one copy, the checkpointing segmented pass, the pick of every row, what stands per
-// segment, the commit of exactly those rows, and the records' download.  No host synchronisation in between.  Launched directly, as enqueue_verify is.
-// `sm` (nullptr: the greedy verify, every row picked by k_argmax_rows): the rows from each segment's last certain one on are picked by the segment's
-// query -- row rc + j at step step0 + j -- and the query table travels in front of the ids.  *rec: the pinned records the download fills.
-int enqueue_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T, const SpecSampleCall *sm,
-                            const SpecSegRec **rec)
-{
-    SpecSegIo *h, *d;
-    PickQ *hq = nullptr, *dq = nullptr;
-    unsigned nq = 0;
-    if (sm) {
-        if (!c->h_specsample) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specsample), sizeof(SpecSampleIo), hipHostMallocDefault));
-        if (const int rc = grow_buffer(c, SPECSAMPLE_IO, sizeof(SpecSampleIo))) return rc;
-        h = &c->h_specsample->s; d = &c->buf<SpecSampleIo>(SPECSAMPLE_IO)->s;
-        hq = c->h_specsample->q; dq = c->buf<SpecSampleIo>(SPECSAMPLE_IO)->q;
-        bool nucleus = false;
-        for (uint64_t i = 0; i < n_segs; i++) { nq += segs[i].n_draft + 1u; nucleus = nucleus || sm->picks[i].kind == RWKV_PICK_NUCLEUS; }
-        if (const int rc = grow_pickq_scratch(c, nq, nucleus)) return rc;
-    } else {
-        if (!c->h_specseg) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specseg), sizeof(SpecSegIo), hipHostMallocDefault));
-        if (const int rc = grow_buffer(c, SPECSEG_IO, sizeof(SpecSegIo))) return rc;
-        if (const int rc = grow_pick_buffers(c, RWKV_PICK_GREEDY, T)) return rc;
-        h = c->h_specseg; d = c->buf<SpecSegIo>(SPECSEG_IO);
-    }
-    if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * T * c->D)) return rc;
-    // (the pinned block is free: every call that used it has returned behind its wait)
-    uint64_t j = 0;
-    unsigned iq = 0;
-    for (uint64_t i = 0; i < n_segs; i++) {
-        for (uint32_t k = 0; k < segs[i].n; k++, j++) { h->ids[j] = tokens[j]; h->plan[j] = SegRow{segs[i].slot, k == 0 ? SEG_FIRST : 0u}; }
-        const unsigned rc = (unsigned)j - segs[i].n_draft - 1u;
-        h->tab[i] = SpecSegEntry{rc, segs[i].n_draft, segs[i].slot, 0u};
-        for (uint32_t k = 0; sm && k <= segs[i].n_draft; k++) hq[iq++] = make_pickq(sm->picks[i], true, rc + k, segs[i].slot, rc + k, true, sm->seeds[i], sm->step0[i] + k, 0.0);
-    }
-    for (; j < (uint64_t)SEQ_TM; j++) { h->ids[j] = 0; h->plan[j] = SegRow{0u, SEG_FIRST}; }
-    for (; sm && iq < (unsigned)SEQ_TM; iq++) hq[iq] = PickQ{};
-    if (sm) HIPCHK(hipMemcpyAsync(dq, hq, offsetof(SpecSampleIo, s) + SPECSEG_UP, hipMemcpyHostToDevice, c->stream));
-    else HIPCHK(hipMemcpyAsync(d, h, SPECSEG_UP, hipMemcpyHostToDevice, c->stream));
-    double *ck = c->buf<double>(SPEC_CKPT);
-    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, d->ids, RowLayout::spec_segments(d->plan, ck)};
-    if (const int rc = enqueue_chunk(c, pass)) return rc;
-    if (const int rc = sm ? enqueue_pickq(c, dq, nq, d->picks) : enqueue_argmax_rows(c, c->logits, (unsigned)T, d->picks)) return rc;
-    k_specseg_accept<64><<<dim3((unsigned)n_segs), dim3(64), 0, c->stream>>>(SpecSegAcceptArgs{d->ids, d->picks, d->tab, d->rec});
-    const SpecSegCommitArgs ca{d->rec, d->tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
-    const unsigned pairs = (unsigned)(c->L * c->D / 2);
-    k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)n_segs), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(h->rec, d->rec, sizeof(SpecSegRec) * n_segs, hipMemcpyDeviceToHost, c->stream));
-    *rec = h->rec;
-    return 0;
-}
-// a verify behind its checks: everything enqueued, the one wait, the records into the caller's arrays
-int run_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T, const SpecSampleCall *sm,
-                        uint32_t *n_accepted, uint64_t *next_token, uint64_t *row)
-{
-    const SpecSegRec *rec = nullptr;
-    const int rc = finish(c, enqueue_verify_segments(c, tokens, segs, n_segs, T, sm, &rec));
-    for (uint64_t i = 0; !rc && i < n_segs; i++) {
-        n_accepted[i] = (uint32_t)rec[i].a; next_token[i] = rec[i].next;
-        if (row) row[i] = rec[i].row;
-    }
-    return rc;
-}
-} // namespace
-
-int rwkv_spec_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags, uint32_t *n_accepted,
-                              uint64_t *next_token, uint64_t *row)
-{
-    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs && n_accepted && next_token)) return rc;
-    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
-    uint64_t T = 0;
-    if (const int rc = check_verify_segments(c, tokens, segs, n_segs, &T)) return rc;
-    return run_verify_segments(c, tokens, segs, n_segs, T, nullptr, n_accepted, next_token, row);
-}
-
-int rwkv_spec_sample_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, const rwkv_pick *picks,
-                              const uint64_t *seeds, const uint64_t *step0, uint32_t flags, uint32_t *n_accepted, uint64_t *next_token, uint64_t *row)
-{
-    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs && picks && seeds && step0 && n_accepted && next_token)) return rc;
-    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
-    uint64_t T = 0;
-    if (const int rc = check_verify_segments(c, tokens, segs, n_segs, &T)) return rc;
-    for (uint64_t i = 0; i < n_segs; i++) {
-        if (picks[i].kind != RWKV_PICK_GREEDY && picks[i].kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "segment %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, picks[i].kind);
-        if (const int rc = check_pick(picks[i])) return rc;
-        if (pick_penalty(picks[i])) return fail(RWKV_E_ARG, "segment %llu: penalties are not verified (the counts behind a row depend on how much of the draft stands)", (unsigned long long)i);
-    }
-    const SpecSampleCall sm{picks, seeds, step0};
-    return run_verify_segments(c, tokens, segs, n_segs, T, &sm, n_accepted, next_token, row);
-}
-
-// ---- draft trees for many streams (spectree.hip.h): rwkv_tree_plan, rwkv_spec_verify_trees, rwkv_spec_sample_trees ----
-namespace {
-SpecTreeFns spectree_fns() { return SpecTreeFns{k_spectree_site<3>, k_spectree_site<2>, k_spectree_wkv<SEQ_T>, k_spectree_wkv<SEQ_TM>}; }
-}
-// the device image of one call (SPECTREE_IO) and its pinned twin.  The query table in front as in SpecSampleIo: a sampled call uploads from q, a greedy
-// one from ids, either way ONE copy up to `rec`; rec and the first n_segs rows of `emitted` come down in one
-struct SpecTreeIo {
-    PickQ q[SEQ_TM];
-    unsigned long long ids[SEQ_TM];
-    SegRow plan[SEQ_TM];
-    SpecSegEntry tab[SEQ_TM];
-    unsigned char from[SEQ_TM];       // the row of the pass each row starts from (spectree.hip.h)
-    SpecSegRec rec[SEQ_TM];           // <- not uploaded
-    unsigned long long emitted[SEQ_TM][SPEC_MAX_DRAFT];
-    unsigned long long picks[SEQ_TM];
-};
-static_assert(offsetof(SpecTreeIo, emitted) == offsetof(SpecTreeIo, rec) + sizeof(SpecSegRec) * SEQ_TM, "records and accepted ids are one download");
-namespace {
-// The one validator of a tree call: the rules of rwkv_spec_verify_segments (check_spec_segments), then per segment the rules of `parent` -- and, into
-// whichever outputs are there, the row each row starts from (a first row: itself) and its depth below the segment's last certain row.  Nothing is
-// written when the call is rejected.
+// The one validator of a verify call: the rules of the segments (check_spec_segments), then per segment the rules of `parent` -- and, into whichever
+// outputs are there, the row each row starts from (a first row: itself) and its depth below the segment's last certain row.  parent == nullptr: every
+// draft is a chain, from[j] = j - 1.  Nothing is written when the call is rejected.
 int tree_plan(const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t maxT, uint64_t pass_rows,
               uint8_t *row_from, uint8_t *row_depth, uint64_t *n_rows)
 {
@@ -3670,10 +3540,10 @@ int tree_plan(const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_seg
         for (uint32_t k = 0; k < n; k++) {
             const uint64_t j = r0 + k;
             if (k <= cr) { from[j] = (uint8_t)(k == 0 ? j : j - 1); depth[j] = 0; continue; }
-            const uint32_t p = parent[j];
+            const uint32_t p = parent ? parent[j] : k - 1u;
             if (p < cr || p >= k)
                 return fail(RWKV_E_ARG, "segment %llu: parent %u of row %u must be in %u..%u (the last certain row or an earlier draft row)", (unsigned long long)i, p, k, cr, k - 1);
-            for (uint32_t q = cr + 1; q < k; q++)
+            for (uint32_t q = cr + 1; parent && q < k; q++)
                 if (parent[r0 + q] == p && tokens[r0 + q] == tokens[j])
                     return fail(RWKV_E_ARG, "segment %llu: rows %u and %u are children of row %u with the same id %llu", (unsigned long long)i, q, k, p, (unsigned long long)tokens[j]);
             from[j] = (uint8_t)(r0 + p); depth[j] = (uint8_t)(depth[r0 + p] + 1u);
@@ -3684,62 +3554,74 @@ int tree_plan(const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_seg
     if (n_rows) *n_rows = T;
     return 0;
 }
-// Everything of one tree call but the wait, as enqueue_verify_segments: ONE upload (query table | ids | plan | segment table | from table), the
-// checkpointing pass in the SPECTREE layout, the pick of every row, the path that stands per segment, the commit of its last row (k_specseg_commit as
-// it is), ONE download (records | accepted ids).  `sm`: row r0 + c + k of segment i is picked by the segment's query at step step0 + depth, the depth
-// below the last certain row -- the step at which a decode of the path would draw there.
-int enqueue_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *from, const uint8_t *depth, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t T,
-                         const SpecSampleCall *sm)
+// how a segment of a sampled verify may pick
+int check_spec_pick(uint64_t i, const rwkv_pick &pk)
+{
+    if (pk.kind != RWKV_PICK_GREEDY && pk.kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "segment %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, pk.kind);
+    if (const int rc = check_pick(pk)) return rc;
+    if (pick_penalty(pk)) return fail(RWKV_E_ARG, "segment %llu: penalties are not verified (the counts behind a row depend on how much of the draft stands)", (unsigned long long)i);
+    return 0;
+}
+// the slots of the table's segments from the checkpoint rows their records name (k_specseg_commit), behind the accept that wrote the records
+int enqueue_spec_commit(rwkv_ctx *c, const SpecSegRec *rec, const SpecSegEntry *tab, uint64_t n_segs, const double *ck, uint64_t T)
+{
+    const SpecSegCommitArgs ca{rec, tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
+    const unsigned pairs = (unsigned)(c->L * c->D / 2);
+    k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)n_segs), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// Everything of one call but the wait: ONE upload (query table | ids | plan | segment table | from table), the checkpointing segmented pass, the pick of
+// every row, the path that stands per segment, the commit of its last row, ONE download (records | accepted ids).  No host synchronisation in between.
+// Launched directly, as enqueue_verify is.  `sm` (nullptr: the greedy verify, every row picked by k_argmax_rows): the rows from each segment's last certain
+// one on are picked by the segment's query, row rc + k at step step0 + depth -- the depth below the last certain row, the step at which a decode of
+// the path would draw there (a chain: step0 + k) -- and the query table travels in front of the ids.
+int enqueue_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *from, const uint8_t *depth, const rwkv_spec_segment *segs, uint64_t n_segs,
+                            uint64_t T, const SpecSampleCall *sm)
 {
     bool nucleus = false;
     unsigned nq = 0;
     for (uint64_t i = 0; sm && i < n_segs; i++) { nq += segs[i].n_draft + 1u; nucleus = nucleus || sm->picks[i].kind == RWKV_PICK_NUCLEUS; }
-    if (!c->h_spectree) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_spectree), sizeof(SpecTreeIo), hipHostMallocDefault));
-    if (const int rc = grow_buffer(c, SPECTREE_IO, sizeof(SpecTreeIo))) return rc;
+    if (!c->h_specseg) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_specseg), sizeof(SpecSegIo), hipHostMallocDefault));
+    if (const int rc = grow_buffer(c, SPECSEG_IO, sizeof(SpecSegIo))) return rc;
     if (const int rc = sm ? grow_pickq_scratch(c, nq, nucleus) : grow_pick_buffers(c, RWKV_PICK_GREEDY, T)) return rc;
     if (const int rc = grow_buffer(c, SPEC_CKPT, sizeof(double) * 4 * c->L * T * c->D)) return rc;
     // (the pinned block is free: every call that used it has returned behind its wait)
-    SpecTreeIo *h = c->h_spectree, *d = c->buf<SpecTreeIo>(SPECTREE_IO);
+    SpecSegIo *h = c->h_specseg, *d = c->buf<SpecSegIo>(SPECSEG_IO);
     uint64_t j = 0;
     unsigned iq = 0;
     for (uint64_t i = 0; i < n_segs; i++) {
         for (uint32_t k = 0; k < segs[i].n; k++, j++) { h->ids[j] = tokens[j]; h->plan[j] = SegRow{segs[i].slot, k == 0 ? SEG_FIRST : 0u}; h->from[j] = from[j]; }
         const unsigned rc = (unsigned)j - segs[i].n_draft - 1u;
-        h->tab[i] = SpecSegEntry{rc, segs[i].n_draft, segs[i].slot, 0u};
+        h->tab[i] = SpecSegEntry{rc, segs[i].n_draft, segs[i].slot, 1u};
         for (uint32_t k = 0; sm && k <= segs[i].n_draft; k++)
             h->q[iq++] = make_pickq(sm->picks[i], true, rc + k, segs[i].slot, rc + k, true, sm->seeds[i], sm->step0[i] + depth[rc + k], 0.0);
     }
     for (; j < (uint64_t)SEQ_TM; j++) { h->ids[j] = 0; h->plan[j] = SegRow{0u, SEG_FIRST}; h->from[j] = (unsigned char)j; }
     for (; sm && iq < (unsigned)SEQ_TM; iq++) h->q[iq] = PickQ{};
-    const size_t up0 = sm ? 0 : offsetof(SpecTreeIo, ids);
-    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(d) + up0, reinterpret_cast<const char *>(h) + up0, offsetof(SpecTreeIo, rec) - up0, hipMemcpyHostToDevice, c->stream));
+    const size_t up0 = sm ? 0 : offsetof(SpecSegIo, ids);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<char *>(d) + up0, reinterpret_cast<const char *>(h) + up0, offsetof(SpecSegIo, rec) - up0, hipMemcpyHostToDevice, c->stream));
     double *ck = c->buf<double>(SPEC_CKPT);
-    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, d->ids, RowLayout::spec_trees(d->plan, d->from, ck)};
+    const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, d->ids, RowLayout::spec_segments(d->plan, d->from, ck)};
     if (const int rc = enqueue_chunk(c, pass)) return rc;
     if (const int rc = sm ? enqueue_pickq(c, d->q, nq, d->picks) : enqueue_argmax_rows(c, c->logits, (unsigned)T, d->picks)) return rc;
-    k_spectree_accept<64><<<dim3((unsigned)n_segs), dim3(64), 0, c->stream>>>(SpecTreeAcceptArgs{d->ids, d->picks, d->from, d->tab, d->rec, &d->emitted[0][0]});
-    const SpecSegCommitArgs ca{d->rec, d->tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
-    const unsigned pairs = (unsigned)(c->L * c->D / 2);
-    k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)n_segs), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
-    HIPCHK(hipGetLastError());
+    k_specseg_accept<64><<<dim3((unsigned)n_segs), dim3(64), 0, c->stream>>>(SpecSegAcceptArgs{d->ids, d->picks, d->from, d->tab, d->rec, &d->emitted[0][0]});
+    if (const int rc = enqueue_spec_commit(c, d->rec, d->tab, n_segs, ck, T)) return rc;
     HIPCHK(hipMemcpyAsync(h->rec, d->rec, sizeof(h->rec) + sizeof(h->emitted[0]) * n_segs, hipMemcpyDeviceToHost, c->stream));
     return 0;
 }
-// a tree call behind its guard: the plan (every rule, before anything is launched or allocated), everything enqueued, the one wait, the outputs
-int run_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, const SpecSampleCall *sm,
-                     uint32_t *n_accepted, uint64_t *next_token, uint64_t *row, uint64_t *emitted)
+// a verify behind its guard: the plan (every rule, before anything is launched or allocated: segments, parents, picks), everything enqueued, the one
+// wait, the outputs.  parent == nullptr: chains
+int run_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, const SpecSampleCall *sm,
+                        uint32_t *n_accepted, uint64_t *next_token, uint64_t *row, uint64_t *emitted)
 {
     uint8_t from[SEQ_TM], depth[SEQ_TM];
     uint64_t T = 0;
     if (const int rc = tree_plan(tokens, parent, segs, n_segs, c->maxT, (uint64_t)(c->seq_rows > SEQ_T ? SEQ_TM : SEQ_T), from, depth, &T)) return rc;
-    for (uint64_t i = 0; sm && i < n_segs; i++) {
-        const rwkv_pick &pk = sm->picks[i];
-        if (pk.kind != RWKV_PICK_GREEDY && pk.kind != RWKV_PICK_NUCLEUS) return fail(RWKV_E_ARG, "segment %llu: kind %d is neither greedy nor nucleus", (unsigned long long)i, pk.kind);
-        if (const int rc = check_pick(pk)) return rc;
-        if (pick_penalty(pk)) return fail(RWKV_E_ARG, "segment %llu: penalties are not verified (the counts behind a row depend on how much of the draft stands)", (unsigned long long)i);
-    }
-    const int rc = finish(c, enqueue_verify_trees(c, tokens, from, depth, segs, n_segs, T, sm));
-    const SpecTreeIo *h = c->h_spectree;
+    for (uint64_t i = 0; sm && i < n_segs; i++)
+        if (const int rc = check_spec_pick(i, sm->picks[i])) return rc;
+    const int rc = finish(c, enqueue_verify_segments(c, tokens, from, depth, segs, n_segs, T, sm));
+    const SpecSegIo *h = c->h_specseg;
     for (uint64_t i = 0; !rc && i < n_segs; i++) {
         n_accepted[i] = (uint32_t)h->rec[i].a; next_token[i] = h->rec[i].next;
         if (row) row[i] = h->rec[i].row;
@@ -3748,6 +3630,23 @@ int run_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent,
     return rc;
 }
 } // namespace
+
+int rwkv_spec_verify_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, uint32_t flags, uint32_t *n_accepted,
+                              uint64_t *next_token, uint64_t *row)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs && n_accepted && next_token)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    return run_verify_segments(c, tokens, nullptr, segs, n_segs, nullptr, n_accepted, next_token, row, nullptr);
+}
+
+int rwkv_spec_sample_segments(rwkv_ctx *c, const uint64_t *tokens, const rwkv_spec_segment *segs, uint64_t n_segs, const rwkv_pick *picks,
+                              const uint64_t *seeds, const uint64_t *step0, uint32_t flags, uint32_t *n_accepted, uint64_t *next_token, uint64_t *row)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && segs && picks && seeds && step0 && n_accepted && next_token)) return rc;
+    if (flags) return fail(RWKV_E_ARG, "flags must be 0");
+    const SpecSampleCall sm{picks, seeds, step0};
+    return run_verify_segments(c, tokens, nullptr, segs, n_segs, &sm, n_accepted, next_token, row, nullptr);
+}
 
 int rwkv_tree_plan(const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, uint64_t max_ctx, uint32_t pass_rows,
                    uint8_t *row_from, uint8_t *row_depth, uint64_t *n_rows)
@@ -3762,7 +3661,7 @@ int rwkv_spec_verify_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *p
 {
     if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && parent && segs && n_accepted && next_token)) return rc;
     if (flags) return fail(RWKV_E_ARG, "flags must be 0");
-    return run_verify_trees(c, tokens, parent, segs, n_segs, nullptr, n_accepted, next_token, row, emitted);
+    return run_verify_segments(c, tokens, parent, segs, n_segs, nullptr, n_accepted, next_token, row, emitted);
 }
 
 int rwkv_spec_sample_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *parent, const rwkv_spec_segment *segs, uint64_t n_segs, const rwkv_pick *picks,
@@ -3772,7 +3671,7 @@ int rwkv_spec_sample_trees(rwkv_ctx *c, const uint64_t *tokens, const uint8_t *p
     if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, tokens && parent && segs && picks && seeds && step0 && n_accepted && next_token)) return rc;
     if (flags) return fail(RWKV_E_ARG, "flags must be 0");
     const SpecSampleCall sm{picks, seeds, step0};
-    return run_verify_trees(c, tokens, parent, segs, n_segs, &sm, n_accepted, next_token, row, emitted);
+    return run_verify_segments(c, tokens, parent, segs, n_segs, &sm, n_accepted, next_token, row, emitted);
 }
 
 // ---- lookup decoding as one device loop (lookup.hip.h): rwkv_decode_lookup_streams, rwkv_debug_lookup_draft ----
@@ -3780,16 +3679,15 @@ static_assert(sizeof(rwkv_lookup_params) == 16 && LK_MAX_N == RWKV_LOOKUP_MAX_NG
 static_assert(sizeof(rwkv_lookup_tree_params) == 16 && LKT_MAX_B == RWKV_LOOKUP_MAX_BRANCHES, "the params of the C ABI; lookuptree.hip.h holds the header's limit");
 namespace {
 // LOOKUP_RUN in bytes for N streams, T rows, `hist` history words (the streams' capacities, each a multiple of 4) and `out` output words.  [0, out)
-// is the call's ONE upload, [st, bytes) its one download.  `tree`: behind `live` the from table (a byte per row) and the accepted ids
-// [N][SPEC_MAX_DRAFT] of lookuptree.hip.h; without it both are empty and the layout is the chain's
+// is the call's ONE upload, [st, bytes) its one download.  Behind `live` the from table (a byte per row) and the accepted ids [N][SPEC_MAX_DRAFT]
 struct LookupLayout {
     size_t ids, picks, rec, plan, tab, live, from, emitted, hist, st, out, bytes;
-    LookupLayout(uint64_t N, uint64_t T, uint64_t hist_words, uint64_t out_words, bool tree = false)
+    LookupLayout(uint64_t N, uint64_t T, uint64_t hist_words, uint64_t out_words)
     {
         const size_t rows = std::max<size_t>(T, SEQ_TM);
         ids = 0; picks = ids + 8 * rows; rec = picks + 8 * rows; plan = rec + sizeof(SpecSegRec) * N; tab = plan + sizeof(SegRow) * rows;
-        live = tab + sizeof(SpecSegEntry) * N; from = live + 8; emitted = (from + (tree ? rows : 0) + 7) / 8 * 8;
-        hist = (emitted + (tree ? 8 * SPEC_MAX_DRAFT * N : 0) + 15) / 16 * 16; st = hist + 4 * hist_words; out = st + sizeof(LookupStream) * N;
+        live = tab + sizeof(SpecSegEntry) * N; from = live + 8; emitted = (from + rows + 7) / 8 * 8;
+        hist = (emitted + 8 * SPEC_MAX_DRAFT * N + 15) / 16 * 16; st = hist + 4 * hist_words; out = st + sizeof(LookupStream) * N;
         bytes = out + 4 * ((out_words + 3) / 4 * 4);
     }
 };
@@ -3798,7 +3696,7 @@ struct LookupRun {
     LookupLayout lay{1, 1, 0, 0};
     LookupArgs a{};
     SpecSegAcceptArgs acc{};
-    LookupTreeArgs ta{};               // branches > 0: the tree form (lookuptree.hip.h) of the same run
+    LookupTreeArgs ta{};               // branches > 0: the tree form's round kernel (lookuptree.hip.h) drafts for the same run
     const SegRow *plan = nullptr;
     uint64_t N = 0, T = 0;
     // the rules the two entry points share, all of them before anything is launched or allocated
@@ -3815,21 +3713,22 @@ struct LookupRun {
         return check_ids(history, total, "token");
     }
     // buffers, the host image and its ONE upload: rows of valid ids, the constant row plan (stream s on slot s, 1 + k rows), a table of retired
-    // entries (the first round applies nothing), the histories as u32 and the streams.  branches > 0: the tree form, whose from table starts as
-    // enqueue_verify_trees leaves the rows behind T -- every row its own
+    // entries (the first round applies nothing), the from table of chains (a segment's first row itself, every other row the one in front: the
+    // chain loop never rewrites it, the tree form's round kernel writes the live segments' bytes every round), the histories as u32 and the streams.
+    // branches > 0: the tree form
     int setup(rwkv_ctx *c, const uint64_t *history, const uint64_t *hist_len, uint64_t n_streams, uint64_t grow, uint32_t k, uint32_t n, uint32_t branches = 0)
     {
         N = n_streams; T = N * (k + 1u);
         std::vector<uint64_t> off(N + 1, 0);
         for (uint64_t s = 0; s < N; s++) off[s + 1] = off[s] + (hist_len[s] + grow + 3) / 4 * 4;
-        lay = LookupLayout(N, T, off[N], N * grow, branches > 0);
+        lay = LookupLayout(N, T, off[N], N * grow);
         if (const int rc = grow_buffer(c, LOOKUP_RUN, lay.bytes)) return rc;
         c->lk_host.assign((lay.bytes + 7) / 8, 0ull);
         unsigned char *hb = reinterpret_cast<unsigned char *>(c->lk_host.data()), *db = c->buf<unsigned char>(LOOKUP_RUN);
         SegRow *hp = reinterpret_cast<SegRow *>(hb + lay.plan);
         for (uint64_t j = 0; j < std::max<uint64_t>(T, SEQ_TM); j++) hp[j] = j < T ? SegRow{(unsigned)(j / (k + 1u)), j % (k + 1u) == 0 ? SEG_FIRST : 0u} : SegRow{0u, SEG_FIRST};
         *reinterpret_cast<unsigned long long *>(hb + lay.live) = N;
-        for (size_t j = lay.from; branches > 0 && j < lay.emitted; j++) hb[j] = (unsigned char)(j - lay.from);
+        for (uint64_t j = 0; j < std::max<uint64_t>(T, SEQ_TM); j++) hb[lay.from + j] = (unsigned char)(j < T && j % (k + 1u) ? j - 1 : j);
         unsigned *hh = reinterpret_cast<unsigned *>(hb + lay.hist);
         LookupStream *hs = reinterpret_cast<LookupStream *>(hb + lay.st);
         for (uint64_t s = 0, j = 0; s < N; s++) {
@@ -3840,11 +3739,12 @@ struct LookupRun {
         a.hist = reinterpret_cast<unsigned *>(db + lay.hist); a.st = reinterpret_cast<LookupStream *>(db + lay.st);
         a.out = reinterpret_cast<unsigned *>(db + lay.out); a.live = reinterpret_cast<unsigned long long *>(db + lay.live);
         a.ids = reinterpret_cast<unsigned long long *>(db + lay.ids); a.tab = reinterpret_cast<SpecSegEntry *>(db + lay.tab);
-        a.rec = reinterpret_cast<const SpecSegRec *>(db + lay.rec);
+        a.rec = reinterpret_cast<const SpecSegRec *>(db + lay.rec); a.emitted = reinterpret_cast<const unsigned long long *>(db + lay.emitted);
         a.n_tokens = (unsigned)grow; a.k = k; a.n = n;
-        acc = SpecSegAcceptArgs{a.ids, reinterpret_cast<const unsigned long long *>(db + lay.picks), a.tab, reinterpret_cast<SpecSegRec *>(db + lay.rec)};
+        acc = SpecSegAcceptArgs{a.ids, reinterpret_cast<const unsigned long long *>(db + lay.picks), db + lay.from, a.tab, reinterpret_cast<SpecSegRec *>(db + lay.rec),
+                                reinterpret_cast<unsigned long long *>(db + lay.emitted)};
         plan = reinterpret_cast<const SegRow *>(db + lay.plan);
-        ta = LookupTreeArgs{a, db + lay.from, reinterpret_cast<const unsigned long long *>(db + lay.emitted), nullptr, branches};
+        ta = LookupTreeArgs{a, db + lay.from, nullptr, branches};
         return 0;
     }
     // apply the records of the round in front (none: nothing), draft the next round's rows
@@ -3860,16 +3760,11 @@ struct LookupRun {
     int verify(rwkv_ctx *c) const
     {
         double *ck = c->buf<double>(SPEC_CKPT);
-        const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, a.ids, ta.branches ? RowLayout::spec_trees(plan, ta.from, ck) : RowLayout::spec_segments(plan, ck)};
+        const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, (int)T, 0, a.ids, RowLayout::spec_segments(plan, acc.from, ck)};
         if (const int rc = enqueue_chunk(c, pass)) return rc;
         if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)T, const_cast<unsigned long long *>(acc.pick))) return rc;
-        if (ta.branches) k_lookup_tree_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(SpecTreeAcceptArgs{a.ids, acc.pick, ta.from, a.tab, acc.rec, const_cast<unsigned long long *>(ta.emitted)});
-        else k_lookup_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(acc);
-        const SpecSegCommitArgs ca{acc.rec, a.tab, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)T};
-        const unsigned pairs = (unsigned)(c->L * c->D / 2);
-        k_specseg_commit<SPEC_COMMIT_NT><<<dim3((pairs + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT, (unsigned)N), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
-        HIPCHK(hipGetLastError());
-        return 0;
+        k_specseg_accept<64><<<dim3((unsigned)N), dim3(64), 0, c->stream>>>(acc);
+        return enqueue_spec_commit(c, acc.rec, a.tab, N, ck, T);
     }
     // All rounds of a call.  A round emits at most k + 1 ids per stream, so the first ceil(n_tokens / (k + 1)) rounds are needed whatever the
     // drafts are worth and are enqueued blind.  From then on the live count travels into the pinned poll word behind every round kernel and the
@@ -4029,8 +3924,6 @@ void rwkv_free(rwkv_ctx *c)
     if (c->h_seg_plan) (void)hipHostFree(c->h_seg_plan);
     if (c->h_specseg) (void)hipHostFree(c->h_specseg);
     if (c->h_pickq) (void)hipHostFree(c->h_pickq);
-    if (c->h_specsample) (void)hipHostFree(c->h_specsample);
-    if (c->h_spectree) (void)hipHostFree(c->h_spectree);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);

@@ -1,16 +1,16 @@
-// lookup.hip.h -- prompt-lookup speculative decoding as ONE device loop (gfx950, wave64): the drafter, the bookkeeping of a round and the accept
-// that knows a retired stream.  include/rwkv_mi355x.h rwkv_decode_lookup_streams has the contract.  No reference counterpart.
+// lookup.hip.h -- prompt-lookup speculative decoding as ONE device loop (gfx950, wave64): the drafter and the bookkeeping of a round.
+// include/rwkv_mi355x.h rwkv_decode_lookup_streams has the contract.  No reference counterpart.
 //
-// A round of the loop is: k_lookup_round, the checkpointing segmented pass (specseg.hip.h, unchanged), the row picks, k_lookup_accept,
+// A round of the loop is: k_lookup_round, the checkpointing segmented pass (specseg.hip.h, unchanged), the row picks, k_specseg_accept,
 // k_specseg_commit.  Nothing is uploaded between rounds: the round kernel PRODUCES what the pass reads (the ids of the rows, the segment table) and
 // CONSUMES what the accept leaves (the records).  The launch shape never changes: N segments of 1 + k rows, stream s on slot s, rows s (k + 1) ..
-//     k_lookup_round<NT, W>   one workgroup per stream.  APPLY the previous round's record: the accepted ids and `next` go behind the stream's history
-//                             and into its output row, its budget and counters move, a stream that has its ids RETIRES (table entry live = 0, the
-//                             count of live streams falls).  Then DRAFT: the up to kd = min(k, remaining - 1) ids behind the MOST RECENT earlier
+//     k_lookup_round<NT, W>   one workgroup per stream.  APPLY the previous round's record (lookup_apply, which the tree form's round kernel shares): the
+//                             accepted ids emitted[s][0 .. a - 1] and `next` go behind the stream's history and into its output row, its budget and
+//                             counters move, a stream that has its ids RETIRES (table entry live = 0, the count of live streams falls: the accept
+//                             gives such an entry a record that names no row, so the commit leaves its slot as it stood).  Then DRAFT: the up to kd = min(k, remaining - 1) ids behind the MOST RECENT earlier
 //                             occurrence of the history's last n ids (engine.ngram_draft's rule, exactly), written as the segment's rows
-//                             [id to feed, draft, padding] and its SpecSegEntry with the true n_draft.
-//     k_lookup_accept<64>     k_specseg_accept for a table with retired entries: their record names no row of the pass, so k_specseg_commit leaves
-//                             the slot bit for bit as it stood and the next k_lookup_round applies nothing.
+//                             [id to feed, draft, padding] and its SpecSegEntry with the true n_draft.  The rows' `from` bytes never change -- row
+//                             s (k + 1) itself, every other row the one in front -- and are the host's, written once.
 // THE SEARCH.  Candidate starts are 0 .. len - n - 1 (something follows the occurrence; it may overlap the tail).  They are walked BACKWARDS in windows
 // of W starts, aligned to W so that every load is 16 bytes wide and aligned: a window's W + 8 ids (the halo: n - 1 <= 7 ids of the next window, which
 // a match that straddles the boundary reads) are staged in LDS by uint4 loads, and the NEXT window's loads are issued before the current one is
@@ -41,10 +41,33 @@ struct LookupArgs {
     unsigned *out;                     // [N][n_tokens] what the streams emitted
     unsigned long long *live;          // the streams that still lack ids
     unsigned long long *ids;           // [N (k + 1)] the rows of the pass
-    SpecSegEntry *tab;                 // [N] the pass's segment table; `pad` = 1: the segment's stream was live when the entry was written
+    SpecSegEntry *tab;                 // [N] the pass's segment table; live = 1: the segment's stream was live when the entry was written
     const SpecSegRec *rec;             // [N] what the accept left of the previous round
+    const unsigned long long *emitted; // [N][SPEC_MAX_DRAFT] the accepted ids of the previous round, in path order
     unsigned n_tokens, k, n;
 };
+
+// APPLY, the first phase of both round kernels (every thread of the workgroup calls it): what the previous round's accept left for stream s goes
+// into st, behind its history h and into its output row -- nothing in front of the first round, nothing for a retired stream
+__device__ __forceinline__ void lookup_apply(const LookupArgs &g, unsigned s, unsigned tid, const SpecSegEntry &prev, LookupStream &st, unsigned *h)
+{
+    if (!prev.live) return;
+    const SpecSegRec rec = g.rec[s];
+    const unsigned a = (unsigned)rec.a;
+    if (a < st.remain && a <= SPEC_MAX_DRAFT && st.len + a + 1u <= st.cap) {      // (always: a <= the draft's depth <= remaining - 1, and cap >= hist_len + n_tokens)
+        if (tid <= a) {
+            const unsigned id = tid < a ? (unsigned)g.emitted[(size_t)s * SPEC_MAX_DRAFT + tid] : (unsigned)rec.next;
+            h[st.len + tid] = id;
+            g.out[(size_t)s * g.n_tokens + (g.n_tokens - st.remain) + tid] = id;
+        }
+        st.len += a + 1u; st.remain -= a + 1u; st.rounds += 1u; st.drafted += prev.n_draft; st.accepted += a;
+    } else st.remain = 0u;
+    __syncthreads();          // every thread has read g.st[s]; the appended ids are visible to the search
+    if (tid == 0) {
+        g.st[s] = st;
+        if (st.remain == 0u) atomicAdd(g.live, ~0ull);
+    }
+}
 
 template <int NT, int W>
 __global__ __launch_bounds__(NT) void k_lookup_round(const LookupArgs g)
@@ -59,24 +82,7 @@ __global__ __launch_bounds__(NT) void k_lookup_round(const LookupArgs g)
     const SpecSegEntry prev = g.tab[s];
     unsigned *h = g.hist + st.off;
 
-    // ---- apply: what the previous round's accept left for this stream (nothing in front of the first round, nothing for a retired stream)
-    if (prev.pad) {
-        const SpecSegRec rec = g.rec[s];
-        const unsigned a = (unsigned)rec.a;
-        if (a < st.remain && st.len + a + 1u <= st.cap) {          // (always: a <= n_draft <= remaining - 1, and cap >= hist_len + n_tokens)
-            if (tid <= a) {
-                const unsigned id = tid < a ? (unsigned)g.ids[r0 + 1u + tid] : (unsigned)rec.next;
-                h[st.len + tid] = id;
-                g.out[(size_t)s * g.n_tokens + (g.n_tokens - st.remain) + tid] = id;
-            }
-            st.len += a + 1u; st.remain -= a + 1u; st.rounds += 1u; st.drafted += prev.n_draft; st.accepted += a;
-        } else st.remain = 0u;
-        __syncthreads();          // every thread has read g.st[s] and the old rows; the appended ids are visible to the search
-        if (tid == 0) {
-            g.st[s] = st;
-            if (st.remain == 0u) atomicAdd(g.live, ~0ull);
-        }
-    }
+    lookup_apply(g, s, tid, prev, st, h);
 
     // ---- draft: the most recent earlier occurrence of the last n ids
     const bool live = st.remain > 0u;
@@ -126,22 +132,6 @@ __global__ __launch_bounds__(NT) void k_lookup_round(const LookupArgs g)
     const unsigned nd = best >= 0 ? min(kd, st.len - ((unsigned)best + n)) : 0u;
     if (live && tid <= g.k) g.ids[r0 + tid] = tid == 0u ? h[st.len - 1u] : tid <= nd ? h[(unsigned)best + n + tid - 1u] : 0ull;
     if (tid == 0) g.tab[s] = SpecSegEntry{r0, nd, s, live ? 1u : 0u};
-}
-
-// k_specseg_accept over a table with retired entries (pad == 0): their record's row is no row of any pass, which k_specseg_commit skips
-template <unsigned NT> __global__ __launch_bounds__(NT) void k_lookup_accept(const SpecSegAcceptArgs g)
-{
-    static_assert(NT == 64 && SPEC_MAX_DRAFT < NT, "one wave, one lane per draft id");
-    const SpecSegEntry e = g.tab[blockIdx.x];
-    const unsigned j = threadIdx.x;
-    if (!e.pad) {
-        if (j == 0) g.rec[blockIdx.x] = SpecSegRec{0ull, 0ull, ~0ull};
-        return;
-    }
-    const bool miss = j >= e.n_draft || g.ids[e.rc + 1 + j] != g.pick[e.rc + j];
-    const unsigned long long m = __ballot(miss);
-    const unsigned acc = (unsigned)__ffsll((long long)m) - 1u;
-    if (j == acc) g.rec[blockIdx.x] = SpecSegRec{acc, g.pick[e.rc + acc], e.rc + acc};
 }
 
 } // namespace rwkvk

@@ -1,11 +1,10 @@
 // lookuptree.hip.h -- prompt-lookup decoding with DRAFT TREES as ONE device loop (gfx950, wave64): lookup.hip.h's loop with a drafter that keeps the
-// `branches` most recent occurrences of the tail and merges what follows them into a trie, verified in the SPECTREE layout of spectree.hip.h.
+// `branches` most recent occurrences of the tail and merges what follows them into a trie, verified by the same pass with a parent per row.
 // include/rwkv_mi355x.h rwkv_decode_lookup_trees has the contract.  No reference counterpart.
 //
-// A round is: k_lookup_tree_round, the checkpointing pass with a parent per row (spectree.hip.h, unchanged), the row picks, k_lookup_tree_accept,
-// k_specseg_commit.  As in lookup.hip.h nothing is uploaded between rounds and the launch shape never changes: N segments of 1 + k rows.
+// A round is: k_lookup_tree_round, the checkpointing segmented pass (specseg.hip.h, unchanged), the row picks, k_specseg_accept, k_specseg_commit.  As in lookup.hip.h nothing is uploaded between rounds and the launch shape never changes: N segments of 1 + k rows.
 //     k_lookup_tree_round<NT, W>  one workgroup per stream, four phases.
-//         APPLY   k_lookup_round's apply; the accepted ids are not consecutive rows of the pass, they come from the accept's emitted[s][0 .. a - 1].
+//         APPLY   lookup_apply (lookup.hip.h).
 //         SEARCH  k_lookup_round's backward walk over windows of W starts (16-byte loads, a halo of 8 ids, the next window prefetched into registers),
 //                 keeping the `branches` MOST RECENT matches.  Thread tid tests start p = i NT + tid at iteration i, so a wave's ballot IS word p / 64
 //                 of the window's match bitmap: the four waves leave 16 words each in a 64-word LDS bitmap, no early exit inside a window.  Wave 0
@@ -22,11 +21,9 @@
 //                 only the first min(k, remaining - 1) levels yields.  nd = the nodes those levels made.
 //         WRITE   the segment's rows [id to feed, nd nodes, padding with id 0], their `from` bytes (the root for a node without a parent and for
 //                 padding, else the parent's row) and the SpecSegEntry with the true n_draft.  A retired stream's rows and bytes stay as they are.
-//     k_lookup_tree_accept<64>    k_spectree_accept over a table with retired entries (pad == 0): their record names no row, as k_lookup_accept's.
 // Plain C++ and vector memory operations only; the one atomic is a vector atomic on the live count.  Nothing here writes host memory or waits.
 #pragma once
 #include "lookup.hip.h"
-#include "spectree.hip.h"
 
 namespace rwkvk {
 
@@ -35,8 +32,7 @@ constexpr unsigned LKT_ROW = 32;                  // words of a staged continuat
 
 struct LookupTreeArgs {
     LookupArgs l;                          // as k_lookup_round reads it
-    unsigned char *from;                   // [rows of the pass] the row each row starts from (spectree.hip.h)
-    const unsigned long long *emitted;     // [N][SPEC_MAX_DRAFT] the accepted ids of the previous round, in path order
+    unsigned char *from;                   // [rows of the pass] the row each row starts from (specseg.hip.h)
     int *parent;                           // the drafter alone: [N][k] the nodes' parents (-1: the root) INSTEAD of the from bytes, whose rows need
                                            // not fit a byte there; nullptr in the loop
     unsigned branches;
@@ -60,24 +56,7 @@ __global__ __launch_bounds__(NT) void k_lookup_tree_round(const LookupTreeArgs t
     const SpecSegEntry prev = g.tab[s];
     unsigned *h = g.hist + st.off;
 
-    // ---- apply: what the previous round's accept left for this stream (nothing in front of the first round, nothing for a retired stream)
-    if (prev.pad) {
-        const SpecSegRec rec = g.rec[s];
-        const unsigned a = (unsigned)rec.a;
-        if (a < st.remain && a <= SPEC_MAX_DRAFT && st.len + a + 1u <= st.cap) {      // (always: a <= the tree's depth <= remaining - 1, and cap >= hist_len + n_tokens)
-            if (tid <= a) {
-                const unsigned id = tid < a ? (unsigned)t.emitted[(size_t)s * SPEC_MAX_DRAFT + tid] : (unsigned)rec.next;
-                h[st.len + tid] = id;
-                g.out[(size_t)s * g.n_tokens + (g.n_tokens - st.remain) + tid] = id;
-            }
-            st.len += a + 1u; st.remain -= a + 1u; st.rounds += 1u; st.drafted += prev.n_draft; st.accepted += a;
-        } else st.remain = 0u;
-        __syncthreads();          // every thread has read g.st[s]; the appended ids are visible to the search
-        if (tid == 0) {
-            g.st[s] = st;
-            if (st.remain == 0u) atomicAdd(g.live, ~0ull);
-        }
-    }
+    lookup_apply(g, s, tid, prev, st, h);
 
     // ---- search: the B most recent earlier occurrences of the last n ids, most recent first
     const bool live = st.remain > 0u;
@@ -187,33 +166,6 @@ __global__ __launch_bounds__(NT) void k_lookup_tree_round(const LookupTreeArgs t
         else t.from[r0 + tid] = (unsigned char)(par < 0 ? r0 : r0 + 1u + (unsigned)par);
     }
     if (tid == 0) g.tab[s] = SpecSegEntry{r0, nd, s, live ? 1u : 0u};
-}
-
-// k_spectree_accept over a table with retired entries (pad == 0): their record's row is no row of any pass, which k_specseg_commit skips
-template <unsigned NT> __global__ __launch_bounds__(NT) void k_lookup_tree_accept(const SpecTreeAcceptArgs g)
-{
-    static_assert(NT == 64 && SPEC_MAX_DRAFT < NT, "one wave, one lane per draft row");
-    const SpecSegEntry e = g.tab[blockIdx.x];
-    const unsigned j = threadIdx.x;
-    if (!e.pad) {
-        if (j == 0) g.rec[blockIdx.x] = SpecSegRec{0ull, 0ull, ~0ull};
-        return;
-    }
-    const bool draft = j < e.n_draft;
-    const unsigned r = draft ? e.rc + 1u + j : e.rc;                          // (the lanes behind the tree look at the root and never stand)
-    const unsigned p = draft ? min(max((unsigned)g.from[r], e.rc), r - 1u) : e.rc;
-    const unsigned long long id = g.ids[r];
-    const bool conf = draft && id == g.pick[p];
-    unsigned long long stand = 0ull;
-    for (unsigned k = 0; k <= SPEC_MAX_DRAFT; k++) {
-        const unsigned long long s = __ballot(conf && (p == e.rc || ((stand >> (p - e.rc - 1u)) & 1ull) != 0ull));
-        if (s == stand) break;
-        stand = s;
-    }
-    const unsigned acc = (unsigned)__popcll(stand);
-    const unsigned row = stand ? e.rc + 64u - (unsigned)__clzll((long long)stand) : e.rc;
-    if ((stand >> j) & 1ull) g.emitted[(size_t)blockIdx.x * SPEC_MAX_DRAFT + __popcll(stand & ((1ull << j) - 1ull))] = id;
-    if (j == 0) g.rec[blockIdx.x] = SpecSegRec{acc, g.pick[row], row};
 }
 
 } // namespace rwkvk

@@ -318,7 +318,7 @@ __device__ __forceinline__ void seq_row_stats2(const SeqStat *stat, int t, int t
 // LayerNorm output of channel j where the layout keeps it.  `keep` is a functor, resolved where the kernel is compiled: no instance carries
 // another layout's branches.
 // seq_site_row_from: the same with the shift input's row named -- `tp`, the row of the pass whose residual stream `xprow` is (read where lnprev).
-// In every layout but a draft tree's (spectree.hip.h) that is the row in front, which is what seq_site_row says.
+// In every layout but the speculative verify's (specseg.hip.h) that is the row in front, which is what seq_site_row says.
 template <int NV, class Keep>
 __device__ __forceinline__ void seq_site_row_from(const SeqSiteArgs &a, int t, int tp, int o, bool shift, bool lnprev, const double *xprow, Keep keep, double *red)
 {

@@ -1,4 +1,4 @@
-"""Draft trees for many streams on the device (include/rwkv_mi355x.h rwkv_spec_verify_trees, csrc/spectree.hip.h).  The greedy continuation of
+"""Draft trees for many streams on the device (include/rwkv_mi355x.h rwkv_spec_verify_trees, csrc/specseg.hip.h).  The greedy continuation of
 every segment is built with rwkv_forward_segments alone, one id at a time; what a tree verify leaves -- records, accepted ids, slot state, the
 logits rows of the certain rows and of the path -- is held bit for bit to rwkv_forward_segments of the certain and accepted ids, alone, from the
 same start; a chain is held bit for bit to rwkv_spec_verify_segments.  One case is held to the f64 oracle within the chunk suite's bounds.
@@ -79,6 +79,10 @@ def models(eng):
 @pytest.mark.parametrize("name", list(cs.LAYOUTS))
 @pytest.mark.parametrize("L,D", WIDTHS)
 def test_a_chain_is_the_segmented_verify(eng, models, L, D, name):
+    """rwkv_spec_verify_segments and rwkv_spec_verify_trees on a chain are two entry points over ONE path (the chain call passes no parents and plans
+    from[t] = t - 1 itself): this holds the host plumbing of both to each other.  The path's independent anchors: tests/test_specseg_gpu.py holds the
+    verify bit for bit to rwkv_forward_segments alone and to rwkv_spec_verify, and to the f64 oracle; test_planted_trees and
+    test_against_the_statement_over_the_oracle cover the trees."""
     w, lay = models(L, D), cs.LAYOUTS[name]
     g = w.greedy([(slot, cs.certain(slot, n - nd)) for slot, n, nd, _ in lay], 1 + max(nd for _, _, nd, _ in lay))
     segs, want = cs.plant(lay, [gi[:nd + 1] for gi, (_, _, nd, _) in zip(g, lay)])
