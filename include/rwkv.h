@@ -464,6 +464,21 @@ public:
         pull_slot0(); draft_model.pull_slot0();
         return SpecResult{std::vector<unsigned long long>(ids.begin(), ids.end()), st.rounds, st.drafted, st.accepted};
     }
+    // decodeSpeculative with a draft model that SAMPLES (rwkv_mi355x.h "speculative SAMPLING with a draft model that samples"): the draft draws at
+    // temp_draft, this model accepts by the ratio rule at temp_target, and every id is distributed as this model's own sampling at temp_target.
+    // To chain: seed + 2 n and draft_seed + the `drafted` of the result.
+    SpecResult decodeSpeculativeSampled(RWKV &draft_model, unsigned long long first, unsigned long long n, unsigned k = 4, float temp_target = 1.0f,
+                                        float temp_draft = 1.0f, unsigned long long seed = 0, unsigned long long draft_seed = 0)
+    {
+        if (!ready || !draft_model.ready) throw std::runtime_error("RWKV not loaded");
+        std::vector<uint64_t> ids(n);
+        rwkv_spec_stats st{0, 0, 0};
+        const rwkv_ratio_params p{temp_target, temp_draft, 0, 0};
+        push_slot0(); draft_model.push_slot0();
+        rwkv_detail::check(rwkv_decode_speculative_sampled(ctx_, draft_model.ctx_, first, n, k, &p, seed, draft_seed, ids.data(), &st));
+        pull_slot0(); draft_model.pull_slot0();
+        return SpecResult{std::vector<unsigned long long>(ids.begin(), ids.end()), st.rounds, st.drafted, st.accepted};
+    }
     // speculative greedy decoding for many streams (rwkv_mi355x.h "speculative greedy decoding for many streams"): the last n_draft ids of a segment
     // are guesses; ONE pass of the chunk path verifies all segments and each slot is left after the ids that stand.  Per segment: the number of
     // draft ids kept, the id that follows them (emitted, not fed) and the logits row it was picked from.  All rows fit one pass (64).

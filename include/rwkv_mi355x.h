@@ -578,8 +578,9 @@ int rwkv_decode_batch_constrained(rwkv_ctx *ctx, const uint64_t *first_tokens, u
  * device or with max_ctx < k + 2, ctx with max_ctx < k + 1, n_tokens == 0 or above RWKV_MAX_DECODE_STEPS; RWKV_E_STATE for a draft context that is
  * not loaded or is a pipeline stage.
  * More than one stream: rwkv_spec_verify_segments below verifies the drafts of many streams in one pass.
- * Out of scope: a draft model that samples (rejection sampling then needs the draft's probabilities; sampled acceptance of a deterministic
- * draft is rwkv_spec_sample_segments), draft trees, pipeline contexts, drafts longer than one
+ * A draft model that SAMPLES is rwkv_decode_speculative_sampled below (the ratio rule over the draft's own logits); sampled acceptance of a
+ * deterministic draft is rwkv_spec_sample_segments.
+ * Out of scope: draft trees, pipeline contexts, drafts longer than one
  * half. */
 #define RWKV_SPEC_MAX_DRAFT 31u
 int rwkv_spec_verify(rwkv_ctx *ctx, uint64_t token, const uint64_t *draft, uint64_t n_draft, uint64_t *n_accepted, uint64_t *next_token);
@@ -588,6 +589,65 @@ typedef struct rwkv_spec_stats {
 } rwkv_spec_stats;
 int rwkv_decode_speculative(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_token, uint64_t n_tokens, uint32_t k, uint64_t *out_tokens,
                             rwkv_spec_stats *stats /* may be NULL */);
+
+/* ---- speculative SAMPLING with a draft model that samples: the ratio rule on the device (no reference counterpart) ----
+ * A draft model that samples proposes id x from its own distribution q.  The target, with distribution p, accepts x with probability
+ * min(1, p(x) / q(x)) and otherwise draws from the normalised max(p - q, 0): the emitted id is then distributed exactly as p, whatever q is.
+ * The pick reads TWO logits rows -- l, a row of ctx's logits buffer, and m, the draft model's row that x was drawn from, anywhere in device
+ * memory -- and nothing leaves the device (csrc/ratio.hip.h: one launch, one workgroup per row).
+ * THE RULE, for one row, temperatures Tt = temp_target and Td = temp_draft, uniforms u_a and u_r in [0, 1).  Id 0 is banned on both sides, as in
+ * every device loop.  Everything is f64, in log space; it = 1 / (double)Tt (exactly 1 for Tt == 1), likewise id from Td:
+ *     s_i = (double)l_i * it,  M = max over i >= 1 of s_i,  Z = sum over i >= 1 of exp(s_i - M),  lp(i) = (s_i - M) - log Z;   lq(i) from m and id alike
+ *     accept  iff 1 <= x and log(u_a) < lp(x) - lq(x) (u_a == 0 always accepts); the pick is x.  A draft id 0 -- an id neither side can emit -- is rejected
+ *     reject  r(i) = max(exp(lp(i)) - exp(lq(i)), 0) for i >= 1, r(x) = 0, r(0) = 0; R = sum of r; the pick is the smallest i with
+ *             sum over i' <= i of r(i') > u_r R: an inverse CDF in id order.  If R == 0 in f64 (both rows so peaked on x that all else underflows)
+ *             the pick is the id with the largest l_i among the ids other than 0 and x, ties to the lowest id
+ *     bonus   a row without a draft id (UINT64_MAX: the row behind a draft that stands entirely): q = 0 and no accept test, a draw from p in id order
+ * So a pick equals x exactly when x was accepted, and is never 0.  With NaN or +inf logits the pick is unspecified but below 50277, and nothing
+ * faults.  include/rwkv_sampler.h ratio_u is the same rule on the host.
+ * faults.  Held pick by pick to an f64 numpy restatement on planted rows by tests/test_spec_ratio_gpu.py; the sums are f64 in another order than
+ * numpy's, so a draw whose u_r R lies within 1e-12 R of a step of the cumulative sum may go to the neighbouring id.
+ *
+ * rwkv_spec_ratio_rows is the pick alone: row i of the call reads logits row rows[i] of ctx (left by the LAST forward; rows need not be distinct)
+ * and row i of q_logits, a DEVICE array [n][50277] f32 (rwkv_logits_device of a draft context serves; the call cannot check the pointer), with draft
+ * id draft[i] and the uniforms u_accept[i], u_draw[i]; picks[i] and accepted[i] (1 / 0, may be NULL) are host arrays.  n is 1 .. 32.  q_logits may
+ * be NULL when every draft id is UINT64_MAX.  One upload, one launch, one download; synchronous; state and logits are left alone.
+ *
+ * rwkv_spec_verify_ratio is rwkv_spec_verify with this pick in place of the greedy one: the same pass over [token, draft ..], the same checkpoints,
+ * and -- because a pick equals the draft id exactly when it accepts -- the same accept and commit kernels behind it.  Row j is judged against row j
+ * of q_logits ([n_draft][50277], device) and is step step0 + j; row n_draft is the bonus row.  The output id of absolute step s uses
+ * u_a = uniform(splitmix64(seed + 2 s)) and u_r = uniform(splitmix64(seed + 2 s + 1)), the generator of the other loops.  *n_accepted = a, *next_token
+ * the pick of row a; a + 1 ids were emitted, so the caller's next step0 is step0 + a + 1.  What rwkv_spec_verify guarantees holds here too: slot 0
+ * and logits rows 0 .. a are bit for bit those of rwkv_forward of the accepted rows, and the result does not depend on the draft ids behind the
+ * first rejected one nor on their rows of q_logits.
+ *
+ * rwkv_decode_speculative_sampled is the loop of rwkv_decode_speculative with a draft model that samples: the same preconditions, the same chaining
+ * of the two contexts, the same stats.  Per round, with k' = min(k, remaining - 1), the draft model runs k' + 1 steps on its slot 0 and copies slot 0
+ * into slot i + 1 behind step i; behind the forward of step i < k' its logits row 0 is copied, device to device, into row i of a stash on the draft
+ * context ([k][50277] f32, allocated at the first call, counted by rwkv_resident_bytes) and draft id i is drawn from that row by the nucleus sampler
+ * at temp_draft with top_p = 1, top_k = 0, no penalty, logit 0 banned, and u = uniform(splitmix64(draft_seed + d)), d counting the draft's draws of
+ * the call from 0 (the last step of a round draws nothing; d is never used twice).  The target verifies with the stash as q_logits, seed and
+ * step0 = the ids emitted so far; the draft's slot 0 comes back from slot a + 1.  At most two host synchronisations per round; no logits leave the
+ * device.  At the end the logits row the last id was picked from is copied to row 0.  Every emitted id is distributed as the target's
+ * softmax(l / Tt) without id 0.  To chain, the next call takes seed + 2 n_tokens and draft_seed + stats.drafted; it continues the ids one longer
+ * call gives whenever the last round of this call was not cut short by n_tokens (k' == k), and an equally valid draw otherwise.
+ * Status: as rwkv_spec_verify / rwkv_decode_speculative, and RWKV_E_ARG for a temperature that is not > 0 (NaN included), flags or reserved != 0,
+ * u outside [0, 1), n outside 1 .. 32, a row >= max_ctx, a NULL q_logits with a draft id, a draft id >= 50277 other than UINT64_MAX.  Every check
+ * runs before any launch or allocation: a rejected call leaves state, logits and buffers as they were.
+ * Out of scope: top-p / top-k truncation or penalties on either side of the rule, many streams or trees with a sampling draft model, pipeline contexts. */
+typedef struct rwkv_ratio_params {
+    float temp_target, temp_draft;
+    uint32_t flags;    /* must be 0 */
+    uint32_t reserved; /* must be 0 */
+} rwkv_ratio_params;
+int rwkv_spec_ratio_rows(rwkv_ctx *ctx, const uint64_t *rows /* [n] */, const float *q_logits /* DEVICE [n][50277], may be NULL */,
+                         const uint64_t *draft /* [n], UINT64_MAX: bonus row */, uint64_t n, const rwkv_ratio_params *params,
+                         const double *u_accept /* [n] */, const double *u_draw /* [n] */, uint64_t *picks /* [n] */, uint8_t *accepted /* [n], may be NULL */);
+int rwkv_spec_verify_ratio(rwkv_ctx *ctx, uint64_t token, const uint64_t *draft, uint64_t n_draft, const float *q_logits /* DEVICE [n_draft][50277] */,
+                           const rwkv_ratio_params *params, uint64_t seed, uint64_t step0, uint64_t *n_accepted, uint64_t *next_token);
+int rwkv_decode_speculative_sampled(rwkv_ctx *ctx, rwkv_ctx *draft_ctx, uint64_t first_token, uint64_t n_tokens, uint32_t k,
+                                    const rwkv_ratio_params *params, uint64_t seed, uint64_t draft_seed, uint64_t *out_tokens,
+                                    rwkv_spec_stats *stats /* may be NULL */);
 
 /* ---- segmented forward: many sequences of any length behind one read of the weights (no reference counterpart: the reference has the two ends) ----
  * The rows of a call are SEGMENTS: segment i is n consecutive tokens of the sequence on state slot `slot`, and the segments' tokens stand back to
@@ -717,8 +777,8 @@ int rwkv_sample_rows(rwkv_ctx *ctx, const rwkv_pick_query *q, uint64_t n, uint64
  * rwkv_sample_rows picks from that row with (seed, step0 + a_i) and RWKV_NUCLEUS_BAN0 after A.
  * Status: as rwkv_spec_verify_segments, and RWKV_E_ARG for a NULL picks, seeds or step0, RWKV_PICK_TYPICAL, whatever rwkv_sample_nucleus rejects in
  * a pick's parameters, and a pick with a penalty.
- * Out of scope: penalties (the counts behind row j would depend on how much of the draft stands), typical sampling, a draft model that samples (it
- * needs the draft's probabilities), pipeline-stage contexts.  Draft trees are rwkv_spec_sample_trees below. */
+ * Out of scope: penalties (the counts behind row j would depend on how much of the draft stands), typical sampling, pipeline-stage contexts.
+ * A draft model that samples is rwkv_spec_verify_ratio / rwkv_decode_speculative_sampled (one stream).  Draft trees are rwkv_spec_sample_trees below. */
 int rwkv_spec_sample_segments(rwkv_ctx *ctx, const uint64_t *tokens /* [T] */, const rwkv_spec_segment *segs, uint64_t n_segs,
                               const rwkv_pick *picks /* [n_segs] */, const uint64_t *seeds /* [n_segs] */, const uint64_t *step0 /* [n_segs] */,
                               uint32_t flags /* must be 0 */, uint32_t *n_accepted /* [n_segs] */, uint64_t *next_token /* [n_segs] */,

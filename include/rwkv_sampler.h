@@ -219,6 +219,43 @@ inline int mirostat_u(const float *_logits, const float *counts, float _temp, fl
     return g;
 }
 
+// ---- speculative sampling with a draft model that samples: the host twin of the ratio pick (csrc/ratio.hip.h; the rule is written out at
+// include/rwkv_mi355x.h rwkv_spec_ratio_rows).  _logits: the target's row, q_logits: the row the draft id x was drawn from (nullptr and x < 0: a
+// bonus row, a draw from p); id 0 banned on both sides; f64, log space.  Returns the pick; *accepted (may be nullptr) says whether it is x.
+inline std::vector<double> ratio_logp(const float *row, float _temp)
+{
+    const double it = _temp == 1.0f ? 1.0 : 1.0 / (double)_temp;
+    std::vector<double> s(50277);
+    for (size_t i = 0; i < s.size(); i++) s[i] = (double)row[i] * it;
+    const double mx = *std::max_element(s.begin() + 1, s.end());
+    double z = 0;
+    for (size_t i = 1; i < s.size(); i++) z += std::exp(s[i] - mx);
+    const double logZ = std::log(z);
+    for (double &v : s) v = (v - mx) - logZ;
+    return s;
+}
+inline int ratio_u(const float *_logits, const float *q_logits, long long x, float temp_target, float temp_draft, double u_a, double u_r, bool *accepted = nullptr)
+{
+    const bool bonus = x < 0 || !q_logits;
+    const std::vector<double> lp = ratio_logp(_logits, temp_target), lq = bonus ? std::vector<double>() : ratio_logp(q_logits, temp_draft);
+    const bool acc = !bonus && x >= 1 && std::log(u_a) < lp[(size_t)x] - lq[(size_t)x];
+    if (accepted) *accepted = acc;
+    if (acc) return (int)x;
+    std::vector<double> r(lp.size(), 0.0);
+    double R = 0;
+    for (size_t i = 1; i < r.size(); i++)
+        if (bonus || (long long)i != x) R += r[i] = std::max(std::exp(lp[i]) - (bonus ? 0.0 : std::exp(lq[i])), 0.0);
+    int best = -1;
+    double c = 0;
+    for (size_t i = 1; i < r.size(); i++) {
+        if (R > 0 ? (c += r[i]) > u_r * R && r[i] > 0 : ((bonus || (long long)i != x) && (best < 0 || _logits[i] > _logits[best]))) {
+            best = (int)i;
+            if (R > 0) break;
+        }
+    }
+    return best;      // (R > 0 and no crossing: a rounding at the upper edge cannot occur here, the sum is the one that made R)
+}
+
 // ---- stop sequences and budgets: the host twin of the scan the device decode loops make behind every pick (csrc/stop.hip.h; the semantics
 // are those of include/rwkv_mi355x.h rwkv_decode_batch_until) for ONE stream.  ids: the picks g_0 .. g_{n-1} of an n-step call fed `first`;
 // stops: the stop sequences (each 1 .. 8 ids); max_new: the budget (0: none; n is none too).  history: the stream's newest ids, oldest first,

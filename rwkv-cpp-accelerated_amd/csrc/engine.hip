@@ -22,6 +22,7 @@
 #include "lookup.hip.h"
 #include "lookuptree.hip.h"
 #include "dry.hip.h"
+#include "ratio.hip.h"
 #include "../../include/rwkv_mi355x.h"
 #include "../../include/rwkv_sampler.h"
 
@@ -265,6 +266,9 @@ enum GrownBuf {
     DRY_HIST,                         // DRY penalties (dry.hip.h): u32 [max_ctx][DRY_MAX_WINDOW] the slots' id rings | u64 [max_ctx] the ids each slot was given; allocated ONCE,
                                       // emptied, at the first call that needs it
     DRY_DBG,                          // rwkv_debug_dry_scan, u32: count | id [DRY_MAX_WINDOW] | L [DRY_MAX_WINDOW]
+    RATIO_IO,                         // rwkv_spec_ratio_rows / rwkv_spec_verify_ratio (ratio.hip.h), RatioIo: the call's row table, behind it the picks and the accepted flags;
+                                      // allocated ONCE at the first call
+    RATIO_STASH,                      // rwkv_decode_speculative_sampled, on the DRAFT context: f32 [k][V], the logits row each draft id was drawn from
     N_GROWN
 };
 
@@ -318,6 +322,7 @@ struct rwkv_ctx {
     SegRow *h_seg_plan = nullptr;   // pinned [maxT]: what rwkv_forward_segments uploads into SEG_PLAN (allocated with it)
     struct SpecSegIo *h_specseg = nullptr;   // pinned twin of SPECSEG_IO: what a many-stream verify uploads into it and downloads from it (allocated with it)
     struct PickIo *h_pickq = nullptr;        // pinned twin of PICKQ_IO (allocated with it)
+    struct RatioIo *h_ratio = nullptr;       // pinned twin of RATIO_IO (allocated with it)
     unsigned long long *gen = nullptr;
     unsigned long long *pick = nullptr;      // device: id drawn by the sampler
     double *ts_part = nullptr;               // sampler scratch (sampler.hip.h)
@@ -3166,6 +3171,12 @@ int rwkv_score(rwkv_ctx *c, const uint64_t *tokens, const uint64_t *targets, uin
     }(), logprob, entropy, argmax);
 }
 
+// the device image of one ratio-pick call (RATIO_IO, ratio.hip.h) and its pinned twin: n records go up, n ids and n flags come down
+struct RatioIo {
+    RatioQ q[RT_MAX_ROWS];
+    unsigned long long out[RT_MAX_ROWS];
+    unsigned char acc[RT_MAX_ROWS];
+};
 namespace {
 // ---- speculative greedy decoding (spec.hip.h): rwkv_spec_verify, rwkv_decode_speculative ----
 static_assert(SPEC_MAX_DRAFT == RWKV_SPEC_MAX_DRAFT, "spec.hip.h holds the header's limit");
@@ -3179,16 +3190,63 @@ int spec_buffers(rwkv_ctx *c, uint64_t n)
     return grow_pick_buffers(c, RWKV_PICK_GREEDY, n);
 }
 
+// ---- the ratio pick (ratio.hip.h): rwkv_spec_ratio_rows, and the pick of rwkv_spec_verify_ratio and rwkv_decode_speculative_sampled ----
+static_assert(RT_MAX_ROWS == (unsigned)SEQ_T && sizeof(rwkv_ratio_params) == 16, "the rows of one half; rwkv_ratio_params is 16 bytes in the C ABI");
+// the ratio pick of a verify: the draft model's rows, the temperatures, and where the uniforms come from (row j is step step0 + j)
+struct RatioCall { const float *q_logits; const rwkv_ratio_params *p; uint64_t seed, step0; };
+int launch_ratio(rwkv_ctx *c, const RatioArgs &a, unsigned rows);      // k_ratio_pick, at the end of this file (see Dryer)
+int ratio_buffers(rwkv_ctx *c)
+{
+    if (!c->h_ratio) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c->h_ratio), sizeof(RatioIo), hipHostMallocDefault));
+    return grow_buffer(c, RATIO_IO, sizeof(RatioIo));
+}
+int check_ratio_params(const rwkv_ratio_params *p)
+{
+    if (!(p->temp_target > 0.f) || !(p->temp_draft > 0.f)) return fail(RWKV_E_ARG, "need temp_target > 0 and temp_draft > 0");
+    if (p->flags || p->reserved) return fail(RWKV_E_ARG, "unknown flag bits (0x%x) or reserved != 0", p->flags);
+    return 0;
+}
+// uniform(splitmix64(x)): the generator of every device loop (sampler.hip.h ts_uniform), on the host
+double splitmix_uniform(uint64_t x)
+{
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return (double)(x >> 11) * (1.0 / 9007199254740992.0);
+}
+// the table (filled in the pinned twin) up, one launch over its n rows; the ids into `out`, the flags into the image's acc
+int enqueue_ratio(rwkv_ctx *c, unsigned n, const float *q_logits, const rwkv_ratio_params &p, unsigned long long *out)
+{
+    RatioIo *d = c->buf<RatioIo>(RATIO_IO);
+    // (the pinned block is free: every call that used it has returned behind its wait)
+    HIPCHK(hipMemcpyAsync(d->q, c->h_ratio->q, sizeof(RatioQ) * n, hipMemcpyHostToDevice, c->stream));
+    const RatioArgs a{d->q, c->logits, q_logits, p.temp_target == 1.0f ? 1.0 : 1.0 / (double)p.temp_target, p.temp_draft == 1.0f ? 1.0 : 1.0 / (double)p.temp_draft, out, d->acc};
+    return launch_ratio(c, a, n);
+}
+// the pick of a verify's n_draft + 1 rows: row j against row j of the draft's logits with the uniforms of step step0 + j, the last row the bonus row
+int enqueue_ratio_verify(rwkv_ctx *c, const RatioCall &rt, const uint64_t *draft, uint64_t n_draft, unsigned long long *picks)
+{
+    for (uint64_t j = 0; j <= n_draft; j++) {
+        const uint64_t s = rt.seed + 2 * (rt.step0 + j);
+        c->h_ratio->q[j] = RatioQ{(unsigned)j, (unsigned)j, j < n_draft ? (unsigned)draft[j] : RT_NONE, (unsigned)j, splitmix_uniform(s), splitmix_uniform(s + 1)};
+    }
+    return enqueue_ratio(c, (unsigned)n_draft + 1u, rt.q_logits, *rt.p, picks);
+}
+
 // Everything of one verify but the wait: ids up, the checkpointing pass over rows [token, draft ..] on slot 0, the pick of every row, what stands,
 // the commit of that row, and the record's download into rec[2].  No host synchronisation in between: k_spec_commit reads a where k_spec_accept
 // left it.  The pass is LAUNCHED DIRECTLY, not replayed as a captured graph under a key of its own.  Measured at 7B both ways
 // (profiles/spec/graph_vs_direct.txt), the replay was never the faster one: 0.01 - 0.02 ms slower up to 16 rows, which is what the runs differ by
 // among themselves, and 0.06 ms slower at 32 rows, which is not.  With nothing to gain the simpler form is kept: one pass per call, with the
 // call's wait behind it, leaves the host nothing to fall behind with.
-int enqueue_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft, unsigned long long *rec)
+// `rt`: the rows are picked by the ratio rule against the draft model's logits (ratio.hip.h) instead of greedily.  That pick returns the draft
+// id exactly where it accepts, so k_spec_accept and k_spec_commit run behind it as they do behind the argmax.
+int enqueue_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft, unsigned long long *rec, const RatioCall *rt = nullptr)
 {
     const int n = (int)n_draft + 1;
     if (const int rc = spec_buffers(c, (uint64_t)n)) return rc;
+    if (const int rc = rt ? ratio_buffers(c) : 0) return rc;
     uint64_t rows[SEQ_T];
     rows[0] = token;
     for (uint64_t i = 0; i < n_draft; i++) rows[i + 1] = draft[i];
@@ -3197,7 +3255,7 @@ int enqueue_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t 
     unsigned long long *drec = c->buf<unsigned long long>(SPEC_REC), *picks = drec + 2;
     const SeqPass pass{c->l0, c->l1, c->stream, &c->sp_scratch[0], 0, n, 0, token_slot(c, 0), RowLayout::checkpoints(ck)};
     if (const int rc = enqueue_chunk(c, pass)) return rc;
-    if (const int rc = enqueue_argmax_rows(c, c->logits, (unsigned)n, picks)) return rc;
+    if (const int rc = rt ? enqueue_ratio_verify(c, *rt, draft, n_draft, picks) : enqueue_argmax_rows(c, c->logits, (unsigned)n, picks)) return rc;
     k_spec_accept<64><<<dim3(1), dim3(64), 0, c->stream>>>(SpecAcceptArgs{token_slot(c, 0), picks, drec, (unsigned)n_draft});
     const SpecCommitArgs ca{drec, ck, c->state[0], c->state[1], c->state[2], c->state[4], (unsigned)c->L, (unsigned)c->D, (unsigned)n};
     k_spec_commit<SPEC_COMMIT_NT><<<dim3((unsigned)((c->L * c->D + SPEC_COMMIT_NT - 1) / SPEC_COMMIT_NT)), dim3(SPEC_COMMIT_NT), 0, c->stream>>>(ca);
@@ -3214,6 +3272,94 @@ int check_verify(const rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint6
     if (const int rc = check_ids(&token, 1, "token")) return rc;
     return check_ids(draft, n_draft, "draft");
 }
+// what the ratio calls check beyond a verify's own rules: the parameters, and the draft's rows where a draft id stands
+int check_verify_ratio(uint64_t n_draft, const float *q_logits, const rwkv_ratio_params *p)
+{
+    if (n_draft && !q_logits) return fail(RWKV_E_ARG, "q_logits is NULL although there are draft ids");
+    return check_ratio_params(p);
+}
+
+// a draft model that SAMPLES (rwkv_decode_speculative_sampled): the temperatures and the two generators
+struct SampledDraft { const rwkv_ratio_params *p; uint64_t seed, draft_seed; };
+
+// The loop of rwkv_decode_speculative (sd == nullptr: the draft decodes greedily, the target picks greedily) and of rwkv_decode_speculative_sampled
+// (the draft draws, the target picks by the ratio rule); every argument has been checked.
+// One round: the draft model's kd + 1 steps on its slot 0 with a copy of slot 0 into slot i + 1 behind step i (the last step only consumes
+// draft[kd - 1]: slot kd + 1 is what the draft holds when all of it stands), the drafts' download; the verify with its 16-byte download; the
+// draft's slot 0 back from slot a + 1.  Two waits, and the restore runs under the next round's first step.
+// Sampled: behind the forward of step i < kd the draft's logits row 0 goes to row i of its stash, device to device, and the nucleus sampler
+// (top_p 1, no top_k, no penalty, logit 0 banned) draws draft[i] from row 0 with u = uniform(splitmix64(draft_seed + d)), d counting the draws
+// of the call: the sampler reads the step of the round from the control block and the round's first d rides in its seed.  The last step draws
+// nothing.  The verify reads the stash on the target's stream behind the wait for the drafts; the next round writes it behind the verify's wait.
+int spec_loop(rwkv_ctx *c, rwkv_ctx *dc, uint64_t first_token, uint64_t n_tokens, uint32_t k, uint64_t *out_tokens, rwkv_spec_stats *stats, const SampledDraft *sd)
+{
+    const size_t LD = (size_t)dc->L * dc->D;
+    // the draft's slot `dst` <- its slot `src`, on its stream
+    auto draft_copy = [&](uint64_t dst, uint64_t src) -> int {
+        for (int s = 0; s < 5; s++)
+            HIPCHK(hipMemcpyAsync(dc->state[s] + dst * LD, dc->state[s] + src * LD, LD * sizeof(double), hipMemcpyDeviceToDevice, dc->stream));
+        return 0;
+    };
+    Sampler smp{};
+    float *stash = nullptr;
+    if (sd) {
+        if (const int rc = grow_buffer(dc, RATIO_STASH, sizeof(float) * k * RWKV_VOCAB)) return rc;
+        stash = dc->buf<float>(RATIO_STASH);
+        rwkv_nucleus_params np{};
+        np.temp = sd->p->temp_draft; np.top_p = 1.f; np.decay = 1.f; np.flags = RWKV_NUCLEUS_BAN0;
+        smp = make_sampler(dc, pick_nucleus(np), true);
+    }
+    // one step of the draft: the forward (with the greedy pick in its graph, or without), then -- sampled, and not the last step -- stash and draw
+    auto draft_step = [&](uint64_t i, bool last) -> int {
+        if (const int rc = run_token(dc, !sd)) return rc;
+        if (!sd || last) return 0;
+        HIPCHK(hipMemcpyAsync(stash + i * RWKV_VOCAB, dc->logits, RWKV_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, dc->stream));
+        return enqueue_pick(dc, smp, 1);
+    };
+    rwkv_spec_stats sts{0, 0, 0};
+    uint64_t done = 0, token = first_token, last_row = 0;
+    unsigned long long draft[SEQ_T], rec[2];
+    int rc = 0;
+    while (!rc && done < n_tokens) {
+        const uint64_t kd = std::min<uint64_t>(k, n_tokens - done - 1);
+        rc = set_ctl(dc, token, 0, 0);
+        if (sd) smp.n.seed = sd->draft_seed + sts.drafted;
+        for (uint64_t i = 0; !rc && i <= kd; i++) {
+            rc = draft_step(i, i == kd);
+            if (!rc) rc = draft_copy(i + 1, 0);
+        }
+        if (!rc && kd) rc = [&]() -> int { HIPCHK(hipMemcpyAsync(draft, dc->gen, kd * sizeof(unsigned long long), hipMemcpyDeviceToHost, dc->stream)); return 0; }();
+        if (kd || rc) rc = finish(dc, rc);
+        if (rc) break;
+        const RatioCall rt{stash, sd ? sd->p : nullptr, sd ? sd->seed : 0, done};
+        rc = finish(c, enqueue_verify(c, token, reinterpret_cast<const uint64_t *>(draft), kd, rec, sd ? &rt : nullptr));
+        if (rc) break;
+        const uint64_t a = rec[0];
+        rc = draft_copy(0, a + 1);
+        for (uint64_t i = 0; i < a; i++) out_tokens[done + i] = draft[i];
+        out_tokens[done + a] = rec[1];
+        done += a + 1; token = rec[1]; last_row = a;
+        sts.rounds++; sts.drafted += kd; sts.accepted += a;
+    }
+    // the row the last id was picked from -> row 0, where a one-stream call leaves it
+    if (!rc && last_row) rc = [&]() -> int { HIPCHK(hipMemcpyAsync(c->logits, c->logits + last_row * RWKV_VOCAB, RWKV_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, c->stream)); return 0; }();
+    rc = finish(dc, rc);
+    rc = finish(c, rc);
+    if (!rc && stats) *stats = sts;
+    return rc;
+}
+// the checks of the two loops behind the target's guard, all of them before anything is launched
+int check_spec_loop(rwkv_ctx *c, rwkv_ctx *dc, uint64_t first_token, uint64_t n_tokens, uint32_t k)
+{
+    if (dc == c) return fail(RWKV_E_ARG, "the draft context must be another context than the target");
+    if (const int rc = guard(dc, NEED_WHOLE | LAUNCHES)) return rc;
+    if (dc->device != c->device) return fail(RWKV_E_ARG, "the draft context is on device %d, the target on device %d", dc->device, c->device);
+    if (k == 0 || k > RWKV_SPEC_MAX_DRAFT) return fail(RWKV_E_ARG, "k must be in 1..%u", RWKV_SPEC_MAX_DRAFT);
+    if (dc->maxT < (uint64_t)k + 2) return fail(RWKV_E_ARG, "the draft context needs max context >= k + 2 = %u (a state slot per draft step)", k + 2);
+    if ((uint64_t)k + 1 > c->maxT) return fail(RWKV_E_ARG, "the target context needs max context >= k + 1 = %u", k + 1);
+    if (const int rc = check_steps(n_tokens, "n_tokens")) return rc;
+    return check_ids(&first_token, 1, "token");
+}
 } // namespace
 
 int rwkv_spec_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft, uint64_t *n_accepted, uint64_t *next_token)
@@ -3229,53 +3375,59 @@ int rwkv_spec_verify(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_
 int rwkv_decode_speculative(rwkv_ctx *c, rwkv_ctx *dc, uint64_t first_token, uint64_t n_tokens, uint32_t k, uint64_t *out_tokens, rwkv_spec_stats *stats)
 {
     if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, dc && out_tokens)) return rc;
-    if (dc == c) return fail(RWKV_E_ARG, "the draft context must be another context than the target");
-    if (const int rc = guard(dc, NEED_WHOLE | LAUNCHES)) return rc;
-    if (dc->device != c->device) return fail(RWKV_E_ARG, "the draft context is on device %d, the target on device %d", dc->device, c->device);
-    if (k == 0 || k > RWKV_SPEC_MAX_DRAFT) return fail(RWKV_E_ARG, "k must be in 1..%u", RWKV_SPEC_MAX_DRAFT);
-    if (dc->maxT < (uint64_t)k + 2) return fail(RWKV_E_ARG, "the draft context needs max context >= k + 2 = %u (a state slot per draft step)", k + 2);
-    if ((uint64_t)k + 1 > c->maxT) return fail(RWKV_E_ARG, "the target context needs max context >= k + 1 = %u", k + 1);
-    if (const int rc = check_steps(n_tokens, "n_tokens")) return rc;
-    if (const int rc = check_ids(&first_token, 1, "token")) return rc;
-    const size_t LD = (size_t)dc->L * dc->D;
-    // the draft's slot `dst` <- its slot `src`, on its stream
-    auto draft_copy = [&](uint64_t dst, uint64_t src) -> int {
-        for (int s = 0; s < 5; s++)
-            HIPCHK(hipMemcpyAsync(dc->state[s] + dst * LD, dc->state[s] + src * LD, LD * sizeof(double), hipMemcpyDeviceToDevice, dc->stream));
-        return 0;
-    };
-    rwkv_spec_stats sts{0, 0, 0};
-    uint64_t done = 0, token = first_token, last_row = 0;
-    unsigned long long draft[SEQ_T], rec[2];
-    // One round: the draft model's kd + 1 greedy steps on its slot 0 with a copy of slot 0 into slot i + 1 behind step i (the last step only
-    // consumes draft[kd - 1]: slot kd + 1 is what the draft holds when all of it stands), the drafts' download; the verify with its 16-byte
-    // download; the draft's slot 0 back from slot a + 1.  Two waits, and the restore runs under the next round's first step.
-    int rc = 0;
-    while (!rc && done < n_tokens) {
-        const uint64_t kd = std::min<uint64_t>(k, n_tokens - done - 1);
-        rc = set_ctl(dc, token, 0, 0);
-        for (uint64_t i = 0; !rc && i <= kd; i++) {
-            rc = run_token(dc, true);
-            if (!rc) rc = draft_copy(i + 1, 0);
-        }
-        if (!rc && kd) rc = [&]() -> int { HIPCHK(hipMemcpyAsync(draft, dc->gen, kd * sizeof(unsigned long long), hipMemcpyDeviceToHost, dc->stream)); return 0; }();
-        if (kd || rc) rc = finish(dc, rc);
-        if (rc) break;
-        rc = finish(c, enqueue_verify(c, token, reinterpret_cast<const uint64_t *>(draft), kd, rec));
-        if (rc) break;
-        const uint64_t a = rec[0];
-        rc = draft_copy(0, a + 1);
-        for (uint64_t i = 0; i < a; i++) out_tokens[done + i] = draft[i];
-        out_tokens[done + a] = rec[1];
-        done += a + 1; token = rec[1]; last_row = a;
-        sts.rounds++; sts.drafted += kd; sts.accepted += a;
+    if (const int rc = check_spec_loop(c, dc, first_token, n_tokens, k)) return rc;
+    return spec_loop(c, dc, first_token, n_tokens, k, out_tokens, stats, nullptr);
+}
+
+// ---- speculative SAMPLING with a draft model that samples (ratio.hip.h): rwkv_spec_ratio_rows, rwkv_spec_verify_ratio, rwkv_decode_speculative_sampled ----
+int rwkv_spec_ratio_rows(rwkv_ctx *c, const uint64_t *rows, const float *q_logits, const uint64_t *draft, uint64_t n, const rwkv_ratio_params *p,
+                         const double *u_accept, const double *u_draw, uint64_t *picks, uint8_t *accepted)
+{
+    if (const int rc = guard(c, NEED_HEAD | LAUNCHES, rows && draft && p && u_accept && u_draw && picks)) return rc;
+    if (n == 0 || n > RT_MAX_ROWS) return fail(RWKV_E_ARG, "n must be in 1..%u", RT_MAX_ROWS);
+    if (const int rc = check_ratio_params(p)) return rc;
+    for (uint64_t i = 0; i < n; i++) {
+        if (rows[i] >= c->maxT) return fail(RWKV_E_ARG, "logits row %llu out of range (max context %llu)", (unsigned long long)rows[i], (unsigned long long)c->maxT);
+        if (draft[i] != UINT64_MAX && draft[i] >= RWKV_VOCAB) return fail(RWKV_E_ARG, "draft id %llu out of range", (unsigned long long)draft[i]);
+        if (draft[i] != UINT64_MAX && !q_logits) return fail(RWKV_E_ARG, "q_logits is NULL although there are draft ids");
+        if (!(u_accept[i] >= 0.0 && u_accept[i] < 1.0) || !(u_draw[i] >= 0.0 && u_draw[i] < 1.0)) return fail(RWKV_E_ARG, "row %llu: need 0 <= u < 1", (unsigned long long)i);
     }
-    // the row the last id was picked from -> row 0, where a one-stream call leaves it
-    if (!rc && last_row) rc = [&]() -> int { HIPCHK(hipMemcpyAsync(c->logits, c->logits + last_row * RWKV_VOCAB, RWKV_VOCAB * sizeof(float), hipMemcpyDeviceToDevice, c->stream)); return 0; }();
-    rc = finish(dc, rc);
-    rc = finish(c, rc);
-    if (!rc && stats) *stats = sts;
+    const int rc = finish(c, [&]() -> int {
+        if (const int rc = ratio_buffers(c)) return rc;
+        RatioIo *h = c->h_ratio, *d = c->buf<RatioIo>(RATIO_IO);
+        for (uint64_t i = 0; i < n; i++)
+            h->q[i] = RatioQ{(unsigned)rows[i], (unsigned)i, draft[i] == UINT64_MAX ? RT_NONE : (unsigned)draft[i], (unsigned)i, u_accept[i], u_draw[i]};
+        if (const int rc = enqueue_ratio(c, (unsigned)n, q_logits, *p, d->out)) return rc;
+        HIPCHK(hipMemcpyAsync(h->out, d->out, sizeof(RatioIo) - offsetof(RatioIo, out), hipMemcpyDeviceToHost, c->stream));      // ids and flags: 288 bytes
+        return 0;
+    }());
+    if (rc) return rc;
+    std::copy(c->h_ratio->out, c->h_ratio->out + n, picks);
+    if (accepted) std::copy(c->h_ratio->acc, c->h_ratio->acc + n, accepted);
+    return 0;
+}
+
+int rwkv_spec_verify_ratio(rwkv_ctx *c, uint64_t token, const uint64_t *draft, uint64_t n_draft, const float *q_logits, const rwkv_ratio_params *p,
+                           uint64_t seed, uint64_t step0, uint64_t *n_accepted, uint64_t *next_token)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, p && n_accepted && next_token)) return rc;
+    if (const int rc = check_verify(c, token, draft, n_draft)) return rc;
+    if (const int rc = check_verify_ratio(n_draft, q_logits, p)) return rc;
+    unsigned long long rec[2] = {0ull, 0ull};
+    const RatioCall rt{q_logits, p, seed, step0};
+    const int rc = finish(c, enqueue_verify(c, token, draft, n_draft, rec, &rt));
+    if (!rc) { *n_accepted = rec[0]; *next_token = rec[1]; }
     return rc;
+}
+
+int rwkv_decode_speculative_sampled(rwkv_ctx *c, rwkv_ctx *dc, uint64_t first_token, uint64_t n_tokens, uint32_t k, const rwkv_ratio_params *p,
+                                    uint64_t seed, uint64_t draft_seed, uint64_t *out_tokens, rwkv_spec_stats *stats)
+{
+    if (const int rc = guard(c, NEED_WHOLE | NEED_SEQ | LAUNCHES, dc && p && out_tokens)) return rc;
+    if (const int rc = check_spec_loop(c, dc, first_token, n_tokens, k)) return rc;
+    if (const int rc = check_ratio_params(p)) return rc;
+    const SampledDraft sd{p, seed, draft_seed};
+    return spec_loop(c, dc, first_token, n_tokens, k, out_tokens, stats, &sd);
 }
 
 // ---- segmented forward (segments.hip.h): rwkv_segment_plan, rwkv_forward_segments ----
@@ -3924,6 +4076,7 @@ void rwkv_free(rwkv_ctx *c)
     if (c->h_seg_plan) (void)hipHostFree(c->h_seg_plan);
     if (c->h_specseg) (void)hipHostFree(c->h_specseg);
     if (c->h_pickq) (void)hipHostFree(c->h_pickq);
+    if (c->h_ratio) (void)hipHostFree(c->h_ratio);
     if (c->herr) (void)hipHostFree(c->herr);
     for (auto &e : c->xs_ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : c->hop_ev) if (e) (void)hipEventDestroy(e);
@@ -4781,6 +4934,13 @@ int Dryer::scan(rwkv_ctx *c, unsigned n) const
 int dry_debug_scan(rwkv_ctx *c, const DryArgs &a)
 {
     k_dry_scan<true><<<dim3(1), dim3(DRY_NT), 0, c->stream>>>(a);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// the launch of ratio.hip.h, named behind them for the same reason: one workgroup per row of the table
+int launch_ratio(rwkv_ctx *c, const RatioArgs &a, unsigned rows)
+{
+    k_ratio_pick<RT_NT><<<dim3(1, rows), dim3(RT_NT), 0, c->stream>>>(a);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -165,6 +165,17 @@ PYBIND11_MODULE(rwkv, m)
     }, "speculative greedy decoding: the model of handle `draft` (loaded with maxGPT >= k + 2, same prefix in slot 0) guesses k ids per round, this "
        "one verifies them in one pass: (ids [n], (rounds, drafted, accepted)); the ids do not depend on the draft model (engine extension)",
           py::arg("rwkvp"), py::arg("draft"), py::arg("first"), py::arg("n"), py::arg("k") = 4u);
+    m.def("decodeSpeculativeSampled", [](std::uintptr_t h, std::uintptr_t draft, int64_t first, int64_t n, unsigned k, float temp_target, float temp_draft,
+                                         uint64_t seed, uint64_t draft_seed) {
+        if (n < 1) throw std::runtime_error("n must be at least 1");
+        const RWKV::SpecResult r = M(h)->decodeSpeculativeSampled(*M(draft), (unsigned long long)first, (unsigned long long)n, k, temp_target, temp_draft, seed, draft_seed);
+        py::array_t<int64_t> ids((size_t)n);
+        std::copy(r.tokens.begin(), r.tokens.end(), ids.mutable_data());
+        return py::make_tuple(ids, py::make_tuple((int64_t)r.rounds, (int64_t)r.drafted, (int64_t)r.accepted));
+    }, "speculative sampling: the model of handle `draft` SAMPLES k ids per round at temp_draft, this one accepts them by the ratio rule at temp_target "
+       "and draws from the residual where it rejects: (ids [n], (rounds, drafted, accepted)), every id distributed as this model's own sampling (engine extension)",
+          py::arg("rwkvp"), py::arg("draft"), py::arg("first"), py::arg("n"), py::arg("k") = 4u, py::arg("temp_target") = 1.0f, py::arg("temp_draft") = 1.0f,
+          py::arg("seed") = 0ull, py::arg("draft_seed") = 0ull);
     m.def("specVerifySegments", [](std::uintptr_t h, const std::vector<std::tuple<unsigned, std::vector<int64_t>, unsigned>> &segments) {
         std::vector<RWKV::SpecSegment> segs;
         for (const auto &s : segments)

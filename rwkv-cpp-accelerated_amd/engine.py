@@ -51,7 +51,9 @@ ABI_SYMBOLS = [
     "rwkv_decode_lookup_streams", "rwkv_debug_lookup_draft",
     "rwkv_decode_lookup_trees", "rwkv_debug_lookup_tree",
     "rwkv_dry_history_set", "rwkv_dry_history_get", "rwkv_debug_dry_scan", "rwkv_decode_batch_dry",
+    "rwkv_spec_ratio_rows", "rwkv_spec_verify_ratio", "rwkv_decode_speculative_sampled",
 ]
+RATIO_MAX_ROWS, RATIO_BONUS = 32, (1 << 64) - 1   # the rows of one rwkv_spec_ratio_rows call; the draft id of a bonus row (UINT64_MAX)
 CONSTRAINT_MAX_STATES, CONSTRAINT_MAX_EDGES, CONSTRAINT_MAX_BIAS, STOP_CONSTRAINT = 4096, 1 << 24, 300, 32   # RWKV_CONSTRAINT_*, RWKV_STOP_CONSTRAINT
 BEAM_MAX, BEAM_MAX_STOP = 16, 16  # RWKV_MAX_BEAM, RWKV_BEAM_MAX_STOP
 SPEC_MAX_DRAFT = 31               # RWKV_SPEC_MAX_DRAFT
@@ -74,6 +76,15 @@ class NucleusParams(C.Structure):
 
 def nucleus_params(temp=1.0, top_p=0.9, top_k=0, presence=0.0, frequency=0.0, decay=1.0, flags=0) -> NucleusParams:
     return NucleusParams(float(temp), float(top_p), int(top_k), float(presence), float(frequency), float(decay), int(flags), 0)
+
+
+class RatioParams(C.Structure):
+    """rwkv_ratio_params of include/rwkv_mi355x.h (16 bytes)"""
+    _fields_ = [("temp_target", C.c_float), ("temp_draft", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def ratio_params(temp_target=1.0, temp_draft=1.0) -> RatioParams:
+    return RatioParams(float(temp_target), float(temp_draft), 0, 0)
 
 
 class Pick(C.Structure):
@@ -486,6 +497,13 @@ def lib():
     L.rwkv_decode_batch_constrained.restype = i32
     L.rwkv_spec_verify.argtypes = [vp, u64, C.POINTER(u64), u64, C.POINTER(u64), C.POINTER(u64)]; L.rwkv_spec_verify.restype = i32
     L.rwkv_decode_speculative.argtypes = [vp, vp, u64, u64, C.c_uint32, C.POINTER(u64), C.POINTER(SpecStats)]; L.rwkv_decode_speculative.restype = i32
+    dblp = C.POINTER(C.c_double)
+    L.rwkv_spec_ratio_rows.argtypes = [vp, C.POINTER(u64), vp, C.POINTER(u64), u64, C.POINTER(RatioParams), dblp, dblp, C.POINTER(u64), C.POINTER(C.c_uint8)]
+    L.rwkv_spec_ratio_rows.restype = i32
+    L.rwkv_spec_verify_ratio.argtypes = [vp, u64, C.POINTER(u64), u64, vp, C.POINTER(RatioParams), u64, u64, C.POINTER(u64), C.POINTER(u64)]
+    L.rwkv_spec_verify_ratio.restype = i32
+    L.rwkv_decode_speculative_sampled.argtypes = [vp, vp, u64, u64, C.c_uint32, C.POINTER(RatioParams), u64, u64, C.POINTER(u64), C.POINTER(SpecStats)]
+    L.rwkv_decode_speculative_sampled.restype = i32
     L.rwkv_forward_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(Segment), u64, C.c_uint32, C.POINTER(u64)]; L.rwkv_forward_segments.restype = i32
     L.rwkv_spec_verify_segments.argtypes = [vp, C.POINTER(u64), C.POINTER(SpecSegment), u64, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(u64), C.POINTER(u64)]
     L.rwkv_spec_verify_segments.restype = i32
@@ -1288,6 +1306,71 @@ class RWKV:
             if not m.resident:
                 m.push_state(1)
         _chk(lib().rwkv_decode_speculative(self._h, draft_model._h, int(first_token), n, int(k), out, C.byref(st)))
+        for m in (self, draft_model):
+            if not m.resident:
+                m.pull_state(1)
+        return np.frombuffer(out, dtype=np.uint64)[:n].astype(np.int64), dict(rounds=int(st.rounds), drafted=int(st.drafted), accepted=int(st.accepted))
+
+    # -- speculative sampling with a draft model that samples (include/rwkv_mi355x.h rwkv_spec_ratio_rows) -----------------------
+    @staticmethod
+    def _q_logits(q):
+        """the draft's logits rows as a device address: None, an address, or a loaded draft model (its logits buffer)"""
+        if q is None:
+            return None
+        return C.c_void_p(int(lib().rwkv_logits_device(q._h)) if isinstance(q, RWKV) else int(q))
+
+    def spec_ratio_rows(self, rows, q_logits, draft, u_accept, u_draw, temp_target: float = 1.0, temp_draft: float = 1.0):
+        """the ratio pick of speculative sampling ON THE DEVICE for len(rows) <= 32 rows: row i reads logits row rows[i] of this model and row i of
+        q_logits (device [n][50277] f32: an address, or the draft model whose logits buffer it is), accepts draft[i] iff
+        log(u_accept[i]) < log p - log q of it, and else draws from the normalised max(p - q, 0) in id order with u_draw[i]; draft id None (or
+        RATIO_BONUS) is a bonus row: a draw from p.  Returns (picks, accepted)."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        n = len(rows)
+        if not (len(draft) == len(u_accept) == len(u_draw) == n):
+            raise ValueError("need one draft id and two uniforms per row")
+        u64a = C.c_uint64 * max(1, n)
+        dba = C.c_double * max(1, n)
+        picks, acc = u64a(), (C.c_uint8 * max(1, n))()
+        p = ratio_params(temp_target, temp_draft)
+        _chk(lib().rwkv_spec_ratio_rows(self._h, u64a(*[int(r) for r in rows]), self._q_logits(q_logits),
+                                        u64a(*[RATIO_BONUS if x is None else int(x) for x in draft]), n, C.byref(p),
+                                        dba(*[float(u) for u in u_accept]), dba(*[float(u) for u in u_draw]), picks, acc))
+        return [int(t) for t in picks[:n]], [int(a) for a in acc[:n]]
+
+    def spec_verify_ratio(self, token: int, draft, q_logits, seed: int, step0: int = 0, temp_target: float = 1.0, temp_draft: float = 1.0):
+        """spec_verify with the ratio pick: row j is judged against row j of q_logits (the rows draft[j] was drawn from) with the uniforms of step
+        step0 + j; (n_accepted, next).  The next call's step0 is step0 + n_accepted + 1."""
+        if not self.ready:
+            raise RuntimeError("RWKV not loaded")
+        d = [int(t) for t in draft]
+        arr = (C.c_uint64 * max(1, len(d)))(*d)
+        a, nx = C.c_uint64(0), C.c_uint64(0)
+        p = ratio_params(temp_target, temp_draft)
+        if not self.resident:
+            self.push_state(1)
+        _chk(lib().rwkv_spec_verify_ratio(self._h, int(token), arr if d else None, len(d), self._q_logits(q_logits), C.byref(p),
+                                          int(seed) & RATIO_BONUS, int(step0), C.byref(a), C.byref(nx)))
+        if not self.resident:
+            self.pull_state(1)
+        return int(a.value), int(nx.value)
+
+    def decode_speculative_sampled(self, draft_model: "RWKV", first_token: int, n_tokens: int, k: int = 4, temp_target: float = 1.0,
+                                   temp_draft: float = 1.0, seed: int = 0, draft_seed: int = 0):
+        """decode_speculative with a draft model that SAMPLES at temp_draft and this model accepting by the ratio rule at temp_target: every id is
+        distributed as this model's own sampling at temp_target.  (ids, stats); to chain, pass seed + 2 * n_tokens and draft_seed +
+        stats["drafted"]."""
+        if not self.ready or not draft_model.ready:
+            raise RuntimeError("RWKV not loaded")
+        n = int(n_tokens)
+        out = (C.c_uint64 * max(1, n))()
+        st = SpecStats()
+        p = ratio_params(temp_target, temp_draft)
+        for m in (self, draft_model):
+            if not m.resident:
+                m.push_state(1)
+        _chk(lib().rwkv_decode_speculative_sampled(self._h, draft_model._h, int(first_token), n, int(k), C.byref(p), int(seed) & RATIO_BONUS,
+                                                   int(draft_seed) & RATIO_BONUS, out, C.byref(st)))
         for m in (self, draft_model):
             if not m.resident:
                 m.pull_state(1)
